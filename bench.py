@@ -38,6 +38,12 @@ class _Done(Exception):
     pass
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6       # --dump-outputs: all arrays together
+DUMP_SAMPLE_ROWS = 1 << 18            # --dump-outputs: spatial rows kept of the last iterate (fewer if the limit needs it)
+DUMP_SOLUTION_ROWS = 1 << 14          # --dump-outputs: spatial rows kept of the separated solution (x all parameter dofs)
+DUMP_SEED = 2024
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -88,7 +94,17 @@ def parse():
                     help="N > 1: deadline (s) of every host-side wait of the sharded solve and of torch.distributed's collectives")
     ap.add_argument("--watchdog-seconds", type=float, default=1500.0,
                     help="N > 1: the whole process exits non-zero with all Python stacks on stderr after this long (0: off)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write what the last one computed as DIR/<name>.npy (float64): space_iterate and "
+                         "mu_iterate (the functions of the two dimensions after that pass) and solution (the separated approximation "
+                         "after it - stored modes plus the rank-one term in progress - at sampled spatial rows x all mu dofs).  Shapes "
+                         "depend on --n / --n-mu only; spatial rows are a fixed, seeded sample (dump_sample_rows: %d for the iterate, "
+                         "%d of those for the solution), everything under %d MB" % (DUMP_SAMPLE_ROWS, DUMP_SOLUTION_ROWS,
+                                                                                            DUMP_LIMIT_BYTES // 10 ** 6))
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 _T0 = time.time()
@@ -167,7 +183,9 @@ def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or os.environ.get("PGD_BENCH_FORCE_LAUNCHER") == "1"):
         # before `import torch.distributed`, before any HIP call: this process only starts and relays
-        raise SystemExit(launch_ranks(args, sys.argv[1:]))
+        # (the ranks run in ROOT: a relative --dump-outputs is passed on as an absolute path - the last occurrence counts)
+        argv = sys.argv[1:] + (["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
+        raise SystemExit(launch_ranks(args, argv))
     # stdout carries exactly ONE line, the JSON result: RCCL prints its version banner to stdout when a
     # communicator is created, so everything else this process (and the libraries it loads) writes to
     # file descriptor 1 is sent to stderr, and the saved descriptor is used for the result line only
@@ -242,6 +260,7 @@ def main():
         space = fem.BoxMesh(P(0, 0, 0), P(1, 1, 1), n - 1, n - 1, n - 1)
     spec = problems.reaction_diffusion(space, args.n_mu, PGD_nmax=50, PGD_tol=1e-12)
     prob = PGDProblem(**spec)
+    last_pass = record_last_pass(prob) if args.dump_outputs else None
     settings = {"linear_solver": "cg", "preconditioner": args.preconditioner, "relative_tolerance": args.rtol}
     # one-time work outside the timed region: mesh upload + topology, the four atoms
     space.atom(fem.STIFF)
@@ -354,6 +373,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        _note("outputs of the timed passes to %s" % args.dump_outputs)
+        dump_outputs(args.dump_outputs, prob, last_pass, ("space", "mu"), dist if sharded else None, rank)
 
     n_sp = n ** 3
     from pgdrome_amd.sizes import nnz_p1_box
@@ -525,6 +547,92 @@ def main():
         if args.watchdog_seconds > 0:
             import faulthandler
             faulthandler.cancel_dump_traceback_later()
+
+
+def record_last_pass(prob):
+    """--dump-outputs: the dict this returns holds, per dimension, the function the most recent fixed-point pass computed (the
+    iterate FP_solve goes on with).  Observation only: the per-dimension solves are the same calls with the same arguments."""
+    last = {}
+    solve_dim = prob._solve_dim
+
+    def recording_solve_dim(dim, *a, **kw):
+        f = solve_dim(dim, *a, **kw)
+        last[dim] = f
+        return f
+    prob._solve_dim = recording_solve_dim
+    return last
+
+
+def dump_sample_rows(n, size, seed=DUMP_SEED):
+    """Rows (global dof order) that --dump-outputs keeps of a dimension with n dofs when it keeps `size` of them: the first `size`
+    entries of a seeded permutation, sorted - the same rows on every rank and in every run, and a smaller sample is a subset of a
+    larger one."""
+    import numpy as np
+    if size >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).permutation(n)[:size])
+
+
+def _dump_rows(prob, d, funcs, rows, dist):
+    """Values of `funcs` (functions of dimension d) at the global dofs `rows`: (len(funcs), len(rows)) float64.  A row-sharded
+    dimension is gathered over torch.distributed (collective: every rank calls, every rank gets the whole array)."""
+    import numpy as np
+    part = getattr(prob.V[d].mesh(), "part", None)
+    if part is None:
+        return np.array([np.asarray(f.vector()[:], dtype=np.float64)[rows] for f in funcs]).reshape(len(funcs), len(rows))
+    # the rows this rank owns, from its local vectors (local dof i is global dof nc * global_offset + i)
+    nc = int(getattr(prob.V[d], "_ncomp", 1))
+    g0 = nc * part.global_offset
+    mine = np.nonzero((rows >= g0 + nc * part.own0) & (rows < g0 + nc * part.own1))[0]
+    local = np.array([np.asarray(f.vector()[:], dtype=np.float64)[rows[mine] - g0] for f in funcs]).reshape(len(funcs), len(mine))
+    box = [None] * dist.get_world_size()
+    dist.all_gather_object(box, (mine, local))
+    assert sum(len(where) for where, _ in box) == len(rows)
+    vals = np.full((len(funcs), len(rows)), np.nan)
+    for where, v in box:
+        vals[:, where] = v
+    return vals
+
+
+def dump_outputs(path, prob, last_pass, names, dist=None, rank=0, limit=DUMP_LIMIT_BYTES, sample_rows=DUMP_SAMPLE_ROWS,
+                 solution_rows=DUMP_SOLUTION_ROWS):
+    """Write what the last timed pass computed as path/<name>.npy in float64, for a problem in two dimensions (names[0], names[1]):
+      <names[d]>_iterate   the function of dimension d after the last timed pass (record_last_pass);
+      solution             the separated approximation after that pass - sum_k X_k (x) M_k over the modes stored so far plus the
+                           rank-one term of the enrichment step in progress (the iterates above) - at sampled rows of dimension 0
+                           x all dofs of dimension 1: what solve_PGD would hand back had its fixed point stopped there.
+    Every shape depends on the problem's sizes alone - not on --steps / --warmup, nor on how many modes the window stored - and
+    no array is empty.  Dimension 0 longer than `sample_rows` is kept on dump_sample_rows(n, S) in <names[0]>_iterate and on
+    dump_sample_rows(n, S_u) (the first S_u of the same permutation) in `solution`, S_u <= solution_rows, both halved until
+    everything fits in `limit` bytes.  Row-sharded dimensions are gathered (collective); rank 0 writes.  Returns {name: shape}."""
+    import numpy as np
+    assert prob.num_pgd_var == 2 and len(names) == 2
+    n_modes = min(len(f) for f in prob.PGD_func) if len(prob.PGD_func) == 2 else 0
+    funcs = [list(prob.PGD_func[d][:n_modes]) + [last_pass[d]] for d in range(2)]
+    part = getattr(prob.V[0].mesh(), "part", None)
+    n0 = int(getattr(prob.V[0], "_ncomp", 1)) * part.n_global if part is not None else prob.V[0].dim()
+    n1 = prob.V[1].dim()
+    s, su = min(n0, sample_rows), min(n0, solution_rows)
+    while 8 * (s + n1 + su * n1) > limit and su > 1:
+        su //= 2
+    while 8 * (s + n1 + su * n1) > limit and s > 1:
+        s //= 2
+    X = _dump_rows(prob, 0, funcs[0], dump_sample_rows(n0, su), dist)
+    M = _dump_rows(prob, 1, funcs[1], np.arange(n1), dist)
+    u = np.zeros((su, n1))
+    for k in range(len(X)):                    # a fixed order of the sum: the same bits from run to run
+        u += np.outer(X[k], M[k])
+    out = {names[0] + "_iterate": _dump_rows(prob, 0, funcs[0][-1:], dump_sample_rows(n0, s), dist)[0],
+           names[1] + "_iterate": M[-1], "solution": u}
+    assert all(a.size for a in out.values()) and sum(a.nbytes for a in out.values()) <= limit
+    if rank == 0:
+        if not os.path.isdir(path):
+            os.makedirs(path)
+            with open(os.path.join(path, ".gitignore"), "w") as f:     # generated data: never part of a commit
+                f.write("*\n")
+        for name, a in out.items():
+            np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: a.shape for name, a in out.items()}
 
 
 def direct_probe(args, comm, space, dist, rank, world, local_rank):

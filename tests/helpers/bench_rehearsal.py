@@ -7,7 +7,8 @@ line) - on THIS script; as a rank it does what bench.main does around the solves
 driver of pgdrome_amd/dist.py, the spectral start with its all-reduced vote, the timing window between barriers, the maximum over
 the ranks, ONE line from rank 0 - over gloo, with the oracle backend doing the local arithmetic at a tiny size (which is why this
 lives under tests/: bench.py itself touches oracle/ only in its cpu_baseline leg).  Its line says "data": "cpu rehearsal": never a
-measurement."""
+measurement.  --dump-outputs DIR writes the outputs of the timed passes with bench.dump_outputs; PGD_REHEARSAL_DUMP_ROWS replaces
+bench.DUMP_SAMPLE_ROWS (and half of it bench.DUMP_SOLUTION_ROWS), so that the tiny sizes of a rehearsal are sampled too."""
 import json
 import os
 import sys
@@ -43,6 +44,7 @@ def rehearse(args, world, rank, result_fd):
         space = fem.BoxMesh(P(0, 0, 0), P(1, 1, 1), n - 1, n - 1, n - 1)
     spec = problems.reaction_diffusion(space, min(args.n_mu, 17), PGD_nmax=50, PGD_tol=1e-12)
     prob = PGDProblem(**spec)
+    last_pass = bench.record_last_pass(prob) if args.dump_outputs else None
     settings = {"linear_solver": "cg", "preconditioner": args.preconditioner, "relative_tolerance": args.rtol}
     spectral_info = None
     if args.spectral_start > 0 and (not sharded or not args.no_spectral_sharded) and args.preconditioner == "jacobi":
@@ -90,6 +92,10 @@ def rehearse(args, world, rank, result_fd):
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        rows = int(os.environ.get("PGD_REHEARSAL_DUMP_ROWS", bench.DUMP_SAMPLE_ROWS))
+        bench.dump_outputs(args.dump_outputs, prob, last_pass, ("space", "mu"), dist if sharded else None, rank,
+                           sample_rows=rows, solution_rows=max(rows // 2, 1))
     out = {"metric": "PGD fixed-point iters/sec + SpMV HBM GB/s, 256^3 P1 space x 1D param", "value": K / elapsed,
            "unit": "fixed-point iterations/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": 1e3 * elapsed / K,
            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "cpu rehearsal",

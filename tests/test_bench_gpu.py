@@ -52,6 +52,29 @@ def test_bench_line_contract():
     assert "Infinity Cache" in r.get("note", "") or "spmv" not in r
 
 
+def test_bench_dumps_the_outputs_of_its_timed_passes(tmp_path):
+    """--dump-outputs: the last timed pass's iterates and the separated solution after it, float64, under 64 MB, the 104^3 spatial
+    dimension on the seeded sample of its rows; two runs with the same arguments write the same arrays, and a window of ONE pass
+    (no stored mode yet) writes the same shapes, none of them empty."""
+    import numpy as np
+    dumps = []
+    for name, steps, warmup in (("a", "3", "1"), ("b", "3", "1"), ("one_pass", "1", "0")):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", "104", "--steps", steps, "--warmup", warmup, "--no-pmc",
+               "--no-cpu-baseline", "--no-csr-section", "--no-general-paths", "--dump-outputs", str(tmp_path / name)]
+        res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        assert json.loads(res.stdout)["steps"] == int(steps)
+        files = sorted(f for f in os.listdir(tmp_path / name) if f.endswith(".npy"))
+        assert files == ["mu_iterate.npy", "solution.npy", "space_iterate.npy"]
+        dumps.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b, one = dumps
+    assert a["space_iterate.npy"].shape == (1 << 18,) and a["mu_iterate.npy"].shape == (128,)
+    assert a["solution.npy"].shape == (1 << 14, 128) and sum(x.nbytes for x in a.values()) <= 64 * 10 ** 6
+    for f in a:
+        assert a[f].dtype == np.float64 and np.all(np.isfinite(a[f])) and np.abs(a[f]).max() > 0 and np.array_equal(a[f], b[f]), f
+        assert one[f].shape == a[f].shape and np.abs(one[f]).max() > 0, f
+
+
 def test_bench_line_of_the_sharded_driver_has_the_phase_timings():
     """bench.py --dist-driver (one rank through the in-library sharded loop over RCCL): the fields a multi-GPU line carries -
     per-rank max / min of the iteration's phases, the communicator's world size, the deadline."""

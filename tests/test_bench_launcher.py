@@ -40,6 +40,15 @@ def test_gpus_2_starts_two_ranks_before_touching_hip(tmp_path):
     assert "NCCL version" in err and "trailing noise" in err          # other stdout of the ranks is not lost, and not on stdout
 
 
+def test_relative_dump_directory_reaches_the_ranks_as_an_absolute_path(tmp_path):
+    """The ranks run in the repository root: `--dump-outputs out` must still mean `out` under the caller's directory."""
+    r, rec = _run(tmp_path, ["--gpus", "2", "--steps", "3", "--dump-outputs", "out"])
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    a = rec["argv"]
+    assert a[a.index(os.path.join(ROOT, "bench.py")) + 1:] == ["--gpus", "2", "--steps", "3", "--dump-outputs", "out",
+                                                               "--dump-outputs", str(tmp_path / "out")]
+
+
 def test_two_launches_use_different_ports(tmp_path):
     _, a = _run(tmp_path, ["--gpus", "4"])
     _, b = _run(tmp_path, ["--gpus", "4"])

@@ -128,6 +128,16 @@ int pgd_vec_dot(pgd_handle ctx, pgd_handle x, pgd_handle y, int64_t lo, int64_t 
  * weighted kinds, 0 otherwise.  Deterministic (owner-computes, no atomics).     */
 int pgd_atom_assemble(pgd_handle ctx, pgd_handle mesh, int kind, int da, int db,
                       pgd_handle wvec, pgd_handle *atom);
+/* Boundary mass  int_Gamma phi_i phi_j ds  over nf facets (the Robin term c*u*v*ds of a form), on the
+ * mesh's own pattern: an atom like any other.  facets: nf records of nvpf node ids of the layout, the
+ * facet's vertices first, then for P2 the nodes of its edges in the UFC local order - interval layouts
+ * nvpf = 1 (a point: 1 on the diagonal), triangle layouts 2 (P1) / 3 (P2) (an edge), tetrahedron layouts
+ * 3 (P1) / 6 (P2) (a triangle).  Measures come from the vertex coordinates of the mesh.  PGD_ERR_INVALID
+ * for a node out of range, nvpf not matching the layout, a blocked layout (pgd_atom_embed builds those
+ * from the scalar atom) or a facet whose nodes the pattern does not couple (no atom is left behind).
+ * Deterministic (owner-computes, no atomics).                                                    */
+int pgd_atom_assemble_facets(pgd_handle ctx, pgd_handle mesh, const int32_t *facets, int64_t nf, int nvpf,
+                             pgd_handle *atom);
 /* dst[(ncomp*i + cv), (ncomp*j + cu)] += coef * src[i, j]: the scalar atom `src` (e.g. DUDV(a,b)) placed
  * in the (test component cv, trial component cu) block of an atom of the blocked layout.  dst = 0
  * creates a zero atom first; *out is the destination.  One term of inner(C*eps(u), eps(v))*dx

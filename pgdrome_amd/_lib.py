@@ -59,6 +59,7 @@ SIGNATURES = {
     "pgd_vec_lincomb": (C.c_int, [H, H, PH, PD, C.c_int]),
     "pgd_vec_dot": (C.c_int, [H, H, H, I64, I64, PD]),
     "pgd_atom_assemble": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PH]),
+    "pgd_atom_assemble_facets": (C.c_int, [H, H, PI32, I64, C.c_int, PH]),
     "pgd_atom_upload": (C.c_int, [H, H, PD, PH]),
     "pgd_atom_download": (C.c_int, [H, H, PD]),
     "pgd_atom_free": (C.c_int, [H, H]),
@@ -373,6 +374,16 @@ class Context:
     def atom_assemble(self, mesh, kind, da=0, db=0, w=0):
         a = H(0)
         self._ck(self.lib.pgd_atom_assemble(self.h, mesh, int(kind), int(da), int(db), int(w), C.byref(a)))
+        return a.value
+
+    def atom_assemble_facets(self, mesh, facets):
+        """int_Gamma phi_i phi_j ds over the facets: an (nf, nodes per facet) array of node ids of the layout."""
+        facets = np.ascontiguousarray(facets, dtype=np.int32)
+        if facets.ndim != 2:
+            raise ValueError("facets: an (nf, nodes per facet) array")
+        a = H(0)
+        self._ck(self.lib.pgd_atom_assemble_facets(self.h, mesh, iptr(facets) if facets.size else None, facets.shape[0],
+                                                   facets.shape[1], C.byref(a)))
         return a.value
 
     def atom_upload(self, mesh, vals):

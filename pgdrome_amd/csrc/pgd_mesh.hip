@@ -700,6 +700,85 @@ __global__ __launch_bounds__(64) void k_assemble_p2_simplex(AsmArgs A, const int
     }
 }
 
+// ------------------------------------------------------------------ facet (boundary) mass
+// int_Gamma phi_i phi_j ds over a list of facets, on the mesh's own pattern (Robin terms).  A facet record is a tuple of NPF
+// nodes: its G vertices first, then for P2 the nodes of its edges in the UFC local order ((1,2), (0,2), (0,1) on a triangle: edge
+// node e lies opposite vertex e).  G = 1: the facet is one point; 2: an edge (P1 2 nodes, P2 3); 3: a triangle (P1 3, P2 6).
+// Owner-computes like k_assemble_p1: one lane per row visits the row's facets in ascending facet id (node -> facet lists built
+// by the k_v2c_* kernels, sorted) and adds each local entry at the column found by a binary search in the row's sorted columns -
+// no atomics, bit-identical from run to run.  A facet coupling that is not in the pattern is NOT written: it raises `flag`.
+template <int G, int NPF>
+__device__ __forceinline__ double facet_entry(int i, int j, double meas) {
+    if constexpr (G == 1) {
+        return 1.0;
+    } else if constexpr (NPF == G) {                                   // P1 edge / triangle: meas / ((G)(G+1)) * (1 + [i == j])
+        return meas * (1.0 / (G * (G + 1))) * (i == j ? 2.0 : 1.0);
+    } else if constexpr (G == 2) {                                     // P2 edge (v0, v1, midpoint): meas / 30 * [[4 -1 2] [-1 4 2] [2 2 16]]
+        const double t = (i == 2 && j == 2) ? 16.0 : (i == 2 || j == 2) ? 2.0 : (i == j ? 4.0 : -1.0);
+        return meas * (1.0 / 30.0) * t;
+    } else {                                                           // P2 triangle: meas / 180 * (vertex-vertex 6 / -1, vertex -
+        const bool vi = i < 3, vj = j < 3;                             // opposite edge node -4, - adjacent 0, edge-edge 32 / 16)
+        double t;
+        if (vi && vj) t = i == j ? 6.0 : -1.0;
+        else if (vi || vj) t = (vi ? j - 3 == i : i - 3 == j) ? -4.0 : 0.0;
+        else t = i == j ? 32.0 : 16.0;
+        return meas * (1.0 / 180.0) * t;
+    }
+}
+
+// measure of the facet from the coordinates of its vertices; on a uniform lattice (AsmArgs::lattice) the edge components are
+// whole steps, as in p1_geometry: congruent facets get identical measures and a uniform grid's boundary rows repeat bit for bit
+template <int G>
+__device__ __forceinline__ double facet_measure(const AsmArgs &A, const int *u) {
+    if constexpr (G == 1) {
+        return 1.0;
+    } else if constexpr (G == 2) {
+        const double ax = A.cx[u[1]] - A.cx[u[0]], ay = A.cy[u[1]] - A.cy[u[0]];
+        return sqrt(ax * ax + ay * ay);
+    } else {
+        const double x0 = A.cx[u[0]], y0 = A.cy[u[0]], z0 = A.cz[u[0]];
+        double ax = A.cx[u[1]] - x0, ay = A.cy[u[1]] - y0, az = A.cz[u[1]] - z0;
+        double bx = A.cx[u[2]] - x0, by = A.cy[u[2]] - y0, bz = A.cz[u[2]] - z0;
+        if (A.lattice) {
+            ax = rint(ax * A.lat_inv[0]) * A.lat_h[0]; ay = rint(ay * A.lat_inv[1]) * A.lat_h[1]; az = rint(az * A.lat_inv[2]) * A.lat_h[2];
+            bx = rint(bx * A.lat_inv[0]) * A.lat_h[0]; by = rint(by * A.lat_inv[1]) * A.lat_h[1]; bz = rint(bz * A.lat_inv[2]) * A.lat_h[2];
+        }
+        const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+        return 0.5 * sqrt(nx * nx + ny * ny + nz * nz);
+    }
+}
+
+template <int G, int NPF>
+__global__ __launch_bounds__(TPB) void k_assemble_facets(AsmArgs A, const int *__restrict__ facets, const int *__restrict__ f_ptr,
+                                                         const int *__restrict__ f_list, int *__restrict__ flag) {
+    const int64_t r = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (r >= A.nv) return;
+    const int fa = f_ptr[r], fb = f_ptr[r + 1];
+    if (fa == fb) return;                                              // (most rows: not on the marked boundary)
+    const int ra = A.row_ptr[r], len = A.row_ptr[r + 1] - ra;
+    for (int k = fa; k < fb; ++k) {
+        const int *rec = facets + (int64_t)f_list[k] * NPF;
+        int u[NPF], i = 0;
+#pragma unroll
+        for (int t = 0; t < NPF; ++t) { u[t] = rec[t]; if (u[t] == (int)r) i = t; }
+        const double meas = facet_measure<G>(A, u);
+#pragma unroll
+        for (int j = 0; j < NPF; ++j) {
+            const double val = facet_entry<G, NPF>(i, j, meas);
+            int lo = 0, hi = len - 1;                                  // lower bound of u[j] in the row's sorted columns
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (A.cols[ra + mid] < u[j]) lo = mid + 1; else hi = mid; }
+            if (len == 0 || A.cols[ra + lo] != u[j]) { flag[0] = 1; continue; }
+            A.vals[ra + lo] += val;
+        }
+    }
+}
+
+// facet node ids checked on the device before any kernel follows them (flag + one offending id)
+__global__ __launch_bounds__(TPB) void k_facets_validate(const int *__restrict__ rec, int64_t n, int64_t nv, int *__restrict__ bad) {
+    for (int64_t k = (int64_t)blockIdx.x * TPB + threadIdx.x; k < n; k += (int64_t)gridDim.x * TPB)
+        if (rec[k] < 0 || rec[k] >= nv) { bad[0] = 1; bad[1] = rec[k]; }
+}
+
 // --------------------------------------------------------------------- host side
 static int build_topology(Ctx *c, Mesh *m) {
     void *p;
@@ -1098,6 +1177,84 @@ int pgd_atom_assemble(pgd_handle h, pgd_handle mh, int kind, int da, int db, pgd
         k_assemble_p1_regular<<<gb, TPB, 0, c->stream>>>(A, (int)(m->nv / ((int64_t)m->sym_nx * m->sym_ny)));
     else k_assemble_p1<3><<<gb, TPB, 0, c->stream>>>(A);
     PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+int pgd_atom_assemble_facets(pgd_handle h, pgd_handle mh, const int32_t *facets, int64_t nf, int nvpf, pgd_handle *out) {
+    PGD_CTX(c, h);
+    Mesh *m = get_mesh(c, mh);
+    if (!m || !out) return fail(c, PGD_ERR_INVALID, "atom_assemble_facets: invalid mesh handle");
+    if (m->ncomp != 1) return fail(c, PGD_ERR_INVALID, "atom_assemble_facets: blocked layouts take their atoms from pgd_atom_embed");
+    const int G = m->gdim;
+    const bool p2 = m->nvpc == (G + 1) * (G + 2) / 2;
+    const int want = G == 1 ? 1 : (p2 ? G * (G + 1) / 2 : G);          // point; P1 edge 2, P2 edge 3; P1 triangle 3, P2 triangle 6
+    if (nvpf != want) return fail(c, PGD_ERR_INVALID, "atom_assemble_facets: a facet of this layout has %d nodes, got %d", want, nvpf);
+    if (nf < 0 || (nf > 0 && !facets)) return fail(c, PGD_ERR_INVALID, "atom_assemble_facets: invalid facet list");
+    if (nf * nvpf >= (int64_t)1 << 31) return fail(c, PGD_ERR_LIMIT, "atom_assemble_facets: index range exceeds int32");
+    const int64_t n = nf * nvpf, nv = m->nv;
+    struct Scratch {                                                   // temporaries, released on every way out
+        std::vector<void *> p;
+        ~Scratch() { for (void *q : p) (void)hipFree(q); }
+    } tmp;
+    auto alloc = [&](size_t bytes, int **res) {
+        void *q;
+        const int rc = dev_alloc(c, &q, bytes);
+        if (rc == PGD_OK) { tmp.p.push_back(q); *res = (int *)q; }
+        return rc;
+    };
+    int *rec = nullptr, *cnt = nullptr, *fptr = nullptr, *flist = nullptr, *flags = nullptr;
+    PGD_TRY(alloc((size_t)(n > 0 ? n : 1) * sizeof(int), &rec));
+    PGD_TRY(alloc((size_t)(nv + 1) * sizeof(int), &cnt));
+    PGD_TRY(alloc((size_t)(nv + 1) * sizeof(int), &fptr));
+    PGD_TRY(alloc((size_t)(n > 0 ? n : 1) * sizeof(int), &flist));
+    PGD_TRY(alloc(4 * sizeof(int), &flags));                          // [0] node id out of range, [1] that id, [2] off-pattern coupling
+    hipStream_t st = c->stream;
+    PGD_HIP(c, hipMemsetAsync(flags, 0, 4 * sizeof(int), st));
+    if (n > 0) {
+        PGD_HIP(c, hipMemcpyAsync(rec, facets, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+        k_facets_validate<<<grid_for(n), TPB, 0, st>>>(rec, n, nv, flags);
+    }
+    int hb[2] = {0, 0};
+    PGD_HIP(c, hipMemcpyAsync(hb, flags, sizeof hb, hipMemcpyDeviceToHost, st));
+    PGD_HIP(c, hipStreamSynchronize(st));
+    PGD_LAUNCH_CHECK(c);
+    if (hb[0]) return fail(c, PGD_ERR_INVALID, "atom_assemble_facets: facet node id %d out of range", hb[1]);
+    // node -> facet lists: count, scan, fill, sort (the facets are the cells of the k_v2c_* kernels)
+    PGD_HIP(c, hipMemsetAsync(cnt, 0, (size_t)(nv + 1) * sizeof(int), st));
+    if (nf > 0) k_v2c_count<6><<<grid_for(nf), TPB, 0, st>>>(rec, nf, nvpf, cnt);
+    PGD_TRY(scan_exclusive_i32(c, cnt, fptr, nv));
+    PGD_HIP(c, hipMemsetAsync(cnt, 0, (size_t)(nv + 1) * sizeof(int), st));
+    if (nf > 0) k_v2c_fill<6><<<grid_for(nf), TPB, 0, st>>>(rec, nf, nvpf, fptr, cnt, flist);
+    k_v2c_sort<<<grid_for(nv), TPB, 0, st>>>(fptr, flist, nv);
+    PGD_LAUNCH_CHECK(c);
+    Csr *a = nullptr;
+    PGD_TRY(new_csr(c, mh, m, out, &a));                               // zero-filled, immutable: an atom like any assembled one
+    AsmArgs A;
+    A.cx = m->coords; A.cy = m->coords + nv; A.cz = m->coords + 2 * nv;
+    A.cells = nullptr; A.v2c_ptr = nullptr; A.v2c = nullptr; A.row_ptr = m->row_ptr; A.cols = m->cols;
+    A.w = nullptr; A.vals = a->vals; A.nv = nv; A.kind = PGD_ATOM_MASS; A.da = 0; A.db = 0;
+    A.lattice = (m->lattice && c->asm_lattice) ? 1 : 0;
+    for (int k = 0; k < 3; ++k) { A.lat_h[k] = m->lat_h[k]; A.lat_inv[k] = m->lattice ? 1.0 / m->lat_h[k] : 0.0; }
+    A.lat_unit = 0; A.nx = m->sym_nx; A.ny = m->sym_ny;
+    const int gb = (int)((nv + TPB - 1) / TPB);
+    switch (G * 10 + nvpf) {
+        case 11: k_assemble_facets<1, 1><<<gb, TPB, 0, st>>>(A, rec, fptr, flist, flags + 2); break;
+        case 22: k_assemble_facets<2, 2><<<gb, TPB, 0, st>>>(A, rec, fptr, flist, flags + 2); break;
+        case 23: k_assemble_facets<2, 3><<<gb, TPB, 0, st>>>(A, rec, fptr, flist, flags + 2); break;
+        case 33: k_assemble_facets<3, 3><<<gb, TPB, 0, st>>>(A, rec, fptr, flist, flags + 2); break;
+        default: k_assemble_facets<3, 6><<<gb, TPB, 0, st>>>(A, rec, fptr, flist, flags + 2); break;
+    }
+    const hipError_t launched = hipGetLastError();
+    int off = 0;
+    const hipError_t copied = hipMemcpyAsync(&off, flags + 2, sizeof off, hipMemcpyDeviceToHost, st);
+    const hipError_t synced = hipStreamSynchronize(st);
+    if (launched != hipSuccess || copied != hipSuccess || synced != hipSuccess || off) {
+        (void)free_obj(c, *out, Obj::CSR);                             // the half-built atom goes
+        *out = 0;
+        if (off && launched == hipSuccess && copied == hipSuccess && synced == hipSuccess)
+            return fail(c, PGD_ERR_INVALID, "atom_assemble_facets: a facet couples nodes the pattern does not - not a facet of this mesh");
+        return fail(c, PGD_ERR_HIP, "atom_assemble_facets: %s", hipGetErrorString(launched != hipSuccess ? launched : copied != hipSuccess ? copied : synced));
+    }
     return PGD_OK;
 }
 

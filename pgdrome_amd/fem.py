@@ -41,6 +41,7 @@ import numpy as np
 LOG = logging.getLogger("pgdrome_amd.fem")
 
 MASS, STIFF, DUDV, CONV, CONVT, WMASS, WSTIFF = range(7)   # == include/pgd_amd.h PGD_ATOM_*
+DS_MASS = "ds_mass"          # int_Gamma phi_i phi_j ds over a facet set (pgd_atom_assemble_facets): the atom of a Robin term
 
 # --------------------------------------------------------------------------- backend
 _backend = None
@@ -301,6 +302,7 @@ class DofLayout:
                                       "/ triangles / tetrahedra (SURVEY 8(f4))" % (self.degree, mesh.ufl_cell()))
         self.n = self.coords.shape[0]
         self._handles, self._atoms, self._atom_weights = {}, {}, {}
+        self._facet_atoms = {}
         self._ones = self._space = None
 
     def _init_p2_slab(self, mesh):
@@ -462,6 +464,23 @@ class DofLayout:
             self._atoms[key] = a
             if weight is not None:
                 self._atom_weights[key] = weakref.ref(weight)
+        return a
+
+    def facet_atom(self, ids):
+        """Cached boundary-mass atom  int_Gamma phi_i phi_j ds  over the facets `ids` (Mesh.facets() numbering), assembled
+        on the device; kept per backend and facet set with the layout, like the cell atoms."""
+        if self.part is not None:
+            raise NotImplementedError("bilinear ds terms (Robin atoms) on a sharded (slab) layout")
+        be = get_backend()
+        fn = getattr(be, "atom_facets", None)
+        if fn is None:
+            raise NotImplementedError("bilinear ds terms need a backend that assembles facet atoms (atom_facets); %r has none"
+                                      % (getattr(be, "name", type(be).__name__),))
+        key = (id(be), ids.tobytes())
+        a = self._facet_atoms.get(key)
+        if a is None:
+            a = fn(self.handle(), _facet_node_tuples(self, ids))
+            self._facet_atoms[key] = a
         return a
 
     def _drop_atom(self, be, key):
@@ -710,8 +729,16 @@ class BlockLayout:
         """Scalar atom (kind, da, db) in block (cv, cu); cv = cu = None: in every diagonal block (norms)."""
         if weight is not None:
             raise NotImplementedError("weighted atoms on vector-valued spaces")
+        return self._embedded(self.base.atom(kind, da, db), cv, cu)
+
+    def facet_atom(self, ids, cv=None, cu=None):
+        """The base layout's boundary-mass atom over the facets `ids` in block (cv, cu) (cv = cu = None: every diagonal block)."""
+        if self.part is not None:
+            raise NotImplementedError("bilinear ds terms (Robin atoms) on a sharded (slab) layout")
+        return self._embedded(self.base.facet_atom(ids), cv, cu)
+
+    def _embedded(self, src, cv, cu):
         be = get_backend()
-        src = self.base.atom(kind, da, db)
         key = (id(be), src, cv, cu)
         a = self._atoms.get(key)
         if a is None:
@@ -2137,19 +2164,31 @@ class _AtomRef:
     def __init__(self, coef, kind, da=0, db=0, weight=None, cv=None, cu=None):
         self.coef, self.kind, self.da, self.db, self.weight, self.cv, self.cu = coef, kind, da, db, weight, cv, cu
 
+    def _wkey(self):
+        # (the facet set of a DS_MASS atom by its contents: every assemble() of the same ds(tag) builds a new one)
+        if self.weight is None:
+            return None
+        return self.weight.key if self.kind == DS_MASS else id(self.weight)
+
     def key(self):
         return (self.kind, self.da if self.kind in (DUDV, CONV) else 0, self.db if self.kind in (DUDV, CONVT) else 0,
-                id(self.weight) if self.weight is not None else None, self.cv or 0, self.cu or 0)
+                self._wkey(), self.cv or 0, self.cu or 0)
 
     def transposed_key(self):
         kind = {CONV: CONVT, CONVT: CONV}.get(self.kind, self.kind)
         da, db = self.key()[1], self.key()[2]
-        return (kind, db, da, id(self.weight) if self.weight is not None else None, self.cu or 0, self.cv or 0)
+        return (kind, db, da, self._wkey(), self.cu or 0, self.cv or 0)
 
 
 def _lay_atom(lay, kind, da, db, w, cv=None, cu=None):
     """Atom of a layout; on a vector-valued layout in block (cv, cu), a side without a vector-valued factor
-    (the all-ones function of a functional) using component 0."""
+    (the all-ones function of a functional) using component 0.  DS_MASS: w is the _FacetSet of the ds measure."""
+    if kind == DS_MASS:
+        if isinstance(lay, BlockLayout):
+            return lay.facet_atom(w.ids, cv or 0, cu or 0)
+        if cv is not None or cu is not None:
+            raise ValueError("component of a vector-valued function in an integrand over a scalar space")
+        return lay.facet_atom(w.ids)
     if isinstance(lay, BlockLayout):
         return lay.atom(kind, da, db, w, cv or 0, cu or 0)
     if cv is not None or cu is not None:
@@ -2852,31 +2891,66 @@ def assemble(form, tensor=None, **kw):
         out = AssembledVector(V)
         _assemble_vector_into(form, V._lay, out)
         return out
-    if any(m.kind == "ds" for t, m in form.integrals):
-        raise NotImplementedError("bilinear forms over ds (Robin terms)")
-    return Matrix(V, [_term_matrix(t, V._lay) for t, m in form.integrals])
+    return Matrix(V, [_ds_matrix(t, V._lay, m) if m.kind == "ds" else _term_matrix(t, V._lay) for t, m in form.integrals])
 
 
-# exterior-facet integrals: only the load-type integrands the reference uses - a constant times one
-# (component of a) test function or Function:  int_Gamma N_i ds  is computed ON THE DEVICE by treating the
-# marked facets as a mesh of their own (one disconnected interval / triangle per facet, same polynomial
-# degree), assembling its mass atom and multiplying by ones; the boundary-sized result is scattered into a
-# vector of the space once and cached.
+# exterior-facet integrals.  Loads - a constant times one (component of a) test function:  int_Gamma N_i ds  is computed ON THE
+# DEVICE by treating the marked facets as a mesh of their own (one disconnected interval / triangle per facet, same polynomial
+# degree), assembling its mass atom and multiplying by ones; the boundary-sized result is scattered into a vector of the space
+# once and cached.  Everything with a second function on the facets - the Robin term c*u*v*ds, the functional F*G*ds, the load
+# F*v*ds - goes through the boundary-mass atom R of the facet set on the layout's own pattern (DofLayout.facet_atom): a Matrix
+# term like any dx atom, F^T R G through _bilinear_scalar, R F through the cached products.
 _DS_CACHE = {}
 
 
-def _boundary_load(scalar_lay, measure):
-    mesh = scalar_lay.mesh
-    fv, ext = mesh.facets()
+def _ds_facet_ids(mesh, measure):
+    """Ids (Mesh.facets() numbering, ascending) of the exterior facets a ds measure integrates over: those a facet
+    MeshFunction marks with ``subdomain_id``, or all of them."""
+    ext = mesh.facets()[1]
     if measure.subdomain_data is not None and measure.subdomain_id is not None:
         mf = measure.subdomain_data
         if mf.mesh() is not mesh or mf.dim() != mesh.topology().dim() - 1:
             raise ValueError("ds: subdomain_data must be a facet MeshFunction of the integration mesh")
-        ids = np.where((mf.array() == measure.subdomain_id) & ext)[0]
-    elif measure.subdomain_id is None:
-        ids = np.where(ext)[0]
-    else:
-        raise ValueError("ds(%r) without subdomain_data" % (measure.subdomain_id,))
+        return np.where((mf.array() == measure.subdomain_id) & ext)[0]
+    if measure.subdomain_id is None:
+        return np.where(ext)[0]
+    raise ValueError("ds(%r) without subdomain_data" % (measure.subdomain_id,))
+
+
+def _facet_node_tuples(scalar_lay, ids):
+    """(len(ids), nodes per facet) node ids of a scalar layout on the given facets: the facet's vertices (sorted), then for P2
+    the nodes of its edges in the UFC local order - (0, 1) on an edge, (1, 2), (0, 2), (0, 1) on a triangle."""
+    mesh = scalar_lay.mesh
+    f = mesh.facets()[0][ids]
+    tdim, deg = mesh.topology().dim(), scalar_lay.degree
+    m, nvert = f.shape
+    pairs = [] if deg == 1 or tdim == 1 else [(0, 1)] if tdim == 2 else [(1, 2), (0, 2), (0, 1)]
+    gl = np.empty((m, nvert + len(pairs)), dtype=np.int64)
+    vn = scalar_lay.vertex_nodes
+    for j in range(nvert):
+        gl[:, j] = f[:, j] if vn is None else np.asarray(vn)[f[:, j]]
+    if pairs:
+        nv = mesh.num_vertices()
+        ekeys = scalar_lay.edge_vertices[:, 0].astype(np.int64) * nv + scalar_lay.edge_vertices[:, 1]
+        order = np.argsort(ekeys)
+        for k, (a_, b_) in enumerate(pairs):
+            lo, hi = np.minimum(f[:, a_], f[:, b_]), np.maximum(f[:, a_], f[:, b_])
+            gl[:, nvert + k] = np.asarray(scalar_lay.edge_nodes)[order[np.searchsorted(ekeys[order], lo * nv + hi)]]
+    return gl
+
+
+class _FacetSet:
+    """The facets of one ds measure: the weight slot of a DS_MASS _AtomRef (keyed by its contents)."""
+    __slots__ = ("ids", "key")
+
+    def __init__(self, ids):
+        self.ids = np.ascontiguousarray(ids, dtype=np.int64)
+        self.key = self.ids.tobytes()
+
+
+def _boundary_load(scalar_lay, measure):
+    mesh = scalar_lay.mesh
+    ids = _ds_facet_ids(mesh, measure)
     key = (id(get_backend()), id(scalar_lay), ids.tobytes())
     hit = _DS_CACHE.get(key)
     if hit is not None and hit[1]() is scalar_lay:       # (an address is reused once a layout has died: check who lives there)
@@ -2887,7 +2961,7 @@ def _boundary_load(scalar_lay, measure):
         out[_facet_nodes(scalar_lay, ids)] = 1.0                    # point evaluation at boundary vertices
     elif ids.size:
         X = mesh.coordinates()
-        f = fv[ids]
+        f = mesh.facets()[0][ids]
         m = f.shape[0]
         if tdim == 2:      # facets = edges -> intervals laid end to end
             length = np.linalg.norm(X[f[:, 1]] - X[f[:, 0]], axis=1)
@@ -2899,9 +2973,6 @@ def _boundary_load(scalar_lay, measure):
                 co[:, 2] = start + 0.5 * length
             bcoords = co.reshape(-1, 1)
             bcells = np.arange(m * per, dtype=np.int32).reshape(m, per)
-            nodes = [f[:, 0], f[:, 1]]
-            if deg == 2:
-                nodes.append(None)     # edge node, filled below
         else:              # facets = triangles -> congruent triangles in the plane, side by side
             a = X[f[:, 1]] - X[f[:, 0]]
             b = X[f[:, 2]] - X[f[:, 0]]
@@ -2918,7 +2989,6 @@ def _boundary_load(scalar_lay, measure):
             per = len(pts)
             bcoords = np.stack(pts, axis=1).reshape(-1, 2)
             bcells = np.arange(m * per, dtype=np.int32).reshape(m, per)
-            nodes = [f[:, 0], f[:, 1], f[:, 2]] + ([None] * 3 if deg == 2 else [])
         be = get_backend()
         bm = be.mesh(bcoords, bcells)
         at = be.atom(bm, MASS, 0, 0, 0)
@@ -2929,20 +2999,7 @@ def _boundary_load(scalar_lay, measure):
             be.vec_free(h)
         be.atom_free(at)
         be.mesh_free(bm)
-        # global node of every local boundary node
-        vn = scalar_lay.vertex_nodes
-        gl = np.empty((m, per), dtype=np.int64)
-        nvert = f.shape[1]
-        for j in range(nvert):
-            gl[:, j] = f[:, j] if vn is None else np.asarray(vn)[f[:, j]]
-        if deg == 2:
-            nv = mesh.num_vertices()
-            ekeys = scalar_lay.edge_vertices[:, 0].astype(np.int64) * nv + scalar_lay.edge_vertices[:, 1]
-            order = np.argsort(ekeys)
-            pairs = [(0, 1)] if tdim == 2 else [(1, 2), (0, 2), (0, 1)]
-            for k, (a_, b_) in enumerate(pairs):
-                lo, hi = np.minimum(f[:, a_], f[:, b_]), np.maximum(f[:, a_], f[:, b_])
-                gl[:, nvert + k] = np.asarray(scalar_lay.edge_nodes)[order[np.searchsorted(ekeys[order], lo * nv + hi)]]
+        gl = _facet_node_tuples(scalar_lay, ids)             # global node of every local boundary node
         np.add.at(out, gl.ravel(), loads.ravel())
     if len(_DS_CACHE) > 64:
         _DS_CACHE.clear()
@@ -2970,14 +3027,33 @@ def _ds_load_vector(lay, measure, comp):
 
 def _ds_split(term, lay):
     test, trial, coefs, gd = _classify(term, lay)
-    if gd is not None or trial is not None or any(c.deriv is not None for c in coefs):
-        raise NotImplementedError("ds integrands beyond  constant * (test function | function)")
-    return test, coefs
+    if gd is not None or any(f is not None and f.deriv is not None for f in [test, trial] + coefs):
+        raise NotImplementedError("derivatives in a ds integrand (only  c * u * v,  c * F * v,  c * F * G  and loads)")
+    return test, trial, coefs
+
+
+def _ds_atom(lay, measure, cv=None, cu=None):
+    """The boundary-mass atom of the measure's facets on `lay` (block (cv, cu) of a vector-valued layout)."""
+    return _lay_atom(lay, DS_MASS, 0, 0, _FacetSet(_ds_facet_ids(lay.mesh, measure)), cv, cu)
+
+
+def _ds_matrix(term, lay, measure):
+    """c * u * v * ds(tag): the Robin term, a Matrix term over the facet set's boundary-mass atom."""
+    test, trial, coefs = _ds_split(term, lay)
+    if test is None or trial is None:
+        raise ValueError("bilinear form needs a trial and a test function")
+    if coefs:
+        raise NotImplementedError("a Function-valued coefficient in a bilinear ds term (only constants: c * u * v * ds)")
+    if lay.part is not None:
+        raise NotImplementedError("bilinear ds terms (Robin atoms) on a sharded (slab) layout")
+    if not hasattr(get_backend(), "atom_facets"):
+        lay.facet_atom(np.zeros(0, dtype=np.int64))          # (raises: no facet atoms on this backend)
+    return _AtomRef(term.coef, DS_MASS, 0, 0, _FacetSet(_ds_facet_ids(lay.mesh, measure)), test.comp, trial.comp)
 
 
 def _ds_scalar(term, lay, measure):
-    test, coefs = _ds_split(term, lay)
-    if test is not None:
+    test, trial, coefs = _ds_split(term, lay)
+    if test is not None or trial is not None:
         raise ValueError("scalar assemble of a form with arguments")
     part = lay.part
     if len(coefs) == 0:
@@ -2987,8 +3063,14 @@ def _ds_scalar(term, lay, measure):
             return term.coef * float(L0.sum())
         lo0, hi0 = scalar.owned_range()              # row-sharded: this rank's rows, summed over the ranks
         return term.coef * part.comm.allreduce_sum(float(L0[lo0:hi0].sum()))
+    if len(coefs) == 2:
+        # F^T R G: the memo, the stored products and the batched functionals of every other functional
+        f, g = coefs
+        atom = _ds_atom(lay, measure, f.comp, g.comp)
+        return term.coef * _bilinear_scalar(lay, atom, _coef_vec(f.leaf, lay), _coef_vec(g.leaf, lay),
+                                            symmetric=f.comp == g.comp)
     if len(coefs) != 1:
-        raise NotImplementedError("ds functional of a product of functions")
+        raise NotImplementedError("ds functional of a product of more than two functions")
     c = coefs[0]
     f, L = _coef_vec(c.leaf, lay), _ds_load_vector(lay, measure, c.comp)
     if part is not None:
@@ -3000,12 +3082,17 @@ def _ds_scalar(term, lay, measure):
 
 
 def _ds_vector(term, lay, measure):
-    """(coef, None, load Vector): b += coef * load."""
-    test, coefs = _ds_split(term, lay)
+    """(coef, None, load Vector): b += coef * load;  with a coefficient F: (coef, R, F), b += coef * R F."""
+    test, trial, coefs = _ds_split(term, lay)
+    if trial is not None:
+        raise ValueError("linear form with a trial function")
     if test is None:
         raise ValueError("linear form without a test function")
+    if len(coefs) > 1:
+        raise NotImplementedError("ds linear form with more than one coefficient function")
     if coefs:
-        raise NotImplementedError("ds linear form with a non-constant coefficient")
+        g = coefs[0]
+        return term.coef, _ds_atom(lay, measure, test.comp, g.comp), _coef_vec(g.leaf, lay)
     return term.coef, None, _ds_load_vector(lay, measure, test.comp)
 
 

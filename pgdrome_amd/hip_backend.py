@@ -31,7 +31,7 @@ class HipBackend:
     _RENAMED = {
         "mesh": "mesh_upload", "vec_zeros": "vec_alloc", "vec_to_host": "vec_download", "atom": "atom_assemble",
         "atom_values": "atom_download", "combine": "op_combine", "pcg": "pcg_solve", "slots_get": "slots_download",
-        "slots_set": "slots_upload",
+        "slots_set": "slots_upload", "atom_facets": "atom_assemble_facets",
     }
 
     def __getattr__(self, name):

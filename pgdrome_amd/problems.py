@@ -359,6 +359,77 @@ def elastic_block(space_mesh, n_e=9, e_range=(0.5, 2.0), nu=0.3, k_found=2.0, PG
                 param=param, rhs_fct=rhs_fct, lhs_fct=lhs_fct, probs=["x", "e"], PGD_nmax=PGD_nmax, PGD_tol=PGD_tol)
 
 
+# ----------------------------- convective (Robin) boundary: the heat-transfer coefficient h as a coordinate
+ROBIN, FIXED = 1, 2          # facet markers of robin_heat
+
+
+def robin_heat(space_mesh, n_h=17, h_range=(0.1, 100.0), k=1.0, f=1.0, u_inf=0.5, PGD_nmax=10, PGD_tol=1e-8):
+    """-div(k grad u) = f in Omega;  u = 0 on the face x[0] = min (marker FIXED);  k du/dn + h u = h u_inf on every other
+    boundary facet (marker ROBIN, ds(ROBIN)), u = u(x; h) with h a separated 1-D P1 coordinate.  Atoms
+    k K_x (x) M_h + R_x (x) Mw_h (w = h), R_x the boundary mass of the Robin facets; load  f 1_x (x) 1_h + u_inf R_x-load (x) h."""
+    h_mesh = fem.IntervalMesh(n_h - 1, h_range[0], h_range[1])
+    meshes = [space_mesh, h_mesh]
+    Vs = [fem.FunctionSpace(space_mesh, "CG", 1), fem.FunctionSpace(h_mesh, "CG", 1)]
+    load = [[fem.interpolate(fem.Expression("%r" % float(f), degree=1), Vs[0])],
+            [fem.interpolate(fem.Expression("1.0", degree=1), Vs[1])]]
+    hfun = fem.interpolate(fem.Expression("x[0]", degree=1), Vs[1])
+    x0 = float(space_mesh.coordinates()[:, 0].min())
+    eps = 1e-10 * max(1.0, float(space_mesh.coordinates()[:, 0].max()) - x0)
+
+    class _Boundary(fem.SubDomain):
+        def inside(self, x, on_boundary):
+            return on_boundary
+
+    class _Fixed(fem.SubDomain):
+        def inside(self, x, on_boundary):
+            return (x[0] < x0 + eps) & on_boundary
+
+    markers = fem.MeshFunction("size_t", space_mesh, space_mesh.topology().dim() - 1, 0)
+    _Boundary().mark(markers, ROBIN)
+    _Fixed().mark(markers, FIXED)
+    ds_r = fem.Measure("ds", domain=space_mesh, subdomain_data=markers)(ROBIN)
+    param = {"h": hfun, "k": float(k), "u_inf": float(u_inf), "markers": markers, "ds_robin": ds_r}
+
+    def bc_fct(Vs, dom, param):
+        def fixed(x, on_boundary):
+            return (x[0] < x0 + eps) & on_boundary
+        return [fem.DirichletBC(Vs[0], 0, fixed), 0]
+
+    def lhs_fct(u, v, Fs, meshes, dom, param, typ, dim):
+        h, kk, dsr = param["h"], param["k"], param["ds_robin"]
+        if typ == "x":
+            return (fem.Constant(kk * fem.assemble(Fs[1] * Fs[1] * fem.dx(meshes[1])))
+                    * fem.inner(fem.grad(u), fem.grad(v)) * fem.dx(meshes[0])
+                    + fem.Constant(fem.assemble(h * Fs[1] * Fs[1] * fem.dx(meshes[1]))) * u * v * dsr)
+        return (fem.Constant(kk * fem.assemble(fem.inner(fem.grad(Fs[0]), fem.grad(Fs[0])) * fem.dx(meshes[0])))
+                * u * v * fem.dx(meshes[1])
+                + fem.Constant(fem.assemble(Fs[0] * Fs[0] * dsr)) * h * u * v * fem.dx(meshes[1]))
+
+    def rhs_fct(u, v, Fs, meshes, dom, param, Q, PGD_func, typ, nE, dim):
+        h, kk, ui, dsr = param["h"], param["k"], param["u_inf"], param["ds_robin"]
+        if typ == "x":
+            l = (fem.Constant(fem.assemble(Q[1][0] * Fs[1] * fem.dx(meshes[1]))) * Q[0][0] * v * fem.dx(meshes[0])
+                 + fem.Constant(ui * fem.assemble(h * Fs[1] * fem.dx(meshes[1]))) * v * dsr)
+            for old in range(nE):
+                l += (-fem.Constant(kk * fem.assemble(PGD_func[1][old] * Fs[1] * fem.dx(meshes[1])))
+                      * fem.inner(fem.grad(PGD_func[0][old]), fem.grad(v)) * fem.dx(meshes[0])
+                      - fem.Constant(fem.assemble(h * PGD_func[1][old] * Fs[1] * fem.dx(meshes[1])))
+                      * PGD_func[0][old] * v * dsr)
+            return l
+        l = (fem.Constant(fem.assemble(Q[0][0] * Fs[0] * fem.dx(meshes[0]))) * Q[1][0] * v * fem.dx(meshes[1])
+             + fem.Constant(ui * fem.assemble(Fs[0] * dsr)) * h * v * fem.dx(meshes[1]))
+        for old in range(nE):
+            l += (-fem.Constant(kk * fem.assemble(fem.inner(fem.grad(PGD_func[0][old]), fem.grad(Fs[0])) * fem.dx(meshes[0])))
+                  * PGD_func[1][old] * v * fem.dx(meshes[1])
+                  - fem.Constant(fem.assemble(PGD_func[0][old] * Fs[0] * dsr))
+                  * h * PGD_func[1][old] * v * fem.dx(meshes[1]))
+        return l
+
+    return dict(name="robin_heat", name_coord=["X", "h"], modes_info=["U", "Node", "Scalar"], Vs=Vs,
+                bc_fct=bc_fct, load=load, param=param, rhs_fct=rhs_fct, lhs_fct=lhs_fct, probs=["x", "h"],
+                PGD_nmax=PGD_nmax, PGD_tol=PGD_tol)
+
+
 def make_problem(spec, cls):
     """PGDProblem(**spec) for either implementation of the class."""
     return cls(**spec)

@@ -52,7 +52,10 @@ enum {
     PGD_ATOM_CONV = 3,    /* int u_{,da} v        (time derivative term)          */
     PGD_ATOM_CONVT = 4,   /* int u v_{,db}                                        */
     PGD_ATOM_WMASS = 5,   /* int w u v,  w a P1 vertex field                      */
-    PGD_ATOM_WSTIFF = 6   /* int w grad u . grad v                                */
+    PGD_ATOM_WSTIFF = 6,  /* int w grad u . grad v                                */
+    PGD_ATOM_WDUDV = 7,   /* int w u_{,da} v_{,db}                                */
+    PGD_ATOM_WCONV = 8,   /* int w u_{,da} v   (convection by a velocity field)   */
+    PGD_ATOM_WCONVT = 9   /* int w u v_{,db}                                      */
 };
 
 /* ----------------------------------------------------------------- context --- */
@@ -124,8 +127,14 @@ int pgd_vec_dot(pgd_handle ctx, pgd_handle x, pgd_handle y, int64_t lo, int64_t 
 /* Replaces FFC tabulate_tensor + dolfin Assembler for one bilinear "atom" on
  * one separated dimension (triggered from solver.py:636,716 and from every
  * dolfin.assemble inside the callbacks, e.g. test_heat1D.py:59-62).  Values
- * are laid out over the mesh's CSR pattern.  wvec: vertex weights for the
- * weighted kinds, 0 otherwise.  Deterministic (owner-computes, no atomics).     */
+ * are laid out over the mesh's CSR pattern.  wvec: the nodal weight w of the
+ * weighted kinds (WMASS, WSTIFF, WDUDV, WCONV, WCONVT), a vector of nv entries in
+ * the layout's own space (P1 or P2, like u and v), 0 otherwise; a weighted kind
+ * without it, or with a vector of another length, is PGD_ERR_INVALID.  One weight
+ * per atom, never differentiated; weights of another Lagrange degree are the
+ * caller's to interpolate.  P1 entries are closed forms (exact for a P1 weight),
+ * P2 entries Gauss quadrature exact to degree 7 (the integrands reach degree 6).
+ * Deterministic (owner-computes, no atomics).                                   */
 int pgd_atom_assemble(pgd_handle ctx, pgd_handle mesh, int kind, int da, int db,
                       pgd_handle wvec, pgd_handle *atom);
 /* Boundary mass  int_Gamma phi_i phi_j ds  over nf facets (the Robin term c*u*v*ds of a form), on the

@@ -407,6 +407,22 @@ __device__ __forceinline__ double p1_entry(int kind, int da, int db, int i, int 
             for (int k = 0; k < D + 1; ++k) wb += wl[k];
             return vol * (wb * (1.0 / (D + 1))) * s;
         }
+        // the gradients are constant per cell, so the weight enters through its integral against at most one basis function
+        // (int w phi_i = vol MFAC sum_k w_k (1 + [k == i])): exact for a P1 weight.  w_i is selected by compare, like gi.
+        case PGD_ATOM_WDUDV: {
+            double wb = 0.0;
+#pragma unroll
+            for (int k = 0; k < D + 1; ++k) wb += wl[k];
+            return vol * (wb * (1.0 / (D + 1))) * gib * gja;
+        }
+        case PGD_ATOM_WCONV: case PGD_ATOM_WCONVT: {
+            double ws = 0.0, wi = wl[0];
+#pragma unroll
+            for (int k = 0; k < D + 1; ++k) ws += wl[k];
+#pragma unroll
+            for (int k = 1; k < D + 1; ++k) if (k == i) wi = wl[k];
+            return kind == PGD_ATOM_WCONV ? gja * (vol * MFAC * (ws + wi)) : gib * (vol * MFAC * (ws + wl[j]));
+        }
     }
     return 0.0;
 }
@@ -564,7 +580,7 @@ __global__ __launch_bounds__(TPB) void k_assemble_p2_interval(AsmArgs A) {
         const int i = (u[0] == (int)r) ? 0 : (u[1] == (int)r) ? 1 : 2;
         const double hs = A.cx[u[1]] - A.cx[u[0]], inv = 1.0 / hs, ah = fabs(hs);
         double wl[3] = {1.0, 1.0, 1.0};
-        const bool weighted = A.kind == PGD_ATOM_WMASS || A.kind == PGD_ATOM_WSTIFF;
+        const bool weighted = A.kind >= PGD_ATOM_WMASS;
         if (weighted) { wl[0] = A.w[u[0]]; wl[1] = A.w[u[1]]; wl[2] = A.w[u[2]]; }
         double loc[3] = {0.0, 0.0, 0.0};
         for (int q = 0; q < 4; ++q) {
@@ -577,9 +593,9 @@ __global__ __launch_bounds__(TPB) void k_assemble_p2_interval(AsmArgs A) {
                 double f;
                 switch (A.kind) {
                     case PGD_ATOM_MASS: case PGD_ATOM_WMASS: f = N[i] * N[j]; break;
-                    case PGD_ATOM_CONV: f = N[i] * dN[j]; break;
-                    case PGD_ATOM_CONVT: f = dN[i] * N[j]; break;
-                    default: f = dN[i] * dN[j]; break;      // STIFF, DUDV(0,0), WSTIFF
+                    case PGD_ATOM_CONV: case PGD_ATOM_WCONV: f = N[i] * dN[j]; break;
+                    case PGD_ATOM_CONVT: case PGD_ATOM_WCONVT: f = dN[i] * N[j]; break;
+                    default: f = dN[i] * dN[j]; break;      // STIFF, DUDV(0,0), WSTIFF, WDUDV(0,0)
                 }
                 loc[j] = fma(jac, f, loc[j]);
             }
@@ -615,7 +631,7 @@ __global__ __launch_bounds__(64) void k_assemble_p2_simplex(AsmArgs A, const int
     if (r >= A.nv) return;
     const int ra = A.row_ptr[r], len = A.row_ptr[r + 1] - ra;
     for (int k = 0; k < len; ++k) A.vals[ra + k] = 0.0;
-    const bool weighted = A.kind == PGD_ATOM_WMASS || A.kind == PGD_ATOM_WSTIFF;
+    const bool weighted = A.kind >= PGD_ATOM_WMASS;
     for (int k = A.v2c_ptr[r]; k < A.v2c_ptr[r + 1]; ++k) {
         const int *rec = cellsN + (int64_t)A.v2c[k] * NN;
         int u[NN], i = 0;
@@ -680,9 +696,9 @@ __global__ __launch_bounds__(64) void k_assemble_p2_simplex(AsmArgs A, const int
                 for (int d = 0; d < D; ++d) if (d == A.da) dNj_a = dN[j][d];
                 switch (A.kind) {
                     case PGD_ATOM_MASS: case PGD_ATOM_WMASS: f = Ni * N[j]; break;
-                    case PGD_ATOM_CONV: f = Ni * dNj_a; break;
-                    case PGD_ATOM_CONVT: f = dNi_b * N[j]; break;
-                    case PGD_ATOM_DUDV: f = dNi_b * dNj_a; break;
+                    case PGD_ATOM_CONV: case PGD_ATOM_WCONV: f = Ni * dNj_a; break;
+                    case PGD_ATOM_CONVT: case PGD_ATOM_WCONVT: f = dNi_b * N[j]; break;
+                    case PGD_ATOM_DUDV: case PGD_ATOM_WDUDV: f = dNi_b * dNj_a; break;
                     default:
 #pragma unroll
                         for (int d = 0; d < D; ++d) f = fma(dNi[d], dN[j][d], f);
@@ -1148,10 +1164,10 @@ int pgd_atom_assemble(pgd_handle h, pgd_handle mh, int kind, int da, int db, pgd
     Mesh *m = get_mesh(c, mh);
     if (!m || !out) return fail(c, PGD_ERR_INVALID, "atom_assemble: invalid mesh handle");
     if (m->ncomp != 1) return fail(c, PGD_ERR_INVALID, "atom_assemble: blocked layouts take their atoms from pgd_atom_embed");
-    if (kind < PGD_ATOM_MASS || kind > PGD_ATOM_WSTIFF) return fail(c, PGD_ERR_INVALID, "atom_assemble: unknown kind %d", kind);
+    if (kind < PGD_ATOM_MASS || kind > PGD_ATOM_WCONVT) return fail(c, PGD_ERR_INVALID, "atom_assemble: unknown kind %d", kind);
     if (da < 0 || da >= m->gdim || db < 0 || db >= m->gdim) return fail(c, PGD_ERR_INVALID, "atom_assemble: derivative axis out of range");
     const double *w = nullptr;
-    if (kind == PGD_ATOM_WMASS || kind == PGD_ATOM_WSTIFF) {
+    if (kind >= PGD_ATOM_WMASS) {
         Vec *wv = get_vec(c, wh);
         if (!wv || wv->n != m->nv) return fail(c, PGD_ERR_INVALID, "atom_assemble: weighted kind needs a vertex weight vector");
         w = wv->d;

@@ -41,6 +41,9 @@ import numpy as np
 LOG = logging.getLogger("pgdrome_amd.fem")
 
 MASS, STIFF, DUDV, CONV, CONVT, WMASS, WSTIFF = range(7)   # == include/pgd_amd.h PGD_ATOM_*
+WDUDV, WCONV, WCONVT = 7, 8, 9                             # int w u_{,da} v_{,db}, int w u_{,da} v, int w u v_{,db}
+# kinds whose (da, db) matter: the trial derivative da, the test derivative db
+_DA_KINDS, _DB_KINDS = (DUDV, CONV, WDUDV, WCONV), (DUDV, CONVT, WDUDV, WCONVT)
 DS_MASS = "ds_mass"          # int_Gamma phi_i phi_j ds over a facet set (pgd_atom_assemble_facets): the atom of a Robin term
 
 # --------------------------------------------------------------------------- backend
@@ -439,15 +442,21 @@ class DofLayout:
             self._handles[id(be)] = h
         return h
 
+    def _atom_key(self, be, kind, da, db, weight):
+        if self.mesh.geometry().dim() == 1 and kind in (DUDV, WDUDV):
+            kind = STIFF if kind == DUDV else WSTIFF
+        wkey = None if weight is None else (id(weight), weight.version)
+        return (id(be), kind, da if kind in _DA_KINDS else 0, db if kind in _DB_KINDS else 0, wkey)
+
     def atom(self, kind, da=0, db=0, weight=None):
         """Cached device atom; weighted atoms are keyed by the weight's identity + version, the identity checked through
         a weak reference: an address (``id``) is reused as soon as a vector dies, and an iterate can end up as the weight
         of a functional (``assemble(E * F * F * dx)`` with E and F equally "old")."""
         be = get_backend()
-        if self.mesh.geometry().dim() == 1 and kind == DUDV:
-            kind = STIFF
-        wkey = None if weight is None else (id(weight), weight.version)
-        key = (id(be), kind, da if kind in (DUDV, CONV) else 0, db if kind in (DUDV, CONVT) else 0, wkey)
+        if kind in (WDUDV, WCONV, WCONVT) and self.part is not None:
+            raise NotImplementedError("weighted derivative atoms on a sharded (slab) layout")
+        key = self._atom_key(be, kind, da, db, weight)
+        kind = key[1]
         a = self._atoms.get(key)
         if a is not None and weight is not None:
             ref = self._atom_weights.get(key)
@@ -456,9 +465,10 @@ class DofLayout:
                 a = None
         if a is None:
             if weight is not None:
-                # drop stale versions of the same weight and the atoms of weights that died (2 GB each at 256^3)
+                # drop the atoms of older versions of this weight and those of weights that died (2 GB each at 256^3) - never
+                # another atom of the same version: the (da, db) atoms of one weight (weighted elasticity) live side by side
                 for k in [k for k in self._atoms if k[0] == id(be) and k[4] and
-                          ((k[1] == kind and k[4][0] == id(weight)) or self._atom_weights[k]() is None)]:
+                          ((k[4][0] == id(weight) and k[4][1] < weight.version) or self._atom_weights[k]() is None)]:
                     self._drop_atom(be, k)
             a = be.atom(self.handle(), kind, key[2], key[3], weight.dev() if weight is not None else 0)
             self._atoms[key] = a
@@ -682,6 +692,7 @@ class BlockLayout:
         self.coords = np.repeat(base.coords, self.ncomp, axis=0)       # dof coordinates
         self.vertex_nodes = base.vertex_nodes
         self._handles, self._atoms = {}, {}
+        self._watoms = {}            # weighted: base atom key + (cv, cu) -> (embedded atom, scalar source, weakref to the weight)
         self._ones = self._space = None
 
     @property
@@ -726,10 +737,36 @@ class BlockLayout:
         return h
 
     def atom(self, kind, da=0, db=0, weight=None, cv=None, cu=None):
-        """Scalar atom (kind, da, db) in block (cv, cu); cv = cu = None: in every diagonal block (norms)."""
-        if weight is not None:
-            raise NotImplementedError("weighted atoms on vector-valued spaces")
-        return self._embedded(self.base.atom(kind, da, db), cv, cu)
+        """Scalar atom (kind, da, db) in block (cv, cu); cv = cu = None: in every diagonal block (norms).  A weight is a
+        scalar field of the base layout (_coef_vec(..., weight=True)): the scalar weighted atom, embedded."""
+        if weight is None:
+            return self._embedded(self.base.atom(kind, da, db), cv, cu)
+        if self.part is not None:
+            raise NotImplementedError("weighted atoms on a sharded (slab) vector-valued layout")
+        if weight.size() != self.base.n:
+            raise NotImplementedError("a weight on a vector-valued space is a scalar field of its Lagrange degree")
+        be = get_backend()
+        src = self.base.atom(kind, da, db, weight)           # (drops the base's atoms of older versions and of dead weights)
+        bkey = self.base._atom_key(be, kind, da, db, weight)
+        key = bkey + (cv, cu)
+        hit = self._watoms.get(key)
+        if hit is not None and hit[1] == src and hit[2]() is weight:
+            return hit[0]
+        # embedded atoms whose scalar source is gone (handle numbers are reused: the source is checked by its key, its handle
+        # and its weight) - or whose entry is replaced here
+        base_atoms, base_w = self.base._atoms, self.base._atom_weights
+        for k, (a, s_, wref) in list(self._watoms.items()):
+            if k[0] != id(be):
+                continue
+            bk = k[:5]
+            alive = wref() is not None and base_atoms.get(bk) == s_ and base_w.get(bk) is not None and base_w[bk]() is wref()
+            if k == key or not alive:
+                del self._watoms[k]
+                _purge_atom(a)
+                be.atom_free(a)
+        a = self._embed(be, src, cv, cu)
+        self._watoms[key] = (a, src, weakref.ref(weight))
+        return a
 
     def facet_atom(self, ids, cv=None, cu=None):
         """The base layout's boundary-mass atom over the facets `ids` in block (cv, cu) (cv = cu = None: every diagonal block)."""
@@ -742,14 +779,17 @@ class BlockLayout:
         key = (id(be), src, cv, cu)
         a = self._atoms.get(key)
         if a is None:
-            if cv is None:
-                a = be.atom_embed(self.handle(), src, 0, 0, 1.0, 0)
-                for c in range(1, self.ncomp):
-                    be.atom_embed(self.handle(), src, c, c, 1.0, a)
-            else:
-                a = be.atom_embed(self.handle(), src, int(cv), int(cu), 1.0, 0)
+            a = self._embed(be, src, cv, cu)
             self._atoms[key] = a
         return a
+
+    def _embed(self, be, src, cv, cu):
+        if cv is None:
+            a = be.atom_embed(self.handle(), src, 0, 0, 1.0, 0)
+            for c in range(1, self.ncomp):
+                be.atom_embed(self.handle(), src, c, c, 1.0, a)
+            return a
+        return be.atom_embed(self.handle(), src, int(cv), int(cu), 1.0, 0)
 
 
 def _block_layout(mesh, degree, ncomp):
@@ -1220,12 +1260,13 @@ class Grad:
 
     def __init__(self, f):
         if type(f) is Function and f._V._ncomp == 1:
-            self.num, self.consts, self.leaf = 1.0, (), f
+            self.num, self.consts, self.leaf, self.comp = 1.0, (), f, None
             return
         p = _as_poly(f)
         if len(p) != 1 or len(p[0].factors) != 1 or p[0].factors[0].deriv is not None:
             raise NotImplementedError("grad() of anything but a plain function")
-        self.num, self.consts, self.leaf = p[0].num, p[0].consts, p[0].factors[0].leaf
+        # comp: grad(u[c]) of a vector-valued u keeps its component (inner() writes it out per axis)
+        self.num, self.consts, self.leaf, self.comp = p[0].num, p[0].consts, p[0].factors[0].leaf, p[0].factors[0].comp
 
 
 def grad(f):
@@ -1373,6 +1414,13 @@ def inner(a, b):
             acc = ListTensor._add(acc, ListTensor._mul(a.a[idx], b.a[idx]))
         return acc if isinstance(acc, Expr) else Poly([Term(float(acc), ())])
     if isinstance(a, Grad) and isinstance(b, Grad):
+        if a.comp is not None or b.comp is not None:
+            # components of vector-valued functions: sum_k u[c]_{,k} v[d]_{,k}, each term an atom in block (d, c)
+            if a.comp is None or b.comp is None:
+                raise NotImplementedError("inner(grad(u[c]), grad(f)) with f not a component of a vector-valued function")
+            gdim = a.leaf._V.mesh().geometry().dim()
+            return Poly([Term(a.num * b.num, (Factor(a.leaf, k, None, a.comp), Factor(b.leaf, k, None, b.comp)),
+                              a.consts + b.consts) for k in range(gdim)])
         if type(a.leaf) is Function and type(b.leaf) is Function and a.num == 1.0 and b.num == 1.0 and not a.consts and not b.consts:
             return _FastProd(((a.leaf, "grad", b.leaf),))
         return Poly([Term(a.num * b.num, (Factor(a.leaf, "grad", b.leaf),), a.consts + b.consts)])
@@ -2171,11 +2219,11 @@ class _AtomRef:
         return self.weight.key if self.kind == DS_MASS else id(self.weight)
 
     def key(self):
-        return (self.kind, self.da if self.kind in (DUDV, CONV) else 0, self.db if self.kind in (DUDV, CONVT) else 0,
+        return (self.kind, self.da if self.kind in _DA_KINDS else 0, self.db if self.kind in _DB_KINDS else 0,
                 self._wkey(), self.cv or 0, self.cu or 0)
 
     def transposed_key(self):
-        kind = {CONV: CONVT, CONVT: CONV}.get(self.kind, self.kind)
+        kind = {CONV: CONVT, CONVT: CONV, WCONV: WCONVT, WCONVT: WCONV}.get(self.kind, self.kind)
         da, db = self.key()[1], self.key()[2]
         return (kind, db, da, self._wkey(), self.cu or 0, self.cv or 0)
 
@@ -2196,12 +2244,17 @@ def _lay_atom(lay, kind, da, db, w, cv=None, cu=None):
     return lay.atom(kind, da, db, w)
 
 
-def _coef_vec(leaf, lay):
-    """Device-resident nodal representation of a coefficient leaf in the layout of the integral."""
+def _coef_vec(leaf, lay, weight=False):
+    """Device-resident nodal representation of a coefficient leaf in the layout of the integral.  weight=True: the leaf
+    weights an atom, and on a vector-valued layout it is a scalar field of the base layout (same mesh, same degree)."""
+    if weight and isinstance(lay, BlockLayout):
+        if isinstance(leaf, Function) and leaf._V._ncomp > 1:
+            raise NotImplementedError("vector-valued weight function (write the components' terms out)")
+        lay = lay.base
     if isinstance(leaf, Function):
         if leaf._V._lay is not lay:
-            if leaf._V.lay() is not lay.lay:
-                raise ValueError("coefficient lives on a different lay than the integral")
+            if leaf._V.mesh() is not lay.mesh:
+                raise ValueError("coefficient lives on a different mesh than the integral")
             raise NotImplementedError("mixing Lagrange degrees in one integrand")
         return leaf._vec
     if isinstance(leaf, Expression):
@@ -2215,16 +2268,16 @@ def _atom_for(test, trial, weights, lay):
         raise AssertionError("grad factors are handled by the caller")
     if len(weights) > 1:
         raise NotImplementedError("more than one weight function in one integrand")
-    w = _coef_vec(weights[0].leaf, lay) if weights else None
     if weights and weights[0].deriv is not None:
         raise NotImplementedError("differentiated weight function")
+    w = _coef_vec(weights[0].leaf, lay, weight=True) if weights else None
     dt, du = test.deriv, trial.deriv
     if dt is None and du is None:
         return (WMASS, 0, 0, w) if w is not None else (MASS, 0, 0, None)
     if w is not None:
-        if dt is not None and du is not None and lay.mesh.topology().dim() == 1:
-            return (WSTIFF, 0, 0, w)
-        raise NotImplementedError("weighted derivative atoms beyond w u' v' in 1-D")
+        if dt is not None and du is not None:
+            return (WSTIFF, 0, 0, w) if lay.mesh.topology().dim() == 1 else (WDUDV, du, dt, w)
+        return (WCONV, du, 0, w) if du is not None else (WCONVT, 0, dt, w)
     if dt is not None and du is not None:
         return (DUDV, du, dt, None)
     if du is not None:
@@ -2237,8 +2290,9 @@ def _weight_last(plain, lay):
     an Expression (fixed data) before anything else, then the vector that changes least often."""
     def key(c):
         # ties (equally "old" vectors): the factor that occurs once in the integrand is the weight, the repeated one
-        # (F * F) the function the functional is evaluated on
-        return (1 if isinstance(c.leaf, Expression) else 0, -_coef_vec(c.leaf, lay).version,
+        # (F * F) the function the functional is evaluated on.  On a vector-valued layout only a scalar field can weight.
+        scalar = not isinstance(lay, BlockLayout) or isinstance(c.leaf, Expression) or c.leaf._V._ncomp == 1
+        return (1 if scalar else 0, 1 if isinstance(c.leaf, Expression) else 0, -_coef_vec(c.leaf, lay, weight=scalar).version,
                 -sum(1 for o in plain if o.leaf is c.leaf))
     return sorted(plain, key=key)
 
@@ -2665,7 +2719,7 @@ def _term_operands(term, lay):
     f, g, rest = ordered[0], ordered[1], ordered[2:]
     kind, da, db, w = _atom_for(Factor(None, f.deriv), Factor(None, g.deriv), rest, lay)
     return (_lay_atom(lay, kind, da, db, w, f.comp, g.comp), _coef_vec(f.leaf, lay), _coef_vec(g.leaf, lay),
-            (kind in _SYMMETRIC_KINDS or (kind == DUDV and da == db)) and f.comp == g.comp)
+            (kind in _SYMMETRIC_KINDS or (kind in (DUDV, WDUDV) and da == db)) and f.comp == g.comp)
 
 
 def _term_scalar(term, lay):
@@ -2860,7 +2914,12 @@ class Matrix:
 
 def _integral_layout(term, mesh):
     """Layout (mesh + Lagrange degree) an integrand lives in: that of its functions / arguments on the
-    integration mesh; pure-Expression integrands are P1."""
+    integration mesh, a vector-valued one before a scalar one (which can only weight it); pure-Expression integrands are P1."""
+    for f in term.factors:
+        for leaf in (f.leaf, f.other):
+            V = getattr(leaf, "_V", None)
+            if V is not None and V.mesh() is mesh and V._ncomp > 1:
+                return V._lay
     for f in term.factors:
         for leaf in (f.leaf, f.other):
             V = getattr(leaf, "_V", None)

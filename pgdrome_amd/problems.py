@@ -301,28 +301,36 @@ def convection_diffusion(space_mesh, n_k=9, n_w=9, beta=(12.0, -5.0, 3.0), k_ran
                 PGD_nmax=PGD_nmax, PGD_tol=PGD_tol)
 
 
+def _voigt_C(nu):
+    """Isotropic elasticity tensor of unit Young's modulus in Voigt notation (strain order of _strain)."""
+    lam, mu = nu / ((1.0 + nu) * (1.0 - 2.0 * nu)), 1.0 / (2.0 * (1.0 + nu))
+    return fem.as_matrix([[lam + 2 * mu, lam, lam, 0, 0, 0], [lam, lam + 2 * mu, lam, 0, 0, 0], [lam, lam, lam + 2 * mu, 0, 0, 0],
+                          [0, 0, 0, mu, 0, 0], [0, 0, 0, 0, mu, 0], [0, 0, 0, 0, 0, mu]])
+
+
+def _strain(w):
+    """Engineering strain of a 3-D displacement in Voigt order (xx, yy, zz, yz, xz, xy)."""
+    return fem.as_vector([w[0].dx(0), w[1].dx(1), w[2].dx(2), w[1].dx(2) + w[2].dx(1), w[0].dx(2) + w[2].dx(0), w[0].dx(1) + w[1].dx(0)])
+
+
+def _clamped(x, on_boundary):
+    return on_boundary and fem.near(x[0], 0.0)
+
+
 def elastic_block(space_mesh, n_e=9, e_range=(0.5, 2.0), nu=0.3, k_found=2.0, PGD_nmax=3, PGD_tol=1e-8, degree=1, traction=None):
     """A 3-D block clamped at x = 0 on an elastic foundation under its own weight: VECTOR-valued P1 displacement u(X; e), Young's
     modulus factor e as the second PGD variable.   int eps(v) : (e C(nu)) eps(u) + k v . u dX = int g . v dX,  g = (0, 0, -1);
     u = sum_m U_m(X) W_m(e).
     (Voigt strain as in the reference's elastic test, /root/reference/tests/integration/test_solver_problem.py:59-75, which is 2-D
     and P2; this one exists to carry a vector-valued space through the row-sharded solve.)"""
-    lam, mu = nu / ((1.0 + nu) * (1.0 - 2.0 * nu)), 1.0 / (2.0 * (1.0 + nu))
-    C = fem.as_matrix([[lam + 2 * mu, lam, lam, 0, 0, 0], [lam, lam + 2 * mu, lam, 0, 0, 0], [lam, lam, lam + 2 * mu, 0, 0, 0],
-                       [0, 0, 0, mu, 0, 0], [0, 0, 0, 0, mu, 0], [0, 0, 0, 0, 0, mu]])
+    C, strain = _voigt_C(nu), _strain
     g = fem.Constant((0.0, 0.0, -1.0))
     meshes = [space_mesh, fem.IntervalMesh(n_e - 1, e_range[0], e_range[1])]
     Vs = [fem.VectorFunctionSpace(meshes[0], "CG", int(degree)), fem.FunctionSpace(meshes[1], "CG", 1)]
     param = {"e": fem.interpolate(fem.Expression("x[0]", degree=1), Vs[1])}
 
-    def strain(w):
-        return fem.as_vector([w[0].dx(0), w[1].dx(1), w[2].dx(2), w[1].dx(2) + w[2].dx(1), w[0].dx(2) + w[2].dx(0), w[0].dx(1) + w[1].dx(0)])
-
-    def clamped(x, on_boundary):
-        return on_boundary and fem.near(x[0], 0.0)
-
     def bc_fct(Vs, dom, param):
-        return [fem.DirichletBC(Vs[0], fem.Constant((0.0, 0.0, 0.0)), clamped), 0]
+        return [fem.DirichletBC(Vs[0], fem.Constant((0.0, 0.0, 0.0)), _clamped), 0]
 
     def op_form(t, j, a, b, meshes, param):
         """term t of the operator on dimension j: t = 0 the strain energy x e-weighted mass, t = 1 the foundation x mass"""
@@ -357,6 +365,54 @@ def elastic_block(space_mesh, n_e=9, e_range=(0.5, 2.0), nu=0.3, k_found=2.0, PG
 
     return dict(name="elastic_block", name_coord=["X", "e"], modes_info=["U", "Node", "Vector"], Vs=Vs, bc_fct=bc_fct, load=[],
                 param=param, rhs_fct=rhs_fct, lhs_fct=lhs_fct, probs=["x", "e"], PGD_nmax=PGD_nmax, PGD_tol=PGD_tol)
+
+
+def graded_block(space_mesh, grading, n_t=9, t_range=(0.0, 2.0), nu=0.3, k_found=2.0, degree=1, PGD_nmax=4, PGD_tol=1e-8):
+    """The block of elastic_block made of a GRADED material: Young's modulus E(X; theta) = 1 + theta g(X), with the grading
+    g a scalar field (an Expression, or a Function on FunctionSpace(space_mesh, "CG", degree)) and its amplitude theta the
+    second PGD variable (a 1-D P1 coordinate).  int eps(v) : E C(nu) eps(u) + k v . u dX = int b . v dX,  b = (0, 0, -1):
+    operator  K_1 (x) M_theta + K_g (x) Mw_theta (w = theta) + k M (x) M_theta,  K_g = int g eps(v) : C eps(u) the weighted
+    elasticity (WDUDV atoms in every block)."""
+    C = _voigt_C(nu)
+    b = fem.Constant((0.0, 0.0, -1.0))
+    meshes = [space_mesh, fem.IntervalMesh(n_t - 1, t_range[0], t_range[1])]
+    Vs = [fem.VectorFunctionSpace(meshes[0], "CG", int(degree)), fem.FunctionSpace(meshes[1], "CG", 1)]
+    param = {"theta": fem.interpolate(fem.Expression("x[0]", degree=1), Vs[1]), "grading": grading}
+
+    def bc_fct(Vs, dom, param):
+        return [fem.DirichletBC(Vs[0], fem.Constant((0.0, 0.0, 0.0)), _clamped), 0]
+
+    def op_form(t, j, u, v, meshes, param):
+        """term t on dimension j: t = 0 the unit strain energy x mass, 1 the graded one x theta-weighted mass, 2 the foundation"""
+        if j == 0:
+            if t == 2:
+                return fem.Constant(k_found) * fem.inner(u, v) * fem.dx(meshes[0])
+            energy = fem.inner(C * _strain(u), _strain(v))
+            return (energy if t == 0 else param["grading"] * energy) * fem.dx(meshes[0])
+        return (param["theta"] * u * v if t == 1 else u * v) * fem.dx(meshes[1])
+
+    def load_form(j, v, meshes):
+        return fem.dot(b, v) * fem.dx(meshes[0]) if j == 0 else v * fem.dx(meshes[1])
+
+    def lhs_fct(u, v, Fs, meshes, dom, param, typ, dim):
+        d = 0 if typ == "x" else 1
+        a = 0
+        for t in (0, 1, 2):
+            c = fem.assemble(op_form(t, 1 - d, Fs[1 - d], Fs[1 - d], meshes, param))
+            a = a + fem.Constant(c) * op_form(t, d, u, v, meshes, param)
+        return a
+
+    def rhs_fct(u, v, Fs, meshes, dom, param, Q, PGD_func, typ, nE, dim):
+        d = 0 if typ == "x" else 1
+        l = fem.Constant(fem.assemble(load_form(1 - d, Fs[1 - d], meshes))) * load_form(d, v, meshes)
+        for old in range(nE):
+            for t in (0, 1, 2):
+                c = fem.assemble(op_form(t, 1 - d, PGD_func[1 - d][old], Fs[1 - d], meshes, param))
+                l = l - fem.Constant(c) * op_form(t, d, PGD_func[d][old], v, meshes, param)
+        return l
+
+    return dict(name="graded_block", name_coord=["X", "theta"], modes_info=["U", "Node", "Vector"], Vs=Vs, bc_fct=bc_fct,
+                load=[], param=param, rhs_fct=rhs_fct, lhs_fct=lhs_fct, probs=["x", "theta"], PGD_nmax=PGD_nmax, PGD_tol=PGD_tol)
 
 
 # ----------------------------- convective (Robin) boundary: the heat-transfer coefficient h as a coordinate

@@ -137,6 +137,16 @@ int pgd_vec_dot(pgd_handle ctx, pgd_handle x, pgd_handle y, int64_t lo, int64_t 
  * Deterministic (owner-computes, no atomics).                                   */
 int pgd_atom_assemble(pgd_handle ctx, pgd_handle mesh, int kind, int da, int db,
                       pgd_handle wvec, pgd_handle *atom);
+/* The atom of pgd_atom_assemble (same kinds, weights, axis checks and kernels) over a subset of the cells:
+ * int_Omega_s ... dx, the cell-subdomain integral dx(id) of a multi-material domain.  cell_mask: nc bytes in
+ * the cell order of the upload, non-zero = the cell belongs to the subset; it is copied into a temporary
+ * device buffer that is freed before the call returns.  The atom lies on the mesh's own pattern (entries that
+ * no marked cell touches are exact zeros), so pgd_op_combine, pgd_spmv and pgd_atom_embed take it unchanged.
+ * Every cell marked: bit-identical to pgd_atom_assemble; none: all zeros.  PGD_ERR_INVALID, with no atom left
+ * behind, for nc other than the mesh's cell count, a blocked layout (pgd_atom_embed builds those from the
+ * scalar atom) or cell_mask = NULL with nc > 0.  Deterministic (owner-computes, no atomics).             */
+int pgd_atom_assemble_cells(pgd_handle ctx, pgd_handle mesh, int kind, int da, int db, pgd_handle wvec,
+                            const uint8_t *cell_mask, int64_t nc, pgd_handle *atom);
 /* Boundary mass  int_Gamma phi_i phi_j ds  over nf facets (the Robin term c*u*v*ds of a form), on the
  * mesh's own pattern: an atom like any other.  facets: nf records of nvpf node ids of the layout, the
  * facet's vertices first, then for P2 the nodes of its edges in the UFC local order - interval layouts

@@ -59,6 +59,7 @@ SIGNATURES = {
     "pgd_vec_lincomb": (C.c_int, [H, H, PH, PD, C.c_int]),
     "pgd_vec_dot": (C.c_int, [H, H, H, I64, I64, PD]),
     "pgd_atom_assemble": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PH]),
+    "pgd_atom_assemble_cells": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PU8, I64, PH]),
     "pgd_atom_assemble_facets": (C.c_int, [H, H, PI32, I64, C.c_int, PH]),
     "pgd_atom_upload": (C.c_int, [H, H, PD, PH]),
     "pgd_atom_download": (C.c_int, [H, H, PD]),
@@ -374,6 +375,17 @@ class Context:
     def atom_assemble(self, mesh, kind, da=0, db=0, w=0):
         a = H(0)
         self._ck(self.lib.pgd_atom_assemble(self.h, mesh, int(kind), int(da), int(db), int(w), C.byref(a)))
+        return a.value
+
+    def atom_assemble_cells(self, mesh, kind, da, db, w, mask):
+        """The atom of atom_assemble over the cells whose byte of `mask` (one per cell, upload order) is non-zero."""
+        mask = np.ascontiguousarray(mask)
+        if mask.ndim != 1 or mask.dtype.itemsize != 1:
+            raise ValueError("mask: one byte per cell")
+        mask = mask.view(np.uint8)
+        a = H(0)
+        self._ck(self.lib.pgd_atom_assemble_cells(self.h, mesh, int(kind), int(da), int(db), int(w),
+                                                  mask.ctypes.data_as(PU8) if mask.size else None, mask.size, C.byref(a)))
         return a.value
 
     def atom_assemble_facets(self, mesh, facets):

@@ -292,6 +292,7 @@ struct AsmArgs {
     const int4 *cells;
     const int *v2c_ptr, *v2c, *row_ptr, *cols;
     const double *w;              // vertex weights (weighted kinds)
+    const uint8_t *mask;          // cell mask of the masked instances (MASK = true): cells whose byte is 0 contribute nothing
     double *vals;
     int64_t nv;
     int kind, da, db;
@@ -426,7 +427,8 @@ __device__ __forceinline__ double p1_entry(int kind, int da, int db, int i, int 
     }
     return 0.0;
 }
-template <int D>
+// MASK (pgd_atom_assemble_cells): the contributions of cells whose mask byte is 0 are skipped, the rest summed in the same order
+template <int D, bool MASK = false>
 __global__ __launch_bounds__(TPB) void k_assemble_p1(AsmArgs A) {
     __shared__ double s_acc[ASM_CAP];
     __shared__ int s_cols[ASM_CAP];
@@ -452,6 +454,7 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1(AsmArgs A) {
         const int *rc = staged ? (s_cols + (ra - s)) : (A.cols + ra);
         const int ca = A.v2c_ptr[r], cb = A.v2c_ptr[r + 1];
         for (int k = ca; k < cb; ++k) {
+            if constexpr (MASK) { if (!A.mask[A.v2c[k]]) continue; }
             const int4 c4 = A.cells[A.v2c[k]];
             const int u[4] = {c4.x, c4.y, c4.z, c4.w};
             int i = 0;
@@ -498,6 +501,10 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1(AsmArgs A) {
 // Same values, same order of summation: bit-identical atoms.  (r04: the general kernel is bound by its gathers - a cell record per
 // visit, 24 visits per row; a table behind one more gather, the cell's type byte, was SLOWER; gather-free with the binary search into
 // the LDS image of the CSR rows: 5.6 ms at 256^3; HISTORY.md.)  Reads 4 B, writes 8 x 15 B per row.
+// MASK: cell 6 q + t (cube q, type t: the numbering k_lattice_regular_verify checks) contributes iff its mask byte is set - the six
+// bytes of an existing cube are read, nothing else.  `present` keeps following cube EXISTENCE: it places the values in the row's
+// compacted CSR entries, and a slot fed by unmarked cells alone is written as an explicit 0.0.
+template <bool MASK = false>
 __global__ __launch_bounds__(TPB) void k_assemble_p1_regular(AsmArgs A, int nz) {
     __shared__ double s_acc[TPB * 15];
     __shared__ int s_rp[TPB + 1];
@@ -539,6 +546,14 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1_regular(AsmArgs A, int nz) 
             const int ox = o & 1, oy = (o >> 1) & 1, oz = o >> 2;
             const int cx = x - ox, cy = y - oy, cz = z - oz;
             const bool have = cx >= 0 && cy >= 0 && cz >= 0 && cx < nx - 1 && cy < A.ny - 1 && cz < nz - 1;
+            bool on[6] = {true, true, true, true, true, true};
+            if constexpr (MASK) {
+                if (have) {
+                    const uint8_t *mq = A.mask + 6 * (cx + (int64_t)(nx - 1) * (cy + (int64_t)(A.ny - 1) * cz));
+#pragma unroll
+                    for (int t = 0; t < 6; ++t) on[t] = mq[t] != 0;
+                }
+            }
 #pragma unroll
             for (int t = 0; t < 6; ++t) {
                 const int i = box_local(t, o);
@@ -548,7 +563,11 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1_regular(AsmArgs A, int nz) 
                     const int cj = box_corner(t, j);
                     const int q = box_slot((cj & 1) - ox, ((cj >> 1) & 1) - oy, (cj >> 2) - oz);
                     const double val = s_loc[t * 16 + 4 * i + j];
-                    if (have) { acc[q] += val; present |= 1u << q; }
+                    if constexpr (MASK) {
+                        if (have) { if (on[t]) acc[q] += val; present |= 1u << q; }
+                    } else {
+                        if (have) { acc[q] += val; present |= 1u << q; }
+                    }
                 }
             }
         }
@@ -567,6 +586,7 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1_regular(AsmArgs A, int nz) 
 // Quadratic Lagrange elements on intervals (cell record = v0, v1, midpoint node): owner-computes like
 // the P1 kernel, local 3x3 entries by 4-point Gauss quadrature (exact to degree 7).  These systems are
 // small (time / parameter dimensions), so every lane accumulates straight into its own CSR row.
+template <bool MASK = false>
 __global__ __launch_bounds__(TPB) void k_assemble_p2_interval(AsmArgs A) {
     const double GX[4] = {0.06943184420297371, 0.33000947820757187, 0.6699905217924281, 0.9305681557970262};
     const double GW[4] = {0.17392742256872692, 0.32607257743127305, 0.32607257743127305, 0.17392742256872692};
@@ -575,6 +595,7 @@ __global__ __launch_bounds__(TPB) void k_assemble_p2_interval(AsmArgs A) {
     const int ra = A.row_ptr[r], len = A.row_ptr[r + 1] - ra;
     for (int k = 0; k < len; ++k) A.vals[ra + k] = 0.0;
     for (int k = A.v2c_ptr[r]; k < A.v2c_ptr[r + 1]; ++k) {
+        if constexpr (MASK) { if (!A.mask[A.v2c[k]]) continue; }
         const int4 c4 = A.cells[A.v2c[k]];
         const int u[3] = {c4.x, c4.y, c4.z};
         const int i = (u[0] == (int)r) ? 0 : (u[1] == (int)r) ? 1 : 2;
@@ -624,7 +645,7 @@ __constant__ double GJ_W[3][4] = {   // weight (1 - t)^alpha on [0, 1], alpha = 
 __constant__ int P2_EA[2][6] = {{1, 0, 0, 0, 0, 0}, {2, 1, 1, 0, 0, 0}};
 __constant__ int P2_EB[2][6] = {{2, 2, 1, 0, 0, 0}, {3, 3, 2, 3, 2, 1}};
 
-template <int D>
+template <int D, bool MASK = false>
 __global__ __launch_bounds__(64) void k_assemble_p2_simplex(AsmArgs A, const int *__restrict__ cellsN) {
     constexpr int NN = (D + 1) * (D + 2) / 2, NE = NN - (D + 1), NQ = (D == 2) ? 16 : 64;
     const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -633,6 +654,7 @@ __global__ __launch_bounds__(64) void k_assemble_p2_simplex(AsmArgs A, const int
     for (int k = 0; k < len; ++k) A.vals[ra + k] = 0.0;
     const bool weighted = A.kind >= PGD_ATOM_WMASS;
     for (int k = A.v2c_ptr[r]; k < A.v2c_ptr[r + 1]; ++k) {
+        if constexpr (MASK) { if (!A.mask[A.v2c[k]]) continue; }
         const int *rec = cellsN + (int64_t)A.v2c[k] * NN;
         int u[NN], i = 0;
 #pragma unroll
@@ -1159,40 +1181,92 @@ static int new_csr(Ctx *c, pgd_handle mh, Mesh *m, pgd_handle *out, Csr **res) {
     return PGD_OK;
 }
 
-int pgd_atom_assemble(pgd_handle h, pgd_handle mh, int kind, int da, int db, pgd_handle wh, pgd_handle *out) {
-    PGD_CTX(c, h);
-    Mesh *m = get_mesh(c, mh);
-    if (!m || !out) return fail(c, PGD_ERR_INVALID, "atom_assemble: invalid mesh handle");
-    if (m->ncomp != 1) return fail(c, PGD_ERR_INVALID, "atom_assemble: blocked layouts take their atoms from pgd_atom_embed");
-    if (kind < PGD_ATOM_MASS || kind > PGD_ATOM_WCONVT) return fail(c, PGD_ERR_INVALID, "atom_assemble: unknown kind %d", kind);
-    if (da < 0 || da >= m->gdim || db < 0 || db >= m->gdim) return fail(c, PGD_ERR_INVALID, "atom_assemble: derivative axis out of range");
-    const double *w = nullptr;
+// the checks of pgd_atom_assemble: *w = the weight's values (weighted kinds), nullptr otherwise
+static int atom_args(Ctx *c, Mesh *m, const char *fn, int kind, int da, int db, pgd_handle wh, const double **w) {
+    if (m->ncomp != 1) return fail(c, PGD_ERR_INVALID, "%s: blocked layouts take their atoms from pgd_atom_embed", fn);
+    if (kind < PGD_ATOM_MASS || kind > PGD_ATOM_WCONVT) return fail(c, PGD_ERR_INVALID, "%s: unknown kind %d", fn, kind);
+    if (da < 0 || da >= m->gdim || db < 0 || db >= m->gdim) return fail(c, PGD_ERR_INVALID, "%s: derivative axis out of range", fn);
+    *w = nullptr;
     if (kind >= PGD_ATOM_WMASS) {
         Vec *wv = get_vec(c, wh);
-        if (!wv || wv->n != m->nv) return fail(c, PGD_ERR_INVALID, "atom_assemble: weighted kind needs a vertex weight vector");
-        w = wv->d;
+        if (!wv || wv->n != m->nv) return fail(c, PGD_ERR_INVALID, "%s: weighted kind needs a vertex weight vector", fn);
+        *w = wv->d;
     }
-    Csr *a = nullptr;
-    PGD_TRY(new_csr(c, mh, m, out, &a));
+    return PGD_OK;
+}
+
+// the assembly kernel of the layout into the zero-filled atom `a`; mask != nullptr: the masked instance of the same kernel
+static void launch_assembly(Ctx *c, Mesh *m, Csr *a, int kind, int da, int db, const double *w, const uint8_t *mask) {
     AsmArgs A;
     A.cx = m->coords; A.cy = m->coords + m->nv; A.cz = m->coords + 2 * m->nv;
     A.cells = m->cells; A.v2c_ptr = m->v2c_ptr; A.v2c = m->v2c; A.row_ptr = m->row_ptr; A.cols = m->cols;
-    A.w = w; A.vals = a->vals; A.nv = m->nv; A.kind = kind; A.da = da; A.db = db;
+    A.w = w; A.mask = mask; A.vals = a->vals; A.nv = m->nv; A.kind = kind; A.da = da; A.db = db;
     A.lattice = (m->lattice && c->asm_lattice) ? 1 : 0;
     for (int k = 0; k < 3; ++k) { A.lat_h[k] = m->lat_h[k]; A.lat_inv[k] = m->lattice ? 1.0 / m->lat_h[k] : 0.0; }
     // (PGD_TUNE_ASM_LATTICE = 2: steps from the coordinates, the r03 form; 3: steps from the indices, in the general kernel)
     A.lat_unit = (A.lattice && m->lattice_unit && (c->asm_lattice == 1 || c->asm_lattice == 3)) ? 1 : 0;
     A.nx = m->sym_nx; A.ny = m->sym_ny;
-    const int gb = (int)((m->nv + TPB - 1) / TPB);
-    if (m->cellsN && m->gdim == 2) k_assemble_p2_simplex<2><<<(int)((m->nv + 63) / 64), 64, 0, c->stream>>>(A, m->cellsN);
-    else if (m->cellsN) k_assemble_p2_simplex<3><<<(int)((m->nv + 63) / 64), 64, 0, c->stream>>>(A, m->cellsN);
-    else if (m->gdim == 1 && m->nvpc == 3) k_assemble_p2_interval<<<gb, TPB, 0, c->stream>>>(A);
-    else if (m->gdim == 1) k_assemble_p1<1><<<gb, TPB, 0, c->stream>>>(A);
-    else if (m->gdim == 2) k_assemble_p1<2><<<gb, TPB, 0, c->stream>>>(A);
-    else if (A.lat_unit && m->lattice_regular && !w && c->asm_lattice == 1 && m->max_row <= 15)
-        k_assemble_p1_regular<<<gb, TPB, 0, c->stream>>>(A, (int)(m->nv / ((int64_t)m->sym_nx * m->sym_ny)));
-    else k_assemble_p1<3><<<gb, TPB, 0, c->stream>>>(A);
+    const int gb = (int)((m->nv + TPB - 1) / TPB), g64 = (int)((m->nv + 63) / 64);
+    const bool regular = A.lat_unit && m->lattice_regular && !w && c->asm_lattice == 1 && m->max_row <= 15;
+    const int nz = regular ? (int)(m->nv / ((int64_t)m->sym_nx * m->sym_ny)) : 0;
+    if (!mask) {
+        if (m->cellsN && m->gdim == 2) k_assemble_p2_simplex<2><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
+        else if (m->cellsN) k_assemble_p2_simplex<3><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
+        else if (m->gdim == 1 && m->nvpc == 3) k_assemble_p2_interval<<<gb, TPB, 0, c->stream>>>(A);
+        else if (m->gdim == 1) k_assemble_p1<1><<<gb, TPB, 0, c->stream>>>(A);
+        else if (m->gdim == 2) k_assemble_p1<2><<<gb, TPB, 0, c->stream>>>(A);
+        else if (regular) k_assemble_p1_regular<<<gb, TPB, 0, c->stream>>>(A, nz);
+        else k_assemble_p1<3><<<gb, TPB, 0, c->stream>>>(A);
+    } else {
+        if (m->cellsN && m->gdim == 2) k_assemble_p2_simplex<2, true><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
+        else if (m->cellsN) k_assemble_p2_simplex<3, true><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
+        else if (m->gdim == 1 && m->nvpc == 3) k_assemble_p2_interval<true><<<gb, TPB, 0, c->stream>>>(A);
+        else if (m->gdim == 1) k_assemble_p1<1, true><<<gb, TPB, 0, c->stream>>>(A);
+        else if (m->gdim == 2) k_assemble_p1<2, true><<<gb, TPB, 0, c->stream>>>(A);
+        else if (regular) k_assemble_p1_regular<true><<<gb, TPB, 0, c->stream>>>(A, nz);
+        else k_assemble_p1<3, true><<<gb, TPB, 0, c->stream>>>(A);
+    }
+}
+
+int pgd_atom_assemble(pgd_handle h, pgd_handle mh, int kind, int da, int db, pgd_handle wh, pgd_handle *out) {
+    PGD_CTX(c, h);
+    Mesh *m = get_mesh(c, mh);
+    if (!m || !out) return fail(c, PGD_ERR_INVALID, "atom_assemble: invalid mesh handle");
+    const double *w = nullptr;
+    PGD_TRY(atom_args(c, m, "atom_assemble", kind, da, db, wh, &w));
+    Csr *a = nullptr;
+    PGD_TRY(new_csr(c, mh, m, out, &a));
+    launch_assembly(c, m, a, kind, da, db, w, nullptr);
     PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+int pgd_atom_assemble_cells(pgd_handle h, pgd_handle mh, int kind, int da, int db, pgd_handle wh, const uint8_t *cell_mask, int64_t nc,
+                            pgd_handle *out) {
+    PGD_CTX(c, h);
+    Mesh *m = get_mesh(c, mh);
+    if (!m || !out) return fail(c, PGD_ERR_INVALID, "atom_assemble_cells: invalid mesh handle");
+    const double *w = nullptr;
+    PGD_TRY(atom_args(c, m, "atom_assemble_cells", kind, da, db, wh, &w));
+    if (nc != m->nc) return fail(c, PGD_ERR_INVALID, "atom_assemble_cells: the mask has %lld bytes, the mesh %lld cells", (long long)nc, (long long)m->nc);
+    if (nc > 0 && !cell_mask) return fail(c, PGD_ERR_INVALID, "atom_assemble_cells: no cell mask");
+    struct Scratch {                                                   // the device copy of the mask, released on every way out
+        void *p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } tmp;
+    PGD_TRY(dev_alloc(c, &tmp.p, (size_t)(nc > 0 ? nc : 1)));
+    hipStream_t st = c->stream;
+    if (nc > 0) PGD_HIP(c, hipMemcpyAsync(tmp.p, cell_mask, (size_t)nc, hipMemcpyHostToDevice, st));
+    Csr *a = nullptr;
+    PGD_TRY(new_csr(c, mh, m, out, &a));                               // zero-filled, immutable: an atom like any assembled one
+    launch_assembly(c, m, a, kind, da, db, w, (const uint8_t *)tmp.p);
+    const hipError_t launched = hipGetLastError();
+    const hipError_t synced = hipStreamSynchronize(st);                // (the mask is read before it is freed)
+    if (launched != hipSuccess || synced != hipSuccess) {
+        (void)free_obj(c, *out, Obj::CSR);                             // the half-built atom goes
+        *out = 0;
+        return fail(c, PGD_ERR_HIP, "atom_assemble_cells: %s", hipGetErrorString(launched != hipSuccess ? launched : synced));
+    }
     return PGD_OK;
 }
 
@@ -1248,7 +1322,7 @@ int pgd_atom_assemble_facets(pgd_handle h, pgd_handle mh, const int32_t *facets,
     AsmArgs A;
     A.cx = m->coords; A.cy = m->coords + nv; A.cz = m->coords + 2 * nv;
     A.cells = nullptr; A.v2c_ptr = nullptr; A.v2c = nullptr; A.row_ptr = m->row_ptr; A.cols = m->cols;
-    A.w = nullptr; A.vals = a->vals; A.nv = nv; A.kind = PGD_ATOM_MASS; A.da = 0; A.db = 0;
+    A.w = nullptr; A.mask = nullptr; A.vals = a->vals; A.nv = nv; A.kind = PGD_ATOM_MASS; A.da = 0; A.db = 0;
     A.lattice = (m->lattice && c->asm_lattice) ? 1 : 0;
     for (int k = 0; k < 3; ++k) { A.lat_h[k] = m->lat_h[k]; A.lat_inv[k] = m->lattice ? 1.0 / m->lat_h[k] : 0.0; }
     A.lat_unit = 0; A.nx = m->sym_nx; A.ny = m->sym_ny;

@@ -28,6 +28,7 @@ explicitly with ``set_backend``.
 """
 from __future__ import annotations
 
+import itertools
 import logging
 import math
 import numbers
@@ -306,6 +307,7 @@ class DofLayout:
         self.n = self.coords.shape[0]
         self._handles, self._atoms, self._atom_weights = {}, {}, {}
         self._facet_atoms = {}
+        self._cell_atoms = {}        # cell-subdomain atoms: _atom_key + (cell-set key,) -> (atom, weakref to the MeshFunction, to the weight)
         self._ones = self._space = None
 
     def _init_p2_slab(self, mesh):
@@ -448,11 +450,13 @@ class DofLayout:
         wkey = None if weight is None else (id(weight), weight.version)
         return (id(be), kind, da if kind in _DA_KINDS else 0, db if kind in _DB_KINDS else 0, wkey)
 
-    def atom(self, kind, da=0, db=0, weight=None):
+    def atom(self, kind, da=0, db=0, weight=None, cells=None):
         """Cached device atom; weighted atoms are keyed by the weight's identity + version, the identity checked through
         a weak reference: an address (``id``) is reused as soon as a vector dies, and an iterate can end up as the weight
-        of a functional (``assemble(E * F * F * dx)`` with E and F equally "old")."""
+        of a functional (``assemble(E * F * F * dx)`` with E and F equally "old").  cells: the _CellSet of a dx(id) measure."""
         be = get_backend()
+        if cells is not None:
+            return self._cell_atom(be, kind, da, db, weight, cells)
         if kind in (WDUDV, WCONV, WCONVT) and self.part is not None:
             raise NotImplementedError("weighted derivative atoms on a sharded (slab) layout")
         key = self._atom_key(be, kind, da, db, weight)
@@ -497,6 +501,42 @@ class DofLayout:
         stale = self._atoms.pop(key)
         self._atom_weights.pop(key, None)
         _purge_atom(stale)       # the library recycles handle numbers: forget everything keyed by it
+        be.atom_free(stale)
+
+    def _cell_atom(self, be, kind, da, db, weight, cells):
+        """The atom over the cells of a dx(id) measure (pgd_atom_assemble_cells), cached per backend, kind, (da, db), weight and
+        cell set.  A cell set is keyed by the generation of its MeshFunction's markers (_cell_generation): the atoms of older
+        generations of the same MeshFunction, of MeshFunctions that died and of stale weights are freed here, with the
+        vector-valued embeddings built from them."""
+        if self.part is not None:
+            raise NotImplementedError("cell-subdomain integrals dx(id) on a sharded (slab) layout")
+        fn = getattr(be, "atom_cells", None)
+        if fn is None:
+            raise NotImplementedError("cell-subdomain integrals dx(id) need a backend that assembles masked atoms (atom_cells); "
+                                      "%r has none" % (getattr(be, "name", type(be).__name__),))
+        key = self._atom_key(be, kind, da, db, weight) + (cells.key,)
+        hit = self._cell_atoms.get(key)
+        if hit is not None and hit[1]() is cells.mf and (weight is None or hit[2]() is weight):
+            return hit[0]
+        for k, (a, mref, wref) in list(self._cell_atoms.items()):
+            if k[0] != id(be):
+                continue
+            mf = mref()
+            stale_cells = mf is None or (mf is cells.mf and k[5][0] != cells.gen)
+            stale_w = k[4] is not None and (wref() is None or (weight is not None and k[4][0] == id(weight) and
+                                                                (wref() is not weight or k[4][1] < weight.version)))
+            if k == key or stale_cells or stale_w:
+                self._drop_cell_atom(be, k)
+        a = fn(self.handle(), key[1], key[2], key[3], weight.dev() if weight is not None else 0, cells.mask())
+        self._cell_atoms[key] = (a, weakref.ref(cells.mf), weakref.ref(weight) if weight is not None else (lambda: None))
+        return a
+
+    def _drop_cell_atom(self, be, key):
+        stale = self._cell_atoms.pop(key)[0]
+        for blk in list(self.mesh._layouts.values()):
+            if isinstance(blk, BlockLayout) and blk.base is self:
+                blk._drop_derived(be, stale)
+        _purge_atom(stale)
         be.atom_free(stale)
 
 
@@ -693,6 +733,7 @@ class BlockLayout:
         self.vertex_nodes = base.vertex_nodes
         self._handles, self._atoms = {}, {}
         self._watoms = {}            # weighted: base atom key + (cv, cu) -> (embedded atom, scalar source, weakref to the weight)
+        self._catoms = {}            # cell-subdomain: (backend, scalar source, cv, cu) -> embedded atom (freed with the source)
         self._ones = self._space = None
 
     @property
@@ -736,9 +777,22 @@ class BlockLayout:
             self._handles[id(be)] = h
         return h
 
-    def atom(self, kind, da=0, db=0, weight=None, cv=None, cu=None):
+    def atom(self, kind, da=0, db=0, weight=None, cv=None, cu=None, cells=None):
         """Scalar atom (kind, da, db) in block (cv, cu); cv = cu = None: in every diagonal block (norms).  A weight is a
-        scalar field of the base layout (_coef_vec(..., weight=True)): the scalar weighted atom, embedded."""
+        scalar field of the base layout (_coef_vec(..., weight=True)): the scalar weighted atom, embedded.  cells: the
+        _CellSet of a dx(id) measure - the base layout's masked atom, embedded."""
+        if cells is not None:
+            if self.part is not None:
+                raise NotImplementedError("cell-subdomain integrals dx(id) on a sharded (slab) vector-valued layout")
+            if weight is not None and weight.size() != self.base.n:
+                raise NotImplementedError("a weight on a vector-valued space is a scalar field of its Lagrange degree")
+            be = get_backend()
+            src = self.base.atom(kind, da, db, weight, cells=cells)     # (frees stale sources, and their embeddings with them)
+            key = (id(be), src, cv, cu)
+            a = self._catoms.get(key)
+            if a is None:
+                a = self._catoms[key] = self._embed(be, src, cv, cu)
+            return a
         if weight is None:
             return self._embedded(self.base.atom(kind, da, db), cv, cu)
         if self.part is not None:
@@ -773,6 +827,13 @@ class BlockLayout:
         if self.part is not None:
             raise NotImplementedError("bilinear ds terms (Robin atoms) on a sharded (slab) layout")
         return self._embedded(self.base.facet_atom(ids), cv, cu)
+
+    def _drop_derived(self, be, src):
+        """Free the embeddings of a scalar cell-subdomain atom that its base layout frees."""
+        for k in [k for k in self._catoms if k[0] == id(be) and k[1] == src]:
+            a = self._catoms.pop(k)
+            _purge_atom(a)
+            be.atom_free(a)
 
     def _embedded(self, src, cv, cu):
         be = get_backend()
@@ -1433,14 +1494,15 @@ dot = inner
 
 
 class Measure:
-    """dx: cell integrals over a whole mesh.  ds: exterior-facet integrals, optionally restricted to the
-    facets a MeshFunction marks with ``subdomain_id`` (``ds(2)``)."""
+    """dx: cell integrals over a whole mesh, or over the cells a cell MeshFunction marks with ``subdomain_id``
+    (``dx(1)`` of ``Measure("dx", domain=mesh, subdomain_data=cf)``; data without an id: the whole mesh).  ds:
+    exterior-facet integrals, optionally restricted to the facets a MeshFunction marks with ``subdomain_id`` (``ds(2)``)."""
 
     def __init__(self, kind="dx", domain=None, subdomain_data=None, subdomain_id=None):
         if kind not in ("dx", "ds"):
             raise NotImplementedError("Measure %r: cell integrals dx and exterior-facet integrals ds" % (kind,))
-        if kind == "dx" and (subdomain_id is not None or subdomain_data is not None):
-            raise NotImplementedError("cell-subdomain integrals dx(id)")
+        if kind == "dx":
+            subdomain_id = _check_cell_subdomain(domain, subdomain_data, subdomain_id)
         self.kind, self.mesh = kind, domain
         self.subdomain_data, self.subdomain_id = subdomain_data, subdomain_id
         if self.mesh is None and subdomain_data is not None:
@@ -1452,14 +1514,41 @@ class Measure:
         for a in args:
             if isinstance(a, Mesh):
                 mesh = a
-            elif isinstance(a, numbers.Integral) and self.kind == "ds":
+            elif isinstance(a, numbers.Integral):
                 sid = int(a)
+            elif isinstance(a, (tuple, list, numbers.Real)) and self.kind == "dx":
+                sid = a                          # (refused by _check_cell_subdomain)
             elif a is not None:
-                raise NotImplementedError("dx(subdomain id)")
+                raise NotImplementedError("%s(%r)" % (self.kind, a))
         return Measure(self.kind, mesh, data, sid)
 
     def __rmul__(self, o):
         return Form([(t, self) for t in _as_poly(o)])
+
+
+def _check_cell_subdomain(domain, data, sid):
+    """The subdomain arguments of a dx measure: a cell MeshFunction with integer values of the integration mesh and an
+    integer id (or no id: the whole mesh).  Returns the id as an int."""
+    if isinstance(sid, (tuple, list)):
+        raise NotImplementedError("dx over a tuple of subdomain ids (write one integral per id)")
+    if sid is not None:
+        if not isinstance(sid, numbers.Integral) or isinstance(sid, bool):
+            raise ValueError("dx: the subdomain id must be an integer, got %r" % (sid,))
+        if data is None:
+            raise ValueError("dx(%r) without subdomain_data (a cell MeshFunction)" % (sid,))
+        sid = int(sid)
+    if data is not None:
+        if not isinstance(data, MeshFunction):
+            raise ValueError("dx: subdomain_data must be a cell MeshFunction, got %r" % (type(data).__name__,))
+        mesh = data.mesh()
+        if data.dim() != mesh.topology().dim():
+            raise ValueError("dx: subdomain_data marks entities of dimension %d, not the cells (%d)"
+                             % (data.dim(), mesh.topology().dim()))
+        if domain is not None and domain is not mesh:
+            raise ValueError("dx: subdomain_data belongs to another mesh than the measure's domain")
+        if data.array().dtype.kind not in "iu":
+            raise ValueError("dx: subdomain_data must hold integer values, not %s" % (data.array().dtype,))
+    return sid
 
 
 dx = Measure("dx")
@@ -2207,10 +2296,11 @@ def _bc_vertices(bcs):
 class _AtomRef:
     """One atom of one mesh with a scalar coefficient; on a vector-valued space the atom sits in the block
     (test component cv, trial component cu)."""
-    __slots__ = ("coef", "kind", "da", "db", "weight", "cv", "cu")
+    __slots__ = ("coef", "kind", "da", "db", "weight", "cv", "cu", "cells")
 
-    def __init__(self, coef, kind, da=0, db=0, weight=None, cv=None, cu=None):
+    def __init__(self, coef, kind, da=0, db=0, weight=None, cv=None, cu=None, cells=None):
         self.coef, self.kind, self.da, self.db, self.weight, self.cv, self.cu = coef, kind, da, db, weight, cv, cu
+        self.cells = cells           # the _CellSet of a dx(id) integral, None: the whole mesh
 
     def _wkey(self):
         # (the facet set of a DS_MASS atom by its contents: every assemble() of the same ds(tag) builds a new one)
@@ -2220,17 +2310,18 @@ class _AtomRef:
 
     def key(self):
         return (self.kind, self.da if self.kind in _DA_KINDS else 0, self.db if self.kind in _DB_KINDS else 0,
-                self._wkey(), self.cv or 0, self.cu or 0)
+                self._wkey(), self.cv or 0, self.cu or 0, self.cells.key if self.cells is not None else None)
 
     def transposed_key(self):
         kind = {CONV: CONVT, CONVT: CONV, WCONV: WCONVT, WCONVT: WCONV}.get(self.kind, self.kind)
-        da, db = self.key()[1], self.key()[2]
-        return (kind, db, da, self._wkey(), self.cu or 0, self.cv or 0)
+        k = self.key()
+        return (kind, k[2], k[1], k[3], k[5], k[4], k[6])
 
 
-def _lay_atom(lay, kind, da, db, w, cv=None, cu=None):
+def _lay_atom(lay, kind, da, db, w, cv=None, cu=None, cells=None):
     """Atom of a layout; on a vector-valued layout in block (cv, cu), a side without a vector-valued factor
-    (the all-ones function of a functional) using component 0.  DS_MASS: w is the _FacetSet of the ds measure."""
+    (the all-ones function of a functional) using component 0.  DS_MASS: w is the _FacetSet of the ds measure.
+    cells: the _CellSet of a dx(id) measure (None: the whole mesh)."""
     if kind == DS_MASS:
         if isinstance(lay, BlockLayout):
             return lay.facet_atom(w.ids, cv or 0, cu or 0)
@@ -2238,10 +2329,10 @@ def _lay_atom(lay, kind, da, db, w, cv=None, cu=None):
             raise ValueError("component of a vector-valued function in an integrand over a scalar space")
         return lay.facet_atom(w.ids)
     if isinstance(lay, BlockLayout):
-        return lay.atom(kind, da, db, w, cv or 0, cu or 0)
+        return lay.atom(kind, da, db, w, cv or 0, cu or 0, cells=cells)
     if cv is not None or cu is not None:
         raise ValueError("component of a vector-valued function in an integrand over a scalar space")
-    return lay.atom(kind, da, db, w)
+    return lay.atom(kind, da, db, w, cells=cells)
 
 
 def _coef_vec(leaf, lay, weight=False):
@@ -2351,6 +2442,9 @@ def _purge_atom(atom):
         del _MV_CACHE[k]
     for k in [k for k in _SCALAR_MEMO if k[0] == atom]:
         del _SCALAR_MEMO[k]
+    for tag, plan in list(_FUNCTIONAL_PLANS.items()):
+        if any(e[1] == atom for e in plan):
+            _FUNCTIONAL_PLANS[tag] = [e for e in plan if e[1] != atom]
 
 
 def _matvec_cached(lay, atom, g):
@@ -2685,8 +2779,9 @@ def _ones(lay):
     return lay._ones
 
 
-def _term_operands(term, lay):
-    """(atom, f, g, symmetric) with  integral of the term = coef * f^T A g  for a term without arguments."""
+def _term_operands(term, lay, cells=None):
+    """(atom, f, g, symmetric) with  integral of the term = coef * f^T A g  for a term without arguments (over the cells of
+    a dx(id) measure: `cells`)."""
     test, trial, coefs, gd = _classify(term, lay)
     if test is not None or trial is not None:
         raise ValueError("scalar assemble of a form with arguments")
@@ -2697,17 +2792,17 @@ def _term_operands(term, lay):
             raise NotImplementedError("weighted inner(grad, grad) functional with several weights")
         f, g = _coef_vec(gd.leaf, lay), _coef_vec(gd.other, lay)
         if coefs:
-            atom = lay.atom(WSTIFF, 0, 0, _coef_vec(coefs[0].leaf, lay))
+            atom = lay.atom(WSTIFF, 0, 0, _coef_vec(coefs[0].leaf, lay), cells=cells)
         else:
-            atom = lay.atom(STIFF)
+            atom = lay.atom(STIFF, cells=cells)
         return atom, f, g, True
     if len(coefs) == 0:
         one = _ones(lay)
-        return _lay_atom(lay, MASS, 0, 0, None), one, one, False
+        return _lay_atom(lay, MASS, 0, 0, None, cells=cells), one, one, False
     if len(coefs) == 1:
         c = coefs[0]
         kind, da, db, w = _atom_for(Factor(None, None), Factor(None, c.deriv), [], lay)
-        return _lay_atom(lay, kind, da, db, w, None, c.comp), _ones(lay), _coef_vec(c.leaf, lay), False
+        return _lay_atom(lay, kind, da, db, w, None, c.comp, cells), _ones(lay), _coef_vec(c.leaf, lay), False
     # f (test side) is the first factor, g (trial side) the second, further undifferentiated ones weight
     der = [c for c in coefs if c.deriv is not None]
     plain = [c for c in coefs if c.deriv is None]
@@ -2718,12 +2813,12 @@ def _term_operands(term, lay):
     ordered = der + plain
     f, g, rest = ordered[0], ordered[1], ordered[2:]
     kind, da, db, w = _atom_for(Factor(None, f.deriv), Factor(None, g.deriv), rest, lay)
-    return (_lay_atom(lay, kind, da, db, w, f.comp, g.comp), _coef_vec(f.leaf, lay), _coef_vec(g.leaf, lay),
+    return (_lay_atom(lay, kind, da, db, w, f.comp, g.comp, cells), _coef_vec(f.leaf, lay), _coef_vec(g.leaf, lay),
             (kind in _SYMMETRIC_KINDS or (kind in (DUDV, WDUDV) and da == db)) and f.comp == g.comp)
 
 
-def _term_scalar(term, lay):
-    atom, f, g, symmetric = _term_operands(term, lay)
+def _term_scalar(term, lay, cells=None):
+    atom, f, g, symmetric = _term_operands(term, lay, cells)
     return term.coef * _bilinear_scalar(lay, atom, f, g, symmetric=symmetric)
 
 
@@ -2799,8 +2894,8 @@ def _fast_scalar(form):
     return _bilinear_scalar(lay, atom, f, g, symmetric=sym)
 
 
-def _term_vector(term, lay):
-    """(coef, atom handle, coefficient Vector g) with  b += coef * A g."""
+def _term_vector(term, lay, cells=None):
+    """(coef, atom handle, coefficient Vector g) with  b += coef * A g  (A over the cells of a dx(id) measure: `cells`)."""
     test, trial, coefs, gd = _classify(term, lay)
     if trial is not None:
         raise ValueError("linear form with a trial function")
@@ -2814,12 +2909,12 @@ def _term_vector(term, lay):
             raise ValueError("two test functions in one integrand")
         if len(coefs) > 1:
             raise NotImplementedError("several weights on inner(grad, grad)")
-        atom = lay.atom(WSTIFF, 0, 0, _coef_vec(coefs[0].leaf, lay)) if coefs else lay.atom(STIFF)
+        atom = lay.atom(WSTIFF, 0, 0, _coef_vec(coefs[0].leaf, lay), cells=cells) if coefs else lay.atom(STIFF, cells=cells)
         return term.coef, atom, _coef_vec(b, lay)
     if test is None:
         raise ValueError("linear form without a test function")
     if not coefs:
-        return term.coef, _lay_atom(lay, MASS, 0, 0, None, test.comp, None), _ones(lay)
+        return term.coef, _lay_atom(lay, MASS, 0, 0, None, test.comp, None, cells), _ones(lay)
     der = [c for c in coefs if c.deriv is not None]
     plain = [c for c in coefs if c.deriv is None]
     if len(der) > 1:
@@ -2830,10 +2925,10 @@ def _term_vector(term, lay):
     ordered = der + plain
     g, rest = ordered[0], ordered[1:]
     kind, da, db, w = _atom_for(test, Factor(None, g.deriv), rest, lay)
-    return term.coef, _lay_atom(lay, kind, da, db, w, test.comp, g.comp), _coef_vec(g.leaf, lay)
+    return term.coef, _lay_atom(lay, kind, da, db, w, test.comp, g.comp, cells), _coef_vec(g.leaf, lay)
 
 
-def _term_matrix(term, lay):
+def _term_matrix(term, lay, cells=None):
     test, trial, coefs, gd = _classify(term, lay)
     if gd is not None:
         a, b = gd.leaf, gd.other
@@ -2844,11 +2939,11 @@ def _term_matrix(term, lay):
         if len(coefs) > 1 or (coefs and coefs[0].deriv is not None):
             raise NotImplementedError("several / differentiated weights on inner(grad, grad)")
         w = _coef_vec(coefs[0].leaf, lay) if coefs else None
-        return _AtomRef(term.coef, WSTIFF if w is not None else STIFF, 0, 0, w)
+        return _AtomRef(term.coef, WSTIFF if w is not None else STIFF, 0, 0, w, cells=cells)
     if test is None or trial is None:
         raise ValueError("bilinear form needs a trial and a test function")
     kind, da, db, w = _atom_for(test, trial, coefs, lay)
-    return _AtomRef(term.coef, kind, da, db, w, test.comp, trial.comp)
+    return _AtomRef(term.coef, kind, da, db, w, test.comp, trial.comp, cells)
 
 
 class AssembledVector(Vector):
@@ -2889,7 +2984,7 @@ class Matrix:
         """Atoms with equal keys summed: (handles, coefs)."""
         acc = {}
         for r in self.refs:
-            h = _lay_atom(self.lay, r.kind, r.da, r.db, r.weight, r.cv, r.cu)
+            h = _lay_atom(self.lay, r.kind, r.da, r.db, r.weight, r.cv, r.cu, r.cells)
             acc[h] = acc.get(h, 0.0) + r.coef
         return list(acc), [acc[h] for h in acc]
 
@@ -2932,8 +3027,8 @@ def assemble(form, tensor=None, **kw):
     """Scalar, vector or matrix of a Form - dolfin.assemble."""
     if isinstance(form, numbers.Real):
         return float(form)
-    if type(form) is _FastForm and form.measure.kind == "dx":
-        return _fast_scalar(form)
+    if type(form) is _FastForm and form.measure.kind == "dx" and form.measure.subdomain_id is None:
+        return _fast_scalar(form)            # (its plans know meshes, not cell sets: dx(id) takes the general path)
     rank = form.rank()
     if rank == 0:
         total = 0.0
@@ -2942,7 +3037,8 @@ def assemble(form, tensor=None, **kw):
             if m.kind == "ds":
                 total += _ds_scalar(t, _integral_layout(t, mesh), m)
             else:
-                total += _term_scalar(t, _integral_layout(t, mesh))
+                lay = _integral_layout(t, mesh)
+                total += _term_scalar(t, lay, _dx_cells(lay, m))
         return total
     mesh = form.mesh()
     V = _argument_space(form, 0)
@@ -2950,7 +3046,48 @@ def assemble(form, tensor=None, **kw):
         out = AssembledVector(V)
         _assemble_vector_into(form, V._lay, out)
         return out
-    return Matrix(V, [_ds_matrix(t, V._lay, m) if m.kind == "ds" else _term_matrix(t, V._lay) for t, m in form.integrals])
+    return Matrix(V, [_ds_matrix(t, V._lay, m) if m.kind == "ds" else _term_matrix(t, V._lay, _dx_cells(V._lay, m))
+                      for t, m in form.integrals])
+
+
+# cell-subdomain integrals dx(id): the atoms of the marked cells (pgd_atom_assemble_cells), cached with the layout per cell
+# set.  A cell set is named by the GENERATION of its MeshFunction's markers: every lookup compares the live markers with the
+# snapshot taken when they were last seen (one vectorised pass, like the facet selection of ds(tag) on every call) and a
+# change of any kind - set_all, item assignment, SubDomain.mark, a write into array() - starts a new generation, whose atoms
+# are built afresh; unchanged markers find the atoms already assembled.
+_CELL_GENERATIONS = itertools.count(1)
+
+
+def _cell_generation(mf):
+    a = mf.array()
+    snap = getattr(mf, "_cells_snapshot", None)
+    if snap is None or snap.shape != a.shape or snap.dtype != a.dtype or not np.array_equal(snap, a):
+        mf._cells_snapshot = a.copy()
+        mf._cells_generation = next(_CELL_GENERATIONS)
+    return mf._cells_generation
+
+
+class _CellSet:
+    """The cells of one dx(id) measure: MeshFunction, generation of its markers and id; keyed by (generation, id)."""
+    __slots__ = ("mf", "gen", "sid", "key")
+
+    def __init__(self, mf, sid):
+        self.mf, self.sid = mf, int(sid)
+        self.gen = _cell_generation(mf)
+        self.key = (self.gen, self.sid)
+
+    def mask(self):
+        """One byte per cell (1: marked), from the snapshot of this generation."""
+        return (self.mf._cells_snapshot == self.sid).view(np.uint8)
+
+
+def _dx_cells(lay, measure):
+    """The _CellSet of a dx measure on the layout's mesh; None for the whole mesh (no subdomain id)."""
+    if measure.subdomain_id is None:
+        return None
+    if measure.subdomain_data.mesh() is not lay.mesh:
+        raise ValueError("dx: subdomain_data belongs to another mesh than the integrand")
+    return _CellSet(measure.subdomain_data, measure.subdomain_id)
 
 
 # exterior-facet integrals.  Loads - a constant times one (component of a) test function:  int_Gamma N_i ds  is computed ON THE
@@ -3166,7 +3303,7 @@ def _argument_space(form, number):
 
 def _assemble_vector_into(form, lay, out):
     """out = sum_s c_s A_s g_s.  Small systems on the host mirror, large ones by axpy on the device."""
-    pieces = [_ds_vector(t, lay, m) if m.kind == "ds" else _term_vector(t, lay) for t, m in form.integrals]
+    pieces = [_ds_vector(t, lay, m) if m.kind == "ds" else _term_vector(t, lay, _dx_cells(lay, m)) for t, m in form.integrals]
     merged = {}
     for c, atom, g in pieces:
         key = (atom, id(g))

@@ -486,6 +486,79 @@ def robin_heat(space_mesh, n_h=17, h_range=(0.1, 100.0), k=1.0, f=1.0, u_inf=0.5
                 PGD_nmax=PGD_nmax, PGD_tol=PGD_tol)
 
 
+# ----------------------------- two materials: the conductivity of an inclusion as a coordinate
+OUTSIDE, INCLUSION = 1, 2    # cell markers of inclusion_heat
+
+
+def inclusion_heat(space_mesh, n_k=17, k_range=(0.1, 10.0), f=1.0, center=None, radius=None, PGD_nmax=10, PGD_tol=1e-8):
+    """-div(k grad u) = f in Omega, u = 0 on the whole boundary, with k = 1 outside a ball (a disk in 2-D) and k = kappa
+    inside it, u = u(x; kappa) with kappa a separated 1-D P1 coordinate.  The ball - by default centred in the bounding box,
+    radius a quarter of its smallest side - is marked on a cell MeshFunction (INCLUSION, every other cell OUTSIDE) that
+    ``dom_fct`` returns; the callbacks integrate over its subdomains with dx(OUTSIDE) / dx(INCLUSION) of the ``dom`` they
+    are given, as a PGDrome user writes a multi-material problem.  Operator  K_out (x) M_kappa + K_in (x) Mw_kappa
+    (w = kappa), K_out / K_in the stiffness over the cells of each material; load  f 1_x (x) 1_kappa."""
+    X = space_mesh.coordinates()
+    lo, hi = X.min(axis=0), X.max(axis=0)
+    c = 0.5 * (lo + hi) if center is None else [float(t) for t in center]
+    r = 0.25 * float((hi - lo).min()) if radius is None else float(radius)
+    k_mesh = fem.IntervalMesh(n_k - 1, k_range[0], k_range[1])
+    meshes = [space_mesh, k_mesh]
+    Vs = [fem.FunctionSpace(space_mesh, "CG", 1), fem.FunctionSpace(k_mesh, "CG", 1)]
+    load = [[fem.interpolate(fem.Expression("%r" % float(f), degree=1), Vs[0])],
+            [fem.interpolate(fem.Expression("1.0", degree=1), Vs[1])]]
+    kappa = fem.interpolate(fem.Expression("x[0]", degree=1), Vs[1])
+
+    class _Inclusion(fem.SubDomain):
+        def inside(self, x, on_boundary):
+            d2 = 0.0
+            for k in range(len(c)):
+                d2 = d2 + (x[k] - c[k]) ** 2
+            return d2 <= r * r * (1.0 + 1e-12)
+
+    markers = fem.MeshFunction("size_t", space_mesh, space_mesh.topology().dim(), OUTSIDE)
+    _Inclusion().mark(markers, INCLUSION)
+    param = {"kappa": kappa, "markers": markers, "center": c, "radius": r, "f": float(f)}
+
+    def dom_fct(Vs, param):
+        return param["markers"]
+
+    def bc_fct(Vs, dom, param):
+        return [fem.DirichletBC(Vs[0], 0, _on_boundary), 0]
+
+    def lhs_fct(u, v, Fs, meshes, dom, param, typ, dim):
+        dxs, kap = fem.Measure("dx", domain=meshes[0], subdomain_data=dom), param["kappa"]
+        if typ == "x":
+            return (fem.Constant(fem.assemble(Fs[1] * Fs[1] * fem.dx(meshes[1])))
+                    * fem.inner(fem.grad(u), fem.grad(v)) * dxs(OUTSIDE)
+                    + fem.Constant(fem.assemble(kap * Fs[1] * Fs[1] * fem.dx(meshes[1])))
+                    * fem.inner(fem.grad(u), fem.grad(v)) * dxs(INCLUSION))
+        return (fem.Constant(fem.assemble(fem.inner(fem.grad(Fs[0]), fem.grad(Fs[0])) * dxs(OUTSIDE))) * u * v * fem.dx(meshes[1])
+                + fem.Constant(fem.assemble(fem.inner(fem.grad(Fs[0]), fem.grad(Fs[0])) * dxs(INCLUSION)))
+                * kap * u * v * fem.dx(meshes[1]))
+
+    def rhs_fct(u, v, Fs, meshes, dom, param, Q, PGD_func, typ, nE, dim):
+        dxs, kap = fem.Measure("dx", domain=meshes[0], subdomain_data=dom), param["kappa"]
+        if typ == "x":
+            l = fem.Constant(fem.assemble(Q[1][0] * Fs[1] * fem.dx(meshes[1]))) * Q[0][0] * v * fem.dx(meshes[0])
+            for old in range(nE):
+                l += (-fem.Constant(fem.assemble(PGD_func[1][old] * Fs[1] * fem.dx(meshes[1])))
+                      * fem.inner(fem.grad(PGD_func[0][old]), fem.grad(v)) * dxs(OUTSIDE)
+                      - fem.Constant(fem.assemble(kap * PGD_func[1][old] * Fs[1] * fem.dx(meshes[1])))
+                      * fem.inner(fem.grad(PGD_func[0][old]), fem.grad(v)) * dxs(INCLUSION))
+            return l
+        l = fem.Constant(fem.assemble(Q[0][0] * Fs[0] * fem.dx(meshes[0]))) * Q[1][0] * v * fem.dx(meshes[1])
+        for old in range(nE):
+            l += (-fem.Constant(fem.assemble(fem.inner(fem.grad(PGD_func[0][old]), fem.grad(Fs[0])) * dxs(OUTSIDE)))
+                  * PGD_func[1][old] * v * fem.dx(meshes[1])
+                  - fem.Constant(fem.assemble(fem.inner(fem.grad(PGD_func[0][old]), fem.grad(Fs[0])) * dxs(INCLUSION)))
+                  * kap * PGD_func[1][old] * v * fem.dx(meshes[1]))
+        return l
+
+    return dict(name="inclusion_heat", name_coord=["X", "kappa"], modes_info=["U", "Node", "Scalar"], Vs=Vs,
+                dom_fct=dom_fct, bc_fct=bc_fct, load=load, param=param, rhs_fct=rhs_fct, lhs_fct=lhs_fct,
+                probs=["x", "kappa"], PGD_nmax=PGD_nmax, PGD_tol=PGD_tol)
+
+
 def make_problem(spec, cls):
     """PGDProblem(**spec) for either implementation of the class."""
     return cls(**spec)

@@ -405,14 +405,22 @@ enum {
                                 classification, the slot arrays keep A.  0: scale the slot arrays and classify them (the same couplings,
                                 bit for bit). */
     PGD_TUNE_MG_MARCH_MIN = 42, /* multigrid levels with at least this many nodes along x and y run their stencil passes in
-                                k_spmv_stencil_march (default 64); smaller ones in the plain kernels of pgd_mg.hip */
+                                k_spmv_stencil_march (default 64); smaller ones in the plain kernels of pgd_mg.hip.  The same bound
+                                decides between k_vmg_march and the plain kernels of pgd_vmg.hip (PGD_TUNE_PCG_PRECOND = 2). */
     PGD_TUNE_MG_CHUNK = 41, /* PCG iterations queued between two looks at the convergence flags when the multigrid preconditioner is on
                                 (even, default 2: an iteration is ~50 launches, the next chunk is queued while the flags of the last travel; the Jacobi form queues 16) */
     PGD_TUNE_PCG_PRECOND = 40, /* preconditioner of pgd_pcg_solve: 0 (default) Jacobi = the symmetric diagonal scaling; 1 a geometric
                                 multigrid V(1,1) cycle on the scaled operator WHERE it is one stencil on a lattice whose eliminated
                                 nodes are exactly the hull (every row verified, pgd_mg.hip), Jacobi everywhere else.  Changes the
                                 iterates (same stop test, same tolerance), not the system solved.  The frontend sets it from
-                                settings["preconditioner"] (solver.py:593-594: forwarded to the linear solver). */
+                                settings["preconditioner"] (solver.py:593-594: forwarded to the linear solver).
+                                2 (opt-in, the frontend's "vmg"): a geometric multigrid V(1,1) cycle on the scaled operator in DIAGONAL
+                                form with per-row coefficients (pgd_vmg.hip) - any scalar P1 operator on a structured vertex lattice
+                                (weighted atoms, several materials, Robin terms), any set of eliminated nodes: the coarse operators
+                                are the Galerkin products P^T A P, formed on the device once per solve, the smoother is l1-Jacobi.
+                                Operators that are one stencil take this cycle as well under 2 (value 1 keeps the cycle of
+                                pgd_mg.hip, bit for bit).  Anything else - no lattice, vector-valued or P2 layouts, lattices with
+                                fewer than 8 nodes along an axis - takes Jacobi and is counted by pgd_vmg_counts. */
     PGD_TUNE_CLS_CACHE = 39, /* 1 (default): a mesh remembers the class codes of the operators classified on it (by the signature of their
                                 Dirichlet set, scaled or not): the next operator with that structure - the same atoms with other
                                 coefficients, every solve of a fixed-point pass - copies the codes, rebuilds the table from the classes'
@@ -543,6 +551,13 @@ int pgd_classify_counts(pgd_handle ctx, int64_t *full, int64_t *cached);
 /* Solves that asked for the multigrid preconditioner (PGD_TUNE_PCG_PRECOND = 1) since the context was created: preconditioned by
  * the V-cycle / fallen back to Jacobi because the operator is not one stencil with an eliminated hull.                  */
 int pgd_mg_counts(pgd_handle ctx, int64_t *solves, int64_t *fallbacks);
+/* The same for PGD_TUNE_PCG_PRECOND = 2 (a solve under 2 does not touch the counters of pgd_mg_counts): solves preconditioned by the
+ * variable-coefficient V-cycle / fallen back to Jacobi; levels of the hierarchy the context holds (0: none).              */
+int pgd_vmg_counts(pgd_handle ctx, int64_t *solves, int64_t *fallbacks, int64_t *levels);
+/* ... and what they cost: device time of the Galerkin setups (eliminated bytes, weights, P^T A P level by level; once per solve) of
+ * all those solves in ms, and the number of level passes issued to the z-march kernel k_vmg_march (a chunk of iterations that is
+ * replayed as a graph counts once).                                                                                        */
+int pgd_vmg_times(pgd_handle ctx, double *setup_ms, int64_t *march_passes);
 /* The V-cycle of the multigrid preconditioner on a z-slab of a ROW-SHARDED lattice: settings["preconditioner"] = "amg"
  * (forwarded by the reference into its solver, solver.py:593-594, 634-635) on a sharded spatial dimension.  Level 0 stays
  * with the rows (this rank's planes + one ghost plane per side), levels >= 1 are whole on every rank.  The caller owns the

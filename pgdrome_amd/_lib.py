@@ -125,6 +125,8 @@ SIGNATURES = {
     "pgd_kernel_counts": (C.c_int, [H, PI64, C.c_int]),
     "pgd_classify_counts": (C.c_int, [H, PI64, PI64]),
     "pgd_mg_counts": (C.c_int, [H, PI64, PI64]),
+    "pgd_vmg_counts": (C.c_int, [H, PI64, PI64, PI64]),
+    "pgd_vmg_times": (C.c_int, [H, C.POINTER(C.c_double), PI64]),
     "pgd_calib_stream": (C.c_int, [H, H, C.c_int, C.c_int]),
     "pgd_timer_start": (C.c_int, [H]),
     "pgd_timer_stop": (C.c_int, [H, PD]),
@@ -724,6 +726,18 @@ class Context:
         a, b = I64(), I64()
         self._ck(self.lib.pgd_mg_counts(self.h, C.byref(a), C.byref(b)))
         return {"solves": a.value, "fallbacks": b.value}
+
+    def precondition_variable(self, on):
+        """Select the V-cycle for variable-coefficient operators (PGD_TUNE_PCG_PRECOND = 2) for the next pcg_solve calls, or
+        (on false) the Jacobi-PCG again; returns the number of solves that cycle has preconditioned so far."""
+        self.tune(40, 2 if on else 0)
+        return self.vmg_stats()["solves"]
+
+    def vmg_stats(self):
+        a, b, l, m, ms = I64(), I64(), I64(), I64(), C.c_double()
+        self._ck(self.lib.pgd_vmg_counts(self.h, C.byref(a), C.byref(b), C.byref(l)))
+        self._ck(self.lib.pgd_vmg_times(self.h, C.byref(ms), C.byref(m)))
+        return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
 
     def calib_stream(self, v, bytes_per_lane, store=False):
         self._ck(self.lib.pgd_calib_stream(self.h, v, int(bytes_per_lane), int(bool(store))))

@@ -283,6 +283,9 @@ struct Ctx {
     struct Mg *mg = nullptr;      // its levels and work vectors, kept across solves on the same lattice
     struct Mg *mg_slab = nullptr; // the same for a z-slab of a row-sharded lattice (pgd_mg_slab_*: levels >= 1 are whole and replicated)
     int64_t mg_solves = 0, mg_fallbacks = 0;
+    struct Vmg *vmg = nullptr;    // pcg_precond = 2: the variable-coefficient hierarchy (pgd_vmg.hip), kept across solves on the same lattice
+    int64_t vmg_solves = 0, vmg_fallbacks = 0, vmg_marches = 0;
+    double vmg_setup_ms = 0.0;    // time the Galerkin setups of those solves took on the device, summed
     int mg_chunk = 2;             // iterations queued between two looks at the flags when the multigrid preconditioner is on (even: the slot parity of a replayed chunk)
     int mg_march_min = 64;        // levels with at least this many nodes along x and y run their stencil passes in k_spmv_stencil_march
     int cls_cache_on = 1;         // classification of an operator whose structure was seen before: codes copied, every row verified (PGD_TUNE_CLS_CACHE)
@@ -405,6 +408,13 @@ int mg_fix_start(Ctx *c, const Csr *a, const double *b, double *x, int64_t n);  
 int mg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out = nullptr);      // z = M r into z_out (default: mg_result(c)); partial sums of r.z into c->partials
 double *mg_result(Ctx *c);
 void mg_release(Ctx *c);
+// pgd_vmg.hip: multigrid preconditioner of a scaled operator in diagonal form with per-row coefficients (PGD_TUNE_PCG_PRECOND = 2)
+bool vmg_prepare(Ctx *c, const Mesh *m, const Csr *a);                         // true: usable for this operator (hierarchy formed from its current slot values)
+int vmg_fix_start(Ctx *c, const double *sc, const double *b, double *x, int64_t n);   // x = s b on the eliminated rows
+int vmg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out = nullptr);
+double *vmg_result(Ctx *c);
+void vmg_note_setup(Ctx *c);
+void vmg_release(Ctx *c);
 int sym_scale(Ctx *c, const Mesh *m, Csr *a, const double *s);   // pgd_spmv.hip: slot values *= s_i s_j
 int launch_spmv_dia_rows2(Ctx *c, const Mesh *m, const Csr *a, const double *x, double *y, const double *w, int64_t r0a,
                           int64_t r1a, int64_t r0b, int64_t r1b, bool dot, const int *flags, int *nparts_out, bool *done);

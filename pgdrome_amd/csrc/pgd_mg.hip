@@ -277,6 +277,7 @@ static void mg_free(Mg *&M) {
 void mg_release(Ctx *c) {
     mg_free(c->mg);
     mg_free(c->mg_slab);
+    vmg_release(c);
 }
 
 double *mg_result(Ctx *c) { return c->mg && !c->mg->lv.empty() ? c->mg->lv[0].x : nullptr; }

@@ -1526,7 +1526,7 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
     // all 16-iteration chunks are identical and can be replayed as one hipGraph.
     constexpr int S_INIT = 18, S_PAIR = 16;
     const bool scaled = sym && c->pcg_scaled && n >= 2;
-    bool mg_on = false;
+    bool mg_on = false, vmg_on = false;   // (vmg_on: the cycle is the variable-coefficient one; mg_on is up as well)
     double *sc = z;                     // the scaled recurrence has no z: its buffer holds s = d^-1/2
     // On EVERY exit after x and the slot arrays were scaled (a failing launch, graph replay or copy included): x back to
     // D^-1/2 x~ and the slot arrays no longer taken for A - a later product with this operator must not read the scaled
@@ -1565,7 +1565,8 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
         // c_s (s_i s_j) - one product, the same for every pair of free nodes - and keep the exact zeros.  The couplings of
         // D^-1/2 A D^-1/2 are DERIVED with that very arithmetic (k_stencil_derive), the codes are A's: no scaling pass over the
         // slot arrays (0.40 ms at 256^3), no second classification (0.25 ms), and the slot arrays still hold A afterwards.
-        if (c->pcg_derive_scaled && m->sym_nx > 0) {
+        // (PGD_TUNE_PCG_PRECOND = 2 builds its hierarchy from the scaled slot arrays: they are formed for every operator, one stencil or not)
+        if (c->pcg_derive_scaled && m->sym_nx > 0 && c->pcg_precond != 2) {
             if (o->cls_count <= 0) PGD_TRY(dia_classify(c, m, o));
             if (stencil_whole_grid(c, m, o) && o->st_ident >= 0 && o->st_c[0] > 0.0) {
                 PGD_TRY(ensure_work(c, 5, 4096));
@@ -1597,6 +1598,12 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
             if (mg_on) { c->mg_solves += 1; PGD_TRY(mg_fix_start(c, o, b->d, x->d, n)); }
             else c->mg_fallbacks += 1;
         }
+        // ... = 2: the V-cycle on the diagonal form with per-row coefficients (pgd_vmg.hip): any operator on a lattice, any Dirichlet set
+        if (c->pcg_precond == 2) {
+            mg_on = vmg_on = m->sym_nx > 0 && vmg_prepare(c, m, o);
+            if (vmg_on) { c->vmg_solves += 1; PGD_TRY(vmg_fix_start(c, sc, b->d, x->d, n)); }
+            else c->vmg_fallbacks += 1;
+        }
         PGD_TRY(launch_spmv_op(c, m, o, x->d, q, nullptr, 0, n, false, true, nullptr, nullptr));
         const int g = grid_for(n);
         PGD_TRY(ensure_partials(c, 4 * (int64_t)MAX_VEC_BLOCKS));
@@ -1605,6 +1612,7 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
         PGD_TRY(reduce_partials(c, c->partials, g, 3, S_INIT, -1, 0, 0));
     } else {
         if (c->pcg_precond == 1) c->mg_fallbacks += 1;      // (no symmetric storage, or the scaled recurrence switched off: Jacobi)
+        if (c->pcg_precond == 2) c->vmg_fallbacks += 1;
         PGD_TRY(launch_spmv_op(c, m, o, x->d, q, nullptr, 0, n, false, true, nullptr, nullptr));
         PGD_TRY(pcg_init(c, b->d, q, o->dinv, r, z, p, 0, n, S_INIT));
     }
@@ -1612,7 +1620,7 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
     PGD_LAUNCH_CHECK(c);
     if (mg_on) {                        // p0 = z0 = M r0; the first "previous r.z"
         int np = 0;
-        PGD_TRY(mg_vcycle(c, r, true, &np, p));
+        PGD_TRY(vmg_on ? vmg_vcycle(c, r, true, &np, p) : mg_vcycle(c, r, true, &np, p));
         PGD_TRY(reduce_partials(c, c->partials, np, 1, S_INIT, -1, 0, 0));
     }
 
@@ -1688,9 +1696,9 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
                 k_pcg_xr_s<<<g2, TPB, 0, c->stream>>>(x->d, r, p, q, sc, n, c->slots, rz_old, S_PQ, c->partials, c->flags);
                 PGD_LAUNCH_CHECK(c);
                 PGD_TRY(reduce_partials(c, c->partials, g2, 2, out, 2, out + 1, S_TOL2));      // counts the iteration, tests
-                PGD_TRY(mg_vcycle(c, r, true, &np));
+                PGD_TRY(vmg_on ? vmg_vcycle(c, r, true, &np) : mg_vcycle(c, r, true, &np));
                 PGD_TRY(reduce_partials(c, c->partials, np, 1, out, -1, 0, 0));                // r.z over the r~.r~ the test has used
-                k_pcg_p<true><<<g2, TPB, 0, c->stream>>>(p, mg_result(c), 0, n, c->slots, out, rz_old, c->flags);
+                k_pcg_p<true><<<g2, TPB, 0, c->stream>>>(p, vmg_on ? vmg_result(c) : mg_result(c), 0, n, c->slots, out, rz_old, c->flags);
                 PGD_LAUNCH_CHECK(c);
                 continue;
             }
@@ -1831,6 +1839,7 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
     double s[PGD_NSLOTS];
     PGD_HIP(c, hipMemcpyAsync(s, c->slots, sizeof s, hipMemcpyDeviceToHost, c->stream));
     PGD_HIP(c, hipStreamSynchronize(c->stream));
+    if (vmg_on) vmg_note_setup(c);
     if (iters) *iters = f[1];
     const double rr = scaled ? s[S_TMP] : (f[1] > 0) ? s[S_PAIR + 2 * ((f[1] - 1) & 1) + 1] : s[S_INIT + 1];
     const double bb = s[S_INIT + 2];

@@ -1,0 +1,632 @@
+// Geometric multigrid preconditioner for pgd_pcg_solve on VARIABLE-COEFFICIENT operators (PGD_TUNE_PCG_PRECOND = 2; the frontend's
+// settings["preconditioner"] = "vmg").  The cycle of pgd_mg.hip holds ONE stencil in registers and needs the hull eliminated; this
+// one works on the diagonal form with per-row coefficients - weighted atoms, several materials, Robin terms, any Dirichlet set.
+//
+// What it rests on: P1 on the 6-tets-per-cube lattice is nested under doubling of the spacing, the interpolation P has weight 1 at
+// the node and 1/2 at the 14 neighbours along the mesh edges, and for ANY 15-point operator A the Galerkin operator P^T A P is
+// again a 15-point operator: (P^T A P)_IJ sums a_ij over i = 2I + e, j = 2J + f with e, f and j - i in the pattern
+// E = {+-(dx, dy, dz), d in {0,1}^3}, so 2 (J - I) = (j - i) + e - f, and a J - I with components of both signs would need four
+// contributions of the right sign from three pattern vectors that can each give one.  That argument only uses the sparsity of P
+// and A, so it also holds where rows of P are dropped (eliminated nodes) or cut off (a far face with an even node count).
+//
+//   * Level 0 is the scaled operator of the solve, D^-1/2 A D^-1/2, in the operator's own slot arrays (not copied).
+//   * An ELIMINATED node is a row without couplings (the Dirichlet rows of pgd_op_combine: identity rows, columns zeroed).  Every
+//     level carries a byte per node; coarse node k is fine node 2k and is eliminated iff that node is.  Every vector of the cycle
+//     is zero on eliminated nodes.  A far face with an even node count has no coarse counterpart: the last coarse node keeps its
+//     own state and what lies beyond it reads as zero (the rule of pgd_mg.hip).
+//   * k_vmg_galerkin forms the 8 slot arrays of P^T A P from the level above, one coarse row per thread, gathering the 15 fine
+//     rows around node 2k through their 15-point rows: no atomics, no CSR.  Once per solve (the operator changes with every
+//     fixed-point pass).
+//   * Smoother: l1-Jacobi, w_i = 1 / sum_j |a_ij| from the level's own rows (k_vmg_rowsum).  D_l1 >= A for every symmetric A, so
+//     the step converges without an eigenvalue estimate, without a reduction over the level and without a tuned factor - the
+//     bound lambda_max(D^-1 A) = 2 of the constant stencils does not hold here.  It is a diagonal matrix: the cycle stays
+//     symmetric positive definite.
+//   * V(1,1), the pre-smoothing step from a zero start folded into the residual (u = W b: t = b - A u) and into the prolongation
+//     (v = u + P e), then x = v + W (b - A v); the coarsest level - the first with at most 4096 nodes - is 24 sweeps
+//     inside one workgroup.  A lattice of at most 4096 nodes has no hierarchy: Jacobi-PCG.
+// Levels with at least mg_march_min nodes along x and y run their two passes in k_vmg_march: the z-march of the diagonal form
+// (k_spmv_dia_march2: planes of the input staged in an LDS ring, the plane-below couplings handed on through LDS) with the two
+// epilogues of the cycle; smaller levels in the plain kernels.
+#include "pgd_internal.h"
+
+#include <cmath>
+#include <cstring>
+#include <type_traits>
+
+namespace pgd {
+
+struct VGrid { int nx, ny, nz; };
+
+struct VLevel {
+    VGrid g{0, 0, 0};
+    int64_t n = 0, stride = 0;
+    double *a = nullptr;                                // 8 slot arrays (level 0: the operator's, not owned)
+    int unit = 0;                                       // slot 0 is exactly 1 and is not loaded
+    double *w = nullptr;                                // l1-Jacobi weights, 0 on eliminated nodes
+    uint8_t *el = nullptr;                              // 1 = eliminated
+    double *b = nullptr, *x = nullptr, *t = nullptr;    // right-hand side, result, work (level 0: b is the caller's r)
+};
+
+struct Vmg {
+    int nx = 0, ny = 0, nz = 0;
+    std::vector<VLevel> lv;
+    int np0 = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
+};
+
+constexpr int VMG_BOTTOM_MAX = 4096, VMG_SWEEPS = 24;
+
+// pattern vector t: 0..7 = +(dx, dy, dz) with the bits of t, 8..14 = -(bits of t - 7)
+__device__ __host__ constexpr int vp_x(int t) { return t < 8 ? (t & 1) : -((t - 7) & 1); }
+__device__ __host__ constexpr int vp_y(int t) { return t < 8 ? ((t >> 1) & 1) : -(((t - 7) >> 1) & 1); }
+__device__ __host__ constexpr int vp_z(int t) { return t < 8 ? ((t >> 2) & 1) : -(((t - 7) >> 2) & 1); }
+// is (cx, cy, cz) a pattern vector?  (all components in {0, 1} or all in {0, -1})
+__device__ __host__ constexpr bool vp_in(int cx, int cy, int cz) {
+    return (cx >= 0 && cy >= 0 && cz >= 0 && cx <= 1 && cy <= 1 && cz <= 1) || (cx <= 0 && cy <= 0 && cz <= 0 && cx >= -1 && cy >= -1 && cz >= -1);
+}
+
+// does fine node 2K + c lie in the support of one of the coarse basis functions K + D, D in {0,1}^3?
+__device__ __host__ constexpr bool vmg_reaches(int cx, int cy, int cz) {
+    for (int D = 0; D < 8; ++D)
+        if (vp_in(cx - 2 * (D & 1), cy - 2 * ((D >> 1) & 1), cz - 2 * (D >> 2))) return true;
+    return false;
+}
+template <int T, int N, class F>
+__device__ __forceinline__ void vmg_static_for(F &&f) {
+    if constexpr (T < N) { f(std::integral_constant<int, T>{}); vmg_static_for<T + 1, N>(f); }
+}
+
+// a(i, i + g) of a level in diagonal form; both nodes inside the lattice
+__device__ __forceinline__ double vmg_entry(const double *__restrict__ a, int64_t stride, int unit, int64_t i, int t, int nx, int64_t P) {
+    if (t == 0) return unit ? 1.0 : a[i];
+    if (t < 8) return a[(int64_t)t * stride + i];
+    const int s = t - 7;
+    const int64_t off = (s & 1) + (int64_t)nx * ((s >> 1) & 1) + P * (s >> 2);
+    return a[(int64_t)s * stride + i - off];
+}
+
+// The 8 slot arrays of P^T A P and the coarse level's eliminated bytes: one coarse node per thread.
+__global__ __launch_bounds__(256) void k_vmg_galerkin(VGrid gf, const double *__restrict__ af, int64_t sf, int unit, const uint8_t *__restrict__ elf,
+                                                      VGrid gc, double *__restrict__ ac, int64_t sc, uint8_t *__restrict__ elc) {
+    const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * 4 + (threadIdx.x >> 6), Z = blockIdx.z;
+    if (X >= gc.nx || Y >= gc.ny) return;
+    const int64_t Pc = (int64_t)gc.nx * gc.ny, I = Pc * Z + (int64_t)gc.nx * Y + X;
+    const int64_t Pf = (int64_t)gf.nx * gf.ny, i0 = Pf * (2 * Z) + (int64_t)gf.nx * (2 * Y) + 2 * X;
+    const bool el = elf[i0] != 0;
+    elc[I] = el ? 1 : 0;
+    double acc[8];
+#pragma unroll
+    for (int D = 0; D < 8; ++D) acc[D] = 0.0;
+    if (el) acc[0] = 1.0;
+    else {
+        // which coarse neighbours K + D carry a coupling: inside the coarse lattice and free
+        bool cok[8];
+#pragma unroll
+        for (int D = 0; D < 8; ++D) {
+            const int dx = D & 1, dy = (D >> 1) & 1, dz = D >> 2;
+            cok[D] = X + dx < gc.nx && Y + dy < gc.ny && Z + dz < gc.nz;
+            if (cok[D] && D) cok[D] = elf[i0 + 2 * (dx + (int64_t)gf.nx * dy + Pf * dz)] == 0;
+        }
+        const int fx = 2 * X, fy = 2 * Y, fz = 2 * Z;
+        vmg_static_for<0, 15>([&](auto ec) {
+            constexpr int e = decltype(ec)::value, ex = vp_x(e), ey = vp_y(e), ez = vp_z(e);
+            const int ix = fx + ex, iy = fy + ey, iz = fz + ez;
+            const bool iok = ix >= 0 && iy >= 0 && iz >= 0 && ix < gf.nx && iy < gf.ny && iz < gf.nz;
+            const int64_t i = i0 + ex + (int64_t)gf.nx * ey + Pf * ez;
+            if (iok && !elf[i]) {                                           // (an eliminated node's row of P is dropped)
+                constexpr double pe = e ? 0.5 : 1.0;
+                vmg_static_for<0, 15>([&](auto gc2) {
+                    constexpr int g = decltype(gc2)::value, cx = ex + vp_x(g), cy = ey + vp_y(g), cz = ez + vp_z(g);      // j = 2K + c
+                    if constexpr (vmg_reaches(cx, cy, cz)) {
+                        const int jx = fx + cx, jy = fy + cy, jz = fz + cz;
+                        if (jx >= 0 && jy >= 0 && jz >= 0 && jx < gf.nx && jy < gf.ny && jz < gf.nz) {
+                            const double aij = pe * vmg_entry(af, sf, unit, i, g, gf.nx, Pf);
+                            vmg_static_for<0, 8>([&](auto dc) {
+                                constexpr int D = decltype(dc)::value, hx = cx - 2 * (D & 1), hy = cy - 2 * ((D >> 1) & 1), hz = cz - 2 * (D >> 2);
+                                if constexpr (vp_in(hx, hy, hz)) {
+                                    constexpr double pf = (hx || hy || hz) ? 0.5 : 1.0;
+                                    if (cok[D]) acc[D] = fma(pf, aij, acc[D]);
+                                }
+                            });
+                        }
+                    }
+                });
+            }
+        });
+    }
+#pragma unroll
+    for (int D = 0; D < 8; ++D) ac[(int64_t)D * sc + I] = acc[D];
+}
+
+// w_i = 1 / sum_j |a_ij|, 0 on eliminated nodes.  FIND: level 0 - a row without couplings IS an eliminated node (el is written);
+// else el is given.
+template <bool FIND>
+__global__ __launch_bounds__(256) void k_vmg_rowsum(VGrid g, const double *__restrict__ a, int64_t stride, int unit, uint8_t *__restrict__ el,
+                                                    double *__restrict__ w) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), z = blockIdx.z;
+    if (x >= g.nx || y >= g.ny) return;
+    const int64_t P = (int64_t)g.nx * g.ny, i = P * z + (int64_t)g.nx * y + x;
+    double off = 0.0;
+#pragma unroll
+    for (int t = 1; t < 15; ++t) {
+        const int jx = x + vp_x(t), jy = y + vp_y(t), jz = z + vp_z(t);
+        if (jx < 0 || jy < 0 || jz < 0 || jx >= g.nx || jy >= g.ny || jz >= g.nz) continue;
+        off += fabs(vmg_entry(a, stride, unit, i, t, g.nx, P));
+    }
+    bool e;
+    if (FIND) { e = off == 0.0; el[i] = e ? 1 : 0; }
+    else e = el[i] != 0;
+    w[i] = e ? 0.0 : 1.0 / (fabs(unit ? 1.0 : a[i]) + off);
+}
+
+// (A v)_i in row order, every neighbour checked against the lattice
+__device__ __forceinline__ double vmg_apply(const VGrid &g, const double *__restrict__ a, int64_t stride, int unit, const double *__restrict__ v,
+                                            int x, int y, int z, int64_t i, int64_t P) {
+    double acc = 0.0;
+#pragma unroll
+    for (int s = 7; s >= 1; --s) {
+        const int dx = s & 1, dy = (s >> 1) & 1, dz = s >> 2;
+        const int64_t off = dx + (int64_t)g.nx * dy + P * dz;
+        if (x >= dx && y >= dy && z >= dz) acc = fma(a[(int64_t)s * stride + i - off], v[i - off], acc);
+    }
+    acc = fma(unit ? 1.0 : a[i], v[i], acc);
+#pragma unroll
+    for (int s = 1; s < 8; ++s) {
+        const int dx = s & 1, dy = (s >> 1) & 1, dz = s >> 2;
+        const int64_t off = dx + (int64_t)g.nx * dy + P * dz;
+        if (x + dx < g.nx && y + dy < g.ny && z + dz < g.nz) acc = fma(a[(int64_t)s * stride + i], v[i + off], acc);
+    }
+    return acc;
+}
+
+// u = w in  (the folded pre-smoothing step; small levels only - the march forms it while staging)
+__global__ __launch_bounds__(TPB) void k_vmg_wmul(const double *__restrict__ w, const double *__restrict__ in, double *__restrict__ u, int64_t n,
+                                                  const int *__restrict__ flags) {
+    if (flags && flags[0]) return;
+    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i < n) u[i] = w[i] * in[i];
+}
+
+// MODE 0: out = b - A in          (in = W b: the residual behind the pre-smoothing step from a zero start)
+// MODE 1: out = in + w (b - A in) (post-smoothing step);  DOT: partial sums of b . out per workgroup
+template <int MODE, bool DOT>
+__global__ __launch_bounds__(256) void k_vmg_pass(VGrid g, const double *__restrict__ a, int64_t stride, int unit, const double *__restrict__ w,
+                                                  const double *__restrict__ in, const double *__restrict__ b, double *__restrict__ out,
+                                                  double *__restrict__ partials, const int *__restrict__ flags) {
+    __shared__ double s_red[4];
+    if (flags && flags[0]) return;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), z = blockIdx.z;
+    double d = 0.0;
+    if (x < g.nx && y < g.ny) {
+        const int64_t P = (int64_t)g.nx * g.ny, i = P * z + (int64_t)g.nx * y + x;
+        const double wi = w[i];
+        double o = 0.0;
+        if (wi != 0.0) {
+            const double av = vmg_apply(g, a, stride, unit, in, x, y, z, i, P), bi = b[i];
+            if (MODE == 0) o = bi - av;
+            else { o = fma(wi, bi - av, in[i]); if (DOT) d = bi * o; }
+        }
+        out[i] = o;
+    }
+    if (DOT) {
+        d = block_sum(d, s_red);
+        if (threadIdx.x == 0) partials[(int64_t)blockIdx.x + (int64_t)gridDim.x * (blockIdx.y + (int64_t)gridDim.y * blockIdx.z)] = d;
+    }
+}
+
+// bc = P^T t: the node's own value + half of its 14 neighbours along the mesh edges (those inside the fine lattice)
+__global__ __launch_bounds__(256) void k_vmg_restrict(VGrid gc, VGrid gf, const uint8_t *__restrict__ elc, const double *__restrict__ t,
+                                                      double *__restrict__ bc, const int *__restrict__ flags) {
+    if (flags && flags[0]) return;
+    const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * 4 + (threadIdx.x >> 6), Z = blockIdx.z;
+    if (X >= gc.nx || Y >= gc.ny) return;
+    const int64_t Pc = (int64_t)gc.nx * gc.ny, I = Pc * Z + (int64_t)gc.nx * Y + X;
+    double o = 0.0;
+    if (!elc[I]) {
+        const int64_t Pf = (int64_t)gf.nx * gf.ny, i = Pf * (2 * Z) + (int64_t)gf.nx * (2 * Y) + 2 * X;
+        double h = 0.0;
+#pragma unroll
+        for (int e = 1; e < 15; ++e) {
+            const int ix = 2 * X + vp_x(e), iy = 2 * Y + vp_y(e), iz = 2 * Z + vp_z(e);
+            if (ix < 0 || iy < 0 || iz < 0 || ix >= gf.nx || iy >= gf.ny || iz >= gf.nz) continue;
+            h += t[i + vp_x(e) + (int64_t)gf.nx * vp_y(e) + Pf * vp_z(e)];
+        }
+        o = fma(0.5, h, t[i]);
+    }
+    bc[I] = o;
+}
+
+// v = w b + P e on the fine lattice: a fine node is a coarse node (all coordinates even) or the midpoint of ONE coarse edge
+__global__ __launch_bounds__(256) void k_vmg_prolong(VGrid gf, VGrid gc, const double *__restrict__ w, const double *__restrict__ b,
+                                                     const double *__restrict__ e, double *__restrict__ v, const int *__restrict__ flags) {
+    if (flags && flags[0]) return;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), z = blockIdx.z;
+    if (x >= gf.nx || y >= gf.ny) return;
+    const int64_t Pf = (int64_t)gf.nx * gf.ny, i = Pf * z + (int64_t)gf.nx * y + x;
+    const double wi = w[i];
+    double o = 0.0;
+    if (wi != 0.0) {
+        const int64_t Pc = (int64_t)gc.nx * gc.ny;
+        const int bx = (x + 1) >> 1, by = (y + 1) >> 1, bz = (z + 1) >> 1;
+        const double ea = e[Pc * (z >> 1) + (int64_t)gc.nx * (y >> 1) + (x >> 1)];
+        const double eb = (bx < gc.nx && by < gc.ny && bz < gc.nz) ? e[Pc * bz + (int64_t)gc.nx * by + bx] : 0.0;      // (ea == eb on a coarse node)
+        o = fma(wi, b[i], 0.5 * (ea + eb));
+    }
+    v[i] = o;
+}
+
+// the coarsest level inside one workgroup: `sweeps` l1-Jacobi steps from a zero start (the iterate in LDS, the rows'
+// coefficients - 256 KB at most - from the caches)
+__global__ __launch_bounds__(1024) void k_vmg_bottom(VGrid g, const double *__restrict__ a, int64_t stride, const double *__restrict__ w,
+                                                     const double *__restrict__ b, double *__restrict__ x, int sweeps, const int *__restrict__ flags) {
+    __shared__ double s_v[2][VMG_BOTTOM_MAX];
+    if (flags && flags[0]) return;
+    const int P = g.nx * g.ny, n = P * g.nz;
+    for (int i = threadIdx.x; i < n; i += 1024) s_v[0][i] = w[i] * b[i];          // (w = 0 on eliminated nodes)
+    __syncthreads();
+    int cur = 0;
+    for (int sw = 1; sw < sweeps; ++sw) {
+#pragma unroll 1
+        for (int i = threadIdx.x; i < n; i += 1024) {
+            const int z = i / P, rem = i - z * P, y = rem / g.nx, xx = rem - y * g.nx;
+            const double wi = w[i];
+            double o = 0.0;
+            if (wi != 0.0) o = fma(wi, b[i] - vmg_apply(g, a, stride, 0, s_v[cur], xx, y, z, i, P), s_v[cur][i]);
+            s_v[cur ^ 1][i] = o;
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    for (int i = threadIdx.x; i < n; i += 1024) x[i] = s_v[cur][i];
+}
+
+// x = s b on the eliminated rows: their exact solution in the scaled unknowns (s = 1 on a Dirichlet row), so that the residual, and
+// with it every vector of the cycle, vanishes there
+__global__ __launch_bounds__(TPB) void k_vmg_fix_start(const uint8_t *__restrict__ el, const double *__restrict__ sc, const double *__restrict__ b,
+                                                       double *__restrict__ x, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i < n && el[i]) x[i] = sc[i] * b[i];
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The z-march of the diagonal form (k_spmv_dia_march2: a 64 x 8 patch per 256-thread workgroup, two rows per thread, three planes of
+// the input in an LDS ring, the plane-below couplings handed on through LDS) with the epilogues of the cycle:
+//   EPI 1: staged u = w in;  out = in - A u on free rows, 0 on eliminated ones                   (in = the level's right-hand side)
+//   EPI 2: staged v = in;    out = v + w (b - A v);  DOT: partial sums of b . out per workgroup  (in = the prolongated vector)
+struct VmArgs {
+    const double *a, *w, *in, *b;
+    double *out, *partials;
+    const int *flags;
+    int64_t n;              // slot stride in doubles
+    int nx, ny, nz, zchunk, tiles_x, tiles_y, unit;
+};
+constexpr int VM_HX = 66;            // cells per line of the staged patch: 64 + one halo cell each way
+
+template <int EPI, bool DOT>
+__global__ __launch_bounds__(256) void k_vmg_march(VmArgs A) {
+    constexpr int NT = 256, PY = 8, HY = PY + 2, SLICE = VM_HX * HY;        // 660 cells per plane
+    __shared__ double s_x[3 * SLICE];
+    __shared__ double s_lo[2 * 4 * NT];                     // [row of the pair][slot 4..7][thread]
+    __shared__ double s_red[4];
+    if (A.flags && A.flags[0]) return;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int per_chunk = A.tiles_x * A.tiles_y;
+    const int chunk = b / per_chunk, tile = b - chunk * per_chunk;
+    const int ty = tile / A.tiles_x, tx = tile - ty * A.tiles_x;
+    const int x0 = tx * 64, y0 = ty * PY;
+    const int x = x0 + lane, ya = y0 + 2 * wv;
+    const bool live0 = x < A.nx && ya < A.ny, live1 = x < A.nx && ya + 1 < A.ny;
+    const bool inx0 = live0 && x > 0, inx1 = live1 && x > 0;
+    const bool iny0 = live0 && ya > 0;                      // the upper row of the pair always has its y - 1 neighbour: the lower row
+    const bool ldx = lane > 0, ldy = wv > 0;
+    const int64_t nx = A.nx, P = (int64_t)A.nx * A.ny, n = A.n;
+    const int64_t base0 = live0 ? x + nx * ya : 0, base1 = live1 ? x + nx * (ya + 1) : 0;
+    const int centre = (2 * wv + 1) * VM_HX + lane + 1;     // the lower row of the pair; the upper one at + VM_HX
+    const int za = chunk * A.zchunk, zb = min(A.nz, za + A.zchunk);
+    int64_t goff[3];
+    bool gok[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int i = tid + q * NT;
+        const int ly = i / VM_HX, lx = i - ly * VM_HX;
+        const int gx = x0 - 1 + lx, gy = y0 - 1 + ly;
+        gok[q] = i < SLICE && gx >= 0 && gx < A.nx && gy >= 0 && gy < A.ny;
+        goff[q] = gok[q] ? gx + nx * gy : 0;
+    }
+    auto fetch = [&](int z, double v[3]) {
+        const bool zok = z >= 0 && z < A.nz;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            v[q] = 0.0;
+            if (zok && gok[q]) {
+                const int64_t j = goff[q] + P * z;
+                v[q] = EPI == 1 ? A.w[j] * A.in[j] : A.in[j];
+            }
+        }
+    };
+    auto put = [&](int z, const double v[3]) {
+        const int sl = ((z % 3) + 3) % 3;
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            if (tid + q * NT < SLICE) s_x[sl * SLICE + tid + q * NT] = v[q];
+    };
+    double dot = 0.0;
+    if (za < zb) {
+        double v[3];
+        for (int z = za - 1; z <= za + 1; ++z) { fetch(z, v); put(z, v); }
+        if (za > 0) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                s_lo[s * NT + tid] = A.a[(int64_t)(4 + s) * n + base0 + P * (za - 1)];
+                s_lo[(4 + s) * NT + tid] = A.a[(int64_t)(4 + s) * n + base1 + P * (za - 1)];
+            }
+        }
+    }
+    __syncthreads();
+    for (int z = za; z < zb; ++z) {
+        double vn[3] = {0.0, 0.0, 0.0};
+        if (z + 2 <= zb) fetch(z + 2, vn);                  // plane zb + 1 is never read
+        const int64_t r0 = base0 + P * z, r1 = base1 + P * z;
+        double u0[8], u1[8];
+        u0[0] = u1[0] = 1.0;                                // unit diagonal of the scaled operator (level 0)
+        if (!A.unit) { u0[0] = A.a[r0]; u1[0] = A.a[r1]; }
+#pragma unroll
+        for (int s = 1; s < 8; ++s) { u0[s] = A.a[(int64_t)s * n + r0]; u1[s] = A.a[(int64_t)s * n + r1]; }
+        // the rows' own vector entries of the epilogue (EPI 1: in = the right-hand side; EPI 2: b)
+        const double w0 = A.w[r0], w1 = A.w[r1];
+        const double e0 = EPI == 1 ? A.in[r0] : A.b[r0], e1 = EPI == 1 ? A.in[r1] : A.b[r1];
+        // in-plane lower couplings from the neighbouring rows' slots (L1 / L2); (0, -1) of the upper row = u0[2]
+        const double t1a = A.a[1 * n + (inx0 ? r0 - 1 : r0)];
+        const double t2a = A.a[2 * n + (iny0 ? r0 - nx : r0)];
+        const double t3a = A.a[3 * n + ((inx0 && iny0) ? r0 - nx - 1 : r0)];
+        const double t1b = A.a[1 * n + (inx1 ? r1 - 1 : r1)];
+        const double t3b = A.a[3 * n + (inx1 ? r1 - nx - 1 : r1)];
+        double a4 = 0.0, a5 = 0.0, a6 = 0.0, a7 = 0.0, b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
+        if (z > 0) {                                        // uniform
+            a4 = live0 ? s_lo[tid] : 0.0;
+            b4 = live1 ? s_lo[4 * NT + tid] : 0.0;
+            if (inx0) a5 = ldx ? s_lo[NT + tid - 1] : A.a[5 * n + r0 - P - 1];
+            if (inx1) b5 = ldx ? s_lo[5 * NT + tid - 1] : A.a[5 * n + r1 - P - 1];
+            if (iny0) a6 = ldy ? s_lo[6 * NT + tid - 64] : A.a[6 * n + r0 - P - nx];          // row below the pair: upper row of wave - 1
+            if (live1) b6 = s_lo[2 * NT + tid];                                                // the pair's own lower row
+            if (inx0 && iny0) a7 = (ldx && ldy) ? s_lo[7 * NT + tid - 65] : A.a[7 * n + r0 - P - nx - 1];
+            if (inx1) b7 = ldx ? s_lo[3 * NT + tid - 1] : A.a[7 * n + r1 - P - nx - 1];
+        }
+        const double a1 = inx0 ? t1a : 0.0, a2 = iny0 ? t2a : 0.0, a3 = (inx0 && iny0) ? t3a : 0.0;
+        const double b1 = inx1 ? t1b : 0.0, b2 = live1 ? u0[2] : 0.0, b3 = inx1 ? t3b : 0.0;
+        const int sl0 = ((z - 1) % 3 + 3) % 3;
+        const double *xm = s_x + sl0 * SLICE + centre;
+        const double *xc = s_x + ((sl0 + 1) % 3) * SLICE + centre;
+        const double *xp = s_x + ((sl0 + 2) % 3) * SLICE + centre;
+        const double xa = xc[0], xb = xc[VM_HX];
+        double acc0 = a7 * xm[-VM_HX - 1];
+        acc0 = fma(a6, xm[-VM_HX], acc0);
+        acc0 = fma(a5, xm[-1], acc0);
+        acc0 = fma(a4, xm[0], acc0);
+        acc0 = fma(a3, xc[-VM_HX - 1], acc0);
+        acc0 = fma(a2, xc[-VM_HX], acc0);
+        acc0 = fma(a1, xc[-1], acc0);
+        acc0 = fma(u0[0], xa, acc0);
+        acc0 = fma(u0[1], xc[1], acc0);
+        acc0 = fma(u0[2], xc[VM_HX], acc0);
+        acc0 = fma(u0[3], xc[VM_HX + 1], acc0);
+        acc0 = fma(u0[4], xp[0], acc0);
+        acc0 = fma(u0[5], xp[1], acc0);
+        acc0 = fma(u0[6], xp[VM_HX], acc0);
+        acc0 = fma(u0[7], xp[VM_HX + 1], acc0);
+        double acc1 = b7 * xm[-1];
+        acc1 = fma(b6, xm[0], acc1);
+        acc1 = fma(b5, xm[VM_HX - 1], acc1);
+        acc1 = fma(b4, xm[VM_HX], acc1);
+        acc1 = fma(b3, xc[-1], acc1);
+        acc1 = fma(b2, xc[0], acc1);
+        acc1 = fma(b1, xc[VM_HX - 1], acc1);
+        acc1 = fma(u1[0], xb, acc1);
+        acc1 = fma(u1[1], xc[VM_HX + 1], acc1);
+        acc1 = fma(u1[2], xc[2 * VM_HX], acc1);
+        acc1 = fma(u1[3], xc[2 * VM_HX + 1], acc1);
+        acc1 = fma(u1[4], xp[VM_HX], acc1);
+        acc1 = fma(u1[5], xp[VM_HX + 1], acc1);
+        acc1 = fma(u1[6], xp[2 * VM_HX], acc1);
+        acc1 = fma(u1[7], xp[2 * VM_HX + 1], acc1);
+        double o0, o1;
+        if (EPI == 1) { o0 = w0 != 0.0 ? e0 - acc0 : 0.0; o1 = w1 != 0.0 ? e1 - acc1 : 0.0; }
+        else { o0 = w0 != 0.0 ? fma(w0, e0 - acc0, xa) : 0.0; o1 = w1 != 0.0 ? fma(w1, e1 - acc1, xb) : 0.0; }
+        if (live0) A.out[r0] = o0;
+        if (live1) A.out[r1] = o1;
+        if (DOT && live0) dot = fma(e0, o0, dot);
+        if (DOT && live1) dot = fma(e1, o1, dot);
+        __syncthreads();
+        put(z + 2, vn);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { s_lo[s * NT + tid] = u0[4 + s]; s_lo[(4 + s) * NT + tid] = u1[4 + s]; }
+        __syncthreads();
+    }
+    if (DOT) {
+        const double sum = wave_sum(dot);
+        __syncthreads();
+        if (lane == 0) s_red[wv] = sum;
+        __syncthreads();
+        if (tid == 0) A.partials[b] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+    }
+}
+
+static void vmg_free(Vmg *&M) {
+    if (!M) return;
+    for (size_t l = 0; l < M->lv.size(); ++l) {
+        VLevel &L = M->lv[l];
+        if (l > 0 && L.a) (void)hipFree(L.a);
+        for (void *p : {(void *)L.w, (void *)L.el, (void *)L.b, (void *)L.x, (void *)L.t}) if (p) (void)hipFree(p);
+    }
+    if (M->ev0) (void)hipEventDestroy(M->ev0);
+    if (M->ev1) (void)hipEventDestroy(M->ev1);
+    delete M;
+    M = nullptr;
+}
+
+void vmg_release(Ctx *c) { vmg_free(c->vmg); }
+
+double *vmg_result(Ctx *c) { return c->vmg && !c->vmg->lv.empty() ? c->vmg->lv[0].x : nullptr; }
+
+static dim3 vmg_grid(const VGrid &g) { return dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4), (unsigned)g.nz); }
+
+static bool vmg_marches(const Ctx *c, const VLevel &L, int *zchunk, int *wgs) {
+    if (!(c->mg_march_min > 0 && L.g.nx >= c->mg_march_min && L.g.ny >= c->mg_march_min && L.g.nz >= 8)) return false;
+    const int64_t tiles = (int64_t)((L.g.nx + 63) / 64) * ((L.g.ny + 7) / 8);
+    // planes per march: about two workgroups per CU in the launch, between 3 (a shorter march pays its prologue too often) and 8
+    const int zc = (int)std::max<int64_t>(3, std::min<int64_t>(8, tiles * L.g.nz / (2 * (int64_t)std::max(1, c->num_cu))));
+    const int64_t g = (int64_t)((L.g.nz + zc - 1) / zc) * tiles;
+    if (g >= ((int64_t)1 << 30)) return false;
+    *zchunk = zc; *wgs = (int)g;
+    return true;
+}
+
+// true: the cycle applies to this solve - hierarchy formed from the operator's CURRENT (scaled) slot values, buffers there
+bool vmg_prepare(Ctx *c, const Mesh *m, const Csr *a) {
+    if (!m || !a || m->sym_nx <= 0 || !a->uvals || !a->uvals_valid || !a->uvals_scaled) return false;
+    const int nx = m->sym_nx, ny = m->sym_ny, nz = (int)(m->nv / ((int64_t)nx * ny));
+    if ((int64_t)nx * ny * nz != m->nv || std::min(nx, std::min(ny, nz)) < 8 || nz > 65535 || ny > 4 * 65535) return false;
+    Vmg *M = c->vmg;
+    if (!M || M->nx != nx || M->ny != ny || M->nz != nz) {                  // another lattice: new levels and buffers
+        vmg_free(c->vmg);
+        M = c->vmg = new Vmg();
+        VGrid g{nx, ny, nz};
+        for (;;) {
+            VLevel L;
+            L.g = g;
+            L.n = (int64_t)g.nx * g.ny * g.nz;
+            M->lv.push_back(L);
+            if (L.n <= VMG_BOTTOM_MAX) break;                               // the first level one workgroup can hold is the coarsest
+            g = VGrid{(g.nx + 1) / 2, (g.ny + 1) / 2, (g.nz + 1) / 2};
+        }
+        if (M->lv.size() < 2) { vmg_free(c->vmg); return false; }          // (at most 4096 nodes: no hierarchy, Jacobi)
+        bool ok = hipEventCreate(&M->ev0) == hipSuccess && hipEventCreate(&M->ev1) == hipSuccess;
+        for (size_t l = 0; ok && l < M->lv.size(); ++l) {
+            VLevel &L = M->lv[l];
+            const bool last = l + 1 == M->lv.size();
+            const size_t bytes = (size_t)L.n * sizeof(double) + PAD_BYTES;
+            auto get = [&](void **p, size_t nbytes) { ok = ok && hipMalloc(p, nbytes) == hipSuccess; };
+            if (l > 0) { get((void **)&L.a, 8 * (size_t)L.n * sizeof(double) + PAD_BYTES); L.stride = L.n; get((void **)&L.b, bytes); }
+            get((void **)&L.w, bytes);
+            get((void **)&L.el, (size_t)L.n + PAD_BYTES);
+            get((void **)&L.x, bytes);
+            if (!last) get((void **)&L.t, bytes);
+        }
+        if (!ok) { (void)hipGetLastError(); vmg_free(c->vmg); return false; }
+        M->nx = nx; M->ny = ny; M->nz = nz;
+    }
+    VLevel &L0 = M->lv[0];
+    L0.a = a->uvals; L0.stride = a->uvals_stride; L0.unit = a->uvals_unit ? 1 : 0;
+    // the hierarchy of THIS operator: eliminated nodes and weights of level 0, then level by level P^T A P and its weights
+    M->timed = hipEventRecord(M->ev0, c->stream) == hipSuccess;
+    k_vmg_rowsum<true><<<vmg_grid(L0.g), 256, 0, c->stream>>>(L0.g, L0.a, L0.stride, L0.unit, L0.el, L0.w);
+    for (size_t l = 1; l < M->lv.size(); ++l) {
+        VLevel &F = M->lv[l - 1], &C = M->lv[l];
+        k_vmg_galerkin<<<vmg_grid(C.g), 256, 0, c->stream>>>(F.g, F.a, F.stride, F.unit, F.el, C.g, C.a, C.stride, C.el);
+        k_vmg_rowsum<false><<<vmg_grid(C.g), 256, 0, c->stream>>>(C.g, C.a, C.stride, 0, C.el, C.w);
+    }
+    M->timed = M->timed && hipEventRecord(M->ev1, c->stream) == hipSuccess;
+    if (hipGetLastError() != hipSuccess) return false;
+    int zc = 0, wgs = 0;
+    const dim3 g0 = vmg_grid(L0.g);
+    M->np0 = vmg_marches(c, L0, &zc, &wgs) ? wgs : (int)((int64_t)g0.x * g0.y * g0.z);
+    if (ensure_partials(c, std::max<int64_t>(M->np0 + 64, 4 * (int64_t)MAX_VEC_BLOCKS)) != PGD_OK) return false;
+    return true;
+}
+
+// after the solve's last synchronisation: the hierarchy's setup time joins the context's sum (pgd_vmg_counts)
+void vmg_note_setup(Ctx *c) {
+    Vmg *M = c->vmg;
+    if (!M || !M->timed) return;
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, M->ev0, M->ev1) == hipSuccess) c->vmg_setup_ms += (double)ms;
+    else (void)hipGetLastError();
+    M->timed = false;
+}
+
+int vmg_fix_start(Ctx *c, const double *sc, const double *b, double *x, int64_t n) {
+    Vmg *M = c->vmg;
+    if (!M || M->lv.empty() || M->lv[0].n != n) return fail(c, PGD_ERR_INVALID, "vmg_fix_start: no hierarchy");
+    k_vmg_fix_start<<<(unsigned)((n + TPB - 1) / TPB), TPB, 0, c->stream>>>(M->lv[0].el, sc, b, x, n);
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+int vmg_levels(const Ctx *c) { return c->vmg ? (int)c->vmg->lv.size() : 0; }
+
+// z = M r: the cycle from level 0 down and back up; the result lands in z_out (default: vmg_result(c)), the partial sums of
+// r . z in c->partials (*nparts of them)
+int vmg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out) {
+    Vmg *M = c->vmg;
+    if (!M || M->lv.size() < 2) return fail(c, PGD_ERR_INVALID, "vmg_vcycle: no hierarchy");
+    const int nl = (int)M->lv.size();
+    const dim3 blk(256, 1, 1);
+    const int *flags = c->flags;
+    int np_dot = M->np0;
+    auto march = [&](const VLevel &L, int epi, const double *in, const double *b, double *out, bool d) -> bool {
+        int zc = 0, wgs = 0;
+        if (!vmg_marches(c, L, &zc, &wgs)) return false;
+        VmArgs A;
+        A.a = L.a; A.w = L.w; A.in = in; A.b = b; A.out = out; A.partials = c->partials; A.flags = flags; A.n = L.stride;
+        A.nx = L.g.nx; A.ny = L.g.ny; A.nz = L.g.nz; A.zchunk = zc; A.tiles_x = (L.g.nx + 63) / 64; A.tiles_y = (L.g.ny + 7) / 8; A.unit = L.unit;
+        if (epi == 1) k_vmg_march<1, false><<<wgs, 256, 0, c->stream>>>(A);
+        else if (d) k_vmg_march<2, true><<<wgs, 256, 0, c->stream>>>(A);
+        else k_vmg_march<2, false><<<wgs, 256, 0, c->stream>>>(A);
+        c->vmg_marches += 1;
+        return true;
+    };
+    // down: residual behind the folded pre-smoothing step, restriction
+    for (int l = 0; l + 1 < nl; ++l) {
+        VLevel &L = M->lv[l], &C = M->lv[l + 1];
+        const double *b = l == 0 ? r : L.b;
+        if (!march(L, 1, b, nullptr, L.t, false)) {
+            k_vmg_wmul<<<(unsigned)((L.n + TPB - 1) / TPB), TPB, 0, c->stream>>>(L.w, b, L.x, L.n, flags);
+            k_vmg_pass<0, false><<<vmg_grid(L.g), blk, 0, c->stream>>>(L.g, L.a, L.stride, L.unit, L.w, L.x, b, L.t, nullptr, flags);
+        }
+        k_vmg_restrict<<<vmg_grid(C.g), blk, 0, c->stream>>>(C.g, L.g, C.el, L.t, C.b, flags);
+    }
+    {
+        VLevel &B = M->lv[nl - 1];
+        k_vmg_bottom<<<1, 1024, 0, c->stream>>>(B.g, B.a, B.stride, B.w, B.b, B.x, VMG_SWEEPS, flags);
+    }
+    // up: v = w b + P e, one more l1-Jacobi step
+    for (int l = nl - 2; l >= 0; --l) {
+        VLevel &L = M->lv[l], &C = M->lv[l + 1];
+        const double *b = l == 0 ? r : L.b;
+        k_vmg_prolong<<<vmg_grid(L.g), blk, 0, c->stream>>>(L.g, C.g, L.w, b, C.x, L.t, flags);
+        double *out = l == 0 && z_out ? z_out : L.x;
+        const bool d = l == 0 && dot;
+        if (!march(L, 2, L.t, b, out, d)) {
+            if (d) k_vmg_pass<1, true><<<vmg_grid(L.g), blk, 0, c->stream>>>(L.g, L.a, L.stride, L.unit, L.w, L.t, b, out, c->partials, flags);
+            else k_vmg_pass<1, false><<<vmg_grid(L.g), blk, 0, c->stream>>>(L.g, L.a, L.stride, L.unit, L.w, L.t, b, out, nullptr, flags);
+        }
+    }
+    if (nparts) *nparts = np_dot;
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+}  // namespace pgd
+
+using namespace pgd;
+
+extern "C" {
+
+int pgd_vmg_counts(pgd_handle h, int64_t *solves, int64_t *fallbacks, int64_t *levels) {
+    PGD_CTX(c, h);
+    if (solves) *solves = c->vmg_solves;
+    if (fallbacks) *fallbacks = c->vmg_fallbacks;
+    if (levels) *levels = vmg_levels(c);
+    return PGD_OK;
+}
+
+int pgd_vmg_times(pgd_handle h, double *setup_ms, int64_t *march_passes) {
+    PGD_CTX(c, h);
+    if (setup_ms) *setup_ms = c->vmg_setup_ms;
+    if (march_passes) *march_passes = c->vmg_marches;
+    return PGD_OK;
+}
+
+}  // extern "C"

@@ -3512,13 +3512,19 @@ def _solve_linear(A, b, x, prm):
             # settings["preconditioner"] (forwarded to PETSc by the reference, solver.py:593-594): the multigrid family asks for
             # the V-cycle of pgd_mg.hip, which the library uses where the operator has the structure for it and says so in its
             # counters; every other value is the Jacobi-PCG.  The row-sharded solve has the Jacobi form only.
+            # VARIABLE_MULTIGRID_NAMES (opt-in) ask for the V-cycle of pgd_vmg.hip instead: any scalar P1 operator on a lattice
+            # mesh, any Dirichlet set.  A backend without it (the numpy oracle) and a row-sharded layout answer with the Jacobi-PCG.
             prec = prm.get("preconditioner", "default")
-            asks_mg = (not isinstance(prec, _Params)) and str(prec).lower() in MULTIGRID_NAMES
+            prec_name = "" if isinstance(prec, _Params) else str(prec).lower()
+            asks_mg = prec_name in MULTIGRID_NAMES
             want_mg = asks_mg and part is None
-            mg0 = None
-            used = 0
+            want_vmg = prec_name in VARIABLE_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_variable")
+            mg0 = vmg0 = None
+            used = used_v = 0
             if want_mg and hasattr(be, "precondition"):
                 mg0 = be.precondition(1)
+            elif want_vmg:
+                vmg0 = be.precondition_variable(True)
             try:
                 if part is not None:
                     # a row-sharded lattice: the V-cycle with level 0 on the slabs and levels >= 1 replicated (dist.pcg_mg);
@@ -3535,10 +3541,14 @@ def _solve_linear(A, b, x, prm):
             finally:
                 if mg0 is not None:
                     used = be.precondition(0) - mg0
+                if vmg0 is not None:
+                    used_v = be.precondition_variable(False) - vmg0
             STATS["pcg_seconds"] += time.perf_counter() - t_solve      # the solve returns synchronised
-            info.update(method="mg_pcg" if used > 0 else "jacobi_pcg", iterations=it, relres=rel)
+            info.update(method="mg_pcg" if used > 0 else "vmg_pcg" if used_v > 0 else "jacobi_pcg", iterations=it, relres=rel)
             if used > 0:
                 STATS["mg_solves"] = STATS.get("mg_solves", 0) + 1
+            if used_v > 0:
+                STATS["vmg_solves"] = STATS.get("vmg_solves", 0) + 1
             if rel > max(rtol, 1e-14) * 1.0001 and it >= maxit:
                 # dolfin's Krylov solvers raise on non-convergence unless told otherwise (error_on_nonconvergence,
                 # default True): an unconverged mode must not be stored silently
@@ -3551,13 +3561,15 @@ def _solve_linear(A, b, x, prm):
     finally:
         be.atom_free(op)
     STATS["linear_solves"] += 1
-    STATS["pcg_iterations"] += info.get("iterations", 0) if info.get("method") in ("jacobi_pcg", "mg_pcg") else 0
+    STATS["pcg_iterations"] += info.get("iterations", 0) if info.get("method") in ("jacobi_pcg", "mg_pcg", "vmg_pcg") else 0
     return info
 
 
-STATS = {"linear_solves": 0, "pcg_iterations": 0, "pcg_seconds": 0.0, "mg_solves": 0}
+STATS = {"linear_solves": 0, "pcg_iterations": 0, "pcg_seconds": 0.0, "mg_solves": 0, "vmg_solves": 0}
 # values of settings["preconditioner"] that select the geometric multigrid V-cycle (dolfin's names of its algebraic ones included)
 MULTIGRID_NAMES = ("amg", "hypre_amg", "petsc_amg", "ml_amg", "gmg", "multigrid", "mg")
+# ... and those that select the V-cycle for variable-coefficient operators (pgd_vmg.hip): opt-in, none of the names above
+VARIABLE_MULTIGRID_NAMES = ("vmg", "variable_multigrid")
 
 
 def _apply_bcs_system(A, b, bcs):

@@ -147,6 +147,19 @@ int pgd_atom_assemble(pgd_handle ctx, pgd_handle mesh, int kind, int da, int db,
  * scalar atom) or cell_mask = NULL with nc > 0.  Deterministic (owner-computes, no atomics).             */
 int pgd_atom_assemble_cells(pgd_handle ctx, pgd_handle mesh, int kind, int da, int db, pgd_handle wvec,
                             const uint8_t *cell_mask, int64_t nc, pgd_handle *atom);
+/* The atom of pgd_atom_assemble_cells with a cell-wise constant (DG0) coefficient: sum over the cells c of
+ * cvec[c] * (local matrix of c), the operator of  kappa * ... * dx  for a material field with one value per
+ * cell.  cvec: a library vector of nc doubles in the cell order of the upload; it stays resident, so one field
+ * serves every atom made from it.  The weight multiplies each finished local entry once as it is added - same
+ * kinds, nodal weight wvec, axis checks, kernels and order of summation as pgd_atom_assemble (a cell weight,
+ * unlike a nodal one, keeps the gather-free kernel of regular lattices: six weights per cube, 48 contiguous
+ * bytes).  cell_mask: NULL = every cell, else nc bytes as in pgd_atom_assemble_cells; the weight of an
+ * unmarked cell never enters.  The atom lies on the mesh's own pattern.  cvec = 1 everywhere: bit-identical to
+ * pgd_atom_assemble (to pgd_atom_assemble_cells with a mask).  PGD_ERR_INVALID, with no atom left behind,
+ * for nc other than the mesh's cell count, cvec not a vector of nc entries, a blocked layout, an unknown kind,
+ * a weighted kind without wvec or an axis out of range.  Deterministic (owner-computes, no atomics).       */
+int pgd_atom_assemble_cellwise(pgd_handle ctx, pgd_handle mesh, int kind, int da, int db, pgd_handle wvec,
+                               pgd_handle cvec, const uint8_t *cell_mask, int64_t nc, pgd_handle *atom);
 /* Boundary mass  int_Gamma phi_i phi_j ds  over nf facets (the Robin term c*u*v*ds of a form), on the
  * mesh's own pattern: an atom like any other.  facets: nf records of nvpf node ids of the layout, the
  * facet's vertices first, then for P2 the nodes of its edges in the UFC local order - interval layouts

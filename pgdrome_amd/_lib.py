@@ -60,6 +60,7 @@ SIGNATURES = {
     "pgd_vec_dot": (C.c_int, [H, H, H, I64, I64, PD]),
     "pgd_atom_assemble": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PH]),
     "pgd_atom_assemble_cells": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PU8, I64, PH]),
+    "pgd_atom_assemble_cellwise": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, H, PU8, I64, PH]),
     "pgd_atom_assemble_facets": (C.c_int, [H, H, PI32, I64, C.c_int, PH]),
     "pgd_atom_upload": (C.c_int, [H, H, PD, PH]),
     "pgd_atom_download": (C.c_int, [H, H, PD]),
@@ -388,6 +389,26 @@ class Context:
         a = H(0)
         self._ck(self.lib.pgd_atom_assemble_cells(self.h, mesh, int(kind), int(da), int(db), int(w),
                                                   mask.ctypes.data_as(PU8) if mask.size else None, mask.size, C.byref(a)))
+        return a.value
+
+    def atom_assemble_cellwise(self, mesh, kind, da, db, w, c, mask=None, nc=None):
+        """The atom of atom_assemble with every cell's local matrix scaled by its entry of the device vector `c` (one per cell,
+        upload order); mask: None = every cell, else one byte per cell as in atom_assemble_cells.  nc: the cell count
+        (default: the mask's length, or the vector's)."""
+        ptr = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask)
+            if mask.ndim != 1 or mask.dtype.itemsize != 1:
+                raise ValueError("mask: one byte per cell")
+            mask = mask.view(np.uint8)
+            ptr = mask.ctypes.data_as(PU8) if mask.size else None
+            if nc is None:
+                nc = mask.size
+        if nc is None:
+            nc = self.vec_size(c)
+        a = H(0)
+        self._ck(self.lib.pgd_atom_assemble_cellwise(self.h, mesh, int(kind), int(da), int(db), int(w), int(c), ptr, int(nc),
+                                                     C.byref(a)))
         return a.value
 
     def atom_assemble_facets(self, mesh, facets):

@@ -293,6 +293,7 @@ struct AsmArgs {
     const int *v2c_ptr, *v2c, *row_ptr, *cols;
     const double *w;              // vertex weights (weighted kinds)
     const uint8_t *mask;          // cell mask of the masked instances (MASK = true): cells whose byte is 0 contribute nothing
+    const double *cw;             // cell weights of the cell-weight instances (CW = true): one per cell, in the cell order of the upload
     double *vals;
     int64_t nv;
     int kind, da, db;
@@ -428,7 +429,9 @@ __device__ __forceinline__ double p1_entry(int kind, int da, int db, int i, int 
     return 0.0;
 }
 // MASK (pgd_atom_assemble_cells): the contributions of cells whose mask byte is 0 are skipped, the rest summed in the same order
-template <int D, bool MASK = false>
+// CW (pgd_atom_assemble_cellwise): every finished local entry of cell c is scaled by cw[c] as it is added - one multiply per
+// entry, same order of summation; a masked cell's weight is never read
+template <int D, bool MASK = false, bool CW = false>
 __global__ __launch_bounds__(TPB) void k_assemble_p1(AsmArgs A) {
     __shared__ double s_acc[ASM_CAP];
     __shared__ int s_cols[ASM_CAP];
@@ -457,6 +460,8 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1(AsmArgs A) {
             if constexpr (MASK) { if (!A.mask[A.v2c[k]]) continue; }
             const int4 c4 = A.cells[A.v2c[k]];
             const int u[4] = {c4.x, c4.y, c4.z, c4.w};
+            double cwc = 1.0;
+            if constexpr (CW) cwc = A.cw[A.v2c[k]];
             int i = 0;
 #pragma unroll
             for (int t = 0; t < D + 1; ++t) if (u[t] == r) i = t;
@@ -481,7 +486,8 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1(AsmArgs A) {
                     pos += rc[pos + half - 1] < u[j] ? half : 0;
                     nleft -= half;
                 }
-                acc[pos] += val;
+                if constexpr (CW) acc[pos] += cwc * val;
+                else acc[pos] += val;
             }
         }
     }
@@ -504,7 +510,10 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1(AsmArgs A) {
 // MASK: cell 6 q + t (cube q, type t: the numbering k_lattice_regular_verify checks) contributes iff its mask byte is set - the six
 // bytes of an existing cube are read, nothing else.  `present` keeps following cube EXISTENCE: it places the values in the row's
 // compacted CSR entries, and a slot fed by unmarked cells alone is written as an explicit 0.0.
-template <bool MASK = false>
+// CW: the six weights of an existing cube are read from cw + 6 q - 48 contiguous, 16-byte aligned bytes, three 16-byte loads, at
+// the cube index the masked instance computes - and every table entry of type t is scaled by the weight of that cell as it is
+// added.  Still nothing gathered: reads 4 B + 8 x 48 B (each cube's weights serve its eight corners), writes 8 x 15 B per row.
+template <bool MASK = false, bool CW = false>
 __global__ __launch_bounds__(TPB) void k_assemble_p1_regular(AsmArgs A, int nz) {
     __shared__ double s_acc[TPB * 15];
     __shared__ int s_rp[TPB + 1];
@@ -554,6 +563,14 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1_regular(AsmArgs A, int nz) 
                     for (int t = 0; t < 6; ++t) on[t] = mq[t] != 0;
                 }
             }
+            double cwt[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
+            if constexpr (CW) {
+                if (have) {
+                    const double2 *wq = (const double2 *)(A.cw + 6 * (cx + (int64_t)(nx - 1) * (cy + (int64_t)(A.ny - 1) * cz)));
+                    const double2 w01 = wq[0], w23 = wq[1], w45 = wq[2];
+                    cwt[0] = w01.x; cwt[1] = w01.y; cwt[2] = w23.x; cwt[3] = w23.y; cwt[4] = w45.x; cwt[5] = w45.y;
+                }
+            }
 #pragma unroll
             for (int t = 0; t < 6; ++t) {
                 const int i = box_local(t, o);
@@ -562,7 +579,8 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1_regular(AsmArgs A, int nz) 
                 for (int j = 0; j < 4; ++j) {
                     const int cj = box_corner(t, j);
                     const int q = box_slot((cj & 1) - ox, ((cj >> 1) & 1) - oy, (cj >> 2) - oz);
-                    const double val = s_loc[t * 16 + 4 * i + j];
+                    double val = s_loc[t * 16 + 4 * i + j];
+                    if constexpr (CW) val *= cwt[t];
                     if constexpr (MASK) {
                         if (have) { if (on[t]) acc[q] += val; present |= 1u << q; }
                     } else {
@@ -586,7 +604,7 @@ __global__ __launch_bounds__(TPB) void k_assemble_p1_regular(AsmArgs A, int nz) 
 // Quadratic Lagrange elements on intervals (cell record = v0, v1, midpoint node): owner-computes like
 // the P1 kernel, local 3x3 entries by 4-point Gauss quadrature (exact to degree 7).  These systems are
 // small (time / parameter dimensions), so every lane accumulates straight into its own CSR row.
-template <bool MASK = false>
+template <bool MASK = false, bool CW = false>
 __global__ __launch_bounds__(TPB) void k_assemble_p2_interval(AsmArgs A) {
     const double GX[4] = {0.06943184420297371, 0.33000947820757187, 0.6699905217924281, 0.9305681557970262};
     const double GW[4] = {0.17392742256872692, 0.32607257743127305, 0.32607257743127305, 0.17392742256872692};
@@ -624,7 +642,8 @@ __global__ __launch_bounds__(TPB) void k_assemble_p2_interval(AsmArgs A) {
         for (int j = 0; j < 3; ++j) {
             int pos = 0;
             while (pos < len - 1 && A.cols[ra + pos] < u[j]) ++pos;
-            A.vals[ra + pos] += loc[j];
+            if constexpr (CW) A.vals[ra + pos] += A.cw[A.v2c[k]] * loc[j];
+            else A.vals[ra + pos] += loc[j];
         }
     }
 }
@@ -645,7 +664,7 @@ __constant__ double GJ_W[3][4] = {   // weight (1 - t)^alpha on [0, 1], alpha = 
 __constant__ int P2_EA[2][6] = {{1, 0, 0, 0, 0, 0}, {2, 1, 1, 0, 0, 0}};
 __constant__ int P2_EB[2][6] = {{2, 2, 1, 0, 0, 0}, {3, 3, 2, 3, 2, 1}};
 
-template <int D, bool MASK = false>
+template <int D, bool MASK = false, bool CW = false>
 __global__ __launch_bounds__(64) void k_assemble_p2_simplex(AsmArgs A, const int *__restrict__ cellsN) {
     constexpr int NN = (D + 1) * (D + 2) / 2, NE = NN - (D + 1), NQ = (D == 2) ? 16 : 64;
     const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -656,6 +675,8 @@ __global__ __launch_bounds__(64) void k_assemble_p2_simplex(AsmArgs A, const int
     for (int k = A.v2c_ptr[r]; k < A.v2c_ptr[r + 1]; ++k) {
         if constexpr (MASK) { if (!A.mask[A.v2c[k]]) continue; }
         const int *rec = cellsN + (int64_t)A.v2c[k] * NN;
+        double cwc = 1.0;
+        if constexpr (CW) cwc = A.cw[A.v2c[k]];
         int u[NN], i = 0;
 #pragma unroll
         for (int t = 0; t < NN; ++t) { u[t] = rec[t]; if (u[t] == (int)r) i = t; }
@@ -733,7 +754,8 @@ __global__ __launch_bounds__(64) void k_assemble_p2_simplex(AsmArgs A, const int
         for (int j = 0; j < NN; ++j) {
             int lo = 0, hi = len - 1;            // binary search: cols are sorted and contain u[j]
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (A.cols[ra + mid] < u[j]) lo = mid + 1; else hi = mid; }
-            A.vals[ra + lo] += loc[j];
+            if constexpr (CW) A.vals[ra + lo] += cwc * loc[j];
+            else A.vals[ra + lo] += loc[j];
         }
     }
 }
@@ -1039,6 +1061,19 @@ __global__ __launch_bounds__(TPB) void k_cells_validate(const int4 *__restrict__
     }
 }
 
+// the kernel of the layout for one (MASK, CW) instance
+template <bool MASK, bool CW>
+static void launch_assembly_instance(Ctx *c, Mesh *m, const AsmArgs &A, bool regular, int nz) {
+    const int gb = (int)((m->nv + TPB - 1) / TPB), g64 = (int)((m->nv + 63) / 64);
+    if (m->cellsN && m->gdim == 2) k_assemble_p2_simplex<2, MASK, CW><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
+    else if (m->cellsN) k_assemble_p2_simplex<3, MASK, CW><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
+    else if (m->gdim == 1 && m->nvpc == 3) k_assemble_p2_interval<MASK, CW><<<gb, TPB, 0, c->stream>>>(A);
+    else if (m->gdim == 1) k_assemble_p1<1, MASK, CW><<<gb, TPB, 0, c->stream>>>(A);
+    else if (m->gdim == 2) k_assemble_p1<2, MASK, CW><<<gb, TPB, 0, c->stream>>>(A);
+    else if (regular) k_assemble_p1_regular<MASK, CW><<<gb, TPB, 0, c->stream>>>(A, nz);
+    else k_assemble_p1<3, MASK, CW><<<gb, TPB, 0, c->stream>>>(A);
+}
+
 }  // namespace pgd
 
 using namespace pgd;
@@ -1195,37 +1230,25 @@ static int atom_args(Ctx *c, Mesh *m, const char *fn, int kind, int da, int db, 
     return PGD_OK;
 }
 
-// the assembly kernel of the layout into the zero-filled atom `a`; mask != nullptr: the masked instance of the same kernel
-static void launch_assembly(Ctx *c, Mesh *m, Csr *a, int kind, int da, int db, const double *w, const uint8_t *mask) {
+// the assembly kernel of the layout into the zero-filled atom `a`; mask != nullptr: the masked instance of the same kernel,
+// cw != nullptr: its cell-weight instance (a cell weight, unlike the nodal weight w, keeps the regular-lattice kernel)
+static void launch_assembly(Ctx *c, Mesh *m, Csr *a, int kind, int da, int db, const double *w, const uint8_t *mask,
+                            const double *cw = nullptr) {
     AsmArgs A;
     A.cx = m->coords; A.cy = m->coords + m->nv; A.cz = m->coords + 2 * m->nv;
     A.cells = m->cells; A.v2c_ptr = m->v2c_ptr; A.v2c = m->v2c; A.row_ptr = m->row_ptr; A.cols = m->cols;
-    A.w = w; A.mask = mask; A.vals = a->vals; A.nv = m->nv; A.kind = kind; A.da = da; A.db = db;
+    A.w = w; A.mask = mask; A.cw = cw; A.vals = a->vals; A.nv = m->nv; A.kind = kind; A.da = da; A.db = db;
     A.lattice = (m->lattice && c->asm_lattice) ? 1 : 0;
     for (int k = 0; k < 3; ++k) { A.lat_h[k] = m->lat_h[k]; A.lat_inv[k] = m->lattice ? 1.0 / m->lat_h[k] : 0.0; }
     // (PGD_TUNE_ASM_LATTICE = 2: steps from the coordinates, the r03 form; 3: steps from the indices, in the general kernel)
     A.lat_unit = (A.lattice && m->lattice_unit && (c->asm_lattice == 1 || c->asm_lattice == 3)) ? 1 : 0;
     A.nx = m->sym_nx; A.ny = m->sym_ny;
-    const int gb = (int)((m->nv + TPB - 1) / TPB), g64 = (int)((m->nv + 63) / 64);
     const bool regular = A.lat_unit && m->lattice_regular && !w && c->asm_lattice == 1 && m->max_row <= 15;
     const int nz = regular ? (int)(m->nv / ((int64_t)m->sym_nx * m->sym_ny)) : 0;
-    if (!mask) {
-        if (m->cellsN && m->gdim == 2) k_assemble_p2_simplex<2><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
-        else if (m->cellsN) k_assemble_p2_simplex<3><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
-        else if (m->gdim == 1 && m->nvpc == 3) k_assemble_p2_interval<<<gb, TPB, 0, c->stream>>>(A);
-        else if (m->gdim == 1) k_assemble_p1<1><<<gb, TPB, 0, c->stream>>>(A);
-        else if (m->gdim == 2) k_assemble_p1<2><<<gb, TPB, 0, c->stream>>>(A);
-        else if (regular) k_assemble_p1_regular<<<gb, TPB, 0, c->stream>>>(A, nz);
-        else k_assemble_p1<3><<<gb, TPB, 0, c->stream>>>(A);
-    } else {
-        if (m->cellsN && m->gdim == 2) k_assemble_p2_simplex<2, true><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
-        else if (m->cellsN) k_assemble_p2_simplex<3, true><<<g64, 64, 0, c->stream>>>(A, m->cellsN);
-        else if (m->gdim == 1 && m->nvpc == 3) k_assemble_p2_interval<true><<<gb, TPB, 0, c->stream>>>(A);
-        else if (m->gdim == 1) k_assemble_p1<1, true><<<gb, TPB, 0, c->stream>>>(A);
-        else if (m->gdim == 2) k_assemble_p1<2, true><<<gb, TPB, 0, c->stream>>>(A);
-        else if (regular) k_assemble_p1_regular<true><<<gb, TPB, 0, c->stream>>>(A, nz);
-        else k_assemble_p1<3, true><<<gb, TPB, 0, c->stream>>>(A);
-    }
+    if (!mask && !cw) launch_assembly_instance<false, false>(c, m, A, regular, nz);
+    else if (!cw) launch_assembly_instance<true, false>(c, m, A, regular, nz);
+    else if (!mask) launch_assembly_instance<false, true>(c, m, A, regular, nz);
+    else launch_assembly_instance<true, true>(c, m, A, regular, nz);
 }
 
 int pgd_atom_assemble(pgd_handle h, pgd_handle mh, int kind, int da, int db, pgd_handle wh, pgd_handle *out) {
@@ -1266,6 +1289,38 @@ int pgd_atom_assemble_cells(pgd_handle h, pgd_handle mh, int kind, int da, int d
         (void)free_obj(c, *out, Obj::CSR);                             // the half-built atom goes
         *out = 0;
         return fail(c, PGD_ERR_HIP, "atom_assemble_cells: %s", hipGetErrorString(launched != hipSuccess ? launched : synced));
+    }
+    return PGD_OK;
+}
+
+int pgd_atom_assemble_cellwise(pgd_handle h, pgd_handle mh, int kind, int da, int db, pgd_handle wh, pgd_handle ch,
+                               const uint8_t *cell_mask, int64_t nc, pgd_handle *out) {
+    PGD_CTX(c, h);
+    Mesh *m = get_mesh(c, mh);
+    if (!m || !out) return fail(c, PGD_ERR_INVALID, "atom_assemble_cellwise: invalid mesh handle");
+    const double *w = nullptr;
+    PGD_TRY(atom_args(c, m, "atom_assemble_cellwise", kind, da, db, wh, &w));
+    if (nc != m->nc) return fail(c, PGD_ERR_INVALID, "atom_assemble_cellwise: nc = %lld, the mesh has %lld cells", (long long)nc, (long long)m->nc);
+    Vec *cv = get_vec(c, ch);
+    if (!cv || cv->n != m->nc) return fail(c, PGD_ERR_INVALID, "atom_assemble_cellwise: the cell weights are a vector of one entry per cell (%lld)", (long long)m->nc);
+    struct Scratch {                                                   // the device copy of the mask, released on every way out
+        void *p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } tmp;
+    hipStream_t st = c->stream;
+    if (cell_mask) {
+        PGD_TRY(dev_alloc(c, &tmp.p, (size_t)(nc > 0 ? nc : 1)));
+        if (nc > 0) PGD_HIP(c, hipMemcpyAsync(tmp.p, cell_mask, (size_t)nc, hipMemcpyHostToDevice, st));
+    }
+    Csr *a = nullptr;
+    PGD_TRY(new_csr(c, mh, m, out, &a));
+    launch_assembly(c, m, a, kind, da, db, w, (const uint8_t *)tmp.p, cv->d);
+    const hipError_t launched = hipGetLastError();
+    const hipError_t synced = cell_mask ? hipStreamSynchronize(st) : hipSuccess;      // (the mask is read before it is freed)
+    if (launched != hipSuccess || synced != hipSuccess) {
+        (void)free_obj(c, *out, Obj::CSR);
+        *out = 0;
+        return fail(c, PGD_ERR_HIP, "atom_assemble_cellwise: %s", hipGetErrorString(launched != hipSuccess ? launched : synced));
     }
     return PGD_OK;
 }

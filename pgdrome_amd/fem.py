@@ -308,6 +308,8 @@ class DofLayout:
         self._handles, self._atoms, self._atom_weights = {}, {}, {}
         self._facet_atoms = {}
         self._cell_atoms = {}        # cell-subdomain atoms: _atom_key + (cell-set key,) -> (atom, weakref to the MeshFunction, to the weight)
+        self._cw_atoms = {}          # cell-weighted atoms: _atom_key + (cell-set key | None, (id, version) of the DG0 field's vector) ->
+        #                              (atom, weakref to the field's vector, to the MeshFunction, to the nodal weight)
         self._ones = self._space = None
 
     def _init_p2_slab(self, mesh):
@@ -450,11 +452,14 @@ class DofLayout:
         wkey = None if weight is None else (id(weight), weight.version)
         return (id(be), kind, da if kind in _DA_KINDS else 0, db if kind in _DB_KINDS else 0, wkey)
 
-    def atom(self, kind, da=0, db=0, weight=None, cells=None):
+    def atom(self, kind, da=0, db=0, weight=None, cells=None, cw=None):
         """Cached device atom; weighted atoms are keyed by the weight's identity + version, the identity checked through
         a weak reference: an address (``id``) is reused as soon as a vector dies, and an iterate can end up as the weight
-        of a functional (``assemble(E * F * F * dx)`` with E and F equally "old").  cells: the _CellSet of a dx(id) measure."""
+        of a functional (``assemble(E * F * F * dx)`` with E and F equally "old").  cells: the _CellSet of a dx(id) measure;
+        cw: the vector of a DG0 Function (one value per cell) that multiplies the integrand."""
         be = get_backend()
+        if cw is not None:
+            return self._cellwise_atom(be, kind, da, db, weight, cells, cw)
         if cells is not None:
             return self._cell_atom(be, kind, da, db, weight, cells)
         if kind in (WDUDV, WCONV, WCONVT) and self.part is not None:
@@ -519,25 +524,76 @@ class DofLayout:
         if hit is not None and hit[1]() is cells.mf and (weight is None or hit[2]() is weight):
             return hit[0]
         for k, (a, mref, wref) in list(self._cell_atoms.items()):
-            if k[0] != id(be):
-                continue
-            mf = mref()
-            stale_cells = mf is None or (mf is cells.mf and k[5][0] != cells.gen)
-            stale_w = k[4] is not None and (wref() is None or (weight is not None and k[4][0] == id(weight) and
-                                                                (wref() is not weight or k[4][1] < weight.version)))
-            if k == key or stale_cells or stale_w:
-                self._drop_cell_atom(be, k)
+            bid, _, _, _, wkey, ckey = k
+            if bid == id(be) and (k == key or _stale_cells(ckey, mref, cells) or _stale_vector(wkey, wref, weight)):
+                self._drop_cell_atom(be, self._cell_atoms, k)
         a = fn(self.handle(), key[1], key[2], key[3], weight.dev() if weight is not None else 0, cells.mask())
         self._cell_atoms[key] = (a, weakref.ref(cells.mf), weakref.ref(weight) if weight is not None else (lambda: None))
         return a
 
-    def _drop_cell_atom(self, be, key):
-        stale = self._cell_atoms.pop(key)[0]
+    def _cellwise_atom(self, be, kind, da, db, weight, cells, cw):
+        """The atom with a cell-wise constant coefficient (pgd_atom_assemble_cellwise), cached per backend, kind, (da, db), nodal
+        weight, cell set and field.  The field is keyed like a nodal weight - identity + version of its vector, the identity
+        checked through a weak reference - and evicted like one: atoms of older versions of this field, of fields that died and
+        of stale weights / cell sets are freed here with their vector-valued embeddings; the atoms of ONE version (the nine of
+        weighted elasticity) live side by side."""
+        if self.part is not None:
+            raise NotImplementedError("cell-wise constant (DG0) coefficients on a sharded (slab) layout")
+        fn = getattr(be, "atom_cellwise", None)
+        if fn is None:
+            raise NotImplementedError("cell-wise constant (DG0) coefficients need a backend that assembles cell-weighted atoms "
+                                      "(atom_cellwise); %r has none" % (getattr(be, "name", type(be).__name__),))
+        if cw.V.mesh() is not self.mesh:
+            raise ValueError("the DG0 coefficient lives on a different mesh than the integral")
+        key = self._atom_key(be, kind, da, db, weight) + (cells.key if cells is not None else None, (id(cw), cw.version))
+        hit = self._cw_atoms.get(key)
+        if (hit is not None and hit[1]() is cw and (cells is None or hit[2]() is cells.mf)
+                and (weight is None or hit[3]() is weight)):
+            return hit[0]
+        for k, (a, cref, mref, wref) in list(self._cw_atoms.items()):
+            bid, _, _, _, wkey, ckey, fkey = k
+            if bid == id(be) and (k == key or _stale_vector(fkey, cref, cw) or _stale_cells(ckey, mref, cells)
+                                  or _stale_vector(wkey, wref, weight)):
+                self._drop_cell_atom(be, self._cw_atoms, k)
+        a = fn(self.handle(), key[1], key[2], key[3], weight.dev() if weight is not None else 0, cw.dev(),
+               cells.mask() if cells is not None else None)
+        none = lambda: None
+        self._cw_atoms[key] = (a, weakref.ref(cw), weakref.ref(cells.mf) if cells is not None else none,
+                               weakref.ref(weight) if weight is not None else none)
+        return a
+
+    def _drop_cell_atom(self, be, store, key):
+        """Free the atom of `key` in `store` (_cell_atoms or _cw_atoms), the vector-valued embeddings built from it and
+        everything keyed by its handle."""
+        stale = store.pop(key)[0]
         for blk in list(self.mesh._layouts.values()):
             if isinstance(blk, BlockLayout) and blk.base is self:
                 blk._drop_derived(be, stale)
         _purge_atom(stale)
         be.atom_free(stale)
+
+
+def _stale_vector(vkey, ref, current):
+    """Is a cached atom keyed by a vector (vkey = (id, version) or None: a nodal weight or a DG0 field, `ref` the weak reference
+    kept with it) out of date?  Yes when the vector died, and when `current` - the vector of the request at hand - lives at
+    that address but is another object or a newer version.  Atoms of the SAME version stay: the (da, db) atoms of one weight
+    live side by side."""
+    if vkey is None:
+        return False
+    if ref() is None:
+        return True
+    return current is not None and vkey[0] == id(current) and (ref() is not current or vkey[1] < current.version)
+
+
+def _stale_cells(ckey, ref, cells):
+    """Is a cached atom keyed by a cell set (ckey = (generation, id) or None, `ref` the weak reference to its MeshFunction) out
+    of date?  Yes when the MeshFunction died, and when `cells` - the _CellSet of the request at hand - is of the same
+    MeshFunction in another generation of its markers."""
+    if ckey is None:
+        return False
+    if ref() is None:
+        return True
+    return cells is not None and ref() is cells.mf and ckey[0] != cells.gen
 
 
 def IntervalMesh(n, a, b):
@@ -658,10 +714,50 @@ class _DofMap:
         return np.arange(self._V.dim())
 
 
+class _CellLayout:
+    """The dofs of a DG0 space: one per cell, dof i = cell i of mesh.cells(), located at the cell's midpoint.  It carries
+    coefficients only - no device mesh, no atoms."""
+    part = None
+
+    def __init__(self, mesh):
+        self.mesh, self.degree = mesh, 0
+        self.coords = mesh.coordinates()[mesh.cells()].mean(axis=1)
+        self.n = self.coords.shape[0]
+        self.vertex_nodes = None
+
+
+class _DG0Element(_Element):
+    def __str__(self):
+        return "FiniteElement('Discontinuous Lagrange', %s, 0)" % (self._cell,)
+
+    __repr__ = __str__
+
+    def family(self):
+        return "Discontinuous Lagrange"
+
+
+_DG_FAMILIES = ("DG", "Discontinuous Lagrange")
+
+
 class FunctionSpace:
     _ncomp = 1
+    _dg0 = False                 # a DG0 space: coefficients that are constant per cell (one undifferentiated factor of a dx integrand)
 
     def __init__(self, mesh, family="CG", degree=1):
+        if str(family) in _DG_FAMILIES:
+            if int(degree) != 0:
+                raise NotImplementedError("discontinuous Lagrange spaces of degree %d: only DG0 (cell-wise constant coefficients)"
+                                          % int(degree))
+            if mesh.part is not None:
+                raise NotImplementedError("DG0 coefficients on a row-sharded mesh")
+            self._mesh, self._dg0 = mesh, True
+            lay = mesh._layouts.get("dg0")
+            if lay is None:
+                lay = mesh._layouts["dg0"] = _CellLayout(mesh)
+            self._lay = lay
+            self._element = _DG0Element(mesh.ufl_cell(), 0)
+            self._d2v = None     # dof i = cell i on every mesh (intervals included)
+            return
         if str(family) not in ("CG", "P", "Lagrange"):
             raise NotImplementedError("FunctionSpace family %r: only Lagrange ('CG'/'P')" % (family,))
         self._mesh = mesh
@@ -777,17 +873,18 @@ class BlockLayout:
             self._handles[id(be)] = h
         return h
 
-    def atom(self, kind, da=0, db=0, weight=None, cv=None, cu=None, cells=None):
+    def atom(self, kind, da=0, db=0, weight=None, cv=None, cu=None, cells=None, cw=None):
         """Scalar atom (kind, da, db) in block (cv, cu); cv = cu = None: in every diagonal block (norms).  A weight is a
         scalar field of the base layout (_coef_vec(..., weight=True)): the scalar weighted atom, embedded.  cells: the
-        _CellSet of a dx(id) measure - the base layout's masked atom, embedded."""
-        if cells is not None:
+        _CellSet of a dx(id) measure - the base layout's masked atom, embedded; cw: the vector of a DG0 coefficient - the base
+        layout's cell-weighted atom, embedded."""
+        if cells is not None or cw is not None:
             if self.part is not None:
-                raise NotImplementedError("cell-subdomain integrals dx(id) on a sharded (slab) vector-valued layout")
+                raise NotImplementedError("cell-subdomain integrals dx(id) and DG0 coefficients on a sharded (slab) vector-valued layout")
             if weight is not None and weight.size() != self.base.n:
                 raise NotImplementedError("a weight on a vector-valued space is a scalar field of its Lagrange degree")
             be = get_backend()
-            src = self.base.atom(kind, da, db, weight, cells=cells)     # (frees stale sources, and their embeddings with them)
+            src = self.base.atom(kind, da, db, weight, cells=cells, cw=cw)     # (frees stale sources, and their embeddings with them)
             key = (id(be), src, cv, cu)
             a = self._catoms.get(key)
             if a is None:
@@ -829,7 +926,7 @@ class BlockLayout:
         return self._embedded(self.base.facet_atom(ids), cv, cu)
 
     def _drop_derived(self, be, src):
-        """Free the embeddings of a scalar cell-subdomain atom that its base layout frees."""
+        """Free the embeddings of a scalar cell-subdomain / cell-weighted atom that its base layout frees."""
         for k in [k for k in self._catoms if k[0] == id(be) and k[1] == src]:
             a = self._catoms.pop(k)
             _purge_atom(a)
@@ -881,6 +978,8 @@ class VectorFunctionSpace(FunctionSpace):
     """Vector-valued Lagrange space, dofs interleaved by component (node-major)."""
 
     def __init__(self, mesh, family="CG", degree=1, dim=None):
+        if str(family) in _DG_FAMILIES:
+            raise NotImplementedError("vector-valued discontinuous Lagrange spaces (a DG0 coefficient is a scalar field)")
         if str(family) not in ("CG", "P", "Lagrange"):
             raise NotImplementedError("VectorFunctionSpace family %r: only Lagrange ('CG'/'P')" % (family,))
         self._mesh = mesh
@@ -1228,7 +1327,7 @@ class _FastProd(Expr):
         if t is Measure:
             return _FastForm(self.fs, o)
         if t is Function:
-            if o._V._ncomp == 1:
+            if o._V._ncomp == 1 and not o._V._dg0:
                 return _FastProd(self.fs + ((o, None, None),))
         elif t is _FastProd:
             return _FastProd(self.fs + o.fs)
@@ -1320,6 +1419,8 @@ class Grad:
     """grad(f): only meaningful inside inner()/dot()."""
 
     def __init__(self, f):
+        if type(f) is Function and f._V._dg0:
+            raise NotImplementedError("grad of a DG0 (cell-wise constant) function")
         if type(f) is Function and f._V._ncomp == 1:
             self.num, self.consts, self.leaf, self.comp = 1.0, (), f, None
             return
@@ -1644,6 +1745,8 @@ class Equation:
 
 class Argument(Expr):
     def __init__(self, V, number):
+        if V._dg0:
+            raise NotImplementedError("DG0 trial / test functions: a DG0 space carries coefficients only")
         self._V, self.number = V, number
 
     def function_space(self):
@@ -1705,6 +1808,8 @@ class Function(Expr):
         return self._V.ufl_element()
 
     def compute_vertex_values(self, mesh=None):
+        if self._V._dg0:
+            raise NotImplementedError("compute_vertex_values of a DG0 function (it has one value per cell, not per vertex)")
         vn = self._V._lay.vertex_nodes
         nc = self._V._ncomp
         if nc > 1:     # dolfin: all vertex values of component 0, then component 1, ...
@@ -1739,11 +1844,11 @@ class Function(Expr):
         self.assign(other)
 
     def __mul__(self, o):
-        # products of plain scalar Functions and their integrals: _FastProd
-        if self._V._ncomp == 1:
+        # products of plain scalar (nodal) Functions and their integrals: _FastProd; a DG0 factor takes the general path
+        if self._V._ncomp == 1 and not self._V._dg0:
             t = type(o)
             if t is Function:
-                if o._V._ncomp == 1:
+                if o._V._ncomp == 1 and not o._V._dg0:
                     return _FastProd(((self, None, None), (o, None, None)))
             elif t is _FastProd:
                 return _FastProd(((self, None, None),) + o.fs)
@@ -1752,6 +1857,8 @@ class Function(Expr):
         return Expr.__mul__(self, o)
 
     def dx(self, *axes):
+        if self._V._dg0:
+            raise NotImplementedError("derivative of a DG0 (cell-wise constant) function")
         if self._V._ncomp == 1 and len(axes) == 1:
             return _FastProd(((self, int(axes[0]), None),))
         return Expr.dx(self, *axes)
@@ -1764,9 +1871,16 @@ class Function(Expr):
         return [Term(1.0, (Factor(self),))]
 
     def __call__(self, *x):
+        _refuse_dg0(self, "point evaluation")
         if len(x) == 1 and hasattr(x[0], "__len__"):
             x = tuple(x[0])
         return _point_eval(self, np.array([float(v) for v in x]))
+
+
+def _refuse_dg0(f, what):
+    """A DG0 Function is a coefficient of dx integrands and nothing else: say so where anything else is asked of it."""
+    if isinstance(f, Function) and f._V._dg0:
+        raise NotImplementedError("%s of a DG0 (cell-wise constant) function: it can only multiply a dx integrand" % (what,))
 
 
 def point_basis(lay, x, grad=False):
@@ -1816,6 +1930,7 @@ def _point_eval(f, x):
 def point_gradient(f, x):
     """Gradient of a scalar Function at a point, taken in the cell that contains it (a cell-wise polynomial:
     what projecting the derivative onto DG(degree - 1) gives, model.py:1088-1205)."""
+    _refuse_dg0(f, "point gradient")
     V = f._V
     if V._ncomp > 1:
         raise NotImplementedError("gradient of a vector-valued function")
@@ -2043,7 +2158,10 @@ def interpolate(v, V):
     if isinstance(v, Function):
         if v._V._lay is V._lay:
             f._vec.assign_from(v._vec)
+        elif V._dg0 and v._V._ncomp > 1:
+            raise NotImplementedError("interpolation of a vector-valued function into a DG0 space")
         else:
+            _refuse_dg0(v, "interpolation into another space")
             f._vec._host = np.array([v(x) for x in V._lay.coords])
             f._vec.touched_host()
     elif isinstance(v, Expression):
@@ -2062,6 +2180,8 @@ def interpolate(v, V):
 def project(v, V, bcs=None, **kw):
     """L2 projection onto P1.  With P1-interpolated data the projection of the
     interpolant is the interpolant itself."""
+    if V._dg0:
+        raise NotImplementedError("project onto a DG0 space (interpolate takes the value at the cell midpoint)")
     return interpolate(v, V)
 
 
@@ -2183,6 +2303,8 @@ def _facet_nodes(lay, facet_ids):
 
 class DirichletBC:
     def __init__(self, V, value, marker, tag=None, method="topological"):
+        if V._dg0:
+            raise NotImplementedError("DirichletBC on a DG0 space: it carries coefficients only")
         self._V, self._value = V, value
         lay = V._lay
         if isinstance(marker, MeshFunction):
@@ -2296,11 +2418,12 @@ def _bc_vertices(bcs):
 class _AtomRef:
     """One atom of one mesh with a scalar coefficient; on a vector-valued space the atom sits in the block
     (test component cv, trial component cu)."""
-    __slots__ = ("coef", "kind", "da", "db", "weight", "cv", "cu", "cells")
+    __slots__ = ("coef", "kind", "da", "db", "weight", "cv", "cu", "cells", "cw")
 
-    def __init__(self, coef, kind, da=0, db=0, weight=None, cv=None, cu=None, cells=None):
+    def __init__(self, coef, kind, da=0, db=0, weight=None, cv=None, cu=None, cells=None, cw=None):
         self.coef, self.kind, self.da, self.db, self.weight, self.cv, self.cu = coef, kind, da, db, weight, cv, cu
         self.cells = cells           # the _CellSet of a dx(id) integral, None: the whole mesh
+        self.cw = cw                 # the vector of a DG0 coefficient of the integrand, None: no cell-wise factor
 
     def _wkey(self):
         # (the facet set of a DS_MASS atom by its contents: every assemble() of the same ds(tag) builds a new one)
@@ -2310,18 +2433,19 @@ class _AtomRef:
 
     def key(self):
         return (self.kind, self.da if self.kind in _DA_KINDS else 0, self.db if self.kind in _DB_KINDS else 0,
-                self._wkey(), self.cv or 0, self.cu or 0, self.cells.key if self.cells is not None else None)
+                self._wkey(), self.cv or 0, self.cu or 0, self.cells.key if self.cells is not None else None,
+                (id(self.cw), self.cw.version) if self.cw is not None else None)
 
     def transposed_key(self):
         kind = {CONV: CONVT, CONVT: CONV, WCONV: WCONVT, WCONVT: WCONV}.get(self.kind, self.kind)
         k = self.key()
-        return (kind, k[2], k[1], k[3], k[5], k[4], k[6])
+        return (kind, k[2], k[1], k[3], k[5], k[4], k[6], k[7])
 
 
-def _lay_atom(lay, kind, da, db, w, cv=None, cu=None, cells=None):
+def _lay_atom(lay, kind, da, db, w, cv=None, cu=None, cells=None, cw=None):
     """Atom of a layout; on a vector-valued layout in block (cv, cu), a side without a vector-valued factor
     (the all-ones function of a functional) using component 0.  DS_MASS: w is the _FacetSet of the ds measure.
-    cells: the _CellSet of a dx(id) measure (None: the whole mesh)."""
+    cells: the _CellSet of a dx(id) measure (None: the whole mesh); cw: the vector of a DG0 coefficient (None: none)."""
     if kind == DS_MASS:
         if isinstance(lay, BlockLayout):
             return lay.facet_atom(w.ids, cv or 0, cu or 0)
@@ -2329,10 +2453,10 @@ def _lay_atom(lay, kind, da, db, w, cv=None, cu=None, cells=None):
             raise ValueError("component of a vector-valued function in an integrand over a scalar space")
         return lay.facet_atom(w.ids)
     if isinstance(lay, BlockLayout):
-        return lay.atom(kind, da, db, w, cv or 0, cu or 0, cells=cells)
+        return lay.atom(kind, da, db, w, cv or 0, cu or 0, cells=cells, cw=cw)
     if cv is not None or cu is not None:
         raise ValueError("component of a vector-valued function in an integrand over a scalar space")
-    return lay.atom(kind, da, db, w, cells=cells)
+    return lay.atom(kind, da, db, w, cells=cells, cw=cw)
 
 
 def _coef_vec(leaf, lay, weight=False):
@@ -2779,9 +2903,9 @@ def _ones(lay):
     return lay._ones
 
 
-def _term_operands(term, lay, cells=None):
+def _term_operands(term, lay, cells=None, cw=None):
     """(atom, f, g, symmetric) with  integral of the term = coef * f^T A g  for a term without arguments (over the cells of
-    a dx(id) measure: `cells`)."""
+    a dx(id) measure: `cells`; with the DG0 coefficient `cw`, already split off the term by _cellwise)."""
     test, trial, coefs, gd = _classify(term, lay)
     if test is not None or trial is not None:
         raise ValueError("scalar assemble of a form with arguments")
@@ -2792,17 +2916,17 @@ def _term_operands(term, lay, cells=None):
             raise NotImplementedError("weighted inner(grad, grad) functional with several weights")
         f, g = _coef_vec(gd.leaf, lay), _coef_vec(gd.other, lay)
         if coefs:
-            atom = lay.atom(WSTIFF, 0, 0, _coef_vec(coefs[0].leaf, lay), cells=cells)
+            atom = lay.atom(WSTIFF, 0, 0, _coef_vec(coefs[0].leaf, lay), cells=cells, cw=cw)
         else:
-            atom = lay.atom(STIFF, cells=cells)
+            atom = lay.atom(STIFF, cells=cells, cw=cw)
         return atom, f, g, True
     if len(coefs) == 0:
         one = _ones(lay)
-        return _lay_atom(lay, MASS, 0, 0, None, cells=cells), one, one, False
+        return _lay_atom(lay, MASS, 0, 0, None, cells=cells, cw=cw), one, one, False
     if len(coefs) == 1:
         c = coefs[0]
         kind, da, db, w = _atom_for(Factor(None, None), Factor(None, c.deriv), [], lay)
-        return _lay_atom(lay, kind, da, db, w, None, c.comp, cells), _ones(lay), _coef_vec(c.leaf, lay), False
+        return _lay_atom(lay, kind, da, db, w, None, c.comp, cells, cw), _ones(lay), _coef_vec(c.leaf, lay), False
     # f (test side) is the first factor, g (trial side) the second, further undifferentiated ones weight
     der = [c for c in coefs if c.deriv is not None]
     plain = [c for c in coefs if c.deriv is None]
@@ -2813,12 +2937,12 @@ def _term_operands(term, lay, cells=None):
     ordered = der + plain
     f, g, rest = ordered[0], ordered[1], ordered[2:]
     kind, da, db, w = _atom_for(Factor(None, f.deriv), Factor(None, g.deriv), rest, lay)
-    return (_lay_atom(lay, kind, da, db, w, f.comp, g.comp, cells), _coef_vec(f.leaf, lay), _coef_vec(g.leaf, lay),
+    return (_lay_atom(lay, kind, da, db, w, f.comp, g.comp, cells, cw), _coef_vec(f.leaf, lay), _coef_vec(g.leaf, lay),
             (kind in _SYMMETRIC_KINDS or (kind in (DUDV, WDUDV) and da == db)) and f.comp == g.comp)
 
 
-def _term_scalar(term, lay, cells=None):
-    atom, f, g, symmetric = _term_operands(term, lay, cells)
+def _term_scalar(term, lay, cells=None, cw=None):
+    atom, f, g, symmetric = _term_operands(term, lay, cells, cw)
     return term.coef * _bilinear_scalar(lay, atom, f, g, symmetric=symmetric)
 
 
@@ -2894,8 +3018,9 @@ def _fast_scalar(form):
     return _bilinear_scalar(lay, atom, f, g, symmetric=sym)
 
 
-def _term_vector(term, lay, cells=None):
-    """(coef, atom handle, coefficient Vector g) with  b += coef * A g  (A over the cells of a dx(id) measure: `cells`)."""
+def _term_vector(term, lay, cells=None, cw=None):
+    """(coef, atom handle, coefficient Vector g) with  b += coef * A g  (A over the cells of a dx(id) measure: `cells`, with
+    the DG0 coefficient `cw`)."""
     test, trial, coefs, gd = _classify(term, lay)
     if trial is not None:
         raise ValueError("linear form with a trial function")
@@ -2909,12 +3034,13 @@ def _term_vector(term, lay, cells=None):
             raise ValueError("two test functions in one integrand")
         if len(coefs) > 1:
             raise NotImplementedError("several weights on inner(grad, grad)")
-        atom = lay.atom(WSTIFF, 0, 0, _coef_vec(coefs[0].leaf, lay), cells=cells) if coefs else lay.atom(STIFF, cells=cells)
+        atom = (lay.atom(WSTIFF, 0, 0, _coef_vec(coefs[0].leaf, lay), cells=cells, cw=cw) if coefs
+                else lay.atom(STIFF, cells=cells, cw=cw))
         return term.coef, atom, _coef_vec(b, lay)
     if test is None:
         raise ValueError("linear form without a test function")
     if not coefs:
-        return term.coef, _lay_atom(lay, MASS, 0, 0, None, test.comp, None, cells), _ones(lay)
+        return term.coef, _lay_atom(lay, MASS, 0, 0, None, test.comp, None, cells, cw), _ones(lay)
     der = [c for c in coefs if c.deriv is not None]
     plain = [c for c in coefs if c.deriv is None]
     if len(der) > 1:
@@ -2925,10 +3051,10 @@ def _term_vector(term, lay, cells=None):
     ordered = der + plain
     g, rest = ordered[0], ordered[1:]
     kind, da, db, w = _atom_for(test, Factor(None, g.deriv), rest, lay)
-    return term.coef, _lay_atom(lay, kind, da, db, w, test.comp, g.comp, cells), _coef_vec(g.leaf, lay)
+    return term.coef, _lay_atom(lay, kind, da, db, w, test.comp, g.comp, cells, cw), _coef_vec(g.leaf, lay)
 
 
-def _term_matrix(term, lay, cells=None):
+def _term_matrix(term, lay, cells=None, cw=None):
     test, trial, coefs, gd = _classify(term, lay)
     if gd is not None:
         a, b = gd.leaf, gd.other
@@ -2939,11 +3065,11 @@ def _term_matrix(term, lay, cells=None):
         if len(coefs) > 1 or (coefs and coefs[0].deriv is not None):
             raise NotImplementedError("several / differentiated weights on inner(grad, grad)")
         w = _coef_vec(coefs[0].leaf, lay) if coefs else None
-        return _AtomRef(term.coef, WSTIFF if w is not None else STIFF, 0, 0, w, cells=cells)
+        return _AtomRef(term.coef, WSTIFF if w is not None else STIFF, 0, 0, w, cells=cells, cw=cw)
     if test is None or trial is None:
         raise ValueError("bilinear form needs a trial and a test function")
     kind, da, db, w = _atom_for(test, trial, coefs, lay)
-    return _AtomRef(term.coef, kind, da, db, w, test.comp, trial.comp, cells)
+    return _AtomRef(term.coef, kind, da, db, w, test.comp, trial.comp, cells, cw)
 
 
 class AssembledVector(Vector):
@@ -2984,7 +3110,7 @@ class Matrix:
         """Atoms with equal keys summed: (handles, coefs)."""
         acc = {}
         for r in self.refs:
-            h = _lay_atom(self.lay, r.kind, r.da, r.db, r.weight, r.cv, r.cu, r.cells)
+            h = _lay_atom(self.lay, r.kind, r.da, r.db, r.weight, r.cv, r.cu, r.cells, r.cw)
             acc[h] = acc.get(h, 0.0) + r.coef
         return list(acc), [acc[h] for h in acc]
 
@@ -3028,17 +3154,19 @@ def assemble(form, tensor=None, **kw):
     if isinstance(form, numbers.Real):
         return float(form)
     if type(form) is _FastForm and form.measure.kind == "dx" and form.measure.subdomain_id is None:
-        return _fast_scalar(form)            # (its plans know meshes, not cell sets: dx(id) takes the general path)
+        return _fast_scalar(form)            # (its plans know meshes, not cell sets: dx(id) takes the general path, and so does
+        #                                       a DG0 factor, which never enters a _FastProd)
     rank = form.rank()
     if rank == 0:
         total = 0.0
         for t, m in form.integrals:
             mesh = m.mesh if m.mesh is not None else Form([(t, m)]).mesh()
+            t, cw = _cellwise(t, m)
             if m.kind == "ds":
                 total += _ds_scalar(t, _integral_layout(t, mesh), m)
             else:
                 lay = _integral_layout(t, mesh)
-                total += _term_scalar(t, lay, _dx_cells(lay, m))
+                total += _term_scalar(t, lay, _dx_cells(lay, m), cw)
         return total
     mesh = form.mesh()
     V = _argument_space(form, 0)
@@ -3046,8 +3174,25 @@ def assemble(form, tensor=None, **kw):
         out = AssembledVector(V)
         _assemble_vector_into(form, V._lay, out)
         return out
-    return Matrix(V, [_ds_matrix(t, V._lay, m) if m.kind == "ds" else _term_matrix(t, V._lay, _dx_cells(V._lay, m))
-                      for t, m in form.integrals])
+    return Matrix(V, [_ds_matrix(t, V._lay, m) if m.kind == "ds" else _term_matrix(t, V._lay, _dx_cells(V._lay, m), cw)
+                      for (t, cw), m in ((_cellwise(t, m), m) for t, m in form.integrals)])
+
+
+def _cellwise(term, measure):
+    """Split the DG0 factor off an integrand: (the term without it, the vector of its cell values), or (term, None).  A cell-wise
+    constant scales a cell's finished local matrix, so everything else about the term is classified as if it were not there."""
+    dg = [f for f in term.factors if (getattr(getattr(f.leaf, "_V", None), "_dg0", False)
+                                      or getattr(getattr(f.other, "_V", None), "_dg0", False))]
+    if not dg:
+        return term, None
+    if len(dg) > 1:
+        raise NotImplementedError("more than one DG0 (cell-wise constant) factor in one integrand")
+    f = dg[0]
+    if f.deriv is not None:
+        raise NotImplementedError("derivative of a DG0 (cell-wise constant) function in an integrand")
+    if measure.kind != "dx":
+        raise NotImplementedError("DG0 coefficients in exterior-facet integrals ds")
+    return term.with_factors(tuple(g for g in term.factors if g is not f)), f.leaf._vec
 
 
 # cell-subdomain integrals dx(id): the atoms of the marked cells (pgd_atom_assemble_cells), cached with the layout per cell
@@ -3303,7 +3448,8 @@ def _argument_space(form, number):
 
 def _assemble_vector_into(form, lay, out):
     """out = sum_s c_s A_s g_s.  Small systems on the host mirror, large ones by axpy on the device."""
-    pieces = [_ds_vector(t, lay, m) if m.kind == "ds" else _term_vector(t, lay, _dx_cells(lay, m)) for t, m in form.integrals]
+    pieces = [_ds_vector(t, lay, m) if m.kind == "ds" else _term_vector(t, lay, _dx_cells(lay, m), cw)
+              for (t, cw), m in ((_cellwise(t, m), m) for t, m in form.integrals)]
     merged = {}
     for c, atom, g in pieces:
         key = (atom, id(g))
@@ -3333,6 +3479,7 @@ def norm(f, norm_type="L2", mesh=None):
     """dolfin.norm: L2 norm of a Function (consistent mass), l2 of a Vector."""
     if isinstance(f, Vector):
         return f.norm("l2")
+    _refuse_dg0(f, "norm")
     kind = norm_type.lower()
     m = f._V._lay
     if kind == "l2":
@@ -3347,6 +3494,8 @@ def norm(f, norm_type="L2", mesh=None):
 
 def errornorm(u, uh, norm_type="L2", degree_rise=3, mesh=None):
     """L2 distance between two P1 functions (or an Expression and a function) on uh's mesh."""
+    _refuse_dg0(uh, "errornorm")
+    _refuse_dg0(u, "errornorm")
     V = uh._V
     a = interpolate(u, V) if not (isinstance(u, Function) and u._V is V) else u
     d = Function(V)

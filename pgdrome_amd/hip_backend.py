@@ -32,7 +32,7 @@ class HipBackend:
         "mesh": "mesh_upload", "vec_zeros": "vec_alloc", "vec_to_host": "vec_download", "atom": "atom_assemble",
         "atom_values": "atom_download", "combine": "op_combine", "pcg": "pcg_solve", "slots_get": "slots_download",
         "slots_set": "slots_upload", "atom_facets": "atom_assemble_facets",
-        "atom_cells": "atom_assemble_cells",
+        "atom_cells": "atom_assemble_cells", "atom_cellwise": "atom_assemble_cellwise",
     }
 
     def __getattr__(self, name):

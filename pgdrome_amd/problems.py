@@ -13,6 +13,8 @@ they evaluate vectorised on multi-million-vertex meshes.
 """
 from __future__ import annotations
 
+import numpy as np
+
 from . import fem
 
 
@@ -557,6 +559,71 @@ def inclusion_heat(space_mesh, n_k=17, k_range=(0.1, 10.0), f=1.0, center=None, 
     return dict(name="inclusion_heat", name_coord=["X", "kappa"], modes_info=["U", "Node", "Scalar"], Vs=Vs,
                 dom_fct=dom_fct, bc_fct=bc_fct, load=load, param=param, rhs_fct=rhs_fct, lhs_fct=lhs_fct,
                 probs=["x", "kappa"], PGD_nmax=PGD_nmax, PGD_tol=PGD_tol)
+
+
+# ----------------------------- heterogeneous conductivity, one value per cell: kappa0 + theta kappa1
+def _dg0_field(V0, k):
+    """A DG0 Function of V0: `k` itself when it is one, else the array of its cell values (cell order of mesh.cells())."""
+    if isinstance(k, fem.Function):
+        if k.function_space().mesh() is not V0.mesh() or not k.function_space()._dg0:
+            raise ValueError("cellwise_heat: the conductivities are DG0 functions of the space mesh")
+        return k
+    f = fem.Function(V0)
+    f.vector()[:] = np.asarray(k, dtype=np.float64)
+    return f
+
+
+def cellwise_heat(space_mesh, kappa0, kappa1, n_t=17, t_range=(0.1, 10.0), f=1.0, PGD_nmax=10, PGD_tol=1e-8):
+    """-div((kappa0 + theta kappa1) grad u) = f in Omega, u = 0 on the whole boundary, with kappa0 and kappa1 constant per cell -
+    DG0 Functions of `space_mesh`, or arrays of one value per cell - and u = u(x; theta), theta a separated 1-D P1
+    coordinate: one term of a Karhunen-Loeve-type material field.  The callbacks write the conductivities as a PGDrome user
+    does, ``kappa * inner(grad(u), grad(v)) * dx``.  Operator  K[kappa0] (x) M_theta + K[kappa1] (x) Mw_theta  (w = theta),
+    K[kappa] the stiffness with the cell-wise coefficient kappa; load  f 1_x (x) 1_theta."""
+    t_mesh = fem.IntervalMesh(n_t - 1, t_range[0], t_range[1])
+    meshes = [space_mesh, t_mesh]
+    Vs = [fem.FunctionSpace(space_mesh, "CG", 1), fem.FunctionSpace(t_mesh, "CG", 1)]
+    V0 = fem.FunctionSpace(space_mesh, "DG", 0)
+    load = [[fem.interpolate(fem.Expression("%r" % float(f), degree=1), Vs[0])],
+            [fem.interpolate(fem.Expression("1.0", degree=1), Vs[1])]]
+    theta = fem.interpolate(fem.Expression("x[0]", degree=1), Vs[1])
+    param = {"theta": theta, "kappa0": _dg0_field(V0, kappa0), "kappa1": _dg0_field(V0, kappa1), "f": float(f)}
+
+    def bc_fct(Vs, dom, param):
+        return [fem.DirichletBC(Vs[0], 0, _on_boundary), 0]
+
+    def lhs_fct(u, v, Fs, meshes, dom, param, typ, dim):
+        k0, k1, th = param["kappa0"], param["kappa1"], param["theta"]
+        if typ == "x":
+            return (fem.Constant(fem.assemble(Fs[1] * Fs[1] * fem.dx(meshes[1])))
+                    * k0 * fem.inner(fem.grad(u), fem.grad(v)) * fem.dx(meshes[0])
+                    + fem.Constant(fem.assemble(th * Fs[1] * Fs[1] * fem.dx(meshes[1])))
+                    * k1 * fem.inner(fem.grad(u), fem.grad(v)) * fem.dx(meshes[0]))
+        return (fem.Constant(fem.assemble(k0 * fem.inner(fem.grad(Fs[0]), fem.grad(Fs[0])) * fem.dx(meshes[0])))
+                * u * v * fem.dx(meshes[1])
+                + fem.Constant(fem.assemble(k1 * fem.inner(fem.grad(Fs[0]), fem.grad(Fs[0])) * fem.dx(meshes[0])))
+                * th * u * v * fem.dx(meshes[1]))
+
+    def rhs_fct(u, v, Fs, meshes, dom, param, Q, PGD_func, typ, nE, dim):
+        k0, k1, th = param["kappa0"], param["kappa1"], param["theta"]
+        if typ == "x":
+            l = fem.Constant(fem.assemble(Q[1][0] * Fs[1] * fem.dx(meshes[1]))) * Q[0][0] * v * fem.dx(meshes[0])
+            for old in range(nE):
+                l += (-fem.Constant(fem.assemble(PGD_func[1][old] * Fs[1] * fem.dx(meshes[1])))
+                      * k0 * fem.inner(fem.grad(PGD_func[0][old]), fem.grad(v)) * fem.dx(meshes[0])
+                      - fem.Constant(fem.assemble(th * PGD_func[1][old] * Fs[1] * fem.dx(meshes[1])))
+                      * k1 * fem.inner(fem.grad(PGD_func[0][old]), fem.grad(v)) * fem.dx(meshes[0]))
+            return l
+        l = fem.Constant(fem.assemble(Q[0][0] * Fs[0] * fem.dx(meshes[0]))) * Q[1][0] * v * fem.dx(meshes[1])
+        for old in range(nE):
+            l += (-fem.Constant(fem.assemble(k0 * fem.inner(fem.grad(PGD_func[0][old]), fem.grad(Fs[0])) * fem.dx(meshes[0])))
+                  * PGD_func[1][old] * v * fem.dx(meshes[1])
+                  - fem.Constant(fem.assemble(k1 * fem.inner(fem.grad(PGD_func[0][old]), fem.grad(Fs[0])) * fem.dx(meshes[0])))
+                  * th * PGD_func[1][old] * v * fem.dx(meshes[1]))
+        return l
+
+    return dict(name="cellwise_heat", name_coord=["X", "theta"], modes_info=["U", "Node", "Scalar"], Vs=Vs,
+                bc_fct=bc_fct, load=load, param=param, rhs_fct=rhs_fct, lhs_fct=lhs_fct,
+                probs=["x", "theta"], PGD_nmax=PGD_nmax, PGD_tol=PGD_tol)
 
 
 def make_problem(spec, cls):

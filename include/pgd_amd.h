@@ -384,10 +384,40 @@ int pgd_vec_multidot(pgd_handle ctx, pgd_handle x, const pgd_handle *ys, int k, 
 int pgd_vec_multidot_pair(pgd_handle ctx, pgd_handle x0, pgd_handle x1, const pgd_handle *ys, int k, int64_t lo,
                           int64_t hi, double *out);
 
+/* ------------------------------------------------- batched online evaluation --- */
+/* U[n x s] = F[n x k] C[k x s]: s samples of the online reconstruction u_j = sum_t C[t][j] F_t in ONE pass over the k mode
+ * vectors (pgd_vec_lincomb reads them again for every sample), with the reductions formed in the kernel that holds the
+ * accumulators - n s doubles are never stored unless the fields themselves are asked for.  The product runs on the f64
+ * matrix unit (v_mfma_f64_16x16x4_f64; PGD_TUNE_EVAL_VARIANT = 0: plain fma chains over k in ascending order).
+ *   modes: k vectors of the same size n, 1 <= k <= 256;  coefs: host, k x s row-major, coefs[t*s + j] = C[t][j], 1 <= s <= 2^24;
+ *   want: bit mask of PGD_EVAL_*;  threshold: of the exceedance count (must be 0 without PGD_EVAL_EXCEED);
+ *   sample_stats: host, 3 x s: min, max and max |.| of every sample over the n entries;
+ *   env_min / env_max: vectors of size n, min / max over the s samples per entry;
+ *   exceed: vector of size n, the number of samples with u > threshold, as a double;
+ *   fields: vector of size n*s, sample-major: sample j at [j*n, (j+1)*n).
+ * PGD_ERR_INVALID with a message, before anything is launched, for: a requested output that is missing, an output (or a
+ * threshold) that is passed but not requested, wrong sizes, a mode aliasing an output, two outputs aliasing each other, k or s
+ * out of range, an s*n that overflows.  n == 0 is PGD_OK with sample_stats untouched.  Large s runs in chunks of samples
+ * (PGD_TUNE_EVAL_SAMPLE_CHUNK); every output is bit-identical for any chunk length and any grid size (no atomics: persistent
+ * workgroups, one row of partial extrema each, a fixed-order final pass).  The call synchronises with the host once, at its
+ * end, if and only if PGD_EVAL_STATS is set.  NaNs in the modes or coefficients give unspecified statistics.             */
+enum { PGD_EVAL_STATS = 1, PGD_EVAL_ENVELOPE = 2, PGD_EVAL_EXCEED = 4, PGD_EVAL_FIELDS = 8 };
+int pgd_eval_batch(pgd_handle ctx, const pgd_handle *modes, int k, const double *coefs, int64_t s, int want,
+                   double threshold, double *sample_stats, pgd_handle env_min, pgd_handle env_max, pgd_handle exceed,
+                   pgd_handle fields);
+
 /* ------------------------------------------------------------------ tuning --- */
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_EVAL_SAMPLE_CHUNK = 52, /* pgd_eval_batch: samples per launch, 1 .. 1024 (0, default: 1024 - the running per-sample extrema
+                                of a workgroup live in LDS beside its block of mode values).  Envelopes and counts accumulate
+                                across the chunks; the outputs do not depend on it, bit for bit. */
+    PGD_TUNE_EVAL_GRID_MAX = 51, /* pgd_eval_batch: > 0: at most this many (persistent) workgroups; 0 (default): as many as are
+                                resident at once.  Same bits either way (tests reach the loop over row blocks with it). */
+    PGD_TUNE_EVAL_VARIANT = 50, /* pgd_eval_batch: 1 (default) the product on the f64 matrix unit (k_eval_mfma), 0 ordinary fma chains
+                                over k in ascending order (k_eval_plain): the cross-check and the baseline of
+                                tools/bench_eval_batch.py.  The two differ by rounding (another summation order), not more. */
     PGD_TUNE_PUSH_IN_UPDATE = 49, /* direct halo (pgd_comm_push_*): 1 (default) the boundary planes of the new search direction leave from the
                                 update kernel of the iteration itself - no launch for the exchange at all; 0: k_halo_push in front of
                                 every product.  Same stores, same iterates. */

@@ -58,6 +58,7 @@ SIGNATURES = {
     "pgd_vec_set": (C.c_int, [H, H, PI32, PD, I64]),
     "pgd_vec_lincomb": (C.c_int, [H, H, PH, PD, C.c_int]),
     "pgd_vec_dot": (C.c_int, [H, H, H, I64, I64, PD]),
+    "pgd_eval_batch": (C.c_int, [H, PH, C.c_int, PD, I64, C.c_int, F64, PD, H, H, H, H]),
     "pgd_atom_assemble": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PH]),
     "pgd_atom_assemble_cells": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PU8, I64, PH]),
     "pgd_atom_assemble_cellwise": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, H, PU8, I64, PH]),
@@ -134,6 +135,8 @@ SIGNATURES = {
 }
 
 NSLOTS = 64
+EVAL_STATS, EVAL_ENVELOPE, EVAL_EXCEED, EVAL_FIELDS = 1, 2, 4, 8      # PGD_EVAL_* (include/pgd_amd.h)
+TUNE_EVAL_VARIANT, TUNE_EVAL_GRID_MAX, TUNE_EVAL_SAMPLE_CHUNK = 50, 51, 52
 
 
 ERR_TIMEOUT, ERR_PEER = -7, -8          # PGD_ERR_TIMEOUT, PGD_ERR_PEER (include/pgd_amd.h)
@@ -341,6 +344,23 @@ class Context:
         arr = (H * max(k, 1))(*[int(x) for x in xs])
         cf = np.ascontiguousarray(coefs, dtype=np.float64)
         self._ck(self.lib.pgd_vec_lincomb(self.h, y, arr, dptr(cf) if k else None, k))
+
+    def eval_batch(self, modes, coefs, stats=True, env_min=0, env_max=0, exceed=0, threshold=0.0, fields=0):
+        """pgd_eval_batch: all samples (columns of ``coefs``, shape (k, s)) of u = sum_t coefs[t] modes[t] in one pass over
+        the modes.  Outputs are requested by passing their vectors (``stats``: a flag); returns the (3, s) array of
+        per-sample min / max / max |.| or None."""
+        k = len(modes)
+        cf = np.ascontiguousarray(coefs, dtype=np.float64)
+        if cf.ndim != 2 or cf.shape[0] != k:
+            raise ValueError("eval_batch: coefs must have shape (len(modes), samples), got %r for %d modes" % (cf.shape, k))
+        s = cf.shape[1]
+        want = (EVAL_STATS if stats else 0) | (EVAL_ENVELOPE if (env_min or env_max) else 0) | \
+               (EVAL_EXCEED if exceed else 0) | (EVAL_FIELDS if fields else 0)
+        arr = (H * max(k, 1))(*[int(x) for x in modes])
+        out = np.empty((3, s), dtype=np.float64) if stats else None
+        self._ck(self.lib.pgd_eval_batch(self.h, arr, k, dptr(cf) if cf.size else None, s, want, float(threshold),
+                                         dptr(out) if stats else None, int(env_min), int(env_max), int(exceed), int(fields)))
+        return out
 
     def vec_set(self, v, idx, val):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

@@ -222,6 +222,7 @@ int pgd_ctx_destroy(pgd_handle h) {
     (void)hipStreamSynchronize(c->stream);
     comm_release(c);
     mg_release(c);
+    eval_release(c);
     c->objs.clear();
     for (auto &kv : c->pool) (void)hipFree(kv.second);
     c->pool.clear();

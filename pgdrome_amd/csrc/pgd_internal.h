@@ -286,6 +286,13 @@ struct Ctx {
     struct Vmg *vmg = nullptr;    // pcg_precond = 2: the variable-coefficient hierarchy (pgd_vmg.hip), kept across solves on the same lattice
     int64_t vmg_solves = 0, vmg_fallbacks = 0, vmg_marches = 0;
     double vmg_setup_ms = 0.0;    // time the Galerkin setups of those solves took on the device, summed
+    // pgd_eval_batch (pgd_eval.hip): kernel variant (1 MFMA, 0 plain fma chains), grid cap and samples per launch (0: the launcher's choice);
+    // the pinned staging of the coefficients in fragment order, two chunks deep, with the events behind the copies
+    int eval_variant = 1, eval_grid_max = 0, eval_chunk = 0;
+    double *eval_pin = nullptr;
+    size_t eval_pin_bytes = 0;
+    hipEvent_t eval_ev[2] = {nullptr, nullptr};
+    bool eval_ev_set[2] = {false, false};
     int mg_chunk = 2;             // iterations queued between two looks at the flags when the multigrid preconditioner is on (even: the slot parity of a replayed chunk)
     int mg_march_min = 64;        // levels with at least this many nodes along x and y run their stencil passes in k_spmv_stencil_march
     int cls_cache_on = 1;         // classification of an operator whose structure was seen before: codes copied, every row verified (PGD_TUNE_CLS_CACHE)
@@ -415,6 +422,7 @@ int vmg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out = n
 double *vmg_result(Ctx *c);
 void vmg_note_setup(Ctx *c);
 void vmg_release(Ctx *c);
+void eval_release(Ctx *c);          // pgd_eval.hip: the pinned coefficient staging of pgd_eval_batch
 int sym_scale(Ctx *c, const Mesh *m, Csr *a, const double *s);   // pgd_spmv.hip: slot values *= s_i s_j
 int launch_spmv_dia_rows2(Ctx *c, const Mesh *m, const Csr *a, const double *x, double *y, const double *w, int64_t r0a,
                           int64_t r1a, int64_t r0b, int64_t r1b, bool dot, const int *flags, int *nparts_out, bool *done);

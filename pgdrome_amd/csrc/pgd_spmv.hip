@@ -2928,6 +2928,9 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_PUSH_IN_UPDATE && (value == 0 || value == 1)) { c->push_in_update = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_MG_CHUNK && value >= 2 && value <= 16 && value % 2 == 0) { c->mg_chunk = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_MG_MARCH_MIN && value >= 0 && value <= 1 << 20) { c->mg_march_min = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_EVAL_VARIANT && value >= 0 && value <= 1) { c->eval_variant = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_EVAL_GRID_MAX && value >= 0 && value <= 1 << 20) { c->eval_grid_max = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_EVAL_SAMPLE_CHUNK && value >= 0 && value <= 1024) { c->eval_chunk = (int)value; return PGD_OK; }
     return fail(c, PGD_ERR_INVALID, "tune: unknown knob %d or value out of range", knob);
 }
 

@@ -95,6 +95,69 @@ class PGDMesh:
             self.typElements = {1: "Polyline", 2: "Triangle", 3: "Tetrahedron"}[self.dim]
 
 
+class EvalManyResult:
+    """What ``PGD.evaluate_many`` returns; outputs that were not asked for are None."""
+    min = max = max_abs = None
+    envelope_min = envelope_max = exceedance = None
+    fields = None
+    coefficients = None
+    _fields_owner = None
+
+
+class _FieldStore:
+    """The one library vector (n * S doubles, sample-major) behind the ``fields`` of a device ``evaluate_many``; freed with
+    the last reference (the result and every field view hold one)."""
+
+    def __init__(self, be, n, S):
+        self.be, self.n = be, n
+        self.handle = be.vec_zeros(n * S)
+
+    def read(self, j):
+        return self.be.vec_to_host(self.handle, j * self.n, self.n)
+
+    def __del__(self):
+        try:
+            self.be.vec_free(self.handle)
+        except Exception:
+            pass
+
+
+class _FieldSlice(fem.Vector):
+    """Vector of one sample's field: a view into the ``_FieldStore`` until somebody reads or writes it (then an ordinary
+    Vector with its own storage)."""
+
+    def __init__(self, V, store, j):
+        super().__init__(V)
+        self._store, self._j = store, j
+        self._zero = False
+
+    def _pull(self):
+        if self._store is not None:
+            store, self._store = self._store, None
+            self._host = store.read(self._j)
+            self._host_ok, self._dev_ok = True, False
+
+    def host(self):
+        self._pull()
+        return super().host()
+
+    def dev(self):
+        self._pull()
+        return super().dev()
+
+    def dev_for_write(self):
+        self._store = None
+        return super().dev_for_write()
+
+    def touched_host(self):
+        self._store = None
+        super().touched_host()
+
+    def touched_dev(self):
+        self._store = None
+        super().touched_dev()
+
+
 class PGD:
     def __init__(self, name=None, n_modes=0, fmeshes=[], pgd_modes=[], name_coord=[], modes_info=[],
                  verbose=False, *args, **kwargs):
@@ -489,6 +552,185 @@ class PGD:
     def evaluate_abs_value(self, fixed_dim, free_dim, coord, attri, *args, **kwargs):
         """max |u(self.pos)| - the field at the point stored in ``pos`` (model.py:1071-1086)."""
         return float(np.max(np.abs(self.evaluate(fixed_dim, free_dim, coord, attri)(self.pos))))
+
+    # ------------------------------------------------------------- batched online evaluation
+    def _free_modes_at(self, d, x, attri):
+        """All used modes of the free dimension d at the coordinates x (array of S points): shape (used_numModes, S)."""
+        att = self.mesh[d].attributes[attri]
+        fcts = att.interpolationfct[:self.used_numModes]
+        x = np.asarray(x, dtype=np.float64)
+        if att.interpolationInfo.get("name") == 0:
+            return np.array([np.asarray(f(x), dtype=np.float64).reshape(-1) for f in fcts])     # interp1d: takes the array
+        f0 = fcts[0]
+        V = f0.function_space() if isinstance(f0, fem.Function) else None
+        if (V is not None and V._ncomp == 1 and not V._dg0 and V.mesh().topology().dim() == 1 and x.ndim == 1
+                and V._lay.degree in (1, 2) and all(isinstance(f, fem.Function) and f.function_space() is V for f in fcts)):
+            # 1-D P1 / P2: cell by searchsorted, basis values, one gather and one contraction for all modes and points
+            lay, mesh = V._lay, V.mesh()
+            X, cells = mesh.coordinates()[:, 0], mesh.cells()
+            a, b = X[cells[:, 0]], X[cells[:, 1]]
+            lo = np.minimum(a, b)
+            order = np.argsort(lo, kind="stable")
+            c = order[np.clip(np.searchsorted(lo[order], x, side="right") - 1, 0, len(order) - 1)]
+            l1 = (x - a[c]) * (1.0 / (b[c] - a[c]))
+            l0 = 1.0 - l1
+            bad = np.minimum(l0, l1) < -1e-10
+            if bad.any():
+                raise ValueError("point %r outside the mesh of dimension %d" % (float(x[np.argmax(bad)]), d))
+            if lay.degree == 1:
+                nodes, N = cells[c], np.stack([l0, l1], axis=1)
+            else:
+                nodes, N = lay.cells[c], np.stack([l0 * (2.0 * l0 - 1.0), l1 * (2.0 * l1 - 1.0), 4.0 * l0 * l1], axis=1)
+            G = np.stack([f.vector().host() for f in fcts])                   # (K, dofs)
+            return np.einsum("sa,ksa->ks", N, G[:, nodes])
+        # anything else (2-D / 3-D free dimensions, vector-valued free modes): the scalar callables, point by point
+        out = np.empty((len(fcts), x.shape[0]))
+        for j in range(x.shape[0]):
+            for k, f in enumerate(fcts):
+                try:
+                    out[k, j] = float(f(x[j]))
+                except RuntimeError as e:           # "point ... outside the mesh"
+                    raise ValueError(str(e)) from e
+        return out
+
+    def _check_many(self, fixed_dim, free_dim, coords, attri):
+        coords = np.asarray(coords, dtype=np.float64)
+        if coords.ndim == 1 and len(free_dim) == 1:
+            coords = coords.reshape(-1, 1)
+        if coords.ndim < 2 or coords.shape[0] < 1:
+            raise ValueError("coords must be array-like of shape (samples, len(free_dim)) with at least one sample, got shape %s"
+                             % (coords.shape,))
+        if coords.shape[1] != len(free_dim):
+            raise ValueError("Number of free Dimensions and given coordinates are not the same, free_dim=%s <-> "
+                             "coordinates per sample=%s" % (free_dim, coords.shape[1]))
+        for d in free_dim:
+            if attri >= len(self.mesh[d].attributes) or attri < 0:
+                raise ValueError("attribute number not possible")
+        if fixed_dim is not None:
+            self._check_eval(fixed_dim, free_dim, list(coords[0]), attri)
+        else:
+            for d in free_dim:
+                if len(self.mesh[d].attributes[attri].interpolationfct) == 0:
+                    self.create_interpolation_fcts(free_dim, attri)
+                    break
+        return coords
+
+    def mode_factors_many(self, free_dim, coords, attri):
+        """C[k, s] = prod_i F_i^k(coords[s, i]) for every used mode and every sample: shape (used_numModes, S), a handful of
+        array operations per free dimension (``mode_factors`` makes used_numModes * len(free_dim) Python calls per sample)."""
+        coords = self._check_many(None, free_dim, coords, attri)
+        C = np.ones((self.used_numModes, coords.shape[0]))
+        for i, d in enumerate(free_dim):
+            x = coords[:, i] if coords.ndim == 2 else coords[:, i, ...]
+            C *= self._free_modes_at(d, x, attri)
+        return C
+
+    def evaluate_many(self, fixed_dim, free_dim, coords, attri, stats=True, envelope=False, threshold=None, fields=False,
+                      fields_max_bytes=4 << 30, sample_chunk=256):
+        """The PGD solution on the fixed dimension for S coordinate sets of the other dimensions in ONE pass over the modes:
+        the product U = F C (fixed-dimension modes times ``mode_factors_many``) with its reductions formed where the product
+        is - on the device (``pgd_eval_batch``) when the backend has it, the modes are Functions and the fixed space has
+        at least DEVICE_EVAL_MIN_DOFS dofs (as ``evaluate`` decides), otherwise in numpy, ``sample_chunk`` samples at a time.
+
+        Returns an ``EvalManyResult``: ``min`` / ``max`` / ``max_abs`` (numpy, (S,)) when ``stats``; ``envelope_min`` /
+        ``envelope_max`` (per dof, over the samples) when ``envelope``; ``exceedance`` (per dof, the fraction of the samples
+        with u > threshold) when ``threshold`` is not None; ``fields`` (the S fields themselves) when ``fields``;
+        ``coefficients`` = C.  Functions on the fixed space (arrays in the interp1d mode).  NaNs give unspecified statistics."""
+        coords = self._check_many(fixed_dim, free_dim, coords, attri)
+        S = coords.shape[0]
+        att = self.mesh[fixed_dim].attributes[attri]
+        as_arrays = self.mesh[free_dim[0]].attributes[attri].interpolationInfo["name"] == 0
+        K = self.used_numModes
+        modes = att.interpolationfct
+        V = None
+        if as_arrays:
+            n = int(np.prod(att.data[0].shape))
+            fmesh = self.mesh[fixed_dim].fenics_mesh
+            sharded = fmesh is not None and getattr(fmesh, "part", None) is not None
+        else:
+            V = modes[0].function_space()
+            n = V.dim()
+            lay = V._lay.base if V._ncomp > 1 else V._lay
+            sharded = V.mesh().part is not None or getattr(lay, "part", None) is not None
+        if sharded:
+            raise NotImplementedError("evaluate_many on a row-sharded fixed dimension (every rank holds a slab of the modes; "
+                                      "the per-sample statistics would need a reduction across ranks)")
+        if fields and n * S * 8 > fields_max_bytes:
+            raise ValueError("evaluate_many: fields=True would store %d bytes (%d dofs x %d samples x 8), more than "
+                             "fields_max_bytes=%d" % (n * S * 8, n, S, fields_max_bytes))
+        thr = None if threshold is None else float(threshold)
+        C = self.mode_factors_many(free_dim, coords, attri)
+        res = EvalManyResult()
+        res.coefficients = C
+        be = fem.get_backend()
+        if (not as_arrays and n >= DEVICE_EVAL_MIN_DOFS and K <= 256 and all(isinstance(m, fem.Function) for m in modes[:K])
+                and hasattr(be, "eval_batch")):
+            def out_function():
+                f = fem.Function(V)
+                return f, f.vector().dev_for_write()
+            kw = {}
+            if envelope:
+                (res.envelope_min, kw["env_min"]), (res.envelope_max, kw["env_max"]) = out_function(), out_function()
+            if thr is not None:
+                (res.exceedance, kw["exceed"]), kw["threshold"] = out_function(), thr
+            if fields:
+                res._fields_owner = _FieldStore(be, n, S)
+                kw["fields"] = res._fields_owner.handle
+            st = be.eval_batch([modes[k].vector().dev() for k in range(K)], C, stats=bool(stats), **kw)
+            fem.STATS["eval_batch_calls"] = fem.STATS.get("eval_batch_calls", 0) + 1
+            if stats:
+                res.min, res.max, res.max_abs = st[0], st[1], st[2]
+            for f in (res.envelope_min, res.envelope_max, res.exceedance):
+                if f is not None:
+                    f.vector().touched_dev()
+            if thr is not None:
+                v = res.exceedance.vector()
+                v._host = v.host() / S                  # counts -> fraction (exactly count / S, as the host path has it)
+                v.touched_host()
+            if fields:
+                res.fields = []
+                for j in range(S):
+                    f = fem.Function(V)
+                    f._vec = _FieldSlice(V, res._fields_owner, j)
+                    res.fields.append(f)
+            return res
+        # ---- host path: the same outputs in numpy, sample_chunk columns of U at a time
+        if as_arrays:
+            F = np.stack([np.asarray(att.data[k], dtype=np.float64).reshape(-1) for k in range(K)], axis=1)
+        else:
+            F = np.stack([modes[k].vector().host() for k in range(K)], axis=1)
+        if stats:
+            res.min, res.max, res.max_abs = np.empty(S), np.empty(S), np.empty(S)
+        emn, emx = np.full(n, np.inf), np.full(n, -np.inf)
+        cnt = np.zeros(n)
+        all_fields = []
+        for j0 in range(0, S, max(1, int(sample_chunk))):
+            U = F @ C[:, j0:j0 + max(1, int(sample_chunk))]               # (n, cs)
+            if stats:
+                sl = slice(j0, j0 + U.shape[1])
+                res.min[sl], res.max[sl], res.max_abs[sl] = U.min(axis=0), U.max(axis=0), np.abs(U).max(axis=0)
+            if envelope:
+                np.minimum(emn, U.min(axis=1), out=emn)
+                np.maximum(emx, U.max(axis=1), out=emx)
+            if thr is not None:
+                cnt += (U > thr).sum(axis=1)
+            if fields:
+                all_fields.extend(np.ascontiguousarray(U[:, j]) for j in range(U.shape[1]))
+
+        def wrap(a):
+            if as_arrays:
+                return a.reshape(att.data[0].shape)
+            f = fem.Function(V)
+            f.vector()._host = np.array(a, dtype=np.float64)
+            f.vector().touched_host()
+            return f
+        if envelope:
+            res.envelope_min, res.envelope_max = wrap(emn), wrap(emx)
+        if thr is not None:
+            res.exceedance = wrap(cnt / S)
+        if fields:
+            res.fields = [wrap(a) for a in all_fields]
+        return res
 
     # ------------------------------------------------------ sensor responses and derivatives
     def _check_free(self, free_dim, coord, attri, fixed_dim):

@@ -410,6 +410,12 @@ int pgd_eval_batch(pgd_handle ctx, const pgd_handle *modes, int k, const double 
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_PCG_RECOMPUTE_Q = 53, /* 1 (default): in the three-launch single-sync recurrence of pgd_pcg_solve (PGD_TUNE_PCG_SINGLE_SYNC) on an
+                                operator whose products run in k_spmv_stencil_march over the whole grid, q = A p is never stored: the
+                                product leaves only its two dots (8 B per row instead of 16) and the vector update is an epilogue of the
+                                same march over p that forms q in registers (32 / 48 B per row instead of 40 / 56) and writes the new
+                                direction to a second buffer.  Same q, same per-row operations; only the grouping of the residual's
+                                partial sums differs.  0: the product stores q and k_pcg1_update reads it */
     PGD_TUNE_EVAL_SAMPLE_CHUNK = 52, /* pgd_eval_batch: samples per launch, 1 .. 1024 (0, default: 1024 - the running per-sample extrema
                                 of a workgroup live in LDS beside its block of mode values).  Envelopes and counts accumulate
                                 across the chunks; the outputs do not depend on it, bit for bit. */
@@ -539,7 +545,9 @@ enum {
     PGD_TUNE_PCG_SINGLE_SYNC = 18, /* 1 (default): scaled recurrence on structured grids above 2^20 rows with ONE reduction and ONE
                                       vector kernel per iteration: the product also leaves q.q, beta comes from
                                       r'.r' = alpha^2 q.q - r.r (exact in exact arithmetic; every alpha and the stop test use the
-                                      measured r.r); 7 vector passes and 3 launches per iteration instead of 8 and 5.  0: off */
+                                      measured r.r); 7 vector passes and 3 launches per iteration instead of 8 and 5 - 6 passes
+                                      where the operator is one stencil and q is formed again by the update instead of stored
+                                      (PGD_TUNE_PCG_RECOMPUTE_Q).  0: off */
     PGD_TUNE_UNIT_DIAG = 17,   /* 1 (default): the scaled operator D^-1/2 A D^-1/2 of pgd_pcg_solve(_sharded) gets its diagonal set to
                                   exactly 1 on structured grids and the products do not load it (7 instead of 8 slot values per row);
                                   0: diagonal s_i^2 a_ii stored and loaded */
@@ -575,7 +583,8 @@ int pgd_prof_read(pgd_handle ctx, int64_t *launches, double *seconds, double *al
 int pgd_prof_read_own(pgd_handle ctx, double *own_bytes);
 /* ... and the same for the vector update of the single-sync recurrence (k_pcg1_update: x += alpha p, r -= alpha q,
  * p = r + beta p and the partial sums of r.r in ONE kernel): launches timed, their seconds, and 56 B per row (4 vectors
- * read, 3 written) - the kernel that takes most of a PCG iteration once the product reads a code byte per row.   */
+ * read, 3 written; 40 where x is left alone) - the kernel that takes most of a PCG iteration once the product reads a code
+ * byte per row.  Where the update forms q itself (PGD_TUNE_PCG_RECOMPUTE_Q) it is priced with 48 / 32 B per row.   */
 int pgd_prof_read_update(pgd_handle ctx, int64_t *launches, double *seconds, double *bytes);
 /* Timed launches that were NOT counted: queued behind the iteration in which their solve converged, every kernel of them returned
  * on the done flag (full bytes, no time - they would bias the averages).  The counts above are the samples that were kept.   */
@@ -588,6 +597,9 @@ int pgd_prof_event_overhead(pgd_handle ctx, double *seconds);
  * [2] k_spmv_sym (row order), [3] k_spmv_dia_rows, [4] k_spmv_dia_march*, [5] k_spmv_multi, [6] k_spmv_diac_march2, [7] k_spmv_stencil_march; tests use them to
  * prove which kernel a call reached, bench.py for its per-kernel breakdown.                          */
 int pgd_kernel_counts(pgd_handle ctx, int64_t *out, int n);
+/* Launches of the vector update that forms q = A p itself (PGD_TUNE_PCG_RECOMPUTE_Q) since the context was created; they are not
+ * product launches and do not enter pgd_kernel_counts.  A chunk of iterations that is replayed as a graph counts once.  */
+int pgd_pcg_recompute_counts(pgd_handle ctx, int64_t *updates);
 /* Row-class classifications since the context was created: done in full (three passes over the slot values with hashing) / served
  * by the mesh's structure cache (codes copied, every row verified against its class: one pass) - PGD_TUNE_CLS_CACHE.   */
 int pgd_classify_counts(pgd_handle ctx, int64_t *full, int64_t *cached);

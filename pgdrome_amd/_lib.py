@@ -125,6 +125,7 @@ SIGNATURES = {
     "pgd_prof_read_dropped": (C.c_int, [H, PI64]),
     "pgd_prof_event_overhead": (C.c_int, [H, PD]),
     "pgd_kernel_counts": (C.c_int, [H, PI64, C.c_int]),
+    "pgd_pcg_recompute_counts": (C.c_int, [H, PI64]),
     "pgd_classify_counts": (C.c_int, [H, PI64, PI64]),
     "pgd_mg_counts": (C.c_int, [H, PI64, PI64]),
     "pgd_vmg_counts": (C.c_int, [H, PI64, PI64, PI64]),
@@ -751,6 +752,12 @@ class Context:
         out = (C.c_int64 * 8)()
         self._ck(self.lib.pgd_kernel_counts(self.h, out, 8))
         return {k: int(out[i]) for i, k in enumerate(self.KERNEL_FAMILIES)}
+
+    def pcg_recompute_updates(self):
+        """Launches of the PCG update that forms A p itself instead of reading it (PGD_TUNE_PCG_RECOMPUTE_Q)."""
+        n = I64()
+        self._ck(self.lib.pgd_pcg_recompute_counts(self.h, C.byref(n)))
+        return n.value
 
     def classify_counts(self):
         full, cached = I64(), I64()

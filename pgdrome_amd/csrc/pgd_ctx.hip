@@ -464,6 +464,13 @@ int pgd_kernel_counts(pgd_handle h, int64_t *out, int n) {
     return PGD_OK;
 }
 
+int pgd_pcg_recompute_counts(pgd_handle h, int64_t *updates) {
+    PGD_CTX(c, h);
+    if (!updates) return fail(c, PGD_ERR_INVALID, "pcg_recompute_counts: invalid arguments");
+    *updates = c->pcg_recompute_launches;
+    return PGD_OK;
+}
+
 int pgd_timer_start(pgd_handle h) {
     PGD_CTX(c, h);
     for (auto &e : c->timer_ev)

@@ -25,6 +25,10 @@ constexpr size_t PAD_BYTES = 256;   // slack after every device array (vector ov
 
 // slots of the device scalar bank used by the library's own PCG loop
 enum { S_PQ = 2, S_TOL2 = 5, S_DMIN = 7 /* smallest diagonal entry (scaled PCG) */, S_TMP = 8 /* ..15: batched functionals */ };   // 16..22: PCG r.z / r.r / b.b
+// single-sync recurrence (pgd_pcg.hip; the stencil march's update epilogue reads them too)
+enum { S1_RZ = 24, S1_RR = 25, S1_ALPHA = 26, S1_BETA = 27, S1_PQ = 28, S1_QQ = 29,
+       S1_ALPHA_PREV = 40, S1_BETA_PREV = 41, S1_PEND = 42 };      // the lagged x update
+constexpr double LAG_MIN_BETA = 0.01;
 
 struct Ctx;
 void dev_release(Ctx *c, void *p, size_t bytes);   // back to the context's buffer pool
@@ -269,6 +273,8 @@ struct Ctx {
     int pcg_small_ss = 1;         // systems up to 2^20 rows: single-sync recurrence with the scalar step inside the update kernel (2 launches)
     int pcg_stream_hints = 1;     // single-sync recurrence: q, r, x non-temporal, p cached (PGD_TUNE_PCG_STREAM_HINTS)
     int pcg_lag_x = 1;            // single-sync recurrence: x is updated every other iteration, two terms at a time (PGD_TUNE_PCG_LAG_X)
+    int pcg_recompute_q = 1;      // ... and on one-stencil grids A p is not stored: the update marches over p and forms it again (PGD_TUNE_PCG_RECOMPUTE_Q)
+    int64_t pcg_recompute_launches = 0;   // launches of that update (k_spmv_stencil_march, EPI 3)
     int asm_lattice = 1;          // lattice meshes: edge vectors as whole lattice steps in the assembly (PGD_TUNE_ASM_LATTICE)
     int spmv_fetch_depth = 6;     // plane fetches in flight per workgroup of k_spmv_diac_march2 (3 or 6; PGD_TUNE_SPMV_FETCH_DEPTH)
     int spmv_zchunk_coded2 = 96;  // ... and where every slot (two workgroups per CU) gets at least 24 planes: marches that fill the slots exactly once, at most this long (0: off)
@@ -407,6 +413,12 @@ bool atom_fast_form(Ctx *c, const Mesh *m, Csr *a, int64_t r0, int64_t r1);   //
 int dia_classify(Ctx *c, const Mesh *m, Csr *a, int zrange_lo = -1, int zrange_hi = -1);
 bool stencil_row_range(const Ctx *c, const Mesh *m, const Csr *a, int64_t r0, int64_t r1);   // ... over the whole planes [r0, r1) of a slab
 bool stencil_whole_grid(const Ctx *c, const Mesh *m, const Csr *a);   // pgd_spmv.hip: a product over all rows would run in k_spmv_stencil_march
+// pgd_spmv.hip: the vector update of the single-sync recurrence as an epilogue of that march (stencil_whole_grid operators only): q = A p_in
+// is formed in registers, x and r are updated in place, the new direction goes to p_out; one (r~.r~, true r.r) pair per workgroup in
+// `pairs`, stencil_update_blocks of them
+int stencil_update_blocks(const Ctx *c, const Mesh *m);
+int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, double *r, const double *s,
+                          double *pairs, int lag);
 int launch_stencil_pass(Ctx *c, const uint8_t *cls, int ident, const double cst[8], int nx, int ny, int nz, int zm0, int zm1,
                         const double *x, const double *b, double *y, double w, int epi, bool dot, int *nparts, int z0 = 0, int z1 = -1);      // pgd_spmv.hip
 // pgd_mg.hip: multigrid preconditioner of the scaled stencil operator

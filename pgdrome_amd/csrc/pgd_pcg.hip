@@ -614,9 +614,7 @@ __global__ __launch_bounds__(TPB) void k_pcg_px_s(double *__restrict__ x, double
 // same vector kernel, feeds the next alpha and the stop test, so nothing accumulates.  Iterates equal the textbook ones
 // up to rounding.  Slots: S1_RZ (measured r~.r~ of the current residual), S1_RR (its true r.r, exact phase),
 // S1_ALPHA, S1_BETA.
-enum { S1_RZ = 24, S1_RR = 25, S1_ALPHA = 26, S1_BETA = 27, S1_PQ = 28, S1_QQ = 29,
-       S1_ALPHA_PREV = 40, S1_BETA_PREV = 41, S1_PEND = 42 };      // the lagged x update (below)
-constexpr double LAG_MIN_BETA = 0.01;
+// (S1_* and LAG_MIN_BETA: pgd_internal.h)
 enum { S1F_ALPHA = 44 /* +parity */, S1F_BETA = 46 /* +parity */, S1F_EXACT = 48 /* +parity */ };   // scalar step inside the update kernel
 
 __device__ __forceinline__ void pcg1_finish(double *slots, int *flags, double pq, double qq, double rz, double rr, int slot_alpha,
@@ -747,6 +745,10 @@ __global__ __launch_bounds__(TPB) void k_pcg1_aux(const double *__restrict__ s, 
 // 145 -> 124 us for this kernel AND 88 -> 81 us for the product behind it (7.4 -> 8.3 passes/s; loads alone + 5 %, stores alone 0,
 // p streamed as well - 3 %).  slots[S1_PEND] (written by workgroup 0 of the lag = 1 launches, read by the lag = 2
 // ones and by k_scale_out when the solve ends between the two) says whether a term is outstanding.  lag = 0: every iteration.
+// ONE-STENCIL OPERATORS (PGD_TUNE_PCG_RECOMPUTE_Q, pgd_pcg_solve above pcg_small_ss_rows): this kernel is not launched at all - q is never
+// stored, and the same per-row operations run as an epilogue of the stencil march over p, which forms q in registers
+// (k_spmv_stencil_march EPI 3, launch_stencil_update: 32 / 48 B per row and 8 less in the product).  What follows is the form of
+// every other operator, of the sharded loop and of PGD_TUNE_PCG_RECOMPUTE_Q = 0.
 // FOLD (the row-sharded loop, whose sums arrive all-reduced in slots[fold_base .. + 3]: p.q, q.q, r~.r~ and the true r.r of the
 // residual this launch starts from): EVERY workgroup runs the scalar step itself - stop test, alpha, beta from those four
 // numbers, bit for bit the same in all of them - and workgroup 0 keeps the books (iteration count, flags, the report's r.r):
@@ -1638,10 +1640,22 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
     const bool lag_x = single_sync && c->pcg_lag_x;
     // (two-launch form above 2^20 rows: 512 workgroups in the update, every one of which sums all partial sums)
     const int g2v = grid_for((n + 1) / 2, TPB, (n > ((int64_t)1 << 20) && n <= c->pcg_small_ss_rows && c->pcg_small_ss) ? 512 : MAX_VEC_BLOCKS);
+    // one-stencil operators in the three-launch form (PGD_TUNE_PCG_RECOMPUTE_Q): q = A p costs 16 of the iteration's 64 B per row to store and
+    // read back and 15 fused multiply-adds per row to form from planes of p the update could stage like the product does.  The product
+    // keeps only its dots (8 B per row), the update marches over p, forms q in registers and writes the new direction to the OTHER of
+    // the two buffers p and q (neighbouring workgroups still stage the old one; q is free once the initial residual is formed): the
+    // direction of iteration k lives in the buffer of parity k & 1, chunks start at even iterations, so a captured chunk replays unchanged.
+    const bool recompute_q = single_sync && !fold && c->pcg_recompute_q && stencil_whole_grid(c, m, o);
+    const int gvec = recompute_q ? stencil_update_blocks(c, m) : g2v;      // (r~.r~, true r.r) pairs the update leaves
+    if (recompute_q && 2 * (int64_t)gvec > 4 * (int64_t)MAX_VEC_BLOCKS) {
+        PGD_TRY(ensure_work(c, 6, 2 * (int64_t)gvec));
+        part2 = c->work[6];
+        part2b = part2 + 2 * (int64_t)MAX_VEC_BLOCKS;
+    }
     if (single_sync) {
         // the first look at the residual happens in the first k_pcg1_scalars: hand it the initial residual's sums
         // (two-launch form: iteration k reads the pairs of parity (k - 1) & 1, so the seed goes to the second half)
-        k_pcg1_seed<<<8, TPB, 0, c->stream>>>(fold ? part2b : part2, g2v, c->slots, S_INIT, S_INIT + 1);
+        k_pcg1_seed<<<8, TPB, 0, c->stream>>>(fold ? part2b : part2, gvec, c->slots, S_INIT, S_INIT + 1);
         if (fold) PGD_HIP(c, hipMemsetAsync(c->slots + S1F_ALPHA, 0, 6 * sizeof(double), c->stream));     // alpha, beta, exact-phase bit x 2 parities
         PGD_LAUNCH_CHECK(c);
     }
@@ -1651,8 +1665,10 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
             int nparts = 0;
             c->prof_iter = start + k;                    // launch timing: which iteration a sample belongs to (prof_commit)
             if (single_sync) {
+                // (recompute_q: the direction of this iteration and the buffer its update writes the next one to)
+                double *p_cur = recompute_q && ((start + k) & 1) ? q : p, *p_next = p_cur == p ? q : p;
                 c->spmv_qq = 1;
-                const int rc = launch_spmv_op(c, m, o, p, q, p, 0, n, true, true, c->flags, &nparts);
+                const int rc = launch_spmv_op(c, m, o, p_cur, q, p_cur, 0, n, true, !recompute_q, c->flags, &nparts);
                 c->spmv_qq = 0;
                 PGD_TRY(rc);
                 const double *prod = c->partials;
@@ -1663,8 +1679,9 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
                     prod = c->work[5];
                     nparts = nb;
                 }
-                if (!fold) k_pcg1_scalars<<<1, 1024, 0, c->stream>>>(prod, nparts, part2, g2v, c->slots, c->flags);
-                // launch timing on: every third update between HIP events (5 or 7 vector passes = 40 or 56 B per row)
+                if (!fold) k_pcg1_scalars<<<1, 1024, 0, c->stream>>>(prod, nparts, part2, gvec, c->slots, c->flags);
+                // launch timing on: every third update between HIP events (5 or 7 vector passes = 40 or 56 B per row; 4 or 6 = 32 or 48 where
+                // the update forms q itself)
                 const bool timed_u = c->prof && ((c->prof_upd_seen++ % 3) == 0);        // one in three: both halves of the x-update pairs get sampled
                 if (timed_u) {
                     if (c->ev_used + 2 > c->ev.size()) prof_flush(c);
@@ -1673,7 +1690,8 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
                 }
                 // the x update lags behind by one iteration in every other one (chunks start at even iteration indices)
                 const int lag = lag_x ? 1 + ((start + k) & 1) : 0;
-                if (fold) {
+                if (recompute_q) PGD_TRY(launch_stencil_update(c, m, o, p_cur, p_next, x->d, r, sc, part2, lag));
+                else if (fold) {
                     const int par = (start + k) & 1;
                     k_pcg1_step<<<g2v, TPB, 0, c->stream>>>(x->d, r, p, q, sc, n, prod, nparts, par ? part2 : part2b, g2v, par ? part2b : part2,
                                                             c->slots, c->flags, par, lag);
@@ -1681,7 +1699,7 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
                 else k_pcg1_update<false, false><<<g2v, TPB, 0, c->stream>>>(x->d, r, p, q, sc, 0, n, c->slots, S1_ALPHA, S1_BETA, part2, c->flags, lag, 0, 0, PushArgs());
                 if (timed_u) {
                     PGD_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-                    c->ev_rec[c->ev_used / 2].bytes = (lag == 1 ? 40.0 : 56.0) * (double)n;      // (a lag = 1 launch that meets beta < 0.01 moves 56)
+                    c->ev_rec[c->ev_used / 2].bytes = ((lag == 1 ? 40.0 : 56.0) - (recompute_q ? 8.0 : 0.0)) * (double)n;      // (a lag = 1 launch that meets beta < 0.01 moves 56 / 48)
                     c->ev_used += 2;
                 }
                 PGD_LAUNCH_CHECK(c);
@@ -1825,7 +1843,9 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
         const bool lag_pending = lag_x && f[1] > 0 && ((f[1] - 1) & 1) == 0;
         // (alpha and beta of that last update: in the two-launch form they sit in the slots of its parity)
         const int last_par = f[1] > 0 ? (f[1] - 1) & 1 : 0;
-        k_scale_out<<<g, TPB, 0, c->stream>>>(x->d, r, sc, n, c->partials, (pending || lag_pending) ? p : nullptr, c->slots,
+        // (recompute_q: f[1] updates ran, each wrote the direction to the other buffer)
+        const double *p_live = recompute_q && (f[1] & 1) ? q : p;
+        k_scale_out<<<g, TPB, 0, c->stream>>>(x->d, r, sc, n, c->partials, (pending || lag_pending) ? p_live : nullptr, c->slots,
                                               S_PAIR + 2 * (f[1] & 1), S_PQ, lag_pending ? 1 : 0,
                                               fold ? S1F_ALPHA + last_par : S1_ALPHA, fold ? S1F_BETA + last_par : S1_BETA);
         PGD_LAUNCH_CHECK(c);

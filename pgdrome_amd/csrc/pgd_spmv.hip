@@ -298,7 +298,8 @@ __global__ __launch_bounds__(TPB) void k_spmv_multi(SpmvMultiArgs A) {
 // HIP-event timing of one launch in four (the events perturb the stream by ~5 us each side); the byte count is
 // the CSR formula of SURVEY 8d for the rows covered, whatever internal form of the operator the kernel reads
 static int prof_begin(Ctx *c, bool dot, bool store, bool *timed) {
-    const bool candidate = c->prof && (!c->prof_pcg_only || (dot && store));
+    // (PCG only: the fused-dot product that stores y, or - where the update forms A p again - the dot-only one of that loop, spmv_qq set)
+    const bool candidate = c->prof && (!c->prof_pcg_only || (dot && (store || c->spmv_qq)));
     *timed = candidate && ((c->prof_seen++ & 3) == 0);
     if (*timed) {
         if (c->ev_used + 2 > c->ev.size()) prof_flush(c);
@@ -1307,6 +1308,13 @@ struct StencilArgs {
     int whatif;             // instrumented builds only (PGD_STENCIL_TIMING): 1 no y stores, 2 no x fetches, 4 no LDS reads / FMAs
     const double *b;        // epilogues of the multigrid passes (EPI 1: y = x - w A x;  EPI 2: y = x + w (b - A x), fused dot b . y)
     double w;
+    // EPI 3, the vector update of the single-sync PCG with q = A p formed here and never stored (x = the direction p, y = the NEW direction,
+    // a second buffer: neighbouring workgroups still stage the old one): residual and iterate, updated in place; s = d^-1/2 (read in the
+    // exact phase only); the scalar bank with alpha, beta and the lagged x update's slots (S1_*); lag as in k_pcg1_update
+    double *ur = nullptr, *ux = nullptr;
+    const double *us = nullptr;
+    double *slots = nullptr;
+    int lag = 0;
 };
 
 #if defined(PGD_STENCIL_TIMING) || defined(PGD_STENCIL_WHATIF)
@@ -1326,10 +1334,26 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
     constexpr int NQ = RW + 1;                                              // cells a thread stages per plane: its own rows + one halo cell
     constexpr int SLOT = NQ * NT;                                           // 1280 >= 66 * 18 = 1188 cells (768 >= 66 * 10 = 660) + dump cells of idle stagers
     constexpr int OOB = (int)0x40000000;                                    // byte offset no plane reaches (planes < 2^27 rows: launcher)
-    constexpr int AUX_ST = NTY ? 2 : 0;                                     // nt
+    constexpr int AUX_ST = (NTY && EPI != 3) ? 2 : 0;                       // nt
+    constexpr int AUX_RX = (NTY && EPI == 3) ? 2 : 0;                       // EPI 3: r and x are streamed (nt), the new p keeps the default policy
+    static_assert(EPI != 3 || (DOT && STORE), "the PCG update leaves its partial sums and stores the new direction");
     __shared__ double s_x[4 * SLOT];
     __shared__ double s_red[4];
     if (A.flags && A.flags[0]) return;
+    // EPI 3: the scalars of k_pcg1_update (alpha and beta from k_pcg1_scalars, the lagged x update's state), uniform over the launch
+    double u_alpha = 0.0, u_beta = 0.0, u_alpha_p = 0.0, u_ibeta_p = 0.0;
+    bool u_exact = false, u_skip_x = false, u_two = false;
+    if (EPI == 3) {
+        u_alpha = A.slots[S1_ALPHA];
+        u_beta = A.slots[S1_BETA];
+        u_exact = A.flags[3] != 0;
+        u_skip_x = A.lag == 1 && u_beta >= LAG_MIN_BETA;
+        u_two = A.lag == 2 && A.slots[S1_PEND] != 0.0;
+        u_alpha_p = u_two ? A.slots[S1_ALPHA_PREV] : 0.0;
+        u_ibeta_p = u_two ? 1.0 / A.slots[S1_BETA_PREV] : 0.0;
+        // (read by the lag = 2 launches and by k_scale_out, never by a workgroup of this launch)
+        if (A.lag == 1 && blockIdx.x == 0 && threadIdx.x == 0) A.slots[S1_PEND] = u_skip_x ? 1.0 : 0.0;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int per_chunk = A.tiles_x * A.tiles_y;
@@ -1447,13 +1471,54 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
 #define PGD_ST_STAMP(k) do { } while (0)
 #endif
     // the product of the rows of plane z (a main plane), yz = y + P z, xo = the plane's raw own values
+    // EPI 3: r, x and s of the rows of the plane at yz - at the same place in their own arrays; cells outside the grid load zeros
+    auto upd_plane = [&](const double *base, const double *yz) {
+        return reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + (reinterpret_cast<const char *>(yz) - reinterpret_cast<const char *>(A.y)));
+    };
+    auto upd_load = [&](const double *yz, double (&ur)[RW], double (&ux)[RW], double (&us)[RW]) {
+        const auto dr = rsrc_of(upd_plane(A.ur, yz), true);
+#pragma unroll
+        for (int r = 0; r < RW; ++r) ur[r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(dr, sv[r], 0, AUX_RX));
+        const auto dx = rsrc_of(upd_plane(A.ux, yz), !u_skip_x);
+#pragma unroll
+        for (int r = 0; r < RW; ++r) ux[r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(dx, sv[r], 0, AUX_RX));
+        const auto ds = rsrc_of(upd_plane(A.us, yz), u_exact);
+#pragma unroll
+        for (int r = 0; r < RW; ++r) us[r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(ds, sv[r], 0, 0));
+    };
+    // ... and the update of those rows from q = A p: the operations of k_pcg1_update in its order, per row.  dot / dot2 take the partial
+    // sums of r'.r' and (exact phase) of (r' / s)^2; a cell outside the grid adds nothing to either and its stores are dropped
+    auto upd_rows = [&](double *yz, const double (&qv)[RW], const double (&xo)[RW], const double (&ur)[RW], const double (&ux)[RW],
+                        const double (&us)[RW]) {
+        const auto dp = rsrc_of(yz, true), dr = rsrc_of(upd_plane(A.ur, yz), true), dx = rsrc_of(upd_plane(A.ux, yz), !u_skip_x);
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            const double pi = xo[r], r0 = ur[r];
+            if (!u_skip_x) {                                                // uniform
+                double xi = ux[r];
+                if (u_two) xi = fma(u_alpha_p, (pi - r0) * u_ibeta_p, xi);
+                xi = fma(u_alpha, pi, xi);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_v2i, xi), dx, sv[r], 0, AUX_RX);
+            }
+            const double ri = fma(-u_alpha, qv[r], r0);
+            const double pn = fma(u_beta, pi, ri);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_v2i, ri), dr, sv[r], 0, AUX_RX);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_v2i, pn), dp, sv[r], 0, 0);
+            const bool in = sv[r] != OOB;                                   // (outside the grid q is a sum over the neighbours inside it: not zero)
+            const double t = in ? ri : 0.0;
+            dot = fma(t, t, dot);
+            if (u_exact) { const double ts = t / (in ? us[r] : 1.0); dot2 = fma(ts, ts, dot2); }
+        }
+    };
     auto rows = [&](int z, double *yz, bool live, const double (&xo)[RW]) {
         double bv[RW];
+        double ur[RW], ux[RW], us[RW];
         if (EPI == 2) {                                                     // issued first: in flight behind the LDS reads and the chains
             const auto rb = rsrc_of(bq, live);
 #pragma unroll
             for (int r = 0; r < RW; ++r) bv[r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rb, sv[r], 0, 0));
         }
+        if (EPI == 3) upd_load(yz, ur, ux, us);                             // likewise
         const double *xm = s_x + ((z - 1) & 3) * SLOT + centre;
         const double *xc = s_x + (z & 3) * SLOT + centre;
         const double *xp = s_x + ((z + 1) & 3) * SLOT + centre;
@@ -1497,6 +1562,13 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
             PGD_ST_ROWS(c7, Q[r + 1][1]);
 #undef PGD_ST_ROWS
         }
+        if (EPI == 3) {                                                     // q = acc, or p itself on an eliminated row
+            double qv[RW];
+#pragma unroll
+            for (int r = 0; r < RW; ++r) qv[r] = fixr[r] ? xo[r] : acc[r];
+            upd_rows(yz, qv, xo, ur, ux, us);
+            return;
+        }
         const auto ry = rsrc_of(yz, live && STORE && !PGD_ST_WHATIF(1));
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
@@ -1513,6 +1585,12 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
     };
     // a plane of identity rows only: y = x out of the registers
     auto copy_rows = [&](double *yz, const double (&xo)[RW]) {
+        if (EPI == 3) {                                                     // q = p on every row of the plane
+            double ur[RW], ux[RW], us[RW];
+            upd_load(yz, ur, ux, us);
+            upd_rows(yz, xo, xo, ur, ux, us);
+            return;
+        }
         const auto ry = rsrc_of(yz, STORE);
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
@@ -1560,6 +1638,7 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
             lds_barrier();
         }
     }
+    if (EPI == 3 && !u_exact) dot2 = dot;                                   // the pair is (r~.r~, true r.r) and outside the exact phase (r~.r~, r~.r~)
     if (DOT) {
         for (int pass = 0; pass < (A.qq ? 2 : 1); ++pass) {
             const double sum = wave_sum(pass ? dot2 : dot);
@@ -2443,6 +2522,33 @@ static int dia_march_chunks(const Ctx *c, const Mesh *m, int z0, int z1, int wy,
     return chunks;
 }
 
+// Shape of a launch of k_spmv_stencil_march over `planes` planes of an nx x ny grid, `depth` plane fetches in flight.
+struct StencilShape { int rows_per_thread, tiles_x, tiles_y, zchunk, wgs; };
+static StencilShape stencil_shape(const Ctx *c, int nx, int ny, int planes, int depth) {
+    StencilShape sh;
+    sh.tiles_x = (nx + 63) / 64;
+    sh.tiles_y = (ny + 15) / 16;
+    const int64_t slots = (int64_t)c->stencil_wg_per_cu * c->num_cu;
+    // rows per thread: four; two where the launch is so thin that marches of four-row patches would be shorter than 8
+    // planes (a z-slab of a sharded solve: 256 x 256 x 32 = 8 marches of 4 planes against 4 of 8) - PGD_TUNE_STENCIL_ROWS
+    sh.rows_per_thread = 4;
+    {
+        const int64_t tiles4 = (int64_t)sh.tiles_x * sh.tiles_y;
+        const int64_t marches4 = std::max<int64_t>(1, slots / tiles4);
+        const int zc4 = (int)((planes + marches4 - 1) / marches4);
+        if (c->stencil_rows == 2 || (c->stencil_rows == 0 && zc4 < 8 && ny >= 16 && c->spmv_zchunk_stencil <= 0 && c->stencil_depth != 6)) sh.rows_per_thread = 2;
+    }
+    if (sh.rows_per_thread == 2) sh.tiles_y = (ny + 7) / 8;
+    // march length: every resident workgroup slot filled once (two workgroups per CU), whole groups of the fetch depth
+    const int64_t tiles = (int64_t)sh.tiles_x * sh.tiles_y;
+    const int64_t marches = std::max<int64_t>(1, slots / tiles);
+    int zc = (int)((planes + marches - 1) / marches);
+    if (c->spmv_zchunk_stencil > 0) zc = c->spmv_zchunk_stencil;
+    sh.zchunk = std::max(depth, zc);                   // (an incomplete last group of steps idles behind the march's last plane)
+    sh.wgs = (int)(((planes + sh.zchunk - 1) / sh.zchunk) * tiles);
+    return sh;
+}
+
 // would a product over ALL rows of this operator (a PCG product: w = x, or no dot) run in k_spmv_stencil_march?  The conditions of
 // launch_spmv_op, for the solve that wants to hold the scaled operator as a stencil only (Csr::st_virtual)
 bool stencil_whole_grid(const Ctx *c, const Mesh *m, const Csr *a) {
@@ -2572,16 +2678,10 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
                 F.zs0 = a->st_zm0 - (a->st_g_lo ? 1 : 0); F.zs1 = a->st_zm1 + (a->st_g_hi ? 1 : 0);
                 for (int s2 = 0; s2 < 8; ++s2) F.c[s2] = a->st_c[s2];
                 F.nx = D.nx; F.ny = D.ny; F.nz = D.nz; F.z0 = D.z0; F.z1 = D.z1; F.tiles_x = D.tiles_x; F.tiles_y = (D.ny + 15) / 16;
-                // rows per thread: four; two where the launch is so thin that marches of four-row patches would be shorter than 8
-                // planes (a z-slab of a sharded solve: 256 x 256 x 32 = 8 marches of 4 planes against 4 of 8) - PGD_TUNE_STENCIL_ROWS
-                int rows_per_thread = 4;
-                {
-                    const int64_t slots4 = (int64_t)c->stencil_wg_per_cu * c->num_cu, tiles4 = (int64_t)F.tiles_x * F.tiles_y;
-                    const int64_t marches4 = std::max<int64_t>(1, slots4 / tiles4);
-                    const int zc4 = (int)((D.z1 - D.z0 + marches4 - 1) / marches4);
-                    if (c->stencil_rows == 2 || (c->stencil_rows == 0 && zc4 < 8 && D.ny >= 16 && c->spmv_zchunk_stencil <= 0 && c->stencil_depth != 6)) rows_per_thread = 2;
-                }
-                if (rows_per_thread == 2) F.tiles_y = (D.ny + 7) / 8;
+                const int depth = c->stencil_depth > 0 ? c->stencil_depth : 3;      // (six plane fetches in flight: no faster, 60 registers more)
+                const StencilShape sh = stencil_shape(c, D.nx, D.ny, D.z1 - D.z0, depth);
+                const int rows_per_thread = sh.rows_per_thread;
+                F.tiles_y = sh.tiles_y;
                 F.qq = D.qq;
                 F.whatif = 0;
                 F.b = nullptr; F.w = 0.0;
@@ -2589,17 +2689,8 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
                 if (const char *wi = getenv("PGD_STENCIL_WHATIF")) F.whatif = atoi(wi);
 #endif
                 const bool nty = D.qq && c->pcg_stream_hints;
-                // march length: every resident workgroup slot filled once (two workgroups per CU), whole groups of the fetch depth
-                const int64_t tiles = (int64_t)F.tiles_x * F.tiles_y, slots = (int64_t)c->stencil_wg_per_cu * c->num_cu;
-                const int planes = D.z1 - D.z0;
-                int64_t marches = std::max<int64_t>(1, slots / tiles);
-                int zc = (int)((planes + marches - 1) / marches);
-                if (c->spmv_zchunk_stencil > 0) zc = c->spmv_zchunk_stencil;
-                int depth = 3;                                 // (six plane fetches in flight: no faster, 60 registers more)
-                if (c->stencil_depth > 0) depth = c->stencil_depth;
-                zc = std::max(depth, zc);                      // (an incomplete last group of steps idles behind the march's last plane)
-                F.zchunk = zc;
-                const int wgs_s = (int)(((planes + zc - 1) / zc) * tiles);
+                F.zchunk = sh.zchunk;
+                const int wgs_s = sh.wgs;
                 if (nparts_out) *nparts_out = wgs_s;
                 if (dot) PGD_TRY(ensure_partials(c, std::max<int64_t>(c->partials_off + (D.qq ? 2 : 1) * (int64_t)wgs_s, 4 * MAX_VEC_BLOCKS)));
                 F.partials = c->partials + c->partials_off;
@@ -2618,7 +2709,7 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
                 } else if (depth == 6) PGD_STENCIL(6, 2); else PGD_STENCIL(3, 2);
 #undef PGD_STENCIL
                 c->kcount[KC_STENCIL_MARCH] += 1;
-                if (timed2) PGD_TRY(prof_end(c, m, nrows, 16.0));
+                if (timed2) PGD_TRY(prof_end(c, m, nrows, store ? 16.0 : 8.0));
                 PGD_LAUNCH_CHECK(c);
                 return PGD_OK;
             }
@@ -2688,6 +2779,42 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
 #undef PGD_SYM_LAUNCH
     c->kcount[KC_SYM_ROWS] += 1;
     if (timed) PGD_TRY(prof_end(c, m, nrows, 8.0 * m->sym_w + 18));
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+// The update of the single-sync recurrence with A p formed again instead of read (EPI 3 of the stencil march): the product's own march over
+// p_in - same patches, staging and chains, so the q of every row is the one the product summed its dots from, bit for bit - with three
+// plane fetches in flight whatever the product uses (its registers go to r, x and s).  The shape depends on the grid and the knobs only.
+int stencil_update_blocks(const Ctx *c, const Mesh *m) {
+    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
+    return stencil_shape(c, m->sym_nx, m->sym_ny, (int)(m->nv / plane), 3).wgs;
+}
+
+int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, double *r, const double *s,
+                          double *pairs, int lag) {
+    if (!stencil_whole_grid(c, m, a) || !c->flags || p_in == p_out)
+        return fail(c, PGD_ERR_INVALID, "stencil update: the operator's products do not run in the stencil march over the whole grid");
+    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
+    const int nz = (int)(m->nv / plane);
+    const StencilShape sh = stencil_shape(c, m->sym_nx, m->sym_ny, nz, 3);
+    StencilArgs F;
+    F.cls = a->cls; F.ident = a->st_ident; F.x = p_in; F.y = p_out; F.flags = c->flags;
+    F.zv0 = a->st_z0; F.zv1 = a->st_z1; F.zm0 = a->st_zm0; F.zm1 = a->st_zm1;
+    F.zs0 = a->st_zm0 - (a->st_g_lo ? 1 : 0); F.zs1 = a->st_zm1 + (a->st_g_hi ? 1 : 0);
+    for (int s2 = 0; s2 < 8; ++s2) F.c[s2] = a->st_c[s2];
+    F.nx = m->sym_nx; F.ny = m->sym_ny; F.nz = nz; F.z0 = 0; F.z1 = nz;
+    F.tiles_x = sh.tiles_x; F.tiles_y = sh.tiles_y; F.zchunk = sh.zchunk;
+    F.qq = 1; F.whatif = 0; F.b = nullptr; F.w = 0.0;
+    F.partials = pairs;
+    F.ur = r; F.ux = x; F.us = s; F.slots = c->slots; F.lag = lag;
+    const bool nt = c->pcg_stream_hints != 0;
+    if (sh.rows_per_thread == 2) {
+        if (nt) k_spmv_stencil_march<true, true, 3, true, 2, 3, 2><<<sh.wgs, 256, 0, c->stream>>>(F);
+        else k_spmv_stencil_march<true, true, 3, false, 2, 3, 2><<<sh.wgs, 256, 0, c->stream>>>(F);
+    } else if (nt) k_spmv_stencil_march<true, true, 3, true, 2, 3><<<sh.wgs, 256, 0, c->stream>>>(F);
+    else k_spmv_stencil_march<true, true, 3, false, 2, 3><<<sh.wgs, 256, 0, c->stream>>>(F);
+    c->pcg_recompute_launches += 1;
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
 }
@@ -2931,6 +3058,7 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_EVAL_VARIANT && value >= 0 && value <= 1) { c->eval_variant = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_EVAL_GRID_MAX && value >= 0 && value <= 1 << 20) { c->eval_grid_max = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_EVAL_SAMPLE_CHUNK && value >= 0 && value <= 1024) { c->eval_chunk = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_PCG_RECOMPUTE_Q && value >= 0 && value <= 1) { c->pcg_recompute_q = (int)value; return PGD_OK; }
     return fail(c, PGD_ERR_INVALID, "tune: unknown knob %d or value out of range", knob);
 }
 

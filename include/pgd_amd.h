@@ -469,7 +469,13 @@ enum {
                                 are the Galerkin products P^T A P, formed on the device once per solve, the smoother is l1-Jacobi.
                                 Operators that are one stencil take this cycle as well under 2 (value 1 keeps the cycle of
                                 pgd_mg.hip, bit for bit).  Anything else - no lattice, vector-valued or P2 layouts, lattices with
-                                fewer than 8 nodes along an axis - takes Jacobi and is counted by pgd_vmg_counts. */
+                                fewer than 8 nodes along an axis - takes Jacobi and is counted by pgd_vmg_counts.
+                                3 (opt-in, the frontend's "cmg"): BLOCKED (vector-valued) P1 layouts over a 3-D box lattice - one such
+                                V-cycle per component on the diagonal blocks of D^-1/2 A D^-1/2, which are scalar operators on the
+                                base lattice (separate-displacement-component preconditioning of elasticity); the blocks are read
+                                from the CSR values once per solve, the iteration stays the unscaled recurrence on the CSR product.
+                                Anything else - scalar or P2 layouts, no lattice, at most 4096 nodes - takes Jacobi and is counted
+                                by pgd_cmg_counts. */
     PGD_TUNE_CLS_CACHE = 39, /* 1 (default): a mesh remembers the class codes of the operators classified on it (by the signature of their
                                 Dirichlet set, scaled or not): the next operator with that structure - the same atoms with other
                                 coefficients, every solve of a fixed-point pass - copies the codes, rebuilds the table from the classes'
@@ -613,6 +619,11 @@ int pgd_vmg_counts(pgd_handle ctx, int64_t *solves, int64_t *fallbacks, int64_t 
  * all those solves in ms, and the number of level passes issued to the z-march kernel k_vmg_march (a chunk of iterations that is
  * replayed as a graph counts once).                                                                                        */
 int pgd_vmg_times(pgd_handle ctx, double *setup_ms, int64_t *march_passes);
+/* The same pair for PGD_TUNE_PCG_PRECOND = 3 (the counters of pgd_mg_counts and pgd_vmg_counts stay untouched): solves preconditioned
+ * by the component-wise V-cycles / fallen back to Jacobi, levels of one component's hierarchy (0: none held); device time of the
+ * setups (extraction of the diagonal blocks + ncomp Galerkin chains) in ms and the level passes issued to k_vmg_march.       */
+int pgd_cmg_counts(pgd_handle ctx, int64_t *solves, int64_t *fallbacks, int64_t *levels);
+int pgd_cmg_times(pgd_handle ctx, double *setup_ms, int64_t *march_passes);
 /* The V-cycle of the multigrid preconditioner on a z-slab of a ROW-SHARDED lattice: settings["preconditioner"] = "amg"
  * (forwarded by the reference into its solver, solver.py:593-594, 634-635) on a sharded spatial dimension.  Level 0 stays
  * with the rows (this rank's planes + one ghost plane per side), levels >= 1 are whole on every rank.  The caller owns the

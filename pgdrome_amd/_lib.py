@@ -130,6 +130,8 @@ SIGNATURES = {
     "pgd_mg_counts": (C.c_int, [H, PI64, PI64]),
     "pgd_vmg_counts": (C.c_int, [H, PI64, PI64, PI64]),
     "pgd_vmg_times": (C.c_int, [H, C.POINTER(C.c_double), PI64]),
+    "pgd_cmg_counts": (C.c_int, [H, PI64, PI64, PI64]),
+    "pgd_cmg_times": (C.c_int, [H, C.POINTER(C.c_double), PI64]),
     "pgd_calib_stream": (C.c_int, [H, H, C.c_int, C.c_int]),
     "pgd_timer_start": (C.c_int, [H]),
     "pgd_timer_stop": (C.c_int, [H, PD]),
@@ -785,6 +787,18 @@ class Context:
         a, b, l, m, ms = I64(), I64(), I64(), I64(), C.c_double()
         self._ck(self.lib.pgd_vmg_counts(self.h, C.byref(a), C.byref(b), C.byref(l)))
         self._ck(self.lib.pgd_vmg_times(self.h, C.byref(ms), C.byref(m)))
+        return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
+
+    def precondition_component(self, on):
+        """Select the component-wise V-cycle for vector-valued P1 operators on box lattices (PGD_TUNE_PCG_PRECOND = 3) for the next
+        pcg_solve calls, or (on false) the Jacobi-PCG again; returns the number of solves that cycle has preconditioned so far."""
+        self.tune(40, 3 if on else 0)
+        return self.cmg_stats()["solves"]
+
+    def cmg_stats(self):
+        a, b, l, m, ms = I64(), I64(), I64(), I64(), C.c_double()
+        self._ck(self.lib.pgd_cmg_counts(self.h, C.byref(a), C.byref(b), C.byref(l)))
+        self._ck(self.lib.pgd_cmg_times(self.h, C.byref(ms), C.byref(m)))
         return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
 
     def calib_stream(self, v, bytes_per_lane, store=False):

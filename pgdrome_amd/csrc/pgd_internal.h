@@ -292,6 +292,9 @@ struct Ctx {
     struct Vmg *vmg = nullptr;    // pcg_precond = 2: the variable-coefficient hierarchy (pgd_vmg.hip), kept across solves on the same lattice
     int64_t vmg_solves = 0, vmg_fallbacks = 0, vmg_marches = 0;
     double vmg_setup_ms = 0.0;    // time the Galerkin setups of those solves took on the device, summed
+    struct Cmg *cmg = nullptr;    // pcg_precond = 3: one such hierarchy per component of a blocked P1 operator, kept across solves on the same lattice and ncomp
+    int64_t cmg_solves = 0, cmg_fallbacks = 0, cmg_marches = 0;
+    double cmg_setup_ms = 0.0;    // extraction of the diagonal blocks + their Galerkin setups, summed
     // pgd_eval_batch (pgd_eval.hip): kernel variant (1 MFMA, 0 plain fma chains), grid cap and samples per launch (0: the launcher's choice);
     // the pinned staging of the coefficients in fragment order, two chunks deep, with the events behind the copies
     int eval_variant = 1, eval_grid_max = 0, eval_chunk = 0;
@@ -428,12 +431,19 @@ int mg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out = nu
 double *mg_result(Ctx *c);
 void mg_release(Ctx *c);
 // pgd_vmg.hip: multigrid preconditioner of a scaled operator in diagonal form with per-row coefficients (PGD_TUNE_PCG_PRECOND = 2)
-bool vmg_prepare(Ctx *c, const Mesh *m, const Csr *a);                         // true: usable for this operator (hierarchy formed from its current slot values)
-int vmg_fix_start(Ctx *c, const double *sc, const double *b, double *x, int64_t n);   // x = s b on the eliminated rows
-int vmg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out = nullptr);
-double *vmg_result(Ctx *c);
+// (the functions take the hierarchy they work on: Ctx::vmg, or one component of Ctx::cmg)
+struct Vmg;
+bool vmg_prepare(Ctx *c, Vmg *&M, const Mesh *m, const Csr *a);                // true: usable for this operator (hierarchy formed from its current slot values)
+int vmg_fix_start(Ctx *c, Vmg *M, const double *sc, const double *b, double *x, int64_t n);   // x = s b on the eliminated rows
+int vmg_vcycle(Ctx *c, Vmg *M, const double *r, bool dot, int *nparts, double *z_out, int64_t *marches);
+double *vmg_result(Vmg *M);
 void vmg_note_setup(Ctx *c);
-void vmg_release(Ctx *c);
+void vmg_release(Ctx *c);           // Ctx::vmg and Ctx::cmg
+// ... and the component-wise cycle of a blocked P1 operator over such a lattice (PGD_TUNE_PCG_PRECOND = 3): z[c::ncomp] = s_c M_c (s_c r[c::ncomp])
+bool cmg_prepare(Ctx *c, const Mesh *m, const Mesh *base, const Csr *a);       // true: usable (diagonal blocks extracted from the CSR values, hierarchies formed)
+int cmg_fix_start(Ctx *c, const double *b, double *x, int64_t n);              // x = b on the dofs the component hierarchies have eliminated
+int cmg_apply(Ctx *c, const double *r, double *z, int64_t n, int *nparts);     // partial sums of r . z into c->partials
+void cmg_note_setup(Ctx *c);
 void eval_release(Ctx *c);          // pgd_eval.hip: the pinned coefficient staging of pgd_eval_batch
 int sym_scale(Ctx *c, const Mesh *m, Csr *a, const double *s);   // pgd_spmv.hip: slot values *= s_i s_j
 int launch_spmv_dia_rows2(Ctx *c, const Mesh *m, const Csr *a, const double *x, double *y, const double *w, int64_t r0a,

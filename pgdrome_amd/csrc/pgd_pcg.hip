@@ -111,8 +111,8 @@ __global__ void k_pcg_check(double *__restrict__ slots, int *__restrict__ flags,
 }
 
 // V2: two consecutive entries per lane (16-byte loads/stores); needs an even `lo`, the odd tail entry
-// is handled by one extra lane.
-template <bool V2>
+// is handled by one extra lane.  Z = false (the component cycle forms z afterwards): no z, both partial sums are r.r.
+template <bool V2, bool Z = true>
 __global__ __launch_bounds__(TPB) void k_pcg_xr(double *__restrict__ x, double *__restrict__ r,
                                                 const double *__restrict__ p, const double *__restrict__ q,
                                                 const double *__restrict__ dinv, double *__restrict__ z, int64_t lo,
@@ -128,35 +128,41 @@ __global__ __launch_bounds__(TPB) void k_pcg_xr(double *__restrict__ x, double *
         for (int64_t k = (int64_t)blockIdx.x * TPB + threadIdx.x; k < npair; k += (int64_t)gridDim.x * TPB) {
             const int64_t i = lo + 2 * k;
             const d2 pi = *reinterpret_cast<const d2 *>(p + i), qi = *reinterpret_cast<const d2 *>(q + i);
-            const d2 di = *reinterpret_cast<const d2 *>(dinv + i);
-            d2 xi = *reinterpret_cast<d2 *>(x + i), ri = *reinterpret_cast<d2 *>(r + i), zi;
+            d2 di = {0.0, 0.0};
+            if (Z) di = *reinterpret_cast<const d2 *>(dinv + i);
+            d2 xi = *reinterpret_cast<d2 *>(x + i), ri = *reinterpret_cast<d2 *>(r + i);
             xi.x = fma(alpha, pi.x, xi.x); xi.y = fma(alpha, pi.y, xi.y);
             ri.x = fma(-alpha, qi.x, ri.x); ri.y = fma(-alpha, qi.y, ri.y);
-            zi.x = di.x * ri.x; zi.y = di.y * ri.y;
             *reinterpret_cast<d2 *>(x + i) = xi;
             *reinterpret_cast<d2 *>(r + i) = ri;
-            *reinterpret_cast<d2 *>(z + i) = zi;
-            rz = fma(ri.x, zi.x, rz); rz = fma(ri.y, zi.y, rz);
+            if (Z) {
+                d2 zi;
+                zi.x = di.x * ri.x; zi.y = di.y * ri.y;
+                *reinterpret_cast<d2 *>(z + i) = zi;
+                rz = fma(ri.x, zi.x, rz); rz = fma(ri.y, zi.y, rz);
+            }
             rr = fma(ri.x, ri.x, rr); rr = fma(ri.y, ri.y, rr);
         }
         if (((hi - lo) & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
             const int64_t i = hi - 1;
             x[i] = fma(alpha, p[i], x[i]);
-            const double ri = fma(-alpha, q[i], r[i]), zi = dinv[i] * ri;
-            r[i] = ri; z[i] = zi;
-            rz = fma(ri, zi, rz); rr = fma(ri, ri, rr);
+            const double ri = fma(-alpha, q[i], r[i]);
+            r[i] = ri;
+            if (Z) { const double zi = dinv[i] * ri; z[i] = zi; rz = fma(ri, zi, rz); }
+            rr = fma(ri, ri, rr);
         }
     } else {
         for (int64_t i = lo + (int64_t)blockIdx.x * TPB + threadIdx.x; i < hi; i += (int64_t)gridDim.x * TPB) {
             x[i] = fma(alpha, p[i], x[i]);
-            const double ri = fma(-alpha, q[i], r[i]), zi = dinv[i] * ri;
-            r[i] = ri; z[i] = zi;
-            rz = fma(ri, zi, rz); rr = fma(ri, ri, rr);
+            const double ri = fma(-alpha, q[i], r[i]);
+            r[i] = ri;
+            if (Z) { const double zi = dinv[i] * ri; z[i] = zi; rz = fma(ri, zi, rz); }
+            rr = fma(ri, ri, rr);
         }
     }
-    rz = block_sum(rz, s_red);
+    if (Z) rz = block_sum(rz, s_red);
     rr = block_sum(rr, s_red);
-    if (threadIdx.x == 0) { partials[2 * blockIdx.x] = rz; partials[2 * blockIdx.x + 1] = rr; }
+    if (threadIdx.x == 0) { partials[2 * blockIdx.x] = Z ? rz : rr; partials[2 * blockIdx.x + 1] = rr; }
 }
 
 template <bool V2>
@@ -1373,17 +1379,22 @@ int pcg1_flush_x(Ctx *c, double *x, const double *p, const double *r, int64_t lo
     return PGD_OK;
 }
 
+// z == nullptr asks for the update without z = D^-1 r (k_pcg_xr<V2, false>; dinv is then not read): the caller's preconditioner
+// writes z itself and overwrites S[slot_out] with its own r.z, S[slot_out + 1] is the true r.r either way
 static int pcg_xr(Ctx *c, double *x, double *r, const double *p, const double *q, const double *dinv, double *z,
                   int64_t lo, int64_t hi, int slot_rz, int slot_pq, int slot_out, int check_mode, int slot_tol2) {
     const int g = grid_for(hi - lo);
+    const bool with_z = z != nullptr;
     PGD_TRY(ensure_partials(c, 4 * (int64_t)MAX_VEC_BLOCKS));
     if ((lo & 1) == 0) {
         const int g2 = grid_for((hi - lo + 1) / 2);
-        k_pcg_xr<true><<<g2, TPB, 0, c->stream>>>(x, r, p, q, dinv, z, lo, hi, c->slots, slot_rz, slot_pq, c->partials, c->flags);
+        if (with_z) k_pcg_xr<true><<<g2, TPB, 0, c->stream>>>(x, r, p, q, dinv, z, lo, hi, c->slots, slot_rz, slot_pq, c->partials, c->flags);
+        else k_pcg_xr<true, false><<<g2, TPB, 0, c->stream>>>(x, r, p, q, nullptr, nullptr, lo, hi, c->slots, slot_rz, slot_pq, c->partials, c->flags);
         PGD_LAUNCH_CHECK(c);
         return reduce_partials(c, c->partials, g2, 2, slot_out, check_mode, slot_out + 1, slot_tol2);
     }
-    k_pcg_xr<false><<<g, TPB, 0, c->stream>>>(x, r, p, q, dinv, z, lo, hi, c->slots, slot_rz, slot_pq, c->partials, c->flags);
+    if (with_z) k_pcg_xr<false><<<g, TPB, 0, c->stream>>>(x, r, p, q, dinv, z, lo, hi, c->slots, slot_rz, slot_pq, c->partials, c->flags);
+    else k_pcg_xr<false, false><<<g, TPB, 0, c->stream>>>(x, r, p, q, nullptr, nullptr, lo, hi, c->slots, slot_rz, slot_pq, c->partials, c->flags);
     PGD_LAUNCH_CHECK(c);
     return reduce_partials(c, c->partials, g, 2, slot_out, check_mode, slot_out + 1, slot_tol2);
 }
@@ -1529,6 +1540,7 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
     constexpr int S_INIT = 18, S_PAIR = 16;
     const bool scaled = sym && c->pcg_scaled && n >= 2;
     bool mg_on = false, vmg_on = false;   // (vmg_on: the cycle is the variable-coefficient one; mg_on is up as well)
+    bool cmg_on = false;                  // the component-wise cycle of a blocked P1 operator (unscaled branch; mg_on is up as well)
     double *sc = z;                     // the scaled recurrence has no z: its buffer holds s = d^-1/2
     // On EVERY exit after x and the slot arrays were scaled (a failing launch, graph replay or copy included): x back to
     // D^-1/2 x~ and the slot arrays no longer taken for A - a later product with this operator must not read the scaled
@@ -1602,10 +1614,11 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
         }
         // ... = 2: the V-cycle on the diagonal form with per-row coefficients (pgd_vmg.hip): any operator on a lattice, any Dirichlet set
         if (c->pcg_precond == 2) {
-            mg_on = vmg_on = m->sym_nx > 0 && vmg_prepare(c, m, o);
-            if (vmg_on) { c->vmg_solves += 1; PGD_TRY(vmg_fix_start(c, sc, b->d, x->d, n)); }
+            mg_on = vmg_on = m->sym_nx > 0 && vmg_prepare(c, c->vmg, m, o);
+            if (vmg_on) { c->vmg_solves += 1; PGD_TRY(vmg_fix_start(c, c->vmg, sc, b->d, x->d, n)); }
             else c->vmg_fallbacks += 1;
         }
+        if (c->pcg_precond == 3) c->cmg_fallbacks += 1;     // (a scalar layout: Jacobi)
         PGD_TRY(launch_spmv_op(c, m, o, x->d, q, nullptr, 0, n, false, true, nullptr, nullptr));
         const int g = grid_for(n);
         PGD_TRY(ensure_partials(c, 4 * (int64_t)MAX_VEC_BLOCKS));
@@ -1615,6 +1628,14 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
     } else {
         if (c->pcg_precond == 1) c->mg_fallbacks += 1;      // (no symmetric storage, or the scaled recurrence switched off: Jacobi)
         if (c->pcg_precond == 2) c->vmg_fallbacks += 1;
+        // ... = 3: blocked P1 layouts over a box lattice - one V-cycle of pgd_vmg.hip per component on the diagonal blocks of
+        // D^-1/2 A D^-1/2, read from the CSR values (the solve itself stays the unscaled textbook recurrence on k_spmv_csr)
+        if (c->pcg_precond == 3) {
+            if (m->ncomp >= 2) PGD_TRY(ensure_vals(c, m, o));
+            mg_on = cmg_on = m->ncomp >= 2 && cmg_prepare(c, m, get_mesh(c, m->base), o);
+            if (cmg_on) { c->cmg_solves += 1; PGD_TRY(cmg_fix_start(c, b->d, x->d, n)); }
+            else c->cmg_fallbacks += 1;
+        }
         PGD_TRY(launch_spmv_op(c, m, o, x->d, q, nullptr, 0, n, false, true, nullptr, nullptr));
         PGD_TRY(pcg_init(c, b->d, q, o->dinv, r, z, p, 0, n, S_INIT));
     }
@@ -1622,7 +1643,8 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
     PGD_LAUNCH_CHECK(c);
     if (mg_on) {                        // p0 = z0 = M r0; the first "previous r.z"
         int np = 0;
-        PGD_TRY(vmg_on ? vmg_vcycle(c, r, true, &np, p) : mg_vcycle(c, r, true, &np, p));
+        if (cmg_on) PGD_TRY(cmg_apply(c, r, p, n, &np));
+        else PGD_TRY(vmg_on ? vmg_vcycle(c, c->vmg, r, true, &np, p, &c->vmg_marches) : mg_vcycle(c, r, true, &np, p));
         PGD_TRY(reduce_partials(c, c->partials, np, 1, S_INIT, -1, 0, 0));
     }
 
@@ -1706,6 +1728,18 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
                 continue;
             }
             PGD_TRY(launch_spmv_op(c, m, o, p, q, p, 0, n, true, true, c->flags, &nparts));
+            if (cmg_on) {
+                // the unscaled textbook recurrence with z = M r from the component cycles in place of z = D^-1 r: the update counts the
+                // iteration and tests the true r.r, the merge leaves r.z
+                int np = 0;
+                PGD_TRY(reduce_partials(c, c->partials, nparts, 1, S_PQ, 0, 0, 0));
+                PGD_TRY(pcg_xr(c, x->d, r, p, q, nullptr, nullptr, 0, n, rz_old, S_PQ, out, 1, S_TOL2));      // (no z = D^-1 r: the merge writes z)
+                PGD_TRY(cmg_apply(c, r, z, n, &np));
+                PGD_TRY(reduce_partials(c, c->partials, np, 1, out, -1, 0, 0));
+                k_pcg_p<true><<<grid_for((n + 1) / 2), TPB, 0, c->stream>>>(p, z, 0, n, c->slots, out, rz_old, c->flags);
+                PGD_LAUNCH_CHECK(c);
+                continue;
+            }
             if (mg_on) {
                 // textbook PCG with z = M r from the V-cycle: the stop test stays the one of the Jacobi form (true r.r in the exact phase)
                 const int g2 = grid_for((n + 1) / 2);
@@ -1714,9 +1748,9 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
                 k_pcg_xr_s<<<g2, TPB, 0, c->stream>>>(x->d, r, p, q, sc, n, c->slots, rz_old, S_PQ, c->partials, c->flags);
                 PGD_LAUNCH_CHECK(c);
                 PGD_TRY(reduce_partials(c, c->partials, g2, 2, out, 2, out + 1, S_TOL2));      // counts the iteration, tests
-                PGD_TRY(vmg_on ? vmg_vcycle(c, r, true, &np) : mg_vcycle(c, r, true, &np));
+                PGD_TRY(vmg_on ? vmg_vcycle(c, c->vmg, r, true, &np, nullptr, &c->vmg_marches) : mg_vcycle(c, r, true, &np));
                 PGD_TRY(reduce_partials(c, c->partials, np, 1, out, -1, 0, 0));                // r.z over the r~.r~ the test has used
-                k_pcg_p<true><<<g2, TPB, 0, c->stream>>>(p, vmg_on ? vmg_result(c) : mg_result(c), 0, n, c->slots, out, rz_old, c->flags);
+                k_pcg_p<true><<<g2, TPB, 0, c->stream>>>(p, vmg_on ? vmg_result(c->vmg) : mg_result(c), 0, n, c->slots, out, rz_old, c->flags);
                 PGD_LAUNCH_CHECK(c);
                 continue;
             }
@@ -1860,6 +1894,7 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
     PGD_HIP(c, hipMemcpyAsync(s, c->slots, sizeof s, hipMemcpyDeviceToHost, c->stream));
     PGD_HIP(c, hipStreamSynchronize(c->stream));
     if (vmg_on) vmg_note_setup(c);
+    if (cmg_on) cmg_note_setup(c);
     if (iters) *iters = f[1];
     const double rr = scaled ? s[S_TMP] : (f[1] > 0) ? s[S_PAIR + 2 * ((f[1] - 1) & 1) + 1] : s[S_INIT + 1];
     const double bb = s[S_INIT + 2];

@@ -53,6 +53,17 @@ struct Vmg {
     int np0 = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
+    bool own0 = false;                                  // level 0 owns its slot arrays and a right-hand side (a component hierarchy of Cmg)
+};
+
+// pcg_precond = 3: one hierarchy per displacement component of a blocked P1 operator (the diagonal blocks of its scaled form)
+struct Cmg {
+    int ncomp = 0;
+    Vmg *comp[3] = {nullptr, nullptr, nullptr};
+    double *s = nullptr;                                // d^-1/2 of the block operator, one per dof
+    int *bad = nullptr;                                 // device flag: a diagonal block holds an entry off the 15-point pattern
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
 };
 
 constexpr int VMG_BOTTOM_MAX = 4096, VMG_SWEEPS = 24;
@@ -290,6 +301,86 @@ __global__ __launch_bounds__(TPB) void k_vmg_fix_start(const uint8_t *__restrict
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// Component-wise cycle for blocked (vector-valued) P1 operators (PGD_TUNE_PCG_PRECOND = 3): the block diagonal of an elasticity
+// operator - its ncomp diagonal blocks A_cc - is spectrally equivalent to it (Korn), and every A_cc is a scalar operator on the
+// 15-point pattern of the base lattice.  B_c = (S A S)[c::ncomp, c::ncomp], S = diag(A)^-1/2, gets a hierarchy of its own
+// (eliminated sets may differ between components), z[c::ncomp] = s_c M_c (s_c r[c::ncomp]).
+struct CmgPtrs { double *p[3]; };
+struct CmgConst { const double *p[3]; };
+struct CmgElim { const uint8_t *p[3]; };
+
+// The 8 upper slot arrays of every B_c from the CSR values of the block operator (rows ncomp i + c, node-major): one lattice node
+// per thread, one pass over its ncomp rows.  Slot 0 is 1, a coupling the row does not store is an exact 0; s = dinv^1/2 is kept
+// for the split and the merge.  A stored non-zero of a diagonal block that is off the pattern raises *bad.
+__global__ __launch_bounds__(256) void k_cmg_extract(VGrid g, int ncomp, const int *__restrict__ row_ptr, const int *__restrict__ cols,
+                                                     const double *__restrict__ vals, const double *__restrict__ dinv, CmgPtrs a,
+                                                     double *__restrict__ s, int *__restrict__ bad) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), z = blockIdx.z;
+    if (x >= g.nx || y >= g.ny) return;
+    const int64_t P = (int64_t)g.nx * g.ny, n = P * g.nz, i = P * z + (int64_t)g.nx * y + x;
+    for (int c = 0; c < ncomp; ++c) {
+        const int64_t row = (int64_t)ncomp * i + c;
+        const double si = sqrt(dinv[row]);
+        double acc[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) acc[t] = 0.0;
+        for (int k = row_ptr[row]; k < row_ptr[row + 1]; ++k) {
+            const int col = cols[k];
+            const int j = col / ncomp;
+            if (col - j * ncomp != c) continue;                               // another block
+            const int jz = (int)(j / P), rem = (int)(j - jz * P), jy = rem / g.nx, jx = rem - jy * g.nx;
+            const int dx = jx - x, dy = jy - y, dz = jz - z;
+            const double v = vals[k];
+            if (dx >= 0 && dy >= 0 && dz >= 0 && dx <= 1 && dy <= 1 && dz <= 1) {
+                const int t = dx + 2 * dy + 4 * dz;
+                const double e = (si * v) * sqrt(dinv[col]);
+#pragma unroll
+                for (int u = 1; u < 8; ++u) if (u == t) acc[u] = e;
+            } else if (!(dx <= 0 && dy <= 0 && dz <= 0 && dx >= -1 && dy >= -1 && dz >= -1) && v != 0.0) *bad = 1;
+        }
+        double *ac = a.p[c];
+        ac[i] = 1.0;
+#pragma unroll
+        for (int t = 1; t < 8; ++t) ac[(int64_t)t * n + i] = acc[t];
+        s[row] = si;
+    }
+}
+
+// b_c = s_c r[c::ncomp]: the level-0 right-hand sides of the component cycles
+__global__ __launch_bounds__(TPB) void k_cmg_split(int ncomp, const double *__restrict__ r, const double *__restrict__ s, CmgPtrs b, int64_t n,
+                                                   const int *__restrict__ flags) {
+    if (flags && flags[0]) return;
+    for (int64_t d = (int64_t)blockIdx.x * TPB + threadIdx.x; d < n; d += (int64_t)gridDim.x * TPB) {
+        const int64_t i = d / ncomp;
+        b.p[d - i * ncomp][i] = s[d] * r[d];
+    }
+}
+
+// z[c::ncomp] = s_c x_c, partial sums of r . z per workgroup (fixed order)
+__global__ __launch_bounds__(TPB) void k_cmg_merge(int ncomp, CmgConst xc, const double *__restrict__ s, const double *__restrict__ r,
+                                                   double *__restrict__ z, int64_t n, double *__restrict__ partials, const int *__restrict__ flags) {
+    __shared__ double s_red[4];
+    if (flags && flags[0]) return;
+    double acc = 0.0;
+    for (int64_t d = (int64_t)blockIdx.x * TPB + threadIdx.x; d < n; d += (int64_t)gridDim.x * TPB) {
+        const int64_t i = d / ncomp;
+        const double zd = s[d] * xc.p[d - i * ncomp][i];
+        z[d] = zd;
+        acc = fma(r[d], zd, acc);
+    }
+    acc = block_sum(acc, s_red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+}
+
+// x = b on the dofs a component hierarchy has eliminated (identity rows): their exact solution; the cycle never moves them
+__global__ __launch_bounds__(TPB) void k_cmg_fix_start(int ncomp, CmgElim el, const double *__restrict__ b, double *__restrict__ x, int64_t n) {
+    const int64_t d = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (d >= n) return;
+    const int64_t i = d / ncomp;
+    if (el.p[d - i * ncomp][i]) x[d] = b[d];
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // The z-march of the diagonal form (k_spmv_dia_march2: a 64 x 8 patch per 256-thread workgroup, two rows per thread, three planes of
 // the input in an LDS ring, the plane-below couplings handed on through LDS) with the epilogues of the cycle:
 //   EPI 1: staged u = w in;  out = in - A u on free rows, 0 on eliminated ones                   (in = the level's right-hand side)
@@ -457,7 +548,7 @@ static void vmg_free(Vmg *&M) {
     if (!M) return;
     for (size_t l = 0; l < M->lv.size(); ++l) {
         VLevel &L = M->lv[l];
-        if (l > 0 && L.a) (void)hipFree(L.a);
+        if ((l > 0 || M->own0) && L.a) (void)hipFree(L.a);
         for (void *p : {(void *)L.w, (void *)L.el, (void *)L.b, (void *)L.x, (void *)L.t}) if (p) (void)hipFree(p);
     }
     if (M->ev0) (void)hipEventDestroy(M->ev0);
@@ -466,9 +557,20 @@ static void vmg_free(Vmg *&M) {
     M = nullptr;
 }
 
-void vmg_release(Ctx *c) { vmg_free(c->vmg); }
+static void cmg_free(Cmg *&G) {
+    if (!G) return;
+    for (Vmg *&M : G->comp) vmg_free(M);
+    if (G->s) (void)hipFree(G->s);
+    if (G->bad) (void)hipFree(G->bad);
+    if (G->ev0) (void)hipEventDestroy(G->ev0);
+    if (G->ev1) (void)hipEventDestroy(G->ev1);
+    delete G;
+    G = nullptr;
+}
 
-double *vmg_result(Ctx *c) { return c->vmg && !c->vmg->lv.empty() ? c->vmg->lv[0].x : nullptr; }
+void vmg_release(Ctx *c) { vmg_free(c->vmg); cmg_free(c->cmg); }
+
+double *vmg_result(Vmg *M) { return M && !M->lv.empty() ? M->lv[0].x : nullptr; }
 
 static dim3 vmg_grid(const VGrid &g) { return dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4), (unsigned)g.nz); }
 
@@ -483,44 +585,49 @@ static bool vmg_marches(const Ctx *c, const VLevel &L, int *zchunk, int *wgs) {
     return true;
 }
 
-// true: the cycle applies to this solve - hierarchy formed from the operator's CURRENT (scaled) slot values, buffers there
-bool vmg_prepare(Ctx *c, const Mesh *m, const Csr *a) {
-    if (!m || !a || m->sym_nx <= 0 || !a->uvals || !a->uvals_valid || !a->uvals_scaled) return false;
-    const int nx = m->sym_nx, ny = m->sym_ny, nz = (int)(m->nv / ((int64_t)nx * ny));
-    if ((int64_t)nx * ny * nz != m->nv || std::min(nx, std::min(ny, nz)) < 8 || nz > 65535 || ny > 4 * 65535) return false;
-    Vmg *M = c->vmg;
-    if (!M || M->nx != nx || M->ny != ny || M->nz != nz) {                  // another lattice: new levels and buffers
-        vmg_free(c->vmg);
-        M = c->vmg = new Vmg();
-        VGrid g{nx, ny, nz};
-        for (;;) {
-            VLevel L;
-            L.g = g;
-            L.n = (int64_t)g.nx * g.ny * g.nz;
-            M->lv.push_back(L);
-            if (L.n <= VMG_BOTTOM_MAX) break;                               // the first level one workgroup can hold is the coarsest
-            g = VGrid{(g.nx + 1) / 2, (g.ny + 1) / 2, (g.nz + 1) / 2};
-        }
-        if (M->lv.size() < 2) { vmg_free(c->vmg); return false; }          // (at most 4096 nodes: no hierarchy, Jacobi)
-        bool ok = hipEventCreate(&M->ev0) == hipSuccess && hipEventCreate(&M->ev1) == hipSuccess;
-        for (size_t l = 0; ok && l < M->lv.size(); ++l) {
-            VLevel &L = M->lv[l];
-            const bool last = l + 1 == M->lv.size();
-            const size_t bytes = (size_t)L.n * sizeof(double) + PAD_BYTES;
-            auto get = [&](void **p, size_t nbytes) { ok = ok && hipMalloc(p, nbytes) == hipSuccess; };
-            if (l > 0) { get((void **)&L.a, 8 * (size_t)L.n * sizeof(double) + PAD_BYTES); L.stride = L.n; get((void **)&L.b, bytes); }
-            get((void **)&L.w, bytes);
-            get((void **)&L.el, (size_t)L.n + PAD_BYTES);
-            get((void **)&L.x, bytes);
-            if (!last) get((void **)&L.t, bytes);
-        }
-        if (!ok) { (void)hipGetLastError(); vmg_free(c->vmg); return false; }
-        M->nx = nx; M->ny = ny; M->nz = nz;
+// the lattices the cycle takes: at least 8 nodes along every axis, within the grid limits of its launches
+static bool vmg_lattice_ok(int64_t nv, int nx, int ny, int nz) {
+    return (int64_t)nx * ny * nz == nv && std::min(nx, std::min(ny, nz)) >= 8 && nz <= 65535 && ny <= 4 * 65535;
+}
+
+// levels and buffers of M for this lattice (kept where M already has them); own0: level 0 gets slot arrays and a right-hand side of
+// its own.  false: no hierarchy (at most 4096 nodes) or no memory - M is released
+static bool vmg_levels_alloc(Vmg *&M, int nx, int ny, int nz, bool own0) {
+    if (M && M->nx == nx && M->ny == ny && M->nz == nz && M->own0 == own0) return true;
+    vmg_free(M);                                                            // another lattice: new levels and buffers
+    M = new Vmg();
+    M->own0 = own0;
+    VGrid g{nx, ny, nz};
+    for (;;) {
+        VLevel L;
+        L.g = g;
+        L.n = (int64_t)g.nx * g.ny * g.nz;
+        M->lv.push_back(L);
+        if (L.n <= VMG_BOTTOM_MAX) break;                                   // the first level one workgroup can hold is the coarsest
+        g = VGrid{(g.nx + 1) / 2, (g.ny + 1) / 2, (g.nz + 1) / 2};
     }
+    if (M->lv.size() < 2) { vmg_free(M); return false; }                   // (at most 4096 nodes: no hierarchy, Jacobi)
+    bool ok = hipEventCreate(&M->ev0) == hipSuccess && hipEventCreate(&M->ev1) == hipSuccess;
+    for (size_t l = 0; ok && l < M->lv.size(); ++l) {
+        VLevel &L = M->lv[l];
+        const bool last = l + 1 == M->lv.size();
+        const size_t bytes = (size_t)L.n * sizeof(double) + PAD_BYTES;
+        auto get = [&](void **p, size_t nbytes) { ok = ok && hipMalloc(p, nbytes) == hipSuccess; };
+        if (l > 0 || own0) { get((void **)&L.a, 8 * (size_t)L.n * sizeof(double) + PAD_BYTES); L.stride = L.n; get((void **)&L.b, bytes); }
+        get((void **)&L.w, bytes);
+        get((void **)&L.el, (size_t)L.n + PAD_BYTES);
+        get((void **)&L.x, bytes);
+        if (!last) get((void **)&L.t, bytes);
+    }
+    if (!ok) { (void)hipGetLastError(); vmg_free(M); return false; }
+    M->nx = nx; M->ny = ny; M->nz = nz;
+    return true;
+}
+
+// the hierarchy of the operator level 0 holds NOW: eliminated nodes and weights of level 0, then level by level P^T A P and its weights
+static bool vmg_form(Ctx *c, Vmg *M, bool timed) {
     VLevel &L0 = M->lv[0];
-    L0.a = a->uvals; L0.stride = a->uvals_stride; L0.unit = a->uvals_unit ? 1 : 0;
-    // the hierarchy of THIS operator: eliminated nodes and weights of level 0, then level by level P^T A P and its weights
-    M->timed = hipEventRecord(M->ev0, c->stream) == hipSuccess;
+    M->timed = timed && hipEventRecord(M->ev0, c->stream) == hipSuccess;
     k_vmg_rowsum<true><<<vmg_grid(L0.g), 256, 0, c->stream>>>(L0.g, L0.a, L0.stride, L0.unit, L0.el, L0.w);
     for (size_t l = 1; l < M->lv.size(); ++l) {
         VLevel &F = M->lv[l - 1], &C = M->lv[l];
@@ -536,6 +643,17 @@ bool vmg_prepare(Ctx *c, const Mesh *m, const Csr *a) {
     return true;
 }
 
+// true: the cycle applies to this solve - hierarchy formed from the operator's CURRENT (scaled) slot values, buffers there
+bool vmg_prepare(Ctx *c, Vmg *&M, const Mesh *m, const Csr *a) {
+    if (!m || !a || m->sym_nx <= 0 || !a->uvals || !a->uvals_valid || !a->uvals_scaled) return false;
+    const int nx = m->sym_nx, ny = m->sym_ny, nz = (int)(m->nv / ((int64_t)nx * ny));
+    if (!vmg_lattice_ok(m->nv, nx, ny, nz)) return false;
+    if (!vmg_levels_alloc(M, nx, ny, nz, false)) return false;
+    VLevel &L0 = M->lv[0];
+    L0.a = a->uvals; L0.stride = a->uvals_stride; L0.unit = a->uvals_unit ? 1 : 0;
+    return vmg_form(c, M, true);
+}
+
 // after the solve's last synchronisation: the hierarchy's setup time joins the context's sum (pgd_vmg_counts)
 void vmg_note_setup(Ctx *c) {
     Vmg *M = c->vmg;
@@ -546,20 +664,18 @@ void vmg_note_setup(Ctx *c) {
     M->timed = false;
 }
 
-int vmg_fix_start(Ctx *c, const double *sc, const double *b, double *x, int64_t n) {
-    Vmg *M = c->vmg;
+int vmg_fix_start(Ctx *c, Vmg *M, const double *sc, const double *b, double *x, int64_t n) {
     if (!M || M->lv.empty() || M->lv[0].n != n) return fail(c, PGD_ERR_INVALID, "vmg_fix_start: no hierarchy");
     k_vmg_fix_start<<<(unsigned)((n + TPB - 1) / TPB), TPB, 0, c->stream>>>(M->lv[0].el, sc, b, x, n);
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
 }
 
-int vmg_levels(const Ctx *c) { return c->vmg ? (int)c->vmg->lv.size() : 0; }
+static int vmg_levels(const Vmg *M) { return M ? (int)M->lv.size() : 0; }
 
 // z = M r: the cycle from level 0 down and back up; the result lands in z_out (default: vmg_result(c)), the partial sums of
-// r . z in c->partials (*nparts of them)
-int vmg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out) {
-    Vmg *M = c->vmg;
+// r . z in c->partials (*nparts of them); the level passes issued to k_vmg_march are counted in *marches
+int vmg_vcycle(Ctx *c, Vmg *M, const double *r, bool dot, int *nparts, double *z_out, int64_t *marches) {
     if (!M || M->lv.size() < 2) return fail(c, PGD_ERR_INVALID, "vmg_vcycle: no hierarchy");
     const int nl = (int)M->lv.size();
     const dim3 blk(256, 1, 1);
@@ -574,7 +690,7 @@ int vmg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out) {
         if (epi == 1) k_vmg_march<1, false><<<wgs, 256, 0, c->stream>>>(A);
         else if (d) k_vmg_march<2, true><<<wgs, 256, 0, c->stream>>>(A);
         else k_vmg_march<2, false><<<wgs, 256, 0, c->stream>>>(A);
-        c->vmg_marches += 1;
+        *marches += 1;
         return true;
     };
     // down: residual behind the folded pre-smoothing step, restriction
@@ -608,6 +724,78 @@ int vmg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out) {
     return PGD_OK;
 }
 
+// true: the component-wise cycle applies to this solve - a blocked P1 layout over a 3-D box lattice with a hierarchy, the diagonal
+// blocks of D^-1/2 A D^-1/2 extracted from the CSR values (a->vals, a->dinv are current) and their hierarchies formed
+bool cmg_prepare(Ctx *c, const Mesh *m, const Mesh *base, const Csr *a) {
+    if (!m || !base || !a || m->ncomp < 2 || m->ncomp > 3 || base->ncomp != 1 || base->gdim != 3 || base->cellsN || base->sym_nx <= 0 ||
+        !a->vals || !a->dinv || !a->dinv_valid || m->nv != base->nv * m->ncomp) return false;
+    const int nx = base->sym_nx, ny = base->sym_ny, nz = (int)(base->nv / ((int64_t)nx * ny)), nc = m->ncomp;
+    if (!vmg_lattice_ok(base->nv, nx, ny, nz) || base->nv <= VMG_BOTTOM_MAX) return false;
+    Cmg *G = c->cmg;
+    if (!G || G->ncomp != nc || !G->comp[0] || G->comp[0]->nx != nx || G->comp[0]->ny != ny || G->comp[0]->nz != nz) {
+        cmg_free(c->cmg);
+        G = c->cmg = new Cmg();
+        G->ncomp = nc;
+        bool ok = hipEventCreate(&G->ev0) == hipSuccess && hipEventCreate(&G->ev1) == hipSuccess;
+        ok = ok && hipMalloc((void **)&G->s, (size_t)m->nv * sizeof(double) + PAD_BYTES) == hipSuccess;
+        ok = ok && hipMalloc((void **)&G->bad, PAD_BYTES) == hipSuccess;
+        for (int k = 0; ok && k < nc; ++k) ok = vmg_levels_alloc(G->comp[k], nx, ny, nz, true);
+        if (!ok) { (void)hipGetLastError(); cmg_free(c->cmg); return false; }
+    }
+    const VGrid g{nx, ny, nz};
+    CmgPtrs ap{{nullptr, nullptr, nullptr}};
+    for (int k = 0; k < nc; ++k) { VLevel &L0 = G->comp[k]->lv[0]; L0.unit = 1; ap.p[k] = L0.a; }
+    G->timed = hipEventRecord(G->ev0, c->stream) == hipSuccess;
+    if (hipMemsetAsync(G->bad, 0, sizeof(int), c->stream) != hipSuccess) { (void)hipGetLastError(); return false; }
+    k_cmg_extract<<<vmg_grid(g), 256, 0, c->stream>>>(g, nc, m->row_ptr, m->cols, a->vals, a->dinv, ap, G->s, G->bad);
+    if (hipGetLastError() != hipSuccess) return false;
+    for (int k = 0; k < nc; ++k)
+        if (!vmg_form(c, G->comp[k], false)) return false;
+    G->timed = G->timed && hipEventRecord(G->ev1, c->stream) == hipSuccess;
+    int bad = 0;
+    if (hipMemcpyAsync(&bad, G->bad, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return bad == 0;
+}
+
+void cmg_note_setup(Ctx *c) {
+    Cmg *G = c->cmg;
+    if (!G || !G->timed) return;
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, G->ev0, G->ev1) == hipSuccess) c->cmg_setup_ms += (double)ms;
+    else (void)hipGetLastError();
+    G->timed = false;
+}
+
+int cmg_fix_start(Ctx *c, const double *b, double *x, int64_t n) {
+    Cmg *G = c->cmg;
+    if (!G || !G->comp[0] || G->comp[0]->lv[0].n * G->ncomp != n) return fail(c, PGD_ERR_INVALID, "cmg_fix_start: no hierarchy");
+    CmgElim el{{nullptr, nullptr, nullptr}};
+    for (int k = 0; k < G->ncomp; ++k) el.p[k] = G->comp[k]->lv[0].el;
+    k_cmg_fix_start<<<(unsigned)((n + TPB - 1) / TPB), TPB, 0, c->stream>>>(G->ncomp, el, b, x, n);
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+// z = M r: split, one cycle per component (one after the other on the stream), merge; the partial sums of r . z in c->partials
+int cmg_apply(Ctx *c, const double *r, double *z, int64_t n, int *nparts) {
+    Cmg *G = c->cmg;
+    if (!G || !G->comp[0] || G->comp[0]->lv[0].n * G->ncomp != n) return fail(c, PGD_ERR_INVALID, "cmg_apply: no hierarchy");
+    CmgPtrs bp{{nullptr, nullptr, nullptr}};
+    CmgConst xp{{nullptr, nullptr, nullptr}};
+    for (int k = 0; k < G->ncomp; ++k) { bp.p[k] = G->comp[k]->lv[0].b; xp.p[k] = G->comp[k]->lv[0].x; }
+    const int g = grid_for(n);
+    k_cmg_split<<<g, TPB, 0, c->stream>>>(G->ncomp, r, G->s, bp, n, c->flags);
+    PGD_LAUNCH_CHECK(c);
+    for (int k = 0; k < G->ncomp; ++k) PGD_TRY(vmg_vcycle(c, G->comp[k], bp.p[k], false, nullptr, nullptr, &c->cmg_marches));
+    k_cmg_merge<<<g, TPB, 0, c->stream>>>(G->ncomp, xp, G->s, r, z, n, c->partials, c->flags);
+    PGD_LAUNCH_CHECK(c);
+    if (nparts) *nparts = g;
+    return PGD_OK;
+}
+
 }  // namespace pgd
 
 using namespace pgd;
@@ -618,7 +806,7 @@ int pgd_vmg_counts(pgd_handle h, int64_t *solves, int64_t *fallbacks, int64_t *l
     PGD_CTX(c, h);
     if (solves) *solves = c->vmg_solves;
     if (fallbacks) *fallbacks = c->vmg_fallbacks;
-    if (levels) *levels = vmg_levels(c);
+    if (levels) *levels = vmg_levels(c->vmg);
     return PGD_OK;
 }
 
@@ -626,6 +814,21 @@ int pgd_vmg_times(pgd_handle h, double *setup_ms, int64_t *march_passes) {
     PGD_CTX(c, h);
     if (setup_ms) *setup_ms = c->vmg_setup_ms;
     if (march_passes) *march_passes = c->vmg_marches;
+    return PGD_OK;
+}
+
+int pgd_cmg_counts(pgd_handle h, int64_t *solves, int64_t *fallbacks, int64_t *levels) {
+    PGD_CTX(c, h);
+    if (solves) *solves = c->cmg_solves;
+    if (fallbacks) *fallbacks = c->cmg_fallbacks;
+    if (levels) *levels = c->cmg ? vmg_levels(c->cmg->comp[0]) : 0;
+    return PGD_OK;
+}
+
+int pgd_cmg_times(pgd_handle h, double *setup_ms, int64_t *march_passes) {
+    PGD_CTX(c, h);
+    if (setup_ms) *setup_ms = c->cmg_setup_ms;
+    if (march_passes) *march_passes = c->cmg_marches;
     return PGD_OK;
 }
 

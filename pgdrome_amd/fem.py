@@ -3663,17 +3663,22 @@ def _solve_linear(A, b, x, prm):
             # counters; every other value is the Jacobi-PCG.  The row-sharded solve has the Jacobi form only.
             # VARIABLE_MULTIGRID_NAMES (opt-in) ask for the V-cycle of pgd_vmg.hip instead: any scalar P1 operator on a lattice
             # mesh, any Dirichlet set.  A backend without it (the numpy oracle) and a row-sharded layout answer with the Jacobi-PCG.
+            # COMPONENT_MULTIGRID_NAMES (opt-in) ask for one such cycle per component of a vector-valued P1 space on a box lattice
+            # (the diagonal blocks of the operator); "amg" and "vmg" on a vector space stay the Jacobi-PCG.
             prec = prm.get("preconditioner", "default")
             prec_name = "" if isinstance(prec, _Params) else str(prec).lower()
             asks_mg = prec_name in MULTIGRID_NAMES
             want_mg = asks_mg and part is None
             want_vmg = prec_name in VARIABLE_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_variable")
-            mg0 = vmg0 = None
-            used = used_v = 0
+            want_cmg = prec_name in COMPONENT_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_component")
+            mg0 = vmg0 = cmg0 = None
+            used = used_v = used_c = 0
             if want_mg and hasattr(be, "precondition"):
                 mg0 = be.precondition(1)
             elif want_vmg:
                 vmg0 = be.precondition_variable(True)
+            elif want_cmg:
+                cmg0 = be.precondition_component(True)
             try:
                 if part is not None:
                     # a row-sharded lattice: the V-cycle with level 0 on the slabs and levels >= 1 replicated (dist.pcg_mg);
@@ -3692,12 +3697,16 @@ def _solve_linear(A, b, x, prm):
                     used = be.precondition(0) - mg0
                 if vmg0 is not None:
                     used_v = be.precondition_variable(False) - vmg0
+                if cmg0 is not None:
+                    used_c = be.precondition_component(False) - cmg0
             STATS["pcg_seconds"] += time.perf_counter() - t_solve      # the solve returns synchronised
-            info.update(method="mg_pcg" if used > 0 else "vmg_pcg" if used_v > 0 else "jacobi_pcg", iterations=it, relres=rel)
+            info.update(method="mg_pcg" if used > 0 else "vmg_pcg" if used_v > 0 else "cmg_pcg" if used_c > 0 else "jacobi_pcg", iterations=it, relres=rel)
             if used > 0:
                 STATS["mg_solves"] = STATS.get("mg_solves", 0) + 1
             if used_v > 0:
                 STATS["vmg_solves"] = STATS.get("vmg_solves", 0) + 1
+            if used_c > 0:
+                STATS["cmg_solves"] = STATS.get("cmg_solves", 0) + 1
             if rel > max(rtol, 1e-14) * 1.0001 and it >= maxit:
                 # dolfin's Krylov solvers raise on non-convergence unless told otherwise (error_on_nonconvergence,
                 # default True): an unconverged mode must not be stored silently
@@ -3710,15 +3719,17 @@ def _solve_linear(A, b, x, prm):
     finally:
         be.atom_free(op)
     STATS["linear_solves"] += 1
-    STATS["pcg_iterations"] += info.get("iterations", 0) if info.get("method") in ("jacobi_pcg", "mg_pcg", "vmg_pcg") else 0
+    STATS["pcg_iterations"] += info.get("iterations", 0) if info.get("method") in ("jacobi_pcg", "mg_pcg", "vmg_pcg", "cmg_pcg") else 0
     return info
 
 
-STATS = {"linear_solves": 0, "pcg_iterations": 0, "pcg_seconds": 0.0, "mg_solves": 0, "vmg_solves": 0}
+STATS = {"linear_solves": 0, "pcg_iterations": 0, "pcg_seconds": 0.0, "mg_solves": 0, "vmg_solves": 0, "cmg_solves": 0}
 # values of settings["preconditioner"] that select the geometric multigrid V-cycle (dolfin's names of its algebraic ones included)
 MULTIGRID_NAMES = ("amg", "hypre_amg", "petsc_amg", "ml_amg", "gmg", "multigrid", "mg")
 # ... and those that select the V-cycle for variable-coefficient operators (pgd_vmg.hip): opt-in, none of the names above
 VARIABLE_MULTIGRID_NAMES = ("vmg", "variable_multigrid")
+# ... and those that select one such cycle per component of a vector-valued P1 space on a box lattice: opt-in, its own names
+COMPONENT_MULTIGRID_NAMES = ("cmg", "component_multigrid")
 
 
 def _apply_bcs_system(A, b, bcs):

@@ -455,7 +455,8 @@ enum {
                                 bit for bit). */
     PGD_TUNE_MG_MARCH_MIN = 42, /* multigrid levels with at least this many nodes along x and y run their stencil passes in
                                 k_spmv_stencil_march (default 64); smaller ones in the plain kernels of pgd_mg.hip.  The same bound
-                                decides between k_vmg_march and the plain kernels of pgd_vmg.hip (PGD_TUNE_PCG_PRECOND = 2). */
+                                decides between k_vmg_march (the march body of k_spmv_dia_march2 with the cycle's epilogues, pgd_dia_march.h) and
+                                the plain kernels of pgd_vmg.hip (PGD_TUNE_PCG_PRECOND = 2). */
     PGD_TUNE_MG_CHUNK = 41, /* PCG iterations queued between two looks at the convergence flags when the multigrid preconditioner is on
                                 (even, default 2: an iteration is ~50 launches, the next chunk is queued while the flags of the last travel; the Jacobi form queues 16) */
     PGD_TUNE_PCG_PRECOND = 40, /* preconditioner of pgd_pcg_solve: 0 (default) Jacobi = the symmetric diagonal scaling; 1 a geometric

@@ -25,6 +25,9 @@
 //
 // Levels with at least mg_march_min nodes along x and y run their two stencil passes in k_spmv_stencil_march (epilogues 1 and 2,
 // pgd_spmv.hip: 16 and 24 B per row at the product's rate); the small ones in the plain kernels below.
+//
+// One builder of the levels (mg_levels) and one Galerkin chain (mg_stencils) serve both users: mg_prepare (the whole lattice on one
+// GPU) and pgd_mg_slab_setup (a z-slab of a row-sharded lattice, whose level 0 lives in the caller's vectors).
 #include "pgd_internal.h"
 
 #include <cmath>
@@ -189,25 +192,20 @@ __global__ __launch_bounds__(1024) void k_mg_bottom(MgGrid g, MgSt S, const doub
     }
 }
 
-// are the eliminated nodes of the operator exactly the hull of the lattice?
-__global__ __launch_bounds__(TPB) void k_mg_hull_check(const uint8_t *__restrict__ cls, int ident, int nx, int ny, int nz, int *__restrict__ bad) {
-    const int64_t P = (int64_t)nx * ny, n = P * nz;
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= n) return;
-    const int z = (int)(i / P), rem = (int)(i - (int64_t)z * P), y = rem / nx, x = rem - y * nx;
+// are the eliminated nodes of the rows [row0, row1) exactly the hull of the lattice?  The array starts at plane zoff of a lattice of
+// nz planes (the whole lattice: zoff = 0, rows [0, n))
+__global__ __launch_bounds__(TPB) void k_mg_hull_check(const uint8_t *__restrict__ cls, int ident, int nx, int ny, int nz, int zoff, int64_t row0,
+                                                       int64_t row1, int *__restrict__ bad) {
+    const int64_t P = (int64_t)nx * ny;
+    const int64_t i = row0 + (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= row1) return;
+    const int zl = (int)(i / P), rem = (int)(i - (int64_t)zl * P), y = rem / nx, x = rem - y * nx, z = zl + zoff;
     const bool hull = x == 0 || y == 0 || z == 0 || x == nx - 1 || y == ny - 1 || z == nz - 1;
     if (((int)cls[i] == ident) != hull) *bad = 1;
 }
 
-__global__ __launch_bounds__(TPB) void k_mg_codes(MgGrid g, uint8_t *__restrict__ cls) {
-    const int64_t P = (int64_t)g.nx * g.ny, n = P * g.nz;
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= n) return;
-    const int z = (int)(i / P), rem = (int)(i - (int64_t)z * P), y = rem / g.nx, x = rem - y * g.nx;
-    cls[i] = mg_is_free(g, x, y, z) ? 0 : 1;
-}
-
-__global__ __launch_bounds__(TPB) void k_mg_codes_slab(MgGrid g, int zoff, int nzloc, uint8_t *__restrict__ cls) {
+// code bytes of the march kernel (1 = eliminated) for the planes [zoff, zoff + nzloc) of lattice g (the whole lattice: 0, g.nz)
+__global__ __launch_bounds__(TPB) void k_mg_codes(MgGrid g, int zoff, int nzloc, uint8_t *__restrict__ cls) {
     const int64_t P = (int64_t)g.nx * g.ny, n = P * nzloc;
     const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
     if (i >= n) return;
@@ -260,14 +258,16 @@ static bool mg_galerkin(const double cf[8], double cc[8]) {
     return cc[0] > 0.0 && leak <= 1e-10 * scale;
 }
 
-static void mg_free(Mg *&M) {
+// releases the levels of M and their buffers; levels_only: M itself, its flag and its slab codes stay
+static void mg_free(Mg *&M, bool levels_only = false) {
     if (!M) return;
-    for (MgLevel &L : M->lv) {
-        if (L.b) (void)hipFree(L.b);
-        if (L.x) (void)hipFree(L.x);
-        if (L.t) (void)hipFree(L.t);
-        if (L.cls) (void)hipFree(L.cls);
-    }
+    for (MgLevel &L : M->lv)
+        for (void *p : {(void *)L.b, (void *)L.x, (void *)L.t, (void *)L.cls}) if (p) (void)hipFree(p);
+    M->lv.clear();
+    M->nx = M->ny = M->nz = 0;
+    M->have_key = false;
+    M->cls_zoff = M->cls_nzloc = -1;                                        // (the slab codes belong to the lattice too)
+    if (levels_only) return;
     if (M->bad) (void)hipFree(M->bad);
     if (M->cls_slab) (void)hipFree(M->cls_slab);
     delete M;
@@ -284,80 +284,97 @@ double *mg_result(Ctx *c) { return c->mg && !c->mg->lv.empty() ? c->mg->lv[0].x 
 
 static dim3 mg_grid(const MgGrid &g) { return dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4), (unsigned)g.nz); }
 
+// the context's hierarchy object, created with its device flag (one per Mg); nullptr: no memory for the flag
+static Mg *mg_get(Mg *&M) {
+    if (M) return M;
+    M = new Mg();
+    if (hipMalloc((void **)&M->bad, sizeof(int)) != hipSuccess) { (void)hipGetLastError(); mg_free(M); }
+    return M;
+}
+
+// one stencil the Galerkin chain can start from: no NaN, positive diagonal
+static bool mg_stencil_ok(const Csr *a) {
+    for (int s = 1; s < 8; ++s) if (!(a->st_c[s] == a->st_c[s])) return false;
+    return a->st_c[0] > 0.0;
+}
+
+// The levels of M for the lattice (nx, ny, nz), kept where M already has them: halve until an axis drops under 8 (the far face of a
+// coarse level is eliminated only where the fine node count is odd), right-hand side / result / work vectors per level, code bytes
+// of the march on the inner levels.  own0: level 0 has a result and a work vector of its own (else it lives in the caller's
+// vectors).  false: no hierarchy (under two levels, or a coarsest level one workgroup cannot hold) or, with *err set, a failing HIP
+// call; M is then left without levels and nothing is leaked.
+static bool mg_levels(Ctx *c, Mg *M, int nx, int ny, int nz, bool own0, hipError_t *err) {
+    *err = hipSuccess;
+    if (M->nx == nx && M->ny == ny && M->nz == nz) return true;
+    mg_free(M, true);                                                       // another lattice: new levels and buffers
+    MgGrid g{nx, ny, nz, 1, 1, 1};
+    for (;;) {
+        MgLevel L;
+        L.g = g;
+        L.n = (int64_t)g.nx * g.ny * g.nz;
+        M->lv.push_back(L);
+        if (std::min(g.nx, std::min(g.ny, g.nz)) < 8) break;
+        g = MgGrid{(g.nx + 1) / 2, (g.ny + 1) / 2, (g.nz + 1) / 2, g.fx && (g.nx & 1), g.fy && (g.ny & 1), g.fz && (g.nz & 1)};
+    }
+    if (M->lv.size() < 2 || M->lv.back().n > MG_BOTTOM_MAX) { mg_free(M, true); return false; }
+    auto get = [&](void **q, size_t bytes) { if (*err == hipSuccess) *err = hipMalloc(q, bytes); };
+    for (size_t l = 0; l < M->lv.size(); ++l) {
+        MgLevel &L = M->lv[l];
+        const bool last = l + 1 == M->lv.size();
+        const size_t bytes = (size_t)L.n * sizeof(double);
+        if (l > 0) get((void **)&L.b, bytes);
+        if (l > 0 || own0) get((void **)&L.x, bytes);
+        if (!last && (l > 0 || own0)) get((void **)&L.t, bytes);
+        if (l > 0 && !last) {
+            get((void **)&L.cls, (size_t)L.n);
+            if (*err == hipSuccess) k_mg_codes<<<(unsigned)((L.n + TPB - 1) / TPB), TPB, 0, c->stream>>>(L.g, 0, L.g.nz, L.cls);
+        }
+    }
+    if (*err == hipSuccess) *err = hipGetLastError();
+    if (*err != hipSuccess) { (void)hipGetLastError(); mg_free(M, true); return false; }
+    M->nx = nx; M->ny = ny; M->nz = nz;
+    return true;
+}
+
+// Stencil and Jacobi weight of every level from the operator's stencil st_c, P^T A P level by level; kept while st_c stays the same
+// bit by bit.  false: a coarse operator leaves the 15-point pattern
+static bool mg_stencils(Mg *M, const double st_c[8]) {
+    if (M->have_key && std::memcmp(M->key, st_c, sizeof M->key) == 0) return true;
+    M->have_key = false;
+    double cf[8];
+    for (int s = 0; s < 8; ++s) cf[s] = st_c[s];
+    for (size_t l = 0; l < M->lv.size(); ++l) {
+        MgLevel &L = M->lv[l];
+        for (int s = 0; s < 8; ++s) L.s.c[s] = cf[s];
+        L.s.w = (6.0 / 7.0) / cf[0];      // (prototype scan at 64^3, V(1,1)-PCG iterations: 0.7 -> 20, 0.8 -> 19, 6/7 -> 18, 0.9 -> 18, 0.95 -> 24, 1 -> 100)
+        if (l + 1 < M->lv.size()) {
+            double cc[8];
+            if (!mg_galerkin(cf, cc)) return false;
+            for (int s = 0; s < 8; ++s) cf[s] = cc[s];
+        }
+    }
+    std::memcpy(M->key, st_c, sizeof M->key);
+    M->have_key = true;
+    return true;
+}
+
 bool mg_prepare(Ctx *c, const Mesh *m, const Csr *a) {
     if (!m || !a || !a->st_ok || a->st_ident < 0 || !a->cls || m->sym_nx <= 0) return false;
     const int nx = m->sym_nx, ny = m->sym_ny, nz = (int)(m->nv / ((int64_t)nx * ny));
     if ((int64_t)nx * ny * nz != m->nv || std::min(nx, std::min(ny, nz)) < 8 || nz > 65535 || ny > 4 * 65535) return false;
     if (a->st_z0 != 0 || a->st_z1 != nz) return false;                     // (the whole lattice was verified, not a slab of it)
-    for (int s = 1; s < 8; ++s) if (!(a->st_c[s] == a->st_c[s])) return false;
-    if (!(a->st_c[0] > 0.0)) return false;
-    if (!c->mg) c->mg = new Mg();
-    Mg *M = c->mg;
-    if (!M->bad) {
-        void *q = nullptr;
-        if (hipMalloc(&q, sizeof(int)) != hipSuccess) return false;
-        M->bad = (int *)q;
-    }
+    if (!mg_stencil_ok(a)) return false;
+    Mg *M = mg_get(c->mg);
+    if (!M) return false;
     // the eliminated nodes must be the hull, nothing else (one pass over the code bytes; read back with the solve's first look)
     int bad = 0;
     if (hipMemsetAsync(M->bad, 0, sizeof(int), c->stream) != hipSuccess) return false;
-    k_mg_hull_check<<<(unsigned)((m->nv + TPB - 1) / TPB), TPB, 0, c->stream>>>(a->cls, a->st_ident, nx, ny, nz, M->bad);
+    k_mg_hull_check<<<(unsigned)((m->nv + TPB - 1) / TPB), TPB, 0, c->stream>>>(a->cls, a->st_ident, nx, ny, nz, 0, 0, m->nv, M->bad);
     if (hipMemcpyAsync(&bad, M->bad, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
         return false;
     if (bad) return false;
-    if (M->nx != nx || M->ny != ny || M->nz != nz) {                       // another lattice: new levels and buffers
-        mg_free(c->mg);
-        c->mg = new Mg();
-        M = c->mg;
-        void *q = nullptr;
-        if (hipMalloc(&q, sizeof(int)) != hipSuccess) return false;
-        M->bad = (int *)q;
-        M->nx = nx; M->ny = ny; M->nz = nz;
-        MgGrid g{nx, ny, nz, 1, 1, 1};
-        for (;;) {
-            MgLevel L;
-            L.g = g;
-            L.n = (int64_t)g.nx * g.ny * g.nz;
-            M->lv.push_back(L);
-            if (std::min(g.nx, std::min(g.ny, g.nz)) < 8) break;
-            MgGrid h;
-            h.nx = (g.nx + 1) / 2; h.ny = (g.ny + 1) / 2; h.nz = (g.nz + 1) / 2;
-            h.fx = g.fx && (g.nx & 1); h.fy = g.fy && (g.ny & 1); h.fz = g.fz && (g.nz & 1);
-            g = h;
-        }
-        if (M->lv.size() < 2 || M->lv.back().n > MG_BOTTOM_MAX) { M->nx = 0; M->lv.clear(); return false; }
-        for (size_t l = 0; l < M->lv.size(); ++l) {
-            MgLevel &L = M->lv[l];
-            void *q2 = nullptr;
-            const size_t bytes = (size_t)L.n * sizeof(double);
-            if (l > 0) { if (hipMalloc(&q2, bytes) != hipSuccess) { M->nx = 0; return false; } L.b = (double *)q2; }
-            if (hipMalloc(&q2, bytes) != hipSuccess) { M->nx = 0; return false; }
-            L.x = (double *)q2;
-            if (l + 1 < M->lv.size()) { if (hipMalloc(&q2, bytes) != hipSuccess) { M->nx = 0; return false; } L.t = (double *)q2; }
-            if (l > 0 && l + 1 < M->lv.size()) {
-                if (hipMalloc(&q2, (size_t)L.n) != hipSuccess) { M->nx = 0; return false; }
-                L.cls = (uint8_t *)q2;
-                k_mg_codes<<<(unsigned)((L.n + TPB - 1) / TPB), TPB, 0, c->stream>>>(L.g, L.cls);
-            }
-        }
-        M->have_key = false;
-    }
-    if (!M->have_key || std::memcmp(M->key, a->st_c, sizeof M->key) != 0) {
-        double cf[8];
-        for (int s = 0; s < 8; ++s) cf[s] = a->st_c[s];
-        for (size_t l = 0; l < M->lv.size(); ++l) {
-            MgLevel &L = M->lv[l];
-            for (int s = 0; s < 8; ++s) L.s.c[s] = cf[s];
-            L.s.w = (6.0 / 7.0) / cf[0];      // (prototype scan at 64^3, V(1,1)-PCG iterations: 0.7 -> 20, 0.8 -> 19, 6/7 -> 18, 0.9 -> 18, 0.95 -> 24, 1 -> 100)
-            if (l + 1 < M->lv.size()) {
-                double cc[8];
-                if (!mg_galerkin(cf, cc)) { M->have_key = false; return false; }
-                for (int s = 0; s < 8; ++s) cf[s] = cc[s];
-            }
-        }
-        std::memcpy(M->key, a->st_c, sizeof M->key);
-        M->have_key = true;
-    }
+    hipError_t err;                                                         // (not reported: a failure here is a fallback, counted by the caller)
+    if (!mg_levels(c, M, nx, ny, nz, true, &err) || !mg_stencils(M, a->st_c)) return false;
     M->cls0 = a->cls;
     M->ident0 = a->st_ident;
     const dim3 g0 = mg_grid(M->lv[0].g);
@@ -444,31 +461,18 @@ int mg_vcycle(Ctx *c, const double *r, bool dot, int *nparts, double *z_out) {
 // Applies where A itself (unscaled) is one stencil + eliminated nodes on the rank's owned planes (dia_classify, every row verified)
 // and the eliminated nodes of those planes are exactly the hull of the GLOBAL lattice.
 
-__global__ __launch_bounds__(TPB) void k_mg_hull_check_slab(const uint8_t *__restrict__ cls, int ident, int nx, int ny, int nz_global, int zoff,
-                                                            int64_t row0, int64_t row1, int *__restrict__ bad) {
-    const int64_t P = (int64_t)nx * ny;
-    const int64_t i = row0 + (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= row1) return;
-    const int zl = (int)(i / P), rem = (int)(i - (int64_t)zl * P), y = rem / nx, x = rem - y * nx, z = zl + zoff;
-    const bool hull = x == 0 || y == 0 || z == 0 || x == nx - 1 || y == ny - 1 || z == nz_global - 1;
-    if (((int)cls[i] == ident) != hull) *bad = 1;
-}
-
-static void mg_free_levels(Mg *M) {
-    for (MgLevel &L : M->lv) {
-        if (L.b) (void)hipFree(L.b);
-        if (L.x) (void)hipFree(L.x);
-        if (L.t) (void)hipFree(L.t);
-        if (L.cls) (void)hipFree(L.cls);
-    }
-    M->lv.clear();
-}
-
 }  // namespace pgd
 
 using namespace pgd;
 
 extern "C" {
+
+int pgd_mg_counts(pgd_handle h, int64_t *solves, int64_t *fallbacks) {
+    PGD_CTX(c, h);
+    if (solves) *solves = c->mg_solves;
+    if (fallbacks) *fallbacks = c->mg_fallbacks;
+    return PGD_OK;
+}
 
 int pgd_mg_slab_setup(pgd_handle h, pgd_handle oh, int nz_global, int z_first, int64_t own0, int64_t own1, int64_t *n_coarse, int *applies) {
     PGD_CTX(c, h);
@@ -492,70 +496,22 @@ int pgd_mg_slab_setup(pgd_handle h, pgd_handle oh, int nz_global, int z_first, i
     if (!sym || !a->uvals_valid || a->uvals_scaled) return PGD_OK;
     PGD_TRY(dia_classify(c, m, a, lz0, lz1));
     if (!a->st_ok || a->st_ident < 0 || !a->cls || a->st_z0 != lz0 || a->st_z1 != lz1) return PGD_OK;
-    for (int s = 1; s < 8; ++s) if (!(a->st_c[s] == a->st_c[s])) return PGD_OK;
-    if (!(a->st_c[0] > 0.0)) return PGD_OK;
-    if (!c->mg_slab) c->mg_slab = new Mg();
-    Mg *M = c->mg_slab;
+    if (!mg_stencil_ok(a)) return PGD_OK;
+    Mg *M = mg_get(c->mg_slab);
+    if (!M) return fail(c, PGD_ERR_HIP, "mg_slab_setup: no device memory for the hull-check flag");
     M->slab = true;
-    if (!M->bad) {
-        void *q = nullptr;
-        PGD_HIP(c, hipMalloc(&q, sizeof(int)));
-        M->bad = (int *)q;
-    }
     int bad = 0;
     PGD_HIP(c, hipMemsetAsync(M->bad, 0, sizeof(int), c->stream));
-    k_mg_hull_check_slab<<<(unsigned)((own1 - own0 + TPB - 1) / TPB), TPB, 0, c->stream>>>(a->cls, a->st_ident, nx, ny, nz_global, z_first, own0, own1, M->bad);
+    k_mg_hull_check<<<(unsigned)((own1 - own0 + TPB - 1) / TPB), TPB, 0, c->stream>>>(a->cls, a->st_ident, nx, ny, nz_global, z_first, own0, own1, M->bad);
     PGD_HIP(c, hipMemcpyAsync(&bad, M->bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     PGD_HIP(c, hipStreamSynchronize(c->stream));
     if (bad) return PGD_OK;
-    if (M->nx != nx || M->ny != ny || M->nz != nz_global) {
-        mg_free_levels(M);
-        M->nx = M->ny = M->nz = 0;
-        MgGrid g{nx, ny, nz_global, 1, 1, 1};
-        for (;;) {
-            MgLevel L;
-            L.g = g;
-            L.n = (int64_t)g.nx * g.ny * g.nz;
-            M->lv.push_back(L);
-            if (std::min(g.nx, std::min(g.ny, g.nz)) < 8) break;
-            MgGrid hh;
-            hh.nx = (g.nx + 1) / 2; hh.ny = (g.ny + 1) / 2; hh.nz = (g.nz + 1) / 2;
-            hh.fx = g.fx && (g.nx & 1); hh.fy = g.fy && (g.ny & 1); hh.fz = g.fz && (g.nz & 1);
-            g = hh;
-        }
-        if (M->lv.size() < 2 || M->lv.back().n > MG_BOTTOM_MAX) { M->lv.clear(); return PGD_OK; }
-        for (size_t l = 1; l < M->lv.size(); ++l) {          // (level 0 lives in the caller's slab vectors)
-            MgLevel &L = M->lv[l];
-            void *q2 = nullptr;
-            const size_t bytes = (size_t)L.n * sizeof(double);
-            PGD_HIP(c, hipMalloc(&q2, bytes)); L.b = (double *)q2;
-            PGD_HIP(c, hipMalloc(&q2, bytes)); L.x = (double *)q2;
-            if (l + 1 < M->lv.size()) {
-                PGD_HIP(c, hipMalloc(&q2, bytes)); L.t = (double *)q2;
-                PGD_HIP(c, hipMalloc(&q2, (size_t)L.n)); L.cls = (uint8_t *)q2;
-                k_mg_codes<<<(unsigned)((L.n + TPB - 1) / TPB), TPB, 0, c->stream>>>(L.g, L.cls);
-            }
-        }
-        PGD_LAUNCH_CHECK(c);
-        M->nx = nx; M->ny = ny; M->nz = nz_global;
-        M->have_key = false;
+    hipError_t err;
+    if (!mg_levels(c, M, nx, ny, nz_global, false, &err)) {               // (level 0 lives in the caller's slab vectors)
+        if (err != hipSuccess) return fail(c, PGD_ERR_HIP, "mg_slab_setup: building the levels failed: %s", hipGetErrorString(err));
+        return PGD_OK;
     }
-    if (!M->have_key || std::memcmp(M->key, a->st_c, sizeof M->key) != 0) {
-        double cf[8];
-        for (int s = 0; s < 8; ++s) cf[s] = a->st_c[s];
-        for (size_t l = 0; l < M->lv.size(); ++l) {
-            MgLevel &L = M->lv[l];
-            for (int s = 0; s < 8; ++s) L.s.c[s] = cf[s];
-            L.s.w = (6.0 / 7.0) / cf[0];
-            if (l + 1 < M->lv.size()) {
-                double cc[8];
-                if (!mg_galerkin(cf, cc)) { M->have_key = false; return PGD_OK; }
-                for (int s = 0; s < 8; ++s) cf[s] = cc[s];
-            }
-        }
-        std::memcpy(M->key, a->st_c, sizeof M->key);
-        M->have_key = true;
-    }
+    if (!mg_stencils(M, a->st_c)) return PGD_OK;
     M->zoff = z_first; M->nzloc = nzloc; M->lz0 = lz0; M->lz1 = lz1;
     if (M->cls_zoff != z_first || M->cls_nzloc != nzloc || M->cls_slab_bytes < (size_t)m->nv) {
         if (M->cls_slab && M->cls_slab_bytes < (size_t)m->nv) { (void)hipFree(M->cls_slab); M->cls_slab = nullptr; M->cls_slab_bytes = 0; }
@@ -564,7 +520,7 @@ int pgd_mg_slab_setup(pgd_handle h, pgd_handle oh, int nz_global, int z_first, i
             PGD_HIP(c, hipMalloc(&q, (size_t)m->nv + PAD_BYTES));
             M->cls_slab = (uint8_t *)q; M->cls_slab_bytes = (size_t)m->nv;
         }
-        k_mg_codes_slab<<<(unsigned)((m->nv + TPB - 1) / TPB), TPB, 0, c->stream>>>(M->lv[0].g, z_first, nzloc, M->cls_slab);
+        k_mg_codes<<<(unsigned)((m->nv + TPB - 1) / TPB), TPB, 0, c->stream>>>(M->lv[0].g, z_first, nzloc, M->cls_slab);
         PGD_LAUNCH_CHECK(c);
         M->cls_zoff = z_first; M->cls_nzloc = nzloc;
     }

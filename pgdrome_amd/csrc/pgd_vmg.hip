@@ -25,9 +25,10 @@
 //     (v = u + P e), then x = v + W (b - A v); the coarsest level - the first with at most 4096 nodes - is 24 sweeps
 //     inside one workgroup.  A lattice of at most 4096 nodes has no hierarchy: Jacobi-PCG.
 // Levels with at least mg_march_min nodes along x and y run their two passes in k_vmg_march: the z-march of the diagonal form
-// (k_spmv_dia_march2: planes of the input staged in an LDS ring, the plane-below couplings handed on through LDS) with the two
-// epilogues of the cycle; smaller levels in the plain kernels.
+// (dia_march2 of pgd_dia_march.h, the one body it shares with k_spmv_dia_march2: planes of the input staged in an LDS ring, the
+// plane-below couplings handed on through LDS) with the two epilogues of the cycle; smaller levels in the plain kernels.
 #include "pgd_internal.h"
+#include "pgd_dia_march.h"
 
 #include <cmath>
 #include <cstring>
@@ -381,168 +382,13 @@ __global__ __launch_bounds__(TPB) void k_cmg_fix_start(int ncomp, CmgElim el, co
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// The z-march of the diagonal form (k_spmv_dia_march2: a 64 x 8 patch per 256-thread workgroup, two rows per thread, three planes of
-// the input in an LDS ring, the plane-below couplings handed on through LDS) with the epilogues of the cycle:
+// The two level passes of the cycle in the z-march of the diagonal form (dia_march2, pgd_dia_march.h: the body of the product
+// k_spmv_dia_march2 - a 64 x 8 patch per 256-thread workgroup, two rows per thread, three planes of the input in an LDS ring, the
+// plane-below couplings handed on through LDS) with its epilogues 1 and 2:
 //   EPI 1: staged u = w in;  out = in - A u on free rows, 0 on eliminated ones                   (in = the level's right-hand side)
 //   EPI 2: staged v = in;    out = v + w (b - A v);  DOT: partial sums of b . out per workgroup  (in = the prolongated vector)
-struct VmArgs {
-    const double *a, *w, *in, *b;
-    double *out, *partials;
-    const int *flags;
-    int64_t n;              // slot stride in doubles
-    int nx, ny, nz, zchunk, tiles_x, tiles_y, unit;
-};
-constexpr int VM_HX = 66;            // cells per line of the staged patch: 64 + one halo cell each way
-
 template <int EPI, bool DOT>
-__global__ __launch_bounds__(256) void k_vmg_march(VmArgs A) {
-    constexpr int NT = 256, PY = 8, HY = PY + 2, SLICE = VM_HX * HY;        // 660 cells per plane
-    __shared__ double s_x[3 * SLICE];
-    __shared__ double s_lo[2 * 4 * NT];                     // [row of the pair][slot 4..7][thread]
-    __shared__ double s_red[4];
-    if (A.flags && A.flags[0]) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int b = xcd_remap(blockIdx.x, gridDim.x);
-    const int per_chunk = A.tiles_x * A.tiles_y;
-    const int chunk = b / per_chunk, tile = b - chunk * per_chunk;
-    const int ty = tile / A.tiles_x, tx = tile - ty * A.tiles_x;
-    const int x0 = tx * 64, y0 = ty * PY;
-    const int x = x0 + lane, ya = y0 + 2 * wv;
-    const bool live0 = x < A.nx && ya < A.ny, live1 = x < A.nx && ya + 1 < A.ny;
-    const bool inx0 = live0 && x > 0, inx1 = live1 && x > 0;
-    const bool iny0 = live0 && ya > 0;                      // the upper row of the pair always has its y - 1 neighbour: the lower row
-    const bool ldx = lane > 0, ldy = wv > 0;
-    const int64_t nx = A.nx, P = (int64_t)A.nx * A.ny, n = A.n;
-    const int64_t base0 = live0 ? x + nx * ya : 0, base1 = live1 ? x + nx * (ya + 1) : 0;
-    const int centre = (2 * wv + 1) * VM_HX + lane + 1;     // the lower row of the pair; the upper one at + VM_HX
-    const int za = chunk * A.zchunk, zb = min(A.nz, za + A.zchunk);
-    int64_t goff[3];
-    bool gok[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const int i = tid + q * NT;
-        const int ly = i / VM_HX, lx = i - ly * VM_HX;
-        const int gx = x0 - 1 + lx, gy = y0 - 1 + ly;
-        gok[q] = i < SLICE && gx >= 0 && gx < A.nx && gy >= 0 && gy < A.ny;
-        goff[q] = gok[q] ? gx + nx * gy : 0;
-    }
-    auto fetch = [&](int z, double v[3]) {
-        const bool zok = z >= 0 && z < A.nz;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            v[q] = 0.0;
-            if (zok && gok[q]) {
-                const int64_t j = goff[q] + P * z;
-                v[q] = EPI == 1 ? A.w[j] * A.in[j] : A.in[j];
-            }
-        }
-    };
-    auto put = [&](int z, const double v[3]) {
-        const int sl = ((z % 3) + 3) % 3;
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-            if (tid + q * NT < SLICE) s_x[sl * SLICE + tid + q * NT] = v[q];
-    };
-    double dot = 0.0;
-    if (za < zb) {
-        double v[3];
-        for (int z = za - 1; z <= za + 1; ++z) { fetch(z, v); put(z, v); }
-        if (za > 0) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                s_lo[s * NT + tid] = A.a[(int64_t)(4 + s) * n + base0 + P * (za - 1)];
-                s_lo[(4 + s) * NT + tid] = A.a[(int64_t)(4 + s) * n + base1 + P * (za - 1)];
-            }
-        }
-    }
-    __syncthreads();
-    for (int z = za; z < zb; ++z) {
-        double vn[3] = {0.0, 0.0, 0.0};
-        if (z + 2 <= zb) fetch(z + 2, vn);                  // plane zb + 1 is never read
-        const int64_t r0 = base0 + P * z, r1 = base1 + P * z;
-        double u0[8], u1[8];
-        u0[0] = u1[0] = 1.0;                                // unit diagonal of the scaled operator (level 0)
-        if (!A.unit) { u0[0] = A.a[r0]; u1[0] = A.a[r1]; }
-#pragma unroll
-        for (int s = 1; s < 8; ++s) { u0[s] = A.a[(int64_t)s * n + r0]; u1[s] = A.a[(int64_t)s * n + r1]; }
-        // the rows' own vector entries of the epilogue (EPI 1: in = the right-hand side; EPI 2: b)
-        const double w0 = A.w[r0], w1 = A.w[r1];
-        const double e0 = EPI == 1 ? A.in[r0] : A.b[r0], e1 = EPI == 1 ? A.in[r1] : A.b[r1];
-        // in-plane lower couplings from the neighbouring rows' slots (L1 / L2); (0, -1) of the upper row = u0[2]
-        const double t1a = A.a[1 * n + (inx0 ? r0 - 1 : r0)];
-        const double t2a = A.a[2 * n + (iny0 ? r0 - nx : r0)];
-        const double t3a = A.a[3 * n + ((inx0 && iny0) ? r0 - nx - 1 : r0)];
-        const double t1b = A.a[1 * n + (inx1 ? r1 - 1 : r1)];
-        const double t3b = A.a[3 * n + (inx1 ? r1 - nx - 1 : r1)];
-        double a4 = 0.0, a5 = 0.0, a6 = 0.0, a7 = 0.0, b4 = 0.0, b5 = 0.0, b6 = 0.0, b7 = 0.0;
-        if (z > 0) {                                        // uniform
-            a4 = live0 ? s_lo[tid] : 0.0;
-            b4 = live1 ? s_lo[4 * NT + tid] : 0.0;
-            if (inx0) a5 = ldx ? s_lo[NT + tid - 1] : A.a[5 * n + r0 - P - 1];
-            if (inx1) b5 = ldx ? s_lo[5 * NT + tid - 1] : A.a[5 * n + r1 - P - 1];
-            if (iny0) a6 = ldy ? s_lo[6 * NT + tid - 64] : A.a[6 * n + r0 - P - nx];          // row below the pair: upper row of wave - 1
-            if (live1) b6 = s_lo[2 * NT + tid];                                                // the pair's own lower row
-            if (inx0 && iny0) a7 = (ldx && ldy) ? s_lo[7 * NT + tid - 65] : A.a[7 * n + r0 - P - nx - 1];
-            if (inx1) b7 = ldx ? s_lo[3 * NT + tid - 1] : A.a[7 * n + r1 - P - nx - 1];
-        }
-        const double a1 = inx0 ? t1a : 0.0, a2 = iny0 ? t2a : 0.0, a3 = (inx0 && iny0) ? t3a : 0.0;
-        const double b1 = inx1 ? t1b : 0.0, b2 = live1 ? u0[2] : 0.0, b3 = inx1 ? t3b : 0.0;
-        const int sl0 = ((z - 1) % 3 + 3) % 3;
-        const double *xm = s_x + sl0 * SLICE + centre;
-        const double *xc = s_x + ((sl0 + 1) % 3) * SLICE + centre;
-        const double *xp = s_x + ((sl0 + 2) % 3) * SLICE + centre;
-        const double xa = xc[0], xb = xc[VM_HX];
-        double acc0 = a7 * xm[-VM_HX - 1];
-        acc0 = fma(a6, xm[-VM_HX], acc0);
-        acc0 = fma(a5, xm[-1], acc0);
-        acc0 = fma(a4, xm[0], acc0);
-        acc0 = fma(a3, xc[-VM_HX - 1], acc0);
-        acc0 = fma(a2, xc[-VM_HX], acc0);
-        acc0 = fma(a1, xc[-1], acc0);
-        acc0 = fma(u0[0], xa, acc0);
-        acc0 = fma(u0[1], xc[1], acc0);
-        acc0 = fma(u0[2], xc[VM_HX], acc0);
-        acc0 = fma(u0[3], xc[VM_HX + 1], acc0);
-        acc0 = fma(u0[4], xp[0], acc0);
-        acc0 = fma(u0[5], xp[1], acc0);
-        acc0 = fma(u0[6], xp[VM_HX], acc0);
-        acc0 = fma(u0[7], xp[VM_HX + 1], acc0);
-        double acc1 = b7 * xm[-1];
-        acc1 = fma(b6, xm[0], acc1);
-        acc1 = fma(b5, xm[VM_HX - 1], acc1);
-        acc1 = fma(b4, xm[VM_HX], acc1);
-        acc1 = fma(b3, xc[-1], acc1);
-        acc1 = fma(b2, xc[0], acc1);
-        acc1 = fma(b1, xc[VM_HX - 1], acc1);
-        acc1 = fma(u1[0], xb, acc1);
-        acc1 = fma(u1[1], xc[VM_HX + 1], acc1);
-        acc1 = fma(u1[2], xc[2 * VM_HX], acc1);
-        acc1 = fma(u1[3], xc[2 * VM_HX + 1], acc1);
-        acc1 = fma(u1[4], xp[VM_HX], acc1);
-        acc1 = fma(u1[5], xp[VM_HX + 1], acc1);
-        acc1 = fma(u1[6], xp[2 * VM_HX], acc1);
-        acc1 = fma(u1[7], xp[2 * VM_HX + 1], acc1);
-        double o0, o1;
-        if (EPI == 1) { o0 = w0 != 0.0 ? e0 - acc0 : 0.0; o1 = w1 != 0.0 ? e1 - acc1 : 0.0; }
-        else { o0 = w0 != 0.0 ? fma(w0, e0 - acc0, xa) : 0.0; o1 = w1 != 0.0 ? fma(w1, e1 - acc1, xb) : 0.0; }
-        if (live0) A.out[r0] = o0;
-        if (live1) A.out[r1] = o1;
-        if (DOT && live0) dot = fma(e0, o0, dot);
-        if (DOT && live1) dot = fma(e1, o1, dot);
-        __syncthreads();
-        put(z + 2, vn);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { s_lo[s * NT + tid] = u0[4 + s]; s_lo[(4 + s) * NT + tid] = u1[4 + s]; }
-        __syncthreads();
-    }
-    if (DOT) {
-        const double sum = wave_sum(dot);
-        __syncthreads();
-        if (lane == 0) s_red[wv] = sum;
-        __syncthreads();
-        if (tid == 0) A.partials[b] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-    }
-}
+__global__ __launch_bounds__(256) void k_vmg_march(DiaArgs A) { dia_march2<DOT, true, EPI>(A); }
 
 static void vmg_free(Vmg *&M) {
     if (!M) return;
@@ -681,12 +527,17 @@ int vmg_vcycle(Ctx *c, Vmg *M, const double *r, bool dot, int *nparts, double *z
     const dim3 blk(256, 1, 1);
     const int *flags = c->flags;
     int np_dot = M->np0;
+    // The march orders its LDS traffic only (lds_barrier) and does not wait for its stores of `out`: no launch below passes an `out`
+    // that aliases in, b, w or the slot arrays.  Down: in = r / L.b, out = L.t.  Up: in = L.t, b = r / L.b, out = L.x or z_out, the
+    // caller's own vector (pgd_pcg_solve: its p, never r; cmg_apply: r is a component's level-0 L.b, z_out is null, out = L.x).
+    // L.a, L.w, L.b, L.x, L.t are separate allocations of the level.
     auto march = [&](const VLevel &L, int epi, const double *in, const double *b, double *out, bool d) -> bool {
         int zc = 0, wgs = 0;
         if (!vmg_marches(c, L, &zc, &wgs)) return false;
-        VmArgs A;
-        A.a = L.a; A.w = L.w; A.in = in; A.b = b; A.out = out; A.partials = c->partials; A.flags = flags; A.n = L.stride;
-        A.nx = L.g.nx; A.ny = L.g.ny; A.nz = L.g.nz; A.zchunk = zc; A.tiles_x = (L.g.nx + 63) / 64; A.tiles_y = (L.g.ny + 7) / 8; A.unit = L.unit;
+        DiaArgs A{};
+        A.uvals = L.a; A.ew = L.w; A.x = in; A.eb = b; A.y = out; A.partials = c->partials; A.flags = flags; A.n = L.stride;
+        A.nx = L.g.nx; A.ny = L.g.ny; A.nz = L.g.nz; A.z0 = 0; A.z1 = L.g.nz; A.zchunk = zc;
+        A.tiles_x = (L.g.nx + 63) / 64; A.tiles_y = (L.g.ny + 7) / 8; A.unit_diag = L.unit;
         if (epi == 1) k_vmg_march<1, false><<<wgs, 256, 0, c->stream>>>(A);
         else if (d) k_vmg_march<2, true><<<wgs, 256, 0, c->stream>>>(A);
         else k_vmg_march<2, false><<<wgs, 256, 0, c->stream>>>(A);

@@ -126,10 +126,13 @@ def test_solve_equals_the_restatement(ctx, box, family):
         ctx.mesh_free(h)
 
 
-def test_march_and_plain_kernels_agree(ctx):
-    """A 72 x 70 x 24 lattice: level 0 runs its two passes in k_vmg_march (counted), with PGD_TUNE_MG_MARCH_MIN = 0 in the plain
-    kernels: the same cycle up to the order of the partial sums of r . z."""
-    shape = (72, 70, 24)
+@pytest.mark.parametrize("shape", [(72, 70, 24), (65, 71, 9)], ids=lambda s: "%dx%dx%d" % s)
+def test_march_and_plain_kernels_agree(ctx, shape):
+    """Level 0 runs its two passes in k_vmg_march (counted), with PGD_TUNE_MG_MARCH_MIN = 0 in the plain kernels: the same cycle up
+    to the order of the partial sums of r . z.  65 x 71 x 9 (41 535 nodes, three levels) is the smallest lattice that adds what
+    72 x 70 x 24 does not reach: an odd ny (the last thread pair of a patch has a live lower and a dead upper row, in both epilogues
+    and in the dot), a second x tile one node wide, and marches of three planes (every march pays the prologue and, from the second
+    on, the hand-over of the plane below)."""
     coords, cells = V.box(shape, steps=(1.0 / 64,) * 3)
     n = coords.shape[0]
     h = ctx.mesh_upload(coords, cells.astype(np.int32))
@@ -152,7 +155,7 @@ def test_march_and_plain_kernels_agree(ctx):
             assert rel <= 1e-10
             ctx.vec_free(xv)
             ctx.atom_free(op)
-        print("72x70x24: %d iterations with the march (%d passes), %d with the plain kernels" % (out[64][0], out[64][2], out[0][0]))
+        print("%dx%dx%d: %d iterations with the march (%d passes), %d with the plain kernels" % (*shape, out[64][0], out[64][2], out[0][0]))
         assert out[64][2] > 0 and out[0][2] == 0                   # (launches issued: a replayed chunk of iterations counts once)
         assert abs(out[64][0] - out[0][0]) <= 1
         assert np.linalg.norm(out[64][1] - out[0][1]) <= 1e-8 * np.linalg.norm(out[0][1])

@@ -211,6 +211,22 @@ int pgd_bilinear_many(pgd_handle ctx, pgd_handle A, pgd_handle x, const pgd_hand
  * copy is dropped.                                                                                         */
 int pgd_pcg_solve(pgd_handle ctx, pgd_handle op, pgd_handle b, pgd_handle x, double rtol,
                   double atol, int maxit, int *iters, double *relres);
+/* Which recurrence and which preconditioner the last pgd_pcg_solve of this context ran (-1, -1 before the first one).  Both
+ * are decided once per solve, from the operator and the PGD_TUNE_PCG_* knobs; every form computes the same iteration.   */
+typedef enum {
+    PGD_PCG_FORM_PRECOND = 0,               /* textbook recurrence around a multigrid cycle (see pgd_pcg_precond) */
+    PGD_PCG_FORM_TEXTBOOK = 1,              /* unscaled Jacobi-PCG: no symmetric storage, or PGD_TUNE_PCG_SCALED = 0 */
+    PGD_PCG_FORM_TWO_LAUNCH = 2,            /* single-sync, the scalar step inside the update (PGD_TUNE_PCG_SMALL_SINGLE_SYNC) */
+    PGD_PCG_FORM_FOLDED = 3,                /* two reductions, folded into their consumers (PGD_TUNE_PCG_FOLD_REDUCE) */
+    PGD_PCG_FORM_SINGLE_SYNC = 4,           /* one reduction + one vector update (PGD_TUNE_PCG_SINGLE_SYNC) */
+    PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE = 5, /* ... whose update forms A p again (PGD_TUNE_PCG_RECOMPUTE_Q) */
+    PGD_PCG_FORM_DEFERRED_X = 6,            /* two reductions, x += alpha p in the p kernel (PGD_TUNE_PCG_DEFER_X) */
+    PGD_PCG_FORM_PLAIN = 7                  /* two reductions, scaled */
+} pgd_pcg_form;
+typedef enum {
+    PGD_PCG_PRECOND_JACOBI = 0, PGD_PCG_PRECOND_MG = 1, PGD_PCG_PRECOND_VMG = 2, PGD_PCG_PRECOND_CMG = 3
+} pgd_pcg_precond;
+int pgd_pcg_last_form(pgd_handle ctx, int *form, int *precond);
 /* Banded LU with partial pivoting in one workgroup, for the small and possibly
  * non-symmetric 1-D systems (time: u'v) and the FD-mode solve (solver.py:939).  */
 int pgd_band_solve(pgd_handle ctx, pgd_handle op, pgd_handle b, pgd_handle x);

@@ -83,6 +83,7 @@ SIGNATURES = {
     "pgd_vec_multidot": (C.c_int, [H, H, PH, C.c_int, I64, I64, PD]),
     "pgd_vec_multidot_pair": (C.c_int, [H, H, H, PH, C.c_int, I64, I64, PD]),
     "pgd_pcg_solve": (C.c_int, [H, H, H, H, F64, F64, C.c_int, C.POINTER(C.c_int), PD]),
+    "pgd_pcg_last_form": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pgd_band_solve": (C.c_int, [H, H, H, H]),
     "pgd_slots_ptr": (C.c_int, [H, C.POINTER(VP)]),
     "pgd_slots_download": (C.c_int, [H, PD, C.c_int, C.c_int]),
@@ -502,6 +503,15 @@ class Context:
         self._ck(self.lib.pgd_pcg_solve(self.h, op, b, x, float(rtol), float(atol), int(maxit),
                                         C.byref(it), C.byref(rel)))
         return it.value, rel.value
+
+    PCG_FORMS = ("PRECOND", "TEXTBOOK", "TWO_LAUNCH", "FOLDED", "SINGLE_SYNC", "SINGLE_SYNC_RECOMPUTE", "DEFERRED_X", "PLAIN")
+    PCG_PRECONDS = ("JACOBI", "MG", "VMG", "CMG")
+
+    def pcg_last_form(self):
+        """(form, preconditioner) of the last pcg_solve by name (pgd_pcg_form / pgd_pcg_precond), (None, None) before the first."""
+        f, p = C.c_int(), C.c_int()
+        self._ck(self.lib.pgd_pcg_last_form(self.h, C.byref(f), C.byref(p)))
+        return (self.PCG_FORMS[f.value] if f.value >= 0 else None, self.PCG_PRECONDS[p.value] if p.value >= 0 else None)
 
     # ---- the V-cycle on a z-slab of a row-sharded lattice (levels >= 1 whole on every rank)
     def mg_slab_setup(self, op, nz_global, z_first, own0, own1):

@@ -995,7 +995,7 @@ int pgd_pcg_solve_sharded(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle
     auto dbg_now = [&]() -> double {
         if (!dbg_t) return 0.0;
         (void)hipStreamSynchronize(c->stream);
-        return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+        return host_now();
     };
     const double dbg_t0 = dbg_now();
     static_assert(V == B - 1, "the vote rides in front of the recurrence's slots");
@@ -1054,7 +1054,7 @@ int pgd_pcg_solve_sharded(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle
 
     // ---- from here on: the collective discipline described above
     Shard S{c};
-    struct ProfIterGuard { Ctx *c; ~ProfIterGuard() { c->prof_iter = -1; } } prof_iter_guard{c};
+    ProfIterGuard prof_iter_guard{c};
     c->prof_pend.clear();
     auto fault_at = [&](int stage) {                    // tests (PGD_TUNE_FAULT_STAGE)
         if (c->fault_stage == stage && !S.poisoned()) {

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <map>
@@ -358,7 +359,12 @@ struct Ctx {
     int *flags_host = nullptr;                       // pinned: two snapshots of the device flags (the PCG loops look at one chunk's
     hipEvent_t flag_ev[2] = {nullptr, nullptr};      //   flags while the next chunk is already queued: pcg_flag_snapshots)
     int pcg_pipeline = 1;                            // 1: the next 16-iteration chunk is queued before the host looks at the flags of the last
+    int pcg_last_form = -1, pcg_last_precond = -1;   // what the last pgd_pcg_solve ran (pgd_pcg_form / pgd_pcg_precond; pgd_pcg_last_form)
 };
+
+// the PCG loops name the iteration whose launches they queue (launch timing); on every way out of the solve it is "none" again
+struct ProfIterGuard { Ctx *c; ~ProfIterGuard() { c->prof_iter = -1; } };
+inline double host_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 enum { KC_CSR = 0, KC_CSR_DICT = 1, KC_SYM_ROWS = 2, KC_DIA_ROWS = 3, KC_DIA_MARCH = 4, KC_MULTI = 5, KC_DIAC_MARCH = 6, KC_STENCIL_MARCH = 7 };
 

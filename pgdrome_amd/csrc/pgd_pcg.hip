@@ -9,8 +9,6 @@
 // bank, and a `done` flag turns every later launch into a no-op, so the host
 // only looks at the flag every CHECK_EVERY iterations.  All reductions are
 // wavefront-shuffle -> LDS -> fixed-order final pass: bitwise reproducible.
-#include <chrono>
-
 #include "pgd_internal.h"
 
 #include <cmath>
@@ -1287,15 +1285,21 @@ int pcg1_aux(Ctx *c, const double *s, const double *r, int64_t lo, int64_t hi, i
     return reduce_partials(c, c->partials, g, 1, slot, -1, 0, 0);
 }
 
+// more than 8192 partial sums of a product (pairs: p.q, q.q): a first reduction stage into work[5], one pair per 1024 of them
+static int stage_product_partials(Ctx *c, const double **prod, int *nprod) {
+    *prod = c->partials;
+    if (*nprod <= 8192) return PGD_OK;
+    const int nb = (*nprod + 1023) / 1024;
+    PGD_TRY(ensure_work(c, 5, (int64_t)nb * 2 > 4096 ? (int64_t)nb * 2 : 4096));
+    PGD_TRY(k_reduce_stage1_pub(c, c->partials, *nprod, 2, c->work[5]));
+    *prod = c->work[5];
+    *nprod = nb;
+    return PGD_OK;
+}
+
 int pcg1_sums(Ctx *c, int nprod, int nvec, int base) {
-    const double *prod = c->partials;
-    if (nprod > 8192) {
-        const int nb = (nprod + 1023) / 1024;
-        PGD_TRY(ensure_work(c, 5, (int64_t)nb * 2 > 4096 ? (int64_t)nb * 2 : 4096));
-        PGD_TRY(k_reduce_stage1_pub(c, c->partials, nprod, 2, c->work[5]));
-        prod = c->work[5];
-        nprod = nb;
-    }
+    const double *prod;
+    PGD_TRY(stage_product_partials(c, &prod, &nprod));
     k_pcg1_sums<<<1, 1024, 0, c->stream>>>(prod, nprod, c->work[6], nvec, c->slots, base, c->flags);
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
@@ -1322,39 +1326,60 @@ unsigned int pcg1_update_push_blocks(int g, int64_t lo, int64_t hi, int64_t lo_e
     return count;
 }
 
+// launch timing on: every third vector update of the single-sync recurrence runs between HIP events (one in three: both halves of
+// the x-update pairs get sampled); the caller prices the launch in bytes when it closes the bracket
+static int update_timing_begin(Ctx *c, bool *timed) {
+    *timed = c->prof && ((c->prof_upd_seen++ % 3) == 0);
+    if (!*timed) return PGD_OK;
+    if (c->ev_used + 2 > c->ev.size()) prof_flush(c);
+    c->ev_rec[c->ev_used / 2] = Ctx::ProfRec{1, c->prof_iter, 0.0, 0.0, 0.0};
+    PGD_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
+    return PGD_OK;
+}
+
+static int update_timing_end(Ctx *c, bool timed, double bytes) {
+    if (!timed) return PGD_OK;
+    PGD_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
+    c->ev_rec[c->ev_used / 2].bytes = bytes;
+    c->ev_used += 2;
+    return PGD_OK;
+}
+
+// k_pcg1_update over [lo, hi) with its template flags resolved: NT from the stream hints; fold_par >= 0: the scalar step in every
+// workgroup (slots from `base` and the parity), else alpha and beta from slot_alpha / slot_beta; push: the direct halo rides along
+template <bool FOLD, bool PUSH>
+static void launch_pcg1_update_t(Ctx *c, int g, double *x, double *r, double *p, const double *q, const double *sc, int64_t lo, int64_t hi,
+                                 int slot_alpha, int slot_beta, double *pairs, int lag, int base, int fold_par, const PushArgs &P) {
+    if (c->pcg_stream_hints) k_pcg1_update<true, FOLD, PUSH><<<g, TPB, 0, c->stream>>>(x, r, p, q, sc, lo, hi, c->slots, slot_alpha, slot_beta, pairs, c->flags, lag, base, fold_par, P);
+    else k_pcg1_update<false, FOLD, PUSH><<<g, TPB, 0, c->stream>>>(x, r, p, q, sc, lo, hi, c->slots, slot_alpha, slot_beta, pairs, c->flags, lag, base, fold_par, P);
+}
+
+static void launch_pcg1_update(Ctx *c, int g, double *x, double *r, double *p, const double *q, const double *sc, int64_t lo, int64_t hi,
+                               int slot_alpha, int slot_beta, double *pairs, int lag, int base, int fold_par, const PushArgs *push) {
+    if (push) launch_pcg1_update_t<true, true>(c, g, x, r, p, q, sc, lo, hi, 0, 0, pairs, lag, base, fold_par, *push);
+    else if (fold_par >= 0) launch_pcg1_update_t<true, false>(c, g, x, r, p, q, sc, lo, hi, 0, 0, pairs, lag, base, fold_par, PushArgs());
+    else launch_pcg1_update_t<false, false>(c, g, x, r, p, q, sc, lo, hi, slot_alpha, slot_beta, pairs, lag, 0, 0, PushArgs());
+}
+
 int pcg1_update(Ctx *c, double *x, double *r, double *p, const double *q, const double *sc, int64_t lo, int64_t hi, int base,
                 int *nblocks, int lag, int fold_par, const PushArgs *push) {       // fold_par >= 0: the scalar step in every workgroup (parity of the iteration)
     *nblocks = 0;
     if (hi == lo) return push ? fail(c, PGD_ERR_INVALID, "pcg1_update: a push from an empty slab") : PGD_OK;
     const int g = grid_for((hi - lo + 1) / 2);
+    PushArgs P;
     if (push) {
         // the caller has checked: fold, lo even, (hi - lo), (lo_end - lo), (hi - hi_begin) even
         if (fold_par < 0 || (lo & 1) || ((hi - lo) & 1) || ((push->lo_end - lo) & 1) || ((hi - push->hi_begin) & 1))
             return fail(c, PGD_ERR_INVALID, "pcg1_update: this launch cannot carry the direct halo");
+        P = *push;
+        if (!P.nblocks) P.nblocks = pcg1_update_push_blocks(g, lo, hi, P.lo_end, P.hi_begin);
     }
     PGD_TRY(ensure_work(c, 6, 2 * (int64_t)MAX_VEC_BLOCKS));
-    const bool timed_u = c->prof && ((c->prof_upd_seen++ % 3) == 0);      // launch timing, as in pgd_pcg_solve
-    if (timed_u) {
-        if (c->ev_used + 2 > c->ev.size()) prof_flush(c);
-        c->ev_rec[c->ev_used / 2] = Ctx::ProfRec{1, c->prof_iter, 0.0, 0.0, 0.0};
-        PGD_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
-    }
-    if (push) {
-        PushArgs P = *push;
-        if (!P.nblocks) P.nblocks = pcg1_update_push_blocks(g, lo, hi, P.lo_end, P.hi_begin);
-        if (c->pcg_stream_hints) k_pcg1_update<true, true, true><<<g, TPB, 0, c->stream>>>(x, r, p, q, sc, lo, hi, c->slots, 0, 0, c->work[6], c->flags, lag, base, fold_par, P);
-        else k_pcg1_update<false, true, true><<<g, TPB, 0, c->stream>>>(x, r, p, q, sc, lo, hi, c->slots, 0, 0, c->work[6], c->flags, lag, base, fold_par, P);
-    } else if (fold_par >= 0) {
-        if (c->pcg_stream_hints) k_pcg1_update<true, true><<<g, TPB, 0, c->stream>>>(x, r, p, q, sc, lo, hi, c->slots, 0, 0, c->work[6], c->flags, lag, base, fold_par, PushArgs());
-        else k_pcg1_update<false, true><<<g, TPB, 0, c->stream>>>(x, r, p, q, sc, lo, hi, c->slots, 0, 0, c->work[6], c->flags, lag, base, fold_par, PushArgs());
-    } else if (c->pcg_stream_hints) k_pcg1_update<true, false><<<g, TPB, 0, c->stream>>>(x, r, p, q, sc, lo, hi, c->slots, base + 5, base + 6, c->work[6], c->flags, lag, 0, 0, PushArgs());
-    else k_pcg1_update<false, false><<<g, TPB, 0, c->stream>>>(x, r, p, q, sc, lo, hi, c->slots, base + 5, base + 6, c->work[6], c->flags, lag, 0, 0, PushArgs());
-    if (timed_u) {
-        PGD_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-        // (outside the exact phase - all but the last few dozen iterations - the kernel does not read s; the host cannot see the flag)
-        c->ev_rec[c->ev_used / 2].bytes = ((lag == 1 ? 40.0 : 56.0) + (c->pcg_exact_phase ? 0.0 : 8.0)) * (double)(hi - lo);
-        c->ev_used += 2;
-    }
+    bool timed_u;
+    PGD_TRY(update_timing_begin(c, &timed_u));
+    launch_pcg1_update(c, g, x, r, p, q, sc, lo, hi, base + 5, base + 6, c->work[6], lag, base, fold_par, push ? &P : nullptr);
+    // (outside the exact phase - all but the last few dozen iterations - the kernel does not read s; the host cannot see the flag)
+    PGD_TRY(update_timing_end(c, timed_u, ((lag == 1 ? 40.0 : 56.0) + (c->pcg_exact_phase ? 0.0 : 8.0)) * (double)(hi - lo)));
     PGD_LAUNCH_CHECK(c);
     *nblocks = g;
     return PGD_OK;
@@ -1397,6 +1422,440 @@ static int pcg_xr(Ctx *c, double *x, double *r, const double *p, const double *q
     else k_pcg_xr<false, false><<<g, TPB, 0, c->stream>>>(x, r, p, q, nullptr, nullptr, lo, hi, c->slots, slot_rz, slot_pq, c->partials, c->flags);
     PGD_LAUNCH_CHECK(c);
     return reduce_partials(c, c->partials, g, 2, slot_out, check_mode, slot_out + 1, slot_tol2);
+}
+
+// ---------------------------------------------------------------- pgd_pcg_solve in pieces
+typedef pgd_pcg_form PcgForm;
+typedef pgd_pcg_precond PcgPrecond;
+
+// the forms with one reduction per iteration: their first scalar step takes the first look at the residual, the product of the
+// iteration that notices convergence still runs, and the x update may lag (PGD_TUNE_PCG_LAG_X)
+static bool pcg_single_sync(PcgForm f) {
+    return f == PGD_PCG_FORM_TWO_LAUNCH || f == PGD_PCG_FORM_SINGLE_SYNC || f == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE;
+}
+
+// THE decision, once per solve, after the preconditioner was prepared: which recurrence runs.  The first line that applies wins.
+// (grid: the mesh is a full structured vertex grid; whole: stencil_whole_grid)
+static PcgForm pcg_choose(const Ctx *c, PcgPrecond precond, bool scaled, int64_t n, bool grid, bool whole) {
+    const bool small = n <= ((int64_t)1 << 20);
+    if (precond != PGD_PCG_PRECOND_JACOBI) return PGD_PCG_FORM_PRECOND;
+    if (!scaled) return PGD_PCG_FORM_TEXTBOOK;
+    if (c->pcg_single_sync && c->pcg_small_ss && (small || (grid && n <= c->pcg_small_ss_rows))) return PGD_PCG_FORM_TWO_LAUNCH;
+    if (c->pcg_fold_reduce && small) return PGD_PCG_FORM_FOLDED;
+    if (c->pcg_single_sync && grid) return (c->pcg_recompute_q && whole) ? PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE : PGD_PCG_FORM_SINGLE_SYNC;
+    return c->pcg_defer_x ? PGD_PCG_FORM_DEFERRED_X : PGD_PCG_FORM_PLAIN;
+}
+
+// One solve.  r0 = b - A x0; (r.z, r.r, b.b) land in slots S_INIT ..+2.  r.z / r.r of iteration k live in slots S_PAIR + 2 (k & 1), +1,
+// so iteration 0 finds "the previous r.z" in slot 18 like every even iteration: all chunks of an even number of iterations are
+// identical and can be replayed as one hipGraph.
+struct PcgRun {
+    static constexpr int S_INIT = 18, S_PAIR = 16;
+    Ctx *c; const Mesh *m; Csr *o; const double *b; double *x; int64_t n;
+    double *r, *z, *p, *q, *sc;         // (the scaled recurrence has no z: its buffer holds s = d^-1/2)
+    // second partials buffer for the folded reductions (the x / r update reads the product's partials while writing its own; the
+    // two-launch form alternates between this half and the next)
+    double *part2 = nullptr, *part2b = nullptr;
+    int gvec = 0, g2v = 0;              // (r~.r~, true r.r) pairs the update leaves; workgroups of the single-sync update
+    PcgForm form = PGD_PCG_FORM_TEXTBOOK;
+    PcgPrecond precond = PGD_PCG_PRECOND_JACOBI;
+    bool scaled = false, lag_x = false;
+    bool x_scaled = false;              // x is in scaled coordinates
+    bool virt = false;                  // the scaled operator is held as a derived stencil only: the slot arrays still hold A
+    double st_saved[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // On EVERY exit (a failing launch, graph replay or copy included): the stencil couplings back to those of A where the scaled
+    // operator was a derived stencil; and, unless the finish has done it, x back to D^-1/2 x~ and the slot arrays no longer taken
+    // for A - a later product with this operator must not read the scaled matrix, the caller must not get x in scaled coordinates.
+    ~PcgRun() {
+        if (virt) {
+            for (int s2 = 0; s2 < 8; ++s2) o->st_c[s2] = st_saved[s2];
+            o->st_virtual = false;
+        }
+        if (!x_scaled) return;
+        (void)vec_div_mul(c, x, sc, n, 1);
+        if (!virt) invalidate_slots();
+    }
+    void invalidate_slots() { o->uvals_valid = false; o->uvals_scaled = false; }
+    int out(int k) const { return S_PAIR + 2 * (k & 1); }             // r.z, r.r of iteration k ...
+    int old(int k) const { return S_PAIR + 2 * ((k + 1) & 1); }       // ... and of the one before it
+    int g2() const { return grid_for((n + 1) / 2); }
+};
+
+// ---- preconditioner (PGD_TUNE_PCG_PRECOND).  1: one stencil on a lattice whose eliminated nodes are its hull (pgd_mg.hip), 2: the V-cycle on
+// the diagonal form with per-row coefficients (pgd_vmg.hip: any operator on a lattice, any Dirichlet set) - both for the scaled
+// recurrence; 3: blocked P1 layouts over a box lattice, one such V-cycle per component on the diagonal blocks of D^-1/2 A D^-1/2, read
+// from the CSR values - for the unscaled one.  The cycles work on vectors that vanish on the eliminated rows: x gets their exact
+// solution from the start.  Any other request is Jacobi, and counted.
+static int pcg_precond_prepare(PcgRun &R) {
+    Ctx *c = R.c;
+    const Mesh *m = R.m;
+    const int want = c->pcg_precond;
+    if (want == 1 && R.scaled && mg_prepare(c, m, R.o)) { R.precond = PGD_PCG_PRECOND_MG; c->mg_solves += 1; return mg_fix_start(c, R.o, R.b, R.x, R.n); }
+    if (want == 2 && R.scaled && m->sym_nx > 0 && vmg_prepare(c, c->vmg, m, R.o)) { R.precond = PGD_PCG_PRECOND_VMG; c->vmg_solves += 1; return vmg_fix_start(c, c->vmg, R.sc, R.b, R.x, R.n); }
+    if (want == 3 && !R.scaled && m->ncomp >= 2) {
+        PGD_TRY(ensure_vals(c, m, R.o));
+        if (cmg_prepare(c, m, get_mesh(c, m->base), R.o)) { R.precond = PGD_PCG_PRECOND_CMG; c->cmg_solves += 1; return cmg_fix_start(c, R.b, R.x, R.n); }
+    }
+    if (want == 1) c->mg_fallbacks += 1;
+    if (want == 2) c->vmg_fallbacks += 1;
+    if (want == 3) c->cmg_fallbacks += 1;
+    return PGD_OK;
+}
+
+// z = M r into z_out (nullptr: the cycle's own result vector, pcg_precond_result), partial sums of r.z into c->partials
+static int pcg_precond_apply(PcgRun &R, const double *r, double *z_out, int *np) {
+    switch (R.precond) {
+    case PGD_PCG_PRECOND_MG: return mg_vcycle(R.c, r, true, np, z_out);
+    case PGD_PCG_PRECOND_VMG: return vmg_vcycle(R.c, R.c->vmg, r, true, np, z_out, &R.c->vmg_marches);
+    case PGD_PCG_PRECOND_CMG: return cmg_apply(R.c, r, z_out ? z_out : R.z, R.n, np);
+    case PGD_PCG_PRECOND_JACOBI: break;
+    }
+    return fail(R.c, PGD_ERR_INVALID, "pcg_solve: no cycle to apply");
+}
+static double *pcg_precond_result(PcgRun &R) {
+    return R.precond == PGD_PCG_PRECOND_MG ? mg_result(R.c) : R.precond == PGD_PCG_PRECOND_VMG ? vmg_result(R.c->vmg) : R.z;
+}
+
+// ---- setup
+// Where A itself is ONE stencil + eliminated nodes on the whole grid (dia_classify: every row and slot verified - the
+// Galerkin start has classified A from two vectors on) the scaled operator is known without touching a slot: every free
+// row has the diagonal c0, s_i = (1 / c0)^1/2 there and 1 on the eliminated rows, and k_dia_scale would write
+// c_s (s_i s_j) - one product, the same for every pair of free nodes - and keep the exact zeros.  The couplings of
+// D^-1/2 A D^-1/2 are DERIVED with that very arithmetic (k_stencil_derive), the codes are A's: no scaling pass over the
+// slot arrays (0.40 ms at 256^3), no second classification (0.25 ms), and the slot arrays still hold A afterwards.
+// (PGD_TUNE_PCG_PRECOND = 2 builds its hierarchy from the scaled slot arrays: they are formed for every operator, one stencil or not)
+static int pcg_derive_stencil(PcgRun &R) {
+    Ctx *c = R.c;
+    Csr *o = R.o;
+    if (!(c->pcg_derive_scaled && R.m->sym_nx > 0 && c->pcg_precond != 2)) return PGD_OK;
+    if (o->cls_count <= 0) PGD_TRY(dia_classify(c, R.m, o));
+    if (!(stencil_whole_grid(c, R.m, o) && o->st_ident >= 0 && o->st_c[0] > 0.0)) return PGD_OK;
+    PGD_TRY(ensure_work(c, 5, 4096));
+    StencilTuple in;
+    for (int s2 = 0; s2 < 8; ++s2) in.c[s2] = o->st_c[s2];
+    k_stencil_derive<<<1, 1, 0, c->stream>>>(in, c->spmv_unit_diag, c->work[5] + 16);
+    PGD_LAUNCH_CHECK(c);
+    double out8[8];
+    PGD_HIP(c, hipMemcpyAsync(out8, c->work[5] + 16, sizeof out8, hipMemcpyDeviceToHost, c->stream));
+    PGD_HIP(c, hipStreamSynchronize(c->stream));
+    for (double v : out8) if (!std::isfinite(v)) return PGD_OK;
+    for (int s2 = 0; s2 < 8; ++s2) { R.st_saved[s2] = o->st_c[s2]; o->st_c[s2] = out8[s2]; }
+    o->st_virtual = R.virt = true;
+    return PGD_OK;
+}
+
+static int pcg_setup_scaled(PcgRun &R) {
+    Ctx *c = R.c;
+    const int64_t n = R.n;
+    PGD_TRY(ensure_work(c, 5, 4096));
+    unsigned long long *bits = reinterpret_cast<unsigned long long *>(c->work[5]);
+    PGD_HIP(c, hipMemsetAsync(bits, 0, sizeof(unsigned long long), c->stream));
+    k_scale_in<<<grid_for(n), TPB, 0, c->stream>>>(R.o->dinv, R.sc, R.x, n, bits);
+    k_dmin_slot<<<1, 1, 0, c->stream>>>(bits, c->slots, c->flags);
+    PGD_LAUNCH_CHECK(c);
+    R.x_scaled = true;
+    PGD_TRY(pcg_derive_stencil(R));
+    if (!R.virt) {
+        PGD_TRY(sym_scale(c, R.m, R.o, R.sc));
+        PGD_TRY(dia_classify(c, R.m, R.o));         // uniform grids: a code byte per row instead of its slot values
+    }
+    PGD_TRY(pcg_precond_prepare(R));
+    PGD_TRY(launch_spmv_op(c, R.m, R.o, R.x, R.q, nullptr, 0, n, false, true, nullptr, nullptr));
+    const int g = grid_for(n);
+    PGD_TRY(ensure_partials(c, 4 * (int64_t)MAX_VEC_BLOCKS));
+    k_pcg_init_s<<<g, TPB, 0, c->stream>>>(R.b, R.q, R.sc, R.r, R.p, n, c->partials);
+    PGD_LAUNCH_CHECK(c);
+    return reduce_partials(c, c->partials, g, 3, R.S_INIT, -1, 0, 0);
+}
+
+// no symmetric storage, or the scaled recurrence switched off: the textbook recurrence on the operator's own products
+static int pcg_setup_unscaled(PcgRun &R) {
+    PGD_TRY(pcg_precond_prepare(R));
+    PGD_TRY(launch_spmv_op(R.c, R.m, R.o, R.x, R.q, nullptr, 0, R.n, false, true, nullptr, nullptr));
+    return pcg_init(R.c, R.b, R.q, R.o->dinv, R.r, R.z, R.p, 0, R.n, R.S_INIT);
+}
+
+// after the start: p0 = z0 = M r0 and the first "previous r.z" where a cycle preconditions; the form, and what it needs allocated and
+// seeded before its first iteration
+static int pcg_choose_and_seed(PcgRun &R) {
+    Ctx *c = R.c;
+    const int64_t n = R.n;
+    if (R.precond != PGD_PCG_PRECOND_JACOBI) {
+        int np = 0;
+        PGD_TRY(pcg_precond_apply(R, R.r, R.p, &np));
+        PGD_TRY(reduce_partials(c, c->partials, np, 1, R.S_INIT, -1, 0, 0));
+    }
+    PGD_TRY(ensure_work(c, 6, 4 * (int64_t)MAX_VEC_BLOCKS));
+    c->pcg_last_precond = R.precond;
+    c->pcg_last_form = R.form = pcg_choose(c, R.precond, R.scaled, n, R.m->sym_nx > 0, stencil_whole_grid(c, R.m, R.o));
+    R.lag_x = c->pcg_lag_x && pcg_single_sync(R.form);
+    // (two-launch form above 2^20 rows: 512 workgroups in the update, every one of which sums all partial sums)
+    R.g2v = grid_for((n + 1) / 2, TPB, (n > ((int64_t)1 << 20) && n <= c->pcg_small_ss_rows && c->pcg_small_ss) ? 512 : MAX_VEC_BLOCKS);
+    R.gvec = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE ? stencil_update_blocks(c, R.m) : R.g2v;
+    if (2 * (int64_t)R.gvec > 4 * (int64_t)MAX_VEC_BLOCKS) PGD_TRY(ensure_work(c, 6, 2 * (int64_t)R.gvec));
+    R.part2 = c->work[6];
+    R.part2b = R.part2 + 2 * (int64_t)MAX_VEC_BLOCKS;
+    if (!pcg_single_sync(R.form)) return PGD_OK;
+    // the first look at the residual happens in the first k_pcg1_scalars: hand it the initial residual's sums
+    // (two-launch form: iteration k reads the pairs of parity (k - 1) & 1, so the seed goes to the second half)
+    const bool two = R.form == PGD_PCG_FORM_TWO_LAUNCH;
+    k_pcg1_seed<<<8, TPB, 0, c->stream>>>(two ? R.part2b : R.part2, R.gvec, c->slots, R.S_INIT, R.S_INIT + 1);
+    if (two) PGD_HIP(c, hipMemsetAsync(c->slots + S1F_ALPHA, 0, 6 * sizeof(double), c->stream));     // alpha, beta, exact-phase bit x 2 parities
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+// ---- one iteration per form (k: its index in the solve).  Two-reduction forms: q = A p with the partial sums of p.q (reduce: p.q into
+// S_PQ), an update whose final reduction counts the iteration and tests (true r.r in the exact phase), the new direction from z
+static int pcg_product(PcgRun &R, int *nparts, bool reduce = true) {
+    PGD_TRY(launch_spmv_op(R.c, R.m, R.o, R.p, R.q, R.p, 0, R.n, true, true, R.c->flags, nparts));
+    return reduce ? reduce_partials(R.c, R.c->partials, *nparts, 1, S_PQ, 0, 0, 0) : PGD_OK;
+}
+static int pcg_update_scaled(PcgRun &R, int k) {
+    k_pcg_xr_s<<<R.g2(), TPB, 0, R.c->stream>>>(R.x, R.r, R.p, R.q, R.sc, R.n, R.c->slots, R.old(k), S_PQ, R.c->partials, R.c->flags);
+    PGD_LAUNCH_CHECK(R.c);
+    return reduce_partials(R.c, R.c->partials, R.g2(), 2, R.out(k), 2, R.out(k) + 1, S_TOL2);
+}
+static int pcg_update_unscaled(PcgRun &R, int k, double *z) {      // (z == nullptr: no z = D^-1 r, the caller's cycle writes z)
+    return pcg_xr(R.c, R.x, R.r, R.p, R.q, z ? R.o->dinv : nullptr, z, 0, R.n, R.old(k), S_PQ, R.out(k), 1, S_TOL2);
+}
+static void pcg_direction(PcgRun &R, int k, const double *z) {
+    k_pcg_p<true><<<R.g2(), TPB, 0, R.c->stream>>>(R.p, z, 0, R.n, R.c->slots, R.out(k), R.old(k), R.c->flags);
+}
+
+static int pcg_iter_textbook(PcgRun &R, int k) {
+    int nparts = 0;
+    PGD_TRY(pcg_product(R, &nparts));
+    PGD_TRY(pcg_update_unscaled(R, k, R.z));
+    pcg_direction(R, k, R.z);
+    return PGD_OK;
+}
+
+static int pcg_iter_plain(PcgRun &R, int k, int nparts = -1) {      // (nparts >= 0: the product has run and left that many partial sums)
+    if (nparts < 0) PGD_TRY(pcg_product(R, &nparts));
+    else PGD_TRY(reduce_partials(R.c, R.c->partials, nparts, 1, S_PQ, 0, 0, 0));
+    PGD_TRY(pcg_update_scaled(R, k));
+    pcg_direction(R, k, R.r);
+    return PGD_OK;
+}
+
+// textbook PCG with z = M r from a cycle in place of z = D^-1 r (MG / VMG: the scaled recurrence, CMG: the unscaled one); the stop test
+// stays the one of the Jacobi form, the cycle's r.z goes over the r~.r~ the test has used
+static int pcg_iter_precond(PcgRun &R, int k) {
+    int nparts = 0, np = 0;
+    PGD_TRY(pcg_product(R, &nparts));
+    PGD_TRY(R.precond == PGD_PCG_PRECOND_CMG ? pcg_update_unscaled(R, k, nullptr) : pcg_update_scaled(R, k));
+    PGD_TRY(pcg_precond_apply(R, R.r, nullptr, &np));
+    PGD_TRY(reduce_partials(R.c, R.c->partials, np, 1, R.out(k), -1, 0, 0));
+    pcg_direction(R, k, pcg_precond_result(R));
+    PGD_LAUNCH_CHECK(R.c);
+    return PGD_OK;
+}
+
+// x += alpha p rides in the p kernel (8 vector passes per iteration instead of 9)
+static int pcg_iter_deferred_x(PcgRun &R, int k) {
+    Ctx *c = R.c;
+    int nparts = 0;
+    PGD_TRY(pcg_product(R, &nparts));
+    k_pcg_r_s<<<R.g2(), TPB, 0, c->stream>>>(R.r, R.q, R.sc, R.n, c->slots, R.old(k), S_PQ, c->partials, c->flags);
+    PGD_LAUNCH_CHECK(c);
+    PGD_TRY(reduce_partials(c, c->partials, R.g2(), 2, R.out(k), 2, R.out(k) + 1, S_TOL2));
+    k_pcg_px_s<<<R.g2(), TPB, 0, c->stream>>>(R.x, R.p, R.r, R.n, c->slots, R.out(k), R.old(k), S_PQ, c->flags);
+    return PGD_OK;
+}
+
+// both final reduction passes inside their consumers (pays only where the launches, not the bytes, set the pace: 256^2 rows +22 %,
+// 128^3 +-0, 256^3 -2 %); a product that leaves no or more than 8192 partial sums: the plain iteration
+static int pcg_iter_folded(PcgRun &R, int k) {
+    Ctx *c = R.c;
+    int nparts = 0;
+    PGD_TRY(pcg_product(R, &nparts, false));
+    if (nparts <= 0 || nparts > 8192) return pcg_iter_plain(R, k, nparts);
+    k_pcg_xr_s2<<<R.g2(), TPB, 0, c->stream>>>(R.x, R.r, R.p, R.q, R.sc, R.n, c->slots, R.old(k), c->partials, nparts, R.part2, c->flags);
+    k_pcg_p_s2<<<R.g2(), TPB, 0, c->stream>>>(R.p, R.r, R.n, R.part2, R.g2(), c->slots, R.out(k), R.old(k), S_TOL2, c->flags);
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+// Single-sync forms: the product leaves p.q and q.q (store = false: q itself is not written), the scalar step is a launch of its own
+// unless the update takes it, the update runs inside the timing bracket.  Its x part lags behind by one iteration in every other one
+// (chunks start at even iteration indices): 5 or 7 vector passes = 40 or 56 B per row (a lag = 1 launch that meets beta < 0.01 moves 56)
+struct Pcg1Iter { const double *prod; int nparts, lag; bool timed; };
+static int pcg1_begin(PcgRun &R, int k, const double *p_cur, bool store, bool scalars, Pcg1Iter *I) {
+    Ctx *c = R.c;
+    I->lag = R.lag_x ? 1 + (k & 1) : 0;
+    c->spmv_qq = 1;
+    const int rc = launch_spmv_op(c, R.m, R.o, p_cur, R.q, p_cur, 0, R.n, true, store, c->flags, &I->nparts);
+    c->spmv_qq = 0;
+    PGD_TRY(rc);
+    PGD_TRY(stage_product_partials(c, &I->prod, &I->nparts));
+    if (scalars) k_pcg1_scalars<<<1, 1024, 0, c->stream>>>(I->prod, I->nparts, R.part2, R.gvec, c->slots, c->flags);
+    return update_timing_begin(c, &I->timed);
+}
+static int pcg1_end(PcgRun &R, const Pcg1Iter &I, double bytes_per_row_less = 0.0) {
+    PGD_TRY(update_timing_end(R.c, I.timed, ((I.lag == 1 ? 40.0 : 56.0) - bytes_per_row_less) * (double)R.n));
+    PGD_LAUNCH_CHECK(R.c);
+    return PGD_OK;
+}
+
+// two launches: the update of iteration k sums the pairs of parity (k - 1) & 1 itself and takes the scalar step in every workgroup
+static int pcg_iter_two_launch(PcgRun &R, int k) {
+    Pcg1Iter I;
+    const int par = k & 1;
+    PGD_TRY(pcg1_begin(R, k, R.p, true, false, &I));
+    k_pcg1_step<<<R.g2v, TPB, 0, R.c->stream>>>(R.x, R.r, R.p, R.q, R.sc, R.n, I.prod, I.nparts, par ? R.part2 : R.part2b, R.g2v, par ? R.part2b : R.part2,
+                                                 R.c->slots, R.c->flags, par, I.lag);
+    return pcg1_end(R, I);
+}
+
+static int pcg_iter_single_sync(PcgRun &R, int k) {
+    Pcg1Iter I;
+    PGD_TRY(pcg1_begin(R, k, R.p, true, true, &I));
+    launch_pcg1_update(R.c, R.g2v, R.x, R.r, R.p, R.q, R.sc, 0, R.n, S1_ALPHA, S1_BETA, R.part2, I.lag, 0, -1, nullptr);
+    return pcg1_end(R, I);
+}
+
+// One-stencil operators (PGD_TUNE_PCG_RECOMPUTE_Q): q = A p is never stored.  The product keeps only its dots, the update marches over p,
+// forms q in registers (4 or 6 vector passes) and writes the new direction to the OTHER of the two buffers p and q (neighbouring
+// workgroups still stage the old one; q is free once the initial residual is formed): the direction of iteration k lives in the
+// buffer of parity k & 1, chunks start at even iterations, so a captured chunk replays unchanged.
+static int pcg_iter_single_sync_recompute(PcgRun &R, int k) {
+    Pcg1Iter I;
+    double *p_cur = (k & 1) ? R.q : R.p, *p_next = (k & 1) ? R.p : R.q;
+    PGD_TRY(pcg1_begin(R, k, p_cur, false, true, &I));
+    PGD_TRY(launch_stencil_update(R.c, R.m, R.o, p_cur, p_next, R.x, R.r, R.sc, R.part2, I.lag));
+    return pcg1_end(R, I, 8.0);
+}
+
+static int pcg_enqueue(PcgRun &R, int start, int count) {
+    for (int k = start; k < start + count; ++k) {
+        R.c->prof_iter = k;                    // launch timing: which iteration a sample belongs to (prof_commit)
+        switch (R.form) {
+        case PGD_PCG_FORM_PRECOND: PGD_TRY(pcg_iter_precond(R, k)); break;
+        case PGD_PCG_FORM_TEXTBOOK: PGD_TRY(pcg_iter_textbook(R, k)); break;
+        case PGD_PCG_FORM_TWO_LAUNCH: PGD_TRY(pcg_iter_two_launch(R, k)); break;
+        case PGD_PCG_FORM_FOLDED: PGD_TRY(pcg_iter_folded(R, k)); break;
+        case PGD_PCG_FORM_SINGLE_SYNC: PGD_TRY(pcg_iter_single_sync(R, k)); break;
+        case PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE: PGD_TRY(pcg_iter_single_sync_recompute(R, k)); break;
+        case PGD_PCG_FORM_DEFERRED_X: PGD_TRY(pcg_iter_deferred_x(R, k)); break;
+        case PGD_PCG_FORM_PLAIN: PGD_TRY(pcg_iter_plain(R, k)); break;
+        }
+    }
+    return PGD_OK;
+}
+
+// ---- the loop: chunks of CE iterations until the done flag is up or maxit are queued (f: the flags the host saw last, enq: iterations
+// queued; dbg: host times before / after the capture and after the loop, and whether there is a graph).  A chunk (80 dependent launches
+// at 16 iterations) is replayed as a hipGraph: small systems are launch-bound, and at 256^3 the replay still saves ~2 % (549 vs 560 us
+// per iteration).  With launch timing on, every PROF_EAGER_EVERY-th chunk is issued eagerly so that its products carry their HIP
+// events; the capture itself records none.
+static int pcg_drive(PcgRun &R, int CE, int maxit, int f[4], int &enq, double *dbg) {
+    Ctx *c = R.c;
+    hipGraphExec_t gexec = nullptr;
+    if (dbg) { (void)hipStreamSynchronize(c->stream); dbg[0] = host_now(); }
+    if (maxit >= CE) {
+        // everything a chunk allocates lazily must exist before the capture starts
+        PGD_TRY(ensure_partials(c, std::max<int64_t>(4 * (int64_t)MAX_VEC_BLOCKS, 2 * ((R.n + 63) / 64) + 64)));
+        PGD_TRY(ensure_work(c, 5, 4096));
+        const bool prof_saved = c->prof;
+        c->prof = false;
+        hipGraph_t graph = nullptr;
+        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            const int rc = pcg_enqueue(R, 0, CE);
+            const hipError_t e = hipStreamEndCapture(c->stream, &graph);
+            if (rc != PGD_OK || e != hipSuccess || !graph ||
+                hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess)
+                gexec = nullptr;
+            if (graph) (void)hipGraphDestroy(graph);
+            (void)hipGetLastError();
+        }
+        c->prof = prof_saved;
+    }
+    if (dbg) { dbg[1] = host_now(); dbg[3] = gexec ? 1.0 : 0.0; }
+    int rc_loop = PGD_OK;
+    auto issue = [&](int chunk) -> int {
+        const bool eager_for_timing = c->prof && ((enq / CE) % PROF_EAGER_EVERY == 0);
+        if (gexec && chunk == CE && !eager_for_timing) {
+            if (hipGraphLaunch(gexec, c->stream) != hipSuccess) return fail(c, PGD_ERR_HIP, "pcg_solve: hipGraphLaunch failed");
+            return PGD_OK;
+        }
+        return pcg_enqueue(R, enq, chunk);
+    };
+    if (c->pcg_pipeline && pcg_flag_snapshots(c) == PGD_OK) {
+        // PIPELINED: the next chunk is queued BEFORE the host waits for the flags of the one before it - a snapshot of the flags
+        // into pinned memory + an event behind every chunk - so the GPU never idles through the host's round trip (copy, wake-up,
+        // graph launch: 50 - 130 us per 16 iterations, i.e. 2 % of a chunk at 256^3 and a third of one on a 256^2 grid).  A chunk
+        // queued behind the iteration that converged is 48 no-op launches (every kernel returns on the done flag), once per solve.
+        auto snap = [&](int slot) -> hipError_t {
+            hipError_t e = hipMemcpyAsync(c->flags_host + 4 * slot, c->flags, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipEventRecord(c->flag_ev[slot], c->stream);
+            return e;
+        };
+        int cur = 0;
+        hipError_t e = snap(0);                           // the flags after the initial residual
+        while (e == hipSuccess) {
+            const int chunk = (maxit - enq < CE) ? maxit - enq : CE;
+            if (chunk > 0) {
+                if ((rc_loop = issue(chunk)) != PGD_OK) break;
+                enq += chunk;
+                if ((e = snap(cur ^ 1)) != hipSuccess) break;
+            }
+            if ((e = hipEventSynchronize(c->flag_ev[cur])) != hipSuccess) break;
+            for (int i = 0; i < 4; ++i) f[i] = c->flags_host[4 * cur + i];
+            if (f[0] || chunk <= 0) break;                // converged (what is queued behind it does nothing), or nothing more to queue
+            cur ^= 1;
+        }
+        if (e != hipSuccess && rc_loop == PGD_OK) rc_loop = fail(c, PGD_ERR_HIP, "pcg_solve: %s", hipGetErrorString(e));
+    } else {
+        while (true) {
+            hipError_t e = hipMemcpyAsync(f, c->flags, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) { rc_loop = fail(c, PGD_ERR_HIP, "pcg_solve: %s", hipGetErrorString(e)); break; }
+            if (f[0] || enq >= maxit) break;
+            const int chunk = (maxit - enq < CE) ? maxit - enq : CE;
+            if ((rc_loop = issue(chunk)) != PGD_OK) break;
+            enq += chunk;
+        }
+    }
+    if (dbg) { (void)hipStreamSynchronize(c->stream); dbg[2] = host_now(); }
+    if (gexec) (void)hipGraphExecDestroy(gexec);
+    return rc_loop;
+}
+
+// ---- the finish: x out of scaled coordinates with the term a lagged or deferred update left outstanding, the report
+static int pcg_finish(PcgRun &R, const int f[4], int *iters, double *relres) {
+    Ctx *c = R.c;
+    if (R.scaled) {      // x = D^-1/2 x~, and the true r.r of the last iterate for the report
+        const int g = grid_for(R.n);
+        R.x_scaled = false;
+        // converged (or broke down) inside an iteration whose p kernel was a no-op: its x update is still to come
+        const bool pending = R.form == PGD_PCG_FORM_DEFERRED_X && f[0] != 0 && f[1] > 0;
+        // lagged x update: f[1] update kernels ran; if the last one had an even index it may have left its term outstanding
+        const bool lag_pending = R.lag_x && f[1] > 0 && ((f[1] - 1) & 1) == 0;
+        // (alpha and beta of that last update: in the two-launch form they sit in the slots of its parity)
+        const int last_par = f[1] > 0 ? (f[1] - 1) & 1 : 0;
+        const bool two = R.form == PGD_PCG_FORM_TWO_LAUNCH;
+        // (the update that forms q itself: f[1] updates ran, each wrote the direction to the other buffer)
+        const double *p_live = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE && (f[1] & 1) ? R.q : R.p;
+        k_scale_out<<<g, TPB, 0, c->stream>>>(R.x, R.r, R.sc, R.n, c->partials, (pending || lag_pending) ? p_live : nullptr, c->slots,
+                                              R.S_PAIR + 2 * (f[1] & 1), S_PQ, lag_pending ? 1 : 0,
+                                              two ? S1F_ALPHA + last_par : S1_ALPHA, two ? S1F_BETA + last_par : S1_BETA);
+        PGD_LAUNCH_CHECK(c);
+        PGD_TRY(reduce_partials(c, c->partials, g, 1, S_TMP, -1, 0, 0));
+        if (!R.virt) R.invalidate_slots();      // the slot arrays hold the scaled operator: nobody else may take them for A
+    }
+    PGD_LAUNCH_CHECK(c);
+    double s[PGD_NSLOTS];
+    PGD_HIP(c, hipMemcpyAsync(s, c->slots, sizeof s, hipMemcpyDeviceToHost, c->stream));
+    PGD_HIP(c, hipStreamSynchronize(c->stream));
+    if (R.precond == PGD_PCG_PRECOND_VMG) vmg_note_setup(c);
+    if (R.precond == PGD_PCG_PRECOND_CMG) cmg_note_setup(c);
+    if (iters) *iters = f[1];
+    const double rr = R.scaled ? s[S_TMP] : (f[1] > 0) ? s[R.S_PAIR + 2 * ((f[1] - 1) & 1) + 1] : s[R.S_INIT + 1];
+    const double bb = s[R.S_INIT + 2];
+    if (relres) *relres = (bb > 0.0) ? sqrt(rr / bb) : 0.0;
+    if (f[2] != 0) return fail(c, f[2], "pcg_solve: breakdown (NaN residual) after %d iterations", f[1]);
+    return PGD_OK;
 }
 
 }  // namespace pgd
@@ -1523,383 +1982,41 @@ int pgd_pcg_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pgd_handle xh, dou
         return fail(c, PGD_ERR_INVALID, "pcg_solve: invalid handles or size mismatch");
     const int64_t n = m->nv;
     const bool dbg_t = getenv("PGD_DEBUG_PCG") != nullptr;
-    auto dbg_now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double dbg_t0 = dbg_now();
-    double dbg_t1 = 0, dbg_t2 = 0, dbg_t3 = 0;
-    struct ProfIterGuard { Ctx *c; ~ProfIterGuard() { c->prof_iter = -1; } } prof_iter_guard{c};
+    const double dbg_t0 = host_now();
+    ProfIterGuard prof_iter_guard{c};
     c->prof_pend.clear();
     PGD_TRY(csr_diag_inv(c, m, o));
     bool sym = false;
     PGD_TRY(ensure_sym(c, m, o, &sym));       // SPD solve: read every off-diagonal value once per product
     for (int i = 0; i < 4; ++i) PGD_TRY(ensure_work(c, i, n));
-    double *r = c->work[0], *z = c->work[1], *p = c->work[2], *q = c->work[3];
     PGD_HIP(c, hipMemsetAsync(c->flags, 0, 8 * sizeof(int), c->stream));
-    // r0 = b - A x0; (r.z, r.r, b.b) land in slots 18..20.  r.z / r.r of iteration k live in slots
-    // 16 + 2 (k & 1), +1, so iteration 0 finds "the previous r.z" in slot 18 like every even iteration:
-    // all 16-iteration chunks are identical and can be replayed as one hipGraph.
-    constexpr int S_INIT = 18, S_PAIR = 16;
-    const bool scaled = sym && c->pcg_scaled && n >= 2;
-    bool mg_on = false, vmg_on = false;   // (vmg_on: the cycle is the variable-coefficient one; mg_on is up as well)
-    bool cmg_on = false;                  // the component-wise cycle of a blocked P1 operator (unscaled branch; mg_on is up as well)
-    double *sc = z;                     // the scaled recurrence has no z: its buffer holds s = d^-1/2
-    // On EVERY exit after x and the slot arrays were scaled (a failing launch, graph replay or copy included): x back to
-    // D^-1/2 x~ and the slot arrays no longer taken for A - a later product with this operator must not read the scaled
-    // matrix, and the caller must not get x in scaled coordinates.
-    struct ScaleGuard {
-        Ctx *c; Csr *o; double *x; const double *sc; int64_t n; bool active; bool slots_scaled;
-        ~ScaleGuard() {
-            if (!active) return;
-            (void)vec_div_mul(c, x, sc, n, 1);
-            if (!slots_scaled) return;      // (the scaled operator was held as a derived stencil only: the slot arrays still hold A)
-            o->uvals_valid = false;
-            o->uvals_scaled = false;
-        }
-    } guard{c, o, x->d, sc, n, false, true};
-    // ... and the stencil couplings back to those of A where the scaled operator was held as a derived stencil only (declared after
-    // `guard`: destroyed first; the slot arrays were never scaled then)
-    struct VirtGuard {
-        Csr *o; bool active; double saved[8];
-        ~VirtGuard() {
-            if (!active) return;
-            for (int s2 = 0; s2 < 8; ++s2) o->st_c[s2] = saved[s2];
-            o->st_virtual = false;
-        }
-    } virt{o, false, {0, 0, 0, 0, 0, 0, 0, 0}};
-    if (scaled) {
-        PGD_TRY(ensure_work(c, 5, 4096));
-        unsigned long long *bits = reinterpret_cast<unsigned long long *>(c->work[5]);
-        PGD_HIP(c, hipMemsetAsync(bits, 0, sizeof(unsigned long long), c->stream));
-        k_scale_in<<<grid_for(n), TPB, 0, c->stream>>>(o->dinv, sc, x->d, n, bits);
-        k_dmin_slot<<<1, 1, 0, c->stream>>>(bits, c->slots, c->flags);
-        PGD_LAUNCH_CHECK(c);
-        guard.active = true;            // x is scaled from here on
-        // Where A itself is ONE stencil + eliminated nodes on the whole grid (dia_classify: every row and slot verified - the
-        // Galerkin start has classified A from two vectors on) the scaled operator is known without touching a slot: every free
-        // row has the diagonal c0, s_i = (1 / c0)^1/2 there and 1 on the eliminated rows, and k_dia_scale would write
-        // c_s (s_i s_j) - one product, the same for every pair of free nodes - and keep the exact zeros.  The couplings of
-        // D^-1/2 A D^-1/2 are DERIVED with that very arithmetic (k_stencil_derive), the codes are A's: no scaling pass over the
-        // slot arrays (0.40 ms at 256^3), no second classification (0.25 ms), and the slot arrays still hold A afterwards.
-        // (PGD_TUNE_PCG_PRECOND = 2 builds its hierarchy from the scaled slot arrays: they are formed for every operator, one stencil or not)
-        if (c->pcg_derive_scaled && m->sym_nx > 0 && c->pcg_precond != 2) {
-            if (o->cls_count <= 0) PGD_TRY(dia_classify(c, m, o));
-            if (stencil_whole_grid(c, m, o) && o->st_ident >= 0 && o->st_c[0] > 0.0) {
-                PGD_TRY(ensure_work(c, 5, 4096));
-                StencilTuple in;
-                for (int s2 = 0; s2 < 8; ++s2) in.c[s2] = o->st_c[s2];
-                k_stencil_derive<<<1, 1, 0, c->stream>>>(in, c->spmv_unit_diag, c->work[5] + 16);
-                PGD_LAUNCH_CHECK(c);
-                double out8[8];
-                PGD_HIP(c, hipMemcpyAsync(out8, c->work[5] + 16, sizeof out8, hipMemcpyDeviceToHost, c->stream));
-                PGD_HIP(c, hipStreamSynchronize(c->stream));
-                bool fin = true;
-                for (double v : out8) fin = fin && std::isfinite(v);
-                if (fin) {
-                    for (int s2 = 0; s2 < 8; ++s2) { virt.saved[s2] = o->st_c[s2]; o->st_c[s2] = out8[s2]; }
-                    o->st_virtual = true;
-                    virt.active = true;
-                    guard.slots_scaled = false;
-                }
-            }
-        }
-        if (!virt.active) {
-            PGD_TRY(sym_scale(c, m, o, sc));
-            PGD_TRY(dia_classify(c, m, o));         // uniform grids: a code byte per row instead of its slot values
-        }
-        // multigrid preconditioner (PGD_TUNE_PCG_PRECOND): one stencil on a lattice whose eliminated nodes are its hull, else Jacobi.
-        // Its cycle works on vectors that vanish on the eliminated rows: x = b there from the start (their exact solution, s = 1)
-        if (c->pcg_precond == 1) {
-            mg_on = mg_prepare(c, m, o);
-            if (mg_on) { c->mg_solves += 1; PGD_TRY(mg_fix_start(c, o, b->d, x->d, n)); }
-            else c->mg_fallbacks += 1;
-        }
-        // ... = 2: the V-cycle on the diagonal form with per-row coefficients (pgd_vmg.hip): any operator on a lattice, any Dirichlet set
-        if (c->pcg_precond == 2) {
-            mg_on = vmg_on = m->sym_nx > 0 && vmg_prepare(c, c->vmg, m, o);
-            if (vmg_on) { c->vmg_solves += 1; PGD_TRY(vmg_fix_start(c, c->vmg, sc, b->d, x->d, n)); }
-            else c->vmg_fallbacks += 1;
-        }
-        if (c->pcg_precond == 3) c->cmg_fallbacks += 1;     // (a scalar layout: Jacobi)
-        PGD_TRY(launch_spmv_op(c, m, o, x->d, q, nullptr, 0, n, false, true, nullptr, nullptr));
-        const int g = grid_for(n);
-        PGD_TRY(ensure_partials(c, 4 * (int64_t)MAX_VEC_BLOCKS));
-        k_pcg_init_s<<<g, TPB, 0, c->stream>>>(b->d, q, sc, r, p, n, c->partials);
-        PGD_LAUNCH_CHECK(c);
-        PGD_TRY(reduce_partials(c, c->partials, g, 3, S_INIT, -1, 0, 0));
-    } else {
-        if (c->pcg_precond == 1) c->mg_fallbacks += 1;      // (no symmetric storage, or the scaled recurrence switched off: Jacobi)
-        if (c->pcg_precond == 2) c->vmg_fallbacks += 1;
-        // ... = 3: blocked P1 layouts over a box lattice - one V-cycle of pgd_vmg.hip per component on the diagonal blocks of
-        // D^-1/2 A D^-1/2, read from the CSR values (the solve itself stays the unscaled textbook recurrence on k_spmv_csr)
-        if (c->pcg_precond == 3) {
-            if (m->ncomp >= 2) PGD_TRY(ensure_vals(c, m, o));
-            mg_on = cmg_on = m->ncomp >= 2 && cmg_prepare(c, m, get_mesh(c, m->base), o);
-            if (cmg_on) { c->cmg_solves += 1; PGD_TRY(cmg_fix_start(c, b->d, x->d, n)); }
-            else c->cmg_fallbacks += 1;
-        }
-        PGD_TRY(launch_spmv_op(c, m, o, x->d, q, nullptr, 0, n, false, true, nullptr, nullptr));
-        PGD_TRY(pcg_init(c, b->d, q, o->dinv, r, z, p, 0, n, S_INIT));
-    }
-    k_pcg_tol<<<1, 64, 0, c->stream>>>(c->slots, c->flags, rtol, atol, S_INIT + 1, S_INIT + 2, S_TOL2);
+    PcgRun R{c, m, o, b->d, x->d, n, c->work[0], c->work[1], c->work[2], c->work[3], c->work[1]};
+    R.scaled = sym && c->pcg_scaled && n >= 2;
+    PGD_TRY(R.scaled ? pcg_setup_scaled(R) : pcg_setup_unscaled(R));
+    k_pcg_tol<<<1, 64, 0, c->stream>>>(c->slots, c->flags, rtol, atol, R.S_INIT + 1, R.S_INIT + 2, S_TOL2);
     PGD_LAUNCH_CHECK(c);
-    if (mg_on) {                        // p0 = z0 = M r0; the first "previous r.z"
-        int np = 0;
-        if (cmg_on) PGD_TRY(cmg_apply(c, r, p, n, &np));
-        else PGD_TRY(vmg_on ? vmg_vcycle(c, c->vmg, r, true, &np, p, &c->vmg_marches) : mg_vcycle(c, r, true, &np, p));
-        PGD_TRY(reduce_partials(c, c->partials, np, 1, S_INIT, -1, 0, 0));
-    }
+    PGD_TRY(pcg_choose_and_seed(R));
 
-    // second partials buffer for the folded reductions (the x / r update reads the product's partials while writing its own)
-    PGD_TRY(ensure_work(c, 6, 4 * (int64_t)MAX_VEC_BLOCKS));
-    double *part2 = c->work[6];                         // (the two-launch form of small systems alternates between this half and the next)
-    // large systems: the x update rides in the p kernel (PGD_TUNE_PCG_DEFER_X); the folded small-system form keeps its own kernels
-    // systems of up to 2^20 rows: single-sync recurrence in two launches per iteration (k_pcg1_step) ...
-    const bool fold = !mg_on && scaled && c->pcg_single_sync && c->pcg_small_ss && (n <= ((int64_t)1 << 20) || (n <= c->pcg_small_ss_rows && m->sym_nx > 0));
-    // ... or the two-reduction recurrence with its final reduction passes folded into their consumers (three launches)
-    const bool folded_form = !mg_on && scaled && c->pcg_fold_reduce && n <= ((int64_t)1 << 20) && !fold;
-    const bool single_sync = !mg_on && (fold || (scaled && c->pcg_single_sync && !folded_form && m->sym_nx > 0));
-    double *part2b = part2 + 2 * (int64_t)MAX_VEC_BLOCKS;
-    const bool deferred_x = !mg_on && scaled && c->pcg_defer_x && !folded_form && !single_sync;
-    const bool lag_x = single_sync && c->pcg_lag_x;
-    // (two-launch form above 2^20 rows: 512 workgroups in the update, every one of which sums all partial sums)
-    const int g2v = grid_for((n + 1) / 2, TPB, (n > ((int64_t)1 << 20) && n <= c->pcg_small_ss_rows && c->pcg_small_ss) ? 512 : MAX_VEC_BLOCKS);
-    // one-stencil operators in the three-launch form (PGD_TUNE_PCG_RECOMPUTE_Q): q = A p costs 16 of the iteration's 64 B per row to store and
-    // read back and 15 fused multiply-adds per row to form from planes of p the update could stage like the product does.  The product
-    // keeps only its dots (8 B per row), the update marches over p, forms q in registers and writes the new direction to the OTHER of
-    // the two buffers p and q (neighbouring workgroups still stage the old one; q is free once the initial residual is formed): the
-    // direction of iteration k lives in the buffer of parity k & 1, chunks start at even iterations, so a captured chunk replays unchanged.
-    const bool recompute_q = single_sync && !fold && c->pcg_recompute_q && stencil_whole_grid(c, m, o);
-    const int gvec = recompute_q ? stencil_update_blocks(c, m) : g2v;      // (r~.r~, true r.r) pairs the update leaves
-    if (recompute_q && 2 * (int64_t)gvec > 4 * (int64_t)MAX_VEC_BLOCKS) {
-        PGD_TRY(ensure_work(c, 6, 2 * (int64_t)gvec));
-        part2 = c->work[6];
-        part2b = part2 + 2 * (int64_t)MAX_VEC_BLOCKS;
-    }
-    if (single_sync) {
-        // the first look at the residual happens in the first k_pcg1_scalars: hand it the initial residual's sums
-        // (two-launch form: iteration k reads the pairs of parity (k - 1) & 1, so the seed goes to the second half)
-        k_pcg1_seed<<<8, TPB, 0, c->stream>>>(fold ? part2b : part2, gvec, c->slots, S_INIT, S_INIT + 1);
-        if (fold) PGD_HIP(c, hipMemsetAsync(c->slots + S1F_ALPHA, 0, 6 * sizeof(double), c->stream));     // alpha, beta, exact-phase bit x 2 parities
-        PGD_LAUNCH_CHECK(c);
-    }
-    auto enqueue = [&](int start, int count) -> int {
-        for (int k = 0; k < count; ++k) {
-            const int out = S_PAIR + 2 * ((start + k) & 1), rz_old = S_PAIR + 2 * ((start + k + 1) & 1);
-            int nparts = 0;
-            c->prof_iter = start + k;                    // launch timing: which iteration a sample belongs to (prof_commit)
-            if (single_sync) {
-                // (recompute_q: the direction of this iteration and the buffer its update writes the next one to)
-                double *p_cur = recompute_q && ((start + k) & 1) ? q : p, *p_next = p_cur == p ? q : p;
-                c->spmv_qq = 1;
-                const int rc = launch_spmv_op(c, m, o, p_cur, q, p_cur, 0, n, true, !recompute_q, c->flags, &nparts);
-                c->spmv_qq = 0;
-                PGD_TRY(rc);
-                const double *prod = c->partials;
-                if (nparts > 8192) {
-                    const int nb = (nparts + 1023) / 1024;
-                    PGD_TRY(ensure_work(c, 5, (int64_t)nb * 2 > 4096 ? (int64_t)nb * 2 : 4096));
-                    PGD_TRY(k_reduce_stage1_pub(c, c->partials, nparts, 2, c->work[5]));
-                    prod = c->work[5];
-                    nparts = nb;
-                }
-                if (!fold) k_pcg1_scalars<<<1, 1024, 0, c->stream>>>(prod, nparts, part2, gvec, c->slots, c->flags);
-                // launch timing on: every third update between HIP events (5 or 7 vector passes = 40 or 56 B per row; 4 or 6 = 32 or 48 where
-                // the update forms q itself)
-                const bool timed_u = c->prof && ((c->prof_upd_seen++ % 3) == 0);        // one in three: both halves of the x-update pairs get sampled
-                if (timed_u) {
-                    if (c->ev_used + 2 > c->ev.size()) prof_flush(c);
-                    c->ev_rec[c->ev_used / 2] = Ctx::ProfRec{1, c->prof_iter, 0.0, 0.0, 0.0};
-                    PGD_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
-                }
-                // the x update lags behind by one iteration in every other one (chunks start at even iteration indices)
-                const int lag = lag_x ? 1 + ((start + k) & 1) : 0;
-                if (recompute_q) PGD_TRY(launch_stencil_update(c, m, o, p_cur, p_next, x->d, r, sc, part2, lag));
-                else if (fold) {
-                    const int par = (start + k) & 1;
-                    k_pcg1_step<<<g2v, TPB, 0, c->stream>>>(x->d, r, p, q, sc, n, prod, nparts, par ? part2 : part2b, g2v, par ? part2b : part2,
-                                                            c->slots, c->flags, par, lag);
-                } else if (c->pcg_stream_hints) k_pcg1_update<true, false><<<g2v, TPB, 0, c->stream>>>(x->d, r, p, q, sc, 0, n, c->slots, S1_ALPHA, S1_BETA, part2, c->flags, lag, 0, 0, PushArgs());
-                else k_pcg1_update<false, false><<<g2v, TPB, 0, c->stream>>>(x->d, r, p, q, sc, 0, n, c->slots, S1_ALPHA, S1_BETA, part2, c->flags, lag, 0, 0, PushArgs());
-                if (timed_u) {
-                    PGD_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-                    c->ev_rec[c->ev_used / 2].bytes = ((lag == 1 ? 40.0 : 56.0) - (recompute_q ? 8.0 : 0.0)) * (double)n;      // (a lag = 1 launch that meets beta < 0.01 moves 56 / 48)
-                    c->ev_used += 2;
-                }
-                PGD_LAUNCH_CHECK(c);
-                continue;
-            }
-            PGD_TRY(launch_spmv_op(c, m, o, p, q, p, 0, n, true, true, c->flags, &nparts));
-            if (cmg_on) {
-                // the unscaled textbook recurrence with z = M r from the component cycles in place of z = D^-1 r: the update counts the
-                // iteration and tests the true r.r, the merge leaves r.z
-                int np = 0;
-                PGD_TRY(reduce_partials(c, c->partials, nparts, 1, S_PQ, 0, 0, 0));
-                PGD_TRY(pcg_xr(c, x->d, r, p, q, nullptr, nullptr, 0, n, rz_old, S_PQ, out, 1, S_TOL2));      // (no z = D^-1 r: the merge writes z)
-                PGD_TRY(cmg_apply(c, r, z, n, &np));
-                PGD_TRY(reduce_partials(c, c->partials, np, 1, out, -1, 0, 0));
-                k_pcg_p<true><<<grid_for((n + 1) / 2), TPB, 0, c->stream>>>(p, z, 0, n, c->slots, out, rz_old, c->flags);
-                PGD_LAUNCH_CHECK(c);
-                continue;
-            }
-            if (mg_on) {
-                // textbook PCG with z = M r from the V-cycle: the stop test stays the one of the Jacobi form (true r.r in the exact phase)
-                const int g2 = grid_for((n + 1) / 2);
-                int np = 0;
-                PGD_TRY(reduce_partials(c, c->partials, nparts, 1, S_PQ, 0, 0, 0));
-                k_pcg_xr_s<<<g2, TPB, 0, c->stream>>>(x->d, r, p, q, sc, n, c->slots, rz_old, S_PQ, c->partials, c->flags);
-                PGD_LAUNCH_CHECK(c);
-                PGD_TRY(reduce_partials(c, c->partials, g2, 2, out, 2, out + 1, S_TOL2));      // counts the iteration, tests
-                PGD_TRY(vmg_on ? vmg_vcycle(c, c->vmg, r, true, &np, nullptr, &c->vmg_marches) : mg_vcycle(c, r, true, &np));
-                PGD_TRY(reduce_partials(c, c->partials, np, 1, out, -1, 0, 0));                // r.z over the r~.r~ the test has used
-                k_pcg_p<true><<<g2, TPB, 0, c->stream>>>(p, vmg_on ? vmg_result(c->vmg) : mg_result(c), 0, n, c->slots, out, rz_old, c->flags);
-                PGD_LAUNCH_CHECK(c);
-                continue;
-            }
-            // (pays only where the launches, not the bytes, set the pace: 256^2 rows +22 %, 128^3 +-0, 256^3 -2 %)
-            if (scaled && c->pcg_fold_reduce && nparts > 0 && nparts <= 8192 && n <= ((int64_t)1 << 20)) {
-                const int g2 = grid_for((n + 1) / 2);
-                k_pcg_xr_s2<<<g2, TPB, 0, c->stream>>>(x->d, r, p, q, sc, n, c->slots, rz_old, c->partials, nparts, part2, c->flags);
-                k_pcg_p_s2<<<g2, TPB, 0, c->stream>>>(p, r, n, part2, g2, c->slots, out, rz_old, S_TOL2, c->flags);
-                PGD_LAUNCH_CHECK(c);
-                continue;
-            }
-            PGD_TRY(reduce_partials(c, c->partials, nparts, 1, S_PQ, 0, 0, 0));
-            if (scaled && deferred_x) {
-                // x += alpha p rides in the p kernel (8 vector passes per iteration instead of 9)
-                const int g2 = grid_for((n + 1) / 2);
-                k_pcg_r_s<<<g2, TPB, 0, c->stream>>>(r, q, sc, n, c->slots, rz_old, S_PQ, c->partials, c->flags);
-                PGD_LAUNCH_CHECK(c);
-                PGD_TRY(reduce_partials(c, c->partials, g2, 2, out, 2, out + 1, S_TOL2));
-                k_pcg_px_s<<<g2, TPB, 0, c->stream>>>(x->d, p, r, n, c->slots, out, rz_old, S_PQ, c->flags);
-                continue;
-            }
-            if (scaled) {
-                const int g2 = grid_for((n + 1) / 2);
-                k_pcg_xr_s<<<g2, TPB, 0, c->stream>>>(x->d, r, p, q, sc, n, c->slots, rz_old, S_PQ, c->partials, c->flags);
-                PGD_LAUNCH_CHECK(c);
-                PGD_TRY(reduce_partials(c, c->partials, g2, 2, out, 2, out + 1, S_TOL2));
-                k_pcg_p<true><<<grid_for((n + 1) / 2), TPB, 0, c->stream>>>(p, r, 0, n, c->slots, out, rz_old, c->flags);
-                continue;
-            }
-            // x, r, z update; the final reduction also runs the convergence test on r.r
-            PGD_TRY(pcg_xr(c, x->d, r, p, q, o->dinv, z, 0, n, rz_old, S_PQ, out, 1, S_TOL2));
-            k_pcg_p<true><<<grid_for((n + 1) / 2), TPB, 0, c->stream>>>(p, z, 0, n, c->slots, out, rz_old, c->flags);
-        }
-        return PGD_OK;
-    };
-
-    // The 16-iteration chunk (80 dependent launches) is replayed as a hipGraph: small systems are launch-bound, and at
-    // 256^3 the replay still saves ~2 % (549 vs 560 us per iteration).  With launch timing on, every PROF_EAGER_EVERY-th
-    // chunk is issued eagerly so that its products carry their HIP events; the capture itself records none.
-    hipGraphExec_t gexec = nullptr;
-    if (dbg_t) { (void)hipStreamSynchronize(c->stream); dbg_t1 = dbg_now(); }
-    // (a multigrid iteration is ~50 launches and a solve ~20 iterations: shorter chunks, less queued behind the converged one)
-    const int CE = mg_on ? std::max(2, std::min(c->mg_chunk & ~1, CHECK_EVERY)) : CHECK_EVERY;      // (even: iteration k uses the slot pair of parity k & 1, and the chunk is replayed)
-    if (maxit >= CE) {
-        // everything a chunk allocates lazily must exist before the capture starts
-        PGD_TRY(ensure_partials(c, std::max<int64_t>(4 * (int64_t)MAX_VEC_BLOCKS, 2 * ((n + 63) / 64) + 64)));
-        PGD_TRY(ensure_work(c, 5, 4096));
-        const bool prof_saved = c->prof;
-        c->prof = false;
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int rc = enqueue(0, CE);
-            const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-            if (rc != PGD_OK || e != hipSuccess || !graph ||
-                hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess)
-                gexec = nullptr;
-            if (graph) (void)hipGraphDestroy(graph);
-            (void)hipGetLastError();
-        }
-        c->prof = prof_saved;
-    }
-    int f[4] = {0, 0, 0, 0};
-    int enq = 0, rc_loop = PGD_OK;
-    if (dbg_t) dbg_t2 = dbg_now();
-    auto issue = [&](int chunk) -> int {
-        const bool eager_for_timing = c->prof && ((enq / CE) % PROF_EAGER_EVERY == 0);
-        if (gexec && chunk == CE && !eager_for_timing) {
-            if (hipGraphLaunch(gexec, c->stream) != hipSuccess) return fail(c, PGD_ERR_HIP, "pcg_solve: hipGraphLaunch failed");
-            return PGD_OK;
-        }
-        return enqueue(enq, chunk);
-    };
-    if (c->pcg_pipeline && pcg_flag_snapshots(c) == PGD_OK) {
-        // PIPELINED: the next chunk is queued BEFORE the host waits for the flags of the one before it - a snapshot of the flags
-        // into pinned memory + an event behind every chunk - so the GPU never idles through the host's round trip (copy, wake-up,
-        // graph launch: 50 - 130 us per 16 iterations, i.e. 2 % of a chunk at 256^3 and a third of one on a 256^2 grid).  A chunk
-        // queued behind the iteration that converged is 48 no-op launches (every kernel returns on the done flag), once per solve.
-        auto snap = [&](int slot) -> hipError_t {
-            hipError_t e = hipMemcpyAsync(c->flags_host + 4 * slot, c->flags, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipEventRecord(c->flag_ev[slot], c->stream);
-            return e;
-        };
-        int cur = 0;
-        hipError_t e = snap(0);                           // the flags after the initial residual
-        while (e == hipSuccess) {
-            const int chunk = (maxit - enq < CE) ? maxit - enq : CE;
-            if (chunk > 0) {
-                if ((rc_loop = issue(chunk)) != PGD_OK) break;
-                enq += chunk;
-                if ((e = snap(cur ^ 1)) != hipSuccess) break;
-            }
-            if ((e = hipEventSynchronize(c->flag_ev[cur])) != hipSuccess) break;
-            for (int i = 0; i < 4; ++i) f[i] = c->flags_host[4 * cur + i];
-            if (f[0] || chunk <= 0) break;                // converged (what is queued behind it does nothing), or nothing more to queue
-            cur ^= 1;
-        }
-        if (e != hipSuccess && rc_loop == PGD_OK) rc_loop = fail(c, PGD_ERR_HIP, "pcg_solve: %s", hipGetErrorString(e));
-    } else {
-        while (true) {
-            hipError_t e = hipMemcpyAsync(f, c->flags, sizeof f, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) { rc_loop = fail(c, PGD_ERR_HIP, "pcg_solve: %s", hipGetErrorString(e)); break; }
-            if (f[0] || enq >= maxit) break;
-            const int chunk = (maxit - enq < CE) ? maxit - enq : CE;
-            if ((rc_loop = issue(chunk)) != PGD_OK) break;
-            enq += chunk;
-        }
-    }
-    if (dbg_t) { (void)hipStreamSynchronize(c->stream); dbg_t3 = dbg_now(); }
-    if (dbg_t) fprintf(stderr, "[pcg_solve] n %lld graph %s iterations queued %d counted %d stencil %d cls %d | setup %.2f ms capture %.2f ms loop %.2f ms = %.1f us/it\n", (long long)n, gexec ? "yes" : "NO", enq, f[1], (int)o->st_ok, o->cls_count, 1e3 * (dbg_t1 - dbg_t0), 1e3 * (dbg_t2 - dbg_t1), 1e3 * (dbg_t3 - dbg_t2), 1e6 * (dbg_t3 - dbg_t2) / (f[1] > 0 ? f[1] : 1));
-    if (gexec) (void)hipGraphExecDestroy(gexec);
+    // (a multigrid iteration is ~50 launches and a solve ~20 iterations: shorter chunks, less queued behind the converged one;
+    // even: iteration k uses the slot pair of parity k & 1, and the chunk is replayed)
+    const int CE = R.form == PGD_PCG_FORM_PRECOND ? std::max(2, std::min(c->mg_chunk & ~1, CHECK_EVERY)) : CHECK_EVERY;
+    int f[4] = {0, 0, 0, 0}, enq = 0;
+    double dbg[4] = {0, 0, 0, 0};
+    const int rc_loop = pcg_drive(R, CE, maxit, f, enq, dbg_t ? dbg : nullptr);
+    if (dbg_t) fprintf(stderr, "[pcg_solve] n %lld graph %s iterations queued %d counted %d stencil %d cls %d form %d precond %d | setup %.2f ms capture %.2f ms loop %.2f ms = %.1f us/it\n", (long long)n, dbg[3] != 0.0 ? "yes" : "NO", enq, f[1], (int)o->st_ok, o->cls_count, (int)R.form, (int)R.precond, 1e3 * (dbg[0] - dbg_t0), 1e3 * (dbg[1] - dbg[0]), 1e3 * (dbg[2] - dbg[1]), 1e6 * (dbg[2] - dbg[1]) / (f[1] > 0 ? f[1] : 1));
     c->prof_iter = -1;
     // launch timing: the product of iteration k ran if no earlier iteration had set the done flag - f[1] iterations were counted, and in
     // the single-sync form the product of the iteration that NOTICED convergence ran as well; its update, and everything queued
     // behind it, did nothing
-    if (c->prof) prof_commit(c, rc_loop == PGD_OK ? f[1] + (single_sync ? 1 : 0) : 0, rc_loop == PGD_OK ? f[1] : 0);
+    if (c->prof) prof_commit(c, rc_loop == PGD_OK ? f[1] + (pcg_single_sync(R.form) ? 1 : 0) : 0, rc_loop == PGD_OK ? f[1] : 0);
     if (rc_loop != PGD_OK) return rc_loop;
-    if (scaled) {      // x = D^-1/2 x~, and the true r.r of the last iterate for the report
-        const int g = grid_for(n);
-        guard.active = false;
-        // converged (or broke down) inside an iteration whose p kernel was a no-op: its x update is still to come
-        const bool pending = deferred_x && f[0] != 0 && f[1] > 0;
-        // lagged x update: f[1] update kernels ran; if the last one had an even index it may have left its term outstanding
-        const bool lag_pending = lag_x && f[1] > 0 && ((f[1] - 1) & 1) == 0;
-        // (alpha and beta of that last update: in the two-launch form they sit in the slots of its parity)
-        const int last_par = f[1] > 0 ? (f[1] - 1) & 1 : 0;
-        // (recompute_q: f[1] updates ran, each wrote the direction to the other buffer)
-        const double *p_live = recompute_q && (f[1] & 1) ? q : p;
-        k_scale_out<<<g, TPB, 0, c->stream>>>(x->d, r, sc, n, c->partials, (pending || lag_pending) ? p_live : nullptr, c->slots,
-                                              S_PAIR + 2 * (f[1] & 1), S_PQ, lag_pending ? 1 : 0,
-                                              fold ? S1F_ALPHA + last_par : S1_ALPHA, fold ? S1F_BETA + last_par : S1_BETA);
-        PGD_LAUNCH_CHECK(c);
-        PGD_TRY(reduce_partials(c, c->partials, g, 1, S_TMP, -1, 0, 0));
-        if (!virt.active) {
-            o->uvals_valid = false;    // the slot arrays hold the scaled operator: nobody else may take them for A
-            o->uvals_scaled = false;
-        }
-    }
-    PGD_LAUNCH_CHECK(c);
-    double s[PGD_NSLOTS];
-    PGD_HIP(c, hipMemcpyAsync(s, c->slots, sizeof s, hipMemcpyDeviceToHost, c->stream));
-    PGD_HIP(c, hipStreamSynchronize(c->stream));
-    if (vmg_on) vmg_note_setup(c);
-    if (cmg_on) cmg_note_setup(c);
-    if (iters) *iters = f[1];
-    const double rr = scaled ? s[S_TMP] : (f[1] > 0) ? s[S_PAIR + 2 * ((f[1] - 1) & 1) + 1] : s[S_INIT + 1];
-    const double bb = s[S_INIT + 2];
-    if (relres) *relres = (bb > 0.0) ? sqrt(rr / bb) : 0.0;
-    if (f[2] != 0) return fail(c, f[2], "pcg_solve: breakdown (NaN residual) after %d iterations", f[1]);
+    return pcg_finish(R, f, iters, relres);
+}
+
+int pgd_pcg_last_form(pgd_handle h, int *form, int *precond) {
+    PGD_CTX(c, h);
+    if (form) *form = c->pcg_last_form;
+    if (precond) *precond = c->pcg_last_precond;
     return PGD_OK;
 }
 

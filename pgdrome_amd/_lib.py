@@ -57,7 +57,16 @@ SIGNATURES = {
     "pgd_vec_axpy": (C.c_int, [H, H, F64, H]),
     "pgd_vec_set": (C.c_int, [H, H, PI32, PD, I64]),
     "pgd_vec_lincomb": (C.c_int, [H, H, PH, PD, C.c_int]),
+    "pgd_vec_lincomb_inplace": (C.c_int, [H, H, PH, PD, C.c_int]),
     "pgd_vec_dot": (C.c_int, [H, H, H, I64, I64, PD]),
+    "pgd_block_create": (C.c_int, [H, I64, C.c_int, C.c_int, PH]),
+    "pgd_block_free": (C.c_int, [H, H]),
+    "pgd_block_info": (C.c_int, [H, H, PI64, C.POINTER(C.c_int), C.POINTER(C.c_int), PI64]),
+    "pgd_block_storage": (C.c_int, [H, C.POINTER(C.c_int)]),
+    "pgd_block_set_column": (C.c_int, [H, H, C.c_int, H]),
+    "pgd_block_get_column": (C.c_int, [H, H, C.c_int, H]),
+    "pgd_block_dots": (C.c_int, [H, H, H, I64, I64, PD]),
+    "pgd_block_combine": (C.c_int, [H, H, PD, H, H]),
     "pgd_eval_batch": (C.c_int, [H, PH, C.c_int, PD, I64, C.c_int, F64, PD, H, H, H, H]),
     "pgd_atom_assemble": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PH]),
     "pgd_atom_assemble_cells": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PU8, I64, PH]),
@@ -141,6 +150,8 @@ SIGNATURES = {
 NSLOTS = 64
 EVAL_STATS, EVAL_ENVELOPE, EVAL_EXCEED, EVAL_FIELDS = 1, 2, 4, 8      # PGD_EVAL_* (include/pgd_amd.h)
 TUNE_EVAL_VARIANT, TUNE_EVAL_GRID_MAX, TUNE_EVAL_SAMPLE_CHUNK = 50, 51, 52
+TUNE_BLOCK_STORAGE = 54
+BLOCK_F32, BLOCK_F64, BLOCK_MAXK = 0, 1, 64                                           # PGD_BLOCK_* (include/pgd_amd.h)
 
 
 ERR_TIMEOUT, ERR_PEER = -7, -8          # PGD_ERR_TIMEOUT, PGD_ERR_PEER (include/pgd_amd.h)
@@ -219,6 +230,7 @@ class Context:
             raise PgdError(rc, self.lib.pgd_last_error(0).decode())
         self.h = h.value
         self.device = device
+        self._block_k = {}            # column blocks of this context: handle -> k
 
     def close(self):
         if getattr(self, "h", 0):
@@ -348,6 +360,55 @@ class Context:
         arr = (H * max(k, 1))(*[int(x) for x in xs])
         cf = np.ascontiguousarray(coefs, dtype=np.float64)
         self._ck(self.lib.pgd_vec_lincomb(self.h, y, arr, dptr(cf) if k else None, k))
+
+    # ---- column blocks (pgd_block.hip)
+    def block_storage(self):
+        """BLOCK_F32 / BLOCK_F64 as PGD_TUNE_BLOCK_STORAGE selects for the spectral start space, None: separate vectors."""
+        d = C.c_int()
+        self._ck(self.lib.pgd_block_storage(self.h, C.byref(d)))
+        return d.value if d.value >= 0 else None
+
+    def block_create(self, n, k, dtype):
+        b = H(0)
+        self._ck(self.lib.pgd_block_create(self.h, int(n), int(k), int(dtype), C.byref(b)))
+        self._block_k[b.value] = int(k)      # (the per-solve calls below need it: no pgd_block_info round trip)
+        return b.value
+
+    def block_free(self, b):
+        self._ck(self.lib.pgd_block_free(self.h, b))
+        self._block_k.pop(b, None)
+
+    def block_info(self, b):
+        n, k, d, nb = I64(), C.c_int(), C.c_int(), I64()
+        self._ck(self.lib.pgd_block_info(self.h, b, C.byref(n), C.byref(k), C.byref(d), C.byref(nb)))
+        return {"n": n.value, "k": k.value, "dtype": ("fp32", "f64")[d.value], "bytes": nb.value}
+
+    def block_set_column(self, b, j, v):
+        self._ck(self.lib.pgd_block_set_column(self.h, b, int(j), v))
+
+    def block_get_column(self, b, j, v):
+        self._ck(self.lib.pgd_block_get_column(self.h, b, int(j), v))
+
+    def block_dots(self, b, r, lo=0, hi=-1):
+        """[Y_j . r for every column j] over [lo, hi): one pass over the block, one host synchronisation."""
+        out = np.zeros(BLOCK_MAXK, dtype=np.float64)
+        self._ck(self.lib.pgd_block_dots(self.h, b, r, int(lo), int(hi), dptr(out)))
+        return out[: self._block_k[b]].copy()
+
+    def block_combine(self, b, coefs, base, x):
+        """x = base + Y coefs (base: a vector, possibly x itself, or 0 / None for none)."""
+        if len(coefs) != self._block_k[b]:
+            raise ValueError("block_combine: one coefficient per column")
+        cf = np.zeros(BLOCK_MAXK, dtype=np.float64)
+        cf[: len(coefs)] = coefs
+        self._ck(self.lib.pgd_block_combine(self.h, b, dptr(cf), int(base or 0), x))
+
+    def vec_lincomb_inplace(self, y, xs, coefs):
+        """vec_lincomb where xs[0] may be y itself (at most 64 terms)."""
+        k = len(xs)
+        arr = (H * max(k, 1))(*[int(x) for x in xs])
+        cf = np.ascontiguousarray(coefs, dtype=np.float64)
+        self._ck(self.lib.pgd_vec_lincomb_inplace(self.h, y, arr, dptr(cf) if k else None, k))
 
     def eval_batch(self, modes, coefs, stats=True, env_min=0, env_max=0, exceed=0, threshold=0.0, fields=0):
         """pgd_eval_batch: all samples (columns of ``coefs``, shape (k, s)) of u = sum_t coefs[t] modes[t] in one pass over

@@ -35,7 +35,7 @@ struct Ctx;
 void dev_release(Ctx *c, void *p, size_t bytes);   // back to the context's buffer pool
 
 struct Obj {
-    enum Kind { FREE = 0, VEC, MESH, CSR } kind = FREE;
+    enum Kind { FREE = 0, VEC, MESH, CSR, BLOCK } kind = FREE;
     Ctx *ctx = nullptr;
     uint64_t serial = 0;        // unique per object of a context (handles are recycled, serials are not): put_obj
     virtual ~Obj() {}
@@ -45,6 +45,16 @@ struct Vec : Obj {
     double *d = nullptr;
     int64_t n = 0;
     ~Vec() override { if (d) dev_release(ctx, d, (size_t)(n > 0 ? n : 1) * sizeof(double)); }
+};
+
+// k columns of n rows in one allocation, as fp32 or f64 (pgd_block.hip): column j starts at element j * stride; the rows past n
+// of every column are zeros and are never written
+struct Block : Obj {
+    void *d = nullptr;
+    int64_t n = 0, stride = 0;
+    int k = 0, dtype = 0;       // PGD_BLOCK_F32 / PGD_BLOCK_F64
+    size_t bytes = 0;
+    ~Block() override { if (d) dev_release(ctx, d, bytes); }
 };
 
 struct Mesh : Obj {
@@ -333,6 +343,7 @@ struct Ctx {
     int pcg_derive_scaled = 1;    // ... whose stencil couplings are DERIVED from the verified stencil of A where that exists (PGD_TUNE_PCG_DERIVE_SCALED)
     int spmv_combine_dia = 1;     // structured grids: op_combine also forms the diagonal form from the atoms' diagonal forms
     int spmv_sym = 1;             // PCG products from the symmetric half storage when the mesh qualifies
+    int block_storage = 1;        // storage of the spectral start space (PGD_TUNE_BLOCK_STORAGE): 0 = f64 vectors, 1 = fp32 block, 2 = f64 block
 
     // SpMV launch timing (HIP events on `stream`)
     bool prof = false;
@@ -461,6 +472,7 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
 inline Vec *get_vec(Ctx *c, pgd_handle h) { return static_cast<Vec *>(get_obj(c, h, Obj::VEC)); }
 inline Mesh *get_mesh(Ctx *c, pgd_handle h) { return static_cast<Mesh *>(get_obj(c, h, Obj::MESH)); }
 inline Csr *get_csr(Ctx *c, pgd_handle h) { return static_cast<Csr *>(get_obj(c, h, Obj::CSR)); }
+inline Block *get_block(Ctx *c, pgd_handle h) { return static_cast<Block *>(get_obj(c, h, Obj::BLOCK)); }
 
 #define PGD_CTX(c, h)                         \
     pgd::Ctx *c = pgd::get_ctx(h);            \
@@ -495,7 +507,7 @@ inline int grid_for(int64_t n, int per_block = TPB, int cap = MAX_VEC_BLOCKS) {
 int scan_exclusive_i32(Ctx *c, const int *in, int *out, int64_t n);   // out has n+1 entries
 int reduce_partials(Ctx *c, const double *partials, int nparts, int nvals, int slot0, int check_mode,
                     int slot_rr, int slot_tol2);
-int reduce_partials_to(Ctx *c, const double *partials, int nparts, int nvals, double *dest);
+int reduce_partials_to(Ctx *c, const double *partials, int nparts, int nvals, double *dest, int blocks = 1);   // blocks > 1: the values dealt over that many workgroups (same order per value)
 int k_reduce_stage1_pub(Ctx *c, const double *partials, int nparts, int nvals, double *out);
 int vec_dot_range(Ctx *c, const double *x, const double *y, int64_t lo, int64_t hi, int slot);
 // pgd_spmv.hip

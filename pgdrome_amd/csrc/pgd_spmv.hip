@@ -2895,6 +2895,7 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_EVAL_GRID_MAX && value >= 0 && value <= 1 << 20) { c->eval_grid_max = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_EVAL_SAMPLE_CHUNK && value >= 0 && value <= 1024) { c->eval_chunk = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_PCG_RECOMPUTE_Q && value >= 0 && value <= 1) { c->pcg_recompute_q = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_BLOCK_STORAGE && value >= 0 && value <= 2) { c->block_storage = (int)value; return PGD_OK; }
     return fail(c, PGD_ERR_INVALID, "tune: unknown knob %d or value out of range", knob);
 }
 

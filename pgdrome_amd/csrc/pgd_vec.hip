@@ -26,22 +26,31 @@ __global__ __launch_bounds__(TPB) void k_set(double *__restrict__ v, const int *
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) v[idx[i]] = val[i];
 }
 
-// y = sum_k c_k x_k for up to 8 vectors per pass (one write per pass instead of one per term):
-// the online reconstruction u(x) = sum_k [prod_i F_i^k(mu_i)] F_x^k of a PGD solution
-// (reference model.py:805-842) is this tall-skinny product; 8 (K + 1) n bytes per call.
+// y = sum_k c_k x_k for up to LINCOMB_MAX vectors per launch, pointers and coefficients in the kernel arguments (one write of y
+// however many terms; eight loads in flight per lane): the online reconstruction u(x) = sum_k [prod_i F_i^k(mu_i)] F_x^k of a
+// PGD solution (reference model.py:805-842) is this tall-skinny product; 8 (K + 1) n bytes per call.  The fma chain runs from 0
+// (or from y) through the terms in ascending order.  Every lane reads entry i of all terms before it writes y_i, so a term may
+// be y itself (pgd_vec_lincomb_inplace).
+constexpr int LINCOMB_MAX = 64;
 struct LincombArgs {
-    const double *x[8];
-    double c[8];
+    const double *x[LINCOMB_MAX];
+    double c[LINCOMB_MAX];
     int k;
     int accumulate;   // 1: y += ..., 0: y = ...
 };
 
-__global__ __launch_bounds__(TPB) void k_lincomb(double *__restrict__ y, LincombArgs A, int64_t n) {
+__global__ __launch_bounds__(TPB) void k_lincomb(double *y, LincombArgs A, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
         double s = A.accumulate ? y[i] : 0.0;
+        for (int t0 = 0; t0 < A.k; t0 += 8) {
+            double v[8];
 #pragma unroll
-        for (int t = 0; t < 8; ++t)
-            if (t < A.k) s = fma(A.c[t], A.x[t][i], s);
+            for (int u = 0; u < 8; ++u)
+                if (t0 + u < A.k) v[u] = A.x[t0 + u][i];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (t0 + u < A.k) s = fma(A.c[t0 + u], v[u], s);
+        }
         y[i] = s;
     }
 }
@@ -60,6 +69,8 @@ __global__ __launch_bounds__(TPB) void k_dot(const double *__restrict__ x, const
 // Final pass of every reduction: one 1024-thread workgroup adds `nparts` partial
 // sums per value in a fixed order and writes slots[slot0 + v].  check_mode 1 adds
 // the PCG convergence test (library-driven loop): iters += 1, done <- rr <= tol2.
+// A launcher may deal the values over several workgroups (reduce_partials_to, check_mode < 0 only): the order per value is the
+// same; the convergence tests below belong to workgroup 0 alone.
 __global__ __launch_bounds__(1024) void k_reduce_partials(const double *__restrict__ partials, int nparts,
                                                           int nvals, double *__restrict__ slots, int slot0,
                                                           int check_mode, int slot_rr, int slot_tol2,
@@ -67,7 +78,7 @@ __global__ __launch_bounds__(1024) void k_reduce_partials(const double *__restri
     __shared__ double s_w[16];
     if (flags && check_mode >= 0 && flags[0]) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int v = 0; v < nvals; ++v) {
+    for (int v = blockIdx.x; v < nvals; v += gridDim.x) {      // (one workgroup unless the launcher deals the values out)
         // 8 independent accumulators: 8 loads in flight per lane instead of a dependent chain
         // (65536 SpMV partials took 30 us as a chain); the order is fixed, so still reproducible
         double a8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -89,7 +100,7 @@ __global__ __launch_bounds__(1024) void k_reduce_partials(const double *__restri
             slots[slot0 + v] = t;
         }
     }
-    if (check_mode == 1 && threadIdx.x == 0) {
+    if (check_mode == 1 && threadIdx.x == 0 && blockIdx.x == 0) {
         __threadfence_block();
         const double rr = slots[slot_rr], tol2 = slots[slot_tol2];
         flags[1] += 1;
@@ -99,7 +110,7 @@ __global__ __launch_bounds__(1024) void k_reduce_partials(const double *__restri
     // check_mode 2: the diagonally scaled recurrence (pgd_pcg.hip).  slots[slot0] = r~.r~; slots[slot_rr] is the TRUE
     // r.r only once flags[3] (exact phase) is set - until then r.r >= d_min r~.r~ proves that the test cannot pass yet,
     // and the phase is entered two orders of magnitude (in the norm) before it could.
-    if (check_mode == 2 && threadIdx.x == 0) {
+    if (check_mode == 2 && threadIdx.x == 0 && blockIdx.x == 0) {
         __threadfence_block();
         const double rz = slots[slot0], rr = slots[slot_rr], tol2 = slots[slot_tol2];
         flags[1] += 1;
@@ -232,7 +243,7 @@ int k_reduce_stage1_pub(Ctx *c, const double *partials, int nparts, int nvals, d
 }
 
 // the same final pass into any device array (dest[0..nvals))
-int reduce_partials_to(Ctx *c, const double *partials, int nparts, int nvals, double *dest) {
+int reduce_partials_to(Ctx *c, const double *partials, int nparts, int nvals, double *dest, int blocks) {
     if (nparts > 8192) {
         const int nb = (nparts + 1023) / 1024;
         PGD_TRY(ensure_work(c, 5, (int64_t)nb * nvals > 4096 ? (int64_t)nb * nvals : 4096));
@@ -240,7 +251,7 @@ int reduce_partials_to(Ctx *c, const double *partials, int nparts, int nvals, do
         partials = c->work[5];
         nparts = nb;
     }
-    k_reduce_partials<<<1, 1024, 0, c->stream>>>(partials, nparts, nvals, dest, 0, -1, 0, 0, nullptr);
+    k_reduce_partials<<<blocks > 1 ? blocks : 1, 1024, 0, c->stream>>>(partials, nparts, nvals, dest, 0, -1, 0, 0, nullptr);
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
 }
@@ -328,14 +339,16 @@ int pgd_vec_axpy(pgd_handle h, pgd_handle yh, double a, pgd_handle xh) {
     return PGD_OK;
 }
 
-int pgd_vec_lincomb(pgd_handle h, pgd_handle yh, const pgd_handle *xs, const double *coefs, int k) {
+// in_place: xs[0] may be y (one launch only)
+static int vec_lincomb(pgd_handle h, pgd_handle yh, const pgd_handle *xs, const double *coefs, int k, bool in_place) {
     PGD_CTX(c, h);
     Vec *y = get_vec(c, yh);
-    if (!y || k < 0 || (k > 0 && (!xs || !coefs))) return fail(c, PGD_ERR_INVALID, "vec_lincomb: bad arguments");
+    if (!y || k < 0 || (k > 0 && (!xs || !coefs)) || (in_place && k > LINCOMB_MAX)) return fail(c, PGD_ERR_INVALID, "vec_lincomb: bad arguments");
     std::vector<const double *> px((size_t)k);
     for (int t = 0; t < k; ++t) {
         Vec *x = get_vec(c, xs[t]);
-        if (!x || x->n != y->n || x == y) return fail(c, PGD_ERR_INVALID, "vec_lincomb: vector %d invalid, of another size or aliasing y", t);
+        if (!x || x->n != y->n || (x == y && !(in_place && t == 0)))
+            return fail(c, PGD_ERR_INVALID, "vec_lincomb: vector %d invalid, of another size or aliasing y", t);
         px[t] = x->d;
     }
     if (y->n == 0) return PGD_OK;
@@ -344,15 +357,23 @@ int pgd_vec_lincomb(pgd_handle h, pgd_handle yh, const pgd_handle *xs, const dou
         PGD_LAUNCH_CHECK(c);
         return PGD_OK;
     }
-    for (int first = 0; first < k; first += 8) {
+    for (int first = 0; first < k; first += LINCOMB_MAX) {
         LincombArgs A;
-        A.k = (k - first < 8) ? k - first : 8;
+        A.k = (k - first < LINCOMB_MAX) ? k - first : LINCOMB_MAX;
         A.accumulate = first > 0;
-        for (int t = 0; t < 8; ++t) { A.x[t] = px[first + (t < A.k ? t : 0)]; A.c[t] = (t < A.k) ? coefs[first + t] : 0.0; }
+        for (int t = 0; t < LINCOMB_MAX; ++t) { A.x[t] = px[first + (t < A.k ? t : 0)]; A.c[t] = (t < A.k) ? coefs[first + t] : 0.0; }
         k_lincomb<<<grid_for(y->n), TPB, 0, c->stream>>>(y->d, A, y->n);
     }
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
+}
+
+int pgd_vec_lincomb(pgd_handle h, pgd_handle yh, const pgd_handle *xs, const double *coefs, int k) {
+    return vec_lincomb(h, yh, xs, coefs, k, false);
+}
+
+int pgd_vec_lincomb_inplace(pgd_handle h, pgd_handle yh, const pgd_handle *xs, const double *coefs, int k) {
+    return vec_lincomb(h, yh, xs, coefs, k, true);
 }
 
 int pgd_start_residual(pgd_handle h, pgd_handle ah, int k, const double *coefs, pgd_handle bh, pgd_handle rh) {
@@ -362,20 +383,15 @@ int pgd_start_residual(pgd_handle h, pgd_handle ah, int k, const double *coefs, 
     if (!c->gram_op || c->gram_op != ah || c->gram_k != k || c->gram_n != b->n || r->n != b->n || !c->gram_w)
         return fail(c, PGD_ERR_INVALID, "start_residual: the library does not hold the %d products of this operator "
                                         "(pgd_start_gram over all rows with at most 9 vectors must come right before)", k);
-    // r = b - sum_j coefs[j] (A v_j): 8 terms per pass, b is the first term of the first pass
-    int done = 0;
-    bool first = true;
-    while (done < k || first) {
-        LincombArgs A;
-        int t = 0;
-        if (first) { A.x[0] = b->d; A.c[0] = 1.0; t = 1; }
-        for (; t < 8 && done < k; ++t, ++done) { A.x[t] = c->gram_w + (size_t)done * (size_t)c->gram_n; A.c[t] = -coefs[done]; }
-        A.k = t;
-        A.accumulate = first ? 0 : 1;
-        for (; t < 8; ++t) { A.x[t] = A.x[0]; A.c[t] = 0.0; }
-        k_lincomb<<<grid_for(r->n), TPB, 0, c->stream>>>(r->d, A, r->n);
-        first = false;
-    }
+    // r = b - sum_j coefs[j] (A v_j): b is the first term of the chain
+    if (k + 1 > LINCOMB_MAX) return fail(c, PGD_ERR_INVALID, "start_residual: too many products");
+    LincombArgs A;
+    A.x[0] = b->d; A.c[0] = 1.0;
+    for (int t = 0; t < k; ++t) { A.x[t + 1] = c->gram_w + (size_t)t * (size_t)c->gram_n; A.c[t + 1] = -coefs[t]; }
+    A.k = k + 1;
+    A.accumulate = 0;
+    for (int t = k + 1; t < LINCOMB_MAX; ++t) { A.x[t] = A.x[0]; A.c[t] = 0.0; }
+    k_lincomb<<<grid_for(r->n), TPB, 0, c->stream>>>(r->d, A, r->n);
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
 }

@@ -3589,6 +3589,9 @@ def _rescale_start(lay, op, b, x):
         return None
     if k == 1:
         be.vec_scale(x.dev(), float(coef[0]))
+    elif hasattr(be, "vec_lincomb_inplace"):
+        # straight into x, which is the first term: every entry of the terms is read before that entry of x is written
+        be.vec_lincomb_inplace(x.dev(), [v.dev() for v in vecs], [float(c) for c in coef])
     else:
         out = be.vec_zeros(lay.n)
         be.vec_lincomb(out, [v.dev() for v in vecs], [float(c) for c in coef])

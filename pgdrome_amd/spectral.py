@@ -8,11 +8,15 @@ along them out of every later start residual:
     harvest   Lanczos on A^-1 started from the first right-hand side (so the Krylov space holds the eigenvectors the run's
               right-hand sides excite, not the whole low end), m = 2.5 k steps, every A^-1 v a solve of the engine's own PCG
               under the multigrid preconditioner (pgd_mg.hip; about 20 ms at 256^3), full re-orthogonalisation;
-              Rayleigh-Ritz of A on the basis; the k lowest Ritz vectors whose residual passed are kept (k x n doubles of HBM).
+              Rayleigh-Ritz of A on the basis; the k lowest Ritz vectors whose residual passed are kept - on the HIP backend
+              (unsharded) in ONE column block of the library, in fp32 by default (4 k n bytes of HBM; PGD_TUNE_BLOCK_STORAGE: f64
+              block, or k separate f64 vectors as on the oracle backend and on row-sharded layouts).  Ritz pairs kept at
+              residuals up to 1e-2 do not need 53 bits; the projection below is exact for whatever span is stored.
     per solve second level of the Galerkin start (fem._rescale_start is the first):  x0 = x1 + Y (Y'AY)^-1 Y'(b - A x1).
               Y'AY = sum_t c_t (Y'A_t Y) from Gram matrices kept per atom (Y vanishes on the eliminated nodes, so the
-              operator's Dirichlet rows play no part): one product, one multi-dot over Y, one linear combination over Y -
-              about 1.5 ms at 256^3 with k = 16 (2.7 ms with 32) against the 20 - 37 ms the iterations it saves would take.
+              operator's Dirichlet rows play no part), the Gram matrices formed from the columns AS STORED: one residual,
+              one pass over Y for all dots (pgd_block_dots), one pass over Y for the combination (pgd_block_combine) - the
+              figures per storage are in profiles/README.md (spectral_block_bench.jsonl).
 
 Measured (tools/spectral_start_study.py, bench.py --spectral-start k, profiles/r04_spectral_start_study_*.jsonl; cfg4, 256^3): PCG
 iterations per pass 551 -> 425 / 338 / 303 / 298 for k = 16 / 32 / 48 / 64 (2.5 k Lanczos steps each: the accuracy of the Ritz pairs
@@ -68,11 +72,52 @@ def clear():
 
 
 class SpectralStart:
-    def __init__(self, lay, Y, theta, residuals, info):
+    """The kept Ritz vectors, either as f64 vectors (``Y``: the oracle backend, row-sharded layouts, PGD_TUNE_BLOCK_STORAGE = 0) or as
+    ONE column block of the library in fp32 or f64 (``block``; pgd_block.hip): the correction reads them twice per solve and
+    nothing else does, so their bytes are its cost.  The correction is the exact Galerkin projection onto the span that is
+    STORED - the Gram matrices are formed from the columns as they come back out of the block."""
+
+    def __init__(self, lay, Y, theta, residuals, info, be=None):
         self.lay = weakref.ref(lay)
         self.Y, self.theta, self.residuals, self.info = Y, theta, residuals, info
-        self.k = len(Y)
+        self.k, self._V = len(Y), Y[0].V
         self._gram = {}           # atom handle -> Y' A_t Y
+        self.block, self._be = None, None
+        dtype = be.block_storage() if be is not None and lay.part is None and hasattr(be, "block_create") else None
+        if dtype is not None:
+            self.block, self._be = be.block_create(lay.n, self.k, dtype), be
+            for j, y in enumerate(Y):
+                be.block_set_column(self.block, j, y.dev())
+            self.Y = None         # the f64 vectors go
+            bi = be.block_info(self.block)
+            info.update(storage=bi["dtype"] + " block", bytes=bi["bytes"])
+        else:
+            info.update(storage="f64 vectors", bytes=8 * self.k * lay.n)
+
+    def __del__(self):
+        if self.block is not None:
+            try:
+                self._be.block_free(self.block)
+            except Exception:
+                pass
+            self.block = None
+
+    def column(self, fem, j, out=None):
+        """Ritz vector j as an f64 Vector: the vector itself, or the block's column as it is stored (rounded for fp32), fetched
+        into `out` (a fresh Vector without one).  ``Y`` is None once the vectors live in a block: this is the way to read them."""
+        if self.Y is not None:
+            return self.Y[j]
+        out = fem.Vector(self._V) if out is None else out
+        self._be.block_get_column(self.block, j, out.dev_for_write())
+        out.touched_dev()
+        return out
+
+    def dots(self, fem, lay, r):
+        """Y' r over the owned rows."""
+        if self.block is None:
+            return _multidot(fem, lay, r, self.Y)
+        lo, hi = lay.owned_range()
+        return self._be.block_dots(self.block, r.dev(), lo, hi)
 
     def gram(self, fem, handles, coefs):
         be = fem.get_backend()
@@ -83,12 +128,14 @@ class SpectralStart:
             Gt = self._gram.get(h)
             if Gt is None:
                 Gt = np.zeros((self.k, self.k))
-                w = fem.Vector(self.Y[0].V)
-                for j, y in enumerate(self.Y):
-                    fem._halo(lay, y)
-                    be.spmv(h, y.dev(), w.dev_for_write(), lo, hi)
+                w = fem.Vector(self._V)
+                y = fem.Vector(self._V) if self.Y is None else None
+                for j in range(self.k):
+                    yj = self.column(fem, j, y)
+                    fem._halo(lay, yj)
+                    be.spmv(h, yj.dev(), w.dev_for_write(), lo, hi)
                     w.touched_dev()
-                    Gt[:, j] = _multidot(fem, lay, w, self.Y)
+                    Gt[:, j] = self.dots(fem, lay, w)
                 Gt = 0.5 * (Gt + Gt.T)
                 self._gram[h] = Gt
             G += float(c) * Gt
@@ -123,7 +170,7 @@ class SpectralStart:
                 r.axpy(1.0, b)
             else:
                 r.touched_dev()
-        g = _multidot(fem, lay, r, self.Y)
+        g = self.dots(fem, lay, r)
         if not (np.all(np.isfinite(G)) and np.all(np.isfinite(g))):
             return False
         d = np.sqrt(np.abs(np.diag(G)))
@@ -131,14 +178,21 @@ class SpectralStart:
         coef = np.linalg.lstsq(G / np.outer(d, d), g / d, rcond=1e-12)[0] / d
         if not np.all(np.isfinite(coef)) or not np.any(coef):
             return False
-        out = be.vec_zeros(lay.n)
-        vecs = [y.dev() for y in self.Y]
         cs = [float(c) for c in coef]
-        if not x._zero:
-            vecs, cs = [x.dev()] + vecs, [1.0] + cs
-        be.vec_lincomb(out, vecs, cs)
-        be.vec_copy(x.dev_for_write(), out)
-        be.vec_free(out)
+        if self.block is not None:
+            if x._zero:
+                be.block_combine(self.block, cs, 0, x.dev_for_write())
+            else:
+                xd = x.dev()
+                be.block_combine(self.block, cs, xd, xd)
+        else:
+            out = be.vec_zeros(lay.n)
+            vecs = [y.dev() for y in self.Y]
+            if not x._zero:
+                vecs, cs = [x.dev()] + vecs, [1.0] + cs
+            be.vec_lincomb(out, vecs, cs)
+            be.vec_copy(x.dev_for_write(), out)
+            be.vec_free(out)
         x.touched_dev()
         if lay.part is not None:
             x._halo_version = -1
@@ -274,4 +328,4 @@ def harvest(fem, A, b, k, steps=None):
             "ritz_values": theta, "relative_residuals": res, "rows": lay.n}
     LOG.info("spectral start: %d Ritz vectors of %d rows in %.2f s (%d inverse-Lanczos steps, %d inner PCG iterations)",
              len(Y), lay.n, dt, m, its)
-    return SpectralStart(lay, Y, theta, res, info)
+    return SpectralStart(lay, Y, theta, res, info, be)

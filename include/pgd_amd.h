@@ -454,6 +454,16 @@ int pgd_eval_batch(pgd_handle ctx, const pgd_handle *modes, int k, const double 
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_PCG_SCALAR_S = 56, /* 1 (default): where pgd_pcg_solve holds the scaled operator as a derived stencil (A itself is one stencil plus
+                                eliminated nodes), s = d^-1/2 takes exactly two values - (1 / c0)^1/2 on the free rows, 1 on the eliminated
+                                ones - and the update march of PGD_TUNE_PCG_RECOMPUTE_Q divides by them in its exact phase instead of
+                                reading s (8 B per row less there).  The same quotients, bit for bit.  0: s is streamed */
+    PGD_TUNE_PCG_FOLD_MARCH = 55, /* 1: PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE runs two launches per iteration - every workgroup of
+                                the update march sums the product's and the previous update's partial sums itself, in the order of
+                                k_pcg1_scalars, and takes the stop test / alpha / beta step on local values (workgroup 0 keeps the scalar
+                                bank and the flags).  Same alpha, beta, stop decisions and iterates, bit for bit.  0 (default): k_pcg1_scalars is a
+                                launch of its own between the product and the update.  Measured at 256^3: 161.3 -> 160.1 us per
+                                iteration, 0.33 ms of 48 per step - less than the run-to-run spread, so it is off */
     PGD_TUNE_BLOCK_STORAGE = 54, /* how pgdrome_amd/spectral.py keeps the Ritz vectors of its start space (pgd_block_storage): 1 (default) a column
                                 block in fp32 - the correction is an exact Galerkin projection onto the span that is stored, its Gram
                                 matrix is formed from the rounded columns, and only the start vector of a solve depends on it; 2: a

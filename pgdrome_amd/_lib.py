@@ -151,6 +151,7 @@ NSLOTS = 64
 EVAL_STATS, EVAL_ENVELOPE, EVAL_EXCEED, EVAL_FIELDS = 1, 2, 4, 8      # PGD_EVAL_* (include/pgd_amd.h)
 TUNE_EVAL_VARIANT, TUNE_EVAL_GRID_MAX, TUNE_EVAL_SAMPLE_CHUNK = 50, 51, 52
 TUNE_BLOCK_STORAGE = 54
+TUNE_PCG_FOLD_MARCH, TUNE_PCG_SCALAR_S = 55, 56
 BLOCK_F32, BLOCK_F64, BLOCK_MAXK = 0, 1, 64                                           # PGD_BLOCK_* (include/pgd_amd.h)
 
 

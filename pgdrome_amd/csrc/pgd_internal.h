@@ -29,6 +29,7 @@ enum { S_PQ = 2, S_TOL2 = 5, S_DMIN = 7 /* smallest diagonal entry (scaled PCG) 
 // single-sync recurrence (pgd_pcg.hip; the stencil march's update epilogue reads them too)
 enum { S1_RZ = 24, S1_RR = 25, S1_ALPHA = 26, S1_BETA = 27, S1_PQ = 28, S1_QQ = 29,
        S1_ALPHA_PREV = 40, S1_BETA_PREV = 41, S1_PEND = 42 };      // the lagged x update
+enum { S1F_ALPHA = 44 /* +parity */, S1F_BETA = 46 /* +parity */, S1F_EXACT = 48 /* +parity */ };   // scalar step inside the update kernel
 constexpr double LAG_MIN_BETA = 0.01;
 
 struct Ctx;
@@ -286,6 +287,8 @@ struct Ctx {
     int pcg_lag_x = 1;            // single-sync recurrence: x is updated every other iteration, two terms at a time (PGD_TUNE_PCG_LAG_X)
     int pcg_recompute_q = 1;      // ... and on one-stencil grids A p is not stored: the update marches over p and forms it again (PGD_TUNE_PCG_RECOMPUTE_Q)
     int64_t pcg_recompute_launches = 0;   // launches of that update (k_spmv_stencil_march, EPI 3)
+    int pcg_fold_march = 0;       // 1: every workgroup of it takes the scalar step itself, no k_pcg1_scalars launch (PGD_TUNE_PCG_FOLD_MARCH; measured: 0.3 ms of 48 per step, under the run-to-run spread - off)
+    int pcg_scalar_s = 1;         // ... and divides by the two values s takes on such an operator instead of streaming it (PGD_TUNE_PCG_SCALAR_S)
     int asm_lattice = 1;          // lattice meshes: edge vectors as whole lattice steps in the assembly (PGD_TUNE_ASM_LATTICE)
     int spmv_fetch_depth = 6;     // plane fetches in flight per workgroup of k_spmv_diac_march2 (3 or 6; PGD_TUNE_SPMV_FETCH_DEPTH)
     int spmv_zchunk_coded2 = 96;  // ... and where every slot (two workgroups per CU) gets at least 24 planes: marches that fill the slots exactly once, at most this long (0: off)
@@ -435,10 +438,16 @@ bool stencil_row_range(const Ctx *c, const Mesh *m, const Csr *a, int64_t r0, in
 bool stencil_whole_grid(const Ctx *c, const Mesh *m, const Csr *a);   // pgd_spmv.hip: a product over all rows would run in k_spmv_stencil_march
 // pgd_spmv.hip: the vector update of the single-sync recurrence as an epilogue of that march (stencil_whole_grid operators only): q = A p_in
 // is formed in registers, x and r are updated in place, the new direction goes to p_out; one (r~.r~, true r.r) pair per workgroup in
-// `pairs`, stencil_update_blocks of them
+// `pairs`, stencil_update_blocks of them.  s_free > 0: s is that number on every free row and 1 on the eliminated ones - it is not read.
+// fold != nullptr: every workgroup takes the scalar step itself (StencilFold)
+struct StencilFold {
+    const double *prod; int nprod;      // the product's (p.q, q.q) pairs
+    const double *vec_in; int nvec;     // the previous update's (r~.r~, true r.r) pairs: the other buffer than `pairs`
+    int par;                            // parity of the iteration
+};
 int stencil_update_blocks(const Ctx *c, const Mesh *m);
 int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, double *r, const double *s,
-                          double *pairs, int lag);
+                          double *pairs, int lag, double s_free = 0.0, const StencilFold *fold = nullptr);
 int launch_stencil_pass(Ctx *c, const uint8_t *cls, int ident, const double cst[8], int nx, int ny, int nz, int zm0, int zm1,
                         const double *x, const double *b, double *y, double w, int epi, bool dot, int *nparts, int z0 = 0, int z1 = -1);      // pgd_spmv.hip
 // pgd_mg.hip: multigrid preconditioner of the scaled stencil operator
@@ -537,6 +546,22 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
+}
+
+// The scalar step of the single-sync recurrence on values every thread holds (what pcg1_finish does on the scalar bank): the stop
+// test on the residual the sums belong to, the switch to the exact phase, alpha and beta for the update that follows
+struct Pcg1Scalars { double alpha, beta; int exact, done, status; double pq, qq, rz, rr; };
+__device__ __forceinline__ void pcg1_local_step(Pcg1Scalars &S, const double *__restrict__ slots, int exact_cur) {
+    S.alpha = S.beta = 0.0; S.exact = exact_cur; S.done = 0; S.status = 0;
+    const double tol2 = slots[S_TOL2];
+    if (!(S.rz == S.rz) || !(S.pq == S.pq)) { S.done = 1; S.status = PGD_ERR_SINGULAR; return; }
+    if (exact_cur) { if (S.rr <= tol2) { S.done = 1; return; } }
+    else if (S.rz * slots[S_DMIN] <= 1e4 * tol2) S.exact = 1;
+    if (!(S.rz > 0.0)) { S.done = 1; return; }
+    S.alpha = S.rz / S.pq;
+    double rnew = S.alpha * S.alpha * S.qq - S.rz;
+    if (!(rnew > 0.0)) rnew = 0.0;
+    S.beta = rnew / S.rz;
 }
 
 // Sum over an NW-wave workgroup in a fixed order; result valid in thread 0.

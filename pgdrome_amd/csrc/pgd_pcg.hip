@@ -471,11 +471,13 @@ __global__ __launch_bounds__(TPB) void k_scale_in(const double *__restrict__ din
 // k_scale_in (its root) and k_dia_scale (value times the product of the two scale factors; the diagonal: set to 1, or value
 // times s times s) on one free row
 struct StencilTuple { double c[8]; };
+// out[8] = that root: what k_scale_in has written to s on every free row
 __global__ void k_stencil_derive(StencilTuple A, int unit, double *__restrict__ out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const double dinv = 1.0 / A.c[0], si = sqrt(dinv);
     out[0] = unit ? 1.0 : A.c[0] * si * si;
     for (int s = 1; s < 8; ++s) { double v = A.c[s]; v *= si * si; out[s] = v; }
+    out[8] = si;
 }
 
 __global__ void k_dmin_slot(const unsigned long long *__restrict__ dmax_bits, double *__restrict__ slots, int *__restrict__ flags) {
@@ -619,7 +621,6 @@ __global__ __launch_bounds__(TPB) void k_pcg_px_s(double *__restrict__ x, double
 // up to rounding.  Slots: S1_RZ (measured r~.r~ of the current residual), S1_RR (its true r.r, exact phase),
 // S1_ALPHA, S1_BETA.
 // (S1_* and LAG_MIN_BETA: pgd_internal.h)
-enum { S1F_ALPHA = 44 /* +parity */, S1F_BETA = 46 /* +parity */, S1F_EXACT = 48 /* +parity */ };   // scalar step inside the update kernel
 
 __device__ __forceinline__ void pcg1_finish(double *slots, int *flags, double pq, double qq, double rz, double rr, int slot_alpha,
                                             int slot_beta, bool keep_prev = false) {
@@ -751,8 +752,13 @@ __global__ __launch_bounds__(TPB) void k_pcg1_aux(const double *__restrict__ s, 
 // ones and by k_scale_out when the solve ends between the two) says whether a term is outstanding.  lag = 0: every iteration.
 // ONE-STENCIL OPERATORS (PGD_TUNE_PCG_RECOMPUTE_Q, pgd_pcg_solve above pcg_small_ss_rows): this kernel is not launched at all - q is never
 // stored, and the same per-row operations run as an epilogue of the stencil march over p, which forms q in registers
-// (k_spmv_stencil_march EPI 3, launch_stencil_update: 32 / 48 B per row and 8 less in the product).  What follows is the form of
-// every other operator, of the sharded loop and of PGD_TUNE_PCG_RECOMPUTE_Q = 0.
+// (k_spmv_stencil_march EPI 3, launch_stencil_update: 32 / 48 B per row and 8 less in the product).  Where the scaled operator is a
+// derived stencil its exact phase reads no s: s is (1 / c0)^1/2 on the free rows and 1 on the eliminated ones, two numbers
+// (PGD_TUNE_PCG_SCALAR_S: 113.5 -> 107.3 us per launch at 256^3, the exact phase being 29 % of the iterations).  That march can take the
+// scalar step as well - no k_pcg1_scalars launch: every workgroup sums the partial sums in that kernel's order behind its first plane
+// fetches, the pairs and alpha / beta / the exact bit alternate with the parity of the iteration as under FOLD below
+// (PGD_TUNE_PCG_FOLD_MARCH; opt-in: 22.0 -> 19.1 us outside the two marches, but the march itself 100.8 -> 103.2 us).  What follows is the form of every other operator, of
+// the sharded loop and of PGD_TUNE_PCG_RECOMPUTE_Q = 0.
 // FOLD (the row-sharded loop, whose sums arrive all-reduced in slots[fold_base .. + 3]: p.q, q.q, r~.r~ and the true r.r of the
 // residual this launch starts from): EVERY workgroup runs the scalar step itself - stop test, alpha, beta from those four
 // numbers, bit for bit the same in all of them - and workgroup 0 keeps the books (iteration count, flags, the report's r.r):
@@ -899,8 +905,6 @@ __global__ __launch_bounds__(TPB) void k_pcg1_update(double *__restrict__ x, dou
 // the parity of the iteration; a workgroup that starts late and finds the done flag already set by workgroup 0 returns, which
 // is what its own test would have told it.  (Measured on larger systems too: at 128^3 a wash, at 256^3 the redundant sums cost
 // more than the launch they save - those keep k_pcg1_scalars + k_pcg1_update.)
-struct Pcg1Scalars { double alpha, beta; int exact, done, status; double pq, qq, rz, rr; };
-
 __device__ __forceinline__ Pcg1Scalars pcg1_wg_scalars(const double *__restrict__ prod, int nprod, const double *__restrict__ vecp, int nvec,
                                                        const double *__restrict__ slots, int exact_cur, double *s_w /* >= 16 */) {
     // all four sums in one sweep (16-byte loads of the pairs, every load independent), one exchange through LDS: a fixed
@@ -924,17 +928,7 @@ __device__ __forceinline__ Pcg1Scalars pcg1_wg_scalars(const double *__restrict_
     __syncthreads();                                     // s_w is the caller's reduction scratch as well
     Pcg1Scalars S;
     S.pq = out[0]; S.qq = out[1]; S.rz = out[2]; S.rr = out[3];
-    S.alpha = S.beta = 0.0; S.exact = exact_cur; S.done = 0; S.status = 0;
-    // (pcg1_finish, on local values)
-    const double tol2 = slots[S_TOL2];
-    if (!(S.rz == S.rz) || !(S.pq == S.pq)) { S.done = 1; S.status = PGD_ERR_SINGULAR; return S; }
-    if (exact_cur) { if (S.rr <= tol2) { S.done = 1; return S; } }
-    else if (S.rz * slots[S_DMIN] <= 1e4 * tol2) S.exact = 1;
-    if (!(S.rz > 0.0)) { S.done = 1; return S; }
-    S.alpha = S.rz / S.pq;
-    double rnew = S.alpha * S.alpha * S.qq - S.rz;
-    if (!(rnew > 0.0)) rnew = 0.0;
-    S.beta = rnew / S.rz;
+    pcg1_local_step(S, slots, exact_cur);
     return S;
 }
 
@@ -1462,6 +1456,8 @@ struct PcgRun {
     bool scaled = false, lag_x = false;
     bool x_scaled = false;              // x is in scaled coordinates
     bool virt = false;                  // the scaled operator is held as a derived stencil only: the slot arrays still hold A
+    double s_free = 0.0;                // ... and then s is this number on every free row, 1 on the eliminated ones (k_stencil_derive)
+    bool fold_march = false;            // the update march takes the scalar step itself (PGD_TUNE_PCG_FOLD_MARCH)
     double st_saved[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // On EVERY exit (a failing launch, graph replay or copy included): the stencil couplings back to those of A where the scaled
     // operator was a derived stencil; and, unless the finish has done it, x back to D^-1/2 x~ and the slot arrays no longer taken
@@ -1535,12 +1531,13 @@ static int pcg_derive_stencil(PcgRun &R) {
     for (int s2 = 0; s2 < 8; ++s2) in.c[s2] = o->st_c[s2];
     k_stencil_derive<<<1, 1, 0, c->stream>>>(in, c->spmv_unit_diag, c->work[5] + 16);
     PGD_LAUNCH_CHECK(c);
-    double out8[8];
-    PGD_HIP(c, hipMemcpyAsync(out8, c->work[5] + 16, sizeof out8, hipMemcpyDeviceToHost, c->stream));
+    double out9[9];
+    PGD_HIP(c, hipMemcpyAsync(out9, c->work[5] + 16, sizeof out9, hipMemcpyDeviceToHost, c->stream));
     PGD_HIP(c, hipStreamSynchronize(c->stream));
-    for (double v : out8) if (!std::isfinite(v)) return PGD_OK;
-    for (int s2 = 0; s2 < 8; ++s2) { R.st_saved[s2] = o->st_c[s2]; o->st_c[s2] = out8[s2]; }
+    for (double v : out9) if (!std::isfinite(v)) return PGD_OK;
+    for (int s2 = 0; s2 < 8; ++s2) { R.st_saved[s2] = o->st_c[s2]; o->st_c[s2] = out9[s2]; }
     o->st_virtual = R.virt = true;
+    R.s_free = out9[8];
     return PGD_OK;
 }
 
@@ -1592,13 +1589,16 @@ static int pcg_choose_and_seed(PcgRun &R) {
     // (two-launch form above 2^20 rows: 512 workgroups in the update, every one of which sums all partial sums)
     R.g2v = grid_for((n + 1) / 2, TPB, (n > ((int64_t)1 << 20) && n <= c->pcg_small_ss_rows && c->pcg_small_ss) ? 512 : MAX_VEC_BLOCKS);
     R.gvec = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE ? stencil_update_blocks(c, R.m) : R.g2v;
-    if (2 * (int64_t)R.gvec > 4 * (int64_t)MAX_VEC_BLOCKS) PGD_TRY(ensure_work(c, 6, 2 * (int64_t)R.gvec));
+    R.fold_march = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE && c->pcg_fold_march;
+    // (the march that takes the scalar step alternates between two halves like the two-launch form: each holds gvec pairs)
+    const int64_t half = 2 * std::max<int64_t>(MAX_VEC_BLOCKS, R.fold_march ? R.gvec : 0);
+    PGD_TRY(ensure_work(c, 6, std::max<int64_t>(2 * half, 2 * (int64_t)R.gvec)));
     R.part2 = c->work[6];
-    R.part2b = R.part2 + 2 * (int64_t)MAX_VEC_BLOCKS;
+    R.part2b = R.part2 + half;
     if (!pcg_single_sync(R.form)) return PGD_OK;
     // the first look at the residual happens in the first k_pcg1_scalars: hand it the initial residual's sums
-    // (two-launch form: iteration k reads the pairs of parity (k - 1) & 1, so the seed goes to the second half)
-    const bool two = R.form == PGD_PCG_FORM_TWO_LAUNCH;
+    // (scalar step in the update: iteration k reads the pairs of parity (k - 1) & 1, so the seed goes to the second half)
+    const bool two = R.form == PGD_PCG_FORM_TWO_LAUNCH || R.fold_march;
     k_pcg1_seed<<<8, TPB, 0, c->stream>>>(two ? R.part2b : R.part2, R.gvec, c->slots, R.S_INIT, R.S_INIT + 1);
     if (two) PGD_HIP(c, hipMemsetAsync(c->slots + S1F_ALPHA, 0, 6 * sizeof(double), c->stream));     // alpha, beta, exact-phase bit x 2 parities
     PGD_LAUNCH_CHECK(c);
@@ -1719,11 +1719,20 @@ static int pcg_iter_single_sync(PcgRun &R, int k) {
 // forms q in registers (4 or 6 vector passes) and writes the new direction to the OTHER of the two buffers p and q (neighbouring
 // workgroups still stage the old one; q is free once the initial residual is formed): the direction of iteration k lives in the
 // buffer of parity k & 1, chunks start at even iterations, so a captured chunk replays unchanged.
+// PGD_TUNE_PCG_FOLD_MARCH (opt-in): two launches - the dot-only product and the update march, every workgroup of which sums the product's pairs and
+// the previous update's pairs (the half of parity (k - 1) & 1; its own go to the other half) in the order of k_pcg1_scalars and takes the
+// scalar step itself; alpha / beta / the exact bit of iteration k live in the slots of parity k & 1 as in the two-launch form.
+// PGD_TUNE_PCG_SCALAR_S: where the scaled operator is a derived stencil the march divides by the two values of s instead of reading it.
 static int pcg_iter_single_sync_recompute(PcgRun &R, int k) {
     Pcg1Iter I;
-    double *p_cur = (k & 1) ? R.q : R.p, *p_next = (k & 1) ? R.p : R.q;
-    PGD_TRY(pcg1_begin(R, k, p_cur, false, true, &I));
-    PGD_TRY(launch_stencil_update(R.c, R.m, R.o, p_cur, p_next, R.x, R.r, R.sc, R.part2, I.lag));
+    const int par = k & 1;
+    double *p_cur = par ? R.q : R.p, *p_next = par ? R.p : R.q;
+    const double s_free = (R.virt && R.c->pcg_scalar_s) ? R.s_free : 0.0;
+    PGD_TRY(pcg1_begin(R, k, p_cur, false, !R.fold_march, &I));
+    if (R.fold_march) {
+        const StencilFold F{I.prod, I.nparts, par ? R.part2 : R.part2b, R.gvec, par};
+        PGD_TRY(launch_stencil_update(R.c, R.m, R.o, p_cur, p_next, R.x, R.r, R.sc, par ? R.part2b : R.part2, I.lag, s_free, &F));
+    } else PGD_TRY(launch_stencil_update(R.c, R.m, R.o, p_cur, p_next, R.x, R.r, R.sc, R.part2, I.lag, s_free));
     return pcg1_end(R, I, 8.0);
 }
 
@@ -1834,7 +1843,7 @@ static int pcg_finish(PcgRun &R, const int f[4], int *iters, double *relres) {
         const bool lag_pending = R.lag_x && f[1] > 0 && ((f[1] - 1) & 1) == 0;
         // (alpha and beta of that last update: in the two-launch form they sit in the slots of its parity)
         const int last_par = f[1] > 0 ? (f[1] - 1) & 1 : 0;
-        const bool two = R.form == PGD_PCG_FORM_TWO_LAUNCH;
+        const bool two = R.form == PGD_PCG_FORM_TWO_LAUNCH || R.fold_march;
         // (the update that forms q itself: f[1] updates ran, each wrote the direction to the other buffer)
         const double *p_live = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE && (f[1] & 1) ? R.q : R.p;
         k_scale_out<<<g, TPB, 0, c->stream>>>(R.x, R.r, R.sc, R.n, c->partials, (pending || lag_pending) ? p_live : nullptr, c->slots,

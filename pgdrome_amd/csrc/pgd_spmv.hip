@@ -1158,7 +1158,46 @@ struct StencilArgs {
     const double *us = nullptr;
     double *slots = nullptr;
     int lag = 0;
+    // s_free > 0 (PGD_TUNE_PCG_SCALAR_S): s is this number on every free row and 1 on the eliminated ones - us is not read.
+    // fold_par >= 0 (PGD_TUNE_PCG_FOLD_MARCH): no k_pcg1_scalars in front of this launch - every workgroup sums the product's (p.q, q.q) pairs
+    // and the previous update's (r~.r~, true r.r) pairs itself and takes the scalar step on local values; fold_par = parity of the iteration
+    double s_free = 0.0;
+    const double *fold_prod = nullptr, *fold_vec = nullptr;
+    int fold_nprod = 0, fold_nvec = 0, fold_par = -1;
+    int *fold_flags = nullptr;
 };
+
+// The four sums of k_pcg1_scalars in ITS order, by a 256-thread workgroup: per value lane t adds the entries t + 256 j, entry j into
+// accumulator j & 7, then the accumulators pairwise, then the wave; the caller adds the four waves as (w0 + w1) + (w2 + w3).  Same bits
+// as that kernel.  The pairs are read whole (16 bytes: p.q with q.q, r~.r~ with r.r) and both arrays in the same sweep, so that all
+// loads are in flight together: one memory round trip, not four, in front of every workgroup's march.
+__device__ __forceinline__ void pcg1_sums_like_scalars(const double *__restrict__ prod, int nprod, const double *__restrict__ vecp, int nvec,
+                                                       double (&w)[4]) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    double a[4][8];
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) a[v][u] = 0.0;
+    const int nmax = nprod > nvec ? nprod : nvec;
+    int i = threadIdx.x;
+    for (; i + 7 * 256 < nmax; i += 8 * 256) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int k = i + u * 256;
+            if (k < nprod) { const d2 t = *reinterpret_cast<const d2 *>(prod + 2 * (int64_t)k); a[0][u] += t.x; a[1][u] += t.y; }
+            if (k < nvec) { const d2 t = *reinterpret_cast<const d2 *>(vecp + 2 * (int64_t)k); a[2][u] += t.x; a[3][u] += t.y; }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 7; ++u) {
+        const int k = i + u * 256;
+        if (k < nprod) { const d2 t = *reinterpret_cast<const d2 *>(prod + 2 * (int64_t)k); a[0][u] += t.x; a[1][u] += t.y; }
+        if (k < nvec) { const d2 t = *reinterpret_cast<const d2 *>(vecp + 2 * (int64_t)k); a[2][u] += t.x; a[3][u] += t.y; }
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) w[v] = wave_sum(((a[v][0] + a[v][1]) + (a[v][2] + a[v][3])) + ((a[v][4] + a[v][5]) + (a[v][6] + a[v][7])));
+}
 
 #if defined(PGD_STENCIL_TIMING) || defined(PGD_STENCIL_WHATIF)
 #define PGD_ST_WHATIF(bit) (A.whatif & (bit))
@@ -1182,11 +1221,22 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
     static_assert(EPI != 3 || (DOT && STORE), "the PCG update leaves its partial sums and stores the new direction");
     __shared__ double s_x[4 * SLOT];
     __shared__ double s_red[4];
-    if (A.flags && A.flags[0]) return;
+    __shared__ double s_w[16];
+    __shared__ int s_done;
+    const bool fold = EPI == 3 && A.fold_par >= 0;
+    if (fold) {
+        // The exit on the done flag must be WORKGROUP-UNIFORM here: workgroup 0 of this very launch sets the flag when the stop test
+        // fires, and the waves of a workgroup that starts late could otherwise read different values - one leaves, the others wait
+        // for it at the next barrier (k_pcg1_step)
+        if (threadIdx.x == 0) s_done = A.flags[0];
+        __syncthreads();
+        if (s_done) return;
+    } else if (A.flags && A.flags[0]) return;
     // EPI 3: the scalars of k_pcg1_update (alpha and beta from k_pcg1_scalars, the lagged x update's state), uniform over the launch
     double u_alpha = 0.0, u_beta = 0.0, u_alpha_p = 0.0, u_ibeta_p = 0.0;
     bool u_exact = false, u_skip_x = false, u_two = false;
-    if (EPI == 3) {
+    const bool u_s_known = EPI == 3 && A.s_free > 0.0;
+    if (EPI == 3 && !fold) {
         u_alpha = A.slots[S1_ALPHA];
         u_beta = A.slots[S1_BETA];
         u_exact = A.flags[3] != 0;
@@ -1288,11 +1338,51 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
     {
         double t0[NQ], t1[NQ], t2[NQ];
         fetch(xq, fetch_live(za - 1), t0); fetch(xq + P, fetch_live(za), t1); fetch(xq + 2 * P, fetch_live(za + 1), t2);
+        xq += 3 * P;
+        if (fold) {
+            // the scalar step, behind ALL plane fetches of the prologue (none depends on it; the sums arrive with them): the four sums in
+            // the order of k_pcg1_scalars, the step of pcg1_finish on local values - the same bits in every workgroup and as in that
+            // kernel.  Nothing read here is written by a workgroup of this launch: the pairs this launch writes go to the other buffer,
+            // alpha / beta / the exact bit to the slots of this parity.  Workgroup 0 keeps the books.
+#pragma unroll
+            for (int s = 0; s < D; ++s) { fetch(xq, fetch_live(za + 2 + s), rr[s]); xq += P; }
+            const int par = A.fold_par;
+            const int exact_cur = A.slots[S1F_EXACT + (par ^ 1)] != 0.0;
+            u_two = A.lag == 2 && A.slots[S1_PEND] != 0.0;
+            u_alpha_p = u_two ? A.slots[S1F_ALPHA + (par ^ 1)] : 0.0;
+            u_ibeta_p = u_two ? 1.0 / A.slots[S1F_BETA + (par ^ 1)] : 0.0;
+            double w[4];
+            pcg1_sums_like_scalars(A.fold_prod, A.fold_nprod, A.fold_vec, A.fold_nvec, w);
+            if (lane == 0) {
+#pragma unroll
+                for (int v = 0; v < 4; ++v) s_w[4 * v + wv] = w[v];
+            }
+            __syncthreads();
+            Pcg1Scalars S;
+            S.pq = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+            S.qq = (s_w[4] + s_w[5]) + (s_w[6] + s_w[7]);
+            S.rz = (s_w[8] + s_w[9]) + (s_w[10] + s_w[11]);
+            S.rr = (s_w[12] + s_w[13]) + (s_w[14] + s_w[15]);
+            pcg1_local_step(S, A.slots, exact_cur);
+            if (blockIdx.x == 0 && tid == 0) {
+                A.slots[S1_PQ] = S.pq; A.slots[S1_QQ] = S.qq; A.slots[S1_RZ] = S.rz; A.slots[S1_RR] = S.rr;
+                A.slots[S1F_EXACT + par] = S.exact ? 1.0 : 0.0;
+                A.fold_flags[3] = S.exact;
+                if (S.done) { if (S.status) A.fold_flags[2] = S.status; A.fold_flags[0] = 1; }
+                else { A.slots[S1F_ALPHA + par] = S.alpha; A.slots[S1F_BETA + par] = S.beta; A.fold_flags[1] += 1; }
+            }
+            if (S.done) return;                                             // uniform over the whole launch; nothing is staged yet
+            u_alpha = S.alpha; u_beta = S.beta;
+            u_exact = S.exact != 0;
+            u_skip_x = A.lag == 1 && u_beta >= LAG_MIN_BETA;
+            if (A.lag == 1 && blockIdx.x == 0 && tid == 0) A.slots[S1_PEND] = u_skip_x ? 1.0 : 0.0;
+        }
         stage(za - 1, t0, own[2]); stage(za, t1, own[0]); stage(za + 1, t2, own[1]);
     }
-    xq += 3 * P;
+    if (!fold) {
 #pragma unroll
-    for (int s = 0; s < D; ++s) { fetch(xq, fetch_live(za + 2 + s), rr[s]); xq += P; }
+        for (int s = 0; s < D; ++s) { fetch(xq, fetch_live(za + 2 + s), rr[s]); xq += P; }
+    }
     yq += P;                                                                // = y + P za
     __syncthreads();
 #ifdef PGD_STENCIL_TIMING
@@ -1325,14 +1415,16 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
         const auto dx = rsrc_of(upd_plane(A.ux, yz), !u_skip_x);
 #pragma unroll
         for (int r = 0; r < RW; ++r) ux[r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(dx, sv[r], 0, AUX_RX));
+        if (u_s_known) return;                                              // uniform: s is two numbers, no load goes through A.us
         const auto ds = rsrc_of(upd_plane(A.us, yz), u_exact);
 #pragma unroll
         for (int r = 0; r < RW; ++r) us[r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(ds, sv[r], 0, 0));
     };
     // ... and the update of those rows from q = A p: the operations of k_pcg1_update in its order, per row.  dot / dot2 take the partial
     // sums of r'.r' and (exact phase) of (r' / s)^2; a cell outside the grid adds nothing to either and its stores are dropped
+    // (ones: bit r set = row r is an eliminated row, s = 1 there - read only where s is not streamed)
     auto upd_rows = [&](double *yz, const double (&qv)[RW], const double (&xo)[RW], const double (&ur)[RW], const double (&ux)[RW],
-                        const double (&us)[RW]) {
+                        const double (&us)[RW], unsigned ones) {
         const auto dp = rsrc_of(yz, true), dr = rsrc_of(upd_plane(A.ur, yz), true), dx = rsrc_of(upd_plane(A.ux, yz), !u_skip_x);
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
@@ -1350,7 +1442,11 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
             const bool in = sv[r] != OOB;                                   // (outside the grid q is a sum over the neighbours inside it: not zero)
             const double t = in ? ri : 0.0;
             dot = fma(t, t, dot);
-            if (u_exact) { const double ts = t / (in ? us[r] : 1.0); dot2 = fma(ts, ts, dot2); }
+            if (u_exact) {
+                const double sr = u_s_known ? (((ones >> r) & 1u) ? 1.0 : A.s_free) : us[r];
+                const double ts = t / (in ? sr : 1.0);
+                dot2 = fma(ts, ts, dot2);
+            }
         }
     };
     auto rows = [&](int z, double *yz, bool live, const double (&xo)[RW]) {
@@ -1409,7 +1505,7 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
             double qv[RW];
 #pragma unroll
             for (int r = 0; r < RW; ++r) qv[r] = fixr[r] ? xo[r] : acc[r];
-            upd_rows(yz, qv, xo, ur, ux, us);
+            upd_rows(yz, qv, xo, ur, ux, us, fix);
             return;
         }
         const auto ry = rsrc_of(yz, live && STORE && !PGD_ST_WHATIF(1));
@@ -1431,7 +1527,7 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
         if (EPI == 3) {                                                     // q = p on every row of the plane
             double ur[RW], ux[RW], us[RW];
             upd_load(yz, ur, ux, us);
-            upd_rows(yz, xo, xo, ur, ux, us);
+            upd_rows(yz, xo, xo, ur, ux, us, ~0u);
             return;
         }
         const auto ry = rsrc_of(yz, STORE);
@@ -2635,8 +2731,8 @@ int stencil_update_blocks(const Ctx *c, const Mesh *m) {
 }
 
 int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, double *r, const double *s,
-                          double *pairs, int lag) {
-    if (!stencil_whole_grid(c, m, a) || !c->flags || p_in == p_out)
+                          double *pairs, int lag, double s_free, const StencilFold *fold) {
+    if (!stencil_whole_grid(c, m, a) || !c->flags || p_in == p_out || (fold && (fold->vec_in == pairs || !fold->prod || !fold->vec_in)))
         return fail(c, PGD_ERR_INVALID, "stencil update: the operator's products do not run in the stencil march over the whole grid");
     const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
     const int nz = (int)(m->nv / plane);
@@ -2651,6 +2747,11 @@ int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_i
     F.qq = 1; F.whatif = 0; F.b = nullptr; F.w = 0.0;
     F.partials = pairs;
     F.ur = r; F.ux = x; F.us = s; F.slots = c->slots; F.lag = lag;
+    F.s_free = s_free;
+    if (fold) {
+        F.fold_prod = fold->prod; F.fold_nprod = fold->nprod; F.fold_vec = fold->vec_in; F.fold_nvec = fold->nvec;
+        F.fold_par = fold->par & 1; F.fold_flags = c->flags;
+    }
     const bool nt = c->pcg_stream_hints != 0;
     if (sh.rows_per_thread == 2) {
         if (nt) k_spmv_stencil_march<true, true, 3, true, 2, 3, 2><<<sh.wgs, 256, 0, c->stream>>>(F);
@@ -2895,6 +2996,8 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_EVAL_GRID_MAX && value >= 0 && value <= 1 << 20) { c->eval_grid_max = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_EVAL_SAMPLE_CHUNK && value >= 0 && value <= 1024) { c->eval_chunk = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_PCG_RECOMPUTE_Q && value >= 0 && value <= 1) { c->pcg_recompute_q = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_PCG_FOLD_MARCH && value >= 0 && value <= 1) { c->pcg_fold_march = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_PCG_SCALAR_S && value >= 0 && value <= 1) { c->pcg_scalar_s = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_BLOCK_STORAGE && value >= 0 && value <= 2) { c->block_storage = (int)value; return PGD_OK; }
     return fail(c, PGD_ERR_INVALID, "tune: unknown knob %d or value out of range", knob);
 }

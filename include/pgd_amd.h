@@ -450,6 +450,39 @@ int pgd_eval_batch(pgd_handle ctx, const pgd_handle *modes, int k, const double 
                    double threshold, double *sample_stats, pgd_handle env_min, pgd_handle env_max, pgd_handle exceed,
                    pgd_handle fields);
 
+/* ----------------------------------- batched evaluation of gradient quantities --- */
+/* Quantities of the spatial gradient of a P1 field - a flux magnitude, a von Mises stress - are Euclidean norms of a few
+ * components that are LINEAR in the field, and the P1 gradient is constant per cell.  Two stages: pgd_cell_gradient turns a
+ * nodal mode into q cell-wise planes, once per mode; pgd_eval_batch_norm is pgd_eval_batch on the q planes of a cell,
+ * combined with a square root before the reductions.
+ *
+ * pgd_cell_gradient: out[i*nc + cell] = scale[cell] * sum_j L[i][j] g[j], g[c*gdim + a] = d u_c / d x_a on the cell.
+ *   mesh: a P1 layout on intervals, triangles or tetrahedra, scalar or blocked (pgd_mesh_blocked: ncomp components);
+ *   u: nv*ncomp entries, node*ncomp + c;  L: host, q x (ncomp*gdim) row-major, 1 <= q <= 9;
+ *   scale: a vector of nc entries in cell order, or 0 for a scale of 1;  out: q*nc entries, plane-major.
+ * A thread per cell; the inverse Jacobian is formed from the cell's own vertices (cofactors and determinant), whatever the mesh.
+ * PGD_ERR_INVALID with a message, before anything is launched, for: a P2 layout, q out of range, a null L, wrong vector sizes,
+ * out aliasing u or scale.  nc == 0 is PGD_OK.  No atomics, no host synchronisation.                                      */
+int pgd_cell_gradient(pgd_handle ctx, pgd_handle mesh, pgd_handle u, const double *L, int q, pgd_handle scale_or_0,
+                      pgd_handle out);
+
+/* pgd_eval_batch_norm: every mode has q*m entries (q planes of m, as pgd_cell_gradient writes them); the value of entry e and
+ * sample j is v = sqrt(sum_i u_i^2) with u_i = sum_t C[t][j] modes[t][i*m + e]; the sum of squares starts from 0 and takes
+ * fma(u_i, u_i, .) over ascending i.  1 <= q <= 9; q = 1 gives |u|.  Every output has m entries (fields: m*s, sample-major),
+ * max |.| equals max.  Everything pgd_eval_batch states holds here: the argument checks (and: q out of range, mode sizes that
+ * are no multiple of q), the sample chunks, the pinned coefficient staging, one host synchronisation if and only if
+ * PGD_EVAL_STATS is set, no atomics, every output bit-identical for any grid size and chunk length, both variants of
+ * PGD_TUNE_EVAL_VARIANT.  The matrix-unit kernel keeps the q planes of a block of 64, 32 or 16 entries in LDS (up to 160 KiB
+ * for 16) and reads them from global memory where even that does not fit (q * k above about 1100): slower, same bits.
+ * Signed components need no new call: pgd_eval_batch on the one plane of a one-row L gives them.                          */
+int pgd_eval_batch_norm(pgd_handle ctx, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want,
+                        double threshold, double *sample_stats, pgd_handle env_min, pgd_handle env_max, pgd_handle exceed,
+                        pgd_handle fields);
+/* How the last pgd_eval_batch_norm call that launched laid out its work: rows = entries per workgroup (64, 32 or 16 on the matrix
+ * unit, 64 in the plain variant), staged = 1 the planes of a row block in at most 64 KiB of LDS, 2 in more (up to 160 KiB), 0 read
+ * from global memory (always in the plain variant); rows = 0, staged = -1 before the first call.                              */
+int pgd_eval_norm_last_shape(pgd_handle ctx, int *rows, int *staged);
+
 /* ------------------------------------------------------------------ tuning --- */
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */

@@ -68,6 +68,9 @@ SIGNATURES = {
     "pgd_block_dots": (C.c_int, [H, H, H, I64, I64, PD]),
     "pgd_block_combine": (C.c_int, [H, H, PD, H, H]),
     "pgd_eval_batch": (C.c_int, [H, PH, C.c_int, PD, I64, C.c_int, F64, PD, H, H, H, H]),
+    "pgd_eval_batch_norm": (C.c_int, [H, PH, C.c_int, C.c_int, PD, I64, C.c_int, F64, PD, H, H, H, H]),
+    "pgd_cell_gradient": (C.c_int, [H, H, H, PD, C.c_int, H, H]),
+    "pgd_eval_norm_last_shape": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pgd_atom_assemble": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PH]),
     "pgd_atom_assemble_cells": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PU8, I64, PH]),
     "pgd_atom_assemble_cellwise": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, H, PU8, I64, PH]),
@@ -427,6 +430,37 @@ class Context:
         self._ck(self.lib.pgd_eval_batch(self.h, arr, k, dptr(cf) if cf.size else None, s, want, float(threshold),
                                          dptr(out) if stats else None, int(env_min), int(env_max), int(exceed), int(fields)))
         return out
+
+    def eval_batch_norm(self, modes, q, coefs, stats=True, env_min=0, env_max=0, exceed=0, threshold=0.0, fields=0):
+        """pgd_eval_batch_norm: eval_batch on modes of ``q`` planes each, the value of an entry being the Euclidean norm over its
+        planes of the combined planes.  Same arguments and return value as ``eval_batch``; the outputs have len(mode) / q entries."""
+        k = len(modes)
+        cf = np.ascontiguousarray(coefs, dtype=np.float64)
+        if cf.ndim != 2 or cf.shape[0] != k:
+            raise ValueError("eval_batch_norm: coefs must have shape (len(modes), samples), got %r for %d modes" % (cf.shape, k))
+        s = cf.shape[1]
+        want = (EVAL_STATS if stats else 0) | (EVAL_ENVELOPE if (env_min or env_max) else 0) | \
+               (EVAL_EXCEED if exceed else 0) | (EVAL_FIELDS if fields else 0)
+        arr = (H * max(k, 1))(*[int(x) for x in modes])
+        out = np.empty((3, s), dtype=np.float64) if stats else None
+        self._ck(self.lib.pgd_eval_batch_norm(self.h, arr, k, int(q), dptr(cf) if cf.size else None, s, want, float(threshold),
+                                              dptr(out) if stats else None, int(env_min), int(env_max), int(exceed), int(fields)))
+        return out
+
+    def eval_norm_last_shape(self):
+        """(entries per workgroup, staged) of the last eval_batch_norm that launched; staged: 1 = the planes of a row block in at most
+        64 KiB of LDS, 2 = in more, 0 = read from global memory (pgd_eval_norm_last_shape)."""
+        rows, staged = C.c_int(), C.c_int()
+        self._ck(self.lib.pgd_eval_norm_last_shape(self.h, C.byref(rows), C.byref(staged)))
+        return rows.value, staged.value
+
+    def cell_gradient(self, mesh, u, L, out, scale=0):
+        """pgd_cell_gradient: out[i * nc + cell] = scale[cell] * sum_j L[i, j] g[j] for the P1 field ``u`` of the layout ``mesh``
+        (scalar or blocked), g[c * gdim + a] = d u_c / d x_a; ``L``: (q, ncomp * gdim); ``scale``: a vector of one entry per cell, or 0."""
+        L = np.ascontiguousarray(L, dtype=np.float64)
+        if L.ndim != 2:
+            raise ValueError("cell_gradient: L is a (q, ncomp * gdim) matrix")
+        self._ck(self.lib.pgd_cell_gradient(self.h, mesh, u, dptr(L) if L.size else None, L.shape[0], int(scale or 0), out))
 
     def vec_set(self, v, idx, val):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

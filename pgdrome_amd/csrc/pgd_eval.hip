@@ -22,6 +22,9 @@
 //
 // k_eval_plain has the same outputs and rules with ordinary fma chains over k in ascending order: the
 // cross-check of the tests and the baseline that shows what the matrix unit buys (PGD_TUNE_EVAL_VARIANT).
+//
+// Further down: the same two kernels on q planes per entry with a Euclidean norm before the reductions (pgd_eval_batch_norm),
+// and the kernel that makes such planes from a nodal P1 mode (pgd_cell_gradient).
 #include "pgd_internal.h"
 
 #include <cmath>
@@ -30,6 +33,7 @@
 namespace pgd {
 
 constexpr int EVAL_KMAX = 256;
+constexpr int EVAL_QMAX = 9;               // planes per mode of pgd_eval_batch_norm, rows of L of pgd_cell_gradient
 constexpr int EVAL_CHUNK_DEFAULT = 1024;   // samples per launch: 16 KiB of running extrema in LDS beside the <= 32 KiB mode block
 constexpr int64_t EVAL_SMAX = (int64_t)1 << 24;
 constexpr int EVAL_PLAIN_TPB = 64;         // k_eval_plain: one wave per workgroup, one row per lane
@@ -232,6 +236,231 @@ __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_plain(EvalModes M, int 
     }
 }
 
+// ---- norms of q linear quantities (pgd_eval_batch_norm): every mode is q planes of m entries, the value of entry e and sample j
+// is v = sqrt(sum_i u_i^2), u_i = sum_t C[t][j] modes[t][i m + e].  Per plane the u_i are the accumulators of k_eval_mfma /
+// k_eval_plain (one fixed chain over k each); the sum of squares starts from 0 and takes fma(u_i, u_i, .) over ascending i, so v
+// does not depend on the grid, the chunk or the row block either.  Everything after v - extrema, envelopes, counts, fields - is the
+// epilogue of the kernels above with v in the place of u.
+//
+// k_eval_norm_mfma stages the q planes of a row block (q x 4 kt x RB values) and reloads the B fragment of plane i, k-step s from
+// LDS inside the sample-tile loop (q x kt fragments do not fit the registers as the kt of k_eval_mfma do): one ds_read_b64 per MFMA,
+// rows padded to 16 (mod 32) doubles so that the two 16-lane row groups of a half wave sit on opposite halves of the bank row.
+// kt is a run-time value here.  The epilogues are copies of those above, not shared device functions: factoring them out changes
+// the instructions of k_eval_mfma and k_eval_plain, which pgd_eval_batch keeps as they were.  LDSB = false reads the fragments from global memory instead (L2: a row block's values are read by
+// every sample tile): the launcher's last resort where q planes of 16 rows do not fit 160 KiB.
+template <int T>
+struct EvalNormShape {
+    static constexpr int RB = 16 * T;
+    static constexpr int RS = RB + (T == 1 ? 0 : 16);      // row stride of the staged values in doubles
+};
+
+template <int T, bool LDSB>
+__global__ __launch_bounds__(TPB) void k_eval_norm_mfma(EvalModes M, int k, int kt, int q, int64_t n, const double *__restrict__ cf, int cs,
+                                                        int64_t j0, int want, int first, double thr, EvalOut O) {
+    extern __shared__ double s_dyn[];
+    constexpr int RB = EvalNormShape<T>::RB, RS = EvalNormShape<T>::RS;
+    const double INF = __builtin_huge_val();
+    const int kp = 4 * kt;
+    const int cs16 = (cs + 15) & ~15, ntile = cs16 >> 4;
+    double *s_f = s_dyn;                                   // q x kp rows of RS: plane i, mode t at row i kp + t
+    double *s_mn = s_f + (LDSB ? (size_t)q * kp * RS : 0);
+    double *s_mx = s_mn + cs16;
+    double *s_env = s_mx + cs16;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 15, lq = lane >> 4;
+    for (int j = threadIdx.x; j < cs16; j += TPB) { s_mn[j] = INF; s_mx[j] = -INF; }
+    const int64_t nblk = (n + RB - 1) / RB;
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t row0 = blk * RB;
+        __syncthreads();
+        if (LDSB) {
+            for (int idx = threadIdx.x; idx < q * kp * RB; idx += TPB) {
+                const int pt = idx / RB, d = idx - pt * RB;
+                const int i = pt / kp, t = pt - i * kp;
+                const int64_t row = row0 + d;
+                s_f[pt * RS + d] = (t < k && row < n) ? M.p[t][(int64_t)i * n + row] : 0.0;
+            }
+        }
+        __syncthreads();
+        bool rv[T];
+        double emn[T], emx[T];
+        int ecnt[T];
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            rv[j] = row0 + 16 * j + lr < n;
+            emn[j] = INF; emx[j] = -INF; ecnt[j] = 0;
+        }
+        for (int st = wv; st < ntile; st += 4) {
+            d4_t ss[T];
+#pragma unroll
+            for (int j = 0; j < T; ++j) ss[j] = d4_t{0.0, 0.0, 0.0, 0.0};
+            const double *cp = cf + (int64_t)st * kt * 64 + lane;
+            for (int i = 0; i < q; ++i) {
+                d4_t acc[T];
+#pragma unroll
+                for (int j = 0; j < T; ++j) acc[j] = d4_t{0.0, 0.0, 0.0, 0.0};
+                for (int s = 0; s < kt; ++s) {
+                    const double a = cp[s * 64];
+#pragma unroll
+                    for (int j = 0; j < T; ++j) {
+                        double b;
+                        if (LDSB) {
+                            b = s_f[(i * kp + 4 * s + lq) * RS + 16 * j + lr];
+                        } else {
+                            const int t = 4 * s + lq;
+                            b = (t < k && rv[j]) ? M.p[t][(int64_t)i * n + row0 + 16 * j + lr] : 0.0;
+                        }
+                        acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < T; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ss[j][r] = fma(acc[j][r], acc[j][r], ss[j][r]);
+            }
+            // lane holds the value of sample 16 st + lq + 4 r of the chunk, row row0 + 16 j + lr
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int js = 16 * st + lq + 4 * r;
+                const bool sv = js < cs;
+                double mn = INF, mx = -INF;
+#pragma unroll
+                for (int j = 0; j < T; ++j) {
+                    const double u = sqrt(ss[j][r]);
+                    if (rv[j] && sv) {
+                        mn = fmin(mn, u);
+                        mx = fmax(mx, u);
+                        emn[j] = fmin(emn[j], u);
+                        emx[j] = fmax(emx[j], u);
+                        ecnt[j] += (u > thr) ? 1 : 0;
+                        if (want & PGD_EVAL_FIELDS) O.fields[(j0 + js) * n + (row0 + 16 * j + lr)] = u;
+                    }
+                }
+                if (want & PGD_EVAL_STATS) {
+#pragma unroll
+                    for (int m = 1; m < 16; m <<= 1) {
+                        mn = fmin(mn, __shfl_xor(mn, m, 64));
+                        mx = fmax(mx, __shfl_xor(mx, m, 64));
+                    }
+                    if (lr == 0 && sv) { s_mn[js] = fmin(s_mn[js], mn); s_mx[js] = fmax(s_mx[js], mx); }
+                }
+            }
+        }
+        if (want & (PGD_EVAL_ENVELOPE | PGD_EVAL_EXCEED)) {
+#pragma unroll
+            for (int j = 0; j < T; ++j) {
+#pragma unroll
+                for (int m = 16; m < 64; m <<= 1) {
+                    emn[j] = fmin(emn[j], __shfl_xor(emn[j], m, 64));
+                    emx[j] = fmax(emx[j], __shfl_xor(emx[j], m, 64));
+                    ecnt[j] += __shfl_xor(ecnt[j], m, 64);
+                }
+                if (lq == 0) {
+                    s_env[(wv * 3 + 0) * RB + 16 * j + lr] = emn[j];
+                    s_env[(wv * 3 + 1) * RB + 16 * j + lr] = emx[j];
+                    s_env[(wv * 3 + 2) * RB + 16 * j + lr] = (double)ecnt[j];
+                }
+            }
+            __syncthreads();
+            const int d = threadIdx.x;
+            if (d < RB && row0 + d < n) {
+                double mn = INF, mx = -INF, ct = 0.0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    mn = fmin(mn, s_env[(w * 3 + 0) * RB + d]);
+                    mx = fmax(mx, s_env[(w * 3 + 1) * RB + d]);
+                    ct += s_env[(w * 3 + 2) * RB + d];
+                }
+                const int64_t row = row0 + d;
+                if (want & PGD_EVAL_ENVELOPE) {
+                    O.env_min[row] = first ? mn : fmin(O.env_min[row], mn);
+                    O.env_max[row] = first ? mx : fmax(O.env_max[row], mx);
+                }
+                if (want & PGD_EVAL_EXCEED) O.exceed[row] = first ? ct : O.exceed[row] + ct;
+            }
+        }
+    }
+    if (want & PGD_EVAL_STATS) {
+        __syncthreads();
+        for (int j = threadIdx.x; j < cs16; j += TPB) {
+            O.part[((int64_t)blockIdx.x * 2 + 0) * cs16 + j] = s_mn[j];
+            O.part[((int64_t)blockIdx.x * 2 + 1) * cs16 + j] = s_mx[j];
+        }
+    }
+}
+
+// k_eval_plain with the loop over the planes around its fma chains
+__global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_norm_plain(EvalModes M, int k, int kt, int q, int64_t n, const double *__restrict__ cf,
+                                                                    int cs, int64_t j0, int want, int first, double thr, EvalOut O) {
+    extern __shared__ double s_dyn[];
+    constexpr int NS = EVAL_PLAIN_NS;
+    const double INF = __builtin_huge_val();
+    const int cs16 = (cs + 15) & ~15;
+    double *s_mn = s_dyn, *s_mx = s_dyn + cs16;
+    const int lane = threadIdx.x;
+    for (int j = lane; j < cs16; j += EVAL_PLAIN_TPB) { s_mn[j] = INF; s_mx[j] = -INF; }
+    __syncthreads();
+    const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t row = blk * EVAL_PLAIN_TPB + lane;
+        const bool rv = row < n;
+        double emn = INF, emx = -INF, ect = 0.0;
+        for (int jb = 0; jb < cs16; jb += NS) {
+            double ss[NS];
+#pragma unroll
+            for (int c = 0; c < NS; ++c) ss[c] = 0.0;
+            for (int i = 0; i < q; ++i) {
+                double acc[NS];
+#pragma unroll
+                for (int c = 0; c < NS; ++c) acc[c] = 0.0;
+                for (int t = 0; t < k; ++t) {
+                    const double f = rv ? M.p[t][(int64_t)i * n + row] : 0.0;
+                    const double *cp = cf + eval_cf_index(kt, t, jb);
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) acc[c] = fma(cp[c], f, acc[c]);
+                }
+#pragma unroll
+                for (int c = 0; c < NS; ++c) ss[c] = fma(acc[c], acc[c], ss[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < NS; ++c) {
+                const int js = jb + c;
+                if (js >= cs) break;                 // uniform
+                const double u = sqrt(ss[c]);
+                double mn = INF, mx = -INF;
+                if (rv) {
+                    mn = mx = u;
+                    emn = fmin(emn, u);
+                    emx = fmax(emx, u);
+                    ect += (u > thr) ? 1.0 : 0.0;
+                    if (want & PGD_EVAL_FIELDS) O.fields[(j0 + js) * n + row] = u;
+                }
+                if (want & PGD_EVAL_STATS) {
+#pragma unroll
+                    for (int m = 1; m < 64; m <<= 1) {
+                        mn = fmin(mn, __shfl_xor(mn, m, 64));
+                        mx = fmax(mx, __shfl_xor(mx, m, 64));
+                    }
+                    if (lane == 0) { s_mn[js] = fmin(s_mn[js], mn); s_mx[js] = fmax(s_mx[js], mx); }
+                }
+            }
+        }
+        if (rv) {
+            if (want & PGD_EVAL_ENVELOPE) {
+                O.env_min[row] = first ? emn : fmin(O.env_min[row], emn);
+                O.env_max[row] = first ? emx : fmax(O.env_max[row], emx);
+            }
+            if (want & PGD_EVAL_EXCEED) O.exceed[row] = first ? ect : O.exceed[row] + ect;
+        }
+    }
+    if (want & PGD_EVAL_STATS) {
+        __syncthreads();
+        for (int j = lane; j < cs16; j += EVAL_PLAIN_TPB) {
+            O.part[((int64_t)blockIdx.x * 2 + 0) * cs16 + j] = s_mn[j];
+            O.part[((int64_t)blockIdx.x * 2 + 1) * cs16 + j] = s_mx[j];
+        }
+    }
+}
+
 // Final pass: sample j of the chunk takes the g workgroups' partial extrema in a fixed order (a thread per sample,
 // coalesced across samples); stats = 3 rows of s_total doubles: min, max, max |.|
 __global__ __launch_bounds__(TPB) void k_eval_finish(const double *__restrict__ part, int g, int cs, double *__restrict__ stats,
@@ -273,6 +502,54 @@ static int eval_launch_mfma(Ctx *c, const EvalModes &M, int k, int64_t n, const 
 // (the B fragments of a wave are at most 64 doubles per lane)
 static int eval_kt(int k) { return k <= 16 ? 4 : k <= 32 ? 8 : k <= 48 ? 12 : k <= 64 ? 16 : k <= 128 ? 32 : 64; }
 
+// ---- k_eval_norm_mfma: the row block and where the B fragments come from, chosen once per call
+constexpr size_t EVAL_LDS_PLAIN = 64 * 1024;      // dynamic LDS a kernel may ask for as it is; up to EVAL_LDS_MAX with the function attribute
+constexpr size_t EVAL_LDS_MAX = 160 * 1024;
+
+struct EvalNormCfg { int t = 1; bool ldsb = false; };
+
+static size_t eval_norm_lds(int t, bool ldsb, int q, int kt, int cs16) {
+    const size_t rb = 16 * (size_t)t, rs = rb + (t == 1 ? 0 : 16);
+    return ((ldsb ? (size_t)q * 4 * kt * rs : 0) + 2 * (size_t)cs16 + 12 * rb) * sizeof(double);
+}
+
+template <int T>
+static bool eval_norm_raise_lds(size_t lds) {
+    if (hipFuncSetAttribute((const void *)k_eval_norm_mfma<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// 64, 32 or 16 rows per workgroup, the largest whose q planes fit 64 KiB beside the extrema; else 16 rows in up to 160 KiB (the
+// function attribute is raised for it); else 16 rows with the fragments read from global memory
+static EvalNormCfg eval_norm_choose(int q, int kt, int cs16_max) {
+    EvalNormCfg cfg;
+    for (int t = 4; t >= 1; t >>= 1)
+        if (eval_norm_lds(t, true, q, kt, cs16_max) <= EVAL_LDS_PLAIN) { cfg.t = t; cfg.ldsb = true; return cfg; }
+    const size_t lds = eval_norm_lds(1, true, q, kt, cs16_max);
+    if (lds <= EVAL_LDS_MAX && eval_norm_raise_lds<1>(lds)) cfg.ldsb = true;
+    return cfg;
+}
+
+template <int T, bool LDSB>
+static int eval_launch_norm(Ctx *c, const EvalModes &M, int k, int kt, int q, int64_t n, const double *cf, int cs, int64_t j0, int want,
+                            int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
+    const size_t lds = eval_norm_lds(T, LDSB, q, kt, (cs + 15) & ~15);
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_eval_norm_mfma<T, LDSB>, TPB, lds) != hipSuccess || occ < 1) {
+        (void)hipGetLastError();
+        occ = 1;
+    }
+    const int64_t nblk = (n + 16 * T - 1) / (16 * T);
+    int64_t g = (int64_t)c->num_cu * occ;
+    if (g > grid_cap) g = grid_cap;
+    if (g > nblk) g = nblk;
+    k_eval_norm_mfma<T, LDSB><<<(int)g, TPB, lds, c->stream>>>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O);
+    PGD_LAUNCH_CHECK(c);
+    *grid_out = (int)g;
+    return PGD_OK;
+}
+
 static size_t eval_round(size_t bytes) { return (bytes + 65535) & ~(size_t)65535; }   // (whole 64 KiB: the pool takes them back)
 
 void eval_release(Ctx *c) {
@@ -286,64 +563,150 @@ void eval_release(Ctx *c) {
     }
 }
 
+// ---- pgd_cell_gradient: a nodal P1 mode to q cell-wise planes, out[i nc + e] = scale[e] sum_j L[i][j] g[j] with
+// g[c G + a] = d u_c / d x_a on cell e (constant there).  A thread per cell: the int4 record, the vertices' coordinates (SoA) and
+// the (G + 1) NC nodal values are gathered, the inverse of the edge matrix comes from its cofactors and determinant in registers -
+// nothing is taken from the lattice description, so any mesh the layout accepts is right.  With x = x_0 + E^T xi (row a of E: the
+// edge x_{a+1} - x_0) the basis function of vertex a + 1 is xi_a, so d u / d x_d = sum_a (u_{a+1} - u_0) inv(E^T)[a][d].
+// L arrives by value.  No atomics; the stores of a plane are coalesced.
+struct GradL { double a[EVAL_QMAX * EVAL_QMAX]; };      // row-major q x qin
+
+template <int G, int NC>
+__global__ __launch_bounds__(TPB) void k_cell_gradient(const int4 *__restrict__ cells, const double *__restrict__ coords, int64_t nv, int64_t nc,
+                                                       const double *__restrict__ u, GradL L, int q, const double *__restrict__ scale,
+                                                       double *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (e >= nc) return;
+    const int4 rec = cells[e];
+    const int v[4] = {rec.x, rec.y, rec.z, rec.w};
+    double E[G][G];                                  // E[a][d] = x_{a+1}[d] - x_0[d]
+#pragma unroll
+    for (int d = 0; d < G; ++d) {
+        const double *x = coords + (int64_t)d * nv;
+        const double x0 = x[v[0]];
+#pragma unroll
+        for (int a = 0; a < G; ++a) E[a][d] = x[v[a + 1]] - x0;
+    }
+    double J[G][G];                                  // J[a][d] = d xi_a / d x_d: the inverse of E^T
+    if constexpr (G == 1) {
+        J[0][0] = 1.0 / E[0][0];
+    } else if constexpr (G == 2) {
+        const double inv = 1.0 / (E[0][0] * E[1][1] - E[0][1] * E[1][0]);
+        J[0][0] = E[1][1] * inv;  J[0][1] = -E[1][0] * inv;
+        J[1][0] = -E[0][1] * inv; J[1][1] = E[0][0] * inv;
+    } else {
+        double C[3][3];                              // cofactor of E[a][d]
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int a1 = (a + 1) % 3, a2 = (a + 2) % 3;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const int d1 = (d + 1) % 3, d2 = (d + 2) % 3;
+                C[a][d] = E[a1][d1] * E[a2][d2] - E[a1][d2] * E[a2][d1];
+            }
+        }
+        const double inv = 1.0 / (E[0][0] * C[0][0] + E[0][1] * C[0][1] + E[0][2] * C[0][2]);
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) J[a][d] = C[a][d] * inv;      // inv(E)[d][a] = C[a][d] / det, and J = inv(E^T) = inv(E)^T
+    }
+    double g[NC * G];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const double u0 = u[(int64_t)v[0] * NC + c];
+        double du[G];
+#pragma unroll
+        for (int a = 0; a < G; ++a) du[a] = u[(int64_t)v[a + 1] * NC + c] - u0;
+#pragma unroll
+        for (int d = 0; d < G; ++d) {
+            double acc = du[0] * J[0][d];
+#pragma unroll
+            for (int a = 1; a < G; ++a) acc = fma(du[a], J[a][d], acc);
+            g[c * G + d] = acc;
+        }
+    }
+    const double sc = scale ? scale[e] : 1.0;
+    for (int i = 0; i < q; ++i) {
+        const double *row = L.a + i * (NC * G);
+        double acc = row[0] * g[0];
+#pragma unroll
+        for (int j = 1; j < NC * G; ++j) acc = fma(row[j], g[j], acc);
+        out[(int64_t)i * nc + e] = sc * acc;
+    }
+}
+
+template <int G, int NC>
+static void cell_gradient_launch(Ctx *c, const Mesh *b, const double *u, const GradL &L, int q, const double *scale, double *out) {
+    const int grid = (int)((b->nc + TPB - 1) / TPB);
+    k_cell_gradient<G, NC><<<grid, TPB, 0, c->stream>>>(b->cells, b->coords, b->nv, b->nc, u, L, q, scale, out);
+}
+
 }  // namespace pgd
 
 using namespace pgd;
 
 extern "C" {
 
-int pgd_eval_batch(pgd_handle h, const pgd_handle *modes, int k, const double *coefs, int64_t s, int want, double threshold,
-                   double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
-    PGD_CTX(c, h);
+// The body of pgd_eval_batch (q == 0: the signed values, k_eval_mfma / k_eval_plain) and of pgd_eval_batch_norm (1 <= q <= 9: every
+// mode is q planes, the norm kernels): the checks, the chunking and the coefficient staging are the same, only the launch differs.
+// fn: the entry point's name for the messages.
+static int eval_batch_run(Ctx *c, const char *fn, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want,
+                          double threshold, double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h,
+                          pgd_handle fields_h) {
     // ---- every argument is checked before anything is launched
-    if (k < 1 || k > EVAL_KMAX) return fail(c, PGD_ERR_INVALID, "eval_batch: k = %d modes, 1 .. %d are possible", k, EVAL_KMAX);
-    if (s < 1 || s > EVAL_SMAX) return fail(c, PGD_ERR_INVALID, "eval_batch: s = %lld samples, 1 .. 2^24 are possible", (long long)s);
-    if (!modes || !coefs) return fail(c, PGD_ERR_INVALID, "eval_batch: modes or coefficients missing");
-    if (want < 1 || want > 15) return fail(c, PGD_ERR_INVALID, "eval_batch: want = %d names no output (bits 1, 2, 4, 8)", want);
+    if (k < 1 || k > EVAL_KMAX) return fail(c, PGD_ERR_INVALID, "%s: k = %d modes, 1 .. %d are possible", fn, k, EVAL_KMAX);
+    if (s < 1 || s > EVAL_SMAX) return fail(c, PGD_ERR_INVALID, "%s: s = %lld samples, 1 .. 2^24 are possible", fn, (long long)s);
+    if (!modes || !coefs) return fail(c, PGD_ERR_INVALID, "%s: modes or coefficients missing", fn);
+    if (want < 1 || want > 15) return fail(c, PGD_ERR_INVALID, "%s: want = %d names no output (bits 1, 2, 4, 8)", fn, want);
     EvalModes M;
     std::vector<Vec *> mv((size_t)k);
     int64_t n = 0;
     for (int t = 0; t < k; ++t) {
         mv[t] = get_vec(c, modes[t]);
-        if (!mv[t]) return fail(c, PGD_ERR_INVALID, "eval_batch: mode %d is not a vector", t);
+        if (!mv[t]) return fail(c, PGD_ERR_INVALID, "%s: mode %d is not a vector", fn, t);
         if (t == 0) n = mv[t]->n;
-        if (mv[t]->n != n) return fail(c, PGD_ERR_INVALID, "eval_batch: mode %d has %lld entries, mode 0 has %lld", t, (long long)mv[t]->n, (long long)n);
+        if (mv[t]->n != n) return fail(c, PGD_ERR_INVALID, "%s: mode %d has %lld entries, mode 0 has %lld", fn, t, (long long)mv[t]->n, (long long)n);
         M.p[t] = mv[t]->d;
     }
     for (int t = k; t < EVAL_KMAX; ++t) M.p[t] = nullptr;
+    if (q > 0) {                                     // q planes of n entries each
+        if (n % q) return fail(c, PGD_ERR_INVALID, "%s: the modes have %lld entries, no multiple of q = %d", fn, (long long)n, q);
+        n /= q;
+    }
     if ((want & PGD_EVAL_STATS) ? !sample_stats : sample_stats != nullptr)
-        return fail(c, PGD_ERR_INVALID, "eval_batch: sample_stats %s", sample_stats ? "passed but not requested (bit 1)" : "requested (bit 1) but missing");
+        return fail(c, PGD_ERR_INVALID, "%s: sample_stats %s", fn, sample_stats ? "passed but not requested (bit 1)" : "requested (bit 1) but missing");
     Vec *outs[4] = {nullptr, nullptr, nullptr, nullptr};
     const pgd_handle oh[4] = {env_min_h, env_max_h, exceed_h, fields_h};
     const int obit[4] = {PGD_EVAL_ENVELOPE, PGD_EVAL_ENVELOPE, PGD_EVAL_EXCEED, PGD_EVAL_FIELDS};
     static const char *const oname[4] = {"env_min", "env_max", "exceed", "fields"};
     for (int i = 0; i < 4; ++i) {
         if (!(want & obit[i])) {
-            if (oh[i] != 0) return fail(c, PGD_ERR_INVALID, "eval_batch: %s passed but not requested (bit %d)", oname[i], obit[i]);
+            if (oh[i] != 0) return fail(c, PGD_ERR_INVALID, "%s: %s passed but not requested (bit %d)", fn, oname[i], obit[i]);
             continue;
         }
         outs[i] = get_vec(c, oh[i]);
-        if (!outs[i]) return fail(c, PGD_ERR_INVALID, "eval_batch: %s requested (bit %d) but missing or not a vector", oname[i], obit[i]);
+        if (!outs[i]) return fail(c, PGD_ERR_INVALID, "%s: %s requested (bit %d) but missing or not a vector", fn, oname[i], obit[i]);
         int64_t need = n;
         if (i == 3) {
             if (n > 0 && s > std::numeric_limits<int64_t>::max() / 8 / n)
-                return fail(c, PGD_ERR_INVALID, "eval_batch: s * n = %lld * %lld overflows the fields vector", (long long)s, (long long)n);
+                return fail(c, PGD_ERR_INVALID, "%s: s * n = %lld * %lld overflows the fields vector", fn, (long long)s, (long long)n);
             need = n * s;
         }
         if (outs[i]->n != need)
-            return fail(c, PGD_ERR_INVALID, "eval_batch: %s has %lld entries, %lld are needed", oname[i], (long long)outs[i]->n, (long long)need);
+            return fail(c, PGD_ERR_INVALID, "%s: %s has %lld entries, %lld are needed", fn, oname[i], (long long)outs[i]->n, (long long)need);
         for (int t = 0; t < k; ++t)
-            if (mv[t] == outs[i]) return fail(c, PGD_ERR_INVALID, "eval_batch: mode %d aliases %s", t, oname[i]);
+            if (mv[t] == outs[i]) return fail(c, PGD_ERR_INVALID, "%s: mode %d aliases %s", fn, t, oname[i]);
         for (int i2 = 0; i2 < i; ++i2)
-            if (outs[i2] == outs[i]) return fail(c, PGD_ERR_INVALID, "eval_batch: %s aliases %s", oname[i], oname[i2]);
+            if (outs[i2] == outs[i]) return fail(c, PGD_ERR_INVALID, "%s: %s aliases %s", fn, oname[i], oname[i2]);
     }
     if (!(want & PGD_EVAL_EXCEED) && threshold != 0.0)
-        return fail(c, PGD_ERR_INVALID, "eval_batch: a threshold without the exceedance output (bit 4)");
-    if (threshold != threshold) return fail(c, PGD_ERR_INVALID, "eval_batch: the threshold is NaN");
+        return fail(c, PGD_ERR_INVALID, "%s: a threshold without the exceedance output (bit 4)", fn);
+    if (threshold != threshold) return fail(c, PGD_ERR_INVALID, "%s: the threshold is NaN", fn);
     if (n == 0) return PGD_OK;
 
     const bool mfma = c->eval_variant != 0;
-    const int kt = mfma ? eval_kt(k) : (k + 3) / 4;
+    const int kt = (mfma && q == 0) ? eval_kt(k) : (k + 3) / 4;
     int64_t chunk = c->eval_chunk > 0 ? c->eval_chunk : EVAL_CHUNK_DEFAULT;
     if (chunk > s) chunk = s;
     const int cs16_max = (int)((chunk + 15) & ~(int64_t)15);
@@ -383,6 +746,13 @@ int pgd_eval_batch(pgd_handle h, const pgd_handle *modes, int k, const double *c
     };
     if (rc != PGD_OK) { release(); return rc; }
 
+    EvalNormCfg ncfg;
+    if (mfma && q > 0) ncfg = eval_norm_choose(q, kt, cs16_max);
+    if (q > 0) {
+        c->eval_norm_rows = mfma ? 16 * ncfg.t : EVAL_PLAIN_TPB;
+        c->eval_norm_staged = !mfma ? 0 : !ncfg.ldsb ? 0 : eval_norm_lds(ncfg.t, true, q, kt, cs16_max) > EVAL_LDS_PLAIN ? 2 : 1;
+    }
+
     EvalOut O;
     O.part = (double *)p_part;
     O.env_min = outs[0] ? outs[0]->d : nullptr;
@@ -411,7 +781,12 @@ int pgd_eval_batch(pgd_handle h, const pgd_handle *modes, int k, const double *c
             const double *cf = (const double *)p_cf;
             const int first = j0 == 0;
             int g = 0;
-            if (mfma) {
+            if (mfma && q > 0) {
+                if (!ncfg.ldsb) PGD_TRY((eval_launch_norm<1, false>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
+                else if (ncfg.t == 4) PGD_TRY((eval_launch_norm<4, true>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
+                else if (ncfg.t == 2) PGD_TRY((eval_launch_norm<2, true>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
+                else PGD_TRY((eval_launch_norm<1, true>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
+            } else if (mfma) {
                 switch (kt) {
                     case 4: PGD_TRY((eval_launch_mfma<4, 4>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g))); break;
                     case 8: PGD_TRY((eval_launch_mfma<8, 4>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g))); break;
@@ -423,8 +798,12 @@ int pgd_eval_batch(pgd_handle h, const pgd_handle *modes, int k, const double *c
             } else {
                 const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
                 g = (int)(nblk < gmax ? nblk : gmax);
-                k_eval_plain<<<g, EVAL_PLAIN_TPB, (size_t)2 * cs16 * sizeof(double), c->stream>>>(M, k, kt, n, cf, cs, j0, want, first,
-                                                                                                 threshold, O);
+                if (q > 0)
+                    k_eval_norm_plain<<<g, EVAL_PLAIN_TPB, (size_t)2 * cs16 * sizeof(double), c->stream>>>(M, k, kt, q, n, cf, cs, j0, want,
+                                                                                                          first, threshold, O);
+                else
+                    k_eval_plain<<<g, EVAL_PLAIN_TPB, (size_t)2 * cs16 * sizeof(double), c->stream>>>(M, k, kt, n, cf, cs, j0, want, first,
+                                                                                                     threshold, O);
                 PGD_LAUNCH_CHECK(c);
             }
             if (want & PGD_EVAL_STATS) {
@@ -441,6 +820,68 @@ int pgd_eval_batch(pgd_handle h, const pgd_handle *modes, int k, const double *c
     rc = run();
     release();
     return rc;
+}
+
+int pgd_eval_batch(pgd_handle h, const pgd_handle *modes, int k, const double *coefs, int64_t s, int want, double threshold,
+                   double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
+    PGD_CTX(c, h);
+    return eval_batch_run(c, "eval_batch", modes, k, 0, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
+}
+
+int pgd_eval_batch_norm(pgd_handle h, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want, double threshold,
+                        double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
+    PGD_CTX(c, h);
+    if (q < 1 || q > EVAL_QMAX) return fail(c, PGD_ERR_INVALID, "eval_batch_norm: q = %d planes, 1 .. %d are possible", q, EVAL_QMAX);
+    return eval_batch_run(c, "eval_batch_norm", modes, k, q, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
+                          fields_h);
+}
+
+int pgd_eval_norm_last_shape(pgd_handle h, int *rows, int *staged) {
+    PGD_CTX(c, h);
+    if (!rows || !staged) return fail(c, PGD_ERR_INVALID, "eval_norm_last_shape: null output");
+    *rows = c->eval_norm_rows;
+    *staged = c->eval_norm_staged;
+    return PGD_OK;
+}
+
+int pgd_cell_gradient(pgd_handle h, pgd_handle mh, pgd_handle uh, const double *L, int q, pgd_handle scale_h, pgd_handle out_h) {
+    PGD_CTX(c, h);
+    Mesh *m = get_mesh(c, mh);
+    if (!m) return fail(c, PGD_ERR_INVALID, "cell_gradient: invalid mesh handle");
+    Mesh *b = m->ncomp > 1 ? get_mesh(c, m->base) : m;          // the scalar layout holds the cells and the coordinates
+    if (!b) return fail(c, PGD_ERR_INVALID, "cell_gradient: the blocked layout's base is gone");
+    const int G = b->gdim, NC = m->ncomp;
+    if (b->nvpc != G + 1) return fail(c, PGD_ERR_INVALID, "cell_gradient: a P2 layout (%d nodes per cell): P1 only", b->nvpc);
+    if (!b->cells || !b->coords) return fail(c, PGD_ERR_INVALID, "cell_gradient: the layout has no cell records");
+    if (q < 1 || q > EVAL_QMAX) return fail(c, PGD_ERR_INVALID, "cell_gradient: q = %d rows of L, 1 .. %d are possible", q, EVAL_QMAX);
+    if (!L) return fail(c, PGD_ERR_INVALID, "cell_gradient: L is missing");
+    Vec *u = get_vec(c, uh), *out = get_vec(c, out_h), *scale = scale_h ? get_vec(c, scale_h) : nullptr;
+    if (!u || u->n != b->nv * NC)
+        return fail(c, PGD_ERR_INVALID, "cell_gradient: u is a vector of %lld entries (nodes x components)", (long long)(b->nv * NC));
+    if (!out || out->n != (int64_t)q * b->nc)
+        return fail(c, PGD_ERR_INVALID, "cell_gradient: out is a vector of q * cells = %lld entries", (long long)((int64_t)q * b->nc));
+    if (scale_h && (!scale || scale->n != b->nc))
+        return fail(c, PGD_ERR_INVALID, "cell_gradient: scale is a vector of one entry per cell (%lld), or 0", (long long)b->nc);
+    if (out == u || out == scale) return fail(c, PGD_ERR_INVALID, "cell_gradient: out aliases %s", out == u ? "u" : "scale");
+    if (b->nc == 0) return PGD_OK;
+    GradL Lv;
+    const int qin = NC * G;
+    for (int i = 0; i < EVAL_QMAX * EVAL_QMAX; ++i) Lv.a[i] = i < q * qin ? L[i] : 0.0;
+    const double *sp = scale ? scale->d : nullptr;
+    switch (G * 10 + NC) {
+        case 11: cell_gradient_launch<1, 1>(c, b, u->d, Lv, q, sp, out->d); break;
+        case 12: cell_gradient_launch<1, 2>(c, b, u->d, Lv, q, sp, out->d); break;
+        case 13: cell_gradient_launch<1, 3>(c, b, u->d, Lv, q, sp, out->d); break;
+        case 21: cell_gradient_launch<2, 1>(c, b, u->d, Lv, q, sp, out->d); break;
+        case 22: cell_gradient_launch<2, 2>(c, b, u->d, Lv, q, sp, out->d); break;
+        case 23: cell_gradient_launch<2, 3>(c, b, u->d, Lv, q, sp, out->d); break;
+        case 31: cell_gradient_launch<3, 1>(c, b, u->d, Lv, q, sp, out->d); break;
+        case 32: cell_gradient_launch<3, 2>(c, b, u->d, Lv, q, sp, out->d); break;
+        case 33: cell_gradient_launch<3, 3>(c, b, u->d, Lv, q, sp, out->d); break;
+        default: return fail(c, PGD_ERR_INVALID, "cell_gradient: gdim = %d with %d components", G, NC);
+    }
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
 }
 
 }  // extern "C"

@@ -312,6 +312,7 @@ struct Ctx {
     // pgd_eval_batch (pgd_eval.hip): kernel variant (1 MFMA, 0 plain fma chains), grid cap and samples per launch (0: the launcher's choice);
     // the pinned staging of the coefficients in fragment order, two chunks deep, with the events behind the copies
     int eval_variant = 1, eval_grid_max = 0, eval_chunk = 0;
+    int eval_norm_rows = 0, eval_norm_staged = -1;   // what the last pgd_eval_batch_norm ran with (pgd_eval_norm_last_shape)
     double *eval_pin = nullptr;
     size_t eval_pin_bytes = 0;
     hipEvent_t eval_ev[2] = {nullptr, nullptr};

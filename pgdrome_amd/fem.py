@@ -1938,6 +1938,38 @@ def point_gradient(f, x):
     return dN.T @ f._vec.host()[nodes]
 
 
+def gradient_quantity(name, gdim, ncomp):
+    """The matrix L (q x ncomp * gdim) of a gradient quantity: the quantity is the Euclidean norm of L g, with
+    g[c * gdim + a] = d u_c / d x_a the (cell-wise constant) gradient of a P1 field of ``ncomp`` components.
+
+    "gradient_norm": L is the identity - |grad u| of a scalar field, the Frobenius norm of the gradient of a vector field.
+    "von_mises": ncomp == gdim in (2, 3); the rows are sqrt(3 / 2) times s_xx, s_yy, s_zz, sqrt(2) s_xy (, sqrt(2) s_yz,
+    sqrt(2) s_xz) of the strain deviator s = eps - tr(eps) / 3 I, in 2-D for plane strain (eps_zz = 0, s_zz = -tr(eps) / 3, as
+    problems._voigt_C has it).  The stress deviator is 2 mu s, so the von Mises stress is 2 mu = E / (1 + nu) times the
+    quantity: the material enters through the ``scale`` alone, Lame's lambda drops out."""
+    gdim, ncomp = int(gdim), int(ncomp)
+    if gdim not in (1, 2, 3) or ncomp not in (1, 2, 3):
+        raise ValueError("gradient_quantity: gdim and ncomp are 1, 2 or 3, got %r and %r" % (gdim, ncomp))
+    qin = gdim * ncomp
+    if name == "gradient_norm":
+        return np.eye(qin)
+    if name == "von_mises":
+        if ncomp != gdim or gdim < 2:
+            raise ValueError("gradient_quantity: von_mises needs a displacement field, ncomp == gdim in (2, 3), got gdim = %d, "
+                             "ncomp = %d" % (gdim, ncomp))
+        G = gdim
+        eps = np.zeros((3, 3, qin))                   # eps[a, b] as a row over g
+        for a in range(G):
+            for b in range(G):
+                eps[a, b, a * G + b] += 0.5
+                eps[a, b, b * G + a] += 0.5
+        tr = eps[0, 0] + eps[1, 1] + eps[2, 2]
+        rows = [eps[a, a] - tr / 3.0 for a in range(3)]
+        rows += [math.sqrt(2.0) * eps[a, b] for a, b in (((0, 1),) if G == 2 else ((0, 1), (1, 2), (0, 2)))]
+        return math.sqrt(1.5) * np.array(rows)
+    raise ValueError("gradient_quantity: unknown quantity %r ('gradient_norm', 'von_mises')" % (name,))
+
+
 class DerivativeFunction:
     """d f / d x_axis of a scalar Function as a callable of the point."""
 

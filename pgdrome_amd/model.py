@@ -122,6 +122,42 @@ class _FieldStore:
             pass
 
 
+class _GradientModes:
+    """The cell-wise planes of the fixed dimension's modes for one gradient quantity (``PGD.evaluate_gradient_many``): on the
+    device one library vector of q * cells doubles per mode (``pgd_cell_gradient``), freed with this object; on the host one
+    array (q, cells, K).  ``key`` says what they were built from."""
+
+    def __init__(self, key, be, mesh, V, modes, L, scale_vec):
+        self.key, self.be, self.planes = key, be, []
+        q, nc, ncomp = L.shape[0], mesh.num_cells(), V._ncomp
+        if be is not None:
+            sc = scale_vec.dev() if scale_vec is not None else 0
+            for m in modes:
+                out = be.vec_zeros(q * nc)
+                self.planes.append(out)
+                be.cell_gradient(V._lay.handle(), m.vector().dev(), L, out, sc)
+            return
+        X, cells = mesh.coordinates(), mesh.cells()
+        G = cells.shape[1] - 1
+        Einv = np.linalg.inv(X[cells[:, 1:]] - X[cells[:, :1]])                  # rows of E: the edges x_a - x_0; (cells, d, a)
+        sc = scale_vec.host() if scale_vec is not None else None
+        P = np.empty((q, nc, len(modes)))
+        for k, m in enumerate(modes):
+            U = m.vector().host().reshape(-1, ncomp)                              # vertex order, (node, component)
+            dU = U[cells[:, 1:]] - U[cells[:, :1]]                                # (cells, a, c)
+            g = np.einsum("eda,eac->ecd", Einv, dU).reshape(nc, ncomp * G)        # g[c * G + d] = d u_c / d x_d
+            P[:, :, k] = L @ g.T if sc is None else (L @ g.T) * sc
+        self.planes = P
+
+    def __del__(self):
+        if self.be is not None:
+            for h in self.planes:
+                try:
+                    self.be.vec_free(h)
+                except Exception:
+                    pass
+
+
 class _FieldSlice(fem.Vector):
     """Vector of one sample's field: a view into the ``_FieldStore`` until somebody reads or writes it (then an ordinary
     Vector with its own storage)."""
@@ -721,6 +757,147 @@ class PGD:
             if as_arrays:
                 return a.reshape(att.data[0].shape)
             f = fem.Function(V)
+            f.vector()._host = np.array(a, dtype=np.float64)
+            f.vector().touched_host()
+            return f
+        if envelope:
+            res.envelope_min, res.envelope_max = wrap(emn), wrap(emx)
+        if thr is not None:
+            res.exceedance = wrap(cnt / S)
+        if fields:
+            res.fields = [wrap(a) for a in all_fields]
+        return res
+
+    # ------------------------------------------------- batched evaluation of gradient quantities
+    def evaluate_gradient_many(self, fixed_dim, free_dim, coords, attri, quantity="gradient_norm", scale=None, stats=True,
+                               envelope=False, threshold=None, fields=False, fields_max_bytes=4 << 30, modes_max_bytes=16 << 30,
+                               sample_chunk=256):
+        """``evaluate_many`` for a quantity of the spatial gradient of the solution: per cell of the fixed mesh and per sample
+        the value ``scale * |L grad u|`` with L = ``fem.gradient_quantity(quantity, ...)`` - "gradient_norm" (with a conductivity
+        as ``scale``: the flux magnitude) or "von_mises" (with ``scale`` = 2 mu = E / (1 + nu): the von Mises stress).  ``scale``:
+        None, a float or a DG0 Function of the fixed mesh.
+
+        The P1 gradient is constant per cell and linear in the mode, so every mode is turned ONCE into q = len(L) cell-wise
+        planes (``pgd_cell_gradient``; q * cells * 8 bytes per mode, refused above ``modes_max_bytes``) and kept on the attribute
+        until the quantity, the number of used modes, the modes or the ``scale`` (its identity or its vector's version) change;
+        a sample batch is then the dense product on the planes with a square root before the reductions
+        (``pgd_eval_batch_norm``).  Device or host as ``evaluate_many`` decides, with the cell count in the place of the dofs;
+        the host path is numpy, ``sample_chunk`` samples at a time.
+
+        Returns an ``EvalManyResult`` whose Functions live on ``FunctionSpace(mesh, "DG", 0)`` of the fixed mesh; ``max_abs``
+        equals ``max``.  Signed components (one row of L, no norm) are ``evaluate_many``-like fields of one plane:
+        ``pgd_eval_batch`` on the output of ``pgd_cell_gradient`` gives them."""
+        coords = self._check_many(fixed_dim, free_dim, coords, attri)
+        S = coords.shape[0]
+        att = self.mesh[fixed_dim].attributes[attri]
+        if self.mesh[free_dim[0]].attributes[attri].interpolationInfo["name"] == 0:
+            raise ValueError("evaluate_gradient_many: the interp1d mode keeps the fixed modes as arrays of vertex values, "
+                             "without the mesh a gradient needs")
+        K = self.used_numModes
+        modes = att.interpolationfct
+        if not all(isinstance(m, fem.Function) for m in modes[:K]):
+            raise ValueError("evaluate_gradient_many: the fixed dimension's modes are not Functions")
+        V = modes[0].function_space()
+        if V._dg0 or V._lay.degree != 1:
+            raise NotImplementedError("evaluate_gradient_many: P1 modes only (the gradient of a P2 mode is not constant per cell)")
+        lay = V._lay.base if V._ncomp > 1 else V._lay
+        mesh = V.mesh()
+        if mesh.part is not None or getattr(lay, "part", None) is not None:
+            raise NotImplementedError("evaluate_gradient_many on a row-sharded fixed dimension (every rank holds a slab of the "
+                                      "modes; the per-sample statistics would need a reduction across ranks)")
+        L = fem.gradient_quantity(quantity, mesh.geometry().dim(), V._ncomp)
+        scale_vec = None
+        if isinstance(scale, fem.Function):
+            Vs = scale.function_space()
+            if not Vs._dg0 or Vs.mesh() is not mesh:
+                raise ValueError("evaluate_gradient_many: scale must be a DG0 Function on the mesh of the fixed dimension")
+            scale_vec = scale.vector()
+            scale_key = (id(scale_vec), scale_vec.version)
+        elif scale is None:
+            scale_key = None
+        else:
+            scale_key = float(scale)
+            L = L * scale_key
+        q, nc = L.shape[0], mesh.num_cells()
+        if K * q * nc * 8 > modes_max_bytes:
+            raise ValueError("evaluate_gradient_many: the derived modes would take %d bytes (%d modes x %d planes x %d cells x "
+                             "8), more than modes_max_bytes=%d" % (K * q * nc * 8, K, q, nc, modes_max_bytes))
+        if fields and nc * S * 8 > fields_max_bytes:
+            raise ValueError("evaluate_gradient_many: fields=True would store %d bytes (%d cells x %d samples x 8), more than "
+                             "fields_max_bytes=%d" % (nc * S * 8, nc, S, fields_max_bytes))
+        thr = None if threshold is None else float(threshold)
+        C = self.mode_factors_many(free_dim, coords, attri)
+        res = EvalManyResult()
+        res.coefficients = C
+        be = fem.get_backend()
+        device = nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "eval_batch_norm") and hasattr(be, "cell_gradient")
+        key = (quantity, K, scale_key, device, id(be), tuple((id(m.vector()), m.vector().version) for m in modes[:K]))
+        cache = getattr(att, "_gradient_modes", None)
+        if cache is None or cache.key != key:
+            att._gradient_modes = None                       # the old planes go before the new ones are allocated
+            cache = att._gradient_modes = _GradientModes(key, be if device else None, mesh, V, modes[:K], L, scale_vec)
+            fem.STATS["gradient_mode_builds"] = fem.STATS.get("gradient_mode_builds", 0) + 1
+        Vc = fem.FunctionSpace(mesh, "DG", 0)
+        if device:
+            def out_function():
+                f = fem.Function(Vc)
+                return f, f.vector().dev_for_write()
+            kw = {}
+            if envelope:
+                (res.envelope_min, kw["env_min"]), (res.envelope_max, kw["env_max"]) = out_function(), out_function()
+            if thr is not None:
+                (res.exceedance, kw["exceed"]), kw["threshold"] = out_function(), thr
+            if fields:
+                res._fields_owner = _FieldStore(be, nc, S)
+                kw["fields"] = res._fields_owner.handle
+            st = be.eval_batch_norm(cache.planes, q, C, stats=bool(stats), **kw)
+            fem.STATS["eval_gradient_calls"] = fem.STATS.get("eval_gradient_calls", 0) + 1
+            if stats:
+                res.min, res.max, res.max_abs = st[0], st[1], st[2]
+            for f in (res.envelope_min, res.envelope_max, res.exceedance):
+                if f is not None:
+                    f.vector().touched_dev()
+            if thr is not None:
+                v = res.exceedance.vector()
+                v._host = v.host() / S                  # counts -> fraction (exactly count / S, as the host path has it)
+                v.touched_host()
+            if fields:
+                res.fields = []
+                for j in range(S):
+                    f = fem.Function(Vc)
+                    f._vec = _FieldSlice(Vc, res._fields_owner, j)
+                    res.fields.append(f)
+            return res
+        # ---- host path: the same outputs in numpy, sample_chunk columns at a time
+        P = cache.planes                                    # (q, cells, K)
+        if stats:
+            res.min, res.max = np.empty(S), np.empty(S)
+        emn, emx = np.full(nc, np.inf), np.full(nc, -np.inf)
+        cnt = np.zeros(nc)
+        all_fields = []
+        step = max(1, int(sample_chunk))
+        for j0 in range(0, S, step):
+            Cc = C[:, j0:j0 + step]
+            ss = np.zeros((nc, Cc.shape[1]))
+            for i in range(q):
+                U = P[i] @ Cc
+                ss += U * U
+            Vn = np.sqrt(ss)                                 # (cells, cs)
+            if stats:
+                sl = slice(j0, j0 + Vn.shape[1])
+                res.min[sl], res.max[sl] = Vn.min(axis=0), Vn.max(axis=0)
+            if envelope:
+                np.minimum(emn, Vn.min(axis=1), out=emn)
+                np.maximum(emx, Vn.max(axis=1), out=emx)
+            if thr is not None:
+                cnt += (Vn > thr).sum(axis=1)
+            if fields:
+                all_fields.extend(np.ascontiguousarray(Vn[:, j]) for j in range(Vn.shape[1]))
+        if stats:
+            res.max_abs = res.max.copy()
+
+        def wrap(a):
+            f = fem.Function(Vc)
             f.vector()._host = np.array(a, dtype=np.float64)
             f.vector().touched_host()
             return f

@@ -414,38 +414,32 @@ class Context:
         cf = np.ascontiguousarray(coefs, dtype=np.float64)
         self._ck(self.lib.pgd_vec_lincomb_inplace(self.h, y, arr, dptr(cf) if k else None, k))
 
+    def _eval_batch(self, name, fn, q, modes, coefs, stats, env_min, env_max, exceed, threshold, fields):
+        """The marshalling of ``eval_batch`` (``q`` = ()) and ``eval_batch_norm`` (``q`` = (planes,)): ``fn`` takes ``q`` after k."""
+        k = len(modes)
+        cf = np.ascontiguousarray(coefs, dtype=np.float64)
+        if cf.ndim != 2 or cf.shape[0] != k:
+            raise ValueError("%s: coefs must have shape (len(modes), samples), got %r for %d modes" % (name, cf.shape, k))
+        s = cf.shape[1]
+        want = (EVAL_STATS if stats else 0) | (EVAL_ENVELOPE if (env_min or env_max) else 0) | \
+               (EVAL_EXCEED if exceed else 0) | (EVAL_FIELDS if fields else 0)
+        arr = (H * max(k, 1))(*[int(x) for x in modes])
+        out = np.empty((3, s), dtype=np.float64) if stats else None
+        self._ck(fn(self.h, arr, k, *q, dptr(cf) if cf.size else None, s, want, float(threshold),
+                    dptr(out) if stats else None, int(env_min), int(env_max), int(exceed), int(fields)))
+        return out
+
     def eval_batch(self, modes, coefs, stats=True, env_min=0, env_max=0, exceed=0, threshold=0.0, fields=0):
         """pgd_eval_batch: all samples (columns of ``coefs``, shape (k, s)) of u = sum_t coefs[t] modes[t] in one pass over
         the modes.  Outputs are requested by passing their vectors (``stats``: a flag); returns the (3, s) array of
         per-sample min / max / max |.| or None."""
-        k = len(modes)
-        cf = np.ascontiguousarray(coefs, dtype=np.float64)
-        if cf.ndim != 2 or cf.shape[0] != k:
-            raise ValueError("eval_batch: coefs must have shape (len(modes), samples), got %r for %d modes" % (cf.shape, k))
-        s = cf.shape[1]
-        want = (EVAL_STATS if stats else 0) | (EVAL_ENVELOPE if (env_min or env_max) else 0) | \
-               (EVAL_EXCEED if exceed else 0) | (EVAL_FIELDS if fields else 0)
-        arr = (H * max(k, 1))(*[int(x) for x in modes])
-        out = np.empty((3, s), dtype=np.float64) if stats else None
-        self._ck(self.lib.pgd_eval_batch(self.h, arr, k, dptr(cf) if cf.size else None, s, want, float(threshold),
-                                         dptr(out) if stats else None, int(env_min), int(env_max), int(exceed), int(fields)))
-        return out
+        return self._eval_batch("eval_batch", self.lib.pgd_eval_batch, (), modes, coefs, stats, env_min, env_max, exceed, threshold, fields)
 
     def eval_batch_norm(self, modes, q, coefs, stats=True, env_min=0, env_max=0, exceed=0, threshold=0.0, fields=0):
         """pgd_eval_batch_norm: eval_batch on modes of ``q`` planes each, the value of an entry being the Euclidean norm over its
         planes of the combined planes.  Same arguments and return value as ``eval_batch``; the outputs have len(mode) / q entries."""
-        k = len(modes)
-        cf = np.ascontiguousarray(coefs, dtype=np.float64)
-        if cf.ndim != 2 or cf.shape[0] != k:
-            raise ValueError("eval_batch_norm: coefs must have shape (len(modes), samples), got %r for %d modes" % (cf.shape, k))
-        s = cf.shape[1]
-        want = (EVAL_STATS if stats else 0) | (EVAL_ENVELOPE if (env_min or env_max) else 0) | \
-               (EVAL_EXCEED if exceed else 0) | (EVAL_FIELDS if fields else 0)
-        arr = (H * max(k, 1))(*[int(x) for x in modes])
-        out = np.empty((3, s), dtype=np.float64) if stats else None
-        self._ck(self.lib.pgd_eval_batch_norm(self.h, arr, k, int(q), dptr(cf) if cf.size else None, s, want, float(threshold),
-                                              dptr(out) if stats else None, int(env_min), int(env_max), int(exceed), int(fields)))
-        return out
+        return self._eval_batch("eval_batch_norm", self.lib.pgd_eval_batch_norm, (int(q),), modes, coefs, stats, env_min, env_max,
+                                exceed, threshold, fields)
 
     def eval_norm_last_shape(self):
         """(entries per workgroup, staged) of the last eval_batch_norm that launched; staged: 1 = the planes of a row block in at most

@@ -24,7 +24,8 @@
 // cross-check of the tests and the baseline that shows what the matrix unit buys (PGD_TUNE_EVAL_VARIANT).
 //
 // Further down: the same two kernels on q planes per entry with a Euclidean norm before the reductions (pgd_eval_batch_norm),
-// and the kernel that makes such planes from a nodal P1 mode (pgd_cell_gradient).
+// and the kernel that makes such planes from a nodal P1 mode (pgd_cell_gradient).  What happens to a value once it
+// is formed is the same in all four kernels: see "the reduction epilogue" below.
 #include "pgd_internal.h"
 
 #include <cmath>
@@ -169,12 +170,153 @@ __global__ __launch_bounds__(TPB) void k_eval_mfma(EvalModes M, int k, int64_t n
     }
 }
 
-// The same outputs from ordinary fma chains over k in ascending order: one wave per workgroup, one row per lane,
-// EVAL_PLAIN_NS samples per pass over the row's mode values (which stay in L1 / L2 between the passes).
+// ---- the reduction epilogue of k_eval_norm_mfma, k_eval_plain and k_eval_norm_plain, once per kernel family in inlined functions:
+// the per-tile step (field store, per-sample extrema into s_mn / s_mx, the lane's per-row state), the per-row-block step (envelope
+// and count into the output vectors, across sample chunks with `first`), the workgroup's row of partial extrema.  The norm kernels
+// pass sqrt of the sum of squares where the signed one passes u.  k_eval_mfma above keeps the same text inline, so a change to the
+// padding, NaN or chunk rule goes in there too: called, it was slower than its own run-to-run spread allows (K = 48, 256^3 rows, 256
+// samples, medians of three runs: 16.65 ms inline, spread 0.04; 16.69 with the state in arrays by reference, 16.89 in a struct).
+
+// row `row` over the samples of this chunk, combined with what the chunks before it left in the output vectors
+__device__ __forceinline__ void eval_row_accumulate(const EvalOut &O, int64_t row, double mn, double mx, double ct, int want, int first) {
+    if (want & PGD_EVAL_ENVELOPE) {
+        O.env_min[row] = first ? mn : fmin(O.env_min[row], mn);
+        O.env_max[row] = first ? mx : fmax(O.env_max[row], mx);
+    }
+    if (want & PGD_EVAL_EXCEED) O.exceed[row] = first ? ct : O.exceed[row] + ct;
+}
+
+// the workgroup's (NT threads) running per-sample extrema become its partial rows
+template <int NT>
+__device__ __forceinline__ void eval_store_partials(const EvalOut &O, const double *s_mn, const double *s_mx, int cs16, int want) {
+    if (!(want & PGD_EVAL_STATS)) return;
+    __syncthreads();
+    for (int j = threadIdx.x; j < cs16; j += NT) {
+        O.part[((int64_t)blockIdx.x * 2 + 0) * cs16 + j] = s_mn[j];
+        O.part[((int64_t)blockIdx.x * 2 + 1) * cs16 + j] = s_mx[j];
+    }
+}
+
+// Matrix-unit family, sample tile st of the chunk: lane (lq = lane >> 4, lr = lane & 15) holds D[lq + 4 r][lr] of every fragment, so
+// v[j][r] is the value of sample 16 st + lq + 4 r of the chunk at row row0 + 16 j + lr.  The lane's state for these rows over the
+// sample tiles of its wave: rv[j] (the row exists), emn[j], emx[j], ecnt[j] (values above the threshold).  A sample's extrema in
+// s_mn / s_mx belong to the wave of its tile.
+template <int T>
+__device__ __forceinline__ void eval_tile_step(const d4_t (&v)[T], const bool (&rv)[T], double (&emn)[T], double (&emx)[T], int (&ecnt)[T],
+                                               int st, int cs, int64_t j0, int64_t n, int64_t row0, int want, double thr, const EvalOut &O,
+                                               double *s_mn, double *s_mx) {
+    const double INF = __builtin_huge_val();
+    const int lane = threadIdx.x & 63, lr = lane & 15, lq = lane >> 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int js = 16 * st + lq + 4 * r;
+        const bool sv = js < cs;
+        double mn = INF, mx = -INF;
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            const double u = v[j][r];
+            if (rv[j] && sv) {
+                mn = fmin(mn, u);
+                mx = fmax(mx, u);
+                emn[j] = fmin(emn[j], u);
+                emx[j] = fmax(emx[j], u);
+                ecnt[j] += (u > thr) ? 1 : 0;
+                if (want & PGD_EVAL_FIELDS) O.fields[(j0 + js) * n + (row0 + 16 * j + lr)] = u;
+            }
+        }
+        if (want & PGD_EVAL_STATS) {
+#pragma unroll
+            for (int m = 1; m < 16; m <<= 1) {
+                mn = fmin(mn, __shfl_xor(mn, m, 64));
+                mx = fmax(mx, __shfl_xor(mx, m, 64));
+            }
+            if (lr == 0 && sv) { s_mn[js] = fmin(s_mn[js], mn); s_mx[js] = fmax(s_mx[js], mx); }
+        }
+    }
+}
+
+// After the sample tiles of a row block: the four sample groups lq of a wave, then the four waves through s_env (4 waves x 3 x RB)
+template <int T>
+__device__ __forceinline__ void eval_block_step(double (&emn)[T], double (&emx)[T], int (&ecnt)[T], double *s_env, int64_t row0, int64_t n,
+                                                int want, int first, const EvalOut &O) {
+    if (!(want & (PGD_EVAL_ENVELOPE | PGD_EVAL_EXCEED))) return;
+    constexpr int RB = 16 * T;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 15, lq = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+#pragma unroll
+        for (int m = 16; m < 64; m <<= 1) {
+            emn[j] = fmin(emn[j], __shfl_xor(emn[j], m, 64));
+            emx[j] = fmax(emx[j], __shfl_xor(emx[j], m, 64));
+            ecnt[j] += __shfl_xor(ecnt[j], m, 64);
+        }
+        if (lq == 0) {
+            s_env[(wv * 3 + 0) * RB + 16 * j + lr] = emn[j];
+            s_env[(wv * 3 + 1) * RB + 16 * j + lr] = emx[j];
+            s_env[(wv * 3 + 2) * RB + 16 * j + lr] = (double)ecnt[j];
+        }
+    }
+    __syncthreads();
+    const int d = threadIdx.x;
+    if (d < RB && row0 + d < n) {
+        double mn = __builtin_huge_val(), mx = -__builtin_huge_val(), ct = 0.0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            mn = fmin(mn, s_env[(w * 3 + 0) * RB + d]);
+            mx = fmax(mx, s_env[(w * 3 + 1) * RB + d]);
+            ct += s_env[(w * 3 + 2) * RB + d];
+        }
+        eval_row_accumulate(O, row0 + d, mn, mx, ct, want, first);
+    }
+}
+
+// One-wave kernels: one row per lane, EVAL_PLAIN_NS samples jb .. of the chunk per pass over the row's mode values (which stay in
+// L1 / L2 between the passes).  The fma chains over k in ascending order, the mode values at M.p[t][at]:
+__device__ __forceinline__ void eval_plain_chains(const EvalModes &M, int k, int kt, const double *__restrict__ cf, int jb, bool rv, int64_t at,
+                                                  double (&acc)[EVAL_PLAIN_NS]) {
+#pragma unroll
+    for (int c = 0; c < EVAL_PLAIN_NS; ++c) acc[c] = 0.0;
+    for (int t = 0; t < k; ++t) {
+        const double f = rv ? M.p[t][at] : 0.0;
+        const double *cp = cf + eval_cf_index(kt, t, jb);
+#pragma unroll
+        for (int c = 0; c < EVAL_PLAIN_NS; ++c) acc[c] = fma(cp[c], f, acc[c]);
+    }
+}
+
+// ... and what becomes of the values v of samples jb .. at the lane's row (emn, emx, ect: the row's state over the chunk)
+__device__ __forceinline__ void eval_plain_step(const double (&v)[EVAL_PLAIN_NS], int jb, int cs, int64_t j0, int64_t n, int64_t row, bool rv,
+                                                int want, double thr, const EvalOut &O, double *s_mn, double *s_mx, double &emn,
+                                                double &emx, double &ect) {
+    const double INF = __builtin_huge_val();
+#pragma unroll
+    for (int c = 0; c < EVAL_PLAIN_NS; ++c) {
+        const int js = jb + c;
+        if (js >= cs) break;                 // uniform
+        const double u = v[c];
+        double mn = INF, mx = -INF;
+        if (rv) {
+            mn = mx = u;
+            emn = fmin(emn, u);
+            emx = fmax(emx, u);
+            ect += (u > thr) ? 1.0 : 0.0;
+            if (want & PGD_EVAL_FIELDS) O.fields[(j0 + js) * n + row] = u;
+        }
+        if (want & PGD_EVAL_STATS) {
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) {
+                mn = fmin(mn, __shfl_xor(mn, m, 64));
+                mx = fmax(mx, __shfl_xor(mx, m, 64));
+            }
+            if (threadIdx.x == 0) { s_mn[js] = fmin(s_mn[js], mn); s_mx[js] = fmax(s_mx[js], mx); }
+        }
+    }
+}
+
+// The same outputs as k_eval_mfma from ordinary fma chains
 __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_plain(EvalModes M, int k, int kt, int64_t n, const double *__restrict__ cf,
                                                                int cs, int64_t j0, int want, int first, double thr, EvalOut O) {
     extern __shared__ double s_dyn[];
-    constexpr int NS = EVAL_PLAIN_NS;
     const double INF = __builtin_huge_val();
     const int cs16 = (cs + 15) & ~15;
     double *s_mn = s_dyn, *s_mx = s_dyn + cs16;
@@ -186,67 +328,26 @@ __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_plain(EvalModes M, int 
         const int64_t row = blk * EVAL_PLAIN_TPB + lane;
         const bool rv = row < n;
         double emn = INF, emx = -INF, ect = 0.0;
-        for (int jb = 0; jb < cs16; jb += NS) {
-            double acc[NS];
-#pragma unroll
-            for (int q = 0; q < NS; ++q) acc[q] = 0.0;
-            for (int t = 0; t < k; ++t) {
-                const double f = rv ? M.p[t][row] : 0.0;
-                const double *cp = cf + eval_cf_index(kt, t, jb);
-#pragma unroll
-                for (int q = 0; q < NS; ++q) acc[q] = fma(cp[q], f, acc[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < NS; ++q) {
-                const int js = jb + q;
-                if (js >= cs) break;                 // uniform
-                const double u = acc[q];
-                double mn = INF, mx = -INF;
-                if (rv) {
-                    mn = mx = u;
-                    emn = fmin(emn, u);
-                    emx = fmax(emx, u);
-                    ect += (u > thr) ? 1.0 : 0.0;
-                    if (want & PGD_EVAL_FIELDS) O.fields[(j0 + js) * n + row] = u;
-                }
-                if (want & PGD_EVAL_STATS) {
-#pragma unroll
-                    for (int m = 1; m < 64; m <<= 1) {
-                        mn = fmin(mn, __shfl_xor(mn, m, 64));
-                        mx = fmax(mx, __shfl_xor(mx, m, 64));
-                    }
-                    if (lane == 0) { s_mn[js] = fmin(s_mn[js], mn); s_mx[js] = fmax(s_mx[js], mx); }
-                }
-            }
+        for (int jb = 0; jb < cs16; jb += EVAL_PLAIN_NS) {
+            double acc[EVAL_PLAIN_NS];
+            eval_plain_chains(M, k, kt, cf, jb, rv, row, acc);
+            eval_plain_step(acc, jb, cs, j0, n, row, rv, want, thr, O, s_mn, s_mx, emn, emx, ect);
         }
-        if (rv) {
-            if (want & PGD_EVAL_ENVELOPE) {
-                O.env_min[row] = first ? emn : fmin(O.env_min[row], emn);
-                O.env_max[row] = first ? emx : fmax(O.env_max[row], emx);
-            }
-            if (want & PGD_EVAL_EXCEED) O.exceed[row] = first ? ect : O.exceed[row] + ect;
-        }
+        if (rv) eval_row_accumulate(O, row, emn, emx, ect, want, first);
     }
-    if (want & PGD_EVAL_STATS) {
-        __syncthreads();
-        for (int j = lane; j < cs16; j += EVAL_PLAIN_TPB) {
-            O.part[((int64_t)blockIdx.x * 2 + 0) * cs16 + j] = s_mn[j];
-            O.part[((int64_t)blockIdx.x * 2 + 1) * cs16 + j] = s_mx[j];
-        }
-    }
+    eval_store_partials<EVAL_PLAIN_TPB>(O, s_mn, s_mx, cs16, want);
 }
 
 // ---- norms of q linear quantities (pgd_eval_batch_norm): every mode is q planes of m entries, the value of entry e and sample j
 // is v = sqrt(sum_i u_i^2), u_i = sum_t C[t][j] modes[t][i m + e].  Per plane the u_i are the accumulators of k_eval_mfma /
 // k_eval_plain (one fixed chain over k each); the sum of squares starts from 0 and takes fma(u_i, u_i, .) over ascending i, so v
 // does not depend on the grid, the chunk or the row block either.  Everything after v - extrema, envelopes, counts, fields - is the
-// epilogue of the kernels above with v in the place of u.
+// reduction epilogue with v in the place of u.
 //
 // k_eval_norm_mfma stages the q planes of a row block (q x 4 kt x RB values) and reloads the B fragment of plane i, k-step s from
 // LDS inside the sample-tile loop (q x kt fragments do not fit the registers as the kt of k_eval_mfma do): one ds_read_b64 per MFMA,
 // rows padded to 16 (mod 32) doubles so that the two 16-lane row groups of a half wave sit on opposite halves of the bank row.
-// kt is a run-time value here.  The epilogues are copies of those above, not shared device functions: factoring them out changes
-// the instructions of k_eval_mfma and k_eval_plain, which pgd_eval_batch keeps as they were.  LDSB = false reads the fragments from global memory instead (L2: a row block's values are read by
+// kt is a run-time value here.  LDSB = false reads the fragments from global memory instead (L2: a row block's values are read by
 // every sample tile): the launcher's last resort where q planes of 16 rows do not fit 160 KiB.
 template <int T>
 struct EvalNormShape {
@@ -317,75 +418,16 @@ __global__ __launch_bounds__(TPB) void k_eval_norm_mfma(EvalModes M, int k, int 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) ss[j][r] = fma(acc[j][r], acc[j][r], ss[j][r]);
             }
-            // lane holds the value of sample 16 st + lq + 4 r of the chunk, row row0 + 16 j + lr
+            d4_t v[T];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int js = 16 * st + lq + 4 * r;
-                const bool sv = js < cs;
-                double mn = INF, mx = -INF;
+            for (int j = 0; j < T; ++j)
 #pragma unroll
-                for (int j = 0; j < T; ++j) {
-                    const double u = sqrt(ss[j][r]);
-                    if (rv[j] && sv) {
-                        mn = fmin(mn, u);
-                        mx = fmax(mx, u);
-                        emn[j] = fmin(emn[j], u);
-                        emx[j] = fmax(emx[j], u);
-                        ecnt[j] += (u > thr) ? 1 : 0;
-                        if (want & PGD_EVAL_FIELDS) O.fields[(j0 + js) * n + (row0 + 16 * j + lr)] = u;
-                    }
-                }
-                if (want & PGD_EVAL_STATS) {
-#pragma unroll
-                    for (int m = 1; m < 16; m <<= 1) {
-                        mn = fmin(mn, __shfl_xor(mn, m, 64));
-                        mx = fmax(mx, __shfl_xor(mx, m, 64));
-                    }
-                    if (lr == 0 && sv) { s_mn[js] = fmin(s_mn[js], mn); s_mx[js] = fmax(s_mx[js], mx); }
-                }
-            }
+                for (int r = 0; r < 4; ++r) v[j][r] = sqrt(ss[j][r]);
+            eval_tile_step<T>(v, rv, emn, emx, ecnt, st, cs, j0, n, row0, want, thr, O, s_mn, s_mx);
         }
-        if (want & (PGD_EVAL_ENVELOPE | PGD_EVAL_EXCEED)) {
-#pragma unroll
-            for (int j = 0; j < T; ++j) {
-#pragma unroll
-                for (int m = 16; m < 64; m <<= 1) {
-                    emn[j] = fmin(emn[j], __shfl_xor(emn[j], m, 64));
-                    emx[j] = fmax(emx[j], __shfl_xor(emx[j], m, 64));
-                    ecnt[j] += __shfl_xor(ecnt[j], m, 64);
-                }
-                if (lq == 0) {
-                    s_env[(wv * 3 + 0) * RB + 16 * j + lr] = emn[j];
-                    s_env[(wv * 3 + 1) * RB + 16 * j + lr] = emx[j];
-                    s_env[(wv * 3 + 2) * RB + 16 * j + lr] = (double)ecnt[j];
-                }
-            }
-            __syncthreads();
-            const int d = threadIdx.x;
-            if (d < RB && row0 + d < n) {
-                double mn = INF, mx = -INF, ct = 0.0;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    mn = fmin(mn, s_env[(w * 3 + 0) * RB + d]);
-                    mx = fmax(mx, s_env[(w * 3 + 1) * RB + d]);
-                    ct += s_env[(w * 3 + 2) * RB + d];
-                }
-                const int64_t row = row0 + d;
-                if (want & PGD_EVAL_ENVELOPE) {
-                    O.env_min[row] = first ? mn : fmin(O.env_min[row], mn);
-                    O.env_max[row] = first ? mx : fmax(O.env_max[row], mx);
-                }
-                if (want & PGD_EVAL_EXCEED) O.exceed[row] = first ? ct : O.exceed[row] + ct;
-            }
-        }
+        eval_block_step<T>(emn, emx, ecnt, s_env, row0, n, want, first, O);
     }
-    if (want & PGD_EVAL_STATS) {
-        __syncthreads();
-        for (int j = threadIdx.x; j < cs16; j += TPB) {
-            O.part[((int64_t)blockIdx.x * 2 + 0) * cs16 + j] = s_mn[j];
-            O.part[((int64_t)blockIdx.x * 2 + 1) * cs16 + j] = s_mx[j];
-        }
-    }
+    eval_store_partials<TPB>(O, s_mn, s_mx, cs16, want);
 }
 
 // k_eval_plain with the loop over the planes around its fma chains
@@ -405,60 +447,21 @@ __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_norm_plain(EvalModes M,
         const bool rv = row < n;
         double emn = INF, emx = -INF, ect = 0.0;
         for (int jb = 0; jb < cs16; jb += NS) {
-            double ss[NS];
+            double ss[NS], acc[NS];
 #pragma unroll
             for (int c = 0; c < NS; ++c) ss[c] = 0.0;
             for (int i = 0; i < q; ++i) {
-                double acc[NS];
-#pragma unroll
-                for (int c = 0; c < NS; ++c) acc[c] = 0.0;
-                for (int t = 0; t < k; ++t) {
-                    const double f = rv ? M.p[t][(int64_t)i * n + row] : 0.0;
-                    const double *cp = cf + eval_cf_index(kt, t, jb);
-#pragma unroll
-                    for (int c = 0; c < NS; ++c) acc[c] = fma(cp[c], f, acc[c]);
-                }
+                eval_plain_chains(M, k, kt, cf, jb, rv, (int64_t)i * n + row, acc);
 #pragma unroll
                 for (int c = 0; c < NS; ++c) ss[c] = fma(acc[c], acc[c], ss[c]);
             }
 #pragma unroll
-            for (int c = 0; c < NS; ++c) {
-                const int js = jb + c;
-                if (js >= cs) break;                 // uniform
-                const double u = sqrt(ss[c]);
-                double mn = INF, mx = -INF;
-                if (rv) {
-                    mn = mx = u;
-                    emn = fmin(emn, u);
-                    emx = fmax(emx, u);
-                    ect += (u > thr) ? 1.0 : 0.0;
-                    if (want & PGD_EVAL_FIELDS) O.fields[(j0 + js) * n + row] = u;
-                }
-                if (want & PGD_EVAL_STATS) {
-#pragma unroll
-                    for (int m = 1; m < 64; m <<= 1) {
-                        mn = fmin(mn, __shfl_xor(mn, m, 64));
-                        mx = fmax(mx, __shfl_xor(mx, m, 64));
-                    }
-                    if (lane == 0) { s_mn[js] = fmin(s_mn[js], mn); s_mx[js] = fmax(s_mx[js], mx); }
-                }
-            }
+            for (int c = 0; c < NS; ++c) ss[c] = sqrt(ss[c]);            // from here on the values
+            eval_plain_step(ss, jb, cs, j0, n, row, rv, want, thr, O, s_mn, s_mx, emn, emx, ect);
         }
-        if (rv) {
-            if (want & PGD_EVAL_ENVELOPE) {
-                O.env_min[row] = first ? emn : fmin(O.env_min[row], emn);
-                O.env_max[row] = first ? emx : fmax(O.env_max[row], emx);
-            }
-            if (want & PGD_EVAL_EXCEED) O.exceed[row] = first ? ect : O.exceed[row] + ect;
-        }
+        if (rv) eval_row_accumulate(O, row, emn, emx, ect, want, first);
     }
-    if (want & PGD_EVAL_STATS) {
-        __syncthreads();
-        for (int j = lane; j < cs16; j += EVAL_PLAIN_TPB) {
-            O.part[((int64_t)blockIdx.x * 2 + 0) * cs16 + j] = s_mn[j];
-            O.part[((int64_t)blockIdx.x * 2 + 1) * cs16 + j] = s_mx[j];
-        }
-    }
+    eval_store_partials<EVAL_PLAIN_TPB>(O, s_mn, s_mx, cs16, want);
 }
 
 // Final pass: sample j of the chunk takes the g workgroups' partial extrema in a fixed order (a thread per sample,
@@ -478,24 +481,31 @@ __global__ __launch_bounds__(TPB) void k_eval_finish(const double *__restrict__ 
     stats[2 * s_total + j0 + j] = fmax(fabs(mn), fabs(mx));
 }
 
+// Launch of a persistent matrix-unit kernel on the nblk row blocks of a call: as many workgroups as are resident at once (the
+// occupancy the runtime reports for this kernel and LDS size), at most grid_cap and at most one per row block
+template <class... P, class... A>
+static int eval_launch_persistent(Ctx *c, void (*kern)(P...), size_t lds, int64_t nblk, int grid_cap, int *grid_out, const A &...args) {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, TPB, lds) != hipSuccess || occ < 1) {
+        (void)hipGetLastError();
+        occ = 1;
+    }
+    int64_t g = (int64_t)c->num_cu * occ;
+    if (g > grid_cap) g = grid_cap;
+    if (g > nblk) g = nblk;
+    kern<<<(int)g, TPB, lds, c->stream>>>(args...);
+    PGD_LAUNCH_CHECK(c);
+    *grid_out = (int)g;
+    return PGD_OK;
+}
+
 template <int KT, int T>
 static int eval_launch_mfma(Ctx *c, const EvalModes &M, int k, int64_t n, const double *cf, int cs, int64_t j0, int want,
                             int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const int cs16 = (cs + 15) & ~15;
     const size_t lds = ((size_t)4 * KT * 16 * T + 2 * (size_t)cs16 + 12 * 16 * T) * sizeof(double);
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_eval_mfma<KT, T>, TPB, lds) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
-    const int64_t nblk = (n + 16 * T - 1) / (16 * T);
-    int64_t g = (int64_t)c->num_cu * occ;
-    if (g > grid_cap) g = grid_cap;
-    if (g > nblk) g = nblk;
-    k_eval_mfma<KT, T><<<(int)g, TPB, lds, c->stream>>>(M, k, n, cf, cs, j0, want, first, thr, O);
-    PGD_LAUNCH_CHECK(c);
-    *grid_out = (int)g;
-    return PGD_OK;
+    return eval_launch_persistent(c, k_eval_mfma<KT, T>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, n, cf, cs, j0, want,
+                                  first, thr, O);
 }
 
 // k-steps of 4 the kernel is compiled for: k <= 16, 32, 48, 64 with 64 rows per workgroup, <= 128 with 32, <= 256 with 16
@@ -535,19 +545,8 @@ template <int T, bool LDSB>
 static int eval_launch_norm(Ctx *c, const EvalModes &M, int k, int kt, int q, int64_t n, const double *cf, int cs, int64_t j0, int want,
                             int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const size_t lds = eval_norm_lds(T, LDSB, q, kt, (cs + 15) & ~15);
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_eval_norm_mfma<T, LDSB>, TPB, lds) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
-    const int64_t nblk = (n + 16 * T - 1) / (16 * T);
-    int64_t g = (int64_t)c->num_cu * occ;
-    if (g > grid_cap) g = grid_cap;
-    if (g > nblk) g = nblk;
-    k_eval_norm_mfma<T, LDSB><<<(int)g, TPB, lds, c->stream>>>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O);
-    PGD_LAUNCH_CHECK(c);
-    *grid_out = (int)g;
-    return PGD_OK;
+    return eval_launch_persistent(c, k_eval_norm_mfma<T, LDSB>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q, n, cf,
+                                  cs, j0, want, first, thr, O);
 }
 
 static size_t eval_round(size_t bytes) { return (bytes + 65535) & ~(size_t)65535; }   // (whole 64 KiB: the pool takes them back)

@@ -194,6 +194,87 @@ class _FieldSlice(fem.Vector):
         super().touched_dev()
 
 
+def _eval_many_device(be, call, V, n, S, stats, envelope, thr, fields):
+    """The device half of ``evaluate_many`` / ``evaluate_gradient_many``: allocates the requested outputs on ``V`` (``n`` entries),
+    runs ``call(stats, **handles)`` - the backend's batch evaluation, which returns the (3, S) statistics or None - and returns
+    the filled ``EvalManyResult``."""
+    res = EvalManyResult()
+
+    def out_function():
+        f = fem.Function(V)
+        return f, f.vector().dev_for_write()
+    kw = {}
+    if envelope:
+        (res.envelope_min, kw["env_min"]), (res.envelope_max, kw["env_max"]) = out_function(), out_function()
+    if thr is not None:
+        (res.exceedance, kw["exceed"]), kw["threshold"] = out_function(), thr
+    if fields:
+        res._fields_owner = _FieldStore(be, n, S)
+        kw["fields"] = res._fields_owner.handle
+    st = call(bool(stats), **kw)
+    if stats:
+        res.min, res.max, res.max_abs = st[0], st[1], st[2]
+    for f in (res.envelope_min, res.envelope_max, res.exceedance):
+        if f is not None:
+            f.vector().touched_dev()
+    if thr is not None:
+        v = res.exceedance.vector()
+        v._host = v.host() / S                  # counts -> fraction (exactly count / S, as the host path has it)
+        v.touched_host()
+    if fields:
+        res.fields = []
+        for j in range(S):
+            f = fem.Function(V)
+            f._vec = _FieldSlice(V, res._fields_owner, j)
+            res.fields.append(f)
+    return res
+
+
+def _eval_many_host(values, n, S, sample_chunk, stats, envelope, thr, fields, wrap, nonnegative=False):
+    """The host half: the same outputs in numpy from ``values(j0, step)``, the (n, <= step) matrix of the samples from j0 on,
+    ``sample_chunk`` samples at a time.  ``wrap`` turns an array of n entries into what the result holds; ``nonnegative``: the
+    values are norms, so ``max_abs`` is a copy of ``max``."""
+    res = EvalManyResult()
+    if stats:
+        res.min, res.max = np.empty(S), np.empty(S)
+        if not nonnegative:
+            res.max_abs = np.empty(S)
+    emn, emx = np.full(n, np.inf), np.full(n, -np.inf)
+    cnt = np.zeros(n)
+    all_fields = []
+    step = max(1, int(sample_chunk))
+    for j0 in range(0, S, step):
+        U = values(j0, step)
+        if stats:
+            sl = slice(j0, j0 + U.shape[1])
+            res.min[sl], res.max[sl] = U.min(axis=0), U.max(axis=0)
+            if not nonnegative:
+                res.max_abs[sl] = np.abs(U).max(axis=0)
+        if envelope:
+            np.minimum(emn, U.min(axis=1), out=emn)
+            np.maximum(emx, U.max(axis=1), out=emx)
+        if thr is not None:
+            cnt += (U > thr).sum(axis=1)
+        if fields:
+            all_fields.extend(np.ascontiguousarray(U[:, j]) for j in range(U.shape[1]))
+    if stats and nonnegative:
+        res.max_abs = res.max.copy()
+    if envelope:
+        res.envelope_min, res.envelope_max = wrap(emn), wrap(emx)
+    if thr is not None:
+        res.exceedance = wrap(cnt / S)
+    if fields:
+        res.fields = [wrap(a) for a in all_fields]
+    return res
+
+
+def _host_function(V, a):
+    f = fem.Function(V)
+    f.vector()._host = np.array(a, dtype=np.float64)
+    f.vector().touched_host()
+    return f
+
+
 class PGD:
     def __init__(self, name=None, n_modes=0, fmeshes=[], pgd_modes=[], name_coord=[], modes_info=[],
                  verbose=False, *args, **kwargs):
@@ -696,76 +777,21 @@ class PGD:
                              "fields_max_bytes=%d" % (n * S * 8, n, S, fields_max_bytes))
         thr = None if threshold is None else float(threshold)
         C = self.mode_factors_many(free_dim, coords, attri)
-        res = EvalManyResult()
-        res.coefficients = C
         be = fem.get_backend()
         if (not as_arrays and n >= DEVICE_EVAL_MIN_DOFS and K <= 256 and all(isinstance(m, fem.Function) for m in modes[:K])
                 and hasattr(be, "eval_batch")):
-            def out_function():
-                f = fem.Function(V)
-                return f, f.vector().dev_for_write()
-            kw = {}
-            if envelope:
-                (res.envelope_min, kw["env_min"]), (res.envelope_max, kw["env_max"]) = out_function(), out_function()
-            if thr is not None:
-                (res.exceedance, kw["exceed"]), kw["threshold"] = out_function(), thr
-            if fields:
-                res._fields_owner = _FieldStore(be, n, S)
-                kw["fields"] = res._fields_owner.handle
-            st = be.eval_batch([modes[k].vector().dev() for k in range(K)], C, stats=bool(stats), **kw)
+            handles = [modes[k].vector().dev() for k in range(K)]
+            res = _eval_many_device(be, lambda st, **kw: be.eval_batch(handles, C, stats=st, **kw), V, n, S, stats, envelope, thr, fields)
             fem.STATS["eval_batch_calls"] = fem.STATS.get("eval_batch_calls", 0) + 1
-            if stats:
-                res.min, res.max, res.max_abs = st[0], st[1], st[2]
-            for f in (res.envelope_min, res.envelope_max, res.exceedance):
-                if f is not None:
-                    f.vector().touched_dev()
-            if thr is not None:
-                v = res.exceedance.vector()
-                v._host = v.host() / S                  # counts -> fraction (exactly count / S, as the host path has it)
-                v.touched_host()
-            if fields:
-                res.fields = []
-                for j in range(S):
-                    f = fem.Function(V)
-                    f._vec = _FieldSlice(V, res._fields_owner, j)
-                    res.fields.append(f)
-            return res
-        # ---- host path: the same outputs in numpy, sample_chunk columns of U at a time
-        if as_arrays:
-            F = np.stack([np.asarray(att.data[k], dtype=np.float64).reshape(-1) for k in range(K)], axis=1)
         else:
-            F = np.stack([modes[k].vector().host() for k in range(K)], axis=1)
-        if stats:
-            res.min, res.max, res.max_abs = np.empty(S), np.empty(S), np.empty(S)
-        emn, emx = np.full(n, np.inf), np.full(n, -np.inf)
-        cnt = np.zeros(n)
-        all_fields = []
-        for j0 in range(0, S, max(1, int(sample_chunk))):
-            U = F @ C[:, j0:j0 + max(1, int(sample_chunk))]               # (n, cs)
-            if stats:
-                sl = slice(j0, j0 + U.shape[1])
-                res.min[sl], res.max[sl], res.max_abs[sl] = U.min(axis=0), U.max(axis=0), np.abs(U).max(axis=0)
-            if envelope:
-                np.minimum(emn, U.min(axis=1), out=emn)
-                np.maximum(emx, U.max(axis=1), out=emx)
-            if thr is not None:
-                cnt += (U > thr).sum(axis=1)
-            if fields:
-                all_fields.extend(np.ascontiguousarray(U[:, j]) for j in range(U.shape[1]))
-
-        def wrap(a):
             if as_arrays:
-                return a.reshape(att.data[0].shape)
-            f = fem.Function(V)
-            f.vector()._host = np.array(a, dtype=np.float64)
-            f.vector().touched_host()
-            return f
-        if envelope:
-            res.envelope_min, res.envelope_max = wrap(emn), wrap(emx)
-        if thr is not None:
-            res.exceedance = wrap(cnt / S)
-        if fields:
-            res.fields = [wrap(a) for a in all_fields]
+                F = np.stack([np.asarray(att.data[k], dtype=np.float64).reshape(-1) for k in range(K)], axis=1)
+                wrap = lambda a: a.reshape(att.data[0].shape)
+            else:
+                F = np.stack([modes[k].vector().host() for k in range(K)], axis=1)
+                wrap = lambda a: _host_function(V, a)
+            res = _eval_many_host(lambda j0, step: F @ C[:, j0:j0 + step], n, S, sample_chunk, stats, envelope, thr, fields, wrap)
+        res.coefficients = C
         return res
 
     # ------------------------------------------------- batched evaluation of gradient quantities
@@ -827,8 +853,6 @@ class PGD:
                              "fields_max_bytes=%d" % (nc * S * 8, nc, S, fields_max_bytes))
         thr = None if threshold is None else float(threshold)
         C = self.mode_factors_many(free_dim, coords, attri)
-        res = EvalManyResult()
-        res.coefficients = C
         be = fem.get_backend()
         device = nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "eval_batch_norm") and hasattr(be, "cell_gradient")
         key = (quantity, K, scale_key, device, id(be), tuple((id(m.vector()), m.vector().version) for m in modes[:K]))
@@ -839,74 +863,22 @@ class PGD:
             fem.STATS["gradient_mode_builds"] = fem.STATS.get("gradient_mode_builds", 0) + 1
         Vc = fem.FunctionSpace(mesh, "DG", 0)
         if device:
-            def out_function():
-                f = fem.Function(Vc)
-                return f, f.vector().dev_for_write()
-            kw = {}
-            if envelope:
-                (res.envelope_min, kw["env_min"]), (res.envelope_max, kw["env_max"]) = out_function(), out_function()
-            if thr is not None:
-                (res.exceedance, kw["exceed"]), kw["threshold"] = out_function(), thr
-            if fields:
-                res._fields_owner = _FieldStore(be, nc, S)
-                kw["fields"] = res._fields_owner.handle
-            st = be.eval_batch_norm(cache.planes, q, C, stats=bool(stats), **kw)
+            res = _eval_many_device(be, lambda st, **kw: be.eval_batch_norm(cache.planes, q, C, stats=st, **kw), Vc, nc, S, stats,
+                                    envelope, thr, fields)
             fem.STATS["eval_gradient_calls"] = fem.STATS.get("eval_gradient_calls", 0) + 1
-            if stats:
-                res.min, res.max, res.max_abs = st[0], st[1], st[2]
-            for f in (res.envelope_min, res.envelope_max, res.exceedance):
-                if f is not None:
-                    f.vector().touched_dev()
-            if thr is not None:
-                v = res.exceedance.vector()
-                v._host = v.host() / S                  # counts -> fraction (exactly count / S, as the host path has it)
-                v.touched_host()
-            if fields:
-                res.fields = []
-                for j in range(S):
-                    f = fem.Function(Vc)
-                    f._vec = _FieldSlice(Vc, res._fields_owner, j)
-                    res.fields.append(f)
-            return res
-        # ---- host path: the same outputs in numpy, sample_chunk columns at a time
-        P = cache.planes                                    # (q, cells, K)
-        if stats:
-            res.min, res.max = np.empty(S), np.empty(S)
-        emn, emx = np.full(nc, np.inf), np.full(nc, -np.inf)
-        cnt = np.zeros(nc)
-        all_fields = []
-        step = max(1, int(sample_chunk))
-        for j0 in range(0, S, step):
-            Cc = C[:, j0:j0 + step]
-            ss = np.zeros((nc, Cc.shape[1]))
-            for i in range(q):
-                U = P[i] @ Cc
-                ss += U * U
-            Vn = np.sqrt(ss)                                 # (cells, cs)
-            if stats:
-                sl = slice(j0, j0 + Vn.shape[1])
-                res.min[sl], res.max[sl] = Vn.min(axis=0), Vn.max(axis=0)
-            if envelope:
-                np.minimum(emn, Vn.min(axis=1), out=emn)
-                np.maximum(emx, Vn.max(axis=1), out=emx)
-            if thr is not None:
-                cnt += (Vn > thr).sum(axis=1)
-            if fields:
-                all_fields.extend(np.ascontiguousarray(Vn[:, j]) for j in range(Vn.shape[1]))
-        if stats:
-            res.max_abs = res.max.copy()
+        else:
+            P = cache.planes                                    # (q, cells, K)
 
-        def wrap(a):
-            f = fem.Function(Vc)
-            f.vector()._host = np.array(a, dtype=np.float64)
-            f.vector().touched_host()
-            return f
-        if envelope:
-            res.envelope_min, res.envelope_max = wrap(emn), wrap(emx)
-        if thr is not None:
-            res.exceedance = wrap(cnt / S)
-        if fields:
-            res.fields = [wrap(a) for a in all_fields]
+            def norms(j0, step):
+                Cc = C[:, j0:j0 + step]
+                ss = np.zeros((nc, Cc.shape[1]))
+                for i in range(q):
+                    U = P[i] @ Cc
+                    ss += U * U
+                return np.sqrt(ss)                              # (cells, cs)
+            res = _eval_many_host(norms, nc, S, sample_chunk, stats, envelope, thr, fields, lambda a: _host_function(Vc, a),
+                                  nonnegative=True)
+        res.coefficients = C
         return res
 
     # ------------------------------------------------------ sensor responses and derivatives

@@ -478,9 +478,28 @@ int pgd_cell_gradient(pgd_handle ctx, pgd_handle mesh, pgd_handle u, const doubl
 int pgd_eval_batch_norm(pgd_handle ctx, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want,
                         double threshold, double *sample_stats, pgd_handle env_min, pgd_handle env_max, pgd_handle exceed,
                         pgd_handle fields);
-/* How the last pgd_eval_batch_norm call that launched laid out its work: rows = entries per workgroup (64, 32 or 16 on the matrix
+/* pgd_eval_batch_grad: pgd_cell_gradient and pgd_eval_batch_norm in one call, with the planes never stored.  Per cell e and sample
+ * j the value is sqrt(sum_i u_i^2), u_i = sum_t C[t][j] P_t[i][e], P_t[i][e] exactly what pgd_cell_gradient(mesh, modes[t], L, q,
+ * scale) would have written; the kernels form P_t from the nodal values where the stored path reads it (the matrix-unit kernel when
+ * it stages a block of cells in LDS, the plain kernel in front of its fma chains), so the call needs no memory beyond the nodal modes.
+ *   mesh, L, q, scale_or_0: as pgd_cell_gradient;  modes: k nodal vectors of nv*ncomp entries;
+ *   coefs .. fields: as pgd_eval_batch_norm, every output with one entry per cell (fields: nc*s, sample-major).
+ * Everything pgd_eval_batch_norm states holds: the want bits, the sample chunks, no atomics, one host synchronisation if and only if
+ * PGD_EVAL_STATS is set, max |.| equals max, outputs bit-identical for any grid size and chunk length, both variants.  PGD_ERR_INVALID
+ * with a message, before anything is launched, for everything pgd_eval_batch and pgd_cell_gradient refuse (a P2 layout, a layout
+ * without cell records, q out of range, a null L, modes of another length than nv*ncomp, a scale of another length than nc) and for
+ * an output aliasing a mode or the scale.  nc == 0 is PGD_OK.
+ * Limits: P1 layouts; norms only; the matrix-unit kernel has no fallback to global memory, so where the q planes of 16 cells do not
+ * fit 160 KiB of LDS (q * 4 ceil(k / 4) above about 1250) the call is refused with PGD_ERR_LIMIT before anything is launched
+ * (PGD_TUNE_EVAL_VARIANT = 0 has no such limit); every sample chunk gathers the nodal values and forms the planes again, so calls
+ * of few samples are dominated by the gathers - where the planes fit in memory and are reused, the two-stage path reads less. */
+int pgd_eval_batch_grad(pgd_handle ctx, pgd_handle mesh, const pgd_handle *modes, int k, const double *L, int q,
+                        pgd_handle scale_or_0, const double *coefs, int64_t s, int want, double threshold, double *sample_stats,
+                        pgd_handle env_min, pgd_handle env_max, pgd_handle exceed, pgd_handle fields);
+/* How the last pgd_eval_batch_norm or pgd_eval_batch_grad call that launched laid out its work: rows = entries per workgroup (64, 32 or 16 on the matrix
  * unit, 64 in the plain variant), staged = 1 the planes of a row block in at most 64 KiB of LDS, 2 in more (up to 160 KiB), 0 read
- * from global memory (always in the plain variant); rows = 0, staged = -1 before the first call.                              */
+ * from global memory (always in the plain variant; never on the matrix unit for pgd_eval_batch_grad); rows = 0, staged = -1
+ * before the first call.                                                                                                      */
 int pgd_eval_norm_last_shape(pgd_handle ctx, int *rows, int *staged);
 
 /* ------------------------------------------------------------------ tuning --- */

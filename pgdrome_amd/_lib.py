@@ -70,6 +70,7 @@ SIGNATURES = {
     "pgd_eval_batch": (C.c_int, [H, PH, C.c_int, PD, I64, C.c_int, F64, PD, H, H, H, H]),
     "pgd_eval_batch_norm": (C.c_int, [H, PH, C.c_int, C.c_int, PD, I64, C.c_int, F64, PD, H, H, H, H]),
     "pgd_cell_gradient": (C.c_int, [H, H, H, PD, C.c_int, H, H]),
+    "pgd_eval_batch_grad": (C.c_int, [H, H, PH, C.c_int, PD, C.c_int, H, PD, I64, C.c_int, F64, PD, H, H, H, H]),
     "pgd_eval_norm_last_shape": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pgd_atom_assemble": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PH]),
     "pgd_atom_assemble_cells": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PU8, I64, PH]),
@@ -414,8 +415,9 @@ class Context:
         cf = np.ascontiguousarray(coefs, dtype=np.float64)
         self._ck(self.lib.pgd_vec_lincomb_inplace(self.h, y, arr, dptr(cf) if k else None, k))
 
-    def _eval_batch(self, name, fn, q, modes, coefs, stats, env_min, env_max, exceed, threshold, fields):
-        """The marshalling of ``eval_batch`` (``q`` = ()) and ``eval_batch_norm`` (``q`` = (planes,)): ``fn`` takes ``q`` after k."""
+    def _eval_batch(self, name, fn, q, modes, coefs, stats, env_min, env_max, exceed, threshold, fields, lead=()):
+        """The marshalling of ``eval_batch`` (``q`` = ()), ``eval_batch_norm`` (``q`` = (planes,)) and ``eval_batch_grad`` (``q`` = (L,
+        planes, scale), ``lead`` = (mesh,)): ``fn`` takes ``lead`` after the context and ``q`` after k."""
         k = len(modes)
         cf = np.ascontiguousarray(coefs, dtype=np.float64)
         if cf.ndim != 2 or cf.shape[0] != k:
@@ -425,7 +427,7 @@ class Context:
                (EVAL_EXCEED if exceed else 0) | (EVAL_FIELDS if fields else 0)
         arr = (H * max(k, 1))(*[int(x) for x in modes])
         out = np.empty((3, s), dtype=np.float64) if stats else None
-        self._ck(fn(self.h, arr, k, *q, dptr(cf) if cf.size else None, s, want, float(threshold),
+        self._ck(fn(self.h, *lead, arr, k, *q, dptr(cf) if cf.size else None, s, want, float(threshold),
                     dptr(out) if stats else None, int(env_min), int(env_max), int(exceed), int(fields)))
         return out
 
@@ -441,8 +443,18 @@ class Context:
         return self._eval_batch("eval_batch_norm", self.lib.pgd_eval_batch_norm, (int(q),), modes, coefs, stats, env_min, env_max,
                                 exceed, threshold, fields)
 
+    def eval_batch_grad(self, mesh, modes, L, coefs, scale=0, stats=True, env_min=0, env_max=0, exceed=0, threshold=0.0, fields=0):
+        """pgd_eval_batch_grad: ``cell_gradient`` of every nodal mode and ``eval_batch_norm`` on the planes in one call that stores no
+        planes.  ``mesh``, ``L`` (q, ncomp * gdim), ``scale`` as ``cell_gradient``; the rest and the return value as ``eval_batch``,
+        the outputs with one entry per cell."""
+        L = np.ascontiguousarray(L, dtype=np.float64)
+        if L.ndim != 2:
+            raise ValueError("eval_batch_grad: L is a (q, ncomp * gdim) matrix")
+        return self._eval_batch("eval_batch_grad", self.lib.pgd_eval_batch_grad, (dptr(L) if L.size else None, L.shape[0], int(scale or 0)),
+                                modes, coefs, stats, env_min, env_max, exceed, threshold, fields, lead=(int(mesh),))
+
     def eval_norm_last_shape(self):
-        """(entries per workgroup, staged) of the last eval_batch_norm that launched; staged: 1 = the planes of a row block in at most
+        """(entries per workgroup, staged) of the last eval_batch_norm / eval_batch_grad that launched; staged: 1 = the planes of a row block in at most
         64 KiB of LDS, 2 = in more, 0 = read from global memory (pgd_eval_norm_last_shape)."""
         rows, staged = C.c_int(), C.c_int()
         self._ck(self.lib.pgd_eval_norm_last_shape(self.h, C.byref(rows), C.byref(staged)))

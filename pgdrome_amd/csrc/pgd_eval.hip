@@ -24,8 +24,9 @@
 // cross-check of the tests and the baseline that shows what the matrix unit buys (PGD_TUNE_EVAL_VARIANT).
 //
 // Further down: the same two kernels on q planes per entry with a Euclidean norm before the reductions (pgd_eval_batch_norm),
-// and the kernel that makes such planes from a nodal P1 mode (pgd_cell_gradient).  What happens to a value once it
-// is formed is the same in all four kernels: see "the reduction epilogue" below.
+// the kernel that makes such planes from a nodal P1 mode (pgd_cell_gradient), and the two norm kernels once more with the planes
+// formed inside them from the nodal modes, never stored (pgd_eval_batch_grad).  What happens to a value once it is formed is the
+// same in all of them: see "the reduction epilogue" below.
 #include "pgd_internal.h"
 
 #include <cmath>
@@ -355,6 +356,62 @@ struct EvalNormShape {
     static constexpr int RS = RB + (T == 1 ? 0 : 16);      // row stride of the staged values in doubles
 };
 
+// A row block of the matrix-unit norm kernels once its B fragments are where they are read (s_f staged and the barrier passed, or
+// global memory): the sample tiles of this wave, then the per-row step.  Whatever filled s_f, from here on the kernels are one text.
+template <int T, bool LDSB>
+__device__ __forceinline__ void eval_norm_tiles(const EvalModes &M, int k, int kt, int q, int64_t n, const double *__restrict__ cf, int cs,
+                                                int64_t j0, int want, int first, double thr, const EvalOut &O, const double *s_f,
+                                                double *s_mn, double *s_mx, double *s_env, int64_t row0) {
+    constexpr int RS = EvalNormShape<T>::RS;
+    const double INF = __builtin_huge_val();
+    const int kp = 4 * kt, ntile = ((cs + 15) & ~15) >> 4;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 15, lq = lane >> 4;
+    bool rv[T];
+    double emn[T], emx[T];
+    int ecnt[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        rv[j] = row0 + 16 * j + lr < n;
+        emn[j] = INF; emx[j] = -INF; ecnt[j] = 0;
+    }
+    for (int st = wv; st < ntile; st += 4) {
+        d4_t ss[T];
+#pragma unroll
+        for (int j = 0; j < T; ++j) ss[j] = d4_t{0.0, 0.0, 0.0, 0.0};
+        const double *cp = cf + (int64_t)st * kt * 64 + lane;
+        for (int i = 0; i < q; ++i) {
+            d4_t acc[T];
+#pragma unroll
+            for (int j = 0; j < T; ++j) acc[j] = d4_t{0.0, 0.0, 0.0, 0.0};
+            for (int s = 0; s < kt; ++s) {
+                const double a = cp[s * 64];
+#pragma unroll
+                for (int j = 0; j < T; ++j) {
+                    double b;
+                    if (LDSB) {
+                        b = s_f[(i * kp + 4 * s + lq) * RS + 16 * j + lr];
+                    } else {
+                        const int t = 4 * s + lq;
+                        b = (t < k && rv[j]) ? M.p[t][(int64_t)i * n + row0 + 16 * j + lr] : 0.0;
+                    }
+                    acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < T; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ss[j][r] = fma(acc[j][r], acc[j][r], ss[j][r]);
+        }
+        d4_t v[T];
+#pragma unroll
+        for (int j = 0; j < T; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[j][r] = sqrt(ss[j][r]);
+        eval_tile_step<T>(v, rv, emn, emx, ecnt, st, cs, j0, n, row0, want, thr, O, s_mn, s_mx);
+    }
+    eval_block_step<T>(emn, emx, ecnt, s_env, row0, n, want, first, O);
+}
+
 template <int T, bool LDSB>
 __global__ __launch_bounds__(TPB) void k_eval_norm_mfma(EvalModes M, int k, int kt, int q, int64_t n, const double *__restrict__ cf, int cs,
                                                         int64_t j0, int want, int first, double thr, EvalOut O) {
@@ -362,12 +419,11 @@ __global__ __launch_bounds__(TPB) void k_eval_norm_mfma(EvalModes M, int k, int 
     constexpr int RB = EvalNormShape<T>::RB, RS = EvalNormShape<T>::RS;
     const double INF = __builtin_huge_val();
     const int kp = 4 * kt;
-    const int cs16 = (cs + 15) & ~15, ntile = cs16 >> 4;
+    const int cs16 = (cs + 15) & ~15;
     double *s_f = s_dyn;                                   // q x kp rows of RS: plane i, mode t at row i kp + t
     double *s_mn = s_f + (LDSB ? (size_t)q * kp * RS : 0);
     double *s_mx = s_mn + cs16;
     double *s_env = s_mx + cs16;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 15, lq = lane >> 4;
     for (int j = threadIdx.x; j < cs16; j += TPB) { s_mn[j] = INF; s_mx[j] = -INF; }
     const int64_t nblk = (n + RB - 1) / RB;
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -382,50 +438,7 @@ __global__ __launch_bounds__(TPB) void k_eval_norm_mfma(EvalModes M, int k, int 
             }
         }
         __syncthreads();
-        bool rv[T];
-        double emn[T], emx[T];
-        int ecnt[T];
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            rv[j] = row0 + 16 * j + lr < n;
-            emn[j] = INF; emx[j] = -INF; ecnt[j] = 0;
-        }
-        for (int st = wv; st < ntile; st += 4) {
-            d4_t ss[T];
-#pragma unroll
-            for (int j = 0; j < T; ++j) ss[j] = d4_t{0.0, 0.0, 0.0, 0.0};
-            const double *cp = cf + (int64_t)st * kt * 64 + lane;
-            for (int i = 0; i < q; ++i) {
-                d4_t acc[T];
-#pragma unroll
-                for (int j = 0; j < T; ++j) acc[j] = d4_t{0.0, 0.0, 0.0, 0.0};
-                for (int s = 0; s < kt; ++s) {
-                    const double a = cp[s * 64];
-#pragma unroll
-                    for (int j = 0; j < T; ++j) {
-                        double b;
-                        if (LDSB) {
-                            b = s_f[(i * kp + 4 * s + lq) * RS + 16 * j + lr];
-                        } else {
-                            const int t = 4 * s + lq;
-                            b = (t < k && rv[j]) ? M.p[t][(int64_t)i * n + row0 + 16 * j + lr] : 0.0;
-                        }
-                        acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < T; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) ss[j][r] = fma(acc[j][r], acc[j][r], ss[j][r]);
-            }
-            d4_t v[T];
-#pragma unroll
-            for (int j = 0; j < T; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[j][r] = sqrt(ss[j][r]);
-            eval_tile_step<T>(v, rv, emn, emx, ecnt, st, cs, j0, n, row0, want, thr, O, s_mn, s_mx);
-        }
-        eval_block_step<T>(emn, emx, ecnt, s_env, row0, n, want, first, O);
+        eval_norm_tiles<T, LDSB>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O, s_f, s_mn, s_mx, s_env, row0);
     }
     eval_store_partials<TPB>(O, s_mn, s_mx, cs16, want);
 }
@@ -523,21 +536,25 @@ static size_t eval_norm_lds(int t, bool ldsb, int q, int kt, int cs16) {
     return ((ldsb ? (size_t)q * 4 * kt * rs : 0) + 2 * (size_t)cs16 + 12 * rb) * sizeof(double);
 }
 
-template <int T>
-static bool eval_norm_raise_lds(size_t lds) {
-    if (hipFuncSetAttribute((const void *)k_eval_norm_mfma<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) return true;
+// (the attribute belongs to one instantiation: every kernel that may run with more than 64 KiB raises its own)
+static bool eval_raise_lds(const void *kern, size_t lds) {
+    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) return true;
     (void)hipGetLastError();
     return false;
 }
 
+template <int T>
+static bool eval_norm_raise_lds(size_t lds) { return eval_raise_lds((const void *)k_eval_norm_mfma<T, true>, lds); }
+
 // 64, 32 or 16 rows per workgroup, the largest whose q planes fit 64 KiB beside the extrema; else 16 rows in up to 160 KiB (the
-// function attribute is raised for it); else 16 rows with the fragments read from global memory
-static EvalNormCfg eval_norm_choose(int q, int kt, int cs16_max) {
+// function attribute is raised for it, by `raise`: the 16-row kernel of the caller); else 16 rows with the fragments read from
+// global memory, which the fused kernels do not have: they refuse
+static EvalNormCfg eval_norm_choose(int q, int kt, int cs16_max, bool (*raise)(size_t)) {
     EvalNormCfg cfg;
     for (int t = 4; t >= 1; t >>= 1)
         if (eval_norm_lds(t, true, q, kt, cs16_max) <= EVAL_LDS_PLAIN) { cfg.t = t; cfg.ldsb = true; return cfg; }
     const size_t lds = eval_norm_lds(1, true, q, kt, cs16_max);
-    if (lds <= EVAL_LDS_MAX && eval_norm_raise_lds<1>(lds)) cfg.ldsb = true;
+    if (lds <= EVAL_LDS_MAX && raise(lds)) cfg.ldsb = true;
     return cfg;
 }
 
@@ -570,14 +587,13 @@ void eval_release(Ctx *c) {
 // L arrives by value.  No atomics; the stores of a plane are coalesced.
 struct GradL { double a[EVAL_QMAX * EVAL_QMAX]; };      // row-major q x qin
 
-template <int G, int NC>
-__global__ __launch_bounds__(TPB) void k_cell_gradient(const int4 *__restrict__ cells, const double *__restrict__ coords, int64_t nv, int64_t nc,
-                                                       const double *__restrict__ u, GradL L, int q, const double *__restrict__ scale,
-                                                       double *__restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (e >= nc) return;
-    const int4 rec = cells[e];
-    const int v[4] = {rec.x, rec.y, rec.z, rec.w};
+// The per-cell arithmetic of k_cell_gradient and of the fused kernels further down, in two steps because the fused kernels walk many
+// modes on one cell: cell_inverse (the record's used entries, the edge matrix, the cofactor inverse - once per cell) and cell_planes
+// (du, g, L g and the scale - once per cell and mode; `put(i, value)` takes plane i).  The loop over the planes is unrolled to
+// EVAL_QMAX with a guard, so a caller that keeps the planes in registers can.
+template <int G>
+__device__ __forceinline__ void cell_inverse(const int4 rec, const double *__restrict__ coords, int64_t nv, int (&v)[4], double (&J)[G][G]) {
+    v[0] = rec.x; v[1] = rec.y; v[2] = rec.z; v[3] = rec.w;      // (entries above G are unused lanes of the record: never an index)
     double E[G][G];                                  // E[a][d] = x_{a+1}[d] - x_0[d]
 #pragma unroll
     for (int d = 0; d < G; ++d) {
@@ -586,7 +602,7 @@ __global__ __launch_bounds__(TPB) void k_cell_gradient(const int4 *__restrict__ 
 #pragma unroll
         for (int a = 0; a < G; ++a) E[a][d] = x[v[a + 1]] - x0;
     }
-    double J[G][G];                                  // J[a][d] = d xi_a / d x_d: the inverse of E^T
+    // J[a][d] = d xi_a / d x_d: the inverse of E^T
     if constexpr (G == 1) {
         J[0][0] = 1.0 / E[0][0];
     } else if constexpr (G == 2) {
@@ -610,6 +626,11 @@ __global__ __launch_bounds__(TPB) void k_cell_gradient(const int4 *__restrict__ 
 #pragma unroll
             for (int d = 0; d < 3; ++d) J[a][d] = C[a][d] * inv;      // inv(E)[d][a] = C[a][d] / det, and J = inv(E^T) = inv(E)^T
     }
+}
+
+template <int G, int NC, class Put>
+__device__ __forceinline__ void cell_planes(const int (&v)[4], const double (&J)[G][G], const double *__restrict__ u, const GradL &L, int q,
+                                            double sc, Put put) {
     double g[NC * G];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -625,20 +646,218 @@ __global__ __launch_bounds__(TPB) void k_cell_gradient(const int4 *__restrict__ 
             g[c * G + d] = acc;
         }
     }
-    const double sc = scale ? scale[e] : 1.0;
-    for (int i = 0; i < q; ++i) {
-        const double *row = L.a + i * (NC * G);
-        double acc = row[0] * g[0];
 #pragma unroll
-        for (int j = 1; j < NC * G; ++j) acc = fma(row[j], g[j], acc);
-        out[(int64_t)i * nc + e] = sc * acc;
+    for (int i = 0; i < EVAL_QMAX; ++i) {
+        if (i < q) {
+            const double *row = L.a + i * (NC * G);
+            double acc = row[0] * g[0];
+#pragma unroll
+            for (int j = 1; j < NC * G; ++j) acc = fma(row[j], g[j], acc);
+            put(i, sc * acc);
+        }
     }
+}
+
+template <int G, int NC>
+__global__ __launch_bounds__(TPB) void k_cell_gradient(const int4 *__restrict__ cells, const double *__restrict__ coords, int64_t nv, int64_t nc,
+                                                       const double *__restrict__ u, GradL L, int q, const double *__restrict__ scale,
+                                                       double *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (e >= nc) return;
+    int v[4];
+    double J[G][G];
+    cell_inverse<G>(cells[e], coords, nv, v, J);
+    cell_planes<G, NC>(v, J, u, L, q, scale ? scale[e] : 1.0, [&](int i, double p) { out[(int64_t)i * nc + e] = p; });
 }
 
 template <int G, int NC>
 static void cell_gradient_launch(Ctx *c, const Mesh *b, const double *u, const GradL &L, int q, const double *scale, double *out) {
     const int grid = (int)((b->nc + TPB - 1) / TPB);
     k_cell_gradient<G, NC><<<grid, TPB, 0, c->stream>>>(b->cells, b->coords, b->nv, b->nc, u, L, q, scale, out);
+}
+
+// ---- pgd_eval_batch_grad: pgd_eval_batch_norm on planes that are never stored.  The planes of a cell are a local, linear function
+// of the nodal mode (cell_inverse once, cell_planes per mode), so the kernels form them where the stored path reads them: the
+// matrix-unit kernel in the staging step of a row block of cells (then it IS k_eval_norm_mfma: eval_norm_tiles), the plain kernel in
+// front of its fma chains.  The nodal values are gathers through the cell record - each node is referenced by every cell around it,
+// so they come from L2 / L1 rather than HBM - and every sample chunk gathers again.  The scalar layout holds cells and coordinates;
+// nodal values sit at node * NC + c.  Cells beyond nc read no record and stage zeros, as the mode rows k <= t < kp do.
+struct EvalGradSrc {
+    const int4 *cells;
+    const double *coords, *scale;      // scale: one entry per cell, or null
+    int64_t nv;
+    GradL L;
+};
+// (the kernel arguments are passed by value: modes, L and the scalars must stay below the 4 KiB the runtime takes)
+static_assert(sizeof(EvalModes) + sizeof(EvalGradSrc) + sizeof(EvalOut) + 128 <= 4096, "kernel arguments of the fused kernels");
+
+template <int T, int G, int NC>
+__global__ __launch_bounds__(TPB) void k_eval_grad_mfma(EvalModes M, int k, int kt, int q, EvalGradSrc S, int64_t n, const double *__restrict__ cf,
+                                                        int cs, int64_t j0, int want, int first, double thr, EvalOut O) {
+    extern __shared__ double s_dyn[];
+    constexpr int RB = EvalNormShape<T>::RB, RS = EvalNormShape<T>::RS, TPC = TPB / RB;      // TPC threads share a cell's modes
+    const double INF = __builtin_huge_val();
+    const int kp = 4 * kt;
+    const int cs16 = (cs + 15) & ~15;
+    double *s_f = s_dyn;                                   // q x kp rows of RS: plane i, mode t at row i kp + t
+    double *s_mn = s_f + (size_t)q * kp * RS;
+    double *s_mx = s_mn + cs16;
+    double *s_env = s_mx + cs16;
+    const int d = threadIdx.x % RB, part = threadIdx.x / RB;
+    for (int j = threadIdx.x; j < cs16; j += TPB) { s_mn[j] = INF; s_mx[j] = -INF; }
+    const int64_t nblk = (n + RB - 1) / RB;
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t row0 = blk * RB, e = row0 + d;
+        const bool cv = e < n;
+        __syncthreads();
+        int v[4] = {0, 0, 0, 0};
+        double J[G][G];
+        double sc = 1.0;
+        if (cv) {
+            cell_inverse<G>(S.cells[e], S.coords, S.nv, v, J);
+            if (S.scale) sc = S.scale[e];
+        }
+        for (int t = part; t < kp; t += TPC) {
+            double *col = s_f + (size_t)t * RS + d;
+            if (cv && t < k) {
+                cell_planes<G, NC>(v, J, M.p[t], S.L, q, sc, [&](int i, double p) { col[(size_t)i * kp * RS] = p; });
+            } else {
+                for (int i = 0; i < q; ++i) col[(size_t)i * kp * RS] = 0.0;
+            }
+        }
+        __syncthreads();
+        eval_norm_tiles<T, true>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O, s_f, s_mn, s_mx, s_env, row0);
+    }
+    eval_store_partials<TPB>(O, s_mn, s_mx, cs16, want);
+}
+
+// k_eval_norm_plain with the planes of mode t formed once per pass and used by all q chains: q x NS accumulators, the chains over t
+// and the squares over i in ascending order as there
+template <int G, int NC>
+__global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_grad_plain(EvalModes M, int k, int kt, int q, EvalGradSrc S, int64_t n,
+                                                                    const double *__restrict__ cf, int cs, int64_t j0, int want, int first,
+                                                                    double thr, EvalOut O) {
+    extern __shared__ double s_dyn[];
+    constexpr int NS = EVAL_PLAIN_NS;
+    const double INF = __builtin_huge_val();
+    const int cs16 = (cs + 15) & ~15;
+    double *s_mn = s_dyn, *s_mx = s_dyn + cs16;
+    const int lane = threadIdx.x;
+    for (int j = lane; j < cs16; j += EVAL_PLAIN_TPB) { s_mn[j] = INF; s_mx[j] = -INF; }
+    __syncthreads();
+    const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t row = blk * EVAL_PLAIN_TPB + lane;
+        const bool rv = row < n;
+        int v[4] = {0, 0, 0, 0};
+        double J[G][G];
+        double sc = 1.0;
+        if (rv) {
+            cell_inverse<G>(S.cells[row], S.coords, S.nv, v, J);
+            if (S.scale) sc = S.scale[row];
+        }
+        double emn = INF, emx = -INF, ect = 0.0;
+        for (int jb = 0; jb < cs16; jb += NS) {
+            double acc[EVAL_QMAX][NS];
+#pragma unroll
+            for (int i = 0; i < EVAL_QMAX; ++i)
+#pragma unroll
+                for (int c = 0; c < NS; ++c) acc[i][c] = 0.0;
+            for (int t = 0; t < k; ++t) {
+                double p[EVAL_QMAX];
+#pragma unroll
+                for (int i = 0; i < EVAL_QMAX; ++i) p[i] = 0.0;
+                if (rv) cell_planes<G, NC>(v, J, M.p[t], S.L, q, sc, [&](int i, double x) { p[i] = x; });
+                const double *cp = cf + eval_cf_index(kt, t, jb);
+#pragma unroll
+                for (int i = 0; i < EVAL_QMAX; ++i)
+                    if (i < q) {
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) acc[i][c] = fma(cp[c], p[i], acc[i][c]);
+                    }
+            }
+            double ss[NS];
+#pragma unroll
+            for (int c = 0; c < NS; ++c) ss[c] = 0.0;
+#pragma unroll
+            for (int i = 0; i < EVAL_QMAX; ++i)
+                if (i < q) {
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) ss[c] = fma(acc[i][c], acc[i][c], ss[c]);
+                }
+#pragma unroll
+            for (int c = 0; c < NS; ++c) ss[c] = sqrt(ss[c]);            // from here on the values
+            eval_plain_step(ss, jb, cs, j0, n, row, rv, want, thr, O, s_mn, s_mx, emn, emx, ect);
+        }
+        if (rv) eval_row_accumulate(O, row, emn, emx, ect, want, first);
+    }
+    eval_store_partials<EVAL_PLAIN_TPB>(O, s_mn, s_mx, cs16, want);
+}
+
+// The instantiations of one (gdim, ncomp): the matrix-unit kernel per row block, the plain kernel, the LDS attribute of the 16-row one
+typedef int (*eval_grad_launch_t)(Ctx *, const EvalModes &, int, int, int, const EvalGradSrc &, int64_t, const double *, int, int64_t, int,
+                                  int, double, const EvalOut &, int, int *);
+struct EvalGradFns {
+    eval_grad_launch_t mfma[3] = {nullptr, nullptr, nullptr};      // 16, 32, 64 cells per workgroup
+    eval_grad_launch_t plain = nullptr;
+    bool (*raise)(size_t) = nullptr;
+};
+
+// What pgd_eval_batch_grad hands to eval_batch_run beside the arguments of pgd_eval_batch_norm
+struct EvalGrad {
+    EvalGradSrc src;
+    EvalGradFns fn;
+    int64_t mode_len, nc;       // nodes x components; cells
+    const Vec *scale;
+};
+
+template <int T, int G, int NC>
+static int eval_launch_grad(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf, int cs,
+                            int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
+    const size_t lds = eval_norm_lds(T, true, q, kt, (cs + 15) & ~15);
+    return eval_launch_persistent(c, k_eval_grad_mfma<T, G, NC>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q, S, n, cf,
+                                  cs, j0, want, first, thr, O);
+}
+
+template <int G, int NC>
+static int eval_launch_grad_plain(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf, int cs,
+                                  int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
+    const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
+    const int g = (int)(nblk < grid_cap ? nblk : grid_cap);
+    const size_t lds = (size_t)2 * ((cs + 15) & ~15) * sizeof(double);
+    k_eval_grad_plain<G, NC><<<g, EVAL_PLAIN_TPB, lds, c->stream>>>(M, k, kt, q, S, n, cf, cs, j0, want, first, thr, O);
+    PGD_LAUNCH_CHECK(c);
+    *grid_out = g;
+    return PGD_OK;
+}
+
+template <int G, int NC>
+static bool eval_grad_raise_lds(size_t lds) { return eval_raise_lds((const void *)k_eval_grad_mfma<1, G, NC>, lds); }
+
+template <int G, int NC>
+static EvalGradFns eval_grad_fns() {
+    EvalGradFns f;
+    f.mfma[0] = eval_launch_grad<1, G, NC>;
+    f.mfma[1] = eval_launch_grad<2, G, NC>;
+    f.mfma[2] = eval_launch_grad<4, G, NC>;
+    f.plain = eval_launch_grad_plain<G, NC>;
+    f.raise = eval_grad_raise_lds<G, NC>;
+    return f;
+}
+
+static bool eval_grad_pick(int G, int NC, EvalGradFns *f) {
+    switch (G * 10 + NC) {
+        case 11: *f = eval_grad_fns<1, 1>(); return true;
+        case 12: *f = eval_grad_fns<1, 2>(); return true;
+        case 13: *f = eval_grad_fns<1, 3>(); return true;
+        case 21: *f = eval_grad_fns<2, 1>(); return true;
+        case 22: *f = eval_grad_fns<2, 2>(); return true;
+        case 23: *f = eval_grad_fns<2, 3>(); return true;
+        case 31: *f = eval_grad_fns<3, 1>(); return true;
+        case 32: *f = eval_grad_fns<3, 2>(); return true;
+        case 33: *f = eval_grad_fns<3, 3>(); return true;
+        default: return false;
+    }
 }
 
 }  // namespace pgd
@@ -649,8 +868,9 @@ extern "C" {
 
 // The body of pgd_eval_batch (q == 0: the signed values, k_eval_mfma / k_eval_plain) and of pgd_eval_batch_norm (1 <= q <= 9: every
 // mode is q planes, the norm kernels): the checks, the chunking and the coefficient staging are the same, only the launch differs.
-// fn: the entry point's name for the messages.
-static int eval_batch_run(Ctx *c, const char *fn, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want,
+// pgd_eval_batch_grad is the second of these with `gs`: the modes are nodal, the planes are formed in the kernel, the outputs have one
+// entry per cell.  fn: the entry point's name for the messages.
+static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want,
                           double threshold, double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h,
                           pgd_handle fields_h) {
     // ---- every argument is checked before anything is launched
@@ -669,7 +889,12 @@ static int eval_batch_run(Ctx *c, const char *fn, const pgd_handle *modes, int k
         M.p[t] = mv[t]->d;
     }
     for (int t = k; t < EVAL_KMAX; ++t) M.p[t] = nullptr;
-    if (q > 0) {                                     // q planes of n entries each
+    if (gs) {                                        // nodal modes, values per cell
+        if (n != gs->mode_len)
+            return fail(c, PGD_ERR_INVALID, "%s: the modes have %lld entries, nodes x components = %lld are needed", fn, (long long)n,
+                        (long long)gs->mode_len);
+        n = gs->nc;
+    } else if (q > 0) {                              // q planes of n entries each
         if (n % q) return fail(c, PGD_ERR_INVALID, "%s: the modes have %lld entries, no multiple of q = %d", fn, (long long)n, q);
         n /= q;
     }
@@ -696,6 +921,7 @@ static int eval_batch_run(Ctx *c, const char *fn, const pgd_handle *modes, int k
             return fail(c, PGD_ERR_INVALID, "%s: %s has %lld entries, %lld are needed", fn, oname[i], (long long)outs[i]->n, (long long)need);
         for (int t = 0; t < k; ++t)
             if (mv[t] == outs[i]) return fail(c, PGD_ERR_INVALID, "%s: mode %d aliases %s", fn, t, oname[i]);
+        if (gs && gs->scale && gs->scale == outs[i]) return fail(c, PGD_ERR_INVALID, "%s: the scale aliases %s", fn, oname[i]);
         for (int i2 = 0; i2 < i; ++i2)
             if (outs[i2] == outs[i]) return fail(c, PGD_ERR_INVALID, "%s: %s aliases %s", fn, oname[i], oname[i2]);
     }
@@ -714,6 +940,13 @@ static int eval_batch_run(Ctx *c, const char *fn, const pgd_handle *modes, int k
     // most workgroups either kernel can be launched with: bounds the partial rows
     int64_t gmax = (int64_t)c->num_cu * 8;
     if (gmax > grid_cap) gmax = grid_cap;
+
+    EvalNormCfg ncfg;
+    if (mfma && q > 0) ncfg = eval_norm_choose(q, kt, cs16_max, gs ? gs->fn.raise : (bool (*)(size_t))eval_norm_raise_lds<1>);
+    if (gs && mfma && !ncfg.ldsb)                    // (no fragments from global memory here: there are no planes to read)
+        return fail(c, PGD_ERR_LIMIT, "%s: q = %d planes of k = %d modes do not fit a workgroup: 16 cells need %zu bytes of LDS "
+                    "(8 q 4 ceil(k / 4) 16 and the extrema), the limit is %zu; PGD_TUNE_EVAL_VARIANT = 0 has no such limit", fn, q, k,
+                    eval_norm_lds(1, true, q, kt, cs16_max), EVAL_LDS_MAX);
 
     // pinned staging of the coefficients in fragment order, two chunks deep (an event per half says when its copy is done)
     const size_t pin_bytes = 2 * cf_doubles * sizeof(double);
@@ -745,8 +978,6 @@ static int eval_batch_run(Ctx *c, const char *fn, const pgd_handle *modes, int k
     };
     if (rc != PGD_OK) { release(); return rc; }
 
-    EvalNormCfg ncfg;
-    if (mfma && q > 0) ncfg = eval_norm_choose(q, kt, cs16_max);
     if (q > 0) {
         c->eval_norm_rows = mfma ? 16 * ncfg.t : EVAL_PLAIN_TPB;
         c->eval_norm_staged = !mfma ? 0 : !ncfg.ldsb ? 0 : eval_norm_lds(ncfg.t, true, q, kt, cs16_max) > EVAL_LDS_PLAIN ? 2 : 1;
@@ -780,7 +1011,10 @@ static int eval_batch_run(Ctx *c, const char *fn, const pgd_handle *modes, int k
             const double *cf = (const double *)p_cf;
             const int first = j0 == 0;
             int g = 0;
-            if (mfma && q > 0) {
+            if (gs) {
+                const eval_grad_launch_t launch = !mfma ? gs->fn.plain : gs->fn.mfma[ncfg.t == 4 ? 2 : ncfg.t == 2 ? 1 : 0];
+                PGD_TRY(launch(c, M, k, kt, q, gs->src, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g));
+            } else if (mfma && q > 0) {
                 if (!ncfg.ldsb) PGD_TRY((eval_launch_norm<1, false>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
                 else if (ncfg.t == 4) PGD_TRY((eval_launch_norm<4, true>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
                 else if (ncfg.t == 2) PGD_TRY((eval_launch_norm<2, true>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
@@ -824,14 +1058,45 @@ static int eval_batch_run(Ctx *c, const char *fn, const pgd_handle *modes, int k
 int pgd_eval_batch(pgd_handle h, const pgd_handle *modes, int k, const double *coefs, int64_t s, int want, double threshold,
                    double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
     PGD_CTX(c, h);
-    return eval_batch_run(c, "eval_batch", modes, k, 0, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
+    return eval_batch_run(c, "eval_batch", nullptr, modes, k, 0, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
 }
 
 int pgd_eval_batch_norm(pgd_handle h, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want, double threshold,
                         double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
     PGD_CTX(c, h);
     if (q < 1 || q > EVAL_QMAX) return fail(c, PGD_ERR_INVALID, "eval_batch_norm: q = %d planes, 1 .. %d are possible", q, EVAL_QMAX);
-    return eval_batch_run(c, "eval_batch_norm", modes, k, q, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
+    return eval_batch_run(c, "eval_batch_norm", nullptr, modes, k, q, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
+                          fields_h);
+}
+
+int pgd_eval_batch_grad(pgd_handle h, pgd_handle mh, const pgd_handle *modes, int k, const double *L, int q, pgd_handle scale_h,
+                        const double *coefs, int64_t s, int want, double threshold, double *sample_stats, pgd_handle env_min_h,
+                        pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
+    PGD_CTX(c, h);
+    Mesh *m = get_mesh(c, mh);
+    if (!m) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: invalid mesh handle");
+    Mesh *b = m->ncomp > 1 ? get_mesh(c, m->base) : m;          // the scalar layout holds the cells and the coordinates
+    if (!b) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: the blocked layout's base is gone");
+    const int G = b->gdim, NC = m->ncomp;
+    if (b->nvpc != G + 1) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: a P2 layout (%d nodes per cell): P1 only", b->nvpc);
+    if (!b->cells || !b->coords) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: the layout has no cell records");
+    if (q < 1 || q > EVAL_QMAX) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: q = %d rows of L, 1 .. %d are possible", q, EVAL_QMAX);
+    if (!L) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: L is missing");
+    Vec *scale = scale_h ? get_vec(c, scale_h) : nullptr;
+    if (scale_h && (!scale || scale->n != b->nc))
+        return fail(c, PGD_ERR_INVALID, "eval_batch_grad: scale is a vector of one entry per cell (%lld), or 0", (long long)b->nc);
+    EvalGrad gs;
+    if (!eval_grad_pick(G, NC, &gs.fn)) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: gdim = %d with %d components", G, NC);
+    gs.src.cells = b->cells;
+    gs.src.coords = b->coords;
+    gs.src.scale = scale ? scale->d : nullptr;
+    gs.src.nv = b->nv;
+    const int qin = NC * G;
+    for (int i = 0; i < EVAL_QMAX * EVAL_QMAX; ++i) gs.src.L.a[i] = i < q * qin ? L[i] : 0.0;
+    gs.mode_len = b->nv * NC;
+    gs.nc = b->nc;
+    gs.scale = scale;
+    return eval_batch_run(c, "eval_batch_grad", &gs, modes, k, q, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
                           fields_h);
 }
 

@@ -797,7 +797,7 @@ class PGD:
     # ------------------------------------------------- batched evaluation of gradient quantities
     def evaluate_gradient_many(self, fixed_dim, free_dim, coords, attri, quantity="gradient_norm", scale=None, stats=True,
                                envelope=False, threshold=None, fields=False, fields_max_bytes=4 << 30, modes_max_bytes=16 << 30,
-                               sample_chunk=256):
+                               sample_chunk=256, planes="stored"):
         """``evaluate_many`` for a quantity of the spatial gradient of the solution: per cell of the fixed mesh and per sample
         the value ``scale * |L grad u|`` with L = ``fem.gradient_quantity(quantity, ...)`` - "gradient_norm" (with a conductivity
         as ``scale``: the flux magnitude) or "von_mises" (with ``scale`` = 2 mu = E / (1 + nu): the von Mises stress).  ``scale``:
@@ -810,9 +810,18 @@ class PGD:
         (``pgd_eval_batch_norm``).  Device or host as ``evaluate_many`` decides, with the cell count in the place of the dofs;
         the host path is numpy, ``sample_chunk`` samples at a time.
 
+        ``planes`` says where the planes live.  "stored" (default) is the above.  "fused" stores none: the kernel forms the planes
+        of a block of cells from the nodal modes where it would have read them (``pgd_eval_batch_grad``), so nothing is built,
+        cached or bounded by ``modes_max_bytes`` - the way to run many modes on a large mesh; every sample chunk gathers the nodal
+        values again, and the matrix-unit kernel refuses q * K above about 1250 (a ValueError).  On the host "fused" combines the
+        nodal modes per sample chunk and takes the cell gradients of the chunk's fields.  "auto" is "stored" while the planes
+        fit ``modes_max_bytes``, else "fused".
+
         Returns an ``EvalManyResult`` whose Functions live on ``FunctionSpace(mesh, "DG", 0)`` of the fixed mesh; ``max_abs``
         equals ``max``.  Signed components (one row of L, no norm) are ``evaluate_many``-like fields of one plane:
         ``pgd_eval_batch`` on the output of ``pgd_cell_gradient`` gives them."""
+        if planes not in ("stored", "fused", "auto"):
+            raise ValueError("evaluate_gradient_many: planes=%r, \"stored\", \"fused\" or \"auto\" are possible" % (planes,))
         coords = self._check_many(fixed_dim, free_dim, coords, attri)
         S = coords.shape[0]
         att = self.mesh[fixed_dim].attributes[attri]
@@ -845,7 +854,9 @@ class PGD:
             scale_key = float(scale)
             L = L * scale_key
         q, nc = L.shape[0], mesh.num_cells()
-        if K * q * nc * 8 > modes_max_bytes:
+        if planes == "auto":
+            planes = "stored" if K * q * nc * 8 <= modes_max_bytes else "fused"
+        if planes == "stored" and K * q * nc * 8 > modes_max_bytes:
             raise ValueError("evaluate_gradient_many: the derived modes would take %d bytes (%d modes x %d planes x %d cells x "
                              "8), more than modes_max_bytes=%d" % (K * q * nc * 8, K, q, nc, modes_max_bytes))
         if fields and nc * S * 8 > fields_max_bytes:
@@ -854,6 +865,11 @@ class PGD:
         thr = None if threshold is None else float(threshold)
         C = self.mode_factors_many(free_dim, coords, attri)
         be = fem.get_backend()
+        Vc = fem.FunctionSpace(mesh, "DG", 0)
+        if planes == "fused":
+            res = self._evaluate_gradient_fused(be, V, Vc, modes[:K], L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk)
+            res.coefficients = C
+            return res
         device = nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "eval_batch_norm") and hasattr(be, "cell_gradient")
         key = (quantity, K, scale_key, device, id(be), tuple((id(m.vector()), m.vector().version) for m in modes[:K]))
         cache = getattr(att, "_gradient_modes", None)
@@ -861,7 +877,6 @@ class PGD:
             att._gradient_modes = None                       # the old planes go before the new ones are allocated
             cache = att._gradient_modes = _GradientModes(key, be if device else None, mesh, V, modes[:K], L, scale_vec)
             fem.STATS["gradient_mode_builds"] = fem.STATS.get("gradient_mode_builds", 0) + 1
-        Vc = fem.FunctionSpace(mesh, "DG", 0)
         if device:
             res = _eval_many_device(be, lambda st, **kw: be.eval_batch_norm(cache.planes, q, C, stats=st, **kw), Vc, nc, S, stats,
                                     envelope, thr, fields)
@@ -880,6 +895,44 @@ class PGD:
                                   nonnegative=True)
         res.coefficients = C
         return res
+
+    @staticmethod
+    def _evaluate_gradient_fused(be, V, Vc, modes, L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk):
+        """``evaluate_gradient_many(planes="fused")``: no planes are built or kept.  Device: ``pgd_eval_batch_grad`` on the nodal
+        modes.  Host: per sample chunk the nodal product F C, then the cell gradients of the chunk's fields - the einsum of
+        ``_GradientModes`` on the fields instead of the modes."""
+        mesh, K = V.mesh(), len(modes)
+        q, nc, ncomp = L.shape[0], mesh.num_cells(), V._ncomp
+        fem.STATS["eval_gradient_fused_calls"] = fem.STATS.get("eval_gradient_fused_calls", 0) + 1
+        if nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "eval_batch_grad"):
+            handles = [m.vector().dev() for m in modes]
+            sc = scale_vec.dev() if scale_vec is not None else 0
+
+            def call(st, **kw):
+                try:
+                    return be.eval_batch_grad(V._lay.handle(), handles, L, C, scale=sc, stats=st, **kw)
+                except RuntimeError as exc:
+                    if getattr(exc, "code", None) != -4:                  # PGD_ERR_LIMIT
+                        raise
+                    raise ValueError("evaluate_gradient_many(planes=\"fused\"): q = %d planes of K = %d modes are more than the "
+                                     "fused kernel holds for a block of cells (q * K up to about 1250): %s" % (q, K, exc)) from None
+            return _eval_many_device(be, call, Vc, nc, S, stats, envelope, thr, fields)
+        X, cells = mesh.coordinates(), mesh.cells()
+        G = cells.shape[1] - 1
+        Einv = np.linalg.inv(X[cells[:, 1:]] - X[cells[:, :1]])                  # rows of E: the edges x_a - x_0; (cells, d, a)
+        sc = scale_vec.host() if scale_vec is not None else None
+        F = np.stack([m.vector().host() for m in modes], axis=1)                 # (nodes * ncomp, K)
+
+        def norms(j0, step):
+            U = (F @ C[:, j0:j0 + step]).reshape(-1, ncomp, min(step, S - j0))    # (node, component, sample)
+            dU = U[cells[:, 1:]] - U[cells[:, :1]]                                # (cells, a, c, cs)
+            g = np.einsum("eda,eacs->ecds", Einv, dU).reshape(nc, ncomp * G, -1)  # g[c * G + d] = d u_c / d x_d
+            P = np.einsum("ij,ejs->ies", L, g)                                    # (q, cells, cs)
+            if sc is not None:
+                P = P * sc[None, :, None]
+            return np.sqrt((P * P).sum(axis=0))
+        return _eval_many_host(norms, nc, S, sample_chunk, stats, envelope, thr, fields, lambda a: _host_function(Vc, a),
+                               nonnegative=True)
 
     # ------------------------------------------------------ sensor responses and derivatives
     def _check_free(self, free_dim, coord, attri, fixed_dim):

@@ -240,7 +240,23 @@ int pgd_band_solve(pgd_handle ctx, pgd_handle op, pgd_handle b, pgd_handle x);
 /* Row-sharded solve: the host drives the recurrence and places the RCCL halo
  * exchange / all-reduce between these calls (pgdrome_amd/dist.py).  Scalars
  * live in a device bank of PGD_NSLOTS doubles so nothing round-trips to the
- * host inside an iteration; every kernel is a no-op once the done flag is set. */
+ * host inside an iteration; every kernel is a no-op once the done flag is set.
+ *
+ * What holds for every piece below:
+ *   - a row range [r0, r1) has 0 <= r0 <= r1 <= n; r1 < 0 means n.  Rows outside it are neither read for the sums nor written.
+ *   - every slot index a piece takes must lie in [0, PGD_NSLOTS) - for the pieces that write two, three or nine consecutive
+ *     slots, the last one as well.  Anything else is PGD_ERR_INVALID, like a bad range or vectors of different lengths: the
+ *     call is refused before anything is launched, and slots, flags and vectors stay as they were.
+ *   - an EMPTY range (r0 == r1) writes 0 into the slots of its sums - a caller all-reduces them unconditionally - unless the
+ *     piece is a no-op because the done flag is set.
+ *   - the done flag turns pgd_spmv_dot_slot, pgd_pcg_xr_slot, pgd_pcg_check_slot, pgd_pcg_p_slot, pgd_cg_update_slot and
+ *     pgd_cg_scalars_slot into no-ops (vectors, slots and flags untouched).  pgd_pcg_init_slot, pgd_cg_init_slot and
+ *     pgd_pcg_tol_slot act regardless: they start a solve (after pgd_flags_reset).
+ *   - a NaN in a residual sum is a breakdown: done = 1, status = PGD_ERR_SINGULAR.
+ *   - slots written besides the ones a call names - keep `slot`, `base` and the indices passed clear of them:
+ *       S[5]        tol^2, by pgd_cg_scalars_slot(init = 1) (pgd_pcg_tol_slot writes the index it is given)
+ *       S[6]        the last live r.r, by pgd_pcg_check_slot and pgd_cg_scalars_slot
+ *       S[40..42]   scratch of pgd_cg_init_slot (overwritten with its three sums before they are placed)          */
 #define PGD_NSLOTS 64
 int pgd_slots_ptr(pgd_handle ctx, void **device_ptr);
 int pgd_slots_download(pgd_handle ctx, double *out, int first, int count);
@@ -265,13 +281,13 @@ int pgd_atom_product_form(pgd_handle ctx, pgd_handle A, int *form);
  * byte per row (k_spmv_diac_march2) - or 0: none (more than 255 classes, not a grid, too few planes).  The library solves
  * call this themselves for the scaled operator; any later change of the operator's values drops the dictionary.   */
 int pgd_op_classify(pgd_handle ctx, pgd_handle op, int *classes);
-/* y = A x on [r0,r1), slot <- sum w_i y_i (local part)                          */
+/* y = A x on [r0,r1), slot <- sum w_i y_i (local part; 0 for an empty range)    */
 int pgd_spmv_dot_slot(pgd_handle ctx, pgd_handle A, pgd_handle x, pgd_handle y, pgd_handle w,
                       int64_t r0, int64_t r1, int slot);
 /* r = b - q, z = dinv r, p = z on [r0,r1); slots s..s+2 <- (r.z, r.r, b.b)       */
 int pgd_pcg_init_slot(pgd_handle ctx, pgd_handle b, pgd_handle q, pgd_handle dinv, pgd_handle r,
                       pgd_handle z, pgd_handle p, int64_t r0, int64_t r1, int slot);
-/* tol2 slot <- max(rtol^2 S[bb], atol^2); done <- S[rr] <= tol2                  */
+/* tol2 slot <- max(rtol^2 S[bb], atol^2); done <- S[rr] <= tol2 (or breakdown: S[rr] is NaN); not gated by the done flag */
 int pgd_pcg_tol_slot(pgd_handle ctx, double rtol, double atol, int slot_rr, int slot_bb,
                      int slot_tol2);
 /* alpha = S[rz]/S[pq]; x += alpha p; r -= alpha q; z = dinv r;
@@ -279,7 +295,7 @@ int pgd_pcg_tol_slot(pgd_handle ctx, double rtol, double atol, int slot_rr, int 
 int pgd_pcg_xr_slot(pgd_handle ctx, pgd_handle x, pgd_handle r, pgd_handle p, pgd_handle q,
                     pgd_handle dinv, pgd_handle z, int64_t r0, int64_t r1, int slot_rz,
                     int slot_pq, int slot_out);
-/* iters += 1; done <- S[rr] <= S[tol2] (or breakdown)                            */
+/* iters += 1; S[6] <- S[rr]; done <- S[rr] <= S[tol2] (or breakdown)             */
 int pgd_pcg_check_slot(pgd_handle ctx, int slot_rr, int slot_tol2);
 /* beta = S[num]/S[den]; p = z + beta p                                           */
 int pgd_pcg_p_slot(pgd_handle ctx, pgd_handle p, pgd_handle z, int64_t r0, int64_t r1,
@@ -287,13 +303,17 @@ int pgd_pcg_p_slot(pgd_handle ctx, pgd_handle p, pgd_handle z, int64_t r0, int64
 
 /* Single-reduction (Chronopoulos-Gear) form of the same recurrence: one all-reduce of
  * S[base..base+4] = (r.u, r.r, w.u interior / low / high boundary rows) per iteration.
- * S[base+5] alpha, S[base+6] beta, S[base+7] previous r.u, S[base+8] b.b.              */
+ * S[base+5] alpha, S[base+6] beta, S[base+7] previous r.u, S[base+8] b.b.  base + 8 < PGD_NSLOTS.
+ * pgd_cg_init_slot: r = b - q, u = dinv r, p = s = 0 on [r0,r1); S[base], S[base+1], S[base+8] <- (r.u, r.r, b.b); S[40..42]
+ * are its scratch.                                                                       */
 int pgd_cg_init_slot(pgd_handle ctx, pgd_handle b, pgd_handle q, pgd_handle dinv, pgd_handle r,
                      pgd_handle u, pgd_handle p, pgd_handle s, int64_t r0, int64_t r1, int base);
 /* p = u + beta p; s = w + beta s; x += alpha p; r -= alpha s; u = dinv r; S[base..+1] <- (r.u, r.r) */
 int pgd_cg_update_slot(pgd_handle ctx, pgd_handle x, pgd_handle r, pgd_handle u, pgd_handle w,
                        pgd_handle p, pgd_handle s, pgd_handle dinv, int64_t r0, int64_t r1, int base);
-/* after the all-reduce: next alpha/beta, iteration count, done <- r.r <= tol2 (init: also sets tol2) */
+/* after the all-reduce: with g = S[base], d = S[base+2] + S[base+3] + S[base+4]: init: S[5] <- max(rtol^2 S[base+8], atol^2),
+ * otherwise iters += 1; S[6] <- S[base+1]; done <- S[base+1] <= S[5], or breakdown (S[base+1] or d is NaN); then
+ * beta = g / S[base+7] (init: 0), alpha = g / (d - beta g / S[base+5]) (init: g / d), S[base+5..7] <- (alpha, beta, g) */
 int pgd_cg_scalars_slot(pgd_handle ctx, int base, int init, double rtol, double atol);
 
 /* ----------------------------------------------- sharded solve, in-library --- */

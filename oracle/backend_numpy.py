@@ -326,14 +326,25 @@ class NumpyBackend:
     def spmv_dot_slot(self, A, x, y, w, r0, r1, slot):
         if self._flags[0]:
             return
+        r1 = self._hi(x, r1)
         if r1 == r0:
             self.slots[slot] = 0.0
             return
         self.spmv(A, x, y, r0, r1)
         self.slots[slot] = float(self._obj[w][r0:r1] @ self._obj[y][r0:r1])
 
+    # (like the kernels: hi < 0 means "to the end"; a NaN in a residual sum is a breakdown - done = 1, status = PGD_ERR_SINGULAR)
+    ERR_SINGULAR = -5
+
+    def _hi(self, v, hi):
+        return self._obj[v].size if hi < 0 else hi
+
+    def _breakdown(self):
+        self._flags[0], self._flags[2] = 1, self.ERR_SINGULAR
+
     def pcg_init_slot(self, b, q, dinv, r, z, p, lo, hi, slot):
         o = self._obj
+        hi = self._hi(b, hi)
         o[r][lo:hi] = o[b][lo:hi] - o[q][lo:hi]
         o[z][lo:hi] = o[dinv][lo:hi] * o[r][lo:hi]
         o[p][lo:hi] = o[z][lo:hi]
@@ -342,15 +353,19 @@ class NumpyBackend:
         self.slots[slot + 2] = float(o[b][lo:hi] @ o[b][lo:hi])
 
     def pcg_tol_slot(self, rtol, atol, s_rr, s_bb, s_tol2):
-        tol2 = max(rtol * rtol * self.slots[s_bb], atol * atol)
+        t1, t2 = rtol * rtol * self.slots[s_bb], atol * atol
+        tol2 = t1 if t1 > t2 else t2
         self.slots[s_tol2] = tol2
-        if self.slots[s_rr] <= tol2:
+        if np.isnan(self.slots[s_rr]):
+            self._breakdown()
+        elif self.slots[s_rr] <= tol2:
             self._flags[0] = 1
 
     def pcg_xr_slot(self, x, r, p, q, dinv, z, lo, hi, s_rz, s_pq, s_out):
         if self._flags[0]:
             return
         o = self._obj
+        hi = self._hi(x, hi)
         alpha = self.slots[s_rz] / self.slots[s_pq]
         o[x][lo:hi] += alpha * o[p][lo:hi]
         o[r][lo:hi] -= alpha * o[q][lo:hi]
@@ -363,18 +378,22 @@ class NumpyBackend:
             return
         self._flags[1] += 1
         self.slots[6] = self.slots[s_rr]
-        if self.slots[s_rr] <= self.slots[s_tol2]:
+        if np.isnan(self.slots[s_rr]):
+            self._breakdown()
+        elif self.slots[s_rr] <= self.slots[s_tol2]:
             self._flags[0] = 1
 
     def pcg_p_slot(self, p, z, lo, hi, s_num, s_den):
         if self._flags[0]:
             return
         o = self._obj
+        hi = self._hi(p, hi)
         beta = self.slots[s_num] / self.slots[s_den]
         o[p][lo:hi] = o[z][lo:hi] + beta * o[p][lo:hi]
 
     def cg_init_slot(self, b, q, dinv, r, u, p, s, lo, hi, base):
         o = self._obj
+        hi = self._hi(b, hi)
         o[r][lo:hi] = o[b][lo:hi] - o[q][lo:hi]
         o[u][lo:hi] = o[dinv][lo:hi] * o[r][lo:hi]
         o[p][lo:hi] = 0.0
@@ -387,6 +406,7 @@ class NumpyBackend:
         if self._flags[0]:
             return
         o = self._obj
+        hi = self._hi(x, hi)
         alpha, beta = self.slots[base + 5], self.slots[base + 6]
         o[p][lo:hi] = o[u][lo:hi] + beta * o[p][lo:hi]
         o[s][lo:hi] = o[w][lo:hi] + beta * o[s][lo:hi]
@@ -402,10 +422,14 @@ class NumpyBackend:
         S = self.slots
         g, rr, d = S[base], S[base + 1], S[base + 2] + S[base + 3] + S[base + 4]
         if init:
-            S[5] = max(rtol * rtol * S[base + 8], atol * atol)
+            t1, t2 = rtol * rtol * S[base + 8], atol * atol
+            S[5] = t1 if t1 > t2 else t2
         else:
             self._flags[1] += 1
         S[6] = rr
+        if np.isnan(rr) or np.isnan(d):
+            self._breakdown()
+            return
         if rr <= S[5]:
             self._flags[0] = 1
             return

@@ -2064,19 +2064,23 @@ static int range_ok(int64_t n, int64_t &lo, int64_t &hi) {
     return lo >= 0 && lo <= hi && hi <= n;
 }
 
+// `count` consecutive slots from s on lie inside the bank (checked on the host: a bad index never reaches a kernel)
+static bool slot_ok(int s, int count = 1) { return s >= 0 && s + count <= PGD_NSLOTS; }
+
 int pgd_pcg_init_slot(pgd_handle h, pgd_handle bh, pgd_handle qh, pgd_handle dh, pgd_handle rh, pgd_handle zh,
                       pgd_handle ph, int64_t lo, int64_t hi, int slot) {
     PGD_CTX(c, h);
     Vec *b, *q, *d, *r, *z, *p;
     if (get3(c, bh, qh, dh, &b, &q, &d) != PGD_OK || get3(c, rh, zh, ph, &r, &z, &p) != PGD_OK || b->n != r->n ||
-        !range_ok(b->n, lo, hi) || slot < 0 || slot + 3 > PGD_NSLOTS)
+        !range_ok(b->n, lo, hi) || !slot_ok(slot, 3))
         return fail(c, PGD_ERR_INVALID, "pcg_init_slot: invalid arguments");
-    if (hi == lo) return PGD_OK;
+    if (hi == lo) return reduce_partials(c, c->partials, 0, 3, slot, -1, 0, 0);   // an empty range contributes zeros (callers all-reduce the slots unconditionally)
     return pcg_init(c, b->d, q->d, d->d, r->d, z->d, p->d, lo, hi, slot);
 }
 
 int pgd_pcg_tol_slot(pgd_handle h, double rtol, double atol, int slot_rr, int slot_bb, int slot_tol2) {
     PGD_CTX(c, h);
+    if (!slot_ok(slot_rr) || !slot_ok(slot_bb) || !slot_ok(slot_tol2)) return fail(c, PGD_ERR_INVALID, "pcg_tol_slot: slot index out of range");
     k_pcg_tol<<<1, 64, 0, c->stream>>>(c->slots, c->flags, rtol, atol, slot_rr, slot_bb, slot_tol2);
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
@@ -2087,14 +2091,15 @@ int pgd_pcg_xr_slot(pgd_handle h, pgd_handle xh, pgd_handle rh, pgd_handle ph, p
     PGD_CTX(c, h);
     Vec *x, *r, *p, *q, *d, *z;
     if (get3(c, xh, rh, ph, &x, &r, &p) != PGD_OK || get3(c, qh, dh, zh, &q, &d, &z) != PGD_OK || x->n != q->n ||
-        !range_ok(x->n, lo, hi) || slot_out < 0 || slot_out + 2 > PGD_NSLOTS)
+        !range_ok(x->n, lo, hi) || !slot_ok(slot_out, 2) || !slot_ok(slot_rz) || !slot_ok(slot_pq))
         return fail(c, PGD_ERR_INVALID, "pcg_xr_slot: invalid arguments");
-    if (hi == lo) return PGD_OK;
+    if (hi == lo) return reduce_partials(c, c->partials, 0, 2, slot_out, 0, slot_out + 1, 0);   // zeros, unless the done flag is set
     return pcg_xr(c, x->d, r->d, p->d, q->d, d->d, z->d, lo, hi, slot_rz, slot_pq, slot_out, 0, 0);
 }
 
 int pgd_pcg_check_slot(pgd_handle h, int slot_rr, int slot_tol2) {
     PGD_CTX(c, h);
+    if (!slot_ok(slot_rr) || !slot_ok(slot_tol2)) return fail(c, PGD_ERR_INVALID, "pcg_check_slot: slot index out of range");
     k_pcg_check<<<1, 64, 0, c->stream>>>(c->slots, c->flags, slot_rr, slot_tol2);
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
@@ -2103,7 +2108,8 @@ int pgd_pcg_check_slot(pgd_handle h, int slot_rr, int slot_tol2) {
 int pgd_pcg_p_slot(pgd_handle h, pgd_handle ph, pgd_handle zh, int64_t lo, int64_t hi, int slot_num, int slot_den) {
     PGD_CTX(c, h);
     Vec *p = get_vec(c, ph), *z = get_vec(c, zh);
-    if (!p || !z || p->n != z->n || !range_ok(p->n, lo, hi)) return fail(c, PGD_ERR_INVALID, "pcg_p_slot: invalid arguments");
+    if (!p || !z || p->n != z->n || !range_ok(p->n, lo, hi) || !slot_ok(slot_num) || !slot_ok(slot_den))
+        return fail(c, PGD_ERR_INVALID, "pcg_p_slot: invalid arguments");
     if (hi == lo) return PGD_OK;
     if ((lo & 1) == 0) k_pcg_p<true><<<grid_for((hi - lo + 1) / 2), TPB, 0, c->stream>>>(p->d, z->d, lo, hi, c->slots, slot_num, slot_den, c->flags);
     else k_pcg_p<false><<<grid_for(hi - lo), TPB, 0, c->stream>>>(p->d, z->d, lo, hi, c->slots, slot_num, slot_den, c->flags);
@@ -2117,13 +2123,14 @@ int pgd_cg_init_slot(pgd_handle h, pgd_handle bh, pgd_handle qh, pgd_handle dh, 
     Vec *b, *q, *d, *r, *u, *p;
     Vec *s = get_vec(c, sh);
     if (get3(c, bh, qh, dh, &b, &q, &d) != PGD_OK || get3(c, rh, uh, ph, &r, &u, &p) != PGD_OK || !s ||
-        b->n != r->n || s->n != b->n || !range_ok(b->n, lo, hi) || base < 0 || base + 9 > PGD_NSLOTS)
+        b->n != r->n || s->n != b->n || !range_ok(b->n, lo, hi) || !slot_ok(base, 9))
         return fail(c, PGD_ERR_INVALID, "cg_init_slot: invalid arguments");
-    if (hi == lo) return PGD_OK;
-    const int g = grid_for(hi - lo);
+    const int g = hi > lo ? grid_for(hi - lo) : 0;      // (an empty range: no partial sums, the slots become zeros)
     PGD_TRY(ensure_partials(c, 4 * (int64_t)MAX_VEC_BLOCKS));
-    k_cg_init<<<g, TPB, 0, c->stream>>>(b->d, q->d, d->d, r->d, u->d, p->d, s->d, lo, hi, c->partials);
-    PGD_LAUNCH_CHECK(c);
+    if (g) {
+        k_cg_init<<<g, TPB, 0, c->stream>>>(b->d, q->d, d->d, r->d, u->d, p->d, s->d, lo, hi, c->partials);
+        PGD_LAUNCH_CHECK(c);
+    }
     // (r.u, r.r) -> S[base], S[base+1]; b.b -> S[base+8]: reduce 3 values to a scratch triple, then place b.b
     PGD_TRY(reduce_partials(c, c->partials, g, 3, 40, -1, 0, 0));
     PGD_HIP(c, hipMemcpyAsync(c->slots + base, c->slots + 40, 2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -2137,20 +2144,21 @@ int pgd_cg_update_slot(pgd_handle h, pgd_handle xh, pgd_handle rh, pgd_handle uh
     Vec *x, *r, *u, *w, *p, *s;
     Vec *d = get_vec(c, dh);
     if (get3(c, xh, rh, uh, &x, &r, &u) != PGD_OK || get3(c, wh, ph, sh, &w, &p, &s) != PGD_OK || !d ||
-        x->n != w->n || d->n != x->n || !range_ok(x->n, lo, hi) || base < 0 || base + 9 > PGD_NSLOTS)
+        x->n != w->n || d->n != x->n || !range_ok(x->n, lo, hi) || !slot_ok(base, 9))
         return fail(c, PGD_ERR_INVALID, "cg_update_slot: invalid arguments");
-    if (hi == lo) return PGD_OK;
-    const int g = grid_for(hi - lo);
+    const int g = hi > lo ? grid_for(hi - lo) : 0;      // (an empty range: zeros, unless the done flag is set)
     PGD_TRY(ensure_partials(c, 4 * (int64_t)MAX_VEC_BLOCKS));
-    k_cg_update<<<g, TPB, 0, c->stream>>>(x->d, r->d, u->d, w->d, p->d, s->d, d->d, lo, hi, c->slots, base,
-                                          c->partials, c->flags);
-    PGD_LAUNCH_CHECK(c);
+    if (g) {
+        k_cg_update<<<g, TPB, 0, c->stream>>>(x->d, r->d, u->d, w->d, p->d, s->d, d->d, lo, hi, c->slots, base,
+                                              c->partials, c->flags);
+        PGD_LAUNCH_CHECK(c);
+    }
     return reduce_partials(c, c->partials, g, 2, base, 0, 0, 0);
 }
 
 int pgd_cg_scalars_slot(pgd_handle h, int base, int init, double rtol, double atol) {
     PGD_CTX(c, h);
-    if (base < 0 || base + 9 > PGD_NSLOTS) return fail(c, PGD_ERR_INVALID, "cg_scalars_slot: bad slot base");
+    if (!slot_ok(base, 9)) return fail(c, PGD_ERR_INVALID, "cg_scalars_slot: bad slot base");
     k_cg_scalars<<<1, 64, 0, c->stream>>>(c->slots, c->flags, base, init, rtol, atol);
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;

@@ -7,8 +7,8 @@ import scipy.sparse.linalg as spla
 
 from oracle import fem_numpy as FN
 from pgdrome_amd import fem, problems
-from tests import robin_reference as R
 from tests import vmg_reference as V
+from tests.mg_cycle_cases import family as _family      # (shared with tests/test_mg_cycles_gpu.py)
 
 pytestmark = pytest.mark.gpu
 P = fem.Point
@@ -26,45 +26,6 @@ def hip_backend():
     yield be
     fem.set_backend(old)
     fem.clear_caches()
-
-
-def _far_facets(coords, cells):
-    on = coords[:, 0] >= coords[:, 0].max()
-    return np.array([c[on[c]] for c in cells[on[cells].sum(axis=1) == 3]], dtype=np.int32)
-
-
-def _family(ctx, h, coords, cells, family):
-    """(device atoms, coefficients, Dirichlet dofs, the same operator from the numpy oracle's assembly, handles to free)."""
-    n = coords.shape[0]
-    sets = V.dirichlet_sets(coords)
-    if family == "weighted":
-        w = 1.0 + coords[:, 0] + 4.0 * coords[:, 1] * coords[:, 2]
-        wv = ctx.vec_from(w)
-        atoms, coefs, bc = [ctx.atom_assemble(h, FN.WSTIFF, 0, 0, wv)], [1.0], sets["hull"]
-        A = FN.assemble_atom(coords, cells, FN.WSTIFF, 0, 0, w)
-        return atoms, coefs, bc, A, [wv]
-    if family == "two_material":
-        mask = V.inclusion_mask(coords, cells)
-        assert 0 < mask.sum() < mask.size
-        atoms = [ctx.atom_assemble_cells(h, FN.STIFF, 0, 0, 0, 1 - mask), ctx.atom_assemble_cells(h, FN.STIFF, 0, 0, 0, mask)]
-        A = FN.assemble_atom(coords, cells[mask == 0], FN.STIFF) + 25.0 * FN.assemble_atom(coords, cells[mask != 0], FN.STIFF)
-        return atoms, [1.0, 25.0], sets["face"], A, []
-    if family == "robin":
-        facets = _far_facets(coords, cells)
-        atoms = [ctx.atom_assemble(h, FN.STIFF), ctx.atom_assemble_facets(h, facets)]
-        A = 2.0 * FN.assemble_atom(coords, cells, FN.STIFF) + 3.0 * sps.csr_matrix(R.facet_mass_matrix(coords, facets, n))
-        return atoms, [2.0, 3.0], sets["none"], A, []
-    if family == "constant":
-        # one stencil with the hull eliminated - what PGD_TUNE_PCG_PRECOND = 1 is made for: under 2 it takes the new cycle as well
-        atoms = [ctx.atom_assemble(h, FN.STIFF), ctx.atom_assemble(h, FN.MASS)]
-        A = FN.assemble_atom(coords, cells, FN.STIFF) + 3.0 * FN.assemble_atom(coords, cells, FN.MASS)
-        return atoms, [1.0, 3.0], sets["hull"], A, []
-    # stiffness + mass, eliminated: the face x = min and the face z = max (two faces that meet in an edge, nothing else)
-    lo, hi = coords.min(axis=0), coords.max(axis=0)
-    bc = np.where((coords[:, 0] <= lo[0]) | (coords[:, 2] >= hi[2]))[0]
-    atoms = [ctx.atom_assemble(h, FN.STIFF), ctx.atom_assemble(h, FN.MASS)]
-    A = FN.assemble_atom(coords, cells, FN.STIFF) + 0.5 * FN.assemble_atom(coords, cells, FN.MASS)
-    return atoms, [1.0, 0.5], bc, A, []
 
 
 @pytest.mark.parametrize("family", FAMILIES)

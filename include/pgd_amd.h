@@ -395,7 +395,14 @@ int pgd_pcg_solve_sharded(pgd_handle ctx, pgd_handle A, pgd_handle b, pgd_handle
 /* BiCGStab with Jacobi scaling on the CSR product, for operators that are NOT symmetric (a convection atom
  * u.dx(a) * v * dx on a 2-D / 3-D space, or a 1-D system too long for pgd_band_solve): replaces the MUMPS solve of
  * LinearVariationalSolver for such systems (solver.py:627-636, 704-716).  x holds the start value; stop test
- * ||b - A x|| <= max(rtol ||b||, atol), confirmed on the true residual; PGD_ERR_SINGULAR on repeated breakdown.  */
+ * ||b - A x|| <= max(rtol ||b||, atol), confirmed on the true residual; *rel_res is ||b - A x|| / ||b|| recomputed from
+ * the x returned (after a third second leg of 50 iterations: the recurrence's, started from the true one), also where maxit ran
+ * out (PGD_OK with *iters == maxit).  x after maxit = k is the k-th iterate.  PGD_ERR_SINGULAR on the fifth breakdown of
+ * a call (rhat . v, t . t, omega or rho exactly zero or not a number, each answered by a restart from the current x): x
+ * then holds the iterate the last restart started from (with the half step x += alpha y of a t . t breakdown) - the start
+ * value if no iteration completed, e.g. with a zero on the diagonal - and *iters and *rel_res are NOT reported (they read
+ * 0).  PGD_ERR_INVALID (b and x the same vector, a length that is not the operator's, maxit < 0) is returned before
+ * anything is launched.  */
 int pgd_bicgstab_solve(pgd_handle ctx, pgd_handle A, pgd_handle b, pgd_handle x, double rtol, double atol,
                        int maxit, int *iters, double *rel_res);
 

@@ -116,7 +116,10 @@ extern "C" int pgd_bicgstab_solve(pgd_handle h, pgd_handle oh, pgd_handle bh, pg
     const int64_t n = m->nv;
     *iters = 0; *relres = 0.0;
     if (n == 0) return PGD_OK;
-    PGD_TRY(csr_diag_inv(c, m, o));           // (forms the CSR values of a deferred combine as well)
+    PGD_TRY(csr_diag_inv(c, m, o));
+    // the products below read o->vals: a deferred combine (PGD_TUNE_LAZY_CSR) has left dinv with the diagonal form and no CSR
+    // values yet, so csr_diag_inv has nothing to do and does not form them
+    PGD_TRY(ensure_vals(c, m, o));
     // seven work vectors of the call's own (the context's work buffers belong to the PCG and the Galerkin start)
     struct Work {
         Ctx *c; double *p[7]; size_t bytes;

@@ -533,6 +533,13 @@ int pgd_eval_norm_last_shape(pgd_handle ctx, int *rows, int *staged);
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_PCG_FUSED_MARCH = 57, /* 1 (default): an iteration of PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE is k_pcg1_scalars + ONE march (k_pcg1_fused_march):
+                                the update on overlapped tiles - a one-cell ring of q, r' and p' is formed redundantly, r alternates
+                                between two buffers - and, two planes behind it, the dots p'.Ap' and Ap'.Ap' of the direction it has just
+                                written.  The solve issues one stand-alone dot-only product, of p0.  Same operations and summation orders:
+                                iterates, iteration counts and residuals are those of 0, bit for bit.  Takes precedence over
+                                PGD_TUNE_PCG_FOLD_MARCH.  0: the three-launch loop.  Measured at 256^3 (profiles/pcg_fused_bench.jsonl):
+                                48.09 -> 44.99 ms per step, 161.3 -> 150.5 us per iteration; the three-launch loop's own spread is 0.70 ms */
     PGD_TUNE_PCG_SCALAR_S = 56, /* 1 (default): where pgd_pcg_solve holds the scaled operator as a derived stencil (A itself is one stencil plus
                                 eliminated nodes), s = d^-1/2 takes exactly two values - (1 / c0)^1/2 on the free rows, 1 on the eliminated
                                 ones - and the update march of PGD_TUNE_PCG_RECOMPUTE_Q divides by them in its exact phase instead of
@@ -744,6 +751,10 @@ int pgd_kernel_counts(pgd_handle ctx, int64_t *out, int n);
 /* Launches of the vector update that forms q = A p itself (PGD_TUNE_PCG_RECOMPUTE_Q) since the context was created; they are not
  * product launches and do not enter pgd_kernel_counts.  A chunk of iterations that is replayed as a graph counts once.  */
 int pgd_pcg_recompute_counts(pgd_handle ctx, int64_t *updates);
+/* Launches of k_pcg1_fused_march (PGD_TUNE_PCG_FUSED_MARCH), counted the same way.  Each of them is an update and a product: it enters
+ * pgd_pcg_recompute_counts and family [7] of pgd_kernel_counts as well, and the stand-alone product of p0 does not enter the latter - a
+ * solve of k iterations reports k updates and k + 1 stencil marches with the knob at either setting.  */
+int pgd_pcg_fused_counts(pgd_handle ctx, int64_t *marches);
 /* Row-class classifications since the context was created: done in full (three passes over the slot values with hashing) / served
  * by the mesh's structure cache (codes copied, every row verified against its class: one pass) - PGD_TUNE_CLS_CACHE.   */
 int pgd_classify_counts(pgd_handle ctx, int64_t *full, int64_t *cached);

@@ -140,6 +140,7 @@ SIGNATURES = {
     "pgd_prof_event_overhead": (C.c_int, [H, PD]),
     "pgd_kernel_counts": (C.c_int, [H, PI64, C.c_int]),
     "pgd_pcg_recompute_counts": (C.c_int, [H, PI64]),
+    "pgd_pcg_fused_counts": (C.c_int, [H, PI64]),
     "pgd_classify_counts": (C.c_int, [H, PI64, PI64]),
     "pgd_mg_counts": (C.c_int, [H, PI64, PI64]),
     "pgd_vmg_counts": (C.c_int, [H, PI64, PI64, PI64]),
@@ -155,7 +156,7 @@ NSLOTS = 64
 EVAL_STATS, EVAL_ENVELOPE, EVAL_EXCEED, EVAL_FIELDS = 1, 2, 4, 8      # PGD_EVAL_* (include/pgd_amd.h)
 TUNE_EVAL_VARIANT, TUNE_EVAL_GRID_MAX, TUNE_EVAL_SAMPLE_CHUNK = 50, 51, 52
 TUNE_BLOCK_STORAGE = 54
-TUNE_PCG_FOLD_MARCH, TUNE_PCG_SCALAR_S = 55, 56
+TUNE_PCG_FOLD_MARCH, TUNE_PCG_SCALAR_S, TUNE_PCG_FUSED_MARCH = 55, 56, 57
 BLOCK_F32, BLOCK_F64, BLOCK_MAXK = 0, 1, 64                                           # PGD_BLOCK_* (include/pgd_amd.h)
 
 
@@ -871,6 +872,12 @@ class Context:
         """Launches of the PCG update that forms A p itself instead of reading it (PGD_TUNE_PCG_RECOMPUTE_Q)."""
         n = I64()
         self._ck(self.lib.pgd_pcg_recompute_counts(self.h, C.byref(n)))
+        return n.value
+
+    def pcg_fused_marches(self):
+        """Launches of the march that holds the PCG update and the next product's dots (PGD_TUNE_PCG_FUSED_MARCH)."""
+        n = I64()
+        self._ck(self.lib.pgd_pcg_fused_counts(self.h, C.byref(n)))
         return n.value
 
     def classify_counts(self):

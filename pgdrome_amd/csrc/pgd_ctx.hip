@@ -471,6 +471,13 @@ int pgd_pcg_recompute_counts(pgd_handle h, int64_t *updates) {
     return PGD_OK;
 }
 
+int pgd_pcg_fused_counts(pgd_handle h, int64_t *marches) {
+    PGD_CTX(c, h);
+    if (!marches) return fail(c, PGD_ERR_INVALID, "pcg_fused_counts: invalid arguments");
+    *marches = c->pcg_fused_launches;
+    return PGD_OK;
+}
+
 int pgd_timer_start(pgd_handle h) {
     PGD_CTX(c, h);
     for (auto &e : c->timer_ev)

@@ -288,6 +288,8 @@ struct Ctx {
     int pcg_recompute_q = 1;      // ... and on one-stencil grids A p is not stored: the update marches over p and forms it again (PGD_TUNE_PCG_RECOMPUTE_Q)
     int64_t pcg_recompute_launches = 0;   // launches of that update (k_spmv_stencil_march, EPI 3)
     int pcg_fold_march = 0;       // 1: every workgroup of it takes the scalar step itself, no k_pcg1_scalars launch (PGD_TUNE_PCG_FOLD_MARCH; measured: 0.3 ms of 48 per step, under the run-to-run spread - off)
+    int64_t pcg_fused_launches = 0;       // launches of k_pcg1_fused_march (each is counted as an update and as a product as well)
+    int pcg_fused_march = 1;      // 1: an iteration is k_pcg1_scalars + ONE march, the update with the next product's dots inside (k_pcg1_fused_march, PGD_TUNE_PCG_FUSED_MARCH; 256^3: 48.1 -> 45.0 ms per step)
     int pcg_scalar_s = 1;         // ... and divides by the two values s takes on such an operator instead of streaming it (PGD_TUNE_PCG_SCALAR_S)
     int asm_lattice = 1;          // lattice meshes: edge vectors as whole lattice steps in the assembly (PGD_TUNE_ASM_LATTICE)
     int spmv_fetch_depth = 6;     // plane fetches in flight per workgroup of k_spmv_diac_march2 (3 or 6; PGD_TUNE_SPMV_FETCH_DEPTH)
@@ -449,6 +451,11 @@ struct StencilFold {
 int stencil_update_blocks(const Ctx *c, const Mesh *m);
 int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, double *r, const double *s,
                           double *pairs, int lag, double s_free = 0.0, const StencilFold *fold = nullptr);
+// ... and with the dot-only product of the direction it writes in the same march (k_pcg1_fused_march): r is read from r_in and written
+// to r_out, the product's (p.q, q.q) pairs go where launch_spmv_op leaves them.  stencil_fused_ok: the launch exists for this operator
+bool stencil_fused_ok(const Ctx *c, const Mesh *m, const Csr *a);
+int launch_stencil_fused(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, const double *r_in, double *r_out,
+                         const double *s, double *pairs, int lag, double s_free);
 int launch_stencil_pass(Ctx *c, const uint8_t *cls, int ident, const double cst[8], int nx, int ny, int nz, int zm0, int zm1,
                         const double *x, const double *b, double *y, double w, int epi, bool dot, int *nparts, int z0 = 0, int z1 = -1);      // pgd_spmv.hip
 // pgd_mg.hip: multigrid preconditioner of the scaled stencil operator

@@ -1458,6 +1458,13 @@ struct PcgRun {
     bool virt = false;                  // the scaled operator is held as a derived stencil only: the slot arrays still hold A
     double s_free = 0.0;                // ... and then s is this number on every free row, 1 on the eliminated ones (k_stencil_derive)
     bool fold_march = false;            // the update march takes the scalar step itself (PGD_TUNE_PCG_FOLD_MARCH)
+    // PGD_TUNE_PCG_FUSED_MARCH: one march per iteration.  r alternates between r and r2 like the direction between p and q (the r of
+    // iteration k lives in the buffer of parity k & 1); fprod / fnprod: the (p.q, q.q) pairs of the current direction, left by the
+    // stand-alone product of p0 and then by every march
+    bool fused = false;
+    double *r2 = nullptr;
+    const double *fprod = nullptr;
+    int fnprod = 0;
     double st_saved[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // On EVERY exit (a failing launch, graph replay or copy included): the stencil couplings back to those of A where the scaled
     // operator was a derived stencil; and, unless the finish has done it, x back to D^-1/2 x~ and the slot arrays no longer taken
@@ -1572,6 +1579,9 @@ static int pcg_setup_unscaled(PcgRun &R) {
     return pcg_init(R.c, R.b, R.q, R.o->dinv, R.r, R.z, R.p, 0, R.n, R.S_INIT);
 }
 
+// partial sums a chunk of iterations may leave (allocated before a chunk is captured - and before the fused form's product of p0)
+static int64_t pcg_partials_needed(int64_t n) { return std::max<int64_t>(4 * (int64_t)MAX_VEC_BLOCKS, 2 * ((n + 63) / 64) + 64); }
+
 // after the start: p0 = z0 = M r0 and the first "previous r.z" where a cycle preconditions; the form, and what it needs allocated and
 // seeded before its first iteration
 static int pcg_choose_and_seed(PcgRun &R) {
@@ -1589,7 +1599,8 @@ static int pcg_choose_and_seed(PcgRun &R) {
     // (two-launch form above 2^20 rows: 512 workgroups in the update, every one of which sums all partial sums)
     R.g2v = grid_for((n + 1) / 2, TPB, (n > ((int64_t)1 << 20) && n <= c->pcg_small_ss_rows && c->pcg_small_ss) ? 512 : MAX_VEC_BLOCKS);
     R.gvec = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE ? stencil_update_blocks(c, R.m) : R.g2v;
-    R.fold_march = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE && c->pcg_fold_march;
+    R.fused = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE && c->pcg_fused_march && stencil_fused_ok(c, R.m, R.o);
+    R.fold_march = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE && c->pcg_fold_march && !R.fused;      // (both knobs on: the fused march)
     // (the march that takes the scalar step alternates between two halves like the two-launch form: each holds gvec pairs)
     const int64_t half = 2 * std::max<int64_t>(MAX_VEC_BLOCKS, R.fold_march ? R.gvec : 0);
     PGD_TRY(ensure_work(c, 6, std::max<int64_t>(2 * half, 2 * (int64_t)R.gvec)));
@@ -1602,6 +1613,26 @@ static int pcg_choose_and_seed(PcgRun &R) {
     k_pcg1_seed<<<8, TPB, 0, c->stream>>>(two ? R.part2b : R.part2, R.gvec, c->slots, R.S_INIT, R.S_INIT + 1);
     if (two) PGD_HIP(c, hipMemsetAsync(c->slots + S1F_ALPHA, 0, 6 * sizeof(double), c->stream));     // alpha, beta, exact-phase bit x 2 parities
     PGD_LAUNCH_CHECK(c);
+    if (R.fused) {
+        // the one stand-alone product of the solve: the dots of p0.  Every march leaves those of the direction it writes in the same
+        // place.  With launch timing on this launch carries events in every solve (it is the only sample of the product bracket).
+        // The counters stay those of the three-launch loop - k iterations are k updates and, with the initial residual's, k + 1
+        // products: the march counts its product, this launch does not (the last march's dots, which no iteration reads, even it out).
+        PGD_TRY(ensure_work(c, 4, n));
+        R.r2 = c->work[4];
+        // (its pairs must outlive the loop's own allocations: what pcg_drive asks for before its capture exists from here on - a
+        // buffer that grows there is a NEW buffer)
+        PGD_TRY(ensure_partials(c, pcg_partials_needed(n)));
+        PGD_TRY(ensure_work(c, 5, 4096));
+        if (c->prof) c->prof_seen &= ~(int64_t)3;
+        c->spmv_qq = 1;
+        const int rc = launch_spmv_op(c, R.m, R.o, R.p, R.q, R.p, 0, n, true, false, c->flags, &R.fnprod);
+        c->spmv_qq = 0;
+        PGD_TRY(rc);
+        if (R.fnprod != R.gvec) return fail(c, PGD_ERR_INVALID, "pcg_solve: the product's launch is not the update's");
+        c->kcount[KC_STENCIL_MARCH] -= 1;
+        PGD_TRY(stage_product_partials(c, &R.fprod, &R.fnprod));
+    }
     return PGD_OK;
 }
 
@@ -1728,6 +1759,19 @@ static int pcg_iter_single_sync_recompute(PcgRun &R, int k) {
     const int par = k & 1;
     double *p_cur = par ? R.q : R.p, *p_next = par ? R.p : R.q;
     const double s_free = (R.virt && R.c->pcg_scalar_s) ? R.s_free : 0.0;
+    if (R.fused) {
+        // PGD_TUNE_PCG_FUSED_MARCH: the scalar step on the pairs the previous march (the product of p0) left, then ONE march - the update and
+        // the dots of the direction it writes; r alternates between two buffers like the direction
+        Ctx *c = R.c;
+        I.lag = R.lag_x ? 1 + (k & 1) : 0;
+        if (R.gvec <= 8192 && R.fprod != c->partials) return fail(c, PGD_ERR_INVALID, "pcg_solve: the partial sums moved under the fused march");
+        k_pcg1_scalars<<<1, 1024, 0, c->stream>>>(R.fprod, R.fnprod, R.part2, R.gvec, c->slots, c->flags);
+        PGD_TRY(update_timing_begin(c, &I.timed));
+        PGD_TRY(launch_stencil_fused(c, R.m, R.o, p_cur, p_next, R.x, par ? R.r2 : R.r, par ? R.r : R.r2, R.sc, R.part2, I.lag, s_free));
+        PGD_TRY(pcg1_end(R, I, 8.0));
+        I.nparts = R.gvec;
+        return stage_product_partials(c, &I.prod, &I.nparts);               // (more than 8192 workgroups: the first stage, into the place fprod names)
+    }
     PGD_TRY(pcg1_begin(R, k, p_cur, false, !R.fold_march, &I));
     if (R.fold_march) {
         const StencilFold F{I.prod, I.nparts, par ? R.part2 : R.part2b, R.gvec, par};
@@ -1764,7 +1808,7 @@ static int pcg_drive(PcgRun &R, int CE, int maxit, int f[4], int &enq, double *d
     if (dbg) { (void)hipStreamSynchronize(c->stream); dbg[0] = host_now(); }
     if (maxit >= CE) {
         // everything a chunk allocates lazily must exist before the capture starts
-        PGD_TRY(ensure_partials(c, std::max<int64_t>(4 * (int64_t)MAX_VEC_BLOCKS, 2 * ((R.n + 63) / 64) + 64)));
+        PGD_TRY(ensure_partials(c, pcg_partials_needed(R.n)));
         PGD_TRY(ensure_work(c, 5, 4096));
         const bool prof_saved = c->prof;
         c->prof = false;
@@ -1846,7 +1890,9 @@ static int pcg_finish(PcgRun &R, const int f[4], int *iters, double *relres) {
         const bool two = R.form == PGD_PCG_FORM_TWO_LAUNCH || R.fold_march;
         // (the update that forms q itself: f[1] updates ran, each wrote the direction to the other buffer)
         const double *p_live = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE && (f[1] & 1) ? R.q : R.p;
-        k_scale_out<<<g, TPB, 0, c->stream>>>(R.x, R.r, R.sc, R.n, c->partials, (pending || lag_pending) ? p_live : nullptr, c->slots,
+        // (the fused march: each of them wrote the residual to the other buffer as well)
+        const double *r_live = R.fused && (f[1] & 1) ? R.r2 : R.r;
+        k_scale_out<<<g, TPB, 0, c->stream>>>(R.x, r_live, R.sc, R.n, c->partials, (pending || lag_pending) ? p_live : nullptr, c->slots,
                                               R.S_PAIR + 2 * (f[1] & 1), S_PQ, lag_pending ? 1 : 0,
                                               two ? S1F_ALPHA + last_par : S1_ALPHA, two ? S1F_BETA + last_par : S1_BETA);
         PGD_LAUNCH_CHECK(c);

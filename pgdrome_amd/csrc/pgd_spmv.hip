@@ -1591,6 +1591,313 @@ __global__ __launch_bounds__(256, OCC) void k_spmv_stencil_march(StencilArgs A) 
 #undef PGD_ST_STAMP
 #undef PGD_ST_WHATIF
 
+// ------------------------------------------------------------------ ONE march per PCG iteration (PGD_TUNE_PCG_FUSED_MARCH)
+// The EPI 3 update of k_spmv_stencil_march AND the dot-only product of the direction it writes, in one launch.  A workgroup of the
+// update does not hold its neighbours' new direction; here it forms it itself: OVERLAPPED tiles, a one-cell ring recomputed
+// redundantly, nothing exchanged between workgroups.  Per plane z of the march (patch = the 64 x PY rows the workgroup owns):
+//   A(z)  q = A p on patch + ring from p staged with a halo of TWO cells (68 x (PY + 4)), r' = r - alpha q, p' = r' + beta p there
+//         - the operations of upd_rows in its order - r', p' and x stored for the patch rows only, p' staged (masked like any staged
+//         plane) into a second LDS ring, 66 x (PY + 2);
+//   B(z)  two steps later the product's chain over the staged p' for the patch rows: p'.Ap' and Ap'.Ap' in the order of the dot-only
+//         product (rows 0 .. RW - 1, planes ascending).
+// The march over [za, zb) runs A for the planes za - 1 .. zb: the two extra planes store nothing and add nothing to the r sums, they
+// give B its p' on za - 1 and zb.  r is read from one buffer and written to another: ring cells and the extra planes are rows that
+// other workgroups of the launch own.  Nothing a workgroup reads is written by this launch.
+// One lds_barrier() per step: in the step of plane z the waves read the p slots of z - 1, z, z + 1 and the p' slots of z - 3, z - 2,
+// z - 1 and write the p slot of z + 2 and the p' slot of z - four slots each, (plane & 3), so no cell written in a step is read in it.
+struct FusedArgs : StencilArgs {
+    double *ur_out = nullptr;           // r' (ur: the r of this iteration, read only)
+    double *prod_pairs = nullptr;       // (p'.Ap', Ap'.Ap') per workgroup, where the product launch this march replaces writes them
+};
+
+// the chains of RW rows one below the other, the first at xm / xc / xp (planes z - 1, z, z + 1 of a tile with W cells per line): all
+// neighbour values first, then the chains side by side - the 15 fused multiply-adds of k_spmv_stencil_march in its order
+template <int RW, int W>
+__device__ __forceinline__ void stencil_chain_rows(const double *xm, const double *xc, const double *xp, const double (&c)[8], double (&acc)[RW]) {
+    double M[RW + 1][2], C[RW + 2][3], Q[RW + 1][2];
+#pragma unroll
+    for (int j = 0; j <= RW; ++j) { M[j][0] = xm[(j - 1) * W - 1]; M[j][1] = xm[(j - 1) * W]; }
+#pragma unroll
+    for (int j = 0; j <= RW + 1; ++j) {
+        if (j <= RW) C[j][0] = xc[(j - 1) * W - 1];
+        C[j][1] = xc[(j - 1) * W];
+        if (j >= 1) C[j][2] = xc[(j - 1) * W + 1];
+    }
+#pragma unroll
+    for (int j = 0; j <= RW; ++j) { Q[j][0] = xp[j * W]; Q[j][1] = xp[j * W + 1]; }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < RW; ++r) acc[r] = c[7] * M[r][0];
+#define PGD_ST_ROWS(cc, V)                           \
+    _Pragma("unroll") for (int r = 0; r < RW; ++r) acc[r] = fma(cc, V, acc[r])
+    PGD_ST_ROWS(c[6], M[r][1]);
+    PGD_ST_ROWS(c[5], M[r + 1][0]);
+    PGD_ST_ROWS(c[4], M[r + 1][1]);
+    PGD_ST_ROWS(c[3], C[r][0]);
+    PGD_ST_ROWS(c[2], C[r][1]);
+    PGD_ST_ROWS(c[1], C[r + 1][0]);
+    PGD_ST_ROWS(c[0], C[r + 1][1]);
+    PGD_ST_ROWS(c[1], C[r + 1][2]);
+    PGD_ST_ROWS(c[2], C[r + 2][1]);
+    PGD_ST_ROWS(c[3], C[r + 2][2]);
+    PGD_ST_ROWS(c[4], Q[r][0]);
+    PGD_ST_ROWS(c[5], Q[r][1]);
+    PGD_ST_ROWS(c[6], Q[r + 1][0]);
+    PGD_ST_ROWS(c[7], Q[r + 1][1]);
+#undef PGD_ST_ROWS
+}
+
+template <bool NTY, int RWT>
+__global__ __launch_bounds__(256, 2) void k_pcg1_fused_march(FusedArgs A) {
+    static_assert(RWT == 4 || RWT == 2, "rows per thread");
+    constexpr int NT = 256, RW = RWT, PY = 4 * RW;
+    constexpr int W2 = DM_HX + 2, H2 = PY + 4, SLOT2 = W2 * H2;             // p, halo of two: 68 x 20 = 1360 cells (68 x 12 = 816)
+    constexpr int W1 = DM_HX, H1 = PY + 2, SLOT1 = W1 * H1;                 // p', halo of one: 66 x 18 = 1188 cells (66 x 10 = 660)
+    constexpr int NH2 = SLOT2 - 64 * PY;                                    // 336 (304) halo cells of p: two per thread
+    constexpr int NR1 = SLOT1 - 64 * PY;                                    // 164 (148) ring cells: one each for the first threads
+    constexpr int NQ = RW + 2;
+    constexpr int OOB = (int)0x40000000;
+    constexpr int AUX_RX = NTY ? 2 : 0;
+    static_assert(NH2 <= 2 * NT && NR1 <= NT, "halo cells per thread");
+    static_assert((4 * SLOT2 + 4 * SLOT1 + 4) * 8 <= 80 * 1024, "two workgroups per CU");
+    __shared__ double s_p[4 * SLOT2];
+    __shared__ double s_n[4 * SLOT1];
+    __shared__ double s_red[4];
+    if (A.flags && A.flags[0]) return;
+    const double u_alpha = A.slots[S1_ALPHA], u_beta = A.slots[S1_BETA];
+    const bool u_exact = A.flags[3] != 0;
+    const bool u_skip_x = A.lag == 1 && u_beta >= LAG_MIN_BETA;
+    const bool u_two = A.lag == 2 && A.slots[S1_PEND] != 0.0;
+    const double u_alpha_p = u_two ? A.slots[S1_ALPHA_PREV] : 0.0;
+    const double u_ibeta_p = u_two ? 1.0 / A.slots[S1_BETA_PREV] : 0.0;
+    const bool u_s_known = A.s_free > 0.0;
+    // (read by the lag = 2 launches and by k_scale_out, never by a workgroup of this launch)
+    if (A.lag == 1 && blockIdx.x == 0 && threadIdx.x == 0) A.slots[S1_PEND] = u_skip_x ? 1.0 : 0.0;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int per_chunk = A.tiles_x * A.tiles_y;
+    const int chunk = b / per_chunk, tile = b - chunk * per_chunk;
+    const int ty = tile / A.tiles_x, tx = tile - ty * A.tiles_x;
+    const int x0 = tx * 64, y0 = ty * PY;
+    const int64_t P = (int64_t)A.nx * A.ny;
+    const unsigned P8 = (unsigned)(P * 8);
+    const int centre2 = (RW * wv + 2) * W2 + lane + 2;                      // row 0 of the thread's rows in the p tile ...
+    const int centre1 = (RW * wv + 1) * W1 + lane + 1;                      // ... and in the p' tile
+    const int za = A.z0 + chunk * A.zchunk, zb = min(A.z1, za + A.zchunk);
+    if (za >= zb) {                                                         // uniform; the launcher sizes the grid so that no chunk is empty
+        if (tid == 0) { A.partials[2 * b] = 0.0; A.partials[2 * b + 1] = 0.0; A.prod_pairs[2 * b] = 0.0; A.prod_pairs[2 * b + 1] = 0.0; }
+        return;
+    }
+    // ---- per-thread state of the whole march, from the codes of one main plane
+    int lv[NQ], sv[RW], hc[2];                                              // byte offsets within a plane (or OOB); LDS cells of the two halo cells (-1: none)
+    double m[RW];                                                           // 1: the row is live and free, 0: eliminated or outside the grid
+    bool fixr[RW];                                                          // the row is live and an identity row of the main planes
+    unsigned fix = 0;
+    int ring_c2 = centre2, ring_c1 = 0, ring_off = OOB;                     // the thread's ring cell in both tiles, its offset (OOB: eliminated, outside, none)
+    {
+        const uint8_t *cz = A.cls + P * min(max(A.zm0, 0), A.nz - 1);
+        auto code = [&](int gx, int gy, bool *in, bool *masked) {
+            *in = gx >= 0 && gx < A.nx && gy >= 0 && gy < A.ny;
+            const int off = *in ? gx + A.nx * gy : 0;
+            *masked = *in && A.ident >= 0 && (int)cz[off] == A.ident;
+            return off;
+        };
+#pragma unroll
+        for (int q = 0; q < RW; ++q) {
+            bool in, masked;
+            const int off = code(x0 + lane, y0 + RW * wv + q, &in, &masked);
+            lv[q] = in ? 8 * off : OOB;                                     // raw: an identity row's own value is its q
+            sv[q] = lv[q];
+            m[q] = (in && !masked) ? 1.0 : 0.0;
+            fixr[q] = in && masked;
+            if (fixr[q]) fix |= 1u << q;
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int k = tid + j * NT;
+            int lx, ly;
+            if (k < 2 * W2) { ly = k / W2; lx = k - ly * W2; }
+            else if (k < 4 * W2) { ly = (k - 2 * W2) / W2; lx = k - 2 * W2 - ly * W2; ly += PY + 2; }
+            else { const int k2 = k - 4 * W2, cx = k2 & 3; ly = 2 + (k2 >> 2); lx = cx < 2 ? cx : 64 + cx; }
+            bool in, masked;
+            const int off = code(x0 - 2 + lx, y0 - 2 + ly, &in, &masked);
+            const bool have = k < NH2;
+            lv[RW + j] = (have && in && !masked) ? 8 * off : OOB;           // the halo cell of an eliminated node reads as 0
+            hc[j] = have ? ly * W2 + lx : -1;
+        }
+        if (tid < NR1) {
+            int lx, ly;
+            if (tid < W1) { lx = tid; ly = 0; }
+            else if (tid < 2 * W1) { lx = tid - W1; ly = H1 - 1; }
+            else if (tid < 2 * W1 + PY) { lx = 0; ly = tid - 2 * W1 + 1; }
+            else { lx = W1 - 1; ly = tid - 2 * W1 - PY + 1; }
+            bool in, masked;
+            const int off = code(x0 - 1 + lx, y0 - 1 + ly, &in, &masked);
+            ring_c1 = ly * W1 + lx;
+            ring_c2 = (ly + 1) * W2 + lx + 1;
+            ring_off = (in && !masked) ? 8 * off : OOB;
+        }
+    }
+    const bool ring_on = ring_off != OOB;
+    const double cc[8] = {A.c[0], A.c[1], A.c[2], A.c[3], A.c[4], A.c[5], A.c[6], A.c[7]};
+    double dot = 0.0, dot2 = 0.0;                                           // r'.r' and the exact phase's sum
+    double pdot = 0.0, pdot2 = 0.0;                                         // p'.Ap' and Ap'.Ap'
+    auto rsrc_of = [&](const double *plane_ptr, bool live) {
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(plane_ptr), 0, live ? (int)P8 : 0, 0x00020000);
+    };
+    auto ld = [&](auto r, int off, int aux) -> double {                     // aux 1: the streams read once (nt under the stream hints)
+        return aux ? __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, AUX_RX))
+                   : __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
+    };
+    const int zd0 = min(A.zv0, A.zs0), zd1 = max(A.zv1, A.zs1);             // planes that hold data
+    auto fetch = [&](int zz, double (&v)[NQ]) {
+        const auto r = rsrc_of(A.x + P * (int64_t)zz, zz >= zd0 && zz < zd1 && zz <= zb + 1);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) v[q] = ld(r, lv[q], 0);
+    };
+    // stage plane zz of p: the masked values for the neighbours (zeros outside the staged planes), the raw own values into `own`
+    auto stage = [&](int zz, const double (&v)[NQ], double (&own)[RW]) {
+        double *dst = s_p + (zz & 3) * SLOT2;
+        const bool data = zz >= A.zs0 && zz < A.zs1;                        // uniform
+#pragma unroll
+        for (int q = 0; q < RW; ++q) { dst[centre2 + q * W2] = data ? v[q] * m[q] : 0.0; own[q] = v[q]; }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (hc[j] >= 0) dst[hc[j]] = data ? v[RW + j] : 0.0;
+    };
+    // A(z): the update of plane z on patch + ring; xo = the plane's raw own p; pn = the new direction of the own rows (0 outside the grid)
+    auto update = [&](int z, const double (&xo)[RW], double (&pn)[RW]) {
+        const bool own_plane = z >= za && z < zb;                           // stored, summed; else one of the two extra planes
+        const bool main = z >= A.zm0 && z < A.zm1, verified = z >= A.zv0 && z < A.zv1;
+        const bool data = z >= A.zs0 && z < A.zs1;                          // p' of this plane is staged as data
+        double *dn = s_n + (z & 3) * SLOT1;
+        if (!(main || (verified && own_plane))) {                           // nothing to form: outside the grid, or an extra plane of identity rows
+#pragma unroll
+            for (int r = 0; r < RW; ++r) { dn[centre1 + r * W1] = 0.0; pn[r] = 0.0; }
+            if (tid < NR1) dn[ring_c1] = 0.0;
+            return;
+        }
+        const int64_t oz = P * (int64_t)z;
+        const auto dr = rsrc_of(A.ur + oz, true);
+        const auto dx = rsrc_of(A.ux + oz, own_plane && !u_skip_x);
+        double ur[RW], ux[RW], us[RW], rring;
+#pragma unroll
+        for (int r = 0; r < RW; ++r) ur[r] = ld(dr, sv[r], 1);
+        rring = ld(dr, main ? ring_off : OOB, 0);                           // (a neighbour's line: default policy)
+#pragma unroll
+        for (int r = 0; r < RW; ++r) ux[r] = ld(dx, sv[r], 1);
+        if (!u_s_known) {                                                   // uniform: else s is two numbers, no load goes through A.us
+            const auto ds = rsrc_of(A.us + oz, own_plane && u_exact);
+#pragma unroll
+            for (int r = 0; r < RW; ++r) us[r] = ld(ds, sv[r], 0);
+        }
+        double qv[RW], qring = 0.0, pring = 0.0;
+        if (main) {
+            const double *xm = s_p + ((z - 1) & 3) * SLOT2, *xc = s_p + (z & 3) * SLOT2, *xp = s_p + ((z + 1) & 3) * SLOT2;
+            double acc[RW];
+            stencil_chain_rows<RW, W2>(xm + centre2, xc + centre2, xp + centre2, cc, acc);
+            if (tid < NR1) {
+                double accr[1];
+                stencil_chain_rows<1, W2>(xm + ring_c2, xc + ring_c2, xp + ring_c2, cc, accr);
+                qring = accr[0];
+                pring = xc[ring_c2];
+            }
+#pragma unroll
+            for (int r = 0; r < RW; ++r) qv[r] = fixr[r] ? xo[r] : acc[r];   // q = acc, or p itself on an eliminated row
+        } else {
+#pragma unroll
+            for (int r = 0; r < RW; ++r) qv[r] = xo[r];                     // a plane of identity rows only: q = p
+        }
+        const unsigned ones = main ? fix : ~0u;
+        const auto so_r = rsrc_of(A.ur_out + oz, own_plane), so_p = rsrc_of(A.y + oz, own_plane);
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            const double pi = xo[r], r0 = ur[r];
+            if (own_plane && !u_skip_x) {                                   // uniform
+                double xi = ux[r];
+                if (u_two) xi = fma(u_alpha_p, (pi - r0) * u_ibeta_p, xi);
+                xi = fma(u_alpha, pi, xi);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_v2i, xi), dx, sv[r], 0, AUX_RX);
+            }
+            const double ri = fma(-u_alpha, qv[r], r0);
+            const double pv = fma(u_beta, pi, ri);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_v2i, ri), so_r, sv[r], 0, AUX_RX);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(st_v2i, pv), so_p, sv[r], 0, 0);
+            const bool in = sv[r] != OOB;                                   // (outside the grid q is a sum over the neighbours inside it: not zero)
+            pn[r] = in ? pv : 0.0;
+            if (own_plane) {                                                // uniform
+                const double t = in ? ri : 0.0;
+                dot = fma(t, t, dot);
+                if (u_exact) {
+                    const double sr = u_s_known ? (((ones >> r) & 1u) ? 1.0 : A.s_free) : us[r];
+                    const double ts = t / (in ? sr : 1.0);
+                    dot2 = fma(ts, ts, dot2);
+                }
+            }
+            dn[centre1 + r * W1] = data ? pn[r] * m[r] : 0.0;
+        }
+        if (tid < NR1) {
+            const double ri = fma(-u_alpha, qring, rring);
+            const double pv = fma(u_beta, pring, ri);
+            dn[ring_c1] = (data && ring_on) ? pv : 0.0;
+        }
+    };
+    // B(z): the dots of the product of p' on the own rows of plane z; xo = the plane's own p' (update's pn)
+    auto product = [&](int z, const double (&xo)[RW]) {
+        if (z >= A.zm0 && z < A.zm1) {
+            const double *xm = s_n + ((z - 1) & 3) * SLOT1 + centre1, *xc = s_n + (z & 3) * SLOT1 + centre1, *xp = s_n + ((z + 1) & 3) * SLOT1 + centre1;
+            double acc[RW];
+            stencil_chain_rows<RW, W1>(xm, xc, xp, cc, acc);
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                const double yv = fixr[r] ? xo[r] : acc[r];
+                pdot = fma(yv, xo[r], pdot);
+                const double t = sv[r] != OOB ? yv : 0.0;
+                pdot2 = fma(t, t, pdot2);
+            }
+        } else if (z >= A.zv0 && z < A.zv1) {
+#pragma unroll
+            for (int r = 0; r < RW; ++r) { pdot = fma(xo[r], xo[r], pdot); pdot2 = fma(xo[r], xo[r], pdot2); }
+        }
+    };
+    double rr[3][NQ];                                                       // three plane fetches in flight, rotating by name
+    double own[3][RW];                                                      // raw own p of the planes z, z + 1, z + 2: own[(plane - (za - 1)) % 3]
+    double pnew[3][RW];                                                     // own p' of the planes z - 2, z - 1, z, likewise
+    {
+        double t0[NQ], t1[NQ], t2[NQ];
+        fetch(za - 2, t0); fetch(za - 1, t1); fetch(za, t2);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) fetch(za + 1 + s, rr[s]);
+        stage(za - 2, t0, own[2]); stage(za - 1, t1, own[0]); stage(za, t2, own[1]);
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int r = 0; r < RW; ++r) pnew[s][r] = 0.0;
+    __syncthreads();
+    // step t: plane z = za - 1 + t.  B(z - 2), A(z), stage p(z + 2), fetch p(z + 5); every test is uniform
+#pragma clang loop unroll(disable)
+    for (int z = za - 1; z <= zb + 1; z += 3) {
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const int zs = z + s;
+            if (zs - 2 >= za && zs - 2 < zb) product(zs - 2, pnew[(s + 1) % 3]);
+            if (zs <= zb) update(zs, own[s], pnew[s]);
+            if (zs + 2 <= zb + 1) stage(zs + 2, rr[s], own[(s + 2) % 3]);
+            if (zs + 5 <= zb + 1) fetch(zs + 5, rr[s]);
+            lds_barrier();
+        }
+    }
+    if (!u_exact) dot2 = dot;                                               // the pair is (r~.r~, true r.r) and outside the exact phase (r~.r~, r~.r~)
+    for (int pass = 0; pass < 4; ++pass) {
+        const double sum = wave_sum(pass == 0 ? dot : pass == 1 ? dot2 : pass == 2 ? pdot : pdot2);
+        __syncthreads();
+        if (lane == 0) s_red[wv] = sum;
+        __syncthreads();
+        if (tid == 0) (pass < 2 ? A.partials : A.prod_pairs)[2 * b + (pass & 1)] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+    }
+}
+
 // Does the dictionary reduce to one stencil?  k_stencil_pick: base class = the class of the row in the middle of the planes
 // [z_lo, z_hi), identity class = the tuple (1, 0 .. 0).  A row's tuple holds only the UPPER half of its row: a free node whose
 // upper neighbours are all eliminated (the last free node before three faces) carries the identity tuple too.  k_stencil_split
@@ -2763,6 +3070,51 @@ int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_i
     return PGD_OK;
 }
 
+// The same update with the dot-only product of the direction it writes in the same march (k_pcg1_fused_march).  Its workgroups leave
+// the product's pairs where the product launch would: that launch must have the update's shape - it has, unless the fetch depth of the
+// product (PGD_TUNE_STENCIL_DEPTH) gives it longer marches - and the whole grid must be main or identity planes, no ghost plane.
+bool stencil_fused_ok(const Ctx *c, const Mesh *m, const Csr *a) {
+    if (!stencil_whole_grid(c, m, a) || a->st_g_lo || a->st_g_hi) return false;
+    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
+    const int nz = (int)(m->nv / plane);
+    const StencilShape su = stencil_shape(c, m->sym_nx, m->sym_ny, nz, 3), sp = stencil_shape(c, m->sym_nx, m->sym_ny, nz, c->stencil_depth > 0 ? c->stencil_depth : 3);
+    return su.wgs == sp.wgs && su.zchunk == sp.zchunk && su.rows_per_thread == sp.rows_per_thread && su.tiles_y == sp.tiles_y &&
+           (sp.rows_per_thread == 4 || c->stencil_depth != 6);
+}
+
+int launch_stencil_fused(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, const double *r_in, double *r_out,
+                         const double *s, double *pairs, int lag, double s_free) {
+    if (!stencil_fused_ok(c, m, a) || !c->flags || p_in == p_out || r_in == r_out)
+        return fail(c, PGD_ERR_INVALID, "fused march: the operator's products do not run in the stencil march over the whole grid");
+    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
+    const int nz = (int)(m->nv / plane);
+    const StencilShape sh = stencil_shape(c, m->sym_nx, m->sym_ny, nz, 3);
+    PGD_TRY(ensure_partials(c, std::max<int64_t>(c->partials_off + 2 * (int64_t)sh.wgs, 4 * MAX_VEC_BLOCKS)));
+    FusedArgs F;
+    F.cls = a->cls; F.ident = a->st_ident; F.x = p_in; F.y = p_out; F.flags = c->flags;
+    F.zv0 = a->st_z0; F.zv1 = a->st_z1; F.zm0 = a->st_zm0; F.zm1 = a->st_zm1;
+    F.zs0 = a->st_zm0; F.zs1 = a->st_zm1;
+    for (int s2 = 0; s2 < 8; ++s2) F.c[s2] = a->st_c[s2];
+    F.nx = m->sym_nx; F.ny = m->sym_ny; F.nz = nz; F.z0 = 0; F.z1 = nz;
+    F.tiles_x = sh.tiles_x; F.tiles_y = sh.tiles_y; F.zchunk = sh.zchunk;
+    F.qq = 1; F.whatif = 0; F.b = nullptr; F.w = 0.0;
+    F.partials = pairs;
+    F.prod_pairs = c->partials + c->partials_off;
+    F.ur = const_cast<double *>(r_in); F.ur_out = r_out; F.ux = x; F.us = s; F.slots = c->slots; F.lag = lag;
+    F.s_free = s_free;
+    const bool nt = c->pcg_stream_hints != 0;
+    if (sh.rows_per_thread == 2) {
+        if (nt) k_pcg1_fused_march<true, 2><<<sh.wgs, 256, 0, c->stream>>>(F);
+        else k_pcg1_fused_march<false, 2><<<sh.wgs, 256, 0, c->stream>>>(F);
+    } else if (nt) k_pcg1_fused_march<true, 4><<<sh.wgs, 256, 0, c->stream>>>(F);
+    else k_pcg1_fused_march<false, 4><<<sh.wgs, 256, 0, c->stream>>>(F);
+    c->pcg_recompute_launches += 1;
+    c->pcg_fused_launches += 1;
+    c->kcount[KC_STENCIL_MARCH] += 1;
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
 // Gram matrix of the Galerkin start of a PCG solve (fem._rescale_start): column j needs w = A v_j, then the dots
 // v_i . w for i <= j and v_j . b - one pass over w and the v_i, partial sums per workgroup, fixed order.
 constexpr int GRAM_MAXV = 17;
@@ -2998,6 +3350,7 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_PCG_RECOMPUTE_Q && value >= 0 && value <= 1) { c->pcg_recompute_q = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_PCG_FOLD_MARCH && value >= 0 && value <= 1) { c->pcg_fold_march = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_PCG_SCALAR_S && value >= 0 && value <= 1) { c->pcg_scalar_s = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_PCG_FUSED_MARCH && value >= 0 && value <= 1) { c->pcg_fused_march = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_BLOCK_STORAGE && value >= 0 && value <= 2) { c->block_storage = (int)value; return PGD_OK; }
     return fail(c, PGD_ERR_INVALID, "tune: unknown knob %d or value out of range", knob);
 }

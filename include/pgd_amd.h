@@ -533,6 +533,18 @@ int pgd_eval_norm_last_shape(pgd_handle ctx, int *rows, int *staged);
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_SPMV_BLOCK_DIA = 58, /* 1: an OPERATOR (pgd_op_combine) on a blocked layout of 2 or 3 components over a scalar 3-D P1 box lattice
+                                (pgd_mesh_blocked of a layout in diagonal form, at least 2 nodes per axis) multiplies over its whole row
+                                range from a row-diagonal form - 15 ncomp arrays of one double per row, array (t, d) holding at row
+                                ncomp i + c the entry a(row, ncomp (i + off_t) + d) for the 15 lattice offsets in ascending order - in
+                                k_spmv_bdia: no column stream, every value load coalesced.  The form is extracted from the CSR values
+                                once per operator and set of values (a second pgd_op_combine into the handle extracts again) and costs
+                                the CSR value array's size a second time.  Same fma chain per row, same rows per workgroup: y, the partial
+                                sums and every pgd_pcg_solve on top are those of 0, bit for bit (a zero may change its sign).  Anything
+                                else - P2, 2-D or crossed bases, partial row ranges, atoms, pgd_bicgstab_solve, an entry off the
+                                pattern, no memory - keeps k_spmv_csr; pgd_bdia_counts says which.  0 (default): k_spmv_csr.  Measured
+                                (profiles/block_dia_bench_n1.jsonl, elastic_block): 7358 -> 533 us per product at 129^3 nodes, 1206 -> 68 us
+                                at 65^3; the "cmg" solve 1098 -> 233 ms and 160.7 -> 56.5 ms; extraction 10.7 and 1.4 ms per operator */
     PGD_TUNE_PCG_FUSED_MARCH = 57, /* 1 (default): an iteration of PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE is k_pcg1_scalars + ONE march (k_pcg1_fused_march):
                                 the update on overlapped tiles - a one-cell ring of q, r' and p' is formed redundantly, r alternates
                                 between two buffers - and, two planes behind it, the dots p'.Ap' and Ap'.Ap' of the direction it has just
@@ -773,6 +785,11 @@ int pgd_vmg_times(pgd_handle ctx, double *setup_ms, int64_t *march_passes);
  * setups (extraction of the diagonal blocks + ncomp Galerkin chains) in ms and the level passes issued to k_vmg_march.       */
 int pgd_cmg_counts(pgd_handle ctx, int64_t *solves, int64_t *fallbacks, int64_t *levels);
 int pgd_cmg_times(pgd_handle ctx, double *setup_ms, int64_t *march_passes);
+/* PGD_TUNE_SPMV_BLOCK_DIA since the context was created: row-diagonal forms extracted, product launches that read one (a chunk of
+ * iterations that is replayed as a graph counts once), operators on a blocked layout that were asked for a whole-range product with
+ * the knob on and kept the CSR kernel (each counted once per set of values); device time of the extractions in ms.           */
+int pgd_bdia_counts(pgd_handle ctx, int64_t *forms_built, int64_t *products, int64_t *fallbacks);
+int pgd_bdia_times(pgd_handle ctx, double *extract_ms);
 /* The V-cycle of the multigrid preconditioner on a z-slab of a ROW-SHARDED lattice: settings["preconditioner"] = "amg"
  * (forwarded by the reference into its solver, solver.py:593-594, 634-635) on a sharded spatial dimension.  Level 0 stays
  * with the rows (this rank's planes + one ghost plane per side), levels >= 1 are whole on every rank.  The caller owns the

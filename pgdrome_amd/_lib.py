@@ -147,6 +147,8 @@ SIGNATURES = {
     "pgd_vmg_times": (C.c_int, [H, C.POINTER(C.c_double), PI64]),
     "pgd_cmg_counts": (C.c_int, [H, PI64, PI64, PI64]),
     "pgd_cmg_times": (C.c_int, [H, C.POINTER(C.c_double), PI64]),
+    "pgd_bdia_counts": (C.c_int, [H, PI64, PI64, PI64]),
+    "pgd_bdia_times": (C.c_int, [H, C.POINTER(C.c_double)]),
     "pgd_calib_stream": (C.c_int, [H, H, C.c_int, C.c_int]),
     "pgd_timer_start": (C.c_int, [H]),
     "pgd_timer_stop": (C.c_int, [H, PD]),
@@ -157,6 +159,7 @@ EVAL_STATS, EVAL_ENVELOPE, EVAL_EXCEED, EVAL_FIELDS = 1, 2, 4, 8      # PGD_EVAL
 TUNE_EVAL_VARIANT, TUNE_EVAL_GRID_MAX, TUNE_EVAL_SAMPLE_CHUNK = 50, 51, 52
 TUNE_BLOCK_STORAGE = 54
 TUNE_PCG_FOLD_MARCH, TUNE_PCG_SCALAR_S, TUNE_PCG_FUSED_MARCH = 55, 56, 57
+TUNE_SPMV_BLOCK_DIA = 58
 BLOCK_F32, BLOCK_F64, BLOCK_MAXK = 0, 1, 64                                           # PGD_BLOCK_* (include/pgd_amd.h)
 
 
@@ -919,6 +922,19 @@ class Context:
         self._ck(self.lib.pgd_cmg_counts(self.h, C.byref(a), C.byref(b), C.byref(l)))
         self._ck(self.lib.pgd_cmg_times(self.h, C.byref(ms), C.byref(m)))
         return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
+
+    def block_product(self, on):
+        """Select the row-diagonal product for operators on vector-valued P1 layouts over box lattices (PGD_TUNE_SPMV_BLOCK_DIA) for
+        the next products and solves, or (on false) the CSR product again; returns the number of products launched from that form
+        so far.  The results do not depend on it, bit for bit."""
+        self.tune(TUNE_SPMV_BLOCK_DIA, 1 if on else 0)
+        return self.bdia_stats()["products"]
+
+    def bdia_stats(self):
+        f, p, b, ms = I64(), I64(), I64(), C.c_double()
+        self._ck(self.lib.pgd_bdia_counts(self.h, C.byref(f), C.byref(p), C.byref(b)))
+        self._ck(self.lib.pgd_bdia_times(self.h, C.byref(ms)))
+        return {"forms_built": f.value, "products": p.value, "fallbacks": b.value, "extract_ms": ms.value}
 
     def calib_stream(self, v, bytes_per_lane, store=False):
         self._ck(self.lib.pgd_calib_stream(self.h, v, int(bytes_per_lane), int(bool(store))))

@@ -167,7 +167,17 @@ struct Csr : Obj {
     int64_t rec_nbc = 0;
     size_t rec_bc_bytes = 0;
     size_t vals_bytes = 0, dinv_bytes = 0, uvals_bytes = 0, cls_bytes = 0;
+    // row-diagonal form of an operator on a blocked P1 layout over a box lattice (pgd_bdia.hip, PGD_TUNE_SPMV_BLOCK_DIA): 15 ncomp
+    // arrays of bdia_stride doubles, array t * ncomp + d holds at row r = ncomp i + c the entry a(r, ncomp (i + off_t) + d), an exact
+    // 0.0 where the row stores none.  It belongs to the values of `version` bdia_seen: bdia_ok says what was decided for them (the
+    // form stands, or the operator keeps the CSR product); any other version has not been looked at yet
+    double *bdia = nullptr;
+    size_t bdia_bytes = 0;
+    int64_t bdia_stride = 0;
+    uint64_t bdia_seen = 0;
+    bool bdia_ok = false;
     ~Csr() override {
+        if (bdia) dev_release(ctx, bdia, bdia_bytes);
         if (rec_bc) dev_release(ctx, rec_bc, rec_bc_bytes);
         if (cls_table) dev_release(ctx, cls_table, cls_bytes);
         if (vals) dev_release(ctx, vals, vals_bytes);
@@ -349,6 +359,10 @@ struct Ctx {
     int pcg_derive_scaled = 1;    // ... whose stencil couplings are DERIVED from the verified stencil of A where that exists (PGD_TUNE_PCG_DERIVE_SCALED)
     int spmv_combine_dia = 1;     // structured grids: op_combine also forms the diagonal form from the atoms' diagonal forms
     int spmv_sym = 1;             // PCG products from the symmetric half storage when the mesh qualifies
+    int spmv_block_dia = 0;       // 1: whole-range products of an operator on a blocked P1 layout over a 3-D box lattice from its row-diagonal form (k_spmv_bdia, PGD_TUNE_SPMV_BLOCK_DIA; bit-identical to k_spmv_csr)
+    int64_t bdia_forms = 0, bdia_products = 0, bdia_fallbacks = 0;   // forms extracted, products launched from one, operators that kept the CSR product
+    double bdia_extract_ms = 0.0; // time the extractions took on the device, summed
+    hipEvent_t bdia_ev[2] = {nullptr, nullptr};
     int block_storage = 1;        // storage of the spectral start space (PGD_TUNE_BLOCK_STORAGE): 0 = f64 vectors, 1 = fp32 block, 2 = f64 block
 
     // SpMV launch timing (HIP events on `stream`)
@@ -485,6 +499,13 @@ int launch_spmv_dia_rows2(Ctx *c, const Mesh *m, const Csr *a, const double *x, 
 int combine_dia(Ctx *c, const Mesh *m, Csr *o, Csr *const *atoms, const double *coefs, int n, const uint8_t *mask);
 int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double *y, const double *w, int64_t r0,
                    int64_t r1, bool dot, bool store, const int *flags, int *nparts_out);
+// pgd_bdia.hip: the product over all rows from the operator's row-diagonal form where the knob is on and the operator has or gets one
+// (*done = true: launched); anything else leaves *done false for the CSR product, counted once per operator as a fallback
+int launch_spmv_bdia(Ctx *c, const Mesh *m, Csr *a, const double *x, double *y, const double *w, bool dot, bool store,
+                     const int *flags, int *nparts_out, bool *done);
+// pgd_spmv.hip: the launch-timing bracket of a product (HIP events around one launch in four)
+int prof_begin(Ctx *c, bool dot, bool store, bool *timed);
+int prof_end(Ctx *c, const Mesh *m, int64_t nrows, double own_per_row);
 
 inline Vec *get_vec(Ctx *c, pgd_handle h) { return static_cast<Vec *>(get_obj(c, h, Obj::VEC)); }
 inline Mesh *get_mesh(Ctx *c, pgd_handle h) { return static_cast<Mesh *>(get_obj(c, h, Obj::MESH)); }

@@ -298,7 +298,7 @@ __global__ __launch_bounds__(TPB) void k_spmv_multi(SpmvMultiArgs A) {
 
 // HIP-event timing of one launch in four (the events perturb the stream by ~5 us each side); the byte count is
 // the CSR formula of SURVEY 8d for the rows covered, whatever internal form of the operator the kernel reads
-static int prof_begin(Ctx *c, bool dot, bool store, bool *timed) {
+int prof_begin(Ctx *c, bool dot, bool store, bool *timed) {
     // (PCG only: the fused-dot product that stores y, or - where the update forms A p again - the dot-only one of that loop, spmv_qq set)
     const bool candidate = c->prof && (!c->prof_pcg_only || (dot && (store || c->spmv_qq)));
     *timed = candidate && ((c->prof_seen++ & 3) == 0);
@@ -312,7 +312,7 @@ static int prof_begin(Ctx *c, bool dot, bool store, bool *timed) {
 
 // own_per_row > 0: bytes per row the kernel that ran must move at least (its own storage form); < 0: -(bytes per
 // stored entry) of a CSR form, plus row pointer / pattern id, x and y per row
-static int prof_end(Ctx *c, const Mesh *m, int64_t nrows, double own_per_row) {
+int prof_end(Ctx *c, const Mesh *m, int64_t nrows, double own_per_row) {
     PGD_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
     Ctx::ProfRec &rec = c->ev_rec[c->ev_used / 2];
     c->ev_used += 2;
@@ -2833,7 +2833,21 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
     if (!(c->spmv_sym && m->sym_w && a->uvals_valid && a->uvals)) {
         PGD_TRY(not_virtual());
         PGD_TRY(ensure_vals(c, m, const_cast<Csr *>(a)));
+        // blocked P1 layouts over a box lattice: the same product, bit for bit, from the operator's row-diagonal form (pgd_bdia.hip)
+        if (c->spmv_block_dia && m->ncomp > 1 && !a->immutable && r0 == 0 && (r1 < 0 || r1 == m->nv)) {
+            bool done = false;
+            PGD_TRY(launch_spmv_bdia(c, m, const_cast<Csr *>(a), x, y, w, dot, store, flags, nparts_out, &done));
+            if (done) return PGD_OK;
+        }
         return launch_spmv(c, m, a->vals, x, y, w, r0, r1, dot, store, flags, nparts_out);
+    }
+    if (c->spmv_block_dia && m->ncomp > 1 && !a->immutable && r0 == 0 && (r1 < 0 || r1 == m->nv) && a->bdia_seen != a->version) {
+        // a blocked operator held in symmetric half storage (2-D bases: rows of at most 14 entries) keeps that product: it has no
+        // row-diagonal form, which is counted once like every other such operator
+        Csr *o = const_cast<Csr *>(a);
+        o->bdia_seen = a->version;
+        o->bdia_ok = false;
+        c->bdia_fallbacks += 1;
     }
     if (r1 < 0) r1 = m->nv;
     if (r0 < 0 || r0 > r1 || r1 > m->nv) return fail(c, PGD_ERR_INVALID, "spmv: bad row range");
@@ -3352,6 +3366,7 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_PCG_SCALAR_S && value >= 0 && value <= 1) { c->pcg_scalar_s = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_PCG_FUSED_MARCH && value >= 0 && value <= 1) { c->pcg_fused_march = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_BLOCK_STORAGE && value >= 0 && value <= 2) { c->block_storage = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_SPMV_BLOCK_DIA && value >= 0 && value <= 1) { c->spmv_block_dia = (int)value; return PGD_OK; }
     return fail(c, PGD_ERR_INVALID, "tune: unknown knob %d or value out of range", knob);
 }
 
@@ -3372,6 +3387,8 @@ int pgd_spmv(pgd_handle h, pgd_handle ah, pgd_handle xh, pgd_handle yh, int64_t 
         if (q0 >= 0 && q1 <= m->nv && q0 <= q1 && q0 % plane == 0 && q1 % plane == 0)
             return launch_spmv_op(c, m, a, x->d, y->d, nullptr, q0, q1, false, true, nullptr, nullptr);
     }
+    // (an operator on a blocked layout with PGD_TUNE_SPMV_BLOCK_DIA on: launch_spmv_op decides between the two forms of the product)
+    if (c->spmv_block_dia && m->ncomp > 1 && !a->immutable) return launch_spmv_op(c, m, a, x->d, y->d, nullptr, r0, r1, false, true, nullptr, nullptr);
     PGD_TRY(ensure_vals(c, m, a));
     return launch_spmv(c, m, a->vals, x->d, y->d, nullptr, r0, r1, false, true, nullptr, nullptr);
 }

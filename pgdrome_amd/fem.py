@@ -3706,6 +3706,10 @@ def _solve_linear(A, b, x, prm):
             want_mg = asks_mg and part is None
             want_vmg = prec_name in VARIABLE_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_variable")
             want_cmg = prec_name in COMPONENT_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_component")
+            prod = prm.get("block_product", "csr")
+            prod_name = "csr" if isinstance(prod, _Params) else str(prod).lower()
+            if prod_name not in BLOCK_PRODUCT_NAMES:      # (before any knob is switched)
+                raise ValueError("settings['block_product']: expected one of %s, got %r" % (BLOCK_PRODUCT_NAMES, prod))
             mg0 = vmg0 = cmg0 = None
             used = used_v = used_c = 0
             if want_mg and hasattr(be, "precondition"):
@@ -3714,6 +3718,14 @@ def _solve_linear(A, b, x, prm):
                 vmg0 = be.precondition_variable(True)
             elif want_cmg:
                 cmg0 = be.precondition_component(True)
+            # settings["block_product"] = "diagonal" (opt-in, default "csr"): the products of a vector-valued P1 space on a box
+            # lattice from the operator's row-diagonal form (csrc/pgd_bdia.hip) - the same numbers, bit for bit; the library says
+            # in its counters whether the operator had one.  A backend without it and a row-sharded layout ignore the key.
+            # (the counter is read either way: PGD_TUNE=58=1 switches whole runs without the key)
+            has_bd = part is None and getattr(A.lay, "ncomp", 1) > 1 and hasattr(be, "block_product") and hasattr(be, "bdia_stats")
+            want_bd = has_bd and prod_name == "diagonal"
+            bd0 = (be.block_product(True) if want_bd else be.bdia_stats()["products"]) if has_bd else None
+            used_b = 0
             try:
                 if part is not None:
                     # a row-sharded lattice: the V-cycle with level 0 on the slabs and levels >= 1 replicated (dist.pcg_mg);
@@ -3734,6 +3746,8 @@ def _solve_linear(A, b, x, prm):
                     used_v = be.precondition_variable(False) - vmg0
                 if cmg0 is not None:
                     used_c = be.precondition_component(False) - cmg0
+                if bd0 is not None:
+                    used_b = (be.block_product(False) if want_bd else be.bdia_stats()["products"]) - bd0
             STATS["pcg_seconds"] += time.perf_counter() - t_solve      # the solve returns synchronised
             info.update(method="mg_pcg" if used > 0 else "vmg_pcg" if used_v > 0 else "cmg_pcg" if used_c > 0 else "jacobi_pcg", iterations=it, relres=rel)
             if used > 0:
@@ -3742,6 +3756,9 @@ def _solve_linear(A, b, x, prm):
                 STATS["vmg_solves"] = STATS.get("vmg_solves", 0) + 1
             if used_c > 0:
                 STATS["cmg_solves"] = STATS.get("cmg_solves", 0) + 1
+            info["product"] = "block_dia" if used_b > 0 else "csr"
+            if used_b > 0:
+                STATS["block_dia_solves"] = STATS.get("block_dia_solves", 0) + 1
             if rel > max(rtol, 1e-14) * 1.0001 and it >= maxit:
                 # dolfin's Krylov solvers raise on non-convergence unless told otherwise (error_on_nonconvergence,
                 # default True): an unconverged mode must not be stored silently
@@ -3765,6 +3782,8 @@ MULTIGRID_NAMES = ("amg", "hypre_amg", "petsc_amg", "ml_amg", "gmg", "multigrid"
 VARIABLE_MULTIGRID_NAMES = ("vmg", "variable_multigrid")
 # ... and those that select one such cycle per component of a vector-valued P1 space on a box lattice: opt-in, its own names
 COMPONENT_MULTIGRID_NAMES = ("cmg", "component_multigrid")
+# values of settings["block_product"]: the product of a vector-valued P1 operator on a box lattice from CSR or from its row-diagonal form
+BLOCK_PRODUCT_NAMES = ("csr", "diagonal")
 
 
 def _apply_bcs_system(A, b, bcs):
@@ -3844,7 +3863,7 @@ class NonlinearVariationalSolver:
             h = DirichletBC.__new__(DirichletBC)
             h._V, h._vertices, h._vals = bc._V, bc._vertices, np.zeros_like(bc._vals)
             bcs_h.append(h)
-        lin = _Params({k: v for k, v in ns.items() if k in ("linear_solver", "preconditioner")})
+        lin = _Params({k: v for k, v in ns.items() if k in ("linear_solver", "preconditioner", "block_product")})
         lin["relative_tolerance"] = ns.get("krylov_relative_tolerance", 1e-10) \
             if not isinstance(ns.get("krylov_relative_tolerance"), _Params) else 1e-10
         rtol, atol, maxit = float(ns["relative_tolerance"]), float(ns["absolute_tolerance"]), int(ns["maximum_iterations"])

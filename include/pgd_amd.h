@@ -87,6 +87,17 @@ int pgd_mesh_upload(pgd_handle ctx, const double *coords, int64_t nv, int gdim,
  * (vectors of ncomp*nv entries; pgd_op_combine, pgd_spmv, pgd_pcg_solve, ... apply unchanged); its atoms
  * are built from atoms of the scalar layout with pgd_atom_embed.                                 */
 int pgd_mesh_blocked(pgd_handle ctx, pgd_handle scalar_mesh, int ncomp, pgd_handle *mesh);
+/* Bind a scalar P2 layout on tetrahedra (nodes: the mesh vertices in their order, then one node per edge) to the box lattice of its
+ * vertices, for PGD_TUNE_PCG_PRECOND = 4.  p1_mesh: the P1 layout of the same mesh - a 3-D lattice in diagonal form, which
+ * supplies the lattice dimensions; edge_vertices: host, n_edges pairs of end vertices, edge e being node nv(p1) + e.  Checked on
+ * the host: nv(p2) = nv(p1) + n_edges, every edge joins two vertices that differ by one of the 14 non-zero pattern vectors
+ * +-(dx, dy, dz), d in {0,1}^3, and no (vertex, pattern vector) slot is taken twice.  *bound = 1: two parent ints per node and a
+ * vertex -> edge-node table of 14 arrays are on the device; 0: a check failed - no error, the layout is remembered as refused and
+ * its solves fall back.  Blocked layouts use the binding of their scalar layout.  A later call decides anew.
+ * The CALLER guarantees that edge_vertices is the edge list of p2_mesh itself (edge e = its node nv(p1) + e, as its cell records
+ * number them) and that p1_mesh holds its vertices: the cell connectivity is not compared with the list, and a consistent list
+ * of another mesh of the same sizes would bind and give wrong blocks without raising the off-pattern flag.                   */
+int pgd_mesh_p2_bind(pgd_handle ctx, pgd_handle p2_mesh, pgd_handle p1_mesh, const int32_t *edge_vertices, int64_t n_edges, int *bound);
 int pgd_mesh_info(pgd_handle ctx, pgd_handle mesh, int64_t *nv, int64_t *nc, int64_t *nnz,
                   int32_t *max_row_len, int32_t *kl, int32_t *ku);
 int pgd_mesh_pattern_download(pgd_handle ctx, pgd_handle mesh, int32_t *row_ptr, int32_t *cols);
@@ -229,7 +240,8 @@ typedef enum {
     PGD_PCG_FORM_PLAIN = 7                  /* two reductions, scaled */
 } pgd_pcg_form;
 typedef enum {
-    PGD_PCG_PRECOND_JACOBI = 0, PGD_PCG_PRECOND_MG = 1, PGD_PCG_PRECOND_VMG = 2, PGD_PCG_PRECOND_CMG = 3
+    PGD_PCG_PRECOND_JACOBI = 0, PGD_PCG_PRECOND_MG = 1, PGD_PCG_PRECOND_VMG = 2, PGD_PCG_PRECOND_CMG = 3,
+    PGD_PCG_PRECOND_PMG = 4
 } pgd_pcg_precond;
 int pgd_pcg_last_form(pgd_handle ctx, int *form, int *precond);
 /* Banded LU with partial pivoting in one workgroup, for the small and possibly
@@ -632,7 +644,15 @@ enum {
                                 base lattice (separate-displacement-component preconditioning of elasticity); the blocks are read
                                 from the CSR values once per solve, the iteration stays the unscaled recurrence on the CSR product.
                                 Anything else - scalar or P2 layouts, no lattice, at most 4096 nodes - takes Jacobi and is counted
-                                by pgd_cmg_counts. */
+                                by pgd_cmg_counts.
+                                4 (opt-in, the frontend's "pmg"): P2 layouts on tetrahedra, scalar or BLOCKED with 2 or 3 components, whose
+                                scalar layout pgd_mesh_p2_bind has bound to the 3-D box lattice of its vertices - p-multigrid:
+                                z = D^-1 r + P (M_c (P^T r)_c)_c, P the interpolation from P1 on the same mesh (1 at a vertex, 1/2 from
+                                each end of an edge), M_c one such V-cycle on the component's block of P^T A P, a 15-point operator
+                                on the vertex lattice formed from the CSR values once per solve; additive, so an iteration has no
+                                product beyond its own.  The unscaled recurrence on the CSR product.  Anything else - P1 or unbound
+                                layouts, at most 4096 vertices or fewer than 8 along an axis, a term off the pattern, no memory -
+                                takes Jacobi and is counted by pgd_pmg_counts. */
     PGD_TUNE_CLS_CACHE = 39, /* 1 (default): a mesh remembers the class codes of the operators classified on it (by the signature of their
                                 Dirichlet set, scaled or not): the next operator with that structure - the same atoms with other
                                 coefficients, every solve of a fixed-point pass - copies the codes, rebuilds the table from the classes'
@@ -785,6 +805,14 @@ int pgd_vmg_times(pgd_handle ctx, double *setup_ms, int64_t *march_passes);
  * setups (extraction of the diagonal blocks + ncomp Galerkin chains) in ms and the level passes issued to k_vmg_march.       */
 int pgd_cmg_counts(pgd_handle ctx, int64_t *solves, int64_t *fallbacks, int64_t *levels);
 int pgd_cmg_times(pgd_handle ctx, double *setup_ms, int64_t *march_passes);
+/* ... and for PGD_TUNE_PCG_PRECOND = 4 (the other three pairs of counters stay untouched): solves preconditioned by the p-multigrid
+ * cycle / fallen back to Jacobi, levels of one component's hierarchy (0: none held); device time of the setups (eliminated bytes,
+ * the blocks of P^T A P from the CSR values, ncomp Galerkin chains) in ms and the level passes issued to k_vmg_march.
+ * pgd_pmg_coarse reads back what the last such solve built for component comp: the 8 slot arrays of level 0 (8 nvert doubles, slot
+ * dx + 2 dy + 4 dz of vertex I = the entry (I, I + (dx, dy, dz)) of the block) and its eliminated bytes (nvert).                 */
+int pgd_pmg_counts(pgd_handle ctx, int64_t *solves, int64_t *fallbacks, int64_t *levels);
+int pgd_pmg_times(pgd_handle ctx, double *setup_ms, int64_t *march_passes);
+int pgd_pmg_coarse(pgd_handle ctx, int comp, double *slots_out, uint8_t *el_out);
 /* PGD_TUNE_SPMV_BLOCK_DIA since the context was created: row-diagonal forms extracted, product launches that read one (a chunk of
  * iterations that is replayed as a graph counts once), operators on a blocked layout that were asked for a whole-range product with
  * the knob on and kept the CSR kernel (each counted once per set of values); device time of the extractions in ms.           */

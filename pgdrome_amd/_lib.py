@@ -37,6 +37,7 @@ SIGNATURES = {
     "pgd_device_count": (C.c_int, []),
     "pgd_mesh_upload": (C.c_int, [H, PD, I64, C.c_int, PI32, I64, C.c_int, PH]),
     "pgd_mesh_blocked": (C.c_int, [H, H, C.c_int, PH]),
+    "pgd_mesh_p2_bind": (C.c_int, [H, H, H, PI32, I64, C.POINTER(C.c_int)]),
     "pgd_atom_embed": (C.c_int, [H, H, H, C.c_int, C.c_int, F64, H, PH]),
     "pgd_mesh_info": (C.c_int, [H, H, PI64, PI64, PI64, PI32, PI32, PI32]),
     "pgd_mesh_pattern_download": (C.c_int, [H, H, PI32, PI32]),
@@ -147,6 +148,9 @@ SIGNATURES = {
     "pgd_vmg_times": (C.c_int, [H, C.POINTER(C.c_double), PI64]),
     "pgd_cmg_counts": (C.c_int, [H, PI64, PI64, PI64]),
     "pgd_cmg_times": (C.c_int, [H, C.POINTER(C.c_double), PI64]),
+    "pgd_pmg_counts": (C.c_int, [H, PI64, PI64, PI64]),
+    "pgd_pmg_times": (C.c_int, [H, C.POINTER(C.c_double), PI64]),
+    "pgd_pmg_coarse": (C.c_int, [H, C.c_int, PD, PU8]),
     "pgd_bdia_counts": (C.c_int, [H, PI64, PI64, PI64]),
     "pgd_bdia_times": (C.c_int, [H, C.POINTER(C.c_double)]),
     "pgd_calib_stream": (C.c_int, [H, H, C.c_int, C.c_int]),
@@ -274,6 +278,13 @@ class Context:
         m = H(0)
         self._ck(self.lib.pgd_mesh_blocked(self.h, mesh, int(ncomp), C.byref(m)))
         return m.value
+
+    def mesh_p2_bind(self, p2_mesh, p1_mesh, edge_vertices):
+        """Bind a scalar P2 layout on tetrahedra to the box lattice of its vertices (pgd_mesh_p2_bind): True where the checks pass."""
+        ev = np.ascontiguousarray(edge_vertices, dtype=np.int32).reshape(-1, 2)
+        ok = C.c_int(0)
+        self._ck(self.lib.pgd_mesh_p2_bind(self.h, p2_mesh, p1_mesh, iptr(ev), ev.shape[0], C.byref(ok)))
+        return bool(ok.value)
 
     def atom_embed(self, bmesh, src, cv, cu, coef=1.0, dst=0):
         out = H(0)
@@ -611,7 +622,7 @@ class Context:
         return it.value, rel.value
 
     PCG_FORMS = ("PRECOND", "TEXTBOOK", "TWO_LAUNCH", "FOLDED", "SINGLE_SYNC", "SINGLE_SYNC_RECOMPUTE", "DEFERRED_X", "PLAIN")
-    PCG_PRECONDS = ("JACOBI", "MG", "VMG", "CMG")
+    PCG_PRECONDS = ("JACOBI", "MG", "VMG", "CMG", "PMG")
 
     def pcg_last_form(self):
         """(form, preconditioner) of the last pcg_solve by name (pgd_pcg_form / pgd_pcg_precond), (None, None) before the first."""
@@ -922,6 +933,26 @@ class Context:
         self._ck(self.lib.pgd_cmg_counts(self.h, C.byref(a), C.byref(b), C.byref(l)))
         self._ck(self.lib.pgd_cmg_times(self.h, C.byref(ms), C.byref(m)))
         return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
+
+    def precondition_p(self, on):
+        """Select the p-multigrid cycle for P2 operators on bound box lattices (PGD_TUNE_PCG_PRECOND = 4) for the next pcg_solve calls,
+        or (on false) the Jacobi-PCG again; returns the number of solves that cycle has preconditioned so far."""
+        self.tune(40, 4 if on else 0)
+        return self.pmg_stats()["solves"]
+
+    def pmg_stats(self):
+        a, b, l, m, ms = I64(), I64(), I64(), I64(), C.c_double()
+        self._ck(self.lib.pgd_pmg_counts(self.h, C.byref(a), C.byref(b), C.byref(l)))
+        self._ck(self.lib.pgd_pmg_times(self.h, C.byref(ms), C.byref(m)))
+        return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
+
+    def pmg_coarse(self, comp, nvert):
+        """What the last solve under the p-multigrid cycle built for component comp: (the 8 level-0 slot arrays as an 8 x nvert
+        array, the eliminated bytes of the nvert vertices)."""
+        slots = np.empty((8, int(nvert)), dtype=np.float64)
+        el = np.empty(int(nvert), dtype=np.uint8)
+        self._ck(self.lib.pgd_pmg_coarse(self.h, int(comp), dptr(slots), el.ctypes.data_as(PU8)))
+        return slots, el
 
     def block_product(self, on):
         """Select the row-diagonal product for operators on vector-valued P1 layouts over box lattices (PGD_TUNE_SPMV_BLOCK_DIA) for

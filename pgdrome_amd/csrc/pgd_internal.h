@@ -118,9 +118,17 @@ struct Mesh : Obj {
     uint16_t *pids = nullptr;    // nv
     int *dict_off = nullptr;     // dict_count x DICT_DLEN relative offsets
     int dict_count = 0;          // 0: dictionary not available (irregular pattern) -> plain CSR kernel
+    // A scalar P2 layout on tetrahedra bound to the box lattice of its vertices (pgd_mesh_p2_bind, pgd_pmg.hip): nodes 0 .. p2_nvert - 1
+    // are the lattice's vertices in lattice order, every further node is the midpoint of an edge along one of the 14 pattern vectors.
+    // p2_bound: 0 never asked, 1 bound, -1 refused (a check failed: solves under PGD_TUNE_PCG_PRECOND = 4 fall back)
+    int p2_bound = 0;
+    int p2_nx = 0, p2_ny = 0, p2_nz = 0;
+    int64_t p2_nvert = 0;
+    int *p2_par = nullptr;       // 2 arrays of nv ints: the two end vertices of a node's edge (equal for a vertex node)
+    int *p2_v2e = nullptr;       // 14 arrays of p2_nvert ints: array t - 1 holds the node of the edge from a vertex along pattern vector t, -1: none
     ~Mesh() override {
         for (void *p : {(void *)coords, (void *)cells, (void *)cellsN, (void *)v2c_ptr, (void *)v2c,
-                        (void *)row_ptr, (void *)cols, (void *)pids, (void *)dict_off, (void *)sym_tab})
+                        (void *)row_ptr, (void *)cols, (void *)pids, (void *)dict_off, (void *)sym_tab, (void *)p2_par, (void *)p2_v2e})
             if (p) (void)hipFree(p);
         for (ClsCache &e : cls_cache) if (e.same) (void)hipFree(e.same);      // (the block starts at `same`)
         if (bc_dev) (void)hipFree(bc_dev);
@@ -321,6 +329,9 @@ struct Ctx {
     struct Cmg *cmg = nullptr;    // pcg_precond = 3: one such hierarchy per component of a blocked P1 operator, kept across solves on the same lattice and ncomp
     int64_t cmg_solves = 0, cmg_fallbacks = 0, cmg_marches = 0;
     double cmg_setup_ms = 0.0;    // extraction of the diagonal blocks + their Galerkin setups, summed
+    struct Pmg *pmg = nullptr;    // pcg_precond = 4: one such hierarchy per component on P^T A P of a P2 operator over a bound box lattice (pgd_pmg.hip)
+    int64_t pmg_solves = 0, pmg_fallbacks = 0, pmg_marches = 0;
+    double pmg_setup_ms = 0.0;    // eliminated bytes + Galerkin blocks from the CSR values + their Galerkin chains, summed
     // pgd_eval_batch (pgd_eval.hip): kernel variant (1 MFMA, 0 plain fma chains), grid cap and samples per launch (0: the launcher's choice);
     // the pinned staging of the coefficients in fragment order, two chunks deep, with the events behind the copies
     int eval_variant = 1, eval_grid_max = 0, eval_chunk = 0;
@@ -492,6 +503,13 @@ bool cmg_prepare(Ctx *c, const Mesh *m, const Mesh *base, const Csr *a);       /
 int cmg_fix_start(Ctx *c, const double *b, double *x, int64_t n);              // x = b on the dofs the component hierarchies have eliminated
 int cmg_apply(Ctx *c, const double *r, double *z, int64_t n, int *nparts);     // partial sums of r . z into c->partials
 void cmg_note_setup(Ctx *c);
+// pgd_pmg.hip: p-multigrid for P2 operators over a bound box lattice (PGD_TUNE_PCG_PRECOND = 4): z = D^-1 r + P (M_c (P^T r)_c)_c with P the
+// interpolation from P1 on the vertex lattice and M_c that V-cycle on the component's block of P^T A P
+bool pmg_prepare(Ctx *c, const Mesh *m, const Csr *a);                         // true: usable (a->vals and a->dinv are current; blocks and hierarchies formed)
+int pmg_fix_start(Ctx *c, const double *b, double *x, int64_t n);              // x = b on the eliminated dofs
+int pmg_apply(Ctx *c, const Csr *a, const double *r, double *z, int64_t n, int *nparts);   // partial sums of r . z into c->partials
+void pmg_note_setup(Ctx *c);
+void pmg_release(Ctx *c);
 void eval_release(Ctx *c);          // pgd_eval.hip: the pinned coefficient staging of pgd_eval_batch
 int sym_scale(Ctx *c, const Mesh *m, Csr *a, const double *s);   // pgd_spmv.hip: slot values *= s_i s_j
 int launch_spmv_dia_rows2(Ctx *c, const Mesh *m, const Csr *a, const double *x, double *y, const double *w, int64_t r0a,

@@ -1487,7 +1487,8 @@ struct PcgRun {
 // ---- preconditioner (PGD_TUNE_PCG_PRECOND).  1: one stencil on a lattice whose eliminated nodes are its hull (pgd_mg.hip), 2: the V-cycle on
 // the diagonal form with per-row coefficients (pgd_vmg.hip: any operator on a lattice, any Dirichlet set) - both for the scaled
 // recurrence; 3: blocked P1 layouts over a box lattice, one such V-cycle per component on the diagonal blocks of D^-1/2 A D^-1/2, read
-// from the CSR values - for the unscaled one.  The cycles work on vectors that vanish on the eliminated rows: x gets their exact
+// from the CSR values - for the unscaled one; 4: P2 layouts bound to a box lattice, z = D^-1 r + P M P^T r with such cycles on the blocks of
+// P^T A P (pgd_pmg.hip) - the unscaled one too.  The cycles work on vectors that vanish on the eliminated rows: x gets their exact
 // solution from the start.  Any other request is Jacobi, and counted.
 static int pcg_precond_prepare(PcgRun &R) {
     Ctx *c = R.c;
@@ -1499,9 +1500,14 @@ static int pcg_precond_prepare(PcgRun &R) {
         PGD_TRY(ensure_vals(c, m, R.o));
         if (cmg_prepare(c, m, get_mesh(c, m->base), R.o)) { R.precond = PGD_PCG_PRECOND_CMG; c->cmg_solves += 1; return cmg_fix_start(c, R.b, R.x, R.n); }
     }
+    if (want == 4 && !R.scaled) {
+        PGD_TRY(ensure_vals(c, m, R.o));
+        if (pmg_prepare(c, m, R.o)) { R.precond = PGD_PCG_PRECOND_PMG; c->pmg_solves += 1; return pmg_fix_start(c, R.b, R.x, R.n); }
+    }
     if (want == 1) c->mg_fallbacks += 1;
     if (want == 2) c->vmg_fallbacks += 1;
     if (want == 3) c->cmg_fallbacks += 1;
+    if (want == 4) c->pmg_fallbacks += 1;
     return PGD_OK;
 }
 
@@ -1511,6 +1517,7 @@ static int pcg_precond_apply(PcgRun &R, const double *r, double *z_out, int *np)
     case PGD_PCG_PRECOND_MG: return mg_vcycle(R.c, r, true, np, z_out);
     case PGD_PCG_PRECOND_VMG: return vmg_vcycle(R.c, R.c->vmg, r, true, np, z_out, &R.c->vmg_marches);
     case PGD_PCG_PRECOND_CMG: return cmg_apply(R.c, r, z_out ? z_out : R.z, R.n, np);
+    case PGD_PCG_PRECOND_PMG: return pmg_apply(R.c, R.o, r, z_out ? z_out : R.z, R.n, np);
     case PGD_PCG_PRECOND_JACOBI: break;
     }
     return fail(R.c, PGD_ERR_INVALID, "pcg_solve: no cycle to apply");
@@ -1670,12 +1677,12 @@ static int pcg_iter_plain(PcgRun &R, int k, int nparts = -1) {      // (nparts >
     return PGD_OK;
 }
 
-// textbook PCG with z = M r from a cycle in place of z = D^-1 r (MG / VMG: the scaled recurrence, CMG: the unscaled one); the stop test
+// textbook PCG with z = M r from a cycle in place of z = D^-1 r (MG / VMG: the scaled recurrence, CMG / PMG: the unscaled one); the stop test
 // stays the one of the Jacobi form, the cycle's r.z goes over the r~.r~ the test has used
 static int pcg_iter_precond(PcgRun &R, int k) {
     int nparts = 0, np = 0;
     PGD_TRY(pcg_product(R, &nparts));
-    PGD_TRY(R.precond == PGD_PCG_PRECOND_CMG ? pcg_update_unscaled(R, k, nullptr) : pcg_update_scaled(R, k));
+    PGD_TRY(R.scaled ? pcg_update_scaled(R, k) : pcg_update_unscaled(R, k, nullptr));
     PGD_TRY(pcg_precond_apply(R, R.r, nullptr, &np));
     PGD_TRY(reduce_partials(R.c, R.c->partials, np, 1, R.out(k), -1, 0, 0));
     pcg_direction(R, k, pcg_precond_result(R));
@@ -1905,6 +1912,7 @@ static int pcg_finish(PcgRun &R, const int f[4], int *iters, double *relres) {
     PGD_HIP(c, hipStreamSynchronize(c->stream));
     if (R.precond == PGD_PCG_PRECOND_VMG) vmg_note_setup(c);
     if (R.precond == PGD_PCG_PRECOND_CMG) cmg_note_setup(c);
+    if (R.precond == PGD_PCG_PRECOND_PMG) pmg_note_setup(c);
     if (iters) *iters = f[1];
     const double rr = R.scaled ? s[S_TMP] : (f[1] > 0) ? s[R.S_PAIR + 2 * ((f[1] - 1) & 1) + 1] : s[R.S_INIT + 1];
     const double bb = s[R.S_INIT + 2];

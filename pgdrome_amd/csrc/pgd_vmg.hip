@@ -27,7 +27,7 @@
 // Levels with at least mg_march_min nodes along x and y run their two passes in k_vmg_march: the z-march of the diagonal form
 // (dia_march2 of pgd_dia_march.h, the one body it shares with k_spmv_dia_march2: planes of the input staged in an LDS ring, the
 // plane-below couplings handed on through LDS) with the two epilogues of the cycle; smaller levels in the plain kernels.
-#include "pgd_internal.h"
+#include "pgd_vmg.h"
 #include "pgd_dia_march.h"
 
 #include <cmath>
@@ -36,26 +36,7 @@
 
 namespace pgd {
 
-struct VGrid { int nx, ny, nz; };
-
-struct VLevel {
-    VGrid g{0, 0, 0};
-    int64_t n = 0, stride = 0;
-    double *a = nullptr;                                // 8 slot arrays (level 0: the operator's, not owned)
-    int unit = 0;                                       // slot 0 is exactly 1 and is not loaded
-    double *w = nullptr;                                // l1-Jacobi weights, 0 on eliminated nodes
-    uint8_t *el = nullptr;                              // 1 = eliminated
-    double *b = nullptr, *x = nullptr, *t = nullptr;    // right-hand side, result, work (level 0: b is the caller's r)
-};
-
-struct Vmg {
-    int nx = 0, ny = 0, nz = 0;
-    std::vector<VLevel> lv;
-    int np0 = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    bool own0 = false;                                  // level 0 owns its slot arrays and a right-hand side (a component hierarchy of Cmg)
-};
+// (VGrid, VLevel, Vmg and the pattern vectors: pgd_vmg.h, shared with pgd_pmg.hip)
 
 // pcg_precond = 3: one hierarchy per displacement component of a blocked P1 operator (the diagonal blocks of its scaled form)
 struct Cmg {
@@ -66,17 +47,6 @@ struct Cmg {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
 };
-
-constexpr int VMG_BOTTOM_MAX = 4096, VMG_SWEEPS = 24;
-
-// pattern vector t: 0..7 = +(dx, dy, dz) with the bits of t, 8..14 = -(bits of t - 7)
-__device__ __host__ constexpr int vp_x(int t) { return t < 8 ? (t & 1) : -((t - 7) & 1); }
-__device__ __host__ constexpr int vp_y(int t) { return t < 8 ? ((t >> 1) & 1) : -(((t - 7) >> 1) & 1); }
-__device__ __host__ constexpr int vp_z(int t) { return t < 8 ? ((t >> 2) & 1) : -(((t - 7) >> 2) & 1); }
-// is (cx, cy, cz) a pattern vector?  (all components in {0, 1} or all in {0, -1})
-__device__ __host__ constexpr bool vp_in(int cx, int cy, int cz) {
-    return (cx >= 0 && cy >= 0 && cz >= 0 && cx <= 1 && cy <= 1 && cz <= 1) || (cx <= 0 && cy <= 0 && cz <= 0 && cx >= -1 && cy >= -1 && cz >= -1);
-}
 
 // does fine node 2K + c lie in the support of one of the coarse basis functions K + D, D in {0,1}^3?
 __device__ __host__ constexpr bool vmg_reaches(int cx, int cy, int cz) {
@@ -390,7 +360,7 @@ __global__ __launch_bounds__(TPB) void k_cmg_fix_start(int ncomp, CmgElim el, co
 template <int EPI, bool DOT>
 __global__ __launch_bounds__(256) void k_vmg_march(DiaArgs A) { dia_march2<DOT, true, EPI>(A); }
 
-static void vmg_free(Vmg *&M) {
+void vmg_free(Vmg *&M) {
     if (!M) return;
     for (size_t l = 0; l < M->lv.size(); ++l) {
         VLevel &L = M->lv[l];
@@ -414,11 +384,11 @@ static void cmg_free(Cmg *&G) {
     G = nullptr;
 }
 
-void vmg_release(Ctx *c) { vmg_free(c->vmg); cmg_free(c->cmg); }
+void vmg_release(Ctx *c) { vmg_free(c->vmg); cmg_free(c->cmg); pmg_release(c); }
 
 double *vmg_result(Vmg *M) { return M && !M->lv.empty() ? M->lv[0].x : nullptr; }
 
-static dim3 vmg_grid(const VGrid &g) { return dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4), (unsigned)g.nz); }
+dim3 vmg_grid(const VGrid &g) { return dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4), (unsigned)g.nz); }
 
 static bool vmg_marches(const Ctx *c, const VLevel &L, int *zchunk, int *wgs) {
     if (!(c->mg_march_min > 0 && L.g.nx >= c->mg_march_min && L.g.ny >= c->mg_march_min && L.g.nz >= 8)) return false;
@@ -432,13 +402,13 @@ static bool vmg_marches(const Ctx *c, const VLevel &L, int *zchunk, int *wgs) {
 }
 
 // the lattices the cycle takes: at least 8 nodes along every axis, within the grid limits of its launches
-static bool vmg_lattice_ok(int64_t nv, int nx, int ny, int nz) {
+bool vmg_lattice_ok(int64_t nv, int nx, int ny, int nz) {
     return (int64_t)nx * ny * nz == nv && std::min(nx, std::min(ny, nz)) >= 8 && nz <= 65535 && ny <= 4 * 65535;
 }
 
 // levels and buffers of M for this lattice (kept where M already has them); own0: level 0 gets slot arrays and a right-hand side of
 // its own.  false: no hierarchy (at most 4096 nodes) or no memory - M is released
-static bool vmg_levels_alloc(Vmg *&M, int nx, int ny, int nz, bool own0) {
+bool vmg_levels_alloc(Vmg *&M, int nx, int ny, int nz, bool own0) {
     if (M && M->nx == nx && M->ny == ny && M->nz == nz && M->own0 == own0) return true;
     vmg_free(M);                                                            // another lattice: new levels and buffers
     M = new Vmg();
@@ -471,7 +441,7 @@ static bool vmg_levels_alloc(Vmg *&M, int nx, int ny, int nz, bool own0) {
 }
 
 // the hierarchy of the operator level 0 holds NOW: eliminated nodes and weights of level 0, then level by level P^T A P and its weights
-static bool vmg_form(Ctx *c, Vmg *M, bool timed) {
+bool vmg_form(Ctx *c, Vmg *M, bool timed) {
     VLevel &L0 = M->lv[0];
     M->timed = timed && hipEventRecord(M->ev0, c->stream) == hipSuccess;
     k_vmg_rowsum<true><<<vmg_grid(L0.g), 256, 0, c->stream>>>(L0.g, L0.a, L0.stride, L0.unit, L0.el, L0.w);
@@ -517,7 +487,7 @@ int vmg_fix_start(Ctx *c, Vmg *M, const double *sc, const double *b, double *x, 
     return PGD_OK;
 }
 
-static int vmg_levels(const Vmg *M) { return M ? (int)M->lv.size() : 0; }
+int vmg_levels(const Vmg *M) { return M ? (int)M->lv.size() : 0; }
 
 // z = M r: the cycle from level 0 down and back up; the result lands in z_out (default: vmg_result(c)), the partial sums of
 // r . z in c->partials (*nparts of them); the level passes issued to k_vmg_march are counted in *marches

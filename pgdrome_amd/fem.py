@@ -306,6 +306,7 @@ class DofLayout:
                                       "/ triangles / tetrahedra (SURVEY 8(f4))" % (self.degree, mesh.ufl_cell()))
         self.n = self.coords.shape[0]
         self._handles, self._atoms, self._atom_weights = {}, {}, {}
+        self._p2_bound = weakref.WeakKeyDictionary()     # backend -> has it bound this layout to its vertex lattice (bind_p2_lattice)
         self._facet_atoms = {}
         self._cell_atoms = {}        # cell-subdomain atoms: _atom_key + (cell-set key,) -> (atom, weakref to the MeshFunction, to the weight)
         self._cw_atoms = {}          # cell-weighted atoms: _atom_key + (cell-set key | None, (id, version) of the DG0 field's vector) ->
@@ -445,6 +446,17 @@ class DofLayout:
             h = be.mesh(self.coords, self.cells)
             self._handles[id(be)] = h
         return h
+
+    def bind_p2_lattice(self, be):
+        """Bind this layout to the box lattice of its vertices on the backend (pgd_mesh_p2_bind), for the p-multigrid cycle: True
+        where the library took it.  Only a degree-2 layout on an unsharded 3-D mesh is offered (its own edge list and the P1 layout
+        of its own mesh, as the entry point requires); the answer is kept per backend, so a run asks once per layout."""
+        if self.degree != 2 or self.mesh.topology().dim() != 3 or self.part is not None or not hasattr(be, "mesh_p2_bind"):
+            return False
+        got = self._p2_bound.get(be)
+        if got is None:
+            got = self._p2_bound[be] = bool(be.mesh_p2_bind(self.handle(), self.mesh.layout(1).handle(), self.edge_vertices))
+        return got
 
     def _atom_key(self, be, kind, da, db, weight):
         if self.mesh.geometry().dim() == 1 and kind in (DUDV, WDUDV):
@@ -872,6 +884,10 @@ class BlockLayout:
             h = be.mesh_blocked(self.base.handle(), self.ncomp)
             self._handles[id(be)] = h
         return h
+
+    def bind_p2_lattice(self, be):
+        """A vector-valued layout uses the binding of its scalar layout."""
+        return self.base.bind_p2_lattice(be)
 
     def atom(self, kind, da=0, db=0, weight=None, cv=None, cu=None, cells=None, cw=None):
         """Scalar atom (kind, da, db) in block (cv, cu); cv = cu = None: in every diagonal block (norms).  A weight is a
@@ -3706,18 +3722,29 @@ def _solve_linear(A, b, x, prm):
             want_mg = asks_mg and part is None
             want_vmg = prec_name in VARIABLE_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_variable")
             want_cmg = prec_name in COMPONENT_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_component")
+            # P_MULTIGRID_NAMES (opt-in) ask for the p-multigrid cycle of pgd_pmg.hip: P2 spaces (scalar or vector-valued) on a 3-D box
+            # lattice, through the P1 V-cycles on P^T A P.  A degree-2 layout on a 3-D mesh is bound to its vertex lattice on the first
+            # such request (DofLayout.bind_p2_lattice).  The degree and the dimension decide only whether a binding is OFFERED, not
+            # whether the library is asked: the request reaches it for every unsharded space - a departure from routing "pmg" in the
+            # frontend only for degree 2 on a 3-D mesh - so that a P1 or a 2-D space under these names is a fallback the library
+            # COUNTS (pgd_pmg_counts), like a 3-D P2 space it refuses to bind; all of them are the Jacobi-PCG.
+            want_pmg = prec_name in P_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_p")
+            if want_pmg:
+                A.lay.bind_p2_lattice(be)
             prod = prm.get("block_product", "csr")
             prod_name = "csr" if isinstance(prod, _Params) else str(prod).lower()
             if prod_name not in BLOCK_PRODUCT_NAMES:      # (before any knob is switched)
                 raise ValueError("settings['block_product']: expected one of %s, got %r" % (BLOCK_PRODUCT_NAMES, prod))
-            mg0 = vmg0 = cmg0 = None
-            used = used_v = used_c = 0
+            mg0 = vmg0 = cmg0 = pmg0 = None
+            used = used_v = used_c = used_p = 0
             if want_mg and hasattr(be, "precondition"):
                 mg0 = be.precondition(1)
             elif want_vmg:
                 vmg0 = be.precondition_variable(True)
             elif want_cmg:
                 cmg0 = be.precondition_component(True)
+            elif want_pmg:
+                pmg0 = be.precondition_p(True)
             # settings["block_product"] = "diagonal" (opt-in, default "csr"): the products of a vector-valued P1 space on a box
             # lattice from the operator's row-diagonal form (csrc/pgd_bdia.hip) - the same numbers, bit for bit; the library says
             # in its counters whether the operator had one.  A backend without it and a row-sharded layout ignore the key.
@@ -3746,16 +3773,21 @@ def _solve_linear(A, b, x, prm):
                     used_v = be.precondition_variable(False) - vmg0
                 if cmg0 is not None:
                     used_c = be.precondition_component(False) - cmg0
+                if pmg0 is not None:
+                    used_p = be.precondition_p(False) - pmg0
                 if bd0 is not None:
                     used_b = (be.block_product(False) if want_bd else be.bdia_stats()["products"]) - bd0
             STATS["pcg_seconds"] += time.perf_counter() - t_solve      # the solve returns synchronised
-            info.update(method="mg_pcg" if used > 0 else "vmg_pcg" if used_v > 0 else "cmg_pcg" if used_c > 0 else "jacobi_pcg", iterations=it, relres=rel)
+            info.update(method="mg_pcg" if used > 0 else "vmg_pcg" if used_v > 0 else "cmg_pcg" if used_c > 0 else "pmg_pcg" if used_p > 0 else "jacobi_pcg",
+                        iterations=it, relres=rel)
             if used > 0:
                 STATS["mg_solves"] = STATS.get("mg_solves", 0) + 1
             if used_v > 0:
                 STATS["vmg_solves"] = STATS.get("vmg_solves", 0) + 1
             if used_c > 0:
                 STATS["cmg_solves"] = STATS.get("cmg_solves", 0) + 1
+            if used_p > 0:
+                STATS["pmg_solves"] = STATS.get("pmg_solves", 0) + 1
             info["product"] = "block_dia" if used_b > 0 else "csr"
             if used_b > 0:
                 STATS["block_dia_solves"] = STATS.get("block_dia_solves", 0) + 1
@@ -3771,17 +3803,19 @@ def _solve_linear(A, b, x, prm):
     finally:
         be.atom_free(op)
     STATS["linear_solves"] += 1
-    STATS["pcg_iterations"] += info.get("iterations", 0) if info.get("method") in ("jacobi_pcg", "mg_pcg", "vmg_pcg", "cmg_pcg") else 0
+    STATS["pcg_iterations"] += info.get("iterations", 0) if info.get("method") in ("jacobi_pcg", "mg_pcg", "vmg_pcg", "cmg_pcg", "pmg_pcg") else 0
     return info
 
 
-STATS = {"linear_solves": 0, "pcg_iterations": 0, "pcg_seconds": 0.0, "mg_solves": 0, "vmg_solves": 0, "cmg_solves": 0}
+STATS = {"linear_solves": 0, "pcg_iterations": 0, "pcg_seconds": 0.0, "mg_solves": 0, "vmg_solves": 0, "cmg_solves": 0, "pmg_solves": 0}
 # values of settings["preconditioner"] that select the geometric multigrid V-cycle (dolfin's names of its algebraic ones included)
 MULTIGRID_NAMES = ("amg", "hypre_amg", "petsc_amg", "ml_amg", "gmg", "multigrid", "mg")
 # ... and those that select the V-cycle for variable-coefficient operators (pgd_vmg.hip): opt-in, none of the names above
 VARIABLE_MULTIGRID_NAMES = ("vmg", "variable_multigrid")
 # ... and those that select one such cycle per component of a vector-valued P1 space on a box lattice: opt-in, its own names
 COMPONENT_MULTIGRID_NAMES = ("cmg", "component_multigrid")
+# ... and those that select the p-multigrid cycle of a P2 space on a 3-D box lattice (pgd_pmg.hip): opt-in, its own names
+P_MULTIGRID_NAMES = ("pmg", "p_multigrid")
 # values of settings["block_product"]: the product of a vector-valued P1 operator on a box lattice from CSR or from its row-diagonal form
 BLOCK_PRODUCT_NAMES = ("csr", "diagonal")
 

@@ -545,6 +545,23 @@ int pgd_eval_norm_last_shape(pgd_handle ctx, int *rows, int *staged);
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_SPMV_P2_LATTICE = 59, /* 1: an OPERATOR (pgd_op_combine) on a P2 layout that pgd_mesh_p2_bind has bound to the 3-D box lattice of its
+                                vertices - scalar, or pgd_mesh_blocked of one with 2 or 3 components; at least 3 vertices per axis, the
+                                edge list ascending - multiplies over its whole row range from a row-class form in k_spmv_p2lat: every
+                                node is (anchor vertex, class 0..7), the columns of a row are a fixed table per class (65 / 27 / 19 slots,
+                                built from the six tetrahedra of the unit cube), and the values are one double per (row, slot, column
+                                component) in arrays indexed by row - 65 ncomp over the vertex rows, 27 ncomp over the edge rows.  No
+                                column stream, every value load coalesced; the form is extracted from the CSR values once per operator
+                                and set of values and costs about 1.12 times the CSR value array on top.  Same fma chain per row, same rows
+                                per workgroup: y, the partial sums and every pgd_pcg_solve on top (Jacobi or PGD_TUNE_PCG_PRECOND = 4) are
+                                those of 0, bit for bit (a zero may change its sign).  A degree-2 operator that gets no form - never
+                                bound, refused, 2-D, 2 vertices along an axis, an entry off the table, no memory - keeps k_spmv_csr and
+                                is counted (pgd_p2lat_counts); partial row ranges, atoms, pgd_bicgstab_solve and degree-1 layouts are not
+                                asked.  With PGD_TUNE_SPMV_BLOCK_DIA on as well an operator that takes this form is not offered to that
+                                one.  0 (default): k_spmv_csr.  Measured
+                                (profiles/p2_lattice_bench_n1.jsonl): elastic_block of degree 2 31569 -> 2199 us per product at 65^3 vertices,
+                                4220 -> 300 us at 33^3, the scalar stiffness 3619 -> 430 and 478 -> 66 us; the "pmg" solve 2653 -> 293 ms and
+                                379 -> 60 ms; extraction 21.5 and 2.9 ms per operator */
     PGD_TUNE_SPMV_BLOCK_DIA = 58, /* 1: an OPERATOR (pgd_op_combine) on a blocked layout of 2 or 3 components over a scalar 3-D P1 box lattice
                                 (pgd_mesh_blocked of a layout in diagonal form, at least 2 nodes per axis) multiplies over its whole row
                                 range from a row-diagonal form - 15 ncomp arrays of one double per row, array (t, d) holding at row
@@ -818,6 +835,11 @@ int pgd_pmg_coarse(pgd_handle ctx, int comp, double *slots_out, uint8_t *el_out)
  * the knob on and kept the CSR kernel (each counted once per set of values); device time of the extractions in ms.           */
 int pgd_bdia_counts(pgd_handle ctx, int64_t *forms_built, int64_t *products, int64_t *fallbacks);
 int pgd_bdia_times(pgd_handle ctx, double *extract_ms);
+/* PGD_TUNE_SPMV_P2_LATTICE since the context was created: row-class forms extracted, product launches that read one, operators on
+ * a degree-2 layout that were asked for a whole-range product with the knob on and kept the CSR kernel (each counted once per set
+ * of values); device time of the extractions in ms.  The counters of PGD_TUNE_SPMV_BLOCK_DIA and of the preconditioners stay untouched. */
+int pgd_p2lat_counts(pgd_handle ctx, int64_t *forms_built, int64_t *products, int64_t *fallbacks);
+int pgd_p2lat_times(pgd_handle ctx, double *extract_ms);
 /* The V-cycle of the multigrid preconditioner on a z-slab of a ROW-SHARDED lattice: settings["preconditioner"] = "amg"
  * (forwarded by the reference into its solver, solver.py:593-594, 634-635) on a sharded spatial dimension.  Level 0 stays
  * with the rows (this rank's planes + one ghost plane per side), levels >= 1 are whole on every rank.  The caller owns the

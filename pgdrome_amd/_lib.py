@@ -153,6 +153,8 @@ SIGNATURES = {
     "pgd_pmg_coarse": (C.c_int, [H, C.c_int, PD, PU8]),
     "pgd_bdia_counts": (C.c_int, [H, PI64, PI64, PI64]),
     "pgd_bdia_times": (C.c_int, [H, C.POINTER(C.c_double)]),
+    "pgd_p2lat_counts": (C.c_int, [H, PI64, PI64, PI64]),
+    "pgd_p2lat_times": (C.c_int, [H, C.POINTER(C.c_double)]),
     "pgd_calib_stream": (C.c_int, [H, H, C.c_int, C.c_int]),
     "pgd_timer_start": (C.c_int, [H]),
     "pgd_timer_stop": (C.c_int, [H, PD]),
@@ -164,6 +166,7 @@ TUNE_EVAL_VARIANT, TUNE_EVAL_GRID_MAX, TUNE_EVAL_SAMPLE_CHUNK = 50, 51, 52
 TUNE_BLOCK_STORAGE = 54
 TUNE_PCG_FOLD_MARCH, TUNE_PCG_SCALAR_S, TUNE_PCG_FUSED_MARCH = 55, 56, 57
 TUNE_SPMV_BLOCK_DIA = 58
+TUNE_SPMV_P2_LATTICE = 59
 BLOCK_F32, BLOCK_F64, BLOCK_MAXK = 0, 1, 64                                           # PGD_BLOCK_* (include/pgd_amd.h)
 
 
@@ -965,6 +968,19 @@ class Context:
         f, p, b, ms = I64(), I64(), I64(), C.c_double()
         self._ck(self.lib.pgd_bdia_counts(self.h, C.byref(f), C.byref(p), C.byref(b)))
         self._ck(self.lib.pgd_bdia_times(self.h, C.byref(ms)))
+        return {"forms_built": f.value, "products": p.value, "fallbacks": b.value, "extract_ms": ms.value}
+
+    def p2_product(self, on):
+        """Select the row-class product for operators on P2 layouts bound to 3-D box lattices (PGD_TUNE_SPMV_P2_LATTICE) for the next
+        products and solves, or (on false) the CSR product again; returns the number of products launched from that form so far.
+        The results do not depend on it, bit for bit."""
+        self.tune(TUNE_SPMV_P2_LATTICE, 1 if on else 0)
+        return self.p2lat_stats()["products"]
+
+    def p2lat_stats(self):
+        f, p, b, ms = I64(), I64(), I64(), C.c_double()
+        self._ck(self.lib.pgd_p2lat_counts(self.h, C.byref(f), C.byref(p), C.byref(b)))
+        self._ck(self.lib.pgd_p2lat_times(self.h, C.byref(ms)))
         return {"forms_built": f.value, "products": p.value, "fallbacks": b.value, "extract_ms": ms.value}
 
     def calib_stream(self, v, bytes_per_lane, store=False):

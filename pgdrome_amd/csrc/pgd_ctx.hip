@@ -230,6 +230,7 @@ int pgd_ctx_destroy(pgd_handle h) {
     for (hipEvent_t e : c->timer_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->flag_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->bdia_ev) if (e) (void)hipEventDestroy(e);
+    p2lat_release(c);
     if (c->flags_host) (void)hipHostFree(c->flags_host);
     if (c->cls_scratch) (void)hipFree(c->cls_scratch);
     if (c->gram_w) (void)hipFree(c->gram_w);

@@ -126,6 +126,10 @@ struct Mesh : Obj {
     int64_t p2_nvert = 0;
     int *p2_par = nullptr;       // 2 arrays of nv ints: the two end vertices of a node's edge (equal for a vertex node)
     int *p2_v2e = nullptr;       // 14 arrays of p2_nvert ints: array t - 1 holds the node of the edge from a vertex along pattern vector t, -1: none
+    // ... and whether the row-class form of pgd_p2lat.hip may be built on it: the edge list strictly ascending in (va, vb) with va < vb
+    // (node ids ascend with the anchor vertex first, the class second), at least 3 vertices per axis.  0: no; otherwise the largest
+    // component count (1..3) with ncomp * nv < 2^31
+    int p2_lat = 0;
     ~Mesh() override {
         for (void *p : {(void *)coords, (void *)cells, (void *)cellsN, (void *)v2c_ptr, (void *)v2c,
                         (void *)row_ptr, (void *)cols, (void *)pids, (void *)dict_off, (void *)sym_tab, (void *)p2_par, (void *)p2_v2e})
@@ -184,7 +188,17 @@ struct Csr : Obj {
     int64_t bdia_stride = 0;
     uint64_t bdia_seen = 0;
     bool bdia_ok = false;
+    // row-class form of an operator on a P2 layout bound to a 3-D box lattice (pgd_p2lat.hip, PGD_TUNE_SPMV_P2_LATTICE): 65 ncomp arrays
+    // of p2lat_sv doubles over the vertex rows, then 27 ncomp arrays of p2lat_se doubles over the edge rows; array s * ncomp + d holds
+    // at its row the entry in slot s of the row's class table and column component d, an exact 0.0 where the row stores none.
+    // Tied to `version` like bdia: p2lat_seen / p2lat_ok
+    double *p2lat = nullptr;
+    size_t p2lat_bytes = 0;
+    int64_t p2lat_sv = 0, p2lat_se = 0;
+    uint64_t p2lat_seen = 0;
+    bool p2lat_ok = false;
     ~Csr() override {
+        if (p2lat) dev_release(ctx, p2lat, p2lat_bytes);
         if (bdia) dev_release(ctx, bdia, bdia_bytes);
         if (rec_bc) dev_release(ctx, rec_bc, rec_bc_bytes);
         if (cls_table) dev_release(ctx, cls_table, cls_bytes);
@@ -374,6 +388,12 @@ struct Ctx {
     int64_t bdia_forms = 0, bdia_products = 0, bdia_fallbacks = 0;   // forms extracted, products launched from one, operators that kept the CSR product
     double bdia_extract_ms = 0.0; // time the extractions took on the device, summed
     hipEvent_t bdia_ev[2] = {nullptr, nullptr};
+    int spmv_p2_lattice = 0;      // 1: whole-range products of an operator on a P2 layout bound to a 3-D box lattice from its row-class form (k_spmv_p2lat, PGD_TUNE_SPMV_P2_LATTICE; bit-identical to k_spmv_csr)
+    int64_t p2lat_forms = 0, p2lat_products = 0, p2lat_fallbacks = 0;   // forms extracted, products launched from one, degree-2 operators that kept the CSR product
+    double p2lat_extract_ms = 0.0;
+    hipEvent_t p2lat_ev[2] = {nullptr, nullptr};
+    uint16_t *p2lat_tab = nullptr; // class slot tables on the device (pgd_p2lat.hip), built once per context: (offset, class) of a slot ...
+    int16_t *p2lat_slot = nullptr; // ... and the slot of (class, offset, class)
     int block_storage = 1;        // storage of the spectral start space (PGD_TUNE_BLOCK_STORAGE): 0 = f64 vectors, 1 = fp32 block, 2 = f64 block
 
     // SpMV launch timing (HIP events on `stream`)
@@ -521,6 +541,12 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
 // (*done = true: launched); anything else leaves *done false for the CSR product, counted once per operator as a fallback
 int launch_spmv_bdia(Ctx *c, const Mesh *m, Csr *a, const double *x, double *y, const double *w, bool dot, bool store,
                      const int *flags, int *nparts_out, bool *done);
+// pgd_p2lat.hip: the same for an operator on a degree-2 layout and its row-class form (PGD_TUNE_SPMV_P2_LATTICE); p2lat_degree2: the
+// layout is a P2 layout on simplices, scalar or blocked (the ones whose operators are counted)
+bool p2lat_degree2(Ctx *c, const Mesh *m);
+int launch_spmv_p2lat(Ctx *c, const Mesh *m, Csr *a, const double *x, double *y, const double *w, bool dot, bool store,
+                      const int *flags, int *nparts_out, bool *done);
+void p2lat_release(Ctx *c);
 // pgd_spmv.hip: the launch-timing bracket of a product (HIP events around one launch in four)
 int prof_begin(Ctx *c, bool dot, bool store, bool *timed);
 int prof_end(Ctx *c, const Mesh *m, int64_t nrows, double own_per_row);

@@ -296,6 +296,7 @@ int pgd_mesh_p2_bind(pgd_handle h, pgd_handle p2h, pgd_handle p1h, const int32_t
     if (p2->p2_par) { (void)hipFree(p2->p2_par); p2->p2_par = nullptr; }
     if (p2->p2_v2e) { (void)hipFree(p2->p2_v2e); p2->p2_v2e = nullptr; }
     p2->p2_bound = -1;
+    p2->p2_lat = 0;
     if (p2->ncomp != 1 || p2->gdim != 3 || !p2->cellsN || p2->nvpc != 10) return PGD_OK;
     if (p1->ncomp != 1 || p1->gdim != 3 || p1->cellsN || p1->sym_nx <= 0 || p1->sym_ny <= 0) return PGD_OK;
     const int nx = p1->sym_nx, ny = p1->sym_ny;
@@ -304,8 +305,11 @@ int pgd_mesh_p2_bind(pgd_handle h, pgd_handle p2h, pgd_handle p1h, const int32_t
     const int nz = (int)(nvert / plane);
     std::vector<int> par((size_t)(2 * nnode)), v2e((size_t)(14 * nvert), -1);
     for (int64_t i = 0; i < nvert; ++i) par[(size_t)i] = par[(size_t)(nnode + i)] = (int)i;
+    // (for the row-class form of pgd_p2lat.hip: is the edge list strictly ascending in (va, vb) with va < vb?)
+    bool ascending = true;
     for (int64_t e = 0; e < n_edges; ++e) {
         const int64_t va = edge_vertices[2 * e], vb = edge_vertices[2 * e + 1];
+        ascending = ascending && va < vb && (e == 0 || edge_vertices[2 * e - 2] < va || (edge_vertices[2 * e - 2] == va && edge_vertices[2 * e - 1] < vb));
         if (va < 0 || vb < 0 || va >= nvert || vb >= nvert || va == vb) return PGD_OK;
         const int az = (int)(va / plane), ay = (int)((va - az * plane) / nx), ax = (int)(va - az * plane - (int64_t)ay * nx);
         const int bz = (int)(vb / plane), by = (int)((vb - bz * plane) / nx), bx = (int)(vb - bz * plane - (int64_t)by * nx);
@@ -333,6 +337,8 @@ int pgd_mesh_p2_bind(pgd_handle h, pgd_handle p2h, pgd_handle p1h, const int32_t
     }
     p2->p2_nx = nx; p2->p2_ny = ny; p2->p2_nz = nz; p2->p2_nvert = nvert;
     p2->p2_bound = 1;
+    if (ascending && nx >= 3 && ny >= 3 && nz >= 3)
+        p2->p2_lat = 3 * nnode < ((int64_t)1 << 31) ? 3 : 2 * nnode < ((int64_t)1 << 31) ? 2 : 1;
     *bound = 1;
     return PGD_OK;
 }

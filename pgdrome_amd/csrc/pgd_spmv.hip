@@ -2833,6 +2833,13 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
     if (!(c->spmv_sym && m->sym_w && a->uvals_valid && a->uvals)) {
         PGD_TRY(not_virtual());
         PGD_TRY(ensure_vals(c, m, const_cast<Csr *>(a)));
+        // P2 layouts bound to a box lattice: the same product, bit for bit, from the operator's row-class form (pgd_p2lat.hip); an
+        // operator that takes it is not offered to the row-diagonal form below
+        if (c->spmv_p2_lattice && !a->immutable && r0 == 0 && (r1 < 0 || r1 == m->nv) && p2lat_degree2(c, m)) {
+            bool done = false;
+            PGD_TRY(launch_spmv_p2lat(c, m, const_cast<Csr *>(a), x, y, w, dot, store, flags, nparts_out, &done));
+            if (done) return PGD_OK;
+        }
         // blocked P1 layouts over a box lattice: the same product, bit for bit, from the operator's row-diagonal form (pgd_bdia.hip)
         if (c->spmv_block_dia && m->ncomp > 1 && !a->immutable && r0 == 0 && (r1 < 0 || r1 == m->nv)) {
             bool done = false;
@@ -2848,6 +2855,13 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
         o->bdia_seen = a->version;
         o->bdia_ok = false;
         c->bdia_fallbacks += 1;
+    }
+    if (c->spmv_p2_lattice && !a->immutable && r0 == 0 && (r1 < 0 || r1 == m->nv) && a->p2lat_seen != a->version && p2lat_degree2(c, m)) {
+        // (likewise a degree-2 operator held in symmetric half storage - short rows, no 3-D P2 layout has them - keeps that product)
+        Csr *o = const_cast<Csr *>(a);
+        o->p2lat_seen = a->version;
+        o->p2lat_ok = false;
+        c->p2lat_fallbacks += 1;
     }
     if (r1 < 0) r1 = m->nv;
     if (r0 < 0 || r0 > r1 || r1 > m->nv) return fail(c, PGD_ERR_INVALID, "spmv: bad row range");
@@ -3367,6 +3381,7 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_PCG_FUSED_MARCH && value >= 0 && value <= 1) { c->pcg_fused_march = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_BLOCK_STORAGE && value >= 0 && value <= 2) { c->block_storage = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_SPMV_BLOCK_DIA && value >= 0 && value <= 1) { c->spmv_block_dia = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_SPMV_P2_LATTICE && value >= 0 && value <= 1) { c->spmv_p2_lattice = (int)value; return PGD_OK; }
     return fail(c, PGD_ERR_INVALID, "tune: unknown knob %d or value out of range", knob);
 }
 
@@ -3389,6 +3404,8 @@ int pgd_spmv(pgd_handle h, pgd_handle ah, pgd_handle xh, pgd_handle yh, int64_t 
     }
     // (an operator on a blocked layout with PGD_TUNE_SPMV_BLOCK_DIA on: launch_spmv_op decides between the two forms of the product)
     if (c->spmv_block_dia && m->ncomp > 1 && !a->immutable) return launch_spmv_op(c, m, a, x->d, y->d, nullptr, r0, r1, false, true, nullptr, nullptr);
+    // (likewise an operator on a degree-2 layout with PGD_TUNE_SPMV_P2_LATTICE on)
+    if (c->spmv_p2_lattice && !a->immutable && p2lat_degree2(c, m)) return launch_spmv_op(c, m, a, x->d, y->d, nullptr, r0, r1, false, true, nullptr, nullptr);
     PGD_TRY(ensure_vals(c, m, a));
     return launch_spmv(c, m, a->vals, x->d, y->d, nullptr, r0, r1, false, true, nullptr, nullptr);
 }

@@ -3735,6 +3735,19 @@ def _solve_linear(A, b, x, prm):
             prod_name = "csr" if isinstance(prod, _Params) else str(prod).lower()
             if prod_name not in BLOCK_PRODUCT_NAMES:      # (before any knob is switched)
                 raise ValueError("settings['block_product']: expected one of %s, got %r" % (BLOCK_PRODUCT_NAMES, prod))
+            # settings["p2_product"] = "lattice" (opt-in, default "csr"): the products of a P2 space (scalar or vector-valued) on a 3-D
+            # box lattice from the operator's row-class form (csrc/pgd_p2lat.hip) - the same numbers, bit for bit.  The request binds
+            # a degree-2 layout on a 3-D mesh to its vertex lattice like a "pmg" request does; the library says in its counters
+            # whether the operator had a form.  A backend without it, a row-sharded layout and a degree-1 space ignore
+            # the key.  (on a degree-2 space the counter is read either way: PGD_TUNE=59=1 switches whole runs without the key)
+            p2prod = prm.get("p2_product", "csr")
+            p2prod_name = "csr" if isinstance(p2prod, _Params) else str(p2prod).lower()
+            if p2prod_name not in P2_PRODUCT_NAMES:       # (before any knob is switched)
+                raise ValueError("settings['p2_product']: expected one of %s, got %r" % (P2_PRODUCT_NAMES, p2prod))
+            has_pl = part is None and getattr(A.lay, "degree", 1) == 2 and hasattr(be, "p2_product") and hasattr(be, "p2lat_stats")
+            want_pl = has_pl and p2prod_name == "lattice"
+            if want_pl:
+                A.lay.bind_p2_lattice(be)
             mg0 = vmg0 = cmg0 = pmg0 = None
             used = used_v = used_c = used_p = 0
             if want_mg and hasattr(be, "precondition"):
@@ -3753,6 +3766,8 @@ def _solve_linear(A, b, x, prm):
             want_bd = has_bd and prod_name == "diagonal"
             bd0 = (be.block_product(True) if want_bd else be.bdia_stats()["products"]) if has_bd else None
             used_b = 0
+            pl0 = (be.p2_product(True) if want_pl else be.p2lat_stats()["products"]) if has_pl else None
+            used_l = 0
             try:
                 if part is not None:
                     # a row-sharded lattice: the V-cycle with level 0 on the slabs and levels >= 1 replicated (dist.pcg_mg);
@@ -3777,6 +3792,8 @@ def _solve_linear(A, b, x, prm):
                     used_p = be.precondition_p(False) - pmg0
                 if bd0 is not None:
                     used_b = (be.block_product(False) if want_bd else be.bdia_stats()["products"]) - bd0
+                if pl0 is not None:
+                    used_l = (be.p2_product(False) if want_pl else be.p2lat_stats()["products"]) - pl0
             STATS["pcg_seconds"] += time.perf_counter() - t_solve      # the solve returns synchronised
             info.update(method="mg_pcg" if used > 0 else "vmg_pcg" if used_v > 0 else "cmg_pcg" if used_c > 0 else "pmg_pcg" if used_p > 0 else "jacobi_pcg",
                         iterations=it, relres=rel)
@@ -3788,9 +3805,11 @@ def _solve_linear(A, b, x, prm):
                 STATS["cmg_solves"] = STATS.get("cmg_solves", 0) + 1
             if used_p > 0:
                 STATS["pmg_solves"] = STATS.get("pmg_solves", 0) + 1
-            info["product"] = "block_dia" if used_b > 0 else "csr"
+            info["product"] = "p2_lattice" if used_l > 0 else "block_dia" if used_b > 0 else "csr"
             if used_b > 0:
                 STATS["block_dia_solves"] = STATS.get("block_dia_solves", 0) + 1
+            if used_l > 0:
+                STATS["p2_lattice_solves"] = STATS.get("p2_lattice_solves", 0) + 1
             if rel > max(rtol, 1e-14) * 1.0001 and it >= maxit:
                 # dolfin's Krylov solvers raise on non-convergence unless told otherwise (error_on_nonconvergence,
                 # default True): an unconverged mode must not be stored silently
@@ -3818,6 +3837,8 @@ COMPONENT_MULTIGRID_NAMES = ("cmg", "component_multigrid")
 P_MULTIGRID_NAMES = ("pmg", "p_multigrid")
 # values of settings["block_product"]: the product of a vector-valued P1 operator on a box lattice from CSR or from its row-diagonal form
 BLOCK_PRODUCT_NAMES = ("csr", "diagonal")
+# values of settings["p2_product"]: the product of a P2 operator on a 3-D box lattice from CSR or from its row-class form
+P2_PRODUCT_NAMES = ("csr", "lattice")
 
 
 def _apply_bcs_system(A, b, bcs):
@@ -3897,7 +3918,7 @@ class NonlinearVariationalSolver:
             h = DirichletBC.__new__(DirichletBC)
             h._V, h._vertices, h._vals = bc._V, bc._vertices, np.zeros_like(bc._vals)
             bcs_h.append(h)
-        lin = _Params({k: v for k, v in ns.items() if k in ("linear_solver", "preconditioner", "block_product")})
+        lin = _Params({k: v for k, v in ns.items() if k in ("linear_solver", "preconditioner", "block_product", "p2_product")})
         lin["relative_tolerance"] = ns.get("krylov_relative_tolerance", 1e-10) \
             if not isinstance(ns.get("krylov_relative_tolerance"), _Params) else 1e-10
         rtol, atol, maxit = float(ns["relative_tolerance"]), float(ns["absolute_tolerance"]), int(ns["maximum_iterations"])

@@ -535,11 +535,36 @@ int pgd_eval_batch_norm(pgd_handle ctx, const pgd_handle *modes, int k, int q, c
 int pgd_eval_batch_grad(pgd_handle ctx, pgd_handle mesh, const pgd_handle *modes, int k, const double *L, int q,
                         pgd_handle scale_or_0, const double *coefs, int64_t s, int want, double threshold, double *sample_stats,
                         pgd_handle env_min, pgd_handle env_max, pgd_handle exceed, pgd_handle fields);
-/* How the last pgd_eval_batch_norm or pgd_eval_batch_grad call that launched laid out its work: rows = entries per workgroup (64, 32 or 16 on the matrix
+/* How the last pgd_eval_batch_norm, pgd_eval_batch_grad or pgd_eval_batch_grad_p2 call that launched laid out its work: rows = entries per workgroup (64, 32 or 16 on the matrix
  * unit, 64 in the plain variant), staged = 1 the planes of a row block in at most 64 KiB of LDS, 2 in more (up to 160 KiB), 0 read
  * from global memory (always in the plain variant; never on the matrix unit for pgd_eval_batch_grad); rows = 0, staged = -1
  * before the first call.                                                                                                      */
 int pgd_eval_norm_last_shape(pgd_handle ctx, int *rows, int *staged);
+
+/* The same two for a P2 field.  Its gradient is affine on a cell, so the caller names npt points of the cell by their barycentric
+ * coordinates lam (host, npt x (gdim+1) row-major, 1 <= npt <= 4; rows that sum to 1) and gets the quantity at every one of them.
+ * Entries are point-major: entry a*nc + e is point a of cell e, so one point's slice is a cell-wise vector.
+ *
+ * pgd_cell_gradient_p2: out[(i*npt + a)*nc + e] = scale[e] * sum_j L[i][j] g[j], g[c*gdim + d] = d u_c / d x_d at point a of cell e:
+ * q planes of m = npt*nc entries, what pgd_eval_batch_norm takes.
+ *   mesh: a P2 layout on triangles or tetrahedra (records of 6 / 10 nodes: the vertices, then the edge nodes of the local edges
+ *   (1,2) (0,2) (0,1) resp. (2,3) (1,3) (1,2) (0,3) (0,2) (0,1)), scalar or blocked;  u: nv*ncomp entries, node*ncomp + c;
+ *   L, q, scale: as pgd_cell_gradient (scale: one entry per CELL);  out: q*npt*nc entries.
+ * With dl_i = u_i (4 lam_i - 1) + sum over the edges (i,b) of 4 u_ib lam_b the reference derivatives are dl_{a+1} - dl_0 (the node
+ * of the edge (0,a+1), which both sums hold with cancelling coefficients, enters once with 4 lam_0 - 4 lam_{a+1}); the
+ * inverse Jacobian comes from the cell's vertices alone, as in pgd_cell_gradient, and so do L g and the scale.  A thread per cell.
+ * PGD_ERR_INVALID with a message, before anything is launched, for: any other layout (P1, the 1-D P2 layout), npt or q out of
+ * range, a null lam or L, wrong vector sizes, out aliasing u or scale.  nc == 0 is PGD_OK.  No atomics, no host synchronisation. */
+int pgd_cell_gradient_p2(pgd_handle ctx, pgd_handle mesh, pgd_handle u, const double *lam, int npt, const double *L, int q,
+                         pgd_handle scale_or_0, pgd_handle out);
+/* pgd_eval_batch_grad_p2: pgd_cell_gradient_p2 and pgd_eval_batch_norm in one call, the planes never stored - pgd_eval_batch_grad
+ * with an entry (point row / nc of cell row % nc) where that has a cell.  Every output has npt*nc entries (fields: npt*nc*s,
+ * sample-major); P_t is exactly what pgd_cell_gradient_p2 would have written.  Everything pgd_eval_batch_grad states holds, the
+ * PGD_ERR_LIMIT rule included; refusals as pgd_cell_gradient_p2 and pgd_eval_batch.  Every entry of a cell forms the inverse and
+ * gathers the record's nodal values again.                                                                                  */
+int pgd_eval_batch_grad_p2(pgd_handle ctx, pgd_handle mesh, const pgd_handle *modes, int k, const double *lam, int npt,
+                           const double *L, int q, pgd_handle scale_or_0, const double *coefs, int64_t s, int want, double threshold,
+                           double *sample_stats, pgd_handle env_min, pgd_handle env_max, pgd_handle exceed, pgd_handle fields);
 
 /* ------------------------------------------------------------------ tuning --- */
 /* Launch-shape knobs; they change speed (and the order of the dot's partial

@@ -73,6 +73,8 @@ SIGNATURES = {
     "pgd_cell_gradient": (C.c_int, [H, H, H, PD, C.c_int, H, H]),
     "pgd_eval_batch_grad": (C.c_int, [H, H, PH, C.c_int, PD, C.c_int, H, PD, I64, C.c_int, F64, PD, H, H, H, H]),
     "pgd_eval_norm_last_shape": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pgd_cell_gradient_p2": (C.c_int, [H, H, H, PD, C.c_int, PD, C.c_int, H, H]),
+    "pgd_eval_batch_grad_p2": (C.c_int, [H, H, PH, C.c_int, PD, C.c_int, PD, C.c_int, H, PD, I64, C.c_int, F64, PD, H, H, H, H]),
     "pgd_atom_assemble": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PH]),
     "pgd_atom_assemble_cells": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PU8, I64, PH]),
     "pgd_atom_assemble_cellwise": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, H, PU8, I64, PH]),
@@ -485,6 +487,28 @@ class Context:
         if L.ndim != 2:
             raise ValueError("cell_gradient: L is a (q, ncomp * gdim) matrix")
         self._ck(self.lib.pgd_cell_gradient(self.h, mesh, u, dptr(L) if L.size else None, L.shape[0], int(scale or 0), out))
+
+    @staticmethod
+    def _p2_points(name, lam, L):
+        lam, L = np.ascontiguousarray(lam, dtype=np.float64), np.ascontiguousarray(L, dtype=np.float64)
+        if lam.ndim != 2 or L.ndim != 2:
+            raise ValueError("%s: lam is a (npt, gdim + 1) matrix, L a (q, ncomp * gdim) matrix" % name)
+        return lam, L
+
+    def cell_gradient_p2(self, mesh, u, lam, L, out, scale=0):
+        """pgd_cell_gradient_p2: ``cell_gradient`` for the P2 field ``u`` of the P2 layout ``mesh`` at the points ``lam`` (npt, gdim + 1:
+        barycentric coordinates) of every cell: out[(i * npt + a) * nc + cell] is plane i at point a."""
+        lam, L = self._p2_points("cell_gradient_p2", lam, L)
+        self._ck(self.lib.pgd_cell_gradient_p2(self.h, mesh, u, dptr(lam) if lam.size else None, lam.shape[0], dptr(L) if L.size else None,
+                                               L.shape[0], int(scale or 0), out))
+
+    def eval_batch_grad_p2(self, mesh, modes, lam, L, coefs, scale=0, stats=True, env_min=0, env_max=0, exceed=0, threshold=0.0, fields=0):
+        """pgd_eval_batch_grad_p2: ``eval_batch_grad`` on nodal P2 modes at the points ``lam`` of every cell; the outputs have npt *
+        cells entries, point-major."""
+        lam, L = self._p2_points("eval_batch_grad_p2", lam, L)
+        return self._eval_batch("eval_batch_grad_p2", self.lib.pgd_eval_batch_grad_p2,
+                                (dptr(lam) if lam.size else None, lam.shape[0], dptr(L) if L.size else None, L.shape[0], int(scale or 0)),
+                                modes, coefs, stats, env_min, env_max, exceed, threshold, fields, lead=(int(mesh),))
 
     def vec_set(self, v, idx, val):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

@@ -25,8 +25,9 @@
 //
 // Further down: the same two kernels on q planes per entry with a Euclidean norm before the reductions (pgd_eval_batch_norm),
 // the kernel that makes such planes from a nodal P1 mode (pgd_cell_gradient), and the two norm kernels once more with the planes
-// formed inside them from the nodal modes, never stored (pgd_eval_batch_grad).  What happens to a value once it is formed is the
-// same in all of them: see "the reduction epilogue" below.
+// formed inside them from the nodal modes, never stored (pgd_eval_batch_grad), and the last two for nodal P2 modes at given points of
+// every cell (pgd_cell_gradient_p2, pgd_eval_batch_grad_p2).  What happens to a value once it is formed is the same in all of
+// them: see "the reduction epilogue" below.
 #include "pgd_internal.h"
 
 #include <cmath>
@@ -628,21 +629,17 @@ __device__ __forceinline__ void cell_inverse(const int4 rec, const double *__res
     }
 }
 
+// (the tail of cell_planes from du on - g, L g, the scale - which the P2 kernels further down share: du[c][a] is d u_c / d xi_a)
 template <int G, int NC, class Put>
-__device__ __forceinline__ void cell_planes(const int (&v)[4], const double (&J)[G][G], const double *__restrict__ u, const GradL &L, int q,
-                                            double sc, Put put) {
+__device__ __forceinline__ void grad_planes(const double (&du)[NC][G], const double (&J)[G][G], const GradL &L, int q, double sc, Put put) {
     double g[NC * G];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        const double u0 = u[(int64_t)v[0] * NC + c];
-        double du[G];
-#pragma unroll
-        for (int a = 0; a < G; ++a) du[a] = u[(int64_t)v[a + 1] * NC + c] - u0;
 #pragma unroll
         for (int d = 0; d < G; ++d) {
-            double acc = du[0] * J[0][d];
+            double acc = du[c][0] * J[0][d];
 #pragma unroll
-            for (int a = 1; a < G; ++a) acc = fma(du[a], J[a][d], acc);
+            for (int a = 1; a < G; ++a) acc = fma(du[c][a], J[a][d], acc);
             g[c * G + d] = acc;
         }
     }
@@ -656,6 +653,19 @@ __device__ __forceinline__ void cell_planes(const int (&v)[4], const double (&J)
             put(i, sc * acc);
         }
     }
+}
+
+template <int G, int NC, class Put>
+__device__ __forceinline__ void cell_planes(const int (&v)[4], const double (&J)[G][G], const double *__restrict__ u, const GradL &L, int q,
+                                            double sc, Put put) {
+    double du[NC][G];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const double u0 = u[(int64_t)v[0] * NC + c];
+#pragma unroll
+        for (int a = 0; a < G; ++a) du[c][a] = u[(int64_t)v[a + 1] * NC + c] - u0;
+    }
+    grad_planes<G, NC>(du, J, L, q, sc, put);
 }
 
 template <int G, int NC>
@@ -676,6 +686,107 @@ static void cell_gradient_launch(Ctx *c, const Mesh *b, const double *u, const G
     k_cell_gradient<G, NC><<<grid, TPB, 0, c->stream>>>(b->cells, b->coords, b->nv, b->nc, u, L, q, scale, out);
 }
 
+// ---- pgd_cell_gradient_p2: the same planes of a nodal P2 mode, taken at npt <= 4 points of every cell given by their barycentric
+// coordinates lam (npt x (G + 1)): the gradient of a P2 field is affine on the cell, so the caller says where.  Entries are
+// point-major, out[(i npt + a) nc + e] is plane i at point a of cell e: q planes of npt nc entries, what pgd_eval_batch_norm takes.
+// The record is the frontend's: the G + 1 vertices, then the edge nodes in the order of p2_edge.  With N_i = l_i (2 l_i - 1) and
+// N_ab = 4 l_a l_b, d u / d l_i = u_i (4 l_i - 1) + sum over the edges (i, b) of 4 u_ib l_b =: dl_i, and with l_0 = 1 - sum xi
+// d u / d xi_a = dl_{a+1} - dl_0: the du of the P1 kernels, so g, L g and the scale are grad_planes.  The Jacobian comes from the
+// vertices alone (the cells are straight): cell_inverse on the first G + 1 entries of the record.
+constexpr int P2_NPT_MAX = 4;
+struct P2Points { double lam[P2_NPT_MAX * 4]; int npt; };
+
+__host__ __device__ constexpr int p2_nodes(int G) { return (G + 1) * (G + 2) / 2; }
+// local edge k of a P2 triangle ((1,2), (0,2), (0,1)) or tetrahedron ((2,3), (1,3), (1,2), (0,3), (0,2), (0,1)): its two vertices
+__host__ __device__ constexpr int p2_edge_a(int G, int k) { return G == 2 ? (k == 0 ? 1 : 0) : (k == 0 ? 2 : k < 3 ? 1 : 0); }
+__host__ __device__ constexpr int p2_edge_b(int G, int k) { return G == 2 ? (k == 2 ? 1 : 2) : (k == 2 || k == 4 ? 2 : k == 5 ? 1 : 3); }
+
+// the record of cell e, its vertices as the int4 of cell_inverse
+template <int G>
+__device__ __forceinline__ int4 p2_record(const int *__restrict__ cellsN, int64_t e, int (&r)[p2_nodes(G)]) {
+    const int *rec = cellsN + e * p2_nodes(G);
+#pragma unroll
+    for (int j = 0; j < p2_nodes(G); ++j) r[j] = rec[j];
+    return make_int4(r[0], r[1], r[2], G == 3 ? r[3] : 0);
+}
+
+// the nodal values of the cell, un[j NC + c] = component c at record entry j
+template <int G, int NC>
+__device__ __forceinline__ void p2_gather(const int (&r)[p2_nodes(G)], const double *__restrict__ u, double (&un)[p2_nodes(G) * NC]) {
+#pragma unroll
+    for (int j = 0; j < p2_nodes(G); ++j)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) un[j * NC + c] = u[(int64_t)r[j] * NC + c];
+}
+
+// w_i = 4 l_i - 1 and l4_i = 4 l_i of point a (a select over the <= 4 points: the table stays in the kernel arguments)
+template <int G>
+__device__ __forceinline__ void p2_weights(const P2Points &P, int a, double (&w)[G + 1], double (&l4)[G + 1]) {
+#pragma unroll
+    for (int i = 0; i <= G; ++i) {
+        double l = P.lam[i];
+#pragma unroll
+        for (int b = 1; b < P2_NPT_MAX; ++b) l = (a == b) ? P.lam[b * (G + 1) + i] : l;
+        l4[i] = 4.0 * l;
+        w[i] = l4[i] - 1.0;
+    }
+}
+
+// the planes at one point.  du_a = dl_{a+1} - dl_0 with the one node both share, the edge (0, a + 1), taken out of the two sums and
+// added as u_e (4 l_0 - 4 l_{a+1}): its two terms cancel (entirely at the barycentre), and summed apart they would leave rounding
+// errors of the size of the terms, not of their difference.  So every du is off by a few units relative to
+// sum_j |d N_j / d xi_a| |u_j|.  Order: the vertex's own term, then its edges in record order; vertex a + 1 minus vertex 0; the
+// shared edge last.
+template <int G, int NC, class Put>
+__device__ __forceinline__ void p2_planes(const double (&un)[p2_nodes(G) * NC], const double (&w)[G + 1], const double (&l4)[G + 1],
+                                          const double (&J)[G][G], const GradL &L, int q, double sc, Put put) {
+    double du[NC][G];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+#pragma unroll
+        for (int a = 0; a < G; ++a) {
+            double hi = un[(a + 1) * NC + c] * w[a + 1], lo = un[c] * w[0], shared = 0.0;
+#pragma unroll
+            for (int k = 0; k < p2_nodes(G) - (G + 1); ++k) {
+                const int ea = p2_edge_a(G, k), eb = p2_edge_b(G, k);      // ea < eb
+                const double ue = un[(G + 1 + k) * NC + c];
+                if (ea == 0 && eb == a + 1) shared = ue;
+                else if (ea == 0) lo = fma(ue, l4[eb], lo);
+                else if (ea == a + 1) hi = fma(ue, l4[eb], hi);
+                else if (eb == a + 1) hi = fma(ue, l4[ea], hi);
+            }
+            du[c][a] = fma(shared, l4[0] - l4[a + 1], hi - lo);
+        }
+    }
+    grad_planes<G, NC>(du, J, L, q, sc, put);
+}
+
+// A thread per cell: record, inverse and nodal values once, in registers; then the points.  The stores of a plane are coalesced.
+template <int G, int NC>
+__global__ __launch_bounds__(TPB) void k_cell_gradient_p2(const int *__restrict__ cellsN, const double *__restrict__ coords, int64_t nv,
+                                                          int64_t nc, const double *__restrict__ u, P2Points P, GradL L, int q,
+                                                          const double *__restrict__ scale, double *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (e >= nc) return;
+    int r[p2_nodes(G)], v[4];
+    double J[G][G], un[p2_nodes(G) * NC];
+    cell_inverse<G>(p2_record<G>(cellsN, e, r), coords, nv, v, J);
+    p2_gather<G, NC>(r, u, un);
+    const double sc = scale ? scale[e] : 1.0;
+    for (int a = 0; a < P.npt; ++a) {
+        double w[G + 1], l4[G + 1];
+        p2_weights<G>(P, a, w, l4);
+        p2_planes<G, NC>(un, w, l4, J, L, q, sc, [&](int i, double p) { out[((int64_t)i * P.npt + a) * nc + e] = p; });
+    }
+}
+
+template <int G, int NC>
+static void cell_gradient_p2_launch(Ctx *c, const Mesh *b, const double *u, const P2Points &P, const GradL &L, int q, const double *scale,
+                                    double *out) {
+    const int grid = (int)((b->nc + TPB - 1) / TPB);
+    k_cell_gradient_p2<G, NC><<<grid, TPB, 0, c->stream>>>(b->cellsN, b->coords, b->nv, b->nc, u, P, L, q, scale, out);
+}
+
 // ---- pgd_eval_batch_grad: pgd_eval_batch_norm on planes that are never stored.  The planes of a cell are a local, linear function
 // of the nodal mode (cell_inverse once, cell_planes per mode), so the kernels form them where the stored path reads them: the
 // matrix-unit kernel in the staging step of a row block of cells (then it IS k_eval_norm_mfma: eval_norm_tiles), the plain kernel in
@@ -688,8 +799,15 @@ struct EvalGradSrc {
     int64_t nv;
     GradL L;
 };
-// (the kernel arguments are passed by value: modes, L and the scalars must stay below the 4 KiB the runtime takes)
-static_assert(sizeof(EvalModes) + sizeof(EvalGradSrc) + sizeof(EvalOut) + 128 <= 4096, "kernel arguments of the fused kernels");
+// ... and what the P2 kernels take: the flat records, the cell count (the rows are entries: point row / nc of cell row % nc) and
+// the points
+struct EvalGradP2Src : EvalGradSrc {
+    const int *cellsN = nullptr;
+    int64_t nc = 0;
+    P2Points pts = {};
+};
+// (the kernel arguments are passed by value: modes, L, the points and the scalars must stay below the 4 KiB the runtime takes)
+static_assert(sizeof(EvalModes) + sizeof(EvalGradP2Src) + sizeof(EvalOut) + 128 <= 4096, "kernel arguments of the fused kernels");
 
 template <int T, int G, int NC>
 __global__ __launch_bounds__(TPB) void k_eval_grad_mfma(EvalModes M, int k, int kt, int q, EvalGradSrc S, int64_t n, const double *__restrict__ cf,
@@ -805,9 +923,9 @@ struct EvalGradFns {
 
 // What pgd_eval_batch_grad hands to eval_batch_run beside the arguments of pgd_eval_batch_norm
 struct EvalGrad {
-    EvalGradSrc src;
+    EvalGradP2Src src;          // (the P1 launchers pass its EvalGradSrc part)
     EvalGradFns fn;
-    int64_t mode_len, nc;       // nodes x components; cells
+    int64_t mode_len, entries;  // nodes x components; rows of the outputs: cells, times the points for P2
     const Vec *scale;
 };
 
@@ -860,6 +978,198 @@ static bool eval_grad_pick(int G, int NC, EvalGradFns *f) {
     }
 }
 
+// ---- pgd_eval_batch_grad_p2: the two fused kernels with the staging step of a P2 entry.  Row = entry: point row / nc of cell
+// row % nc, as pgd_cell_gradient_p2 orders them, so a row block is 16 T consecutive cells at one point (or the seam of two points).
+// Every entry of a cell forms the inverse and gathers the record's nodal values again - from L2, the npt entries of a cell sit nc
+// rows apart - and from the barrier on the kernels are eval_norm_tiles / eval_plain_step.  Rows beyond the range read no record.
+template <int T, int G, int NC>
+__global__ __launch_bounds__(TPB) void k_eval_grad_p2_mfma(EvalModes M, int k, int kt, int q, EvalGradP2Src S, int64_t n,
+                                                           const double *__restrict__ cf, int cs, int64_t j0, int want, int first, double thr,
+                                                           EvalOut O) {
+    extern __shared__ double s_dyn[];
+    constexpr int RB = EvalNormShape<T>::RB, RS = EvalNormShape<T>::RS, TPC = TPB / RB;      // TPC threads share an entry's modes
+    const double INF = __builtin_huge_val();
+    const int kp = 4 * kt;
+    const int cs16 = (cs + 15) & ~15;
+    double *s_f = s_dyn;                                   // q x kp rows of RS: plane i, mode t at row i kp + t
+    double *s_mn = s_f + (size_t)q * kp * RS;
+    double *s_mx = s_mn + cs16;
+    double *s_env = s_mx + cs16;
+    const int d = threadIdx.x % RB, part = threadIdx.x / RB;
+    for (int j = threadIdx.x; j < cs16; j += TPB) { s_mn[j] = INF; s_mx[j] = -INF; }
+    const int64_t nblk = (n + RB - 1) / RB;
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t row0 = blk * RB, row = row0 + d;
+        const bool cv = row < n;
+        __syncthreads();
+        int r[p2_nodes(G)], v[4];
+        double J[G][G], w[G + 1], l4[G + 1];
+        double sc = 1.0;
+        if (cv) {
+            const int64_t e = row % S.nc;
+            cell_inverse<G>(p2_record<G>(S.cellsN, e, r), S.coords, S.nv, v, J);
+            p2_weights<G>(S.pts, (int)(row / S.nc), w, l4);
+            if (S.scale) sc = S.scale[e];
+        }
+        for (int t = part; t < kp; t += TPC) {
+            double *col = s_f + (size_t)t * RS + d;
+            if (cv && t < k) {
+                double un[p2_nodes(G) * NC];
+                p2_gather<G, NC>(r, M.p[t], un);
+                p2_planes<G, NC>(un, w, l4, J, S.L, q, sc, [&](int i, double p) { col[(size_t)i * kp * RS] = p; });
+            } else {
+                for (int i = 0; i < q; ++i) col[(size_t)i * kp * RS] = 0.0;
+            }
+        }
+        __syncthreads();
+        eval_norm_tiles<T, true>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O, s_f, s_mn, s_mx, s_env, row0);
+    }
+    eval_store_partials<TPB>(O, s_mn, s_mx, cs16, want);
+}
+
+template <int G, int NC>
+__global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_grad_p2_plain(EvalModes M, int k, int kt, int q, EvalGradP2Src S, int64_t n,
+                                                                       const double *__restrict__ cf, int cs, int64_t j0, int want,
+                                                                       int first, double thr, EvalOut O) {
+    extern __shared__ double s_dyn[];
+    constexpr int NS = EVAL_PLAIN_NS;
+    const double INF = __builtin_huge_val();
+    const int cs16 = (cs + 15) & ~15;
+    double *s_mn = s_dyn, *s_mx = s_dyn + cs16;
+    const int lane = threadIdx.x;
+    for (int j = lane; j < cs16; j += EVAL_PLAIN_TPB) { s_mn[j] = INF; s_mx[j] = -INF; }
+    __syncthreads();
+    const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
+    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int64_t row = blk * EVAL_PLAIN_TPB + lane;
+        const bool rv = row < n;
+        int r[p2_nodes(G)], v[4];
+        double J[G][G], w[G + 1], l4[G + 1];
+        double sc = 1.0;
+        if (rv) {
+            const int64_t e = row % S.nc;
+            cell_inverse<G>(p2_record<G>(S.cellsN, e, r), S.coords, S.nv, v, J);
+            p2_weights<G>(S.pts, (int)(row / S.nc), w, l4);
+            if (S.scale) sc = S.scale[e];
+        }
+        double emn = INF, emx = -INF, ect = 0.0;
+        for (int jb = 0; jb < cs16; jb += NS) {
+            double acc[EVAL_QMAX][NS];
+#pragma unroll
+            for (int i = 0; i < EVAL_QMAX; ++i)
+#pragma unroll
+                for (int c = 0; c < NS; ++c) acc[i][c] = 0.0;
+            for (int t = 0; t < k; ++t) {
+                double p[EVAL_QMAX];
+#pragma unroll
+                for (int i = 0; i < EVAL_QMAX; ++i) p[i] = 0.0;
+                if (rv) {
+                    double un[p2_nodes(G) * NC];
+                    p2_gather<G, NC>(r, M.p[t], un);
+                    p2_planes<G, NC>(un, w, l4, J, S.L, q, sc, [&](int i, double x) { p[i] = x; });
+                }
+                const double *cp = cf + eval_cf_index(kt, t, jb);
+#pragma unroll
+                for (int i = 0; i < EVAL_QMAX; ++i)
+                    if (i < q) {
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) acc[i][c] = fma(cp[c], p[i], acc[i][c]);
+                    }
+            }
+            double ss[NS];
+#pragma unroll
+            for (int c = 0; c < NS; ++c) ss[c] = 0.0;
+#pragma unroll
+            for (int i = 0; i < EVAL_QMAX; ++i)
+                if (i < q) {
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) ss[c] = fma(acc[i][c], acc[i][c], ss[c]);
+                }
+#pragma unroll
+            for (int c = 0; c < NS; ++c) ss[c] = sqrt(ss[c]);            // from here on the values
+            eval_plain_step(ss, jb, cs, j0, n, row, rv, want, thr, O, s_mn, s_mx, emn, emx, ect);
+        }
+        if (rv) eval_row_accumulate(O, row, emn, emx, ect, want, first);
+    }
+    eval_store_partials<EVAL_PLAIN_TPB>(O, s_mn, s_mx, cs16, want);
+}
+
+// (the launchers take the EvalGradSrc of eval_grad_launch_t: pgd_eval_batch_grad_p2 hands them the EvalGradP2Src it filled)
+template <int T, int G, int NC>
+static int eval_launch_grad_p2(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf, int cs,
+                               int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
+    const size_t lds = eval_norm_lds(T, true, q, kt, (cs + 15) & ~15);
+    return eval_launch_persistent(c, k_eval_grad_p2_mfma<T, G, NC>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q,
+                                  static_cast<const EvalGradP2Src &>(S), n, cf, cs, j0, want, first, thr, O);
+}
+
+template <int G, int NC>
+static int eval_launch_grad_p2_plain(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf,
+                                     int cs, int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
+    const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
+    const int g = (int)(nblk < grid_cap ? nblk : grid_cap);
+    const size_t lds = (size_t)2 * ((cs + 15) & ~15) * sizeof(double);
+    k_eval_grad_p2_plain<G, NC><<<g, EVAL_PLAIN_TPB, lds, c->stream>>>(M, k, kt, q, static_cast<const EvalGradP2Src &>(S), n, cf, cs, j0,
+                                                                      want, first, thr, O);
+    PGD_LAUNCH_CHECK(c);
+    *grid_out = g;
+    return PGD_OK;
+}
+
+template <int G, int NC>
+static bool eval_grad_p2_raise_lds(size_t lds) { return eval_raise_lds((const void *)k_eval_grad_p2_mfma<1, G, NC>, lds); }
+
+template <int G, int NC>
+static EvalGradFns eval_grad_p2_fns() {
+    EvalGradFns f;
+    f.mfma[0] = eval_launch_grad_p2<1, G, NC>;
+    f.mfma[1] = eval_launch_grad_p2<2, G, NC>;
+    f.mfma[2] = eval_launch_grad_p2<4, G, NC>;
+    f.plain = eval_launch_grad_p2_plain<G, NC>;
+    f.raise = eval_grad_p2_raise_lds<G, NC>;
+    return f;
+}
+
+static bool eval_grad_p2_pick(int G, int NC, EvalGradFns *f) {
+    switch (G * 10 + NC) {
+        case 21: *f = eval_grad_p2_fns<2, 1>(); return true;
+        case 22: *f = eval_grad_p2_fns<2, 2>(); return true;
+        case 23: *f = eval_grad_p2_fns<2, 3>(); return true;
+        case 31: *f = eval_grad_p2_fns<3, 1>(); return true;
+        case 32: *f = eval_grad_p2_fns<3, 2>(); return true;
+        case 33: *f = eval_grad_p2_fns<3, 3>(); return true;
+        default: return false;
+    }
+}
+
+// The checks pgd_cell_gradient_p2 and pgd_eval_batch_grad_p2 share (fn: the entry point's name): the layout - P2 triangles or
+// tetrahedra, whose 6 / 10-node records are the flat ones; the 1-D P2 layout keeps its 3-node record in `cells` and is served by
+// the host -, the points, L and the scale.  On success *bp is the scalar layout, P and Lv are filled.
+static int grad_p2_check(Ctx *c, const char *fn, pgd_handle mh, const double *lam, int npt, const double *L, int q, pgd_handle scale_h,
+                         Mesh **mp, Mesh **bp, Vec **scalep, P2Points *P, GradL *Lv) {
+    Mesh *m = get_mesh(c, mh);
+    if (!m) return fail(c, PGD_ERR_INVALID, "%s: invalid mesh handle", fn);
+    Mesh *b = m->ncomp > 1 ? get_mesh(c, m->base) : m;          // the scalar layout holds the cells and the coordinates
+    if (!b) return fail(c, PGD_ERR_INVALID, "%s: the blocked layout's base is gone", fn);
+    const int G = b->gdim, NC = m->ncomp;
+    if ((G != 2 && G != 3) || !b->cellsN || b->nvpc != p2_nodes(G) || !b->coords)
+        return fail(c, PGD_ERR_INVALID, "%s: a layout of %d nodes per cell in %d-D: P2 triangles (6) or tetrahedra (10) only", fn, b->nvpc, G);
+    if (NC < 1 || NC > 3) return fail(c, PGD_ERR_INVALID, "%s: gdim = %d with %d components", fn, G, NC);
+    if (npt < 1 || npt > P2_NPT_MAX) return fail(c, PGD_ERR_INVALID, "%s: npt = %d points per cell, 1 .. %d are possible", fn, npt, P2_NPT_MAX);
+    if (!lam) return fail(c, PGD_ERR_INVALID, "%s: lam is missing", fn);
+    if (q < 1 || q > EVAL_QMAX) return fail(c, PGD_ERR_INVALID, "%s: q = %d rows of L, 1 .. %d are possible", fn, q, EVAL_QMAX);
+    if (!L) return fail(c, PGD_ERR_INVALID, "%s: L is missing", fn);
+    Vec *scale = scale_h ? get_vec(c, scale_h) : nullptr;
+    if (scale_h && (!scale || scale->n != b->nc))
+        return fail(c, PGD_ERR_INVALID, "%s: scale is a vector of one entry per cell (%lld), or 0", fn, (long long)b->nc);
+    for (int i = 0; i < P2_NPT_MAX * 4; ++i) P->lam[i] = i < npt * (G + 1) ? lam[i] : 0.0;
+    P->npt = npt;
+    const int qin = NC * G;
+    for (int i = 0; i < EVAL_QMAX * EVAL_QMAX; ++i) Lv->a[i] = i < q * qin ? L[i] : 0.0;
+    *mp = m; *bp = b; *scalep = scale;
+    return PGD_OK;
+}
+
 }  // namespace pgd
 
 using namespace pgd;
@@ -868,8 +1178,8 @@ extern "C" {
 
 // The body of pgd_eval_batch (q == 0: the signed values, k_eval_mfma / k_eval_plain) and of pgd_eval_batch_norm (1 <= q <= 9: every
 // mode is q planes, the norm kernels): the checks, the chunking and the coefficient staging are the same, only the launch differs.
-// pgd_eval_batch_grad is the second of these with `gs`: the modes are nodal, the planes are formed in the kernel, the outputs have one
-// entry per cell.  fn: the entry point's name for the messages.
+// pgd_eval_batch_grad and pgd_eval_batch_grad_p2 are the second of these with `gs`: the modes are nodal, the planes are formed in
+// the kernel, the outputs have gs->entries rows (one per cell; per point and cell for P2).  fn: the entry point's name for the messages.
 static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want,
                           double threshold, double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h,
                           pgd_handle fields_h) {
@@ -893,7 +1203,7 @@ static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_
         if (n != gs->mode_len)
             return fail(c, PGD_ERR_INVALID, "%s: the modes have %lld entries, nodes x components = %lld are needed", fn, (long long)n,
                         (long long)gs->mode_len);
-        n = gs->nc;
+        n = gs->entries;
     } else if (q > 0) {                              // q planes of n entries each
         if (n % q) return fail(c, PGD_ERR_INVALID, "%s: the modes have %lld entries, no multiple of q = %d", fn, (long long)n, q);
         n /= q;
@@ -1094,7 +1404,7 @@ int pgd_eval_batch_grad(pgd_handle h, pgd_handle mh, const pgd_handle *modes, in
     const int qin = NC * G;
     for (int i = 0; i < EVAL_QMAX * EVAL_QMAX; ++i) gs.src.L.a[i] = i < q * qin ? L[i] : 0.0;
     gs.mode_len = b->nv * NC;
-    gs.nc = b->nc;
+    gs.entries = b->nc;
     gs.scale = scale;
     return eval_batch_run(c, "eval_batch_grad", &gs, modes, k, q, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
                           fields_h);
@@ -1146,6 +1456,59 @@ int pgd_cell_gradient(pgd_handle h, pgd_handle mh, pgd_handle uh, const double *
     }
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
+}
+
+int pgd_cell_gradient_p2(pgd_handle h, pgd_handle mh, pgd_handle uh, const double *lam, int npt, const double *L, int q, pgd_handle scale_h,
+                         pgd_handle out_h) {
+    PGD_CTX(c, h);
+    Mesh *m, *b;
+    Vec *scale;
+    P2Points P;
+    GradL Lv;
+    PGD_TRY(grad_p2_check(c, "cell_gradient_p2", mh, lam, npt, L, q, scale_h, &m, &b, &scale, &P, &Lv));
+    const int G = b->gdim, NC = m->ncomp;
+    Vec *u = get_vec(c, uh), *out = get_vec(c, out_h);
+    if (!u || u->n != b->nv * NC)
+        return fail(c, PGD_ERR_INVALID, "cell_gradient_p2: u is a vector of %lld entries (nodes x components)", (long long)(b->nv * NC));
+    const int64_t need = (int64_t)q * npt * b->nc;
+    if (!out || out->n != need)
+        return fail(c, PGD_ERR_INVALID, "cell_gradient_p2: out is a vector of q * npt * cells = %lld entries", (long long)need);
+    if (out == u || out == scale) return fail(c, PGD_ERR_INVALID, "cell_gradient_p2: out aliases %s", out == u ? "u" : "scale");
+    if (b->nc == 0) return PGD_OK;
+    const double *sp = scale ? scale->d : nullptr;
+    switch (G * 10 + NC) {
+        case 21: cell_gradient_p2_launch<2, 1>(c, b, u->d, P, Lv, q, sp, out->d); break;
+        case 22: cell_gradient_p2_launch<2, 2>(c, b, u->d, P, Lv, q, sp, out->d); break;
+        case 23: cell_gradient_p2_launch<2, 3>(c, b, u->d, P, Lv, q, sp, out->d); break;
+        case 31: cell_gradient_p2_launch<3, 1>(c, b, u->d, P, Lv, q, sp, out->d); break;
+        case 32: cell_gradient_p2_launch<3, 2>(c, b, u->d, P, Lv, q, sp, out->d); break;
+        default: cell_gradient_p2_launch<3, 3>(c, b, u->d, P, Lv, q, sp, out->d); break;      // (grad_p2_check left these six)
+    }
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+int pgd_eval_batch_grad_p2(pgd_handle h, pgd_handle mh, const pgd_handle *modes, int k, const double *lam, int npt, const double *L, int q,
+                           pgd_handle scale_h, const double *coefs, int64_t s, int want, double threshold, double *sample_stats,
+                           pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
+    PGD_CTX(c, h);
+    Mesh *m, *b;
+    Vec *scale;
+    EvalGrad gs;
+    PGD_TRY(grad_p2_check(c, "eval_batch_grad_p2", mh, lam, npt, L, q, scale_h, &m, &b, &scale, &gs.src.pts, &gs.src.L));
+    if (!eval_grad_p2_pick(b->gdim, m->ncomp, &gs.fn))
+        return fail(c, PGD_ERR_INVALID, "eval_batch_grad_p2: gdim = %d with %d components", b->gdim, m->ncomp);
+    gs.src.cells = nullptr;
+    gs.src.cellsN = b->cellsN;
+    gs.src.coords = b->coords;
+    gs.src.scale = scale ? scale->d : nullptr;
+    gs.src.nv = b->nv;
+    gs.src.nc = b->nc;
+    gs.mode_len = b->nv * m->ncomp;
+    gs.entries = (int64_t)npt * b->nc;
+    gs.scale = scale;
+    return eval_batch_run(c, "eval_batch_grad_p2", &gs, modes, k, q, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
+                          fields_h);
 }
 
 }  // extern "C"

@@ -122,25 +122,60 @@ class _FieldStore:
             pass
 
 
-class _GradientModes:
-    """The cell-wise planes of the fixed dimension's modes for one gradient quantity (``PGD.evaluate_gradient_many``): on the
-    device one library vector of q * cells doubles per mode (``pgd_cell_gradient``), freed with this object; on the host one
-    array (q, cells, K).  ``key`` says what they were built from."""
+def _p2_point_gradients(lay, U, lam):
+    """g[a, e, c * G + d, ...] = d u_c / d x_d at the point of barycentric coordinates ``lam[a]`` of cell e, for nodal values U
+    (nodes, ncomp, ...) of the scalar P2 layout ``lay`` (intervals, triangles, tetrahedra).  With N_i = l_i (2 l_i - 1),
+    N_ab = 4 l_a l_b and d l_i / d xi_a = [i == a + 1] - [i == 0]: d u / d xi_a = sum_j d N_j / d xi_a u_j - the formula of
+    ``pgd_cell_gradient_p2`` (the edge (0, a + 1) with its coefficient 4 l_0 - 4 l_{a+1} in one piece) -, and the Jacobian comes
+    from the vertices alone."""
+    rec, G = lay.cells, lay.coords.shape[1]
+    edges = ((0, 1),) if G == 1 else lay.P2_EDGES[G]
+    Xv = lay.coords[rec[:, :G + 1]]
+    Einv = np.linalg.inv(Xv[:, 1:] - Xv[:, :1])                                  # rows of E: the edges x_a - x_0; (cells, d, a)
+    Un = U[rec]                                                                   # (cells, record entry, c, ...)
+    dlam = np.concatenate([-np.ones((1, G)), np.eye(G)])                          # d l_i / d xi_a
+    out = []
+    for l in np.asarray(lam, dtype=np.float64):
+        D = np.array([(4.0 * l[i] - 1.0) * dlam[i] for i in range(G + 1)] +
+                     [4.0 * l[b] * dlam[i] + 4.0 * l[i] * dlam[b] for i, b in edges])      # d N_j / d xi_a, (record entry, a)
+        du = np.einsum("ja,ejc...->eac...", D, Un)
+        g = np.einsum("eda,eac...->ecd...", Einv, du)                            # (cells, c, d, ...)
+        out.append(g.reshape((g.shape[0], g.shape[1] * G) + g.shape[3:]))
+    return np.stack(out)
 
-    def __init__(self, key, be, mesh, V, modes, L, scale_vec):
+
+class _GradientModes:
+    """The planes of the fixed dimension's modes for one gradient quantity (``PGD.evaluate_gradient_many``): on the device one
+    library vector of q * entries doubles per mode (``pgd_cell_gradient``; ``pgd_cell_gradient_p2`` at the points ``lam`` of every
+    cell for P2 modes), freed with this object; on the host one array (q, entries, K).  Entries: the cells, point-major times the
+    points for P2.  ``key`` says what they were built from."""
+
+    def __init__(self, key, be, mesh, V, modes, L, scale_vec, lam=None):
         self.key, self.be, self.planes = key, be, []
         q, nc, ncomp = L.shape[0], mesh.num_cells(), V._ncomp
         if be is not None:
             sc = scale_vec.dev() if scale_vec is not None else 0
             for m in modes:
-                out = be.vec_zeros(q * nc)
+                out = be.vec_zeros(q * nc * (1 if lam is None else len(lam)))
                 self.planes.append(out)
-                be.cell_gradient(V._lay.handle(), m.vector().dev(), L, out, sc)
+                if lam is None:
+                    be.cell_gradient(V._lay.handle(), m.vector().dev(), L, out, sc)
+                else:
+                    be.cell_gradient_p2(V._lay.handle(), m.vector().dev(), lam, L, out, sc)
+            return
+        sc = scale_vec.host() if scale_vec is not None else None
+        if lam is not None:
+            lay = V._lay.base if ncomp > 1 else V._lay
+            P = np.empty((q, len(lam) * nc, len(modes)))
+            for k, m in enumerate(modes):
+                g = _p2_point_gradients(lay, m.vector().host().reshape(-1, ncomp), lam)           # (npt, cells, ncomp * G)
+                p = np.einsum("ij,aej->iae", L, g)
+                P[:, :, k] = (p if sc is None else p * sc).reshape(q, -1)
+            self.planes = P
             return
         X, cells = mesh.coordinates(), mesh.cells()
         G = cells.shape[1] - 1
         Einv = np.linalg.inv(X[cells[:, 1:]] - X[cells[:, :1]])                  # rows of E: the edges x_a - x_0; (cells, d, a)
-        sc = scale_vec.host() if scale_vec is not None else None
         P = np.empty((q, nc, len(modes)))
         for k, m in enumerate(modes):
             U = m.vector().host().reshape(-1, ncomp)                              # vertex order, (node, component)
@@ -265,6 +300,24 @@ def _eval_many_host(values, n, S, sample_chunk, stats, envelope, thr, fields, wr
         res.exceedance = wrap(cnt / S)
     if fields:
         res.fields = [wrap(a) for a in all_fields]
+    return res
+
+
+def _eval_points_device(be, call, m, stats, envelope):
+    """``_eval_many_device`` for entries that are no function space (several points per cell): the statistics as they come, the
+    two envelopes of ``m`` entries as numpy arrays."""
+    res, hs = EvalManyResult(), []
+    try:
+        if envelope:
+            hs = [be.vec_zeros(m), be.vec_zeros(m)]
+        st = call(bool(stats), **({"env_min": hs[0], "env_max": hs[1]} if envelope else {}))
+        if stats:
+            res.min, res.max, res.max_abs = st[0], st[1], st[2]
+        if envelope:
+            res.envelope_min, res.envelope_max = be.vec_to_host(hs[0], 0, m), be.vec_to_host(hs[1], 0, m)
+    finally:
+        for h in hs:
+            be.vec_free(h)
     return res
 
 
@@ -797,7 +850,7 @@ class PGD:
     # ------------------------------------------------- batched evaluation of gradient quantities
     def evaluate_gradient_many(self, fixed_dim, free_dim, coords, attri, quantity="gradient_norm", scale=None, stats=True,
                                envelope=False, threshold=None, fields=False, fields_max_bytes=4 << 30, modes_max_bytes=16 << 30,
-                               sample_chunk=256, planes="stored"):
+                               sample_chunk=256, planes="stored", at=None):
         """``evaluate_many`` for a quantity of the spatial gradient of the solution: per cell of the fixed mesh and per sample
         the value ``scale * |L grad u|`` with L = ``fem.gradient_quantity(quantity, ...)`` - "gradient_norm" (with a conductivity
         as ``scale``: the flux magnitude) or "von_mises" (with ``scale`` = 2 mu = E / (1 + nu): the von Mises stress).  ``scale``:
@@ -817,11 +870,24 @@ class PGD:
         nodal modes per sample chunk and takes the cell gradients of the chunk's fields.  "auto" is "stored" while the planes
         fit ``modes_max_bytes``, else "fused".
 
+        P2 modes: the gradient is affine per cell, so ``at`` says where in the cell the quantity is taken (``None``, the default,
+        refuses P2 modes).  "midpoint": at the barycentre, one value per cell - everything above holds as it stands.  "vertices":
+        at the G + 1 corners of every cell, (G + 1) * cells entries (``modes_max_bytes`` counts them).  |L grad u| is the norm of an
+        affine function on the cell, hence convex, hence largest at a corner: ``max`` is the exact maximum of the quantity over the
+        mesh for every sample, and ``envelope_max`` (DG0: the largest of a cell's corners) the exact maximum over the cell and the
+        samples.  ``min`` and ``envelope_min`` are minima over the evaluation points, so upper bounds of the true minima.
+        ``threshold`` and ``fields`` are refused with "vertices" (a per-cell exceedance needs the per-sample maximum over a cell's
+        points, which the entry-wise kernels do not form).  The planes come from ``pgd_cell_gradient_p2``, the fused product is
+        ``pgd_eval_batch_grad_p2``; intervals are always served by the host.  P1 modes take ``None`` or "midpoint" (the same
+        thing) and refuse "vertices".
+
         Returns an ``EvalManyResult`` whose Functions live on ``FunctionSpace(mesh, "DG", 0)`` of the fixed mesh; ``max_abs``
         equals ``max``.  Signed components (one row of L, no norm) are ``evaluate_many``-like fields of one plane:
         ``pgd_eval_batch`` on the output of ``pgd_cell_gradient`` gives them."""
         if planes not in ("stored", "fused", "auto"):
             raise ValueError("evaluate_gradient_many: planes=%r, \"stored\", \"fused\" or \"auto\" are possible" % (planes,))
+        if at not in (None, "midpoint", "vertices"):
+            raise ValueError("evaluate_gradient_many: at=%r, None, \"midpoint\" or \"vertices\" are possible" % (at,))
         coords = self._check_many(fixed_dim, free_dim, coords, attri)
         S = coords.shape[0]
         att = self.mesh[fixed_dim].attributes[attri]
@@ -833,10 +899,24 @@ class PGD:
         if not all(isinstance(m, fem.Function) for m in modes[:K]):
             raise ValueError("evaluate_gradient_many: the fixed dimension's modes are not Functions")
         V = modes[0].function_space()
-        if V._dg0 or V._lay.degree != 1:
-            raise NotImplementedError("evaluate_gradient_many: P1 modes only (the gradient of a P2 mode is not constant per cell)")
+        if V._dg0 or V._lay.degree not in (1, 2):
+            raise NotImplementedError("evaluate_gradient_many: P1 or P2 modes only")
+        if V._lay.degree == 2 and at is None:
+            raise NotImplementedError("evaluate_gradient_many: P1 modes only unless ``at`` says where in the cell the quantity is "
+                                      "taken (the gradient of a P2 mode is not constant per cell): at=\"midpoint\" or at=\"vertices\"")
+        if V._lay.degree == 1 and at == "vertices":
+            raise ValueError("evaluate_gradient_many: at=\"vertices\" with P1 modes (the gradient is constant per cell: there is "
+                             "nothing to choose)")
         lay = V._lay.base if V._ncomp > 1 else V._lay
         mesh = V.mesh()
+        lam = None                                       # P2: the barycentric coordinates of the points of every cell
+        if V._lay.degree == 2:
+            G1 = mesh.topology().dim() + 1
+            lam = np.full((1, G1), 1.0 / G1) if at == "midpoint" else np.eye(G1)
+        npt = 1 if lam is None else lam.shape[0]
+        if npt > 1 and (fields or threshold is not None):
+            raise ValueError("evaluate_gradient_many: at=\"vertices\" has %d entries per cell: no ``fields`` and no ``threshold`` "
+                             "(a per-cell exceedance needs the per-sample maximum over a cell's points)" % npt)
         if mesh.part is not None or getattr(lay, "part", None) is not None:
             raise NotImplementedError("evaluate_gradient_many on a row-sharded fixed dimension (every rank holds a slab of the "
                                       "modes; the per-sample statistics would need a reduction across ranks)")
@@ -854,11 +934,13 @@ class PGD:
             scale_key = float(scale)
             L = L * scale_key
         q, nc = L.shape[0], mesh.num_cells()
+        m = npt * nc                                     # entries: one per point and cell, point-major
         if planes == "auto":
-            planes = "stored" if K * q * nc * 8 <= modes_max_bytes else "fused"
-        if planes == "stored" and K * q * nc * 8 > modes_max_bytes:
-            raise ValueError("evaluate_gradient_many: the derived modes would take %d bytes (%d modes x %d planes x %d cells x "
-                             "8), more than modes_max_bytes=%d" % (K * q * nc * 8, K, q, nc, modes_max_bytes))
+            planes = "stored" if K * q * m * 8 <= modes_max_bytes else "fused"
+        if planes == "stored" and K * q * m * 8 > modes_max_bytes:
+            raise ValueError("evaluate_gradient_many: the derived modes would take %d bytes (%d modes x %d planes x %s%d cells x "
+                             "8), more than modes_max_bytes=%d" % (K * q * m * 8, K, q, "%d points x " % npt if npt > 1 else "", nc,
+                                                                  modes_max_bytes))
         if fields and nc * S * 8 > fields_max_bytes:
             raise ValueError("evaluate_gradient_many: fields=True would store %d bytes (%d cells x %d samples x 8), more than "
                              "fields_max_bytes=%d" % (nc * S * 8, nc, S, fields_max_bytes))
@@ -867,61 +949,85 @@ class PGD:
         be = fem.get_backend()
         Vc = fem.FunctionSpace(mesh, "DG", 0)
         if planes == "fused":
-            res = self._evaluate_gradient_fused(be, V, Vc, modes[:K], L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk)
-            res.coefficients = C
-            return res
-        device = nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "eval_batch_norm") and hasattr(be, "cell_gradient")
-        key = (quantity, K, scale_key, device, id(be), tuple((id(m.vector()), m.vector().version) for m in modes[:K]))
-        cache = getattr(att, "_gradient_modes", None)
-        if cache is None or cache.key != key:
-            att._gradient_modes = None                       # the old planes go before the new ones are allocated
-            cache = att._gradient_modes = _GradientModes(key, be if device else None, mesh, V, modes[:K], L, scale_vec)
-            fem.STATS["gradient_mode_builds"] = fem.STATS.get("gradient_mode_builds", 0) + 1
-        if device:
-            res = _eval_many_device(be, lambda st, **kw: be.eval_batch_norm(cache.planes, q, C, stats=st, **kw), Vc, nc, S, stats,
-                                    envelope, thr, fields)
-            fem.STATS["eval_gradient_calls"] = fem.STATS.get("eval_gradient_calls", 0) + 1
+            res = self._evaluate_gradient_fused(be, V, Vc, modes[:K], L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk, lam)
         else:
-            P = cache.planes                                    # (q, cells, K)
+            p2dev = lam is not None and lay.coords.shape[1] > 1 and hasattr(be, "cell_gradient_p2")      # (intervals: the host)
+            device = (nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "eval_batch_norm") and
+                      (hasattr(be, "cell_gradient") if lam is None else p2dev))
+            key = (quantity, K, scale_key, device, id(be), tuple((id(f.vector()), f.vector().version) for f in modes[:K]),
+                   at if lam is not None else None)
+            cache = getattr(att, "_gradient_modes", None)
+            if cache is None or cache.key != key:
+                att._gradient_modes = None                       # the old planes go before the new ones are allocated
+                cache = att._gradient_modes = _GradientModes(key, be if device else None, mesh, V, modes[:K], L, scale_vec, lam)
+                fem.STATS["gradient_mode_builds"] = fem.STATS.get("gradient_mode_builds", 0) + 1
+            if device:
+                call = lambda st, **kw: be.eval_batch_norm(cache.planes, q, C, stats=st, **kw)
+                res = (_eval_many_device(be, call, Vc, nc, S, stats, envelope, thr, fields) if npt == 1 else
+                       _eval_points_device(be, call, m, stats, envelope))
+                fem.STATS["eval_gradient_calls"] = fem.STATS.get("eval_gradient_calls", 0) + 1
+            else:
+                P = cache.planes                                    # (q, entries, K)
 
-            def norms(j0, step):
-                Cc = C[:, j0:j0 + step]
-                ss = np.zeros((nc, Cc.shape[1]))
-                for i in range(q):
-                    U = P[i] @ Cc
-                    ss += U * U
-                return np.sqrt(ss)                              # (cells, cs)
-            res = _eval_many_host(norms, nc, S, sample_chunk, stats, envelope, thr, fields, lambda a: _host_function(Vc, a),
-                                  nonnegative=True)
+                def norms(j0, step):
+                    Cc = C[:, j0:j0 + step]
+                    ss = np.zeros((m, Cc.shape[1]))
+                    for i in range(q):
+                        U = P[i] @ Cc
+                        ss += U * U
+                    return np.sqrt(ss)                              # (entries, cs)
+                res = _eval_many_host(norms, m, S, sample_chunk, stats, envelope, thr, fields,
+                                      (lambda a: _host_function(Vc, a)) if npt == 1 else (lambda a: a), nonnegative=True)
+        if npt > 1 and envelope:                         # the corners of a cell -> DG0 (the entries are point-major)
+            res.envelope_min = _host_function(Vc, res.envelope_min.reshape(npt, nc).min(axis=0))
+            res.envelope_max = _host_function(Vc, res.envelope_max.reshape(npt, nc).max(axis=0))
         res.coefficients = C
         return res
 
     @staticmethod
-    def _evaluate_gradient_fused(be, V, Vc, modes, L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk):
+    def _evaluate_gradient_fused(be, V, Vc, modes, L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk, lam=None):
         """``evaluate_gradient_many(planes="fused")``: no planes are built or kept.  Device: ``pgd_eval_batch_grad`` on the nodal
-        modes.  Host: per sample chunk the nodal product F C, then the cell gradients of the chunk's fields - the einsum of
-        ``_GradientModes`` on the fields instead of the modes."""
+        modes (``pgd_eval_batch_grad_p2`` at the points ``lam`` for P2 modes).  Host: per sample chunk the nodal product F C, then
+        the cell gradients of the chunk's fields - the einsum of ``_GradientModes`` on the fields instead of the modes.  With more
+        than one point per cell the envelopes come back as arrays of points x cells entries."""
         mesh, K = V.mesh(), len(modes)
         q, nc, ncomp = L.shape[0], mesh.num_cells(), V._ncomp
+        npt = 1 if lam is None else len(lam)
+        lay = V._lay.base if ncomp > 1 else V._lay
         fem.STATS["eval_gradient_fused_calls"] = fem.STATS.get("eval_gradient_fused_calls", 0) + 1
-        if nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "eval_batch_grad"):
+        p2dev = lam is not None and lay.coords.shape[1] > 1 and hasattr(be, "eval_batch_grad_p2")          # (intervals: the host)
+        if nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and (hasattr(be, "eval_batch_grad") if lam is None else p2dev):
             handles = [m.vector().dev() for m in modes]
             sc = scale_vec.dev() if scale_vec is not None else 0
 
             def call(st, **kw):
                 try:
+                    if lam is not None:
+                        return be.eval_batch_grad_p2(V._lay.handle(), handles, lam, L, C, scale=sc, stats=st, **kw)
                     return be.eval_batch_grad(V._lay.handle(), handles, L, C, scale=sc, stats=st, **kw)
                 except RuntimeError as exc:
                     if getattr(exc, "code", None) != -4:                  # PGD_ERR_LIMIT
                         raise
                     raise ValueError("evaluate_gradient_many(planes=\"fused\"): q = %d planes of K = %d modes are more than the "
                                      "fused kernel holds for a block of cells (q * K up to about 1250): %s" % (q, K, exc)) from None
+            if npt > 1:
+                return _eval_points_device(be, call, npt * nc, stats, envelope)
             return _eval_many_device(be, call, Vc, nc, S, stats, envelope, thr, fields)
+        sc = scale_vec.host() if scale_vec is not None else None
+        F = np.stack([m.vector().host() for m in modes], axis=1)                 # (nodes * ncomp, K)
+        if lam is not None:
+            wrap = (lambda a: _host_function(Vc, a)) if npt == 1 else (lambda a: a)
+
+            def norms_p2(j0, step):
+                U = (F @ C[:, j0:j0 + step]).reshape(-1, ncomp, min(step, S - j0))
+                P = np.einsum("ij,aejs->iaes", L, _p2_point_gradients(lay, U, lam))       # (q, npt, cells, cs)
+                if sc is not None:
+                    P = P * sc[None, None, :, None]
+                return np.sqrt((P * P).sum(axis=0)).reshape(npt * nc, -1)
+            return _eval_many_host(norms_p2, npt * nc, S, sample_chunk, stats, envelope, thr, fields, wrap, nonnegative=True)
         X, cells = mesh.coordinates(), mesh.cells()
         G = cells.shape[1] - 1
         Einv = np.linalg.inv(X[cells[:, 1:]] - X[cells[:, :1]])                  # rows of E: the edges x_a - x_0; (cells, d, a)
-        sc = scale_vec.host() if scale_vec is not None else None
-        F = np.stack([m.vector().host() for m in modes], axis=1)                 # (nodes * ncomp, K)
 
         def norms(j0, step):
             U = (F @ C[:, j0:j0 + step]).reshape(-1, ncomp, min(step, S - j0))    # (node, component, sample)

@@ -286,6 +286,12 @@ int pgd_op_symmetrize(pgd_handle ctx, pgd_handle op, int *used);
  * change).  The frontend asks before it trades a fused product-dot (fem._bilinear_scalar, the functionals of
  * solver.py:547-569) for product + dot with the product kept.  y is bit-identical in all three forms. */
 int pgd_atom_product_form(pgd_handle ctx, pgd_handle A, int *form);
+/* Which kernel family a product over the rows [r0, r1) (r1 < 0: all) of this operator would run in right now - its current storage, the
+ * current knobs - and with which launch shape; nothing is launched, classified or counted.  pcg_like: the product of a PCG (w = x)
+ * or a plain one, as opposed to a product fused with the dot against a third vector.  out[0..7) = family (index of pgd_kernel_counts,
+ * -1: not decided by form - no symmetric storage, the CSR kernels or a lattice form), workgroups, planes per march, tiles in x,
+ * tiles in y, rows per thread, plane fetches in flight (the last two: the stencil march only, else 0).  n >= 7. */
+int pgd_product_plan(pgd_handle ctx, pgd_handle op, int64_t r0, int64_t r1, int pcg_like, int64_t *out, int n);
 
 /* Look for the lossless row-class dictionary of the operator's diagonal form (structured vertex grids, after
  * pgd_op_symmetrize / pgd_op_combine; PGD_TUNE_SPMV_ROW_CLASSES): *classes = number of distinct 8-tuples of slot values

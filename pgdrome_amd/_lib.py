@@ -96,6 +96,7 @@ SIGNATURES = {
     "pgd_mg_slab_up": (C.c_int, [H, H, H, H, H, C.c_int, PD]),
     "pgd_bicgstab_solve": (C.c_int, [H, H, H, H, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), PD]),
     "pgd_atom_product_form": (C.c_int, [H, H, C.POINTER(C.c_int)]),
+    "pgd_product_plan": (C.c_int, [H, H, I64, I64, C.c_int, PI64, C.c_int]),
     "pgd_vec_multidot": (C.c_int, [H, H, PH, C.c_int, I64, I64, PD]),
     "pgd_vec_multidot_pair": (C.c_int, [H, H, H, PH, C.c_int, I64, I64, PD]),
     "pgd_pcg_solve": (C.c_int, [H, H, H, H, F64, F64, C.c_int, C.POINTER(C.c_int), PD]),
@@ -908,6 +909,15 @@ class Context:
         out = (C.c_int64 * 8)()
         self._ck(self.lib.pgd_kernel_counts(self.h, out, 8))
         return {k: int(out[i]) for i, k in enumerate(self.KERNEL_FAMILIES)}
+
+    def product_plan(self, op, r0=0, r1=-1, pcg_like=True):
+        """Kernel family (a name of KERNEL_FAMILIES, None: not decided by form) and launch shape of a product over [r0, r1) of `op`
+        as it stands, under the current knobs; launches and counts nothing."""
+        out = (C.c_int64 * 7)()
+        self._ck(self.lib.pgd_product_plan(self.h, op, int(r0), int(r1), 1 if pcg_like else 0, out, 7))
+        plan = dict(zip(("form", "wgs", "zchunk", "tiles_x", "tiles_y", "rows_per_thread", "depth"), map(int, out)))
+        plan["family"] = self.KERNEL_FAMILIES[plan["form"]] if plan["form"] >= 0 else None
+        return plan
 
     def pcg_recompute_updates(self):
         """Launches of the PCG update that forms A p itself instead of reading it (PGD_TUNE_PCG_RECOMPUTE_Q)."""

@@ -493,7 +493,7 @@ struct StencilFold {
     const double *vec_in; int nvec;     // the previous update's (r~.r~, true r.r) pairs: the other buffer than `pairs`
     int par;                            // parity of the iteration
 };
-int stencil_update_blocks(const Ctx *c, const Mesh *m);
+int stencil_update_blocks(const Ctx *c, const Mesh *m, const Csr *a);
 int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, double *r, const double *s,
                           double *pairs, int lag, double s_free = 0.0, const StencilFold *fold = nullptr);
 // ... and with the dot-only product of the direction it writes in the same march (k_pcg1_fused_march): r is read from r_in and written

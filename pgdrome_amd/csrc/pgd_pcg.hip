@@ -1605,7 +1605,7 @@ static int pcg_choose_and_seed(PcgRun &R) {
     R.lag_x = c->pcg_lag_x && pcg_single_sync(R.form);
     // (two-launch form above 2^20 rows: 512 workgroups in the update, every one of which sums all partial sums)
     R.g2v = grid_for((n + 1) / 2, TPB, (n > ((int64_t)1 << 20) && n <= c->pcg_small_ss_rows && c->pcg_small_ss) ? 512 : MAX_VEC_BLOCKS);
-    R.gvec = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE ? stencil_update_blocks(c, R.m) : R.g2v;
+    R.gvec = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE ? stencil_update_blocks(c, R.m, R.o) : R.g2v;
     R.fused = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE && c->pcg_fused_march && stencil_fused_ok(c, R.m, R.o);
     R.fold_march = R.form == PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE && c->pcg_fold_march && !R.fused;      // (both knobs on: the fused march)
     // (the march that takes the scalar step alternates between two halves like the two-launch form: each holds gvec pairs)

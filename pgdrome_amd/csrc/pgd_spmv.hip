@@ -22,8 +22,10 @@
 
 #include "pgd_internal.h"
 #include "pgd_dia_march.h"
+#include "pgd_product_plan.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace pgd {
 
@@ -941,7 +943,6 @@ struct DiacArgs {
 //   z + 2 being staged - make ONE barrier per step enough.
 using d2 = __attribute__((ext_vector_type(2))) double;
 struct DiacT { d2 A15, A37, A26, A40, B15, B37, B26, B40, L15, L37, LB15, D26, LD37; };
-constexpr int DIAC_MAXCHUNK = 1024;    // planes per march at most
 
 template <bool DOT, bool STORE, int D, bool NTY>
 __global__ __launch_bounds__(256) void k_spmv_diac_march2(DiacArgs A) {
@@ -2753,85 +2754,138 @@ bool atom_fast_form(Ctx *c, const Mesh *m, Csr *a, int64_t r0, int64_t r1) {
     return true;
 }
 
-// planes per march of the plain z-march over the planes [z0, z1) of a structured grid (0 marches: row order)
-static int dia_march_chunks(const Ctx *c, const Mesh *m, int z0, int z1, int wy, int *zchunk_out) {
-    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
-    const int tiles_x = (m->sym_nx + 63) / 64, tiles_y = (m->sym_ny + wy - 1) / wy;
-    int zchunk = 0, chunks = 0;
-    if (c->spmv_zchunk > 0 && plane * 64 >= c->spmv_grid_min_plane_bytes) {
-        const int64_t tile_planes = (int64_t)tiles_x * tiles_y * (z1 - z0);
-        zchunk = (int)std::min<int64_t>(c->spmv_zchunk, tile_planes * (wy / 4) / (4 * (int64_t)c->num_cu));
-        if (c->spmv_zchunk_force > 0) zchunk = c->spmv_zchunk_force;       // tests: the march on any grid size
-        chunks = (zchunk >= 3 || c->spmv_zchunk_force > 0) ? (z1 - z0 + zchunk - 1) / zchunk : 0;
-    }
-    *zchunk_out = zchunk;
-    return chunks;
-}
-
-// Shape of a launch of k_spmv_stencil_march over `planes` planes of an nx x ny grid, `depth` plane fetches in flight.
-struct StencilShape { int rows_per_thread, tiles_x, tiles_y, zchunk, wgs; };
-static StencilShape stencil_shape(const Ctx *c, int nx, int ny, int planes, int depth) {
-    StencilShape sh;
-    sh.tiles_x = (nx + 63) / 64;
-    sh.tiles_y = (ny + 15) / 16;
-    const int64_t slots = (int64_t)c->stencil_wg_per_cu * c->num_cu;
-    // rows per thread: four; two where the launch is so thin that marches of four-row patches would be shorter than 8
-    // planes (a z-slab of a sharded solve: 256 x 256 x 32 = 8 marches of 4 planes against 4 of 8) - PGD_TUNE_STENCIL_ROWS
-    sh.rows_per_thread = 4;
-    {
-        const int64_t tiles4 = (int64_t)sh.tiles_x * sh.tiles_y;
-        const int64_t marches4 = std::max<int64_t>(1, slots / tiles4);
-        const int zc4 = (int)((planes + marches4 - 1) / marches4);
-        if (c->stencil_rows == 2 || (c->stencil_rows == 0 && zc4 < 8 && ny >= 16 && c->spmv_zchunk_stencil <= 0 && c->stencil_depth != 6)) sh.rows_per_thread = 2;
-    }
-    if (sh.rows_per_thread == 2) sh.tiles_y = (ny + 7) / 8;
-    // march length: every resident workgroup slot filled once (two workgroups per CU), whole groups of the fetch depth
-    const int64_t tiles = (int64_t)sh.tiles_x * sh.tiles_y;
-    const int64_t marches = std::max<int64_t>(1, slots / tiles);
-    int zc = (int)((planes + marches - 1) / marches);
-    if (c->spmv_zchunk_stencil > 0) zc = c->spmv_zchunk_stencil;
-    sh.zchunk = std::max(depth, zc);                   // (an incomplete last group of steps idles behind the march's last plane)
-    sh.wgs = (int)(((planes + sh.zchunk - 1) / sh.zchunk) * tiles);
-    return sh;
-}
-
-// would a product over ALL rows of this operator (a PCG product: w = x, or no dot) run in k_spmv_stencil_march?  The conditions of
-// launch_spmv_op, for the solve that wants to hold the scaled operator as a stencil only (Csr::st_virtual)
-bool stencil_whole_grid(const Ctx *c, const Mesh *m, const Csr *a) {
-    if (!(c->spmv_sym && m->sym_w && a->uvals_valid && a->uvals) || m->sym_nx <= 0) return false;
-    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
-    const int nz = (int)(m->nv / plane);
-    int zchunk = 0;
-    if (dia_march_chunks(c, m, 0, nz, c->spmv_variant <= 1 ? 8 : 4, &zchunk) <= 0) return false;
-    const bool coded = c->spmv_variant == 0 && c->spmv_classes && a->cls_count > 0;
-    return coded && c->spmv_stencil && a->st_ok && (c->spmv_zchunk_force <= 0 || c->spmv_zchunk_stencil > 0) &&
-           a->st_z0 == 0 && a->st_z1 == nz && plane < ((int64_t)1 << 26);
-}
+// would a product over ALL rows of this operator (a PCG product: w = x, or no dot) run in k_spmv_stencil_march?  For the solve that wants
+// to hold the scaled operator as a stencil only (Csr::st_virtual)
+bool stencil_whole_grid(const Ctx *c, const Mesh *m, const Csr *a) { return plan_product(c, m, a, 0, m->nv, true).form == KC_STENCIL_MARCH; }
 
 // ... and over the whole planes [r0, r1) of a sharded slab, ghost planes as halo included
 bool stencil_row_range(const Ctx *c, const Mesh *m, const Csr *a, int64_t r0, int64_t r1) {
-    if (!(c->spmv_sym && m->sym_w && a->uvals_valid && a->uvals) || m->sym_nx <= 0) return false;
-    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
-    if (r0 < 0 || r1 <= r0 || r1 > m->nv || r0 % plane != 0 || r1 % plane != 0) return false;
-    const int nz = (int)(m->nv / plane), z0 = (int)(r0 / plane), z1 = (int)(r1 / plane);
-    int zchunk = 0;
-    if (dia_march_chunks(c, m, z0, z1, c->spmv_variant <= 1 ? 8 : 4, &zchunk) <= 0) return false;
-    const bool coded = c->spmv_variant == 0 && c->spmv_classes && a->cls_count > 0;
-    const bool st_lower = z0 == 0 ? a->st_z0 == 0 : (z0 - 1 >= a->st_z0 || (z0 == a->st_z0 && a->st_g_lo));
-    const bool st_upper = z1 == nz ? a->st_z1 == nz : (z1 + 1 <= a->st_z1 || (z1 == a->st_z1 && a->st_g_hi));
-    return coded && c->spmv_stencil && a->st_ok && (c->spmv_zchunk_force <= 0 || c->spmv_zchunk_stencil > 0) && st_lower && st_upper &&
-           plane < ((int64_t)1 << 26);
+    return r1 > r0 && plan_product(c, m, a, r0, r1, true).form == KC_STENCIL_MARCH;
+}
+
+// The run-time (dot, store, nty) of a product launch as template arguments, exactly the instances the products have: a launch without a
+// dot stores, and only a dot launch that stores takes the non-temporal hint for y.  f(D, S, NT) gets std::bool_constants.
+template <class F>
+static void with_product_kind(bool dot, bool store, bool nty, F &&f) {
+    constexpr std::true_type T{}; constexpr std::false_type N{};
+    if (dot && store && nty) f(T, T, T);
+    else if (dot && store) f(T, T, N);
+    else if (dot) f(T, N, N);
+    else f(N, T, N);
+}
+
+// one product launch: what launch_spmv_op was asked for (the row range validated, r1 >= 0)
+struct ProductCall {
+    const double *x; double *y; const double *w;
+    int64_t r0, r1;
+    bool dot, store;
+    const int *flags;
+    int qq;                 // DOT launches: partial sums in pairs (set by the single-sync recurrence around its product launches)
+};
+
+// Everything the launches of k_spmv_stencil_march and k_pcg1_fused_march with an operator's stencil share; the callers add their partial
+// sums, qq and what their epilogue reads
+static void stencil_args(StencilArgs &F, const Ctx *c, const Mesh *m, const Csr *a, const ProductPlan &P, const double *x, double *y) {
+    F.cls = a->cls; F.ident = a->st_ident; F.x = x; F.y = y; F.flags = c->flags;
+    F.zv0 = a->st_z0; F.zv1 = a->st_z1; F.zm0 = a->st_zm0; F.zm1 = a->st_zm1;
+    F.zs0 = a->st_zm0 - (a->st_g_lo ? 1 : 0); F.zs1 = a->st_zm1 + (a->st_g_hi ? 1 : 0);
+    for (int s2 = 0; s2 < 8; ++s2) F.c[s2] = a->st_c[s2];
+    F.nx = m->sym_nx; F.ny = m->sym_ny; F.nz = (int)(m->nv / ((int64_t)m->sym_nx * m->sym_ny)); F.z0 = P.z0; F.z1 = P.z1;
+    F.tiles_x = P.tiles_x; F.tiles_y = P.tiles_y; F.zchunk = P.zchunk;
+    F.whatif = 0; F.b = nullptr; F.w = 0.0;
+}
+
+static int launch_product_stencil(Ctx *c, const Mesh *m, const Csr *a, const ProductPlan &P, const ProductCall &k) {
+    StencilArgs F;
+    stencil_args(F, c, m, a, P, k.x, k.y);
+    F.flags = k.flags; F.qq = k.qq; F.partials = c->partials + c->partials_off;
+#if defined(PGD_STENCIL_TIMING) || defined(PGD_STENCIL_WHATIF)
+    if (const char *wi = getenv("PGD_STENCIL_WHATIF")) F.whatif = atoi(wi);
+#endif
+    bool timed = false;
+    PGD_TRY(prof_begin(c, k.dot, k.store, &timed));
+    with_product_kind(k.dot, k.store, k.qq && c->pcg_stream_hints, [&](auto D, auto S, auto NT) {
+        if (P.rows_per_thread == 2) k_spmv_stencil_march<D.value, S.value, 3, NT.value, 2, 0, 2><<<P.wgs, 256, 0, c->stream>>>(F);
+        else if (P.depth == 6) k_spmv_stencil_march<D.value, S.value, 6, NT.value, 2><<<P.wgs, 256, 0, c->stream>>>(F);
+        else k_spmv_stencil_march<D.value, S.value, 3, NT.value, 2><<<P.wgs, 256, 0, c->stream>>>(F);
+    });
+    c->kcount[KC_STENCIL_MARCH] += 1;
+    if (timed) PGD_TRY(prof_end(c, m, k.r1 - k.r0, k.store ? 16.0 : 8.0));
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+static int launch_product_diac(Ctx *c, const Mesh *m, const Csr *a, const ProductPlan &P, const ProductCall &k) {
+    DiacArgs E;
+    E.cls = a->cls; E.same = a->cls_same; E.table = a->cls_table; E.ncls = a->cls_count; E.x = k.x; E.y = k.y; E.flags = k.flags;
+    E.partials = c->partials + c->partials_off;
+    E.nx = m->sym_nx; E.ny = m->sym_ny; E.nz = (int)(m->nv / ((int64_t)m->sym_nx * m->sym_ny));
+    E.z0 = P.z0; E.z1 = P.z1; E.zchunk = P.zchunk; E.tiles_x = P.tiles_x; E.tiles_y = P.tiles_y;
+    E.qq = k.qq;
+    E.nt_y = (k.qq && c->pcg_stream_hints) ? 1 : 0;      // the PCG's q: read once, by the vector update (+ 1 %)
+    bool timed = false;
+    PGD_TRY(prof_begin(c, k.dot, k.store, &timed));
+    with_product_kind(k.dot, k.store, E.nt_y != 0, [&](auto D, auto S, auto NT) {
+        if (P.six) k_spmv_diac_march2<D.value, S.value, 6, NT.value><<<P.wgs, 256, 0, c->stream>>>(E);
+        else k_spmv_diac_march2<D.value, S.value, 3, NT.value><<<P.wgs, 256, 0, c->stream>>>(E);
+    });
+    c->kcount[KC_DIAC_MARCH] += 1;
+    if (timed) PGD_TRY(prof_end(c, m, k.r1 - k.r0, 17.0));
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+// the slot values themselves: row order (KC_DIA_ROWS) or one of the plain marches (KC_DIA_MARCH)
+static int launch_product_dia(Ctx *c, const Mesh *m, const Csr *a, const ProductPlan &P, const ProductCall &k) {
+    DiaArgs D;
+    D.uvals = a->uvals; D.x = k.x; D.w = k.w; D.y = k.y; D.partials = c->partials + c->partials_off; D.flags = k.flags; D.n = a->uvals_stride;
+    D.nx = m->sym_nx; D.ny = m->sym_ny; D.nz = (int)(m->nv / ((int64_t)m->sym_nx * m->sym_ny));
+    D.row_begin = (int)k.r0; D.row_end = (int)k.r1;
+    D.nblk1 = -1; D.row_begin2 = D.row_end2 = 0;
+    D.z0 = P.z0; D.z1 = P.z1; D.tiles_x = P.tiles_x; D.tiles_y = P.tiles_y; D.zchunk = P.zchunk;
+    D.unit_diag = (a->uvals_scaled && a->uvals_unit) ? 1 : 0;
+    D.qq = k.qq;
+    bool timed = false;
+    PGD_TRY(prof_begin(c, k.dot, k.store, &timed));
+    with_product_kind(k.dot, k.store, false, [&](auto DT, auto S, auto) {
+        if (P.form == KC_DIA_ROWS) k_spmv_dia_rows<DT.value, S.value><<<P.nblk, 64, 0, c->stream>>>(D);
+        else if (P.variant == MARCH_3) k_spmv_dia_march3<DT.value, S.value><<<P.wgs, 256, 0, c->stream>>>(D);
+        else if (P.variant == MARCH_2) k_spmv_dia_march2<DT.value, S.value><<<P.wgs, 256, 0, c->stream>>>(D);
+        else if (P.variant == MARCH_WY8) k_spmv_dia_march<DT.value, S.value, 8><<<P.wgs, 64 * 8, 0, c->stream>>>(D);
+        else k_spmv_dia_march<DT.value, S.value, 4><<<P.wgs, 64 * 4, 0, c->stream>>>(D);
+    });
+    c->kcount[P.form] += 1;
+    if (timed) PGD_TRY(prof_end(c, m, k.r1 - k.r0, 8.0 * (D.unit_diag ? 7 : 8) + 16));
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+static int launch_product_sym(Ctx *c, const Mesh *m, const Csr *a, const ProductPlan &P, const ProductCall &k) {
+    SymArgs A;
+    A.uvals = a->uvals; A.x = k.x; A.w = k.w; A.y = k.y; A.partials = c->partials + c->partials_off; A.flags = k.flags;
+    A.tab = m->sym_tab; A.pids = m->pids; A.n = a->uvals_stride; A.row_begin = (int)k.r0; A.row_end = (int)k.r1;
+    A.qq = k.qq;
+    bool timed = false;
+    PGD_TRY(prof_begin(c, k.dot, k.store, &timed));
+    with_product_kind(k.dot, k.store, false, [&](auto D, auto S, auto) {
+        if (m->sym_w == 4) k_spmv_sym<D.value, S.value, 4><<<P.nblk, 64, 0, c->stream>>>(A);
+        else k_spmv_sym<D.value, S.value, 8><<<P.nblk, 64, 0, c->stream>>>(A);
+    });
+    c->kcount[KC_SYM_ROWS] += 1;
+    if (timed) PGD_TRY(prof_end(c, m, k.r1 - k.r0, 8.0 * m->sym_w + 18));
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
 }
 
 int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double *y, const double *w, int64_t r0,
                    int64_t r1, bool dot, bool store, const int *flags, int *nparts_out) {
     // (st_virtual: the stencil couplings describe D^-1/2 A D^-1/2 while the slot arrays and the CSR values hold A - inside
     // pgd_pcg_solve, which has checked that its products take the stencil form; anything else must not compute with the wrong numbers)
-    auto not_virtual = [&]() -> int {
-        return a->st_virtual ? fail(c, PGD_ERR_INVALID, "spmv: the operator is held as a scaled stencil; this launch cannot take that form") : PGD_OK;
+    auto not_virtual = [&](bool ok) -> int {
+        return a->st_virtual && !ok ? fail(c, PGD_ERR_INVALID, "spmv: the operator is held as a scaled stencil; this launch cannot take that form") : PGD_OK;
     };
     if (!(c->spmv_sym && m->sym_w && a->uvals_valid && a->uvals)) {
-        PGD_TRY(not_virtual());
+        PGD_TRY(not_virtual(false));
         PGD_TRY(ensure_vals(c, m, const_cast<Csr *>(a)));
         // P2 layouts bound to a box lattice: the same product, bit for bit, from the operator's row-class form (pgd_p2lat.hip); an
         // operator that takes it is not offered to the row-diagonal form below
@@ -2865,221 +2919,37 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
     }
     if (r1 < 0) r1 = m->nv;
     if (r0 < 0 || r0 > r1 || r1 > m->nv) return fail(c, PGD_ERR_INVALID, "spmv: bad row range");
-    const int64_t nrows = r1 - r0;
-    const int nblk = (int)((nrows + 63) / 64);
-    if (nparts_out) *nparts_out = nblk;
-    if (nblk == 0) return PGD_OK;
-    if (dot) PGD_TRY(ensure_partials(c, std::max<int64_t>(c->partials_off + 2 * (int64_t)nblk, 4 * MAX_VEC_BLOCKS)));
-    SymArgs A;
-    A.uvals = a->uvals; A.x = x; A.w = w; A.y = y; A.partials = c->partials + c->partials_off; A.flags = flags;
-    A.tab = m->sym_tab; A.pids = m->pids; A.n = a->uvals_stride; A.row_begin = (int)r0; A.row_end = (int)r1;
-    A.qq = (dot && c->spmv_qq) ? 1 : 0;
-    if (m->sym_nx > 0) {
-        // structured vertex grid: the operator is held in diagonal form
-        const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
-        DiaArgs D;
-        D.uvals = a->uvals; D.x = x; D.w = w; D.y = y; D.partials = c->partials + c->partials_off; D.flags = flags; D.n = a->uvals_stride;
-        D.nx = m->sym_nx; D.ny = m->sym_ny; D.nz = (int)(m->nv / plane);
-        D.row_begin = (int)r0; D.row_end = (int)r1;
-        D.nblk1 = -1; D.row_begin2 = D.row_end2 = 0;
-        D.z0 = (int)(r0 / plane); D.z1 = (int)(r1 / plane);
-        const int wy = c->spmv_variant <= 1 ? 8 : 4;        // patch rows (0: 4 waves x two rows per thread; 1: 8 waves; 2: 4 waves, one row)
-        D.tiles_x = (D.nx + 63) / 64; D.tiles_y = (D.ny + wy - 1) / wy; D.zchunk = 0;
-        D.unit_diag = (a->uvals_scaled && a->uvals_unit) ? 1 : 0;
-        D.qq = (dot && c->spmv_qq) ? 1 : 0;                  // set by the single-sync recurrence around its product launches
-        // plane-aligned row range, PCG product (w = x) or plain product, planes large enough: the LDS march
-        int chunks = 0;
-        if ((!dot || w == x) && r0 % plane == 0 && r1 % plane == 0) {
-            // planes per march: as long as the launch still has ~4 workgroups per CU (measured on z-slabs of the 256 x 256
-            // grid, tools/bench_spmv_slab.py: 30 planes - the interior of an 8-GPU rank - 31.9 us marching 8 planes vs 41.4 us
-            // in row order; a march of fewer than 3 planes pays its prologue too often, and a single plane - the boundary
-            // launches of the sharded solve - is faster in row order: 7.1 vs 8-14 us)
-            chunks = dia_march_chunks(c, m, D.z0, D.z1, wy, &D.zchunk);
-        }
-        const int64_t gg = (int64_t)chunks * D.tiles_x * D.tiles_y;
-        bool timed2 = false;
-        if (gg > 0 && gg < ((int64_t)1 << 30)) {
-            const int wgs = (int)gg;
-            if (nparts_out) *nparts_out = wgs;
-            if (dot) PGD_TRY(ensure_partials(c, std::max<int64_t>(c->partials_off + (D.qq ? 2 : 1) * (int64_t)wgs, 4 * MAX_VEC_BLOCKS)));
-            D.partials = c->partials + c->partials_off;
-            PGD_TRY(prof_begin(c, dot, store, &timed2));
-#define PGD_MARCH(WY)                                                                                  \
-    do {                                                                                               \
-        if (dot && store) k_spmv_dia_march<true, true, WY><<<wgs, 64 * WY, 0, c->stream>>>(D);         \
-        else if (dot) k_spmv_dia_march<true, false, WY><<<wgs, 64 * WY, 0, c->stream>>>(D);            \
-        else k_spmv_dia_march<false, true, WY><<<wgs, 64 * WY, 0, c->stream>>>(D);                     \
-    } while (0)
-            bool coded = c->spmv_variant == 0 && c->spmv_classes && a->cls_count > 0;
-            int wgs_c = wgs, zchunk_c = D.zchunk;
-            if (coded && c->spmv_zchunk_force <= 0) {
-                // the coded march is unrolled six (three) planes at a time and its steps are light: longer marches (fewer halo planes
-                // and prologues per row; 256^3: 24 planes 81 us, 12 planes 89 us, 6 planes 103 us), in whole sixes (threes)
-                const int64_t tile_planes = (int64_t)D.tiles_x * D.tiles_y * (D.z1 - D.z0);
-                // (about one workgroup per CU is enough for this kernel - 128^3: marches of 18 planes = 256 workgroups 61.6 passes/s of
-                // cfg3, 12 planes 59.9, 3 planes (four workgroups per CU, the rule of the plain march) 55.7, 24 planes 58.4)
-                zchunk_c = (int)std::min<int64_t>(c->spmv_zchunk_coded, (tile_planes + c->num_cu / 2) / (int64_t)c->num_cu);
-                zchunk_c = zchunk_c >= 9 ? std::max(12, (zchunk_c + 3) / 6 * 6) : std::max(3, zchunk_c / 3 * 3);
-                // Large grids: a CU holds TWO of these workgroups (246 VGPRs), so with marches of 24 planes 256^3 is 1408 workgroups on
-                // 512 slots - 2.75 rounds, the last one three quarters empty, and eleven prologues per column.  Where there is work for
-                // at least 24 planes per slot the march is as long as it takes to fill every slot exactly once: 256^3 = 4 marches of 66
-                // planes = 512 workgroups, 71 -> 63 us per product (8.87 -> 9.15 passes/s; one workgroup per CU - marches of 126 planes -
-                // 102 us; 36 planes 68 us, 48 planes 72 us: `PGD_TUNE=21=...` before this rule)
-                // (slabs of the sharded solve, tools/bench_coded_march.py 256x256xNZ: 32 planes 21.0 -> 17.9 us with 4 marches of 9,
-                // 64 planes 29.9 -> 25.5 us with 4 of 18, 128 planes 41 us with 4 of 36 against 45-46 us with 18 or 24: the rule holds
-                // from about 8 planes per slot on; marches under 12 planes run three steps at a time)
-                const int64_t per_slot2 = (tile_planes + c->num_cu) / (2 * (int64_t)c->num_cu);
-                if (c->spmv_zchunk_coded2 > 0 && per_slot2 >= 8)
-                    zchunk_c = (int)std::min<int64_t>(c->spmv_zchunk_coded2, per_slot2 >= 12 ? (per_slot2 + 5) / 6 * 6 : (per_slot2 + 2) / 3 * 3);
-                wgs_c = (D.z1 - D.z0 + zchunk_c - 1) / zchunk_c * D.tiles_x * D.tiles_y;
-            }
-            coded = coded && zchunk_c <= DIAC_MAXCHUNK;
-            // one stencil + eliminated nodes (dia_classify verified every row of the planes this launch reads couplings of: its
-            // own and the plane below its first): couplings in scalar registers, four rows per thread, no table
-            // (tests force the march onto small grids with PGD_TUNE_SPMV_ZCHUNK_FORCE, which selects the dictionary kernel - unless
-            // PGD_TUNE_SPMV_ZCHUNK_STENCIL names a march length for this one)
-            // Every plane the launch READS - its own and one halo plane either way - must be a verified plane or lie outside the grid
-            // (the kernel stages what is outside the verified planes as zeros: right for the rim of the grid, wrong for a ghost plane
-            // of a sharded slab, whose rows hold the neighbour rank's x)
-            // (... or a ghost plane whose eliminated nodes are the main planes': staged as data, k_stencil_ghost)
-            const bool st_lower = D.z0 == 0 ? a->st_z0 == 0 : (D.z0 - 1 >= a->st_z0 || (D.z0 == a->st_z0 && a->st_g_lo));
-            const bool st_upper = D.z1 == D.nz ? a->st_z1 == D.nz : (D.z1 + 1 <= a->st_z1 || (D.z1 == a->st_z1 && a->st_g_hi));
-            if (coded && c->spmv_stencil && a->st_ok && (c->spmv_zchunk_force <= 0 || c->spmv_zchunk_stencil > 0) && st_lower && st_upper &&
-                plane < ((int64_t)1 << 26)) {
-                StencilArgs F;
-                F.cls = a->cls; F.ident = a->st_ident; F.x = x; F.y = y; F.flags = flags;
-                F.zv0 = a->st_z0; F.zv1 = a->st_z1; F.zm0 = a->st_zm0; F.zm1 = a->st_zm1;
-                F.zs0 = a->st_zm0 - (a->st_g_lo ? 1 : 0); F.zs1 = a->st_zm1 + (a->st_g_hi ? 1 : 0);
-                for (int s2 = 0; s2 < 8; ++s2) F.c[s2] = a->st_c[s2];
-                F.nx = D.nx; F.ny = D.ny; F.nz = D.nz; F.z0 = D.z0; F.z1 = D.z1; F.tiles_x = D.tiles_x; F.tiles_y = (D.ny + 15) / 16;
-                const int depth = c->stencil_depth > 0 ? c->stencil_depth : 3;      // (six plane fetches in flight: no faster, 60 registers more)
-                const StencilShape sh = stencil_shape(c, D.nx, D.ny, D.z1 - D.z0, depth);
-                const int rows_per_thread = sh.rows_per_thread;
-                F.tiles_y = sh.tiles_y;
-                F.qq = D.qq;
-                F.whatif = 0;
-                F.b = nullptr; F.w = 0.0;
-#if defined(PGD_STENCIL_TIMING) || defined(PGD_STENCIL_WHATIF)
-                if (const char *wi = getenv("PGD_STENCIL_WHATIF")) F.whatif = atoi(wi);
-#endif
-                const bool nty = D.qq && c->pcg_stream_hints;
-                F.zchunk = sh.zchunk;
-                const int wgs_s = sh.wgs;
-                if (nparts_out) *nparts_out = wgs_s;
-                if (dot) PGD_TRY(ensure_partials(c, std::max<int64_t>(c->partials_off + (D.qq ? 2 : 1) * (int64_t)wgs_s, 4 * MAX_VEC_BLOCKS)));
-                F.partials = c->partials + c->partials_off;
-#define PGD_STENCIL(DD, OC)                                                                                   \
-    do {                                                                                                      \
-        if (dot && store && nty) k_spmv_stencil_march<true, true, DD, true, OC><<<wgs_s, 256, 0, c->stream>>>(F);      \
-        else if (dot && store) k_spmv_stencil_march<true, true, DD, false, OC><<<wgs_s, 256, 0, c->stream>>>(F);       \
-        else if (dot) k_spmv_stencil_march<true, false, DD, false, OC><<<wgs_s, 256, 0, c->stream>>>(F);               \
-        else k_spmv_stencil_march<false, true, DD, false, OC><<<wgs_s, 256, 0, c->stream>>>(F);                        \
-    } while (0)
-                if (rows_per_thread == 2 && depth != 6) {
-                    if (dot && store && nty) k_spmv_stencil_march<true, true, 3, true, 2, 0, 2><<<wgs_s, 256, 0, c->stream>>>(F);
-                    else if (dot && store) k_spmv_stencil_march<true, true, 3, false, 2, 0, 2><<<wgs_s, 256, 0, c->stream>>>(F);
-                    else if (dot) k_spmv_stencil_march<true, false, 3, false, 2, 0, 2><<<wgs_s, 256, 0, c->stream>>>(F);
-                    else k_spmv_stencil_march<false, true, 3, false, 2, 0, 2><<<wgs_s, 256, 0, c->stream>>>(F);
-                } else if (depth == 6) PGD_STENCIL(6, 2); else PGD_STENCIL(3, 2);
-#undef PGD_STENCIL
-                c->kcount[KC_STENCIL_MARCH] += 1;
-                if (timed2) PGD_TRY(prof_end(c, m, nrows, store ? 16.0 : 8.0));
-                PGD_LAUNCH_CHECK(c);
-                return PGD_OK;
-            }
-            PGD_TRY(not_virtual());
-            if (coded) {
-                // the operator has a row-class dictionary (dia_classify): one byte per row instead of the slot values
-                DiacArgs E;
-                E.cls = a->cls; E.same = a->cls_same; E.table = a->cls_table; E.ncls = a->cls_count; E.x = x; E.y = y; E.partials = D.partials; E.flags = flags;
-                E.nx = D.nx; E.ny = D.ny; E.nz = D.nz; E.z0 = D.z0; E.z1 = D.z1; E.zchunk = zchunk_c; E.tiles_x = D.tiles_x; E.tiles_y = D.tiles_y;
-                E.qq = D.qq;
-                E.nt_y = (D.qq && c->pcg_stream_hints) ? 1 : 0;      // the PCG's q: read once, by the vector update (+ 1 %)
-                if (nparts_out) *nparts_out = wgs_c;
-                if (dot) PGD_TRY(ensure_partials(c, std::max<int64_t>(c->partials_off + (D.qq ? 2 : 1) * (int64_t)wgs_c, 4 * MAX_VEC_BLOCKS)));
-                E.partials = c->partials + c->partials_off;
-                // six plane fetches in flight where the march is long enough to run in sixes (a light kernel is paced by the bytes
-                // a CU keeps in flight), three otherwise
-                const bool six = zchunk_c >= 12 && zchunk_c % 6 == 0 && c->spmv_fetch_depth != 3;
-#define PGD_DIAC(DD)                                                                                       \
-    do {                                                                                                   \
-        if (dot && store && E.nt_y) k_spmv_diac_march2<true, true, DD, true><<<wgs_c, 256, 0, c->stream>>>(E);   \
-        else if (dot && store) k_spmv_diac_march2<true, true, DD, false><<<wgs_c, 256, 0, c->stream>>>(E);       \
-        else if (dot) k_spmv_diac_march2<true, false, DD, false><<<wgs_c, 256, 0, c->stream>>>(E);               \
-        else k_spmv_diac_march2<false, true, DD, false><<<wgs_c, 256, 0, c->stream>>>(E);                        \
-    } while (0)
-                if (six) PGD_DIAC(6); else PGD_DIAC(3);
-#undef PGD_DIAC
-                c->kcount[KC_DIAC_MARCH] += 1;
-                if (timed2) PGD_TRY(prof_end(c, m, nrows, 17.0));
-                PGD_LAUNCH_CHECK(c);
-                return PGD_OK;
-            }
-            if (c->spmv_variant == 0 && c->dia_march3 && (int64_t)64 * D.n < ((int64_t)1 << 31) && plane < ((int64_t)1 << 27)) {
-                if (dot && store) k_spmv_dia_march3<true, true><<<wgs, 256, 0, c->stream>>>(D);
-                else if (dot) k_spmv_dia_march3<true, false><<<wgs, 256, 0, c->stream>>>(D);
-                else k_spmv_dia_march3<false, true><<<wgs, 256, 0, c->stream>>>(D);
-            } else if (c->spmv_variant == 0) {
-                if (dot && store) k_spmv_dia_march2<true, true><<<wgs, 256, 0, c->stream>>>(D);
-                else if (dot) k_spmv_dia_march2<true, false><<<wgs, 256, 0, c->stream>>>(D);
-                else k_spmv_dia_march2<false, true><<<wgs, 256, 0, c->stream>>>(D);
-            } else if (wy == 8) PGD_MARCH(8); else PGD_MARCH(4);
-#undef PGD_MARCH
-            c->kcount[KC_DIA_MARCH] += 1;
-        } else {
-            PGD_TRY(not_virtual());
-            PGD_TRY(prof_begin(c, dot, store, &timed2));
-            if (dot && store) k_spmv_dia_rows<true, true><<<nblk, 64, 0, c->stream>>>(D);
-            else if (dot) k_spmv_dia_rows<true, false><<<nblk, 64, 0, c->stream>>>(D);
-            else k_spmv_dia_rows<false, true><<<nblk, 64, 0, c->stream>>>(D);
-            c->kcount[KC_DIA_ROWS] += 1;
-        }
-        if (timed2) PGD_TRY(prof_end(c, m, nrows, 8.0 * (D.unit_diag ? 7 : 8) + 16));
-        PGD_LAUNCH_CHECK(c);
-        return PGD_OK;
+    const ProductPlan P = plan_product(c, m, a, r0, r1, !dot || w == x);
+    if (nparts_out) *nparts_out = P.wgs;
+    if (P.nblk == 0) return PGD_OK;
+    const ProductCall k = {x, y, w, r0, r1, dot, store, flags, (dot && c->spmv_qq) ? 1 : 0};
+    // partial sums: room for two per block of 64 rows whatever the form (the row kernels leave them), a pair per workgroup of a march
+    if (dot) PGD_TRY(ensure_partials(c, std::max<int64_t>(c->partials_off + 2 * (int64_t)std::max(P.nblk, P.wgs), 4 * MAX_VEC_BLOCKS)));
+    PGD_TRY(not_virtual(P.form == KC_STENCIL_MARCH));
+    switch (P.form) {
+    case KC_STENCIL_MARCH: return launch_product_stencil(c, m, a, P, k);
+    case KC_DIAC_MARCH: return launch_product_diac(c, m, a, P, k);
+    case KC_DIA_MARCH:
+    case KC_DIA_ROWS: return launch_product_dia(c, m, a, P, k);
+    default: return launch_product_sym(c, m, a, P, k);
     }
-    PGD_TRY(not_virtual());
-    const int grid = nblk;
-    bool timed = false;
-    PGD_TRY(prof_begin(c, dot, store, &timed));
-#define PGD_SYM_LAUNCH(D, S)                                                          \
-    do {                                                                              \
-        if (m->sym_w == 4) k_spmv_sym<D, S, 4><<<grid, 64, 0, c->stream>>>(A);        \
-        else k_spmv_sym<D, S, 8><<<grid, 64, 0, c->stream>>>(A);                      \
-    } while (0)
-    if (dot && store) PGD_SYM_LAUNCH(true, true);
-    else if (dot) PGD_SYM_LAUNCH(true, false);
-    else PGD_SYM_LAUNCH(false, true);
-#undef PGD_SYM_LAUNCH
-    c->kcount[KC_SYM_ROWS] += 1;
-    if (timed) PGD_TRY(prof_end(c, m, nrows, 8.0 * m->sym_w + 18));
-    PGD_LAUNCH_CHECK(c);
-    return PGD_OK;
 }
 
 // The update of the single-sync recurrence with A p formed again instead of read (EPI 3 of the stencil march): the product's own march over
 // p_in - same patches, staging and chains, so the q of every row is the one the product summed its dots from, bit for bit - with three
-// plane fetches in flight whatever the product uses (its registers go to r, x and s).  The shape depends on the grid and the knobs only.
-int stencil_update_blocks(const Ctx *c, const Mesh *m) {
-    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
-    return stencil_shape(c, m->sym_nx, m->sym_ny, (int)(m->nv / plane), 3).wgs;
-}
+// plane fetches in flight whatever the product uses (its registers go to r, x and s): the product's plan at depth 3.
+static ProductPlan plan_stencil_update(const Ctx *c, const Mesh *m, const Csr *a) { return plan_product(c, m, a, 0, m->nv, true, 3); }
+
+int stencil_update_blocks(const Ctx *c, const Mesh *m, const Csr *a) { return plan_stencil_update(c, m, a).wgs; }
 
 int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, double *r, const double *s,
                           double *pairs, int lag, double s_free, const StencilFold *fold) {
-    if (!stencil_whole_grid(c, m, a) || !c->flags || p_in == p_out || (fold && (fold->vec_in == pairs || !fold->prod || !fold->vec_in)))
+    const ProductPlan P = plan_stencil_update(c, m, a);
+    if (P.form != KC_STENCIL_MARCH || !c->flags || p_in == p_out || (fold && (fold->vec_in == pairs || !fold->prod || !fold->vec_in)))
         return fail(c, PGD_ERR_INVALID, "stencil update: the operator's products do not run in the stencil march over the whole grid");
-    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
-    const int nz = (int)(m->nv / plane);
-    const StencilShape sh = stencil_shape(c, m->sym_nx, m->sym_ny, nz, 3);
     StencilArgs F;
-    F.cls = a->cls; F.ident = a->st_ident; F.x = p_in; F.y = p_out; F.flags = c->flags;
-    F.zv0 = a->st_z0; F.zv1 = a->st_z1; F.zm0 = a->st_zm0; F.zm1 = a->st_zm1;
-    F.zs0 = a->st_zm0 - (a->st_g_lo ? 1 : 0); F.zs1 = a->st_zm1 + (a->st_g_hi ? 1 : 0);
-    for (int s2 = 0; s2 < 8; ++s2) F.c[s2] = a->st_c[s2];
-    F.nx = m->sym_nx; F.ny = m->sym_ny; F.nz = nz; F.z0 = 0; F.z1 = nz;
-    F.tiles_x = sh.tiles_x; F.tiles_y = sh.tiles_y; F.zchunk = sh.zchunk;
-    F.qq = 1; F.whatif = 0; F.b = nullptr; F.w = 0.0;
+    stencil_args(F, c, m, a, P, p_in, p_out);
+    F.qq = 1;
     F.partials = pairs;
     F.ur = r; F.ux = x; F.us = s; F.slots = c->slots; F.lag = lag;
     F.s_free = s_free;
@@ -3087,12 +2957,10 @@ int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_i
         F.fold_prod = fold->prod; F.fold_nprod = fold->nprod; F.fold_vec = fold->vec_in; F.fold_nvec = fold->nvec;
         F.fold_par = fold->par & 1; F.fold_flags = c->flags;
     }
-    const bool nt = c->pcg_stream_hints != 0;
-    if (sh.rows_per_thread == 2) {
-        if (nt) k_spmv_stencil_march<true, true, 3, true, 2, 3, 2><<<sh.wgs, 256, 0, c->stream>>>(F);
-        else k_spmv_stencil_march<true, true, 3, false, 2, 3, 2><<<sh.wgs, 256, 0, c->stream>>>(F);
-    } else if (nt) k_spmv_stencil_march<true, true, 3, true, 2, 3><<<sh.wgs, 256, 0, c->stream>>>(F);
-    else k_spmv_stencil_march<true, true, 3, false, 2, 3><<<sh.wgs, 256, 0, c->stream>>>(F);
+    with_product_kind(true, true, c->pcg_stream_hints != 0, [&](auto, auto, auto NT) {
+        if (P.rows_per_thread == 2) k_spmv_stencil_march<true, true, 3, NT.value, 2, 3, 2><<<P.wgs, 256, 0, c->stream>>>(F);
+        else k_spmv_stencil_march<true, true, 3, NT.value, 2, 3><<<P.wgs, 256, 0, c->stream>>>(F);
+    });
     c->pcg_recompute_launches += 1;
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
@@ -3100,42 +2968,32 @@ int launch_stencil_update(Ctx *c, const Mesh *m, const Csr *a, const double *p_i
 
 // The same update with the dot-only product of the direction it writes in the same march (k_pcg1_fused_march).  Its workgroups leave
 // the product's pairs where the product launch would: that launch must have the update's shape - it has, unless the fetch depth of the
-// product (PGD_TUNE_STENCIL_DEPTH) gives it longer marches - and the whole grid must be main or identity planes, no ghost plane.
+// product (PGD_TUNE_STENCIL_DEPTH) gives it longer marches or another kernel - and the whole grid must be main or identity planes, no
+// ghost plane.
 bool stencil_fused_ok(const Ctx *c, const Mesh *m, const Csr *a) {
-    if (!stencil_whole_grid(c, m, a) || a->st_g_lo || a->st_g_hi) return false;
-    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
-    const int nz = (int)(m->nv / plane);
-    const StencilShape su = stencil_shape(c, m->sym_nx, m->sym_ny, nz, 3), sp = stencil_shape(c, m->sym_nx, m->sym_ny, nz, c->stencil_depth > 0 ? c->stencil_depth : 3);
-    return su.wgs == sp.wgs && su.zchunk == sp.zchunk && su.rows_per_thread == sp.rows_per_thread && su.tiles_y == sp.tiles_y &&
-           (sp.rows_per_thread == 4 || c->stencil_depth != 6);
+    const ProductPlan u = plan_stencil_update(c, m, a), p = plan_product(c, m, a, 0, m->nv, true);
+    return u.form == KC_STENCIL_MARCH && !a->st_g_lo && !a->st_g_hi && u.wgs == p.wgs && u.zchunk == p.zchunk &&
+           u.rows_per_thread == p.rows_per_thread && u.tiles_y == p.tiles_y;
 }
 
 int launch_stencil_fused(Ctx *c, const Mesh *m, const Csr *a, const double *p_in, double *p_out, double *x, const double *r_in, double *r_out,
                          const double *s, double *pairs, int lag, double s_free) {
     if (!stencil_fused_ok(c, m, a) || !c->flags || p_in == p_out || r_in == r_out)
         return fail(c, PGD_ERR_INVALID, "fused march: the operator's products do not run in the stencil march over the whole grid");
-    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
-    const int nz = (int)(m->nv / plane);
-    const StencilShape sh = stencil_shape(c, m->sym_nx, m->sym_ny, nz, 3);
-    PGD_TRY(ensure_partials(c, std::max<int64_t>(c->partials_off + 2 * (int64_t)sh.wgs, 4 * MAX_VEC_BLOCKS)));
+    const ProductPlan P = plan_stencil_update(c, m, a);
+    PGD_TRY(ensure_partials(c, std::max<int64_t>(c->partials_off + 2 * (int64_t)P.wgs, 4 * MAX_VEC_BLOCKS)));
     FusedArgs F;
-    F.cls = a->cls; F.ident = a->st_ident; F.x = p_in; F.y = p_out; F.flags = c->flags;
-    F.zv0 = a->st_z0; F.zv1 = a->st_z1; F.zm0 = a->st_zm0; F.zm1 = a->st_zm1;
-    F.zs0 = a->st_zm0; F.zs1 = a->st_zm1;
-    for (int s2 = 0; s2 < 8; ++s2) F.c[s2] = a->st_c[s2];
-    F.nx = m->sym_nx; F.ny = m->sym_ny; F.nz = nz; F.z0 = 0; F.z1 = nz;
-    F.tiles_x = sh.tiles_x; F.tiles_y = sh.tiles_y; F.zchunk = sh.zchunk;
-    F.qq = 1; F.whatif = 0; F.b = nullptr; F.w = 0.0;
+    stencil_args(F, c, m, a, P, p_in, p_out);
+    F.zs0 = a->st_zm0; F.zs1 = a->st_zm1;       // no ghost planes (stencil_fused_ok): the main run only
+    F.qq = 1;
     F.partials = pairs;
     F.prod_pairs = c->partials + c->partials_off;
     F.ur = const_cast<double *>(r_in); F.ur_out = r_out; F.ux = x; F.us = s; F.slots = c->slots; F.lag = lag;
     F.s_free = s_free;
-    const bool nt = c->pcg_stream_hints != 0;
-    if (sh.rows_per_thread == 2) {
-        if (nt) k_pcg1_fused_march<true, 2><<<sh.wgs, 256, 0, c->stream>>>(F);
-        else k_pcg1_fused_march<false, 2><<<sh.wgs, 256, 0, c->stream>>>(F);
-    } else if (nt) k_pcg1_fused_march<true, 4><<<sh.wgs, 256, 0, c->stream>>>(F);
-    else k_pcg1_fused_march<false, 4><<<sh.wgs, 256, 0, c->stream>>>(F);
+    with_product_kind(true, true, c->pcg_stream_hints != 0, [&](auto, auto, auto NT) {
+        if (P.rows_per_thread == 2) k_pcg1_fused_march<NT.value, 2><<<P.wgs, 256, 0, c->stream>>>(F);
+        else k_pcg1_fused_march<NT.value, 4><<<P.wgs, 256, 0, c->stream>>>(F);
+    });
     c->pcg_recompute_launches += 1;
     c->pcg_fused_launches += 1;
     c->kcount[KC_STENCIL_MARCH] += 1;
@@ -3464,6 +3322,19 @@ int pgd_atom_product_form(pgd_handle h, pgd_handle ah, int *form) {
     if (!a || !m || !form) return fail(c, PGD_ERR_INVALID, "atom_product_form: invalid handle");
     *form = 0;
     if (atom_fast_form(c, m, a, 0, m->nv)) *form = a->cls_count > 0 ? 2 : 1;
+    return PGD_OK;
+}
+
+int pgd_product_plan(pgd_handle h, pgd_handle ah, int64_t r0, int64_t r1, int pcg_like, int64_t *out, int n) {
+    PGD_CTX(c, h);
+    Csr *a = get_csr(c, ah);
+    Mesh *m = a ? get_mesh(c, a->mesh) : nullptr;
+    if (!a || !m || !out || n < 7) return fail(c, PGD_ERR_INVALID, "product_plan: invalid handle or fewer than 7 fields");
+    if (r1 < 0) r1 = m->nv;
+    if (r0 < 0 || r0 > r1 || r1 > m->nv) return fail(c, PGD_ERR_INVALID, "product_plan: bad row range");
+    const ProductPlan P = plan_product(c, m, a, r0, r1, pcg_like != 0);
+    const int64_t f[7] = {P.form, P.wgs, P.zchunk, P.tiles_x, P.tiles_y, P.rows_per_thread, P.depth};
+    std::copy(f, f + 7, out);
     return PGD_OK;
 }
 

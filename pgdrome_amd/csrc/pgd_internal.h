@@ -94,18 +94,22 @@ struct Mesh : Obj {
     int pat_off[6][4] = {{0}};    // vertex offsets of tetrahedron t relative to its cube's first vertex
     int pat_loc[6][8] = {{0}};    // local index of cube corner (dx + 2 dy + 4 dz) in tetrahedron t, -1: not a vertex of it
     double lat_h[3] = {0.0, 0.0, 0.0};
-    // What dia_classify learned about operators on this mesh (pgd_spmv.hip): the class CODES of an operator depend on its atoms'
+    // What dia_classify learned about operators on this mesh (pgd_classify.hip): the class CODES of an operator depend on its atoms'
     // structure and its Dirichlet set, not on the coefficients it is combined with - every solve of a fixed-point pass classifies
     // "the same operator with other numbers".  A later classification with the same signature copies the codes, rebuilds the class
     // table from the representative rows and VERIFIES every row against its class bit by bit (+ the class-level stencil relations):
     // one pass over the slot values instead of three with hashing; any mismatch falls back to the full classification.
+    // An entry owns ONE device allocation, `block`; same, reps and codes are views into it (cls_cache_alloc).  Entries are
+    // copied around inside the vector: no destructor, whoever removes one calls release()
     struct ClsCache {
         uint64_t sig = 0; int scaled = 0, z_lo = 0, z_hi = 0, ncls = 0;
-        uint8_t *codes = nullptr; int *same = nullptr; int *reps = nullptr; size_t bytes = 0;
+        void *block = nullptr;
+        uint8_t *codes = nullptr; int *same = nullptr; int *reps = nullptr;
         bool st_ok = false; int ident = -1, base = -1, zm0 = 0, zm1 = 0;
         uint8_t zero_pat[256];      // per class: bit s = slot s is an exact zero (a coupling to an eliminated node / the rim)
         uint8_t in_range[256];      // per class: it occurs on the verified planes [z_lo, z_hi) (a slab's ghost rows carry classes of their own)
-        uint64_t used = 0;
+        uint64_t used = 0;          // Mesh::cls_clock at its last use: the least recently used entry makes room
+        void release() { if (block) (void)hipFree(block); block = nullptr; codes = nullptr; same = reps = nullptr; }
     };
     mutable std::vector<ClsCache> cls_cache;
     mutable uint64_t cls_clock = 0;
@@ -134,7 +138,7 @@ struct Mesh : Obj {
         for (void *p : {(void *)coords, (void *)cells, (void *)cellsN, (void *)v2c_ptr, (void *)v2c,
                         (void *)row_ptr, (void *)cols, (void *)pids, (void *)dict_off, (void *)sym_tab, (void *)p2_par, (void *)p2_v2e})
             if (p) (void)hipFree(p);
-        for (ClsCache &e : cls_cache) if (e.same) (void)hipFree(e.same);      // (the block starts at `same`)
+        for (ClsCache &e : cls_cache) e.release();
         if (bc_dev) (void)hipFree(bc_dev);
     }
 };
@@ -152,8 +156,8 @@ struct Csr : Obj {
     bool uvals_scaled = false;  // the slot arrays hold D^-1/2 A D^-1/2 (inside pgd_pcg_solve only)
     bool uvals_unit = false;    // ... in diagonal form, whose slot 0 is exactly 1 and is not loaded by the products
     int64_t uvals_stride = 0;  // doubles between two slot arrays (rows + padding)
-    // row-class dictionary of the CURRENT slot values in diagonal form (dia_classify, pgd_spmv.hip): a code per row and
-    // the classes' slot tuples; cls_count = 0: none (every writer of the slot arrays resets it)
+    // row-class dictionary of the CURRENT slot values in diagonal form (dia_classify, pgd_classify.hip): a code per row and
+    // the classes' slot tuples; cls_count = 0: none (every writer of the slot arrays calls drop_classes)
     uint8_t *cls = nullptr;
     int *cls_same = nullptr;       // per plane: same codes, row by row, as the plane below
     double *cls_table = nullptr;   // owns the allocation: table, then the codes
@@ -165,6 +169,7 @@ struct Csr : Obj {
     int st_ident = -1, st_z0 = 0, st_z1 = 0, st_zm0 = 0, st_zm1 = 0;   // (st_zm0 .. st_zm1: the run of planes with identical codes; the rest of the verified planes hold identity rows only)
     double st_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool st_g_lo = false, st_g_hi = false;   // the plane below st_z0 / above st_z1 - 1 is a ghost DATA plane of a sharded slab (k_stencil_ghost)
+    void drop_classes() { cls_count = 0; st_ok = false; st_g_lo = st_g_hi = false; }   // the slot values changed: no dictionary, no stencil
     bool st_virtual = false;       // st_c holds the couplings of D^-1/2 A D^-1/2 while slots, table and CSR values hold A (pgd_pcg_solve)
     bool cls_tried = false;        // atoms: the dictionary was looked for once for the current slot values (atom_fast_form)
     bool immutable = false;        // an ATOM (assembled / uploaded / embedded): its values change only through pgd_atom_embed(dst)
@@ -480,7 +485,12 @@ int vec_sqrt(Ctx *c, double *v, int64_t n);
 int vec_div_mul(Ctx *c, double *x, const double *sc, int64_t n, int mul);
 int ensure_vals(Ctx *c, const Mesh *m, Csr *a);                 // pgd_pcg.hip: CSR values of an operator whose combine was deferred
 bool atom_fast_form(Ctx *c, const Mesh *m, Csr *a, int64_t r0, int64_t r1);   // pgd_spmv.hip
-// pgd_spmv.hip: row-class dictionary of the current slot values (+ its stencil form, verified on the planes [zlo, zhi) - whole grid: -1)
+// pgd_classify.hip: row-class dictionary of the current slot values (+ its stencil form, verified on the planes [zlo, zhi) - whole grid: -1)
+// A table row holds a class's slot values as [s1 s5 | s3 s7 | s2 s6 | s4 s0] (why: k_spmv_diac_march2, pgd_spmv.hip)
+constexpr int CLS_MAX = 255;             // classes per operator (+ the zero class = 256 table rows of 64 B)
+__host__ __device__ constexpr int cls_pos(int s) {      // position of slot s in a table row
+    return s == 1 ? 0 : s == 5 ? 1 : s == 3 ? 2 : s == 7 ? 3 : s == 2 ? 4 : s == 6 ? 5 : s == 4 ? 6 : 7;
+}
 int dia_classify(Ctx *c, const Mesh *m, Csr *a, int zrange_lo = -1, int zrange_hi = -1);
 bool stencil_row_range(const Ctx *c, const Mesh *m, const Csr *a, int64_t r0, int64_t r1);   // ... over the whole planes [r0, r1) of a slab
 bool stencil_whole_grid(const Ctx *c, const Mesh *m, const Csr *a);   // pgd_spmv.hip: a product over all rows would run in k_spmv_stencil_march

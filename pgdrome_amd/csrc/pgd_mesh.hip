@@ -1447,7 +1447,7 @@ int pgd_atom_embed(pgd_handle h, pgd_handle bmh, pgd_handle src, int cv, int cu,
     }
     PGD_TRY(ensure_vals(c, m, a));
     d->version += 1;           // new values: forms derived from the old ones are gone
-    d->uvals_valid = false; d->uvals_scaled = false; d->cls_count = 0; d->cls_tried = false; d->dinv_valid = false;
+    d->uvals_valid = false; d->uvals_scaled = false; d->drop_classes(); d->cls_tried = false; d->dinv_valid = false;
     k_block_embed<<<(int)((m->nv + TPB - 1) / TPB), TPB, 0, c->stream>>>(m->row_ptr, a->vals, m->nv, b->ncomp, cv, cu, coef, b->row_ptr, d->vals);
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;

@@ -899,8 +899,7 @@ __global__ __launch_bounds__(256) void k_spmv_dia_march3(DiaArgs A) {
 // ------------------------------------------------------------------ diagonal form with a row-class dictionary
 // On a uniform grid with piecewise-constant coefficients the rows of the (scaled) operator repeat a few 8-tuples of slot
 // values: every interior row carries the same one, the rows next to a face, an edge, a corner or a Dirichlet row a few dozen
-// others.  dia_classify() (below) finds them per solve, LOSSLESSLY - the class table holds the slot values bit by bit and
-// every row is compared with its class's tuple before the code is trusted - and the product then streams ONE BYTE per row
+// others.  dia_classify() (pgd_classify.hip) finds them per solve, losslessly, and the product then streams ONE BYTE per row
 // instead of 56: 17 B per row (code + x + y).  The table lives in LDS; a row of it is [s1 s5 | s3 s7 | s2 s6 | s4 s0], so the
 // pairs a neighbour's row contributes - (-1, 0) gives slots 1 and 5, (-1, -1) gives 3 and 7, (0, -1) gives 2 and 6 - are
 // one ds_read_b128 each, and the second value of each pair is the coupling to the plane ABOVE the neighbour, i.e. exactly
@@ -908,12 +907,6 @@ __global__ __launch_bounds__(256) void k_spmv_dia_march3(DiaArgs A) {
 // carried in registers from step to step, nothing of the operator is re-read.  Class id `ncls` is the all-zero row: cells
 // outside the grid carry it, so the boundary needs no predicates (0 * x adds an exact 0, as the masked form does).
 // Same values, same order of the 15 fused multiply-adds per row: bit-identical to k_spmv_dia_march2.
-constexpr int CLS_MAX = 255;             // classes per operator (+ the zero class = 256 table rows of 64 B)
-constexpr int CLS_SLOTS = 1024;          // hash slots of the classification
-__host__ __device__ constexpr int cls_pos(int s) {      // position of slot s in a table row
-    return s == 1 ? 0 : s == 5 ? 1 : s == 3 ? 2 : s == 7 ? 3 : s == 2 ? 4 : s == 6 ? 5 : s == 4 ? 6 : 7;
-}
-
 struct DiacArgs {
     const uint8_t *cls;
     const int *same;        // [nz]: plane z carries, row by row, the codes of plane z - 1 (scalar loads: ints)
@@ -1109,7 +1102,7 @@ __global__ __launch_bounds__(256) void k_spmv_diac_march2(DiacArgs A) {
 }
 
 // ------------------------------------------------------------------ STENCIL form of the row-class dictionary (r03)
-// Where dia_classify finds that the classes of an operator are ONE tuple (c0 .. c7) - the "base class" - plus the rows it
+// Where dia_classify (pgd_classify.hip) finds that the classes of an operator are ONE tuple (c0 .. c7) - the "base class" - plus the rows it
 // becomes next to eliminated (Dirichlet) nodes and next to the rim of the grid, i.e. every coupling a(i, j) is either c_s
 // bit for bit or an exact 0 where j is an identity row or lies outside the grid (k_stencil_verify checks EVERY row of the
 // planes a launch may touch, every slot, bitwise), the product needs no table at all:
@@ -1899,163 +1892,6 @@ __global__ __launch_bounds__(256, 2) void k_pcg1_fused_march(FusedArgs A) {
     }
 }
 
-// Does the dictionary reduce to one stencil?  k_stencil_pick: base class = the class of the row in the middle of the planes
-// [z_lo, z_hi), identity class = the tuple (1, 0 .. 0).  A row's tuple holds only the UPPER half of its row: a free node whose
-// upper neighbours are all eliminated (the last free node before three faces) carries the identity tuple too.  k_stencil_split
-// gives those rows a class id of their own (same tuple, a duplicate table row: the dictionary product does not care), so that
-// "class == identity class" means an eliminated node: every coupling TO it is zero as well.  k_stencil_verify: every row of those
-// planes, every slot, bit for bit.
-struct StencilInfo { int ok, ident, base, split; double c[8]; int zm0, zm1, g_lo, g_hi; };     // g_lo / g_hi: the plane below / above the verified planes is a ghost DATA plane (k_stencil_ghost)
-
-__global__ void k_stencil_pick(const uint8_t *__restrict__ cls, double *__restrict__ table, const int *__restrict__ info,
-                               int nx, int ny, int z_lo, int z_hi, StencilInfo *S) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    S->ok = 0; S->ident = -1; S->base = -1; S->split = 0;
-    const int ncls = info[0];
-    if (info[1] != 0 || ncls <= 0 || ncls >= CLS_MAX || z_hi <= z_lo) return;      // (room for one more class id)
-    const int64_t mid = (int64_t)nx * ny * ((z_lo + z_hi) / 2) + (int64_t)nx * (ny / 2) + nx / 2;
-    for (int k = 0; k < ncls; ++k) {
-        bool id = table[k * 8 + cls_pos(0)] == 1.0;
-        for (int s = 1; s < 8; ++s) id = id && table[k * 8 + cls_pos(s)] == 0.0;
-        if (id) S->ident = k;
-    }
-    // base class: the tuple with the most couplings (the row in the middle of a thin grid sits next to a face); the middle row's on ties
-    int base = cls[mid], best = -1;
-    for (int k = 0; k < ncls; ++k) {
-        int nzc = 0;
-        for (int s = 1; s < 8; ++s) nzc += table[k * 8 + cls_pos(s)] != 0.0 ? 1 : 0;
-        if (nzc > best || (nzc == best && k == (int)cls[mid])) { best = nzc; base = k; }
-    }
-    if (base == S->ident) return;                            // (nothing but identity rows: keep the dictionary form)
-    S->base = base;
-    for (int s = 0; s < 8; ++s) S->c[s] = table[base * 8 + cls_pos(s)];
-    if (S->ident >= 0) {                                     // the duplicate row of the free nodes with the identity tuple, then the zero class
-        for (int s = 0; s < 8; ++s) { table[ncls * 8 + s] = table[S->ident * 8 + s]; table[(ncls + 1) * 8 + s] = 0.0; }
-    }
-    S->ok = 1;
-}
-
-__global__ __launch_bounds__(TPB) void k_stencil_split(uint8_t *__restrict__ cls, const double *__restrict__ table, const int *__restrict__ info,
-                                                       int nx, int ny, int64_t nv, StencilInfo *S) {
-    if (!S->ok || S->ident < 0) return;
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= nv || (int)cls[i] != S->ident) return;
-    const int64_t P = (int64_t)nx * ny;
-    const int z = (int)(i / P), rem = (int)(i - (int64_t)z * P), y = rem / nx, x = rem - y * nx;
-    bool coupled = false;
-#pragma unroll
-    for (int s = 1; s < 8; ++s) {                            // the lower neighbour whose slot s points at this row
-        const int dx = s & 1, dy = (s >> 1) & 1, dz = s >> 2;
-        if (x - dx < 0 || y - dy < 0 || z - dz < 0) continue;
-        const int kc = cls[i - dx - (int64_t)nx * dy - P * dz];      // (a neighbour re-coded meanwhile carries the same tuple)
-        coupled = coupled || table[kc * 8 + cls_pos(s)] != 0.0;
-    }
-    if (coupled) { cls[i] = (uint8_t)info[0]; S->split = 1; }
-}
-
-__global__ void k_stencil_commit(double *__restrict__ table, int *__restrict__ info, StencilInfo *S) {
-    if (threadIdx.x != 0 || blockIdx.x != 0 || !S->ok || S->ident < 0) return;
-    const int n = info[0];
-    if (S->split) info[0] = n + 1;                           // one more class; its zero class sits behind it
-    else for (int s = 0; s < 8; ++s) table[n * 8 + s] = 0.0;      // unused: row n is the zero class again
-}
-
-// allid[z] = 1 iff plane z holds identity rows only; samem[z] = 1 iff the identity rows of plane z sit where those of plane z - 1 do
-__global__ __launch_bounds__(TPB) void k_stencil_allid(const uint8_t *__restrict__ cls, int64_t plane, const StencilInfo *S, int *__restrict__ allid,
-                                                       int *__restrict__ samem) {
-    __shared__ int s_other, s_diff;
-    const int z = blockIdx.x;
-    if (threadIdx.x == 0) { s_other = 0; s_diff = 0; }
-    __syncthreads();
-    const uint8_t *a = cls + plane * z;
-    const int ident = S->ident;
-    bool other = false, diff = z == 0;
-    for (int64_t i = threadIdx.x; i < plane; i += TPB) {
-        const bool id = (int)a[i] == ident;
-        other = other || !id;
-        if (z > 0) diff = diff || id != ((int)a[i - plane] == ident);
-    }
-    if (other) s_other = 1;
-    if (diff) s_diff = 1;
-    __syncthreads();
-    if (threadIdx.x == 0) { allid[z] = s_other ? 0 : 1; samem[z] = s_diff ? 0 : 1; }
-}
-
-// the planes of [z_lo, z_hi) must read [identity planes]* [one run of planes with the SAME identity rows] [identity planes]*
-__global__ void k_stencil_planes(const int *__restrict__ same, const int *__restrict__ allid, int z_lo, int z_hi, StencilInfo *S) {
-    if (threadIdx.x != 0 || blockIdx.x != 0 || !S->ok) return;
-    int a = z_lo, b = z_hi;
-    while (a < z_hi && allid[a]) ++a;
-    while (b > a && allid[b - 1]) --b;
-    bool simple = true;
-    for (int z = a; z < b; ++z) simple = simple && !allid[z] && (z == a || same[z] != 0);
-    S->zm0 = a; S->zm1 = b;
-    if (!simple) S->ok = 0;
-}
-
-// A sharded slab's ghost planes: the plane below z_lo (above z_hi - 1) lies inside the array, next to a main plane, and its
-// eliminated nodes are exactly those of the main planes - then the march may stage it like a main plane (its rows hold the
-// neighbour rank's x; couplings to its eliminated nodes are the exact zeros k_stencil_verify found in the owned rows next to it)
-__global__ void k_stencil_ghost_init(StencilInfo *S, int z_lo, int z_hi, int nz, int zm0, int zm1) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (zm0 < 0) { zm0 = S->zm0; zm1 = S->zm1; }
-    S->g_lo = (S->ok && z_lo > 0 && zm0 == z_lo && zm1 > zm0) ? 1 : 0;
-    S->g_hi = (S->ok && z_hi < nz && zm1 == z_hi && zm1 > zm0) ? 1 : 0;
-}
-// The couplings between the LOWER ghost plane and the first owned plane live in the ghost rows' dz = 1 slots (half storage: a
-// row holds its couplings to the rows behind it), which k_stencil_verify - owned rows only - never sees: they are compared here,
-// bitwise, with the stencil's couplings (exact zeros where the target is eliminated or outside), so that the march applies
-// c[s] to the neighbour rank's x on evidence, like everywhere else.  (The upper ghost plane is reached through
-// the owned rows' own dz = 1 slots, which k_stencil_verify has compared.)
-__global__ __launch_bounds__(TPB) void k_stencil_ghost(const uint8_t *__restrict__ cls, const double *__restrict__ table, int nx, int ny,
-                                                       int z_lo, int z_hi, int zm0, StencilInfo *S) {
-    const int64_t plane = (int64_t)nx * ny;
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= plane || !S->ok) return;
-    if (zm0 < 0) zm0 = S->zm0;
-    const int ident = S->ident;
-    const bool id = (int)cls[plane * zm0 + i] == ident;
-    if (S->g_lo) {
-        const int k = cls[plane * (z_lo - 1) + i];
-        bool good = (k == ident) == id;
-        if (good && k != ident) {
-            const int y = (int)(i / nx), x = (int)(i - (int64_t)y * nx);
-            const double *t = table + k * 8;
-#pragma unroll
-            for (int s = 4; s < 8; ++s) {
-                const int dx = s & 1, dy = (s >> 1) & 1;
-                const bool live = x + dx < nx && y + dy < ny && (int)cls[plane * z_lo + i + dx + (int64_t)nx * dy] != ident;
-                const double v = t[cls_pos(s)];
-                good = good && (live ? __double_as_longlong(v) == __double_as_longlong(S->c[s]) : v == 0.0);
-            }
-        }
-        if (!good) S->g_lo = 0;
-    }
-    if (S->g_hi && ((int)cls[plane * z_hi + i] == ident) != id) S->g_hi = 0;
-}
-
-__global__ __launch_bounds__(TPB) void k_stencil_verify(const uint8_t *__restrict__ cls, const double *__restrict__ table, int nx, int ny,
-                                                        int nz, int z_lo, int z_hi, StencilInfo *S) {
-    if (!S->ok) return;
-    const int64_t P = (int64_t)nx * ny;
-    const int64_t i = P * z_lo + (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= P * z_hi) return;
-    const int k = cls[i];
-    if (k == S->ident) return;
-    const int z = (int)(i / P), rem = (int)(i - (int64_t)z * P), y = rem / nx, x = rem - y * nx;
-    const double *t = table + k * 8;
-    bool good = __double_as_longlong(t[cls_pos(0)]) == __double_as_longlong(S->c[0]);
-#pragma unroll
-    for (int s = 1; s < 8; ++s) {
-        const int dx = s & 1, dy = (s >> 1) & 1, dz = s >> 2;
-        const bool inside = x + dx < nx && y + dy < ny && z + dz < nz;
-        const bool live = inside && (int)cls[i + dx + (int64_t)nx * dy + P * dz] != S->ident;
-        const double v = t[cls_pos(s)];
-        good = good && (live ? __double_as_longlong(v) == __double_as_longlong(S->c[s]) : v == 0.0);
-    }
-    if (!good) S->ok = 0;
-}
-
 // The stencil march with an epilogue, over the whole lattice (pgd_mg.hip: the two stencil passes of a multigrid level):
 //   epi 1: y = x - w A x;   epi 2: y = x + w (b - A x), dot: partial sums of b . y (one per workgroup, *nparts of them in c->partials).
 // cls / ident as in the product: code byte per node, `ident` marks eliminated nodes; planes [zm0, zm1) share one pattern of
@@ -2085,376 +1921,6 @@ int launch_stencil_pass(Ctx *c, const uint8_t *cls, int ident, const double cst[
     else return fail(c, PGD_ERR_INVALID, "launch_stencil_pass: epilogue %d", epi);
     c->kcount[KC_STENCIL_MARCH] += 1;
     PGD_LAUNCH_CHECK(c);
-    return PGD_OK;
-}
-
-// --- the classification (per solve, after the slot arrays got their final values)
-__device__ __forceinline__ unsigned long long cls_hash(const double *__restrict__ uvals, int64_t stride, int64_t i) {
-    unsigned long long h = 0x9e3779b97f4a7c15ull;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        unsigned long long v = (unsigned long long)__double_as_longlong(uvals[(int64_t)s * stride + i]);
-        v *= 0xff51afd7ed558ccdull; v ^= v >> 32;
-        h = (h ^ v) * 0xc4ceb9fe1a85ec53ull; h ^= h >> 29;
-    }
-    return h ? h : 1ull;
-}
-
-struct ClsScratch {
-    unsigned long long keys[CLS_SLOTS];     // 0 = empty
-    int rep[CLS_SLOTS];                     // lowest row with that key
-    int id[CLS_SLOTS];                      // class id of the slot (rank of its rep row)
-    int info[4];                            // [0] distinct keys, [1] != 0: no dictionary (too many classes / a hash collision)
-};
-
-__global__ __launch_bounds__(TPB) void k_cls_insert(const double *__restrict__ uvals, int64_t stride, int64_t nv, ClsScratch *S) {
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (*(volatile int *)&S->info[1]) return;
-    const bool active = i < nv;
-    const unsigned long long h = active ? cls_hash(uvals, stride, i) : 0ull;
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(active);
-    while (todo) {                                          // one insertion per distinct key of the wavefront
-        if (*(volatile int *)&S->info[1]) return;           // too many classes already: no point in probing a full table
-        const int leader = __ffsll((long long)todo) - 1;
-        const unsigned long long h0 = __shfl(h, leader);
-        todo &= ~__ballot(active && h == h0);
-        if (lane != leader) continue;
-        int slot = (int)(h0 & (CLS_SLOTS - 1));
-        for (int probe = 0; probe < CLS_SLOTS; ++probe, slot = (slot + 1) & (CLS_SLOTS - 1)) {
-            unsigned long long k = *(volatile unsigned long long *)&S->keys[slot];
-            if (k == 0ull) {
-                k = atomicCAS(&S->keys[slot], 0ull, h0);
-                if (k == 0ull) {
-                    k = h0;
-                    if (atomicAdd(&S->info[0], 1) + 1 > CLS_MAX) atomicExch(&S->info[1], 1);
-                }
-            }
-            if (k == h0) {
-                if (*(volatile int *)&S->rep[slot] > (int)i) atomicMin(&S->rep[slot], (int)i);
-                break;
-            }
-        }
-    }
-}
-
-// class ids in the order of the representative rows (deterministic), the table in the products' layout
-__global__ __launch_bounds__(CLS_SLOTS) void k_cls_table(const double *__restrict__ uvals, int64_t stride, ClsScratch *S,
-                                                          double *__restrict__ table) {
-    __shared__ int s_rep[CLS_SLOTS];
-    const int t = threadIdx.x;
-    const bool used = S->keys[t] != 0ull;
-    s_rep[t] = used ? S->rep[t] : 0x7fffffff;
-    __syncthreads();
-    if (S->info[1]) return;
-    int rank = 0;
-    for (int k = 0; k < CLS_SLOTS; ++k) rank += (s_rep[k] < s_rep[t]) ? 1 : 0;
-    S->id[t] = used ? rank : -1;
-    if (used && rank <= CLS_MAX) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) table[rank * 8 + cls_pos(s)] = uvals[(int64_t)s * stride + s_rep[t]];
-    }
-    if (t < 8) table[min(S->info[0], CLS_MAX) * 8 + t] = 0.0;        // the zero class
-}
-
-__global__ __launch_bounds__(TPB) void k_cls_assign(const double *__restrict__ uvals, int64_t stride, int64_t nv, ClsScratch *S,
-                                                    const double *__restrict__ table, uint8_t *__restrict__ cls) {
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= nv || S->info[1]) return;
-    const unsigned long long h = cls_hash(uvals, stride, i);
-    int slot = (int)(h & (CLS_SLOTS - 1)), id = -1;
-    for (int probe = 0; probe < CLS_SLOTS; ++probe, slot = (slot + 1) & (CLS_SLOTS - 1)) {
-        const unsigned long long k = S->keys[slot];
-        if (k == h) { id = S->id[slot]; break; }
-        if (k == 0ull) break;
-    }
-    bool same = id >= 0 && id <= CLS_MAX;
-    if (same) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-            same = same && __double_as_longlong(uvals[(int64_t)s * stride + i]) == __double_as_longlong(table[id * 8 + cls_pos(s)]);
-    }
-    if (!same) { atomicExch(&S->info[1], 2); return; }       // two tuples under one key: keep the plain diagonal form
-    cls[i] = (uint8_t)id;
-}
-
-// same[z] = 1 iff every row of plane z has the code of the row below it in plane z - 1 (same[0] = 0): the march keeps its
-// couplings across such planes without looking at a code
-__global__ __launch_bounds__(TPB) void k_cls_planes(const uint8_t *__restrict__ cls, int64_t plane, int nz, int *__restrict__ same) {
-    __shared__ int s_diff;
-    const int z = blockIdx.x;
-    if (threadIdx.x == 0) s_diff = 0;
-    __syncthreads();
-    bool diff = z == 0;
-    if (z > 0) {
-        const uint8_t *a = cls + plane * z, *b = a - plane;
-        for (int64_t i = threadIdx.x; i < plane; i += TPB) diff = diff || a[i] != b[i];
-    }
-    if (diff) s_diff = 1;
-    __syncthreads();
-    if (threadIdx.x == 0) same[z] = s_diff ? 0 : 1;
-}
-
-// ---- classification with known codes (Mesh::cls_cache)
-__global__ void k_cls_table_known(const double *__restrict__ uvals, int64_t stride, int64_t nv, const int *__restrict__ reps, int ncls,
-                                  double *__restrict__ table) {
-    const int k = threadIdx.x;
-    if (k < ncls) {
-        const int64_t r = reps[k];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) table[k * 8 + cls_pos(s)] = (r >= 0 && r < nv) ? uvals[(int64_t)s * stride + r] : 0.0;
-    } else if (k == ncls) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) table[k * 8 + s] = 0.0;                 // the zero class
-    }
-}
-
-__global__ __launch_bounds__(TPB) void k_cls_verify_known(const double *__restrict__ uvals, int64_t stride, int64_t nv,
-                                                          const double *__restrict__ table, const uint8_t *__restrict__ cls, int ncls,
-                                                          int *__restrict__ info) {
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= nv) return;
-    const int k = cls[i];
-    bool same = k < ncls;
-    if (same) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-            same = same && __double_as_longlong(uvals[(int64_t)s * stride + i]) == __double_as_longlong(table[k * 8 + cls_pos(s)]);
-    }
-    if (!same) info[1] = 2;
-}
-
-struct ZeroPat { uint8_t b[256]; };
-
-// the class-level relations of the stencil form for known codes: the identity tuple, and every class = the base tuple with
-// exact zeros where (and only where) the structure - verified row by row when the codes were first seen - has them
-// (`use`: the classes that occur on the verified planes - the incomplete ghost rows of a sharded slab have tuples of their own, which
-// the full classification never holds against the stencil either: k_stencil_verify walks the verified planes only)
-__global__ void k_stencil_known(const double *__restrict__ table, int ncls, int ident, int base, ZeroPat pat, ZeroPat use, StencilInfo *S) {
-    __shared__ int s_bad;
-    if (threadIdx.x == 0) s_bad = 0;
-    __syncthreads();
-    const int k = threadIdx.x;
-    if (k < ncls && use.b[k]) {
-        bool good = true;
-        if (k == ident) {
-            good = table[k * 8 + cls_pos(0)] == 1.0;
-            for (int s = 1; s < 8; ++s) good = good && table[k * 8 + cls_pos(s)] == 0.0;
-        } else {
-            good = __double_as_longlong(table[k * 8 + cls_pos(0)]) == __double_as_longlong(table[base * 8 + cls_pos(0)]);
-            for (int s = 1; s < 8; ++s) {
-                const double v = table[k * 8 + cls_pos(s)];
-                good = good && (((pat.b[k] >> s) & 1) ? v == 0.0
-                                                      : __double_as_longlong(v) == __double_as_longlong(table[base * 8 + cls_pos(s)]));
-            }
-        }
-        if (!good) s_bad = 1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        S->ok = s_bad ? 0 : 1; S->ident = ident; S->base = base; S->split = 0;
-        for (int s = 0; s < 8; ++s) S->c[s] = table[base * 8 + cls_pos(s)];
-    }
-}
-
-// after a full classification: a representative row per class, the zero patterns
-__global__ __launch_bounds__(TPB) void k_cls_reps(const uint8_t *__restrict__ cls, int64_t nv, int *__restrict__ reps) {
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    const bool active = i < nv;
-    const int code = active ? (int)cls[i] : -1;
-    // one atomic per distinct code of the wavefront (its lowest lane holds the lowest row), and none where the class already has
-    // a representative further down: 16.7 M atomics on nine addresses took 188 ms
-    unsigned long long todo = __ballot(active);
-    const int lane = threadIdx.x & 63;
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int c0 = __shfl(code, leader);
-        todo &= ~__ballot(active && code == c0);
-        if (lane == leader && reps[c0] > (int)i) atomicMin(&reps[c0], (int)i);
-    }
-}
-
-// Row classes of the operator's CURRENT slot values (a->uvals, diagonal form).  a->cls_count > 0 afterwards when the
-// dictionary exists; any later change of the slot values must reset it (sym_scale, combine_dia, ensure_sym do).
-int dia_classify(Ctx *c, const Mesh *m, Csr *a, int zrange_lo, int zrange_hi) {
-    a->cls_count = 0;
-    a->st_ok = false;
-    a->st_g_lo = a->st_g_hi = false;
-    if (!c->spmv_classes || m->sym_nx <= 0 || !(a->uvals && a->uvals_valid) || m->nv >= ((int64_t)1 << 31)) return PGD_OK;
-    const int64_t plane = (int64_t)m->sym_nx * m->sym_ny;
-    if (m->nv / plane < 3 || plane * 64 < c->spmv_grid_min_plane_bytes) return PGD_OK;          // no march on this grid anyway
-    void *p;
-    if (m->nv / plane > 65536) return PGD_OK;                                // (plane flags of the stencil check: room for 2^16 planes)
-    if (!c->cls_scratch) { PGD_TRY(dev_alloc(c, &p, sizeof(ClsScratch) + sizeof(StencilInfo) + 2 * 65536 * sizeof(int))); c->cls_scratch = p; }
-    const int nzp = (int)(m->nv / plane);
-    const size_t same_bytes = ((size_t)nzp * sizeof(int) + 63) / 64 * 64;
-    if (!a->cls) {
-        a->cls_bytes = (size_t)m->nv + (size_t)(CLS_MAX + 1) * 8 * sizeof(double) + same_bytes + 64;
-        PGD_TRY(dev_alloc(c, &p, a->cls_bytes));
-        a->cls_table = (double *)p;                          // the table first (aligned), then the plane flags, then the codes
-        a->cls_same = (int *)((uint8_t *)p + (size_t)(CLS_MAX + 1) * 8 * sizeof(double));
-        a->cls = (uint8_t *)a->cls_same + same_bytes;
-    }
-    ClsScratch *S = (ClsScratch *)c->cls_scratch;
-    hipStream_t st = c->stream;
-    const int g = (int)((m->nv + TPB - 1) / TPB);
-    int z_lo = 0, z_hi = nzp;
-    if (zrange_lo >= 0) { z_lo = std::max(0, zrange_lo); z_hi = std::min(nzp, zrange_hi); }
-    StencilInfo *SI = reinterpret_cast<StencilInfo *>(S + 1);
-    const bool try_stencil = c->spmv_stencil && z_hi - z_lo >= 3;
-    struct { int info[4]; StencilInfo si; } host;
-    const int scaled_key = (a->uvals_scaled ? 1 : 0) + (a->uvals_unit ? 2 : 0) + (try_stencil ? 4 : 0);
-    // ---- known structure: codes copied, table from the representative rows, EVERY row compared with its class bit by bit
-    if (c->cls_cache_on) {
-        for (size_t e = 0; e < m->cls_cache.size(); ++e) {
-            Mesh::ClsCache &E = m->cls_cache[e];
-            if (E.sig != a->bc_sig || E.scaled != scaled_key || E.z_lo != z_lo || E.z_hi != z_hi || !E.codes) continue;
-            PGD_HIP(c, hipMemsetAsync(S->info, 0, sizeof S->info, st));
-            PGD_HIP(c, hipMemcpyAsync(a->cls, E.codes, (size_t)m->nv, hipMemcpyDeviceToDevice, st));
-            PGD_HIP(c, hipMemcpyAsync(a->cls_same, E.same, (size_t)nzp * sizeof(int), hipMemcpyDeviceToDevice, st));
-            k_cls_table_known<<<1, 256, 0, st>>>(a->uvals, a->uvals_stride, m->nv, E.reps, E.ncls, a->cls_table);
-            k_cls_verify_known<<<g, TPB, 0, st>>>(a->uvals, a->uvals_stride, m->nv, a->cls_table, a->cls, E.ncls, S->info);
-            host.si.ok = 0;
-            if (E.st_ok) {
-                ZeroPat zp;
-                memcpy(zp.b, E.zero_pat, sizeof zp.b);
-                ZeroPat use;
-                memcpy(use.b, E.in_range, sizeof use.b);
-                k_stencil_known<<<1, 256, 0, st>>>(a->cls_table, E.ncls, E.ident, E.base, zp, use, SI);
-                k_stencil_ghost_init<<<1, 1, 0, st>>>(SI, z_lo, z_hi, nzp, E.zm0, E.zm1);
-                if (z_lo > 0 || z_hi < nzp) k_stencil_ghost<<<(int)((plane + TPB - 1) / TPB), TPB, 0, st>>>(a->cls, a->cls_table, m->sym_nx, m->sym_ny, z_lo, z_hi, E.zm0, SI);
-            }
-            host.info[1] = 1;
-            PGD_HIP(c, hipMemcpyAsync(host.info, S->info, sizeof host.info, hipMemcpyDeviceToHost, st));
-            if (E.st_ok) PGD_HIP(c, hipMemcpyAsync(&host.si, SI, sizeof(StencilInfo), hipMemcpyDeviceToHost, st));
-            PGD_HIP(c, hipStreamSynchronize(st));
-            PGD_LAUNCH_CHECK(c);
-            if (getenv("PGD_DEBUG_CLS"))
-                fprintf(stderr, "[dia_classify] known structure %zu of %zu: z %d..%d mismatches %d (info %d %d %d %d) stencil %d -> %d\n", e, m->cls_cache.size(),
-                        z_lo, z_hi, host.info[1], host.info[0], host.info[1], host.info[2], host.info[3], (int)E.st_ok, host.si.ok);
-            if (host.info[1] != 0 || (E.st_ok && !host.si.ok)) {          // not that structure after all: forget it, classify in full
-                (void)hipFree(E.same);
-                m->cls_cache.erase(m->cls_cache.begin() + (long)e);
-                break;
-            }
-            E.used = ++m->cls_clock;
-            c->cls_fast += 1;
-            a->cls_count = E.ncls;
-            if (E.st_ok) {
-                a->st_ok = true;
-                a->st_ident = E.ident;
-                a->st_z0 = z_lo; a->st_z1 = z_hi; a->st_zm0 = E.zm0; a->st_zm1 = E.zm1;
-                a->st_g_lo = host.si.g_lo != 0; a->st_g_hi = host.si.g_hi != 0;
-                for (int s2 = 0; s2 < 8; ++s2) a->st_c[s2] = host.si.c[s2];
-            }
-            return PGD_OK;
-        }
-    }
-    c->cls_full += 1;
-    PGD_HIP(c, hipMemsetAsync(S->keys, 0, sizeof S->keys, st));
-    PGD_HIP(c, hipMemsetAsync(S->rep, 0x7f, sizeof S->rep, st));
-    PGD_HIP(c, hipMemsetAsync(S->info, 0, sizeof S->info, st));
-    k_cls_insert<<<g, TPB, 0, st>>>(a->uvals, a->uvals_stride, m->nv, S);
-    k_cls_table<<<1, CLS_SLOTS, 0, st>>>(a->uvals, a->uvals_stride, S, a->cls_table);
-    k_cls_assign<<<g, TPB, 0, st>>>(a->uvals, a->uvals_stride, m->nv, S, a->cls_table, a->cls);
-    // ... and whether the classes are ONE stencil with eliminated nodes (k_spmv_stencil_march) on the planes [z_lo, z_hi) - the
-    // whole grid, or the owned planes of a sharded rank's slab, whose ghost-plane rows are incomplete by construction
-    if (try_stencil) {
-        k_stencil_pick<<<1, 64, 0, st>>>(a->cls, a->cls_table, S->info, m->sym_nx, m->sym_ny, z_lo, z_hi, SI);
-        k_stencil_split<<<g, TPB, 0, st>>>(a->cls, a->cls_table, S->info, m->sym_nx, m->sym_ny, m->nv, SI);
-        k_stencil_commit<<<1, 64, 0, st>>>(a->cls_table, S->info, SI);
-    }
-    k_cls_planes<<<nzp, TPB, 0, st>>>(a->cls, plane, nzp, a->cls_same);
-    if (try_stencil) {
-        const int64_t rows = plane * (z_hi - z_lo);
-        k_stencil_verify<<<(int)((rows + TPB - 1) / TPB), TPB, 0, st>>>(a->cls, a->cls_table, m->sym_nx, m->sym_ny, nzp, z_lo, z_hi, SI);
-        int *allid = reinterpret_cast<int *>(SI + 1);
-        k_stencil_allid<<<nzp, TPB, 0, st>>>(a->cls, plane, SI, allid, allid + 65536);
-        k_stencil_planes<<<1, 64, 0, st>>>(allid + 65536, allid, z_lo, z_hi, SI);
-        k_stencil_ghost_init<<<1, 1, 0, st>>>(SI, z_lo, z_hi, nzp, -1, -1);
-        if (z_lo > 0 || z_hi < nzp) k_stencil_ghost<<<(int)((plane + TPB - 1) / TPB), TPB, 0, st>>>(a->cls, a->cls_table, m->sym_nx, m->sym_ny, z_lo, z_hi, -1, SI);
-    }
-    host.info[0] = 0; host.info[1] = 1; host.si.ok = 0;
-    PGD_HIP(c, hipMemcpyAsync(host.info, S->info, sizeof host.info, hipMemcpyDeviceToHost, st));
-    if (try_stencil) PGD_HIP(c, hipMemcpyAsync(&host.si, SI, sizeof(StencilInfo), hipMemcpyDeviceToHost, st));
-    PGD_HIP(c, hipStreamSynchronize(st));
-    PGD_LAUNCH_CHECK(c);
-    // (an operator without classes - a variable coefficient - costs 0.55 ms at 256^3 here: the insert pass gives up as soon as the
-    // 256th class appears)
-    if (host.info[1] != 0 || host.info[0] <= 0 || host.info[0] > CLS_MAX) return PGD_OK;
-    a->cls_count = host.info[0];
-    if (getenv("PGD_DEBUG_STENCIL"))
-        fprintf(stderr, "[dia_classify] classes %d info1 %d try %d ok %d ident %d base %d c = %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g  z [%d, %d)\n",
-                host.info[0], host.info[1], (int)try_stencil, host.si.ok, host.si.ident, host.si.base, host.si.c[0], host.si.c[1], host.si.c[2],
-                host.si.c[3], host.si.c[4], host.si.c[5], host.si.c[6], host.si.c[7], z_lo, z_hi);
-    if (getenv("PGD_DEBUG_STENCIL")) fprintf(stderr, "[dia_classify] main run [%d, %d)\n", host.si.zm0, host.si.zm1);
-    if (try_stencil && host.si.ok) {
-        a->st_ok = true;
-        a->st_ident = host.si.ident;
-        a->st_z0 = z_lo; a->st_z1 = z_hi;
-        a->st_zm0 = host.si.zm0; a->st_zm1 = host.si.zm1;
-        a->st_g_lo = host.si.g_lo != 0; a->st_g_hi = host.si.g_hi != 0;
-        for (int s2 = 0; s2 < 8; ++s2) a->st_c[s2] = host.si.c[s2];
-    }
-    // ---- remember the structure for the next operator with this signature (at most four per mesh, least recently used out)
-    if (c->cls_cache_on) {
-        const int ncls = a->cls_count;
-        Mesh::ClsCache E;
-        E.sig = a->bc_sig; E.scaled = scaled_key; E.z_lo = z_lo; E.z_hi = z_hi; E.ncls = ncls;
-        const size_t same_b = ((size_t)nzp * sizeof(int) + 63) / 64 * 64, reps_b = 256 * sizeof(int);
-        E.bytes = (size_t)m->nv + same_b + reps_b + 64;
-        void *q = nullptr;
-        if (hipMalloc(&q, E.bytes + PAD_BYTES) == hipSuccess) {
-            E.same = (int *)q;
-            E.reps = (int *)((uint8_t *)q + same_b);
-            E.codes = (uint8_t *)q + same_b + reps_b;          // (freed through this pointer's base: keep the base first)
-            // layout note: the allocation starts at E.same; hipFree takes that address
-            double tab[(CLS_MAX + 1) * 8];
-            bool okc = hipMemcpyAsync(E.codes, a->cls, (size_t)m->nv, hipMemcpyDeviceToDevice, st) == hipSuccess &&
-                       hipMemcpyAsync(E.same, a->cls_same, (size_t)nzp * sizeof(int), hipMemcpyDeviceToDevice, st) == hipSuccess &&
-                       hipMemsetAsync(E.reps, 0x7f, reps_b, st) == hipSuccess;
-            int reps_rng[256];
-            if (okc) {
-                // (first the classes that occur on the verified planes - representatives within them, through the same kernel on
-                // that range - then the representatives of ALL classes, which is what the entry keeps)
-                const int64_t r0 = (int64_t)z_lo * plane, r1 = std::min<int64_t>((int64_t)z_hi * plane, m->nv);
-                if (r1 > r0) k_cls_reps<<<(int)((r1 - r0 + TPB - 1) / TPB), TPB, 0, st>>>(a->cls + r0, r1 - r0, E.reps);
-                okc = hipMemcpyAsync(reps_rng, E.reps, sizeof reps_rng, hipMemcpyDeviceToHost, st) == hipSuccess &&
-                      hipStreamSynchronize(st) == hipSuccess && hipMemsetAsync(E.reps, 0x7f, reps_b, st) == hipSuccess;
-            }
-            if (okc) {
-                k_cls_reps<<<g, TPB, 0, st>>>(a->cls, m->nv, E.reps);
-                okc = hipMemcpyAsync(tab, a->cls_table, (size_t)(ncls + 1) * 8 * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                      hipStreamSynchronize(st) == hipSuccess;
-            }
-            if (okc) {
-                E.st_ok = a->st_ok; E.ident = a->st_ident; E.base = try_stencil ? host.si.base : -1; E.zm0 = a->st_zm0; E.zm1 = a->st_zm1;
-                for (int k = 0; k < 256; ++k) E.in_range[k] = (k < ncls && reps_rng[k] >= 0 && reps_rng[k] < 0x7f000000) ? 1 : 0;
-                for (int k = 0; k < 256; ++k) {
-                    uint8_t b = 0;
-                    if (k < ncls) for (int s2 = 1; s2 < 8; ++s2) if (tab[k * 8 + cls_pos(s2)] == 0.0) b |= (uint8_t)(1u << s2);
-                    E.zero_pat[k] = b;
-                }
-                // (a structural zero of the BASE tuple itself is no pattern bit: such a slot is compared with the base value)
-                if (E.base >= 0) for (int k = 0; k < ncls; ++k) E.zero_pat[k] &= (uint8_t)~E.zero_pat[E.base];
-                E.codes = (uint8_t *)q + same_b + reps_b;
-                E.used = ++m->cls_clock;
-                // keep the allocation's base in `same` (first member of the block); free through it
-                if (m->cls_cache.size() >= 4) {
-                    size_t old = 0;
-                    for (size_t e = 1; e < m->cls_cache.size(); ++e) if (m->cls_cache[e].used < m->cls_cache[old].used) old = e;
-                    (void)hipFree(m->cls_cache[old].same);
-                    m->cls_cache.erase(m->cls_cache.begin() + (long)old);
-                }
-                m->cls_cache.push_back(E);
-            } else {
-                (void)hipFree(q);
-                (void)hipGetLastError();
-            }
-        } else {
-            (void)hipGetLastError();
-        }
-    }
     return PGD_OK;
 }
 
@@ -2609,7 +2075,7 @@ __global__ __launch_bounds__(TPB) void k_sym_scale(double *__restrict__ uvals, i
 
 int sym_scale(Ctx *c, const Mesh *m, Csr *a, const double *sc) {
     if (!(a->uvals && a->uvals_valid) || a->uvals_scaled) return fail(c, PGD_ERR_INVALID, "sym_scale: no unscaled symmetric copy");
-    a->cls_count = 0;
+    a->drop_classes();
     const int g = (int)((m->nv + TPB - 1) / TPB);
     if (m->sym_nx > 0) k_dia_scale<<<g, TPB, 0, c->stream>>>(a->uvals, a->uvals_stride, sc, m->nv, m->sym_nx, m->sym_ny, c->spmv_unit_diag);
     else if (m->sym_w == 4) k_sym_scale<4><<<g, TPB, 0, c->stream>>>(a->uvals, a->uvals_stride, m->pids, m->sym_tab, sc, m->nv);
@@ -2625,8 +2091,8 @@ int ensure_sym(Ctx *c, const Mesh *m, Csr *a, bool *usable) {
     if (!c->spmv_sym || m->sym_w == 0) return PGD_OK;
     if (a->uvals_valid && !a->uvals_scaled) { *usable = a->uvals != nullptr; return PGD_OK; }
     a->uvals_scaled = false;
-    a->cls_count = 0;
-    a->uvals_valid = true;                       // decided for this set of values, whatever the outcome
+    a->drop_classes();
+    a->uvals_valid = true;                      // decided for this set of values, whatever the outcome
     const int64_t stride = m->nv;      // (padding the arrays apart - 2^27-byte strides at 256^3 - measured no difference)
     if (a->uvals && a->uvals_stride != stride) { dev_release(c, a->uvals, a->uvals_bytes); a->uvals = nullptr; }
     if (!a->uvals) {
@@ -2695,7 +2161,7 @@ __global__ __launch_bounds__(TPB) void k_combine_dia(CombineDiaArgs A, double *_
 // mask: Dirichlet flags per row (or null) - only valid on the LAST pass, like k_combine's column mask
 int combine_dia(Ctx *c, const Mesh *m, Csr *o, Csr *const *atoms, const double *coefs, int n, const uint8_t *mask) {
     o->uvals_valid = false;
-    o->cls_count = 0;
+    o->drop_classes();
     o->cls_tried = false;
     if (!c->spmv_sym || m->sym_nx <= 0 || !c->spmv_combine_dia) return PGD_OK;
     for (int t = 0; t < n; ++t) {
@@ -2749,7 +2215,7 @@ bool atom_fast_form(Ctx *c, const Mesh *m, Csr *a, int64_t r0, int64_t r1) {
     if (plane * 64 < c->spmv_grid_min_plane_bytes || c->spmv_zchunk <= 0) return false;
     if (!a->cls_tried) {
         a->cls_tried = true;
-        if (dia_classify(c, m, a) != PGD_OK) { a->cls_count = 0; return false; }
+        if (dia_classify(c, m, a) != PGD_OK) { a->drop_classes(); return false; }
     }
     return true;
 }

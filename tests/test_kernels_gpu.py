@@ -1218,6 +1218,72 @@ def test_classification_cache_is_verified_not_trusted(ctx):
     ctx.mesh_free(h)
 
 
+def test_classification_cache_evicts_least_recently_used(ctx):
+    """A mesh keeps at most four remembered structures and drops the least recently USED one.  Five Dirichlet lists on one fresh
+    mesh - the hull plus 0 .. 4 interior vertices: the signature mixes the list's length - are classified in order, then S4, S0, S2,
+    S1 again; pgd_classify_counts around every classification says whether the cache served it.  Every operator's product from
+    its classes equals the CSR product bit for bit, whichever way the classes came."""
+    nx, ny, nz = 12, 9, 7
+    coords, cells = F.box_mesh((0, 0, 0), (1.0, 0.7, 1.3), nx - 1, ny - 1, nz - 1)
+    h = ctx.mesh_upload(coords, cells)
+    n = coords.shape[0]
+    plane = nx * ny
+    ak, am = ctx.atom_assemble(h, F.STIFF), ctx.atom_assemble(h, F.MASS)
+    bnd = boundary_dofs(coords).astype(np.int32)
+    interior = np.array([(2 + 2 * k) + nx * (2 + k) + plane * (1 + k) for k in range(4)], dtype=np.int32)
+    assert np.intersect1d(bnd, interior).size == 0 and np.unique(interior).size == 4
+    lists = [np.union1d(bnd, interior[:k]).astype(np.int32) for k in range(5)]
+    rng = np.random.default_rng(11)
+    x = rng.uniform(-1, 1, n)
+    xv, yv = ctx.vec_from(x), ctx.vec_alloc(n)
+    ctx.flags_reset()
+
+    def product(op):
+        ctx.tune(7, 4)
+        ctx.tune(36, 5)
+        ctx.vec_fill(yv, -2.0)
+        ctx.spmv_dot_slot(op, xv, yv, xv, 0, n, 30)
+        return ctx.vec_download(yv)
+
+    def reference(op):
+        ctx.tune(3, 0)
+        ctx.vec_fill(yv, -2.0)
+        ctx.spmv_dot_slot(op, xv, yv, xv, 0, n, 30)
+        ctx.tune(3, 1)
+        assert ctx.op_symmetrize(op)
+        return ctx.vec_download(yv)
+    # (list, full, cached): the fifth insert evicts S0; S4 is served; S0 is classified in full again and evicts S1 - S4 was used
+    # after it -; S2 is served; S1 is gone
+    steps = [(0, 1, 0), (1, 1, 0), (2, 1, 0), (3, 1, 0), (4, 1, 0), (4, 0, 1), (0, 1, 0), (2, 0, 1), (1, 1, 0)]
+    try:
+        ctx.tune(39, 1)
+        for step, (k, full, cached) in enumerate(steps):
+            op = ctx.op_combine(h, [ak, am], [1.0, 0.37], lists[k])
+            ref = reference(op)
+            c0 = ctx.classify_counts()
+            ncls = ctx.op_classify(op)
+            c1 = ctx.classify_counts()
+            print("step %d: S%d classes %d full +%d cached +%d" % (step + 1, k, ncls, c1["full"] - c0["full"], c1["cached"] - c0["cached"]))
+            assert ncls > 0, (step, k)
+            assert (c1["full"] - c0["full"], c1["cached"] - c0["cached"]) == (full, cached), (step, k)
+            k0 = ctx.kernel_counts()
+            y = product(op)
+            k1 = ctx.kernel_counts()
+            assert k1["stencil_march"] + k1["diac_march"] == k0["stencil_march"] + k0["diac_march"] + 1, (step, k)
+            assert np.array_equal(y, ref), (step, k)
+            ctx.atom_free(op)
+    finally:
+        ctx.tune(7, 0)
+        ctx.tune(36, 0)
+        ctx.tune(39, 1)
+        ctx.tune(3, 1)
+    for v in (xv, yv):
+        ctx.vec_free(v)
+    for a in (ak, am):
+        ctx.atom_free(a)
+    ctx.mesh_free(h)
+
+
 def test_pcg_on_the_stencil_form_walks_the_same_iterates(ctx):
     """The library's PCG with the scaled operator in its stencil form (k_spmv_stencil_march) against the same solve on the
     row-class dictionary: y is bit-identical, the fused dots are grouped per workgroup (64 x 16 patches instead of 64 x 8), so

@@ -936,11 +936,21 @@ class Context:
         self._ck(self.lib.pgd_classify_counts(self.h, C.byref(full), C.byref(cached)))
         return {"full": full.value, "cached": cached.value}
 
+    def _precondition(self, which, stats):
+        """PGD_TUNE_PCG_PRECOND = which; the solves that the cycle behind `stats` has preconditioned so far."""
+        self.tune(40, which)
+        return stats()["solves"]
+
+    def _cycle_stats(self, cycle):
+        a, b, l, m, ms = I64(), I64(), I64(), I64(), C.c_double()
+        self._ck(getattr(self.lib, "pgd_%s_counts" % cycle)(self.h, C.byref(a), C.byref(b), C.byref(l)))
+        self._ck(getattr(self.lib, "pgd_%s_times" % cycle)(self.h, C.byref(ms), C.byref(m)))
+        return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
+
     def precondition(self, multigrid):
         """Select the preconditioner of the next pcg_solve calls (1: the multigrid V-cycle where the operator allows it,
         0: Jacobi); returns the number of solves the V-cycle has preconditioned so far."""
-        self.tune(40, 1 if multigrid else 0)
-        return self.mg_stats()["solves"]
+        return self._precondition(1 if multigrid else 0, self.mg_stats)
 
     def mg_stats(self):
         a, b = I64(), I64()
@@ -950,38 +960,26 @@ class Context:
     def precondition_variable(self, on):
         """Select the V-cycle for variable-coefficient operators (PGD_TUNE_PCG_PRECOND = 2) for the next pcg_solve calls, or
         (on false) the Jacobi-PCG again; returns the number of solves that cycle has preconditioned so far."""
-        self.tune(40, 2 if on else 0)
-        return self.vmg_stats()["solves"]
+        return self._precondition(2 if on else 0, self.vmg_stats)
 
     def vmg_stats(self):
-        a, b, l, m, ms = I64(), I64(), I64(), I64(), C.c_double()
-        self._ck(self.lib.pgd_vmg_counts(self.h, C.byref(a), C.byref(b), C.byref(l)))
-        self._ck(self.lib.pgd_vmg_times(self.h, C.byref(ms), C.byref(m)))
-        return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
+        return self._cycle_stats("vmg")
 
     def precondition_component(self, on):
         """Select the component-wise V-cycle for vector-valued P1 operators on box lattices (PGD_TUNE_PCG_PRECOND = 3) for the next
         pcg_solve calls, or (on false) the Jacobi-PCG again; returns the number of solves that cycle has preconditioned so far."""
-        self.tune(40, 3 if on else 0)
-        return self.cmg_stats()["solves"]
+        return self._precondition(3 if on else 0, self.cmg_stats)
 
     def cmg_stats(self):
-        a, b, l, m, ms = I64(), I64(), I64(), I64(), C.c_double()
-        self._ck(self.lib.pgd_cmg_counts(self.h, C.byref(a), C.byref(b), C.byref(l)))
-        self._ck(self.lib.pgd_cmg_times(self.h, C.byref(ms), C.byref(m)))
-        return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
+        return self._cycle_stats("cmg")
 
     def precondition_p(self, on):
         """Select the p-multigrid cycle for P2 operators on bound box lattices (PGD_TUNE_PCG_PRECOND = 4) for the next pcg_solve calls,
         or (on false) the Jacobi-PCG again; returns the number of solves that cycle has preconditioned so far."""
-        self.tune(40, 4 if on else 0)
-        return self.pmg_stats()["solves"]
+        return self._precondition(4 if on else 0, self.pmg_stats)
 
     def pmg_stats(self):
-        a, b, l, m, ms = I64(), I64(), I64(), I64(), C.c_double()
-        self._ck(self.lib.pgd_pmg_counts(self.h, C.byref(a), C.byref(b), C.byref(l)))
-        self._ck(self.lib.pgd_pmg_times(self.h, C.byref(ms), C.byref(m)))
-        return {"solves": a.value, "fallbacks": b.value, "levels": l.value, "setup_ms": ms.value, "march_passes": m.value}
+        return self._cycle_stats("pmg")
 
     def pmg_coarse(self, comp, nvert):
         """What the last solve under the p-multigrid cycle built for component comp: (the 8 level-0 slot arrays as an 8 x nvert
@@ -991,31 +989,34 @@ class Context:
         self._ck(self.lib.pgd_pmg_coarse(self.h, int(comp), dptr(slots), el.ctypes.data_as(PU8)))
         return slots, el
 
+    def _product_form(self, knob, on, stats):
+        """Tune knob = on; the products launched so far from the form behind `stats`."""
+        self.tune(knob, 1 if on else 0)
+        return stats()["products"]
+
+    def _form_stats(self, form):
+        f, p, b, ms = I64(), I64(), I64(), C.c_double()
+        self._ck(getattr(self.lib, "pgd_%s_counts" % form)(self.h, C.byref(f), C.byref(p), C.byref(b)))
+        self._ck(getattr(self.lib, "pgd_%s_times" % form)(self.h, C.byref(ms)))
+        return {"forms_built": f.value, "products": p.value, "fallbacks": b.value, "extract_ms": ms.value}
+
     def block_product(self, on):
         """Select the row-diagonal product for operators on vector-valued P1 layouts over box lattices (PGD_TUNE_SPMV_BLOCK_DIA) for
         the next products and solves, or (on false) the CSR product again; returns the number of products launched from that form
         so far.  The results do not depend on it, bit for bit."""
-        self.tune(TUNE_SPMV_BLOCK_DIA, 1 if on else 0)
-        return self.bdia_stats()["products"]
+        return self._product_form(TUNE_SPMV_BLOCK_DIA, on, self.bdia_stats)
 
     def bdia_stats(self):
-        f, p, b, ms = I64(), I64(), I64(), C.c_double()
-        self._ck(self.lib.pgd_bdia_counts(self.h, C.byref(f), C.byref(p), C.byref(b)))
-        self._ck(self.lib.pgd_bdia_times(self.h, C.byref(ms)))
-        return {"forms_built": f.value, "products": p.value, "fallbacks": b.value, "extract_ms": ms.value}
+        return self._form_stats("bdia")
 
     def p2_product(self, on):
         """Select the row-class product for operators on P2 layouts bound to 3-D box lattices (PGD_TUNE_SPMV_P2_LATTICE) for the next
         products and solves, or (on false) the CSR product again; returns the number of products launched from that form so far.
         The results do not depend on it, bit for bit."""
-        self.tune(TUNE_SPMV_P2_LATTICE, 1 if on else 0)
-        return self.p2lat_stats()["products"]
+        return self._product_form(TUNE_SPMV_P2_LATTICE, on, self.p2lat_stats)
 
     def p2lat_stats(self):
-        f, p, b, ms = I64(), I64(), I64(), C.c_double()
-        self._ck(self.lib.pgd_p2lat_counts(self.h, C.byref(f), C.byref(p), C.byref(b)))
-        self._ck(self.lib.pgd_p2lat_times(self.h, C.byref(ms)))
-        return {"forms_built": f.value, "products": p.value, "fallbacks": b.value, "extract_ms": ms.value}
+        return self._form_stats("p2lat")
 
     def calib_stream(self, v, bytes_per_lane, store=False):
         self._ck(self.lib.pgd_calib_stream(self.h, v, int(bytes_per_lane), int(bool(store))))

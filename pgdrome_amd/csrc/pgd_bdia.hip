@@ -146,7 +146,7 @@ static int bdia_ensure(Ctx *c, const Mesh *m, Csr *a, int nx, int ny) {
     PGD_HIP(c, hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     PGD_HIP(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c->bdia_ev[0], c->bdia_ev[1]) == hipSuccess) c->bdia_extract_ms += (double)ms;
+    if (hipEventElapsedTime(&ms, c->bdia_ev[0], c->bdia_ev[1]) == hipSuccess) c->form[FORM_BDIA].extract_ms += (double)ms;
     else (void)hipGetLastError();
     if (bad) {      // an entry off the pattern: the form is dropped
         dev_release(c, a->bdia, a->bdia_bytes);
@@ -155,7 +155,7 @@ static int bdia_ensure(Ctx *c, const Mesh *m, Csr *a, int nx, int ny) {
         return PGD_OK;
     }
     a->bdia_ok = true;
-    c->bdia_forms += 1;
+    c->form[FORM_BDIA].forms += 1;
     return PGD_OK;
 }
 
@@ -171,7 +171,7 @@ int launch_spmv_bdia(Ctx *c, const Mesh *m, Csr *a, const double *x, double *y, 
         if (cap != hipStreamCaptureStatusNone) return PGD_OK;
         if (bdia_lattice(c, m, &nx, &ny, &nz)) PGD_TRY(bdia_ensure(c, m, a, nx, ny));
         else { a->bdia_seen = a->version; a->bdia_ok = false; }
-        if (!a->bdia_ok) c->bdia_fallbacks += 1;
+        if (!a->bdia_ok) c->form[FORM_BDIA].fallbacks += 1;
     }
     if (!a->bdia_ok || !a->bdia || !bdia_lattice(c, m, &nx, &ny, &nz)) return PGD_OK;
     const int R = c->spmv_rows;
@@ -201,7 +201,7 @@ int launch_spmv_bdia(Ctx *c, const Mesh *m, Csr *a, const double *x, double *y, 
     else PGD_BDIA_LAUNCH(false, true);
 #undef PGD_BDIA_LAUNCH
 #undef PGD_BDIA_R
-    c->bdia_products += 1;
+    c->form[FORM_BDIA].products += 1;
     if (timed) PGD_TRY(prof_end(c, m, m->nv, 8.0 * 15.0 * m->ncomp + 16.0 + (dot && w != x ? 8.0 : 0.0)));
     PGD_LAUNCH_CHECK(c);
     return PGD_OK;
@@ -215,16 +215,12 @@ extern "C" {
 
 int pgd_bdia_counts(pgd_handle h, int64_t *forms_built, int64_t *products, int64_t *fallbacks) {
     PGD_CTX(c, h);
-    if (forms_built) *forms_built = c->bdia_forms;
-    if (products) *products = c->bdia_products;
-    if (fallbacks) *fallbacks = c->bdia_fallbacks;
-    return PGD_OK;
+    return form_read(c->form[FORM_BDIA], forms_built, products, fallbacks, nullptr);
 }
 
 int pgd_bdia_times(pgd_handle h, double *extract_ms) {
     PGD_CTX(c, h);
-    if (extract_ms) *extract_ms = c->bdia_extract_ms;
-    return PGD_OK;
+    return form_read(c->form[FORM_BDIA], nullptr, nullptr, nullptr, extract_ms);
 }
 
 }  // extern "C"

@@ -272,6 +272,20 @@ struct Comm {
 };
 constexpr int PUSH_BLOCK_BYTES = 4096, PUSH_AR_FLAG0 = 8, PUSH_BOX_OFF = 512, PUSH_AR_MAXW = 16;
 
+// What the library counts per preconditioner cycle of pgd_pcg_solve (indexed by pgd_pcg_precond; the Jacobi entry stays zero) ...
+struct CycleStats {
+    int64_t solves = 0, fallbacks = 0;   // solves the cycle preconditioned; requests for it that took Jacobi instead
+    int64_t marches = 0;                 // passes of its levels run in k_spmv_stencil_march / the z-march (not counted for the one-stencil cycle)
+    double setup_ms = 0.0;               // time its setups took on the device, summed (not counted for the one-stencil cycle).  VMG: the Galerkin setups; CMG: extraction
+                                         // of the diagonal blocks + their Galerkin setups; PMG: eliminated bytes + Galerkin blocks from the CSR values + their Galerkin chains
+};
+// ... and per product form that a knob switches on (PGD_TUNE_SPMV_BLOCK_DIA, PGD_TUNE_SPMV_P2_LATTICE)
+struct FormStats {
+    int64_t forms = 0, products = 0, fallbacks = 0;   // forms extracted, products launched from one, operators that kept the CSR product
+    double extract_ms = 0.0;                          // time the extractions took on the device, summed
+};
+enum ProductForm { FORM_BDIA = 0, FORM_P2LAT = 1, FORM_COUNT = 2 };
+
 struct Ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -341,16 +355,10 @@ struct Ctx {
                                   // stencil on a lattice whose eliminated nodes are exactly its hull (pgd_mg.hip); anything else falls back to 0
     struct Mg *mg = nullptr;      // its levels and work vectors, kept across solves on the same lattice
     struct Mg *mg_slab = nullptr; // the same for a z-slab of a row-sharded lattice (pgd_mg_slab_*: levels >= 1 are whole and replicated)
-    int64_t mg_solves = 0, mg_fallbacks = 0;
+    CycleStats cycle[PGD_PCG_PRECOND_PMG + 1];   // the counters behind pgd_{mg,vmg,cmg,pmg}_counts / _times
     struct Vmg *vmg = nullptr;    // pcg_precond = 2: the variable-coefficient hierarchy (pgd_vmg.hip), kept across solves on the same lattice
-    int64_t vmg_solves = 0, vmg_fallbacks = 0, vmg_marches = 0;
-    double vmg_setup_ms = 0.0;    // time the Galerkin setups of those solves took on the device, summed
     struct Cmg *cmg = nullptr;    // pcg_precond = 3: one such hierarchy per component of a blocked P1 operator, kept across solves on the same lattice and ncomp
-    int64_t cmg_solves = 0, cmg_fallbacks = 0, cmg_marches = 0;
-    double cmg_setup_ms = 0.0;    // extraction of the diagonal blocks + their Galerkin setups, summed
     struct Pmg *pmg = nullptr;    // pcg_precond = 4: one such hierarchy per component on P^T A P of a P2 operator over a bound box lattice (pgd_pmg.hip)
-    int64_t pmg_solves = 0, pmg_fallbacks = 0, pmg_marches = 0;
-    double pmg_setup_ms = 0.0;    // eliminated bytes + Galerkin blocks from the CSR values + their Galerkin chains, summed
     // pgd_eval_batch (pgd_eval.hip): kernel variant (1 MFMA, 0 plain fma chains), grid cap and samples per launch (0: the launcher's choice);
     // the pinned staging of the coefficients in fragment order, two chunks deep, with the events behind the copies
     int eval_variant = 1, eval_grid_max = 0, eval_chunk = 0;
@@ -390,12 +398,9 @@ struct Ctx {
     int spmv_combine_dia = 1;     // structured grids: op_combine also forms the diagonal form from the atoms' diagonal forms
     int spmv_sym = 1;             // PCG products from the symmetric half storage when the mesh qualifies
     int spmv_block_dia = 0;       // 1: whole-range products of an operator on a blocked P1 layout over a 3-D box lattice from its row-diagonal form (k_spmv_bdia, PGD_TUNE_SPMV_BLOCK_DIA; bit-identical to k_spmv_csr)
-    int64_t bdia_forms = 0, bdia_products = 0, bdia_fallbacks = 0;   // forms extracted, products launched from one, operators that kept the CSR product
-    double bdia_extract_ms = 0.0; // time the extractions took on the device, summed
+    FormStats form[FORM_COUNT];   // the counters behind pgd_{bdia,p2lat}_counts / _times (p2lat: degree-2 operators that kept the CSR product)
     hipEvent_t bdia_ev[2] = {nullptr, nullptr};
     int spmv_p2_lattice = 0;      // 1: whole-range products of an operator on a P2 layout bound to a 3-D box lattice from its row-class form (k_spmv_p2lat, PGD_TUNE_SPMV_P2_LATTICE; bit-identical to k_spmv_csr)
-    int64_t p2lat_forms = 0, p2lat_products = 0, p2lat_fallbacks = 0;   // forms extracted, products launched from one, degree-2 operators that kept the CSR product
-    double p2lat_extract_ms = 0.0;
     hipEvent_t p2lat_ev[2] = {nullptr, nullptr};
     uint16_t *p2lat_tab = nullptr; // class slot tables on the device (pgd_p2lat.hip), built once per context: (offset, class) of a slot ...
     int16_t *p2lat_slot = nullptr; // ... and the slot of (class, offset, class)
@@ -570,6 +575,17 @@ inline Block *get_block(Ctx *c, pgd_handle h) { return static_cast<Block *>(get_
     pgd::Ctx *c = pgd::get_ctx(h);            \
     if (!c) return PGD_ERR_INVALID;           \
     (void)hipSetDevice(c->device)
+
+// the bodies of the counter getters of the C ABI, one per record type (null pointers are skipped)
+#define PGD_PUT(p, v) do { if (p) *(p) = (v); } while (0)
+static inline int cycle_read(const CycleStats &s, int64_t *solves, int64_t *fallbacks, double *setup_ms, int64_t *march_passes) {
+    PGD_PUT(solves, s.solves); PGD_PUT(fallbacks, s.fallbacks); PGD_PUT(setup_ms, s.setup_ms); PGD_PUT(march_passes, s.marches);
+    return PGD_OK;
+}
+static inline int form_read(const FormStats &s, int64_t *forms_built, int64_t *products, int64_t *fallbacks, double *extract_ms) {
+    PGD_PUT(forms_built, s.forms); PGD_PUT(products, s.products); PGD_PUT(fallbacks, s.fallbacks); PGD_PUT(extract_ms, s.extract_ms);
+    return PGD_OK;
+}
 
 #define PGD_HIP(c, call)                                                                    \
     do {                                                                                    \

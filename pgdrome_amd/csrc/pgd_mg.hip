@@ -469,9 +469,7 @@ extern "C" {
 
 int pgd_mg_counts(pgd_handle h, int64_t *solves, int64_t *fallbacks) {
     PGD_CTX(c, h);
-    if (solves) *solves = c->mg_solves;
-    if (fallbacks) *fallbacks = c->mg_fallbacks;
-    return PGD_OK;
+    return cycle_read(c->cycle[PGD_PCG_PRECOND_MG], solves, fallbacks, nullptr, nullptr);
 }
 
 int pgd_mg_slab_setup(pgd_handle h, pgd_handle oh, int nz_global, int z_first, int64_t own0, int64_t own1, int64_t *n_coarse, int *applies) {

@@ -322,7 +322,7 @@ static int p2lat_ensure(Ctx *c, const Mesh *m, Csr *a, const P2Lattice &L) {
     PGD_HIP(c, hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     PGD_HIP(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c->p2lat_ev[0], c->p2lat_ev[1]) == hipSuccess) c->p2lat_extract_ms += (double)ms;
+    if (hipEventElapsedTime(&ms, c->p2lat_ev[0], c->p2lat_ev[1]) == hipSuccess) c->form[FORM_P2LAT].extract_ms += (double)ms;
     else (void)hipGetLastError();
     if (bad) {      // the form would not be the operator: it is dropped
         dev_release(c, a->p2lat, a->p2lat_bytes);
@@ -331,7 +331,7 @@ static int p2lat_ensure(Ctx *c, const Mesh *m, Csr *a, const P2Lattice &L) {
         return PGD_OK;
     }
     a->p2lat_ok = true;
-    c->p2lat_forms += 1;
+    c->form[FORM_P2LAT].forms += 1;
     return PGD_OK;
 }
 
@@ -347,7 +347,7 @@ int launch_spmv_p2lat(Ctx *c, const Mesh *m, Csr *a, const double *x, double *y,
         if (cap != hipStreamCaptureStatusNone) return PGD_OK;
         if (p2lat_lattice(c, m, &L)) PGD_TRY(p2lat_ensure(c, m, a, L));
         else { a->p2lat_seen = a->version; a->p2lat_ok = false; }
-        if (!a->p2lat_ok) c->p2lat_fallbacks += 1;
+        if (!a->p2lat_ok) c->form[FORM_P2LAT].fallbacks += 1;
     }
     if (!a->p2lat_ok || !a->p2lat || !c->p2lat_tab || !p2lat_lattice(c, m, &L)) return PGD_OK;
     const int R = c->spmv_rows;
@@ -379,7 +379,7 @@ int launch_spmv_p2lat(Ctx *c, const Mesh *m, Csr *a, const double *x, double *y,
     else PGD_P2LAT_LAUNCH(false, true);
 #undef PGD_P2LAT_LAUNCH
 #undef PGD_P2LAT_R
-    c->p2lat_products += 1;
+    c->form[FORM_P2LAT].products += 1;
     if (timed) {
         const double per_row = 8.0 * ((double)P2L_WV * A.nvr + (double)P2L_WE * (m->nv - A.nvr)) * m->ncomp / (double)std::max<int64_t>(m->nv, 1);
         PGD_TRY(prof_end(c, m, m->nv, per_row + 16.0 + (dot && w != x ? 8.0 : 0.0)));
@@ -396,16 +396,12 @@ extern "C" {
 
 int pgd_p2lat_counts(pgd_handle h, int64_t *forms_built, int64_t *products, int64_t *fallbacks) {
     PGD_CTX(c, h);
-    if (forms_built) *forms_built = c->p2lat_forms;
-    if (products) *products = c->p2lat_products;
-    if (fallbacks) *fallbacks = c->p2lat_fallbacks;
-    return PGD_OK;
+    return form_read(c->form[FORM_P2LAT], forms_built, products, fallbacks, nullptr);
 }
 
 int pgd_p2lat_times(pgd_handle h, double *extract_ms) {
     PGD_CTX(c, h);
-    if (extract_ms) *extract_ms = c->p2lat_extract_ms;
-    return PGD_OK;
+    return form_read(c->form[FORM_P2LAT], nullptr, nullptr, nullptr, extract_ms);
 }
 
 }  // extern "C"

@@ -1494,20 +1494,17 @@ static int pcg_precond_prepare(PcgRun &R) {
     Ctx *c = R.c;
     const Mesh *m = R.m;
     const int want = c->pcg_precond;
-    if (want == 1 && R.scaled && mg_prepare(c, m, R.o)) { R.precond = PGD_PCG_PRECOND_MG; c->mg_solves += 1; return mg_fix_start(c, R.o, R.b, R.x, R.n); }
-    if (want == 2 && R.scaled && m->sym_nx > 0 && vmg_prepare(c, c->vmg, m, R.o)) { R.precond = PGD_PCG_PRECOND_VMG; c->vmg_solves += 1; return vmg_fix_start(c, c->vmg, R.sc, R.b, R.x, R.n); }
+    if (want == 1 && R.scaled && mg_prepare(c, m, R.o)) { R.precond = PGD_PCG_PRECOND_MG; c->cycle[R.precond].solves += 1; return mg_fix_start(c, R.o, R.b, R.x, R.n); }
+    if (want == 2 && R.scaled && m->sym_nx > 0 && vmg_prepare(c, c->vmg, m, R.o)) { R.precond = PGD_PCG_PRECOND_VMG; c->cycle[R.precond].solves += 1; return vmg_fix_start(c, c->vmg, R.sc, R.b, R.x, R.n); }
     if (want == 3 && !R.scaled && m->ncomp >= 2) {
         PGD_TRY(ensure_vals(c, m, R.o));
-        if (cmg_prepare(c, m, get_mesh(c, m->base), R.o)) { R.precond = PGD_PCG_PRECOND_CMG; c->cmg_solves += 1; return cmg_fix_start(c, R.b, R.x, R.n); }
+        if (cmg_prepare(c, m, get_mesh(c, m->base), R.o)) { R.precond = PGD_PCG_PRECOND_CMG; c->cycle[R.precond].solves += 1; return cmg_fix_start(c, R.b, R.x, R.n); }
     }
     if (want == 4 && !R.scaled) {
         PGD_TRY(ensure_vals(c, m, R.o));
-        if (pmg_prepare(c, m, R.o)) { R.precond = PGD_PCG_PRECOND_PMG; c->pmg_solves += 1; return pmg_fix_start(c, R.b, R.x, R.n); }
+        if (pmg_prepare(c, m, R.o)) { R.precond = PGD_PCG_PRECOND_PMG; c->cycle[R.precond].solves += 1; return pmg_fix_start(c, R.b, R.x, R.n); }
     }
-    if (want == 1) c->mg_fallbacks += 1;
-    if (want == 2) c->vmg_fallbacks += 1;
-    if (want == 3) c->cmg_fallbacks += 1;
-    if (want == 4) c->pmg_fallbacks += 1;
+    if (want >= PGD_PCG_PRECOND_MG && want <= PGD_PCG_PRECOND_PMG) c->cycle[want].fallbacks += 1;
     return PGD_OK;
 }
 
@@ -1515,7 +1512,7 @@ static int pcg_precond_prepare(PcgRun &R) {
 static int pcg_precond_apply(PcgRun &R, const double *r, double *z_out, int *np) {
     switch (R.precond) {
     case PGD_PCG_PRECOND_MG: return mg_vcycle(R.c, r, true, np, z_out);
-    case PGD_PCG_PRECOND_VMG: return vmg_vcycle(R.c, R.c->vmg, r, true, np, z_out, &R.c->vmg_marches);
+    case PGD_PCG_PRECOND_VMG: return vmg_vcycle(R.c, R.c->vmg, r, true, np, z_out, &R.c->cycle[PGD_PCG_PRECOND_VMG].marches);
     case PGD_PCG_PRECOND_CMG: return cmg_apply(R.c, r, z_out ? z_out : R.z, R.n, np);
     case PGD_PCG_PRECOND_PMG: return pmg_apply(R.c, R.o, r, z_out ? z_out : R.z, R.n, np);
     case PGD_PCG_PRECOND_JACOBI: break;

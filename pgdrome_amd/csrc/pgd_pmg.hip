@@ -243,7 +243,7 @@ void pmg_note_setup(Ctx *c) {
     Pmg *G = c->pmg;
     if (!G || !G->timed) return;
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, G->ev0, G->ev1) == hipSuccess) c->pmg_setup_ms += (double)ms;
+    if (hipEventElapsedTime(&ms, G->ev0, G->ev1) == hipSuccess) c->cycle[PGD_PCG_PRECOND_PMG].setup_ms += (double)ms;
     else (void)hipGetLastError();
     G->timed = false;
 }
@@ -271,7 +271,7 @@ int pmg_apply(Ctx *c, const Csr *a, const double *r, double *z, int64_t n, int *
     else if (G->ncomp == 2) k_pmg_restrict<2><<<vmg_grid(g), 256, 0, c->stream>>>(g, G->nvert, r, G->el, G->v2e, bp, flags);
     else k_pmg_restrict<3><<<vmg_grid(g), 256, 0, c->stream>>>(g, G->nvert, r, G->el, G->v2e, bp, flags);
     PGD_LAUNCH_CHECK(c);
-    for (int k = 0; k < G->ncomp; ++k) PGD_TRY(vmg_vcycle(c, G->comp[k], bp.p[k], false, nullptr, nullptr, &c->pmg_marches));
+    for (int k = 0; k < G->ncomp; ++k) PGD_TRY(vmg_vcycle(c, G->comp[k], bp.p[k], false, nullptr, nullptr, &c->cycle[PGD_PCG_PRECOND_PMG].marches));
     if (G->ncomp == 1) k_pmg_prolong<1><<<gp, TPB, 0, c->stream>>>(n, nnode, G->par, G->el, a->dinv, r, xp, z, c->partials, flags);
     else if (G->ncomp == 2) k_pmg_prolong<2><<<gp, TPB, 0, c->stream>>>(n, nnode, G->par, G->el, a->dinv, r, xp, z, c->partials, flags);
     else k_pmg_prolong<3><<<gp, TPB, 0, c->stream>>>(n, nnode, G->par, G->el, a->dinv, r, xp, z, c->partials, flags);
@@ -345,17 +345,13 @@ int pgd_mesh_p2_bind(pgd_handle h, pgd_handle p2h, pgd_handle p1h, const int32_t
 
 int pgd_pmg_counts(pgd_handle h, int64_t *solves, int64_t *fallbacks, int64_t *levels) {
     PGD_CTX(c, h);
-    if (solves) *solves = c->pmg_solves;
-    if (fallbacks) *fallbacks = c->pmg_fallbacks;
-    if (levels) *levels = c->pmg ? vmg_levels(c->pmg->comp[0]) : 0;
-    return PGD_OK;
+    PGD_PUT(levels, c->pmg ? vmg_levels(c->pmg->comp[0]) : 0);
+    return cycle_read(c->cycle[PGD_PCG_PRECOND_PMG], solves, fallbacks, nullptr, nullptr);
 }
 
 int pgd_pmg_times(pgd_handle h, double *setup_ms, int64_t *march_passes) {
     PGD_CTX(c, h);
-    if (setup_ms) *setup_ms = c->pmg_setup_ms;
-    if (march_passes) *march_passes = c->pmg_marches;
-    return PGD_OK;
+    return cycle_read(c->cycle[PGD_PCG_PRECOND_PMG], nullptr, nullptr, setup_ms, march_passes);
 }
 
 int pgd_pmg_coarse(pgd_handle h, int comp, double *slots_out, uint8_t *el_out) {

@@ -2374,14 +2374,14 @@ int launch_spmv_op(Ctx *c, const Mesh *m, const Csr *a, const double *x, double 
         Csr *o = const_cast<Csr *>(a);
         o->bdia_seen = a->version;
         o->bdia_ok = false;
-        c->bdia_fallbacks += 1;
+        c->form[FORM_BDIA].fallbacks += 1;
     }
     if (c->spmv_p2_lattice && !a->immutable && r0 == 0 && (r1 < 0 || r1 == m->nv) && a->p2lat_seen != a->version && p2lat_degree2(c, m)) {
         // (likewise a degree-2 operator held in symmetric half storage - short rows, no 3-D P2 layout has them - keeps that product)
         Csr *o = const_cast<Csr *>(a);
         o->p2lat_seen = a->version;
         o->p2lat_ok = false;
-        c->p2lat_fallbacks += 1;
+        c->form[FORM_P2LAT].fallbacks += 1;
     }
     if (r1 < 0) r1 = m->nv;
     if (r0 < 0 || r0 > r1 || r1 > m->nv) return fail(c, PGD_ERR_INVALID, "spmv: bad row range");

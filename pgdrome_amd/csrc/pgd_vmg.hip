@@ -475,7 +475,7 @@ void vmg_note_setup(Ctx *c) {
     Vmg *M = c->vmg;
     if (!M || !M->timed) return;
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, M->ev0, M->ev1) == hipSuccess) c->vmg_setup_ms += (double)ms;
+    if (hipEventElapsedTime(&ms, M->ev0, M->ev1) == hipSuccess) c->cycle[PGD_PCG_PRECOND_VMG].setup_ms += (double)ms;
     else (void)hipGetLastError();
     M->timed = false;
 }
@@ -585,7 +585,7 @@ void cmg_note_setup(Ctx *c) {
     Cmg *G = c->cmg;
     if (!G || !G->timed) return;
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, G->ev0, G->ev1) == hipSuccess) c->cmg_setup_ms += (double)ms;
+    if (hipEventElapsedTime(&ms, G->ev0, G->ev1) == hipSuccess) c->cycle[PGD_PCG_PRECOND_CMG].setup_ms += (double)ms;
     else (void)hipGetLastError();
     G->timed = false;
 }
@@ -610,7 +610,7 @@ int cmg_apply(Ctx *c, const double *r, double *z, int64_t n, int *nparts) {
     const int g = grid_for(n);
     k_cmg_split<<<g, TPB, 0, c->stream>>>(G->ncomp, r, G->s, bp, n, c->flags);
     PGD_LAUNCH_CHECK(c);
-    for (int k = 0; k < G->ncomp; ++k) PGD_TRY(vmg_vcycle(c, G->comp[k], bp.p[k], false, nullptr, nullptr, &c->cmg_marches));
+    for (int k = 0; k < G->ncomp; ++k) PGD_TRY(vmg_vcycle(c, G->comp[k], bp.p[k], false, nullptr, nullptr, &c->cycle[PGD_PCG_PRECOND_CMG].marches));
     k_cmg_merge<<<g, TPB, 0, c->stream>>>(G->ncomp, xp, G->s, r, z, n, c->partials, c->flags);
     PGD_LAUNCH_CHECK(c);
     if (nparts) *nparts = g;
@@ -625,32 +625,24 @@ extern "C" {
 
 int pgd_vmg_counts(pgd_handle h, int64_t *solves, int64_t *fallbacks, int64_t *levels) {
     PGD_CTX(c, h);
-    if (solves) *solves = c->vmg_solves;
-    if (fallbacks) *fallbacks = c->vmg_fallbacks;
-    if (levels) *levels = vmg_levels(c->vmg);
-    return PGD_OK;
+    PGD_PUT(levels, vmg_levels(c->vmg));
+    return cycle_read(c->cycle[PGD_PCG_PRECOND_VMG], solves, fallbacks, nullptr, nullptr);
 }
 
 int pgd_vmg_times(pgd_handle h, double *setup_ms, int64_t *march_passes) {
     PGD_CTX(c, h);
-    if (setup_ms) *setup_ms = c->vmg_setup_ms;
-    if (march_passes) *march_passes = c->vmg_marches;
-    return PGD_OK;
+    return cycle_read(c->cycle[PGD_PCG_PRECOND_VMG], nullptr, nullptr, setup_ms, march_passes);
 }
 
 int pgd_cmg_counts(pgd_handle h, int64_t *solves, int64_t *fallbacks, int64_t *levels) {
     PGD_CTX(c, h);
-    if (solves) *solves = c->cmg_solves;
-    if (fallbacks) *fallbacks = c->cmg_fallbacks;
-    if (levels) *levels = c->cmg ? vmg_levels(c->cmg->comp[0]) : 0;
-    return PGD_OK;
+    PGD_PUT(levels, c->cmg ? vmg_levels(c->cmg->comp[0]) : 0);
+    return cycle_read(c->cycle[PGD_PCG_PRECOND_CMG], solves, fallbacks, nullptr, nullptr);
 }
 
 int pgd_cmg_times(pgd_handle h, double *setup_ms, int64_t *march_passes) {
     PGD_CTX(c, h);
-    if (setup_ms) *setup_ms = c->cmg_setup_ms;
-    if (march_passes) *march_passes = c->cmg_marches;
-    return PGD_OK;
+    return cycle_read(c->cycle[PGD_PCG_PRECOND_CMG], nullptr, nullptr, setup_ms, march_passes);
 }
 
 }  // extern "C"

@@ -28,6 +28,9 @@ explicitly with ``set_backend``.
 """
 from __future__ import annotations
 
+import collections
+import contextlib
+import functools
 import itertools
 import logging
 import math
@@ -3651,181 +3654,6 @@ def _rescale_start(lay, op, b, x):
     return coef
 
 
-def _solve_linear(A, b, x, prm):
-    """Solve A x = b on the device.  A: Matrix (BCs already registered), b: Vector (BC values set).
-
-    1-D meshes (time / parameter dimensions, possibly non-symmetric) use the banded
-    LU kernel - the counterpart of the reference's MUMPS solve; larger SPD systems
-    use Jacobi-PCG with `relative_tolerance` (default 1e-10) from the settings."""
-    be, mesh = get_backend(), A.mesh()
-    method = str(prm.get("linear_solver", "default"))
-    n = A.lay.n
-    op = A.op()
-    info = {}
-    # the rows' partition and what the communicator takes for "the mesh": the layout's (a vector-valued space has ncomp rows per vertex)
-    part, view = A.lay.part, (A.lay.shard_view() if A.lay.part is not None else mesh)
-    try:
-        use_direct = mesh.topology().dim() == 1 and n <= SMALL_DIRECT_N and part is None
-        nonsym = not use_direct and not A.is_symmetric()
-        if use_direct:
-            be.band_solve(op, b.dev(), x.dev_for_write())
-            x.touched_dev()
-            info.update(method="band_lu", iterations=1)
-        elif nonsym:
-            # a convection atom on a 2-D / 3-D space (or a 1-D system beyond the banded LU): BiCGStab with Jacobi scaling on the
-            # CSR product (csrc/pgd_krylov.hip) where the reference's MUMPS solves whatever the callbacks produce
-            # (solver.py:627-636); same relative_tolerance / maximum_iterations / error_on_nonconvergence semantics as the PCG
-            rtol = float(prm.get("relative_tolerance", 1e-10)) if not isinstance(prm.get("relative_tolerance"), _Params) else 1e-10
-            atol = float(prm.get("absolute_tolerance", 0.0)) if not isinstance(prm.get("absolute_tolerance"), _Params) else 0.0
-            maxit = int(prm.get("maximum_iterations", 20000)) if not isinstance(prm.get("maximum_iterations"), _Params) else 20000
-            t_solve = time.perf_counter()
-            if part is not None:
-                # (row-sharded: the same recurrence driven over the communicator - pgdrome_amd/dist.py::TorchComm.bicgstab;
-                # is_symmetric() reads the forms' coefficients, which are all-reduced numbers: every rank takes this branch or none)
-                it, rel = part.comm.bicgstab(view, op, b, x, rtol, atol, maxit)
-            else:
-                it, rel = be.bicgstab(op, b.dev(), x.dev(), rtol, atol, maxit)
-            x.touched_dev()
-            STATS["bicgstab_seconds"] = STATS.get("bicgstab_seconds", 0.0) + time.perf_counter() - t_solve
-            STATS["bicgstab_iterations"] = STATS.get("bicgstab_iterations", 0) + it
-            info.update(method="jacobi_bicgstab", iterations=it, relres=rel)
-            if rel > max(rtol, 1e-14) * 1.0001 and (atol <= 0.0 or it >= maxit):
-                msg = "BiCGStab did not reach rtol %g in %d iterations (relres %g)" % (rtol, it, rel)
-                eon = prm.get("error_on_nonconvergence", True)
-                if isinstance(eon, _Params) or eon:
-                    raise RuntimeError(msg)
-                LOG.error(msg)
-        else:
-            rtol = float(prm.get("relative_tolerance", 1e-10)) if not isinstance(prm.get("relative_tolerance"), _Params) else 1e-10
-            atol = float(prm.get("absolute_tolerance", 0.0)) if not isinstance(prm.get("absolute_tolerance"), _Params) else 0.0
-            maxit = int(prm.get("maximum_iterations", 20000)) if not isinstance(prm.get("maximum_iterations"), _Params) else 20000
-            # settings["spectral_start"] = k: the second level of the Galerkin start, over k Ritz vectors harvested once per space
-            # and Dirichlet set (pgdrome_amd/spectral.py); the harvest itself is one-time work and stays out of the solve's clock
-            k_spec = spectral.requested(prm) if n >= spectral.MIN_ROWS else 0
-            spec = spectral.get(sys.modules[__name__], A, b, k_spec, prm) if k_spec != 0 else None
-            t_solve = time.perf_counter()
-            start_coefs = None
-            if WARM_START_RESCALE and not x._zero:
-                start_coefs = _rescale_start(A.lay, op, b, x)
-            if spec is not None:
-                spec.correct(sys.modules[__name__], A, op, b, x, start_coefs)
-            # settings["preconditioner"] (forwarded to PETSc by the reference, solver.py:593-594): the multigrid family asks for
-            # the V-cycle of pgd_mg.hip, which the library uses where the operator has the structure for it and says so in its
-            # counters; every other value is the Jacobi-PCG.  The row-sharded solve has the Jacobi form only.
-            # VARIABLE_MULTIGRID_NAMES (opt-in) ask for the V-cycle of pgd_vmg.hip instead: any scalar P1 operator on a lattice
-            # mesh, any Dirichlet set.  A backend without it (the numpy oracle) and a row-sharded layout answer with the Jacobi-PCG.
-            # COMPONENT_MULTIGRID_NAMES (opt-in) ask for one such cycle per component of a vector-valued P1 space on a box lattice
-            # (the diagonal blocks of the operator); "amg" and "vmg" on a vector space stay the Jacobi-PCG.
-            prec = prm.get("preconditioner", "default")
-            prec_name = "" if isinstance(prec, _Params) else str(prec).lower()
-            asks_mg = prec_name in MULTIGRID_NAMES
-            want_mg = asks_mg and part is None
-            want_vmg = prec_name in VARIABLE_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_variable")
-            want_cmg = prec_name in COMPONENT_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_component")
-            # P_MULTIGRID_NAMES (opt-in) ask for the p-multigrid cycle of pgd_pmg.hip: P2 spaces (scalar or vector-valued) on a 3-D box
-            # lattice, through the P1 V-cycles on P^T A P.  A degree-2 layout on a 3-D mesh is bound to its vertex lattice on the first
-            # such request (DofLayout.bind_p2_lattice).  The degree and the dimension decide only whether a binding is OFFERED, not
-            # whether the library is asked: the request reaches it for every unsharded space - a departure from routing "pmg" in the
-            # frontend only for degree 2 on a 3-D mesh - so that a P1 or a 2-D space under these names is a fallback the library
-            # COUNTS (pgd_pmg_counts), like a 3-D P2 space it refuses to bind; all of them are the Jacobi-PCG.
-            want_pmg = prec_name in P_MULTIGRID_NAMES and part is None and hasattr(be, "precondition_p")
-            if want_pmg:
-                A.lay.bind_p2_lattice(be)
-            prod = prm.get("block_product", "csr")
-            prod_name = "csr" if isinstance(prod, _Params) else str(prod).lower()
-            if prod_name not in BLOCK_PRODUCT_NAMES:      # (before any knob is switched)
-                raise ValueError("settings['block_product']: expected one of %s, got %r" % (BLOCK_PRODUCT_NAMES, prod))
-            # settings["p2_product"] = "lattice" (opt-in, default "csr"): the products of a P2 space (scalar or vector-valued) on a 3-D
-            # box lattice from the operator's row-class form (csrc/pgd_p2lat.hip) - the same numbers, bit for bit.  The request binds
-            # a degree-2 layout on a 3-D mesh to its vertex lattice like a "pmg" request does; the library says in its counters
-            # whether the operator had a form.  A backend without it, a row-sharded layout and a degree-1 space ignore
-            # the key.  (on a degree-2 space the counter is read either way: PGD_TUNE=59=1 switches whole runs without the key)
-            p2prod = prm.get("p2_product", "csr")
-            p2prod_name = "csr" if isinstance(p2prod, _Params) else str(p2prod).lower()
-            if p2prod_name not in P2_PRODUCT_NAMES:       # (before any knob is switched)
-                raise ValueError("settings['p2_product']: expected one of %s, got %r" % (P2_PRODUCT_NAMES, p2prod))
-            has_pl = part is None and getattr(A.lay, "degree", 1) == 2 and hasattr(be, "p2_product") and hasattr(be, "p2lat_stats")
-            want_pl = has_pl and p2prod_name == "lattice"
-            if want_pl:
-                A.lay.bind_p2_lattice(be)
-            mg0 = vmg0 = cmg0 = pmg0 = None
-            used = used_v = used_c = used_p = 0
-            if want_mg and hasattr(be, "precondition"):
-                mg0 = be.precondition(1)
-            elif want_vmg:
-                vmg0 = be.precondition_variable(True)
-            elif want_cmg:
-                cmg0 = be.precondition_component(True)
-            elif want_pmg:
-                pmg0 = be.precondition_p(True)
-            # settings["block_product"] = "diagonal" (opt-in, default "csr"): the products of a vector-valued P1 space on a box
-            # lattice from the operator's row-diagonal form (csrc/pgd_bdia.hip) - the same numbers, bit for bit; the library says
-            # in its counters whether the operator had one.  A backend without it and a row-sharded layout ignore the key.
-            # (the counter is read either way: PGD_TUNE=58=1 switches whole runs without the key)
-            has_bd = part is None and getattr(A.lay, "ncomp", 1) > 1 and hasattr(be, "block_product") and hasattr(be, "bdia_stats")
-            want_bd = has_bd and prod_name == "diagonal"
-            bd0 = (be.block_product(True) if want_bd else be.bdia_stats()["products"]) if has_bd else None
-            used_b = 0
-            pl0 = (be.p2_product(True) if want_pl else be.p2lat_stats()["products"]) if has_pl else None
-            used_l = 0
-            try:
-                if part is not None:
-                    # a row-sharded lattice: the V-cycle with level 0 on the slabs and levels >= 1 replicated (dist.pcg_mg);
-                    # where it does not apply on some rank every rank takes the Jacobi-PCG (decided by an all-reduce)
-                    got = part.comm.pcg_mg(view, op, b, x, rtol, atol, maxit) if asks_mg and hasattr(part.comm, "pcg_mg") else None
-                    if got is not None:
-                        it, rel = got
-                        used = 1
-                    else:
-                        it, rel = part.comm.pcg(view, op, b, x, rtol, atol, maxit)
-                else:
-                    it, rel = be.pcg(op, b.dev(), x.dev(), rtol, atol, maxit)
-                    x.touched_dev()
-            finally:
-                if mg0 is not None:
-                    used = be.precondition(0) - mg0
-                if vmg0 is not None:
-                    used_v = be.precondition_variable(False) - vmg0
-                if cmg0 is not None:
-                    used_c = be.precondition_component(False) - cmg0
-                if pmg0 is not None:
-                    used_p = be.precondition_p(False) - pmg0
-                if bd0 is not None:
-                    used_b = (be.block_product(False) if want_bd else be.bdia_stats()["products"]) - bd0
-                if pl0 is not None:
-                    used_l = (be.p2_product(False) if want_pl else be.p2lat_stats()["products"]) - pl0
-            STATS["pcg_seconds"] += time.perf_counter() - t_solve      # the solve returns synchronised
-            info.update(method="mg_pcg" if used > 0 else "vmg_pcg" if used_v > 0 else "cmg_pcg" if used_c > 0 else "pmg_pcg" if used_p > 0 else "jacobi_pcg",
-                        iterations=it, relres=rel)
-            if used > 0:
-                STATS["mg_solves"] = STATS.get("mg_solves", 0) + 1
-            if used_v > 0:
-                STATS["vmg_solves"] = STATS.get("vmg_solves", 0) + 1
-            if used_c > 0:
-                STATS["cmg_solves"] = STATS.get("cmg_solves", 0) + 1
-            if used_p > 0:
-                STATS["pmg_solves"] = STATS.get("pmg_solves", 0) + 1
-            info["product"] = "p2_lattice" if used_l > 0 else "block_dia" if used_b > 0 else "csr"
-            if used_b > 0:
-                STATS["block_dia_solves"] = STATS.get("block_dia_solves", 0) + 1
-            if used_l > 0:
-                STATS["p2_lattice_solves"] = STATS.get("p2_lattice_solves", 0) + 1
-            if rel > max(rtol, 1e-14) * 1.0001 and it >= maxit:
-                # dolfin's Krylov solvers raise on non-convergence unless told otherwise (error_on_nonconvergence,
-                # default True): an unconverged mode must not be stored silently
-                msg = "PCG did not reach rtol %g in %d iterations (relres %g)" % (rtol, it, rel)
-                eon = prm.get("error_on_nonconvergence", True)
-                if isinstance(eon, _Params) or eon:
-                    raise RuntimeError(msg)
-                LOG.error(msg)
-        LOG.debug("linear solve (%s requested): %s", method, info)
-    finally:
-        be.atom_free(op)
-    STATS["linear_solves"] += 1
-    STATS["pcg_iterations"] += info.get("iterations", 0) if info.get("method") in ("jacobi_pcg", "mg_pcg", "vmg_pcg", "cmg_pcg", "pmg_pcg") else 0
-    return info
-
-
 STATS = {"linear_solves": 0, "pcg_iterations": 0, "pcg_seconds": 0.0, "mg_solves": 0, "vmg_solves": 0, "cmg_solves": 0, "pmg_solves": 0}
 # values of settings["preconditioner"] that select the geometric multigrid V-cycle (dolfin's names of its algebraic ones included)
 MULTIGRID_NAMES = ("amg", "hypre_amg", "petsc_amg", "ml_amg", "gmg", "multigrid", "mg")
@@ -3839,6 +3667,200 @@ P_MULTIGRID_NAMES = ("pmg", "p_multigrid")
 BLOCK_PRODUCT_NAMES = ("csr", "diagonal")
 # values of settings["p2_product"]: the product of a P2 operator on a 3-D box lattice from CSR or from its row-class form
 P2_PRODUCT_NAMES = ("csr", "lattice")
+
+# One row per cycle that settings["preconditioner"] can ask for: its names, the backend's selector with its on / off arguments
+# (the selector returns the number of solves the cycle has preconditioned so far), the communicator's solve that stands in for it on
+# a row-sharded layout (None: that layout has the Jacobi form only), whether a request offers DofLayout.bind_p2_lattice first, what
+# info["method"] says where the cycle was used and the STATS key that counts those solves.
+_Cycle = collections.namedtuple("_Cycle", "names selector on off sharded binds method stat")
+PRECONDITIONERS = (
+    # settings["preconditioner"] (forwarded to PETSc by the reference, solver.py:593-594): the multigrid family asks for
+    # the V-cycle of pgd_mg.hip, which the library uses where the operator has the structure for it and says so in its
+    # counters; every other value is the Jacobi-PCG.  The row-sharded solve has the Jacobi form only - but for this family on
+    # a row-sharded lattice: the V-cycle with level 0 on the slabs and levels >= 1 replicated (dist.pcg_mg); where it does not
+    # apply on some rank every rank takes the Jacobi-PCG (decided by an all-reduce)
+    _Cycle(MULTIGRID_NAMES, "precondition", 1, 0, "pcg_mg", False, "mg_pcg", "mg_solves"),
+    # VARIABLE_MULTIGRID_NAMES (opt-in) ask for the V-cycle of pgd_vmg.hip instead: any scalar P1 operator on a lattice
+    # mesh, any Dirichlet set.  A backend without it (the numpy oracle) and a row-sharded layout answer with the Jacobi-PCG.
+    _Cycle(VARIABLE_MULTIGRID_NAMES, "precondition_variable", True, False, None, False, "vmg_pcg", "vmg_solves"),
+    # COMPONENT_MULTIGRID_NAMES (opt-in) ask for one such cycle per component of a vector-valued P1 space on a box lattice
+    # (the diagonal blocks of the operator); "amg" and "vmg" on a vector space stay the Jacobi-PCG.
+    _Cycle(COMPONENT_MULTIGRID_NAMES, "precondition_component", True, False, None, False, "cmg_pcg", "cmg_solves"),
+    # P_MULTIGRID_NAMES (opt-in) ask for the p-multigrid cycle of pgd_pmg.hip: P2 spaces (scalar or vector-valued) on a 3-D box
+    # lattice, through the P1 V-cycles on P^T A P.  A degree-2 layout on a 3-D mesh is bound to its vertex lattice on the first
+    # such request (DofLayout.bind_p2_lattice).  The degree and the dimension decide only whether a binding is OFFERED, not
+    # whether the library is asked: the request reaches it for every unsharded space - a departure from routing "pmg" in the
+    # frontend only for degree 2 on a 3-D mesh - so that a P1 or a 2-D space under these names is a fallback the library
+    # COUNTS (pgd_pmg_counts), like a 3-D P2 space it refuses to bind; all of them are the Jacobi-PCG.
+    _Cycle(P_MULTIGRID_NAMES, "precondition_p", True, False, None, True, "pmg_pcg", "pmg_solves"),
+)
+
+# One row per product form: the settings key, its allowed values (the first is the default) and the one that switches the form on,
+# the backend's selector (True / False; returns the number of products launched from the form so far) and its stats method (whose
+# "products" is that number), which layouts can have the form, whether a request offers DofLayout.bind_p2_lattice first, what
+# info["product"] says where the form was used (the later row where two were) and the STATS key that counts those solves.
+_Form = collections.namedtuple("_Form", "key values on selector stats applies binds product stat")
+PRODUCT_FORMS = (
+    # settings["block_product"] = "diagonal" (opt-in, default "csr"): the products of a vector-valued P1 space on a box
+    # lattice from the operator's row-diagonal form (csrc/pgd_bdia.hip) - the same numbers, bit for bit; the library says
+    # in its counters whether the operator had one.  A backend without it and a row-sharded layout ignore the key.
+    # (the counter is read either way: PGD_TUNE=58=1 switches whole runs without the key)
+    _Form("block_product", BLOCK_PRODUCT_NAMES, "diagonal", "block_product", "bdia_stats",
+          lambda lay: getattr(lay, "ncomp", 1) > 1, False, "block_dia", "block_dia_solves"),
+    # settings["p2_product"] = "lattice" (opt-in, default "csr"): the products of a P2 space (scalar or vector-valued) on a 3-D
+    # box lattice from the operator's row-class form (csrc/pgd_p2lat.hip) - the same numbers, bit for bit.  The request binds
+    # a degree-2 layout on a 3-D mesh to its vertex lattice like a "pmg" request does; the library says in its counters
+    # whether the operator had a form.  A backend without it, a row-sharded layout and a degree-1 space ignore
+    # the key.  (on a degree-2 space the counter is read either way: PGD_TUNE=59=1 switches whole runs without the key)
+    _Form("p2_product", P2_PRODUCT_NAMES, "lattice", "p2_product", "p2lat_stats",
+          lambda lay: getattr(lay, "degree", 1) == 2, True, "p2_lattice", "p2_lattice_solves"),
+)
+# the settings a nonlinear solve hands on to its linear solves
+LINEAR_SOLVE_KEYS = ("linear_solver", "preconditioner") + tuple(f.key for f in PRODUCT_FORMS)
+
+
+def _setting(prm, key, default, cast=None):
+    """settings[key], cast; the default where the key is absent or was touched but never set (an empty _Params sits there)."""
+    v = prm.get(key, default)
+    if isinstance(v, _Params):
+        v = default
+    return v if cast is None else cast(v)
+
+
+def _tolerances(prm):
+    return (_setting(prm, "relative_tolerance", 1e-10, float), _setting(prm, "absolute_tolerance", 0.0, float),
+            _setting(prm, "maximum_iterations", 20000, int))
+
+
+def _report_nonconvergence(prm, failed, solver, rtol, it, rel):
+    """dolfin's Krylov solvers raise on non-convergence unless told otherwise (error_on_nonconvergence,
+    default True): an unconverged mode must not be stored silently"""
+    if not failed:
+        return
+    msg = "%s did not reach rtol %g in %d iterations (relres %g)" % (solver, rtol, it, rel)
+    if _setting(prm, "error_on_nonconvergence", True):
+        raise RuntimeError(msg)
+    LOG.error(msg)
+
+
+@contextlib.contextmanager
+def _switched_on(be, lay, cycle, forms):
+    """Switch on the cycle (a row of PRECONDITIONERS or None) and the product forms ([(row of PRODUCT_FORMS, asked for)]; a form
+    not asked for is only watched through its stats) for the solve inside; on the way out, exception or not, switch every one of
+    them off again.  Yields a dict that then holds, per row's STATS key, how far its counter advanced."""
+    for row, wanted in [(cycle, cycle is not None)] + forms:
+        if wanted and row.binds:
+            lay.bind_p2_lattice(be)
+    used, watch = {}, []         # watch: (STATS key, the counter at the start, what switches off and reads it again)
+    try:
+        if cycle is not None:
+            select = getattr(be, cycle.selector)
+            watch.append((cycle.stat, select(cycle.on), functools.partial(select, cycle.off)))
+        for row, wanted in forms:
+            if wanted:
+                select = getattr(be, row.selector)
+                watch.append((row.stat, select(True), functools.partial(select, False)))
+            else:
+                read = getattr(be, row.stats)
+                watch.append((row.stat, read()["products"], lambda read=read: read()["products"]))
+        yield used
+    finally:
+        for stat, start, off in watch:
+            used[stat] = off() - start
+
+
+def _solve_band(be, A, op, b, x, prm):
+    be.band_solve(op, b.dev(), x.dev_for_write())
+    x.touched_dev()
+    return dict(method="band_lu", iterations=1)
+
+
+def _solve_bicgstab(be, A, op, b, x, prm):
+    """A convection atom on a 2-D / 3-D space (or a 1-D system beyond the banded LU): BiCGStab with Jacobi scaling on the
+    CSR product (csrc/pgd_krylov.hip) where the reference's MUMPS solves whatever the callbacks produce
+    (solver.py:627-636); same relative_tolerance / maximum_iterations / error_on_nonconvergence semantics as the PCG"""
+    rtol, atol, maxit = _tolerances(prm)
+    part = A.lay.part
+    t_solve = time.perf_counter()
+    if part is not None:
+        # (row-sharded: the same recurrence driven over the communicator - pgdrome_amd/dist.py::TorchComm.bicgstab;
+        # is_symmetric() reads the forms' coefficients, which are all-reduced numbers: every rank takes this branch or none)
+        it, rel = part.comm.bicgstab(A.lay.shard_view(), op, b, x, rtol, atol, maxit)
+    else:
+        it, rel = be.bicgstab(op, b.dev(), x.dev(), rtol, atol, maxit)
+    x.touched_dev()
+    STATS["bicgstab_seconds"] = STATS.get("bicgstab_seconds", 0.0) + time.perf_counter() - t_solve
+    STATS["bicgstab_iterations"] = STATS.get("bicgstab_iterations", 0) + it
+    _report_nonconvergence(prm, rel > max(rtol, 1e-14) * 1.0001 and (atol <= 0.0 or it >= maxit), "BiCGStab", rtol, it, rel)
+    return dict(method="jacobi_bicgstab", iterations=it, relres=rel)
+
+
+def _solve_pcg(be, A, op, b, x, prm):
+    """Jacobi-PCG, or the PCG under the cycle of PRECONDITIONERS that settings["preconditioner"] names, with the products from the
+    forms of PRODUCT_FORMS that the settings ask for: where the backend has them and the rows are not sharded."""
+    lay, part = A.lay, A.lay.part
+    rtol, atol, maxit = _tolerances(prm)
+    prec_name = _setting(prm, "preconditioner", "default", lambda v: str(v).lower())
+    asked = next((row for row in PRECONDITIONERS if prec_name in row.names), None)
+    cycle = asked if asked is not None and part is None and hasattr(be, asked.selector) else None
+    forms = []
+    for row in PRODUCT_FORMS:        # (both keys are checked before anything is bound or switched)
+        value = _setting(prm, row.key, row.values[0])
+        if str(value).lower() not in row.values:
+            raise ValueError("settings['%s']: expected one of %s, got %r" % (row.key, row.values, value))
+        if part is None and row.applies(lay) and hasattr(be, row.selector) and hasattr(be, row.stats):
+            forms.append((row, str(value).lower() == row.on))
+    # settings["spectral_start"] = k: the second level of the Galerkin start, over k Ritz vectors harvested once per space
+    # and Dirichlet set (pgdrome_amd/spectral.py); the harvest itself is one-time work and stays out of the solve's clock
+    k_spec = spectral.requested(prm) if lay.n >= spectral.MIN_ROWS else 0
+    spec = spectral.get(sys.modules[__name__], A, b, k_spec, prm) if k_spec != 0 else None
+    t_solve = time.perf_counter()
+    start_coefs = None
+    if WARM_START_RESCALE and not x._zero:
+        start_coefs = _rescale_start(lay, op, b, x)
+    if spec is not None:
+        spec.correct(sys.modules[__name__], A, op, b, x, start_coefs)
+    got = None
+    with _switched_on(be, lay, cycle, forms) as used:
+        if part is None:
+            it, rel = be.pcg(op, b.dev(), x.dev(), rtol, atol, maxit)
+            x.touched_dev()
+        else:
+            # the rows' partition and what the communicator takes for "the mesh": the layout's (a vector-valued space has ncomp rows per vertex)
+            view = lay.shard_view()
+            if asked is not None and asked.sharded and hasattr(part.comm, asked.sharded):
+                got = getattr(part.comm, asked.sharded)(view, op, b, x, rtol, atol, maxit)
+            it, rel = got if got is not None else part.comm.pcg(view, op, b, x, rtol, atol, maxit)
+    if got is not None:
+        used[asked.stat] = 1
+    STATS["pcg_seconds"] += time.perf_counter() - t_solve      # the solve returns synchronised
+    for stat, advanced in used.items():
+        if advanced > 0:
+            STATS[stat] = STATS.get(stat, 0) + 1
+    info = dict(method=next((row.method for row in PRECONDITIONERS if used.get(row.stat, 0) > 0), "jacobi_pcg"), iterations=it, relres=rel,
+                product=next((row.product for row in reversed(PRODUCT_FORMS) if used.get(row.stat, 0) > 0), "csr"))
+    _report_nonconvergence(prm, rel > max(rtol, 1e-14) * 1.0001 and it >= maxit, "PCG", rtol, it, rel)
+    return info
+
+
+def _solve_linear(A, b, x, prm):
+    """Solve A x = b on the device.  A: Matrix (BCs already registered), b: Vector (BC values set).
+
+    1-D meshes (time / parameter dimensions, possibly non-symmetric) use the banded
+    LU kernel - the counterpart of the reference's MUMPS solve; larger SPD systems
+    use Jacobi-PCG with `relative_tolerance` (default 1e-10) from the settings."""
+    be = get_backend()
+    op = A.op()
+    try:
+        use_direct = A.mesh().topology().dim() == 1 and A.lay.n <= SMALL_DIRECT_N and A.lay.part is None
+        solve = _solve_band if use_direct else _solve_pcg if A.is_symmetric() else _solve_bicgstab
+        info = solve(be, A, op, b, x, prm)
+        LOG.debug("linear solve (%s requested): %s", str(prm.get("linear_solver", "default")), info)
+    finally:
+        be.atom_free(op)
+    STATS["linear_solves"] += 1
+    STATS["pcg_iterations"] += info["iterations"] if solve is _solve_pcg else 0
+    return info
 
 
 def _apply_bcs_system(A, b, bcs):
@@ -3918,9 +3940,8 @@ class NonlinearVariationalSolver:
             h = DirichletBC.__new__(DirichletBC)
             h._V, h._vertices, h._vals = bc._V, bc._vertices, np.zeros_like(bc._vals)
             bcs_h.append(h)
-        lin = _Params({k: v for k, v in ns.items() if k in ("linear_solver", "preconditioner", "block_product", "p2_product")})
-        lin["relative_tolerance"] = ns.get("krylov_relative_tolerance", 1e-10) \
-            if not isinstance(ns.get("krylov_relative_tolerance"), _Params) else 1e-10
+        lin = _Params({k: v for k, v in ns.items() if k in LINEAR_SOLVE_KEYS})
+        lin["relative_tolerance"] = _setting(ns, "krylov_relative_tolerance", 1e-10)
         rtol, atol, maxit = float(ns["relative_tolerance"]), float(ns["absolute_tolerance"]), int(ns["maximum_iterations"])
         r = self._residual(bcs_h)
         r0 = r.norm("l2")

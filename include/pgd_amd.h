@@ -519,7 +519,7 @@ int pgd_cell_gradient(pgd_handle ctx, pgd_handle mesh, pgd_handle u, const doubl
  * PGD_EVAL_STATS is set, no atomics, every output bit-identical for any grid size and chunk length, both variants of
  * PGD_TUNE_EVAL_VARIANT.  The matrix-unit kernel keeps the q planes of a block of 64, 32 or 16 entries in LDS (up to 160 KiB
  * for 16) and reads them from global memory where even that does not fit (q * k above about 1100): slower, same bits.
- * Signed components need no new call: pgd_eval_batch on the one plane of a one-row L gives them.                          */
+ * Signed components and eigenvalues of the planes: pgd_eval_batch_quantity, further down.                                */
 int pgd_eval_batch_norm(pgd_handle ctx, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want,
                         double threshold, double *sample_stats, pgd_handle env_min, pgd_handle env_max, pgd_handle exceed,
                         pgd_handle fields);
@@ -534,7 +534,7 @@ int pgd_eval_batch_norm(pgd_handle ctx, const pgd_handle *modes, int k, int q, c
  * with a message, before anything is launched, for everything pgd_eval_batch and pgd_cell_gradient refuse (a P2 layout, a layout
  * without cell records, q out of range, a null L, modes of another length than nv*ncomp, a scale of another length than nc) and for
  * an output aliasing a mode or the scale.  nc == 0 is PGD_OK.
- * Limits: P1 layouts; norms only; the matrix-unit kernel has no fallback to global memory, so where the q planes of 16 cells do not
+ * Limits: P1 layouts; the matrix-unit kernel has no fallback to global memory, so where the q planes of 16 cells do not
  * fit 160 KiB of LDS (q * 4 ceil(k / 4) above about 1250) the call is refused with PGD_ERR_LIMIT before anything is launched
  * (PGD_TUNE_EVAL_VARIANT = 0 has no such limit); every sample chunk gathers the nodal values and forms the planes again, so calls
  * of few samples are dominated by the gathers - where the planes fit in memory and are reused, the two-stage path reads less. */
@@ -571,6 +571,44 @@ int pgd_cell_gradient_p2(pgd_handle ctx, pgd_handle mesh, pgd_handle u, const do
 int pgd_eval_batch_grad_p2(pgd_handle ctx, pgd_handle mesh, const pgd_handle *modes, int k, const double *lam, int npt,
                            const double *L, int q, pgd_handle scale_or_0, const double *coefs, int64_t s, int want, double threshold,
                            double *sample_stats, pgd_handle env_min, pgd_handle env_max, pgd_handle exceed, pgd_handle fields);
+
+/* --------------------------------------- other values of the combined planes --- */
+/* What becomes of the q combined planes u_0 .. u_{q-1} of an entry and sample before the reductions.  The norm is one choice;
+ * failure criteria that tell tension from compression (the largest principal stress of a brittle material, Tresca) are
+ * eigenvalue functions of the stress tensor, which a sum of squares taken plane by plane cannot form.
+ *   PGD_EVAL_Q_NORM        sqrt(sum_i u_i^2): what the three calls above compute, bit for bit.
+ *   PGD_EVAL_Q_VALUE       q = 1: u_0 with its sign - the accumulator of pgd_eval_batch on that plane, bit for bit.
+ *   PGD_EVAL_Q_EIG_MAX     the largest eigenvalue of the symmetric tensor whose planes are xx, yy, zz, xy, yz, xz (q = 6) or
+ *   PGD_EVAL_Q_EIG_MIN     xx, yy, zz, xy with yz = xz = 0 (q = 4: plane strain);  the smallest;
+ *   PGD_EVAL_Q_EIG_SPREAD  largest minus smallest (twice the largest shear stress: Tresca), never negative.
+ * The eigenvalues come from a deflating form: with m = tr / 3, p^2 = |sigma - m I|_F^2 / 6, C = (sigma - m I) / p only the root
+ * of the characteristic polynomial that is separated from the other two is taken from the angle acos(det C / 2) / 3, its
+ * eigenvector from the largest cross product of two rows of C - lambda I, the other two eigenvalues from the 2 x 2 problem on
+ * the plane orthogonal to it, the isolated one again as a Rayleigh quotient.  Every eigenvalue is off by a few units of
+ * 2^-53 |sigma|_F beyond what the errors of the u_i move it by (Weyl: at most their Frobenius norm), also where two eigenvalues
+ * coincide - where the three roots taken from the angle alone lose half the digits.  p = 0 gives m.  Tensors whose squares
+ * over- or underflow are not served.
+ * With signed values max |.| (row 2 of sample_stats) is max(|min|, |max|) and no copy of max. */
+enum pgd_eval_quantity {
+    PGD_EVAL_Q_NORM = 0, PGD_EVAL_Q_VALUE = 1, PGD_EVAL_Q_EIG_MAX = 2, PGD_EVAL_Q_EIG_MIN = 3, PGD_EVAL_Q_EIG_SPREAD = 4
+};
+/* pgd_eval_batch_norm, pgd_eval_batch_grad and pgd_eval_batch_grad_p2 with the kind (a pgd_eval_quantity) after q; those three are
+ * kind 0 of these.  Everything they state holds - arguments, outputs, want bits, chunks, no atomics, bit-identical outputs for
+ * any grid size and chunk length, both variants of PGD_TUNE_EVAL_VARIANT, the PGD_ERR_LIMIT rule of the fused calls,
+ * pgd_eval_norm_last_shape - with the value of the kind in the place of the norm.  The eigenvalue kinds keep the q accumulator
+ * tiles of a sample tile in registers, so their matrix-unit kernels take 16 entries per workgroup, never 32 or 64.
+ * PGD_ERR_INVALID with a message, before anything is launched, also for: a kind out of range, PGD_EVAL_Q_VALUE with q != 1, an
+ * eigenvalue kind with q other than 4 or 6. */
+int pgd_eval_batch_quantity(pgd_handle ctx, const pgd_handle *modes, int k, int q, int kind, const double *coefs, int64_t s, int want,
+                            double threshold, double *sample_stats, pgd_handle env_min, pgd_handle env_max, pgd_handle exceed,
+                            pgd_handle fields);
+int pgd_eval_batch_grad_quantity(pgd_handle ctx, pgd_handle mesh, const pgd_handle *modes, int k, const double *L, int q, int kind,
+                                 pgd_handle scale_or_0, const double *coefs, int64_t s, int want, double threshold,
+                                 double *sample_stats, pgd_handle env_min, pgd_handle env_max, pgd_handle exceed, pgd_handle fields);
+int pgd_eval_batch_grad_p2_quantity(pgd_handle ctx, pgd_handle mesh, const pgd_handle *modes, int k, const double *lam, int npt,
+                                    const double *L, int q, int kind, pgd_handle scale_or_0, const double *coefs, int64_t s, int want,
+                                    double threshold, double *sample_stats, pgd_handle env_min, pgd_handle env_max,
+                                    pgd_handle exceed, pgd_handle fields);
 
 /* ------------------------------------------------------------------ tuning --- */
 /* Launch-shape knobs; they change speed (and the order of the dot's partial

@@ -75,6 +75,10 @@ SIGNATURES = {
     "pgd_eval_norm_last_shape": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pgd_cell_gradient_p2": (C.c_int, [H, H, H, PD, C.c_int, PD, C.c_int, H, H]),
     "pgd_eval_batch_grad_p2": (C.c_int, [H, H, PH, C.c_int, PD, C.c_int, PD, C.c_int, H, PD, I64, C.c_int, F64, PD, H, H, H, H]),
+    "pgd_eval_batch_quantity": (C.c_int, [H, PH, C.c_int, C.c_int, C.c_int, PD, I64, C.c_int, F64, PD, H, H, H, H]),
+    "pgd_eval_batch_grad_quantity": (C.c_int, [H, H, PH, C.c_int, PD, C.c_int, C.c_int, H, PD, I64, C.c_int, F64, PD, H, H, H, H]),
+    "pgd_eval_batch_grad_p2_quantity": (C.c_int, [H, H, PH, C.c_int, PD, C.c_int, PD, C.c_int, C.c_int, H, PD, I64, C.c_int, F64, PD, H, H, H,
+                                                  H]),
     "pgd_atom_assemble": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PH]),
     "pgd_atom_assemble_cells": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, PU8, I64, PH]),
     "pgd_atom_assemble_cellwise": (C.c_int, [H, H, C.c_int, C.c_int, C.c_int, H, H, PU8, I64, PH]),
@@ -165,6 +169,7 @@ SIGNATURES = {
 
 NSLOTS = 64
 EVAL_STATS, EVAL_ENVELOPE, EVAL_EXCEED, EVAL_FIELDS = 1, 2, 4, 8      # PGD_EVAL_* (include/pgd_amd.h)
+EVAL_Q_NORM, EVAL_Q_VALUE, EVAL_Q_EIG_MAX, EVAL_Q_EIG_MIN, EVAL_Q_EIG_SPREAD = range(5)      # pgd_eval_quantity
 TUNE_EVAL_VARIANT, TUNE_EVAL_GRID_MAX, TUNE_EVAL_SAMPLE_CHUNK = 50, 51, 52
 TUNE_BLOCK_STORAGE = 54
 TUNE_PCG_FOLD_MARCH, TUNE_PCG_SCALAR_S, TUNE_PCG_FUSED_MARCH = 55, 56, 57
@@ -473,6 +478,30 @@ class Context:
             raise ValueError("eval_batch_grad: L is a (q, ncomp * gdim) matrix")
         return self._eval_batch("eval_batch_grad", self.lib.pgd_eval_batch_grad, (dptr(L) if L.size else None, L.shape[0], int(scale or 0)),
                                 modes, coefs, stats, env_min, env_max, exceed, threshold, fields, lead=(int(mesh),))
+
+    def eval_batch_quantity(self, modes, q, kind, coefs, stats=True, env_min=0, env_max=0, exceed=0, threshold=0.0, fields=0):
+        """pgd_eval_batch_quantity: ``eval_batch_norm`` with the value of ``kind`` (EVAL_Q_*: the norm, the signed value of one plane,
+        the largest / smallest eigenvalue of the symmetric tensor of q = 6 or 4 planes, or their difference) in the place of the norm."""
+        return self._eval_batch("eval_batch_quantity", self.lib.pgd_eval_batch_quantity, (int(q), int(kind)), modes, coefs, stats, env_min,
+                                env_max, exceed, threshold, fields)
+
+    def eval_batch_grad_quantity(self, mesh, modes, L, kind, coefs, scale=0, stats=True, env_min=0, env_max=0, exceed=0, threshold=0.0,
+                                 fields=0):
+        """pgd_eval_batch_grad_quantity: ``eval_batch_grad`` with the value of ``kind`` as ``eval_batch_quantity`` has it."""
+        L = np.ascontiguousarray(L, dtype=np.float64)
+        if L.ndim != 2:
+            raise ValueError("eval_batch_grad_quantity: L is a (q, ncomp * gdim) matrix")
+        return self._eval_batch("eval_batch_grad_quantity", self.lib.pgd_eval_batch_grad_quantity,
+                                (dptr(L) if L.size else None, L.shape[0], int(kind), int(scale or 0)), modes, coefs, stats, env_min, env_max,
+                                exceed, threshold, fields, lead=(int(mesh),))
+
+    def eval_batch_grad_p2_quantity(self, mesh, modes, lam, L, kind, coefs, scale=0, stats=True, env_min=0, env_max=0, exceed=0,
+                                    threshold=0.0, fields=0):
+        """pgd_eval_batch_grad_p2_quantity: ``eval_batch_grad_p2`` with the value of ``kind`` as ``eval_batch_quantity`` has it."""
+        lam, L = self._p2_points("eval_batch_grad_p2_quantity", lam, L)
+        return self._eval_batch("eval_batch_grad_p2_quantity", self.lib.pgd_eval_batch_grad_p2_quantity,
+                                (dptr(lam) if lam.size else None, lam.shape[0], dptr(L) if L.size else None, L.shape[0], int(kind),
+                                 int(scale or 0)), modes, coefs, stats, env_min, env_max, exceed, threshold, fields, lead=(int(mesh),))
 
     def eval_norm_last_shape(self):
         """(entries per workgroup, staged) of the last eval_batch_norm / eval_batch_grad that launched; staged: 1 = the planes of a row block in at most

@@ -27,7 +27,8 @@
 // the kernel that makes such planes from a nodal P1 mode (pgd_cell_gradient), and the two norm kernels once more with the planes
 // formed inside them from the nodal modes, never stored (pgd_eval_batch_grad), and the last two for nodal P2 modes at given points of
 // every cell (pgd_cell_gradient_p2, pgd_eval_batch_grad_p2).  What happens to a value once it is formed is the same in all of
-// them: see "the reduction epilogue" below.
+// them: see "the reduction epilogue" below.  What the value IS - the norm of the planes, one plane with its sign, an eigenvalue of
+// the symmetric tensor they are - is a compile-time kind of those six kernels (pgd_eval_quantity, eval_eig).
 #include "pgd_internal.h"
 
 #include <cmath>
@@ -274,25 +275,27 @@ __device__ __forceinline__ void eval_block_step(double (&emn)[T], double (&emx)[
 
 // One-wave kernels: one row per lane, EVAL_PLAIN_NS samples jb .. of the chunk per pass over the row's mode values (which stay in
 // L1 / L2 between the passes).  The fma chains over k in ascending order, the mode values at M.p[t][at]:
+template <int NS>
 __device__ __forceinline__ void eval_plain_chains(const EvalModes &M, int k, int kt, const double *__restrict__ cf, int jb, bool rv, int64_t at,
-                                                  double (&acc)[EVAL_PLAIN_NS]) {
+                                                  double (&acc)[NS]) {
 #pragma unroll
-    for (int c = 0; c < EVAL_PLAIN_NS; ++c) acc[c] = 0.0;
+    for (int c = 0; c < NS; ++c) acc[c] = 0.0;
     for (int t = 0; t < k; ++t) {
         const double f = rv ? M.p[t][at] : 0.0;
         const double *cp = cf + eval_cf_index(kt, t, jb);
 #pragma unroll
-        for (int c = 0; c < EVAL_PLAIN_NS; ++c) acc[c] = fma(cp[c], f, acc[c]);
+        for (int c = 0; c < NS; ++c) acc[c] = fma(cp[c], f, acc[c]);
     }
 }
 
 // ... and what becomes of the values v of samples jb .. at the lane's row (emn, emx, ect: the row's state over the chunk)
-__device__ __forceinline__ void eval_plain_step(const double (&v)[EVAL_PLAIN_NS], int jb, int cs, int64_t j0, int64_t n, int64_t row, bool rv,
+template <int NS>
+__device__ __forceinline__ void eval_plain_step(const double (&v)[NS], int jb, int cs, int64_t j0, int64_t n, int64_t row, bool rv,
                                                 int want, double thr, const EvalOut &O, double *s_mn, double *s_mx, double &emn,
                                                 double &emx, double &ect) {
     const double INF = __builtin_huge_val();
 #pragma unroll
-    for (int c = 0; c < EVAL_PLAIN_NS; ++c) {
+    for (int c = 0; c < NS; ++c) {
         const int js = jb + c;
         if (js >= cs) break;                 // uniform
         const double u = v[c];
@@ -351,6 +354,67 @@ __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_plain(EvalModes M, int 
 // rows padded to 16 (mod 32) doubles so that the two 16-lane row groups of a half wave sit on opposite halves of the bank row.
 // kt is a run-time value here.  LDSB = false reads the fragments from global memory instead (L2: a row block's values are read by
 // every sample tile): the launcher's last resort where q planes of 16 rows do not fit 160 KiB.
+//
+// What becomes of the q combined planes u_0 .. u_{q-1} of an entry and sample is a compile-time kind QK (pgd_eval_quantity) of all six
+// value kernels: PGD_EVAL_Q_NORM is the text above, PGD_EVAL_Q_VALUE (q = 1) passes u_0 on with its sign, the three EIG kinds keep
+// all q planes of a tile in registers and reduce the symmetric tensor [xx, yy, zz, xy, yz, xz] (q = 4: yz = xz = 0) with eval_eig.
+// The value depends on the u_i alone, so it is as independent of grid, chunk and row block as they are.
+constexpr int EVAL_TENSOR_Q = 6;
+constexpr bool eval_kind_is_tensor(int kind) { return kind >= PGD_EVAL_Q_EIG_MAX; }
+
+// An extreme eigenvalue (or their difference) of a symmetric 3 x 3 tensor.  The three roots of the characteristic polynomial from
+// its invariants are NOT used: acos is ill-conditioned at +-1, so where two eigenvalues nearly coincide (uniaxial stress in any
+// frame) the angle is off by sqrt(u) and the close pair with it.  Instead only the root the angle gives well - the one away from
+// the other two: the largest for det >= 0, the smallest otherwise - is taken from the angle, and only to find its eigenvector w:
+// the largest cross product of two rows of C - lambda I.  The other two eigenvalues are those of C on the plane orthogonal to w
+// (a 2 x 2 problem in an orthonormal pair a, b: mean +- radius, no cancellation), the isolated one is taken again as w' C w; errors
+// of w enter all three in second order only.  C = (sigma - m I) / p with m = tr / 3, p^2 = |sigma - m I|_F^2 / 6 has eigenvalues
+// in [-2, 2], so nothing here over- or underflows once p is formed; p = 0 (a multiple of the identity) gives m, m, m.
+template <int QK>
+__device__ __forceinline__ double eval_eig(double xx, double yy, double zz, double xy, double yz, double xz) {
+    static_assert(QK == PGD_EVAL_Q_EIG_MAX || QK == PGD_EVAL_Q_EIG_MIN || QK == PGD_EVAL_Q_EIG_SPREAD, "an eigenvalue kind");
+    const double m = (xx + yy + zz) / 3.0;
+    const double bx = xx - m, by = yy - m, bz = zz - m;
+    const double p = sqrt((bx * bx + by * by + bz * bz + 2.0 * (xy * xy + yz * yz + xz * xz)) / 6.0);
+    const double inv = p > 0.0 ? 1.0 / p : 0.0;
+    const double cx = bx * inv, cy = by * inv, cz = bz * inv, cxy = xy * inv, cyz = yz * inv, cxz = xz * inv;
+    const double det = cx * (cy * cz - cyz * cyz) - cxy * (cxy * cz - cyz * cxz) + cxz * (cxy * cyz - cy * cxz);
+    const double h = fmin(fmax(0.5 * det, -1.0), 1.0);
+    const double th = acos(h) / 3.0;
+    const double lam = 2.0 * cos(h >= 0.0 ? th : th + 2.0943951023931954923);      // (2 pi / 3)
+    // rows of C - lam I and their cross products
+    const double r0x = cx - lam, r1y = cy - lam, r2z = cz - lam;
+    const double u0 = cxy * cyz - cxz * r1y, u1 = cxz * cxy - r0x * cyz, u2 = r0x * r1y - cxy * cxy;          // r0 x r1
+    const double v0 = r1y * r2z - cyz * cyz, v1 = cyz * cxz - cxy * r2z, v2 = cxy * cyz - r1y * cxz;          // r1 x r2
+    const double t0 = cyz * cxz - r2z * cxy, t1 = r2z * r0x - cxz * cxz, t2 = cxz * cxy - cyz * r0x;          // r2 x r0
+    const double nu = u0 * u0 + u1 * u1 + u2 * u2, nv = v0 * v0 + v1 * v1 + v2 * v2, nt = t0 * t0 + t1 * t1 + t2 * t2;
+    double w0 = u0, w1 = u1, w2 = u2, nw = nu;
+    if (nv > nw) { w0 = v0; w1 = v1; w2 = v2; nw = nv; }
+    if (nt > nw) { w0 = t0; w1 = t1; w2 = t2; nw = nt; }
+    if (nw > 0.0) {
+        const double s = 1.0 / sqrt(nw);
+        w0 *= s; w1 *= s; w2 *= s;
+    } else {
+        w0 = 1.0; w1 = 0.0; w2 = 0.0;
+    }
+    // a orthogonal to w from the larger of |w0|, |w1|; b = w x a
+    const bool f = fabs(w0) >= fabs(w1);
+    const double s = 1.0 / sqrt(f ? w0 * w0 + w2 * w2 : w1 * w1 + w2 * w2);
+    const double a0 = f ? -w2 * s : 0.0, a1 = f ? 0.0 : w2 * s, a2 = f ? w0 * s : -w1 * s;
+    const double b0 = w1 * a2 - w2 * a1, b1 = w2 * a0 - w0 * a2, b2 = w0 * a1 - w1 * a0;
+    const double ca0 = cx * a0 + cxy * a1 + cxz * a2, ca1 = cxy * a0 + cy * a1 + cyz * a2, ca2 = cxz * a0 + cyz * a1 + cz * a2;
+    const double cb0 = cx * b0 + cxy * b1 + cxz * b2, cb1 = cxy * b0 + cy * b1 + cyz * b2, cb2 = cxz * b0 + cyz * b1 + cz * b2;
+    const double cw0 = cx * w0 + cxy * w1 + cxz * w2, cw1 = cxy * w0 + cy * w1 + cyz * w2, cw2 = cxz * w0 + cyz * w1 + cz * w2;
+    const double m00 = a0 * ca0 + a1 * ca1 + a2 * ca2, m11 = b0 * cb0 + b1 * cb1 + b2 * cb2, m01 = a0 * cb0 + a1 * cb1 + a2 * cb2;
+    const double mid = 0.5 * (m00 + m11), hd = 0.5 * (m00 - m11);
+    const double rad = sqrt(hd * hd + m01 * m01);          // (entries of a matrix of norm <= 2: no scaling as in hypot is needed)
+    const double iso = w0 * cw0 + w1 * cw1 + w2 * cw2;
+    const double emx = fmax(iso, mid + rad), emn = fmin(iso, mid - rad);
+    if constexpr (QK == PGD_EVAL_Q_EIG_MAX) return m + p * emx;
+    else if constexpr (QK == PGD_EVAL_Q_EIG_MIN) return m + p * emn;
+    else return p * (emx - emn);
+}
+
 template <int T>
 struct EvalNormShape {
     static constexpr int RB = 16 * T;
@@ -359,7 +423,7 @@ struct EvalNormShape {
 
 // A row block of the matrix-unit norm kernels once its B fragments are where they are read (s_f staged and the barrier passed, or
 // global memory): the sample tiles of this wave, then the per-row step.  Whatever filled s_f, from here on the kernels are one text.
-template <int T, bool LDSB>
+template <int T, bool LDSB, int QK>
 __device__ __forceinline__ void eval_norm_tiles(const EvalModes &M, int k, int kt, int q, int64_t n, const double *__restrict__ cf, int cs,
                                                 int64_t j0, int want, int first, double thr, const EvalOut &O, const double *s_f,
                                                 double *s_mn, double *s_mx, double *s_env, int64_t row0) {
@@ -376,12 +440,9 @@ __device__ __forceinline__ void eval_norm_tiles(const EvalModes &M, int k, int k
         emn[j] = INF; emx[j] = -INF; ecnt[j] = 0;
     }
     for (int st = wv; st < ntile; st += 4) {
-        d4_t ss[T];
-#pragma unroll
-        for (int j = 0; j < T; ++j) ss[j] = d4_t{0.0, 0.0, 0.0, 0.0};
         const double *cp = cf + (int64_t)st * kt * 64 + lane;
-        for (int i = 0; i < q; ++i) {
-            d4_t acc[T];
+        // the combined plane i of this tile: one fixed chain over the k-steps per accumulator
+        auto plane = [&](int i, d4_t (&acc)[T]) {
 #pragma unroll
             for (int j = 0; j < T; ++j) acc[j] = d4_t{0.0, 0.0, 0.0, 0.0};
             for (int s = 0; s < kt; ++s) {
@@ -398,22 +459,48 @@ __device__ __forceinline__ void eval_norm_tiles(const EvalModes &M, int k, int k
                     acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
                 }
             }
+        };
+        d4_t v[T];
+        if constexpr (QK == PGD_EVAL_Q_NORM) {
+            d4_t ss[T];
+#pragma unroll
+            for (int j = 0; j < T; ++j) ss[j] = d4_t{0.0, 0.0, 0.0, 0.0};
+            for (int i = 0; i < q; ++i) {
+                d4_t acc[T];
+                plane(i, acc);
+#pragma unroll
+                for (int j = 0; j < T; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ss[j][r] = fma(acc[j][r], acc[j][r], ss[j][r]);
+            }
 #pragma unroll
             for (int j = 0; j < T; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) ss[j][r] = fma(acc[j][r], acc[j][r], ss[j][r]);
+                for (int r = 0; r < 4; ++r) v[j][r] = sqrt(ss[j][r]);
+        } else if constexpr (QK == PGD_EVAL_Q_VALUE) {
+            plane(0, v);
+        } else {
+            d4_t u[EVAL_TENSOR_Q][T];                  // all planes of the tile at once: 8 q T registers
+#pragma unroll
+            for (int i = 0; i < EVAL_TENSOR_Q; ++i) {
+                if (i < q) {
+                    plane(i, u[i]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < T; ++j) u[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < T; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[j][r] = eval_eig<QK>(u[0][j][r], u[1][j][r], u[2][j][r], u[3][j][r], u[4][j][r], u[5][j][r]);
         }
-        d4_t v[T];
-#pragma unroll
-        for (int j = 0; j < T; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[j][r] = sqrt(ss[j][r]);
         eval_tile_step<T>(v, rv, emn, emx, ecnt, st, cs, j0, n, row0, want, thr, O, s_mn, s_mx);
     }
     eval_block_step<T>(emn, emx, ecnt, s_env, row0, n, want, first, O);
 }
 
-template <int T, bool LDSB>
+template <int T, bool LDSB, int QK>
 __global__ __launch_bounds__(TPB) void k_eval_norm_mfma(EvalModes M, int k, int kt, int q, int64_t n, const double *__restrict__ cf, int cs,
                                                         int64_t j0, int want, int first, double thr, EvalOut O) {
     extern __shared__ double s_dyn[];
@@ -439,16 +526,33 @@ __global__ __launch_bounds__(TPB) void k_eval_norm_mfma(EvalModes M, int k, int 
             }
         }
         __syncthreads();
-        eval_norm_tiles<T, LDSB>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O, s_f, s_mn, s_mx, s_env, row0);
+        eval_norm_tiles<T, LDSB, QK>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O, s_f, s_mn, s_mx, s_env, row0);
     }
     eval_store_partials<TPB>(O, s_mn, s_mx, cs16, want);
 }
 
+// Samples per pass of the plain kernels of a kind: the eigenvalue kinds hold q planes per sample and the temporaries of eval_eig
+constexpr int eval_plain_ns(int kind) { return eval_kind_is_tensor(kind) ? EVAL_PLAIN_NS / 2 : EVAL_PLAIN_NS; }
+
+// The plain kernels that hold all planes of a pass (u[i][c]: plane i, sample c; planes from q on are zero): the values of a kind
+// other than the norm, whose text stays where it was
+template <int QK, int NS>
+__device__ __forceinline__ void eval_plain_values(const double (&u)[EVAL_QMAX][NS], int q, double (&v)[NS]) {
+    if constexpr (QK == PGD_EVAL_Q_VALUE) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) v[c] = u[0][c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) v[c] = eval_eig<QK>(u[0][c], u[1][c], u[2][c], u[3][c], u[4][c], u[5][c]);
+    }
+}
+
 // k_eval_plain with the loop over the planes around its fma chains
+template <int QK>
 __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_norm_plain(EvalModes M, int k, int kt, int q, int64_t n, const double *__restrict__ cf,
                                                                     int cs, int64_t j0, int want, int first, double thr, EvalOut O) {
     extern __shared__ double s_dyn[];
-    constexpr int NS = EVAL_PLAIN_NS;
+    constexpr int NS = eval_plain_ns(QK);
     const double INF = __builtin_huge_val();
     const int cs16 = (cs + 15) & ~15;
     double *s_mn = s_dyn, *s_mx = s_dyn + cs16;
@@ -461,16 +565,33 @@ __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_norm_plain(EvalModes M,
         const bool rv = row < n;
         double emn = INF, emx = -INF, ect = 0.0;
         for (int jb = 0; jb < cs16; jb += NS) {
-            double ss[NS], acc[NS];
+            double ss[NS];
+            if constexpr (QK == PGD_EVAL_Q_NORM) {
+                double acc[NS];
 #pragma unroll
-            for (int c = 0; c < NS; ++c) ss[c] = 0.0;
-            for (int i = 0; i < q; ++i) {
-                eval_plain_chains(M, k, kt, cf, jb, rv, (int64_t)i * n + row, acc);
+                for (int c = 0; c < NS; ++c) ss[c] = 0.0;
+                for (int i = 0; i < q; ++i) {
+                    eval_plain_chains(M, k, kt, cf, jb, rv, (int64_t)i * n + row, acc);
 #pragma unroll
-                for (int c = 0; c < NS; ++c) ss[c] = fma(acc[c], acc[c], ss[c]);
+                    for (int c = 0; c < NS; ++c) ss[c] = fma(acc[c], acc[c], ss[c]);
+                }
+#pragma unroll
+                for (int c = 0; c < NS; ++c) ss[c] = sqrt(ss[c]);            // from here on the values
+            } else if constexpr (QK == PGD_EVAL_Q_VALUE) {
+                eval_plain_chains(M, k, kt, cf, jb, rv, row, ss);
+            } else {
+                double u[EVAL_QMAX][NS];
+#pragma unroll
+                for (int i = 0; i < EVAL_TENSOR_Q; ++i) {
+                    if (i < q) {
+                        eval_plain_chains(M, k, kt, cf, jb, rv, (int64_t)i * n + row, u[i]);
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) u[i][c] = 0.0;
+                    }
+                }
+                eval_plain_values<QK>(u, q, ss);
             }
-#pragma unroll
-            for (int c = 0; c < NS; ++c) ss[c] = sqrt(ss[c]);            // from here on the values
             eval_plain_step(ss, jb, cs, j0, n, row, rv, want, thr, O, s_mn, s_mx, emn, emx, ect);
         }
         if (rv) eval_row_accumulate(O, row, emn, emx, ect, want, first);
@@ -544,27 +665,72 @@ static bool eval_raise_lds(const void *kern, size_t lds) {
     return false;
 }
 
-template <int T>
-static bool eval_norm_raise_lds(size_t lds) { return eval_raise_lds((const void *)k_eval_norm_mfma<T, true>, lds); }
+template <int QK>
+static bool eval_norm_raise_lds(size_t lds) { return eval_raise_lds((const void *)k_eval_norm_mfma<1, true, QK>, lds); }
 
-// 64, 32 or 16 rows per workgroup, the largest whose q planes fit 64 KiB beside the extrema; else 16 rows in up to 160 KiB (the
-// function attribute is raised for it, by `raise`: the 16-row kernel of the caller); else 16 rows with the fragments read from
-// global memory, which the fused kernels do not have: they refuse
-static EvalNormCfg eval_norm_choose(int q, int kt, int cs16_max, bool (*raise)(size_t)) {
+// The eigenvalue kinds hold the q accumulator tiles of a sample tile at once (8 q T registers where the norm holds 8 T and a sum)
+// beside the temporaries of eval_eig: their kernels exist for 16 rows per workgroup (about 200 vector registers, two workgroups
+// per CU; 32 rows took 300, one wave per SIMD).  No vector register is spilled; scalar registers are - the constants of acos and
+// cos are hoisted out of the sample loop, and in the fused kernels L arrives by value - DESIGN.md has the counts per kernel
+constexpr int eval_kind_tmax(int kind) { return eval_kind_is_tensor(kind) ? 1 : 4; }
+
+// 64, 32 or 16 rows per workgroup (from 16 tmax down), the largest whose q planes fit 64 KiB beside the extrema; else 16 rows in up
+// to 160 KiB (the function attribute is raised for it, by `raise`: the 16-row kernel of the caller); else 16 rows with the
+// fragments read from global memory, which the fused kernels do not have: they refuse
+static EvalNormCfg eval_norm_choose(int q, int kt, int cs16_max, int tmax, bool (*raise)(size_t)) {
     EvalNormCfg cfg;
-    for (int t = 4; t >= 1; t >>= 1)
+    for (int t = tmax; t >= 1; t >>= 1)
         if (eval_norm_lds(t, true, q, kt, cs16_max) <= EVAL_LDS_PLAIN) { cfg.t = t; cfg.ldsb = true; return cfg; }
     const size_t lds = eval_norm_lds(1, true, q, kt, cs16_max);
     if (lds <= EVAL_LDS_MAX && raise(lds)) cfg.ldsb = true;
     return cfg;
 }
 
-template <int T, bool LDSB>
+template <int T, bool LDSB, int QK>
 static int eval_launch_norm(Ctx *c, const EvalModes &M, int k, int kt, int q, int64_t n, const double *cf, int cs, int64_t j0, int want,
                             int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const size_t lds = eval_norm_lds(T, LDSB, q, kt, (cs + 15) & ~15);
-    return eval_launch_persistent(c, k_eval_norm_mfma<T, LDSB>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q, n, cf,
+    return eval_launch_persistent(c, k_eval_norm_mfma<T, LDSB, QK>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q, n, cf,
                                   cs, j0, want, first, thr, O);
+}
+
+// One sample chunk of the stored planes with the kind's kernels: plain, or the matrix unit as cfg says
+template <int QK>
+static int eval_launch_norm_kind(Ctx *c, bool mfma, const EvalNormCfg &cfg, const EvalModes &M, int k, int kt, int q, int64_t n,
+                                 const double *cf, int cs, int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap,
+                                 int *grid_out) {
+    if (!mfma) {
+        const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
+        const int g = (int)(nblk < grid_cap ? nblk : grid_cap);
+        const size_t lds = (size_t)2 * ((cs + 15) & ~15) * sizeof(double);
+        k_eval_norm_plain<QK><<<g, EVAL_PLAIN_TPB, lds, c->stream>>>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O);
+        PGD_LAUNCH_CHECK(c);
+        *grid_out = g;
+        return PGD_OK;
+    }
+    if (!cfg.ldsb) return eval_launch_norm<1, false, QK>(c, M, k, kt, q, n, cf, cs, j0, want, first, thr, O, grid_cap, grid_out);
+    if constexpr (eval_kind_tmax(QK) >= 4) {
+        if (cfg.t == 4) return eval_launch_norm<4, true, QK>(c, M, k, kt, q, n, cf, cs, j0, want, first, thr, O, grid_cap, grid_out);
+        if (cfg.t == 2) return eval_launch_norm<2, true, QK>(c, M, k, kt, q, n, cf, cs, j0, want, first, thr, O, grid_cap, grid_out);
+    }
+    return eval_launch_norm<1, true, QK>(c, M, k, kt, q, n, cf, cs, j0, want, first, thr, O, grid_cap, grid_out);
+}
+
+typedef int (*eval_norm_launch_t)(Ctx *, bool, const EvalNormCfg &, const EvalModes &, int, int, int, int64_t, const double *, int, int64_t,
+                                  int, int, double, const EvalOut &, int, int *);
+struct EvalNormFns { eval_norm_launch_t launch; bool (*raise)(size_t); };
+
+template <int QK>
+static EvalNormFns eval_norm_fns() { return {eval_launch_norm_kind<QK>, eval_norm_raise_lds<QK>}; }
+
+static EvalNormFns eval_norm_pick(int kind) {
+    switch (kind) {
+        case PGD_EVAL_Q_VALUE: return eval_norm_fns<PGD_EVAL_Q_VALUE>();
+        case PGD_EVAL_Q_EIG_MAX: return eval_norm_fns<PGD_EVAL_Q_EIG_MAX>();
+        case PGD_EVAL_Q_EIG_MIN: return eval_norm_fns<PGD_EVAL_Q_EIG_MIN>();
+        case PGD_EVAL_Q_EIG_SPREAD: return eval_norm_fns<PGD_EVAL_Q_EIG_SPREAD>();
+        default: return eval_norm_fns<PGD_EVAL_Q_NORM>();
+    }
 }
 
 static size_t eval_round(size_t bytes) { return (bytes + 65535) & ~(size_t)65535; }   // (whole 64 KiB: the pool takes them back)
@@ -809,7 +975,7 @@ struct EvalGradP2Src : EvalGradSrc {
 // (the kernel arguments are passed by value: modes, L, the points and the scalars must stay below the 4 KiB the runtime takes)
 static_assert(sizeof(EvalModes) + sizeof(EvalGradP2Src) + sizeof(EvalOut) + 128 <= 4096, "kernel arguments of the fused kernels");
 
-template <int T, int G, int NC>
+template <int T, int G, int NC, int QK>
 __global__ __launch_bounds__(TPB) void k_eval_grad_mfma(EvalModes M, int k, int kt, int q, EvalGradSrc S, int64_t n, const double *__restrict__ cf,
                                                         int cs, int64_t j0, int want, int first, double thr, EvalOut O) {
     extern __shared__ double s_dyn[];
@@ -844,19 +1010,19 @@ __global__ __launch_bounds__(TPB) void k_eval_grad_mfma(EvalModes M, int k, int 
             }
         }
         __syncthreads();
-        eval_norm_tiles<T, true>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O, s_f, s_mn, s_mx, s_env, row0);
+        eval_norm_tiles<T, true, QK>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O, s_f, s_mn, s_mx, s_env, row0);
     }
     eval_store_partials<TPB>(O, s_mn, s_mx, cs16, want);
 }
 
 // k_eval_norm_plain with the planes of mode t formed once per pass and used by all q chains: q x NS accumulators, the chains over t
 // and the squares over i in ascending order as there
-template <int G, int NC>
+template <int G, int NC, int QK>
 __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_grad_plain(EvalModes M, int k, int kt, int q, EvalGradSrc S, int64_t n,
                                                                     const double *__restrict__ cf, int cs, int64_t j0, int want, int first,
                                                                     double thr, EvalOut O) {
     extern __shared__ double s_dyn[];
-    constexpr int NS = EVAL_PLAIN_NS;
+    constexpr int NS = eval_plain_ns(QK);
     const double INF = __builtin_huge_val();
     const int cs16 = (cs + 15) & ~15;
     double *s_mn = s_dyn, *s_mx = s_dyn + cs16;
@@ -895,16 +1061,20 @@ __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_grad_plain(EvalModes M,
                     }
             }
             double ss[NS];
+            if constexpr (QK == PGD_EVAL_Q_NORM) {
 #pragma unroll
-            for (int c = 0; c < NS; ++c) ss[c] = 0.0;
+                for (int c = 0; c < NS; ++c) ss[c] = 0.0;
 #pragma unroll
-            for (int i = 0; i < EVAL_QMAX; ++i)
-                if (i < q) {
+                for (int i = 0; i < EVAL_QMAX; ++i)
+                    if (i < q) {
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) ss[c] = fma(acc[i][c], acc[i][c], ss[c]);
-                }
+                        for (int c = 0; c < NS; ++c) ss[c] = fma(acc[i][c], acc[i][c], ss[c]);
+                    }
 #pragma unroll
-            for (int c = 0; c < NS; ++c) ss[c] = sqrt(ss[c]);            // from here on the values
+                for (int c = 0; c < NS; ++c) ss[c] = sqrt(ss[c]);            // from here on the values
+            } else {
+                eval_plain_values<QK>(acc, q, ss);
+            }
             eval_plain_step(ss, jb, cs, j0, n, row, rv, want, thr, O, s_mn, s_mx, emn, emx, ect);
         }
         if (rv) eval_row_accumulate(O, row, emn, emx, ect, want, first);
@@ -929,51 +1099,64 @@ struct EvalGrad {
     const Vec *scale;
 };
 
-template <int T, int G, int NC>
+template <int T, int G, int NC, int QK>
 static int eval_launch_grad(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf, int cs,
                             int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const size_t lds = eval_norm_lds(T, true, q, kt, (cs + 15) & ~15);
-    return eval_launch_persistent(c, k_eval_grad_mfma<T, G, NC>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q, S, n, cf,
+    return eval_launch_persistent(c, k_eval_grad_mfma<T, G, NC, QK>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q, S, n, cf,
                                   cs, j0, want, first, thr, O);
 }
 
-template <int G, int NC>
+template <int G, int NC, int QK>
 static int eval_launch_grad_plain(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf, int cs,
                                   int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
     const int g = (int)(nblk < grid_cap ? nblk : grid_cap);
     const size_t lds = (size_t)2 * ((cs + 15) & ~15) * sizeof(double);
-    k_eval_grad_plain<G, NC><<<g, EVAL_PLAIN_TPB, lds, c->stream>>>(M, k, kt, q, S, n, cf, cs, j0, want, first, thr, O);
+    k_eval_grad_plain<G, NC, QK><<<g, EVAL_PLAIN_TPB, lds, c->stream>>>(M, k, kt, q, S, n, cf, cs, j0, want, first, thr, O);
     PGD_LAUNCH_CHECK(c);
     *grid_out = g;
     return PGD_OK;
 }
 
-template <int G, int NC>
-static bool eval_grad_raise_lds(size_t lds) { return eval_raise_lds((const void *)k_eval_grad_mfma<1, G, NC>, lds); }
+template <int G, int NC, int QK>
+static bool eval_grad_raise_lds(size_t lds) { return eval_raise_lds((const void *)k_eval_grad_mfma<1, G, NC, QK>, lds); }
 
-template <int G, int NC>
+template <int G, int NC, int QK>
 static EvalGradFns eval_grad_fns() {
     EvalGradFns f;
-    f.mfma[0] = eval_launch_grad<1, G, NC>;
-    f.mfma[1] = eval_launch_grad<2, G, NC>;
-    f.mfma[2] = eval_launch_grad<4, G, NC>;
-    f.plain = eval_launch_grad_plain<G, NC>;
-    f.raise = eval_grad_raise_lds<G, NC>;
+    f.mfma[0] = eval_launch_grad<1, G, NC, QK>;
+    if constexpr (eval_kind_tmax(QK) >= 4) {
+        f.mfma[1] = eval_launch_grad<2, G, NC, QK>;
+        f.mfma[2] = eval_launch_grad<4, G, NC, QK>;
+    }
+    f.plain = eval_launch_grad_plain<G, NC, QK>;
+    f.raise = eval_grad_raise_lds<G, NC, QK>;
     return f;
 }
 
-static bool eval_grad_pick(int G, int NC, EvalGradFns *f) {
+template <int G, int NC>
+static EvalGradFns eval_grad_fns_kind(int kind) {
+    switch (kind) {
+        case PGD_EVAL_Q_VALUE: return eval_grad_fns<G, NC, PGD_EVAL_Q_VALUE>();
+        case PGD_EVAL_Q_EIG_MAX: return eval_grad_fns<G, NC, PGD_EVAL_Q_EIG_MAX>();
+        case PGD_EVAL_Q_EIG_MIN: return eval_grad_fns<G, NC, PGD_EVAL_Q_EIG_MIN>();
+        case PGD_EVAL_Q_EIG_SPREAD: return eval_grad_fns<G, NC, PGD_EVAL_Q_EIG_SPREAD>();
+        default: return eval_grad_fns<G, NC, PGD_EVAL_Q_NORM>();
+    }
+}
+
+static bool eval_grad_pick(int G, int NC, int kind, EvalGradFns *f) {
     switch (G * 10 + NC) {
-        case 11: *f = eval_grad_fns<1, 1>(); return true;
-        case 12: *f = eval_grad_fns<1, 2>(); return true;
-        case 13: *f = eval_grad_fns<1, 3>(); return true;
-        case 21: *f = eval_grad_fns<2, 1>(); return true;
-        case 22: *f = eval_grad_fns<2, 2>(); return true;
-        case 23: *f = eval_grad_fns<2, 3>(); return true;
-        case 31: *f = eval_grad_fns<3, 1>(); return true;
-        case 32: *f = eval_grad_fns<3, 2>(); return true;
-        case 33: *f = eval_grad_fns<3, 3>(); return true;
+        case 11: *f = eval_grad_fns_kind<1, 1>(kind); return true;
+        case 12: *f = eval_grad_fns_kind<1, 2>(kind); return true;
+        case 13: *f = eval_grad_fns_kind<1, 3>(kind); return true;
+        case 21: *f = eval_grad_fns_kind<2, 1>(kind); return true;
+        case 22: *f = eval_grad_fns_kind<2, 2>(kind); return true;
+        case 23: *f = eval_grad_fns_kind<2, 3>(kind); return true;
+        case 31: *f = eval_grad_fns_kind<3, 1>(kind); return true;
+        case 32: *f = eval_grad_fns_kind<3, 2>(kind); return true;
+        case 33: *f = eval_grad_fns_kind<3, 3>(kind); return true;
         default: return false;
     }
 }
@@ -982,7 +1165,7 @@ static bool eval_grad_pick(int G, int NC, EvalGradFns *f) {
 // row % nc, as pgd_cell_gradient_p2 orders them, so a row block is 16 T consecutive cells at one point (or the seam of two points).
 // Every entry of a cell forms the inverse and gathers the record's nodal values again - from L2, the npt entries of a cell sit nc
 // rows apart - and from the barrier on the kernels are eval_norm_tiles / eval_plain_step.  Rows beyond the range read no record.
-template <int T, int G, int NC>
+template <int T, int G, int NC, int QK>
 __global__ __launch_bounds__(TPB) void k_eval_grad_p2_mfma(EvalModes M, int k, int kt, int q, EvalGradP2Src S, int64_t n,
                                                            const double *__restrict__ cf, int cs, int64_t j0, int want, int first, double thr,
                                                            EvalOut O) {
@@ -1022,17 +1205,17 @@ __global__ __launch_bounds__(TPB) void k_eval_grad_p2_mfma(EvalModes M, int k, i
             }
         }
         __syncthreads();
-        eval_norm_tiles<T, true>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O, s_f, s_mn, s_mx, s_env, row0);
+        eval_norm_tiles<T, true, QK>(M, k, kt, q, n, cf, cs, j0, want, first, thr, O, s_f, s_mn, s_mx, s_env, row0);
     }
     eval_store_partials<TPB>(O, s_mn, s_mx, cs16, want);
 }
 
-template <int G, int NC>
+template <int G, int NC, int QK>
 __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_grad_p2_plain(EvalModes M, int k, int kt, int q, EvalGradP2Src S, int64_t n,
                                                                        const double *__restrict__ cf, int cs, int64_t j0, int want,
                                                                        int first, double thr, EvalOut O) {
     extern __shared__ double s_dyn[];
-    constexpr int NS = EVAL_PLAIN_NS;
+    constexpr int NS = eval_plain_ns(QK);
     const double INF = __builtin_huge_val();
     const int cs16 = (cs + 15) & ~15;
     double *s_mn = s_dyn, *s_mx = s_dyn + cs16;
@@ -1077,16 +1260,20 @@ __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_grad_p2_plain(EvalModes
                     }
             }
             double ss[NS];
+            if constexpr (QK == PGD_EVAL_Q_NORM) {
 #pragma unroll
-            for (int c = 0; c < NS; ++c) ss[c] = 0.0;
+                for (int c = 0; c < NS; ++c) ss[c] = 0.0;
 #pragma unroll
-            for (int i = 0; i < EVAL_QMAX; ++i)
-                if (i < q) {
+                for (int i = 0; i < EVAL_QMAX; ++i)
+                    if (i < q) {
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) ss[c] = fma(acc[i][c], acc[i][c], ss[c]);
-                }
+                        for (int c = 0; c < NS; ++c) ss[c] = fma(acc[i][c], acc[i][c], ss[c]);
+                    }
 #pragma unroll
-            for (int c = 0; c < NS; ++c) ss[c] = sqrt(ss[c]);            // from here on the values
+                for (int c = 0; c < NS; ++c) ss[c] = sqrt(ss[c]);            // from here on the values
+            } else {
+                eval_plain_values<QK>(acc, q, ss);
+            }
             eval_plain_step(ss, jb, cs, j0, n, row, rv, want, thr, O, s_mn, s_mx, emn, emx, ect);
         }
         if (rv) eval_row_accumulate(O, row, emn, emx, ect, want, first);
@@ -1095,49 +1282,62 @@ __global__ __launch_bounds__(EVAL_PLAIN_TPB) void k_eval_grad_p2_plain(EvalModes
 }
 
 // (the launchers take the EvalGradSrc of eval_grad_launch_t: pgd_eval_batch_grad_p2 hands them the EvalGradP2Src it filled)
-template <int T, int G, int NC>
+template <int T, int G, int NC, int QK>
 static int eval_launch_grad_p2(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf, int cs,
                                int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const size_t lds = eval_norm_lds(T, true, q, kt, (cs + 15) & ~15);
-    return eval_launch_persistent(c, k_eval_grad_p2_mfma<T, G, NC>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q,
+    return eval_launch_persistent(c, k_eval_grad_p2_mfma<T, G, NC, QK>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q,
                                   static_cast<const EvalGradP2Src &>(S), n, cf, cs, j0, want, first, thr, O);
 }
 
-template <int G, int NC>
+template <int G, int NC, int QK>
 static int eval_launch_grad_p2_plain(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf,
                                      int cs, int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
     const int g = (int)(nblk < grid_cap ? nblk : grid_cap);
     const size_t lds = (size_t)2 * ((cs + 15) & ~15) * sizeof(double);
-    k_eval_grad_p2_plain<G, NC><<<g, EVAL_PLAIN_TPB, lds, c->stream>>>(M, k, kt, q, static_cast<const EvalGradP2Src &>(S), n, cf, cs, j0,
+    k_eval_grad_p2_plain<G, NC, QK><<<g, EVAL_PLAIN_TPB, lds, c->stream>>>(M, k, kt, q, static_cast<const EvalGradP2Src &>(S), n, cf, cs, j0,
                                                                       want, first, thr, O);
     PGD_LAUNCH_CHECK(c);
     *grid_out = g;
     return PGD_OK;
 }
 
-template <int G, int NC>
-static bool eval_grad_p2_raise_lds(size_t lds) { return eval_raise_lds((const void *)k_eval_grad_p2_mfma<1, G, NC>, lds); }
+template <int G, int NC, int QK>
+static bool eval_grad_p2_raise_lds(size_t lds) { return eval_raise_lds((const void *)k_eval_grad_p2_mfma<1, G, NC, QK>, lds); }
 
-template <int G, int NC>
+template <int G, int NC, int QK>
 static EvalGradFns eval_grad_p2_fns() {
     EvalGradFns f;
-    f.mfma[0] = eval_launch_grad_p2<1, G, NC>;
-    f.mfma[1] = eval_launch_grad_p2<2, G, NC>;
-    f.mfma[2] = eval_launch_grad_p2<4, G, NC>;
-    f.plain = eval_launch_grad_p2_plain<G, NC>;
-    f.raise = eval_grad_p2_raise_lds<G, NC>;
+    f.mfma[0] = eval_launch_grad_p2<1, G, NC, QK>;
+    if constexpr (eval_kind_tmax(QK) >= 4) {
+        f.mfma[1] = eval_launch_grad_p2<2, G, NC, QK>;
+        f.mfma[2] = eval_launch_grad_p2<4, G, NC, QK>;
+    }
+    f.plain = eval_launch_grad_p2_plain<G, NC, QK>;
+    f.raise = eval_grad_p2_raise_lds<G, NC, QK>;
     return f;
 }
 
-static bool eval_grad_p2_pick(int G, int NC, EvalGradFns *f) {
+template <int G, int NC>
+static EvalGradFns eval_grad_p2_fns_kind(int kind) {
+    switch (kind) {
+        case PGD_EVAL_Q_VALUE: return eval_grad_p2_fns<G, NC, PGD_EVAL_Q_VALUE>();
+        case PGD_EVAL_Q_EIG_MAX: return eval_grad_p2_fns<G, NC, PGD_EVAL_Q_EIG_MAX>();
+        case PGD_EVAL_Q_EIG_MIN: return eval_grad_p2_fns<G, NC, PGD_EVAL_Q_EIG_MIN>();
+        case PGD_EVAL_Q_EIG_SPREAD: return eval_grad_p2_fns<G, NC, PGD_EVAL_Q_EIG_SPREAD>();
+        default: return eval_grad_p2_fns<G, NC, PGD_EVAL_Q_NORM>();
+    }
+}
+
+static bool eval_grad_p2_pick(int G, int NC, int kind, EvalGradFns *f) {
     switch (G * 10 + NC) {
-        case 21: *f = eval_grad_p2_fns<2, 1>(); return true;
-        case 22: *f = eval_grad_p2_fns<2, 2>(); return true;
-        case 23: *f = eval_grad_p2_fns<2, 3>(); return true;
-        case 31: *f = eval_grad_p2_fns<3, 1>(); return true;
-        case 32: *f = eval_grad_p2_fns<3, 2>(); return true;
-        case 33: *f = eval_grad_p2_fns<3, 3>(); return true;
+        case 21: *f = eval_grad_p2_fns_kind<2, 1>(kind); return true;
+        case 22: *f = eval_grad_p2_fns_kind<2, 2>(kind); return true;
+        case 23: *f = eval_grad_p2_fns_kind<2, 3>(kind); return true;
+        case 31: *f = eval_grad_p2_fns_kind<3, 1>(kind); return true;
+        case 32: *f = eval_grad_p2_fns_kind<3, 2>(kind); return true;
+        case 33: *f = eval_grad_p2_fns_kind<3, 3>(kind); return true;
         default: return false;
     }
 }
@@ -1180,7 +1380,7 @@ extern "C" {
 // mode is q planes, the norm kernels): the checks, the chunking and the coefficient staging are the same, only the launch differs.
 // pgd_eval_batch_grad and pgd_eval_batch_grad_p2 are the second of these with `gs`: the modes are nodal, the planes are formed in
 // the kernel, the outputs have gs->entries rows (one per cell; per point and cell for P2).  fn: the entry point's name for the messages.
-static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want,
+static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_handle *modes, int k, int q, int kind, const double *coefs, int64_t s, int want,
                           double threshold, double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h,
                           pgd_handle fields_h) {
     // ---- every argument is checked before anything is launched
@@ -1252,7 +1452,8 @@ static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_
     if (gmax > grid_cap) gmax = grid_cap;
 
     EvalNormCfg ncfg;
-    if (mfma && q > 0) ncfg = eval_norm_choose(q, kt, cs16_max, gs ? gs->fn.raise : (bool (*)(size_t))eval_norm_raise_lds<1>);
+    const EvalNormFns nfn = eval_norm_pick(kind);
+    if (mfma && q > 0) ncfg = eval_norm_choose(q, kt, cs16_max, eval_kind_tmax(kind), gs ? gs->fn.raise : nfn.raise);
     if (gs && mfma && !ncfg.ldsb)                    // (no fragments from global memory here: there are no planes to read)
         return fail(c, PGD_ERR_LIMIT, "%s: q = %d planes of k = %d modes do not fit a workgroup: 16 cells need %zu bytes of LDS "
                     "(8 q 4 ceil(k / 4) 16 and the extrema), the limit is %zu; PGD_TUNE_EVAL_VARIANT = 0 has no such limit", fn, q, k,
@@ -1324,11 +1525,8 @@ static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_
             if (gs) {
                 const eval_grad_launch_t launch = !mfma ? gs->fn.plain : gs->fn.mfma[ncfg.t == 4 ? 2 : ncfg.t == 2 ? 1 : 0];
                 PGD_TRY(launch(c, M, k, kt, q, gs->src, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g));
-            } else if (mfma && q > 0) {
-                if (!ncfg.ldsb) PGD_TRY((eval_launch_norm<1, false>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
-                else if (ncfg.t == 4) PGD_TRY((eval_launch_norm<4, true>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
-                else if (ncfg.t == 2) PGD_TRY((eval_launch_norm<2, true>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
-                else PGD_TRY((eval_launch_norm<1, true>(c, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g)));
+            } else if (q > 0) {
+                PGD_TRY(nfn.launch(c, mfma, ncfg, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g));
             } else if (mfma) {
                 switch (kt) {
                     case 4: PGD_TRY((eval_launch_mfma<4, 4>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g))); break;
@@ -1341,12 +1539,7 @@ static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_
             } else {
                 const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
                 g = (int)(nblk < gmax ? nblk : gmax);
-                if (q > 0)
-                    k_eval_norm_plain<<<g, EVAL_PLAIN_TPB, (size_t)2 * cs16 * sizeof(double), c->stream>>>(M, k, kt, q, n, cf, cs, j0, want,
-                                                                                                          first, threshold, O);
-                else
-                    k_eval_plain<<<g, EVAL_PLAIN_TPB, (size_t)2 * cs16 * sizeof(double), c->stream>>>(M, k, kt, n, cf, cs, j0, want, first,
-                                                                                                     threshold, O);
+                k_eval_plain<<<g, EVAL_PLAIN_TPB, (size_t)2 * cs16 * sizeof(double), c->stream>>>(M, k, kt, n, cf, cs, j0, want, first, threshold, O);
                 PGD_LAUNCH_CHECK(c);
             }
             if (want & PGD_EVAL_STATS) {
@@ -1368,35 +1561,63 @@ static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_
 int pgd_eval_batch(pgd_handle h, const pgd_handle *modes, int k, const double *coefs, int64_t s, int want, double threshold,
                    double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
     PGD_CTX(c, h);
-    return eval_batch_run(c, "eval_batch", nullptr, modes, k, 0, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
+    return eval_batch_run(c, "eval_batch", nullptr, modes, k, 0, PGD_EVAL_Q_NORM, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
+}
+
+// The kind of a *_quantity call against its q (fn: the entry point's name)
+static int eval_kind_check(Ctx *c, const char *fn, int q, int kind) {
+    if (kind < PGD_EVAL_Q_NORM || kind > PGD_EVAL_Q_EIG_SPREAD)
+        return fail(c, PGD_ERR_INVALID, "%s: kind = %d is no pgd_eval_quantity (0 .. %d)", fn, kind, (int)PGD_EVAL_Q_EIG_SPREAD);
+    if (kind == PGD_EVAL_Q_VALUE && q != 1)
+        return fail(c, PGD_ERR_INVALID, "%s: the signed value (kind 1) is that of one plane, q = %d", fn, q);
+    if (eval_kind_is_tensor(kind) && q != 4 && q != EVAL_TENSOR_Q)
+        return fail(c, PGD_ERR_INVALID, "%s: the eigenvalue kinds take the q = 6 planes xx, yy, zz, xy, yz, xz of a symmetric tensor or the "
+                    "q = 4 planes xx, yy, zz, xy of plane strain, q = %d", fn, q);
+    return PGD_OK;
+}
+
+// pgd_eval_batch_norm is kind 0 of pgd_eval_batch_quantity; likewise the two fused calls below (fn: the entry point's name)
+static int eval_batch_planes(Ctx *c, const char *fn, const pgd_handle *modes, int k, int q, int kind, const double *coefs, int64_t s, int want,
+                             double threshold, double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h,
+                             pgd_handle fields_h) {
+    if (q < 1 || q > EVAL_QMAX) return fail(c, PGD_ERR_INVALID, "%s: q = %d planes, 1 .. %d are possible", fn, q, EVAL_QMAX);
+    PGD_TRY(eval_kind_check(c, fn, q, kind));
+    return eval_batch_run(c, fn, nullptr, modes, k, q, kind, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
 }
 
 int pgd_eval_batch_norm(pgd_handle h, const pgd_handle *modes, int k, int q, const double *coefs, int64_t s, int want, double threshold,
                         double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
     PGD_CTX(c, h);
-    if (q < 1 || q > EVAL_QMAX) return fail(c, PGD_ERR_INVALID, "eval_batch_norm: q = %d planes, 1 .. %d are possible", q, EVAL_QMAX);
-    return eval_batch_run(c, "eval_batch_norm", nullptr, modes, k, q, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
-                          fields_h);
+    return eval_batch_planes(c, "eval_batch_norm", modes, k, q, PGD_EVAL_Q_NORM, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h,
+                             exceed_h, fields_h);
 }
 
-int pgd_eval_batch_grad(pgd_handle h, pgd_handle mh, const pgd_handle *modes, int k, const double *L, int q, pgd_handle scale_h,
-                        const double *coefs, int64_t s, int want, double threshold, double *sample_stats, pgd_handle env_min_h,
-                        pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
+int pgd_eval_batch_quantity(pgd_handle h, const pgd_handle *modes, int k, int q, int kind, const double *coefs, int64_t s, int want,
+                            double threshold, double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h,
+                            pgd_handle fields_h) {
     PGD_CTX(c, h);
+    return eval_batch_planes(c, "eval_batch_quantity", modes, k, q, kind, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
+                             fields_h);
+}
+
+static int eval_batch_fused(Ctx *c, const char *fn, pgd_handle mh, const pgd_handle *modes, int k, const double *L, int q, int kind,
+                            pgd_handle scale_h, const double *coefs, int64_t s, int want, double threshold, double *sample_stats,
+                            pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
     Mesh *m = get_mesh(c, mh);
-    if (!m) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: invalid mesh handle");
+    if (!m) return fail(c, PGD_ERR_INVALID, "%s: invalid mesh handle", fn);
     Mesh *b = m->ncomp > 1 ? get_mesh(c, m->base) : m;          // the scalar layout holds the cells and the coordinates
-    if (!b) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: the blocked layout's base is gone");
+    if (!b) return fail(c, PGD_ERR_INVALID, "%s: the blocked layout's base is gone", fn);
     const int G = b->gdim, NC = m->ncomp;
-    if (b->nvpc != G + 1) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: a P2 layout (%d nodes per cell): P1 only", b->nvpc);
-    if (!b->cells || !b->coords) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: the layout has no cell records");
-    if (q < 1 || q > EVAL_QMAX) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: q = %d rows of L, 1 .. %d are possible", q, EVAL_QMAX);
-    if (!L) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: L is missing");
+    if (b->nvpc != G + 1) return fail(c, PGD_ERR_INVALID, "%s: a P2 layout (%d nodes per cell): P1 only", fn, b->nvpc);
+    if (!b->cells || !b->coords) return fail(c, PGD_ERR_INVALID, "%s: the layout has no cell records", fn);
+    if (q < 1 || q > EVAL_QMAX) return fail(c, PGD_ERR_INVALID, "%s: q = %d rows of L, 1 .. %d are possible", fn, q, EVAL_QMAX);
+    if (!L) return fail(c, PGD_ERR_INVALID, "%s: L is missing", fn);
     Vec *scale = scale_h ? get_vec(c, scale_h) : nullptr;
     if (scale_h && (!scale || scale->n != b->nc))
-        return fail(c, PGD_ERR_INVALID, "eval_batch_grad: scale is a vector of one entry per cell (%lld), or 0", (long long)b->nc);
+        return fail(c, PGD_ERR_INVALID, "%s: scale is a vector of one entry per cell (%lld), or 0", fn, (long long)b->nc);
+    PGD_TRY(eval_kind_check(c, fn, q, kind));
     EvalGrad gs;
-    if (!eval_grad_pick(G, NC, &gs.fn)) return fail(c, PGD_ERR_INVALID, "eval_batch_grad: gdim = %d with %d components", G, NC);
+    if (!eval_grad_pick(G, NC, kind, &gs.fn)) return fail(c, PGD_ERR_INVALID, "%s: gdim = %d with %d components", fn, G, NC);
     gs.src.cells = b->cells;
     gs.src.coords = b->coords;
     gs.src.scale = scale ? scale->d : nullptr;
@@ -1406,8 +1627,23 @@ int pgd_eval_batch_grad(pgd_handle h, pgd_handle mh, const pgd_handle *modes, in
     gs.mode_len = b->nv * NC;
     gs.entries = b->nc;
     gs.scale = scale;
-    return eval_batch_run(c, "eval_batch_grad", &gs, modes, k, q, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
-                          fields_h);
+    return eval_batch_run(c, fn, &gs, modes, k, q, kind, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
+}
+
+int pgd_eval_batch_grad(pgd_handle h, pgd_handle mh, const pgd_handle *modes, int k, const double *L, int q, pgd_handle scale_h,
+                        const double *coefs, int64_t s, int want, double threshold, double *sample_stats, pgd_handle env_min_h,
+                        pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
+    PGD_CTX(c, h);
+    return eval_batch_fused(c, "eval_batch_grad", mh, modes, k, L, q, PGD_EVAL_Q_NORM, scale_h, coefs, s, want, threshold, sample_stats, env_min_h,
+                            env_max_h, exceed_h, fields_h);
+}
+
+int pgd_eval_batch_grad_quantity(pgd_handle h, pgd_handle mh, const pgd_handle *modes, int k, const double *L, int q, int kind,
+                                 pgd_handle scale_h, const double *coefs, int64_t s, int want, double threshold, double *sample_stats,
+                                 pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
+    PGD_CTX(c, h);
+    return eval_batch_fused(c, "eval_batch_grad_quantity", mh, modes, k, L, q, kind, scale_h, coefs, s, want, threshold, sample_stats, env_min_h,
+                            env_max_h, exceed_h, fields_h);
 }
 
 int pgd_eval_norm_last_shape(pgd_handle h, int *rows, int *staged) {
@@ -1488,16 +1724,16 @@ int pgd_cell_gradient_p2(pgd_handle h, pgd_handle mh, pgd_handle uh, const doubl
     return PGD_OK;
 }
 
-int pgd_eval_batch_grad_p2(pgd_handle h, pgd_handle mh, const pgd_handle *modes, int k, const double *lam, int npt, const double *L, int q,
-                           pgd_handle scale_h, const double *coefs, int64_t s, int want, double threshold, double *sample_stats,
-                           pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
-    PGD_CTX(c, h);
+static int eval_batch_fused_p2(Ctx *c, const char *fn, pgd_handle mh, const pgd_handle *modes, int k, const double *lam, int npt,
+                               const double *L, int q, int kind, pgd_handle scale_h, const double *coefs, int64_t s, int want, double threshold,
+                               double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
     Mesh *m, *b;
     Vec *scale;
     EvalGrad gs;
-    PGD_TRY(grad_p2_check(c, "eval_batch_grad_p2", mh, lam, npt, L, q, scale_h, &m, &b, &scale, &gs.src.pts, &gs.src.L));
-    if (!eval_grad_p2_pick(b->gdim, m->ncomp, &gs.fn))
-        return fail(c, PGD_ERR_INVALID, "eval_batch_grad_p2: gdim = %d with %d components", b->gdim, m->ncomp);
+    PGD_TRY(grad_p2_check(c, fn, mh, lam, npt, L, q, scale_h, &m, &b, &scale, &gs.src.pts, &gs.src.L));
+    PGD_TRY(eval_kind_check(c, fn, q, kind));
+    if (!eval_grad_p2_pick(b->gdim, m->ncomp, kind, &gs.fn))
+        return fail(c, PGD_ERR_INVALID, "%s: gdim = %d with %d components", fn, b->gdim, m->ncomp);
     gs.src.cells = nullptr;
     gs.src.cellsN = b->cellsN;
     gs.src.coords = b->coords;
@@ -1507,8 +1743,24 @@ int pgd_eval_batch_grad_p2(pgd_handle h, pgd_handle mh, const pgd_handle *modes,
     gs.mode_len = b->nv * m->ncomp;
     gs.entries = (int64_t)npt * b->nc;
     gs.scale = scale;
-    return eval_batch_run(c, "eval_batch_grad_p2", &gs, modes, k, q, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h,
-                          fields_h);
+    return eval_batch_run(c, fn, &gs, modes, k, q, kind, coefs, s, want, threshold, sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
+}
+
+int pgd_eval_batch_grad_p2(pgd_handle h, pgd_handle mh, const pgd_handle *modes, int k, const double *lam, int npt, const double *L, int q,
+                           pgd_handle scale_h, const double *coefs, int64_t s, int want, double threshold, double *sample_stats,
+                           pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h, pgd_handle fields_h) {
+    PGD_CTX(c, h);
+    return eval_batch_fused_p2(c, "eval_batch_grad_p2", mh, modes, k, lam, npt, L, q, PGD_EVAL_Q_NORM, scale_h, coefs, s, want, threshold,
+                               sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
+}
+
+int pgd_eval_batch_grad_p2_quantity(pgd_handle h, pgd_handle mh, const pgd_handle *modes, int k, const double *lam, int npt, const double *L,
+                                    int q, int kind, pgd_handle scale_h, const double *coefs, int64_t s, int want, double threshold,
+                                    double *sample_stats, pgd_handle env_min_h, pgd_handle env_max_h, pgd_handle exceed_h,
+                                    pgd_handle fields_h) {
+    PGD_CTX(c, h);
+    return eval_batch_fused_p2(c, "eval_batch_grad_p2_quantity", mh, modes, k, lam, npt, L, q, kind, scale_h, coefs, s, want, threshold,
+                               sample_stats, env_min_h, env_max_h, exceed_h, fields_h);
 }
 
 }  // extern "C"

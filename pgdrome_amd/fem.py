@@ -1989,6 +1989,61 @@ def gradient_quantity(name, gdim, ncomp):
     raise ValueError("gradient_quantity: unknown quantity %r ('gradient_norm', 'von_mises')" % (name,))
 
 
+# What becomes of the rows of L g (pgd_eval_quantity of include/pgd_amd.h): their norm, the one row with its sign, an eigenvalue of the
+# symmetric tensor they are
+from ._lib import EVAL_Q_EIG_MAX, EVAL_Q_EIG_MIN, EVAL_Q_EIG_SPREAD, EVAL_Q_NORM, EVAL_Q_VALUE      # noqa: E402  (plain integers)
+STRESS_QUANTITIES = {"max_principal": EVAL_Q_EIG_MAX, "min_principal": EVAL_Q_EIG_MIN, "tresca": EVAL_Q_EIG_SPREAD,
+                     "stress_component": EVAL_Q_VALUE}
+
+
+def stress_quantity(name, gdim, nu, component=None):
+    """(L, kind) of a quantity of the stress tensor of a displacement field (ncomp == gdim in (2, 3)) of an isotropic material with
+    Poisson's ratio ``nu`` in (-1, 1/2): the rows of L (q x gdim^2, on g[c * gdim + a] = d u_c / d x_a as ``gradient_quantity``) are
+    the components xx, yy, zz, xy (, yz, xz) of sigma / E = eps / (1 + nu) + nu / ((1 + nu) (1 - 2 nu)) tr(eps) I - Lame's lambda
+    does not drop out of a principal stress as it does out of the deviator - so Young's modulus is the ``scale``; in 2-D for plane
+    strain (eps_zz = 0, sigma_zz = nu (sigma_xx + sigma_yy), no yz and xz).  ``kind`` says what becomes of them:
+
+    "max_principal", "min_principal": the largest / smallest eigenvalue of sigma (EVAL_Q_EIG_MAX / EVAL_Q_EIG_MIN);
+    "tresca": their difference, twice the largest shear stress (EVAL_Q_EIG_SPREAD);
+    "stress_component": the one row sigma_ab of ``component`` = (a, b) with its sign (EVAL_Q_VALUE); in 2-D a, b in (0, 1), or
+    (2, 2) for sigma_zz."""
+    gdim = int(gdim)
+    if gdim not in (2, 3):
+        raise ValueError("stress_quantity: a displacement field in 2 or 3 dimensions, got gdim = %r" % (gdim,))
+    if name not in STRESS_QUANTITIES:
+        raise ValueError("stress_quantity: unknown quantity %r (%s)" % (name, ", ".join(repr(k) for k in STRESS_QUANTITIES)))
+    if nu is None:
+        raise ValueError("stress_quantity: %r needs Poisson's ratio nu (Lame's lambda is in the stress)" % (name,))
+    nu = float(nu)
+    if not -1.0 < nu < 0.5:
+        raise ValueError("stress_quantity: nu = %r, Poisson's ratio lies in (-1, 1/2)" % (nu,))
+    G = gdim
+    eps = np.zeros((3, 3, G * G))                     # eps[a, b] as a row over g
+    for a in range(G):
+        for b in range(G):
+            eps[a, b, a * G + b] += 0.5
+            eps[a, b, b * G + a] += 0.5
+    tr = eps[0, 0] + eps[1, 1] + eps[2, 2]
+    lam = nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+    sig = eps / (1.0 + nu)
+    for a in range(3):
+        sig[a, a] += lam * tr
+    kind = STRESS_QUANTITIES[name]
+    if kind == EVAL_Q_VALUE:
+        try:
+            a, b = (int(i) for i in component)
+        except (TypeError, ValueError):
+            raise ValueError("stress_quantity: \"stress_component\" needs component=(a, b), got %r" % (component,)) from None
+        if not ((0 <= a < G and 0 <= b < G) or (a, b) == (2, 2)):
+            raise ValueError("stress_quantity: unknown component %r in %d-D (a, b below %d%s)"
+                             % (component, G, G, ", or (2, 2)" if G == 2 else ""))
+        return sig[a, b][None, :].copy(), kind
+    if component is not None:
+        raise ValueError("stress_quantity: component=%r goes with \"stress_component\" only" % (component,))
+    planes = ((0, 0), (1, 1), (2, 2), (0, 1)) + (((1, 2), (0, 2)) if G == 3 else ())
+    return np.array([sig[a, b] for a, b in planes]), kind
+
+
 class DerivativeFunction:
     """d f / d x_axis of a scalar Function as a callable of the point."""
 

@@ -303,6 +303,25 @@ def _eval_many_host(values, n, S, sample_chunk, stats, envelope, thr, fields, wr
     return res
 
 
+_TENSOR_PLANES = ((0, 0), (1, 1), (2, 2), (0, 1), (1, 2), (0, 2))      # the plane order of fem.stress_quantity
+
+
+def _quantity_values(U, kind):
+    """The values of kind ``kind`` (fem.EVAL_Q_*) of combined planes U (q, ...): the host half of the value epilogue of
+    ``pgd_eval_batch_quantity`` - the norm over the planes, the one plane with its sign, or the largest / smallest eigenvalue (or
+    their difference) of the symmetric tensors whose planes are xx, yy, zz, xy (, yz, xz), from ``np.linalg.eigvalsh``."""
+    if kind == fem.EVAL_Q_NORM:
+        return np.sqrt((U * U).sum(axis=0))
+    if kind == fem.EVAL_Q_VALUE:
+        return U[0]
+    T = np.zeros(U.shape[1:] + (3, 3))
+    for i in range(U.shape[0]):
+        a, b = _TENSOR_PLANES[i]
+        T[..., a, b] = T[..., b, a] = U[i]
+    w = np.linalg.eigvalsh(T)                        # ascending
+    return w[..., 2] if kind == fem.EVAL_Q_EIG_MAX else w[..., 0] if kind == fem.EVAL_Q_EIG_MIN else w[..., 2] - w[..., 0]
+
+
 def _eval_points_device(be, call, m, stats, envelope):
     """``_eval_many_device`` for entries that are no function space (several points per cell): the statistics as they come, the
     two envelopes of ``m`` entries as numpy arrays."""
@@ -850,7 +869,7 @@ class PGD:
     # ------------------------------------------------- batched evaluation of gradient quantities
     def evaluate_gradient_many(self, fixed_dim, free_dim, coords, attri, quantity="gradient_norm", scale=None, stats=True,
                                envelope=False, threshold=None, fields=False, fields_max_bytes=4 << 30, modes_max_bytes=16 << 30,
-                               sample_chunk=256, planes="stored", at=None):
+                               sample_chunk=256, planes="stored", at=None, nu=None, component=None):
         """``evaluate_many`` for a quantity of the spatial gradient of the solution: per cell of the fixed mesh and per sample
         the value ``scale * |L grad u|`` with L = ``fem.gradient_quantity(quantity, ...)`` - "gradient_norm" (with a conductivity
         as ``scale``: the flux magnitude) or "von_mises" (with ``scale`` = 2 mu = E / (1 + nu): the von Mises stress).  ``scale``:
@@ -881,9 +900,19 @@ class PGD:
         ``pgd_eval_batch_grad_p2``; intervals are always served by the host.  P1 modes take ``None`` or "midpoint" (the same
         thing) and refuse "vertices".
 
-        Returns an ``EvalManyResult`` whose Functions live on ``FunctionSpace(mesh, "DG", 0)`` of the fixed mesh; ``max_abs``
-        equals ``max``.  Signed components (one row of L, no norm) are ``evaluate_many``-like fields of one plane:
-        ``pgd_eval_batch`` on the output of ``pgd_cell_gradient`` gives them."""
+        Quantities of the stress tensor itself, for a displacement field of an isotropic material with Poisson's ratio ``nu`` and
+        ``scale`` = E (``fem.stress_quantity``; Lame's lambda is in them, so ``nu`` is needed): "max_principal" (the largest
+        principal stress: Rankine, tension in brittle materials), "min_principal", "tresca" (largest minus smallest principal
+        stress) and "stress_component" with ``component`` = (a, b), the signed sigma_ab.  Everything above holds for them -
+        ``planes``, P1 and P2 with ``at``, host and device (``pgd_eval_batch_quantity`` and its fused forms; the host takes the
+        eigenvalues from ``np.linalg.eigvalsh``) - with signed values: ``max_abs`` is max |v| (equal to ``max`` for "tresca").
+        What ``at="vertices"`` bounds changes with the quantity: the largest eigenvalue and the spread are convex functions of
+        a tensor that is affine on the cell, so for "max_principal" and "tresca" ``max`` and ``envelope_max`` are exact over the
+        cell and ``min`` / ``envelope_min`` upper bounds; the smallest eigenvalue is concave, so for "min_principal" ``min`` and
+        ``envelope_min`` are exact and ``max`` / ``envelope_max`` lower bounds; a component is affine: both are exact.
+
+        Returns an ``EvalManyResult`` whose Functions live on ``FunctionSpace(mesh, "DG", 0)`` of the fixed mesh; for the two
+        norms ``max_abs`` equals ``max``."""
         if planes not in ("stored", "fused", "auto"):
             raise ValueError("evaluate_gradient_many: planes=%r, \"stored\", \"fused\" or \"auto\" are possible" % (planes,))
         if at not in (None, "midpoint", "vertices"):
@@ -920,7 +949,17 @@ class PGD:
         if mesh.part is not None or getattr(lay, "part", None) is not None:
             raise NotImplementedError("evaluate_gradient_many on a row-sharded fixed dimension (every rank holds a slab of the "
                                       "modes; the per-sample statistics would need a reduction across ranks)")
-        L = fem.gradient_quantity(quantity, mesh.geometry().dim(), V._ncomp)
+        if quantity in fem.STRESS_QUANTITIES:
+            if V._ncomp != mesh.geometry().dim():
+                raise ValueError("evaluate_gradient_many: %r is a quantity of the stress of a displacement field, the modes have %d "
+                                 "component%s in %d-D" % (quantity, V._ncomp, "" if V._ncomp == 1 else "s", mesh.geometry().dim()))
+            L, kind = fem.stress_quantity(quantity, mesh.geometry().dim(), nu, component)
+        else:
+            if nu is not None or component is not None:
+                raise ValueError("evaluate_gradient_many: nu and component go with the stress quantities (%s), not with %r"
+                                 % (", ".join(repr(k) for k in fem.STRESS_QUANTITIES), quantity))
+            L, kind = fem.gradient_quantity(quantity, mesh.geometry().dim(), V._ncomp), fem.EVAL_Q_NORM
+        nonneg = kind in (fem.EVAL_Q_NORM, fem.EVAL_Q_EIG_SPREAD)
         scale_vec = None
         if isinstance(scale, fem.Function):
             Vs = scale.function_space()
@@ -949,20 +988,25 @@ class PGD:
         be = fem.get_backend()
         Vc = fem.FunctionSpace(mesh, "DG", 0)
         if planes == "fused":
-            res = self._evaluate_gradient_fused(be, V, Vc, modes[:K], L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk, lam)
+            res = self._evaluate_gradient_fused(be, V, Vc, modes[:K], L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk, lam,
+                                                kind)
         else:
             p2dev = lam is not None and lay.coords.shape[1] > 1 and hasattr(be, "cell_gradient_p2")      # (intervals: the host)
-            device = (nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "eval_batch_norm") and
+            device = (nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and
+                      hasattr(be, "eval_batch_norm" if kind == fem.EVAL_Q_NORM else "eval_batch_quantity") and
                       (hasattr(be, "cell_gradient") if lam is None else p2dev))
             key = (quantity, K, scale_key, device, id(be), tuple((id(f.vector()), f.vector().version) for f in modes[:K]),
-                   at if lam is not None else None)
+                   None if nu is None else float(nu), None if component is None else tuple(component), at if lam is not None else None)
             cache = getattr(att, "_gradient_modes", None)
             if cache is None or cache.key != key:
                 att._gradient_modes = None                       # the old planes go before the new ones are allocated
                 cache = att._gradient_modes = _GradientModes(key, be if device else None, mesh, V, modes[:K], L, scale_vec, lam)
                 fem.STATS["gradient_mode_builds"] = fem.STATS.get("gradient_mode_builds", 0) + 1
             if device:
-                call = lambda st, **kw: be.eval_batch_norm(cache.planes, q, C, stats=st, **kw)
+                if kind == fem.EVAL_Q_NORM:
+                    call = lambda st, **kw: be.eval_batch_norm(cache.planes, q, C, stats=st, **kw)
+                else:
+                    call = lambda st, **kw: be.eval_batch_quantity(cache.planes, q, kind, C, stats=st, **kw)
                 res = (_eval_many_device(be, call, Vc, nc, S, stats, envelope, thr, fields) if npt == 1 else
                        _eval_points_device(be, call, m, stats, envelope))
                 fem.STATS["eval_gradient_calls"] = fem.STATS.get("eval_gradient_calls", 0) + 1
@@ -971,13 +1015,15 @@ class PGD:
 
                 def norms(j0, step):
                     Cc = C[:, j0:j0 + step]
+                    if kind != fem.EVAL_Q_NORM:
+                        return _quantity_values(np.stack([P[i] @ Cc for i in range(q)]), kind)
                     ss = np.zeros((m, Cc.shape[1]))
                     for i in range(q):
                         U = P[i] @ Cc
                         ss += U * U
                     return np.sqrt(ss)                              # (entries, cs)
                 res = _eval_many_host(norms, m, S, sample_chunk, stats, envelope, thr, fields,
-                                      (lambda a: _host_function(Vc, a)) if npt == 1 else (lambda a: a), nonnegative=True)
+                                      (lambda a: _host_function(Vc, a)) if npt == 1 else (lambda a: a), nonnegative=nonneg)
         if npt > 1 and envelope:                         # the corners of a cell -> DG0 (the entries are point-major)
             res.envelope_min = _host_function(Vc, res.envelope_min.reshape(npt, nc).min(axis=0))
             res.envelope_max = _host_function(Vc, res.envelope_max.reshape(npt, nc).max(axis=0))
@@ -985,25 +1031,35 @@ class PGD:
         return res
 
     @staticmethod
-    def _evaluate_gradient_fused(be, V, Vc, modes, L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk, lam=None):
+    def _evaluate_gradient_fused(be, V, Vc, modes, L, scale_vec, C, S, stats, envelope, thr, fields, sample_chunk, lam=None,
+                                 kind=fem.EVAL_Q_NORM):
         """``evaluate_gradient_many(planes="fused")``: no planes are built or kept.  Device: ``pgd_eval_batch_grad`` on the nodal
         modes (``pgd_eval_batch_grad_p2`` at the points ``lam`` for P2 modes).  Host: per sample chunk the nodal product F C, then
         the cell gradients of the chunk's fields - the einsum of ``_GradientModes`` on the fields instead of the modes.  With more
-        than one point per cell the envelopes come back as arrays of points x cells entries."""
+        than one point per cell the envelopes come back as arrays of points x cells entries.  ``kind``: what becomes of the
+        planes (fem.EVAL_Q_*; other than the norm: the backend's ``*_quantity`` calls, ``_quantity_values`` on the host)."""
         mesh, K = V.mesh(), len(modes)
         q, nc, ncomp = L.shape[0], mesh.num_cells(), V._ncomp
         npt = 1 if lam is None else len(lam)
         lay = V._lay.base if ncomp > 1 else V._lay
         fem.STATS["eval_gradient_fused_calls"] = fem.STATS.get("eval_gradient_fused_calls", 0) + 1
-        p2dev = lam is not None and lay.coords.shape[1] > 1 and hasattr(be, "eval_batch_grad_p2")          # (intervals: the host)
-        if nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and (hasattr(be, "eval_batch_grad") if lam is None else p2dev):
+        norm = kind == fem.EVAL_Q_NORM
+        nonneg = kind in (fem.EVAL_Q_NORM, fem.EVAL_Q_EIG_SPREAD)
+        p2dev = (lam is not None and lay.coords.shape[1] > 1 and                                            # (intervals: the host)
+                 hasattr(be, "eval_batch_grad_p2" if norm else "eval_batch_grad_p2_quantity"))
+        if nc >= DEVICE_EVAL_MIN_DOFS and K <= 256 and (hasattr(be, "eval_batch_grad" if norm else "eval_batch_grad_quantity")
+                                                        if lam is None else p2dev):
             handles = [m.vector().dev() for m in modes]
             sc = scale_vec.dev() if scale_vec is not None else 0
 
             def call(st, **kw):
                 try:
                     if lam is not None:
+                        if not norm:
+                            return be.eval_batch_grad_p2_quantity(V._lay.handle(), handles, lam, L, kind, C, scale=sc, stats=st, **kw)
                         return be.eval_batch_grad_p2(V._lay.handle(), handles, lam, L, C, scale=sc, stats=st, **kw)
+                    if not norm:
+                        return be.eval_batch_grad_quantity(V._lay.handle(), handles, L, kind, C, scale=sc, stats=st, **kw)
                     return be.eval_batch_grad(V._lay.handle(), handles, L, C, scale=sc, stats=st, **kw)
                 except RuntimeError as exc:
                     if getattr(exc, "code", None) != -4:                  # PGD_ERR_LIMIT
@@ -1023,8 +1079,8 @@ class PGD:
                 P = np.einsum("ij,aejs->iaes", L, _p2_point_gradients(lay, U, lam))       # (q, npt, cells, cs)
                 if sc is not None:
                     P = P * sc[None, None, :, None]
-                return np.sqrt((P * P).sum(axis=0)).reshape(npt * nc, -1)
-            return _eval_many_host(norms_p2, npt * nc, S, sample_chunk, stats, envelope, thr, fields, wrap, nonnegative=True)
+                return _quantity_values(P, kind).reshape(npt * nc, -1)
+            return _eval_many_host(norms_p2, npt * nc, S, sample_chunk, stats, envelope, thr, fields, wrap, nonnegative=nonneg)
         X, cells = mesh.coordinates(), mesh.cells()
         G = cells.shape[1] - 1
         Einv = np.linalg.inv(X[cells[:, 1:]] - X[cells[:, :1]])                  # rows of E: the edges x_a - x_0; (cells, d, a)
@@ -1036,9 +1092,9 @@ class PGD:
             P = np.einsum("ij,ejs->ies", L, g)                                    # (q, cells, cs)
             if sc is not None:
                 P = P * sc[None, :, None]
-            return np.sqrt((P * P).sum(axis=0))
+            return _quantity_values(P, kind)
         return _eval_many_host(norms, nc, S, sample_chunk, stats, envelope, thr, fields, lambda a: _host_function(Vc, a),
-                               nonnegative=True)
+                               nonnegative=nonneg)
 
     # ------------------------------------------------------ sensor responses and derivatives
     def _check_free(self, free_dim, coord, attri, fixed_dim):

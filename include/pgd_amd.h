@@ -610,10 +610,61 @@ int pgd_eval_batch_grad_p2_quantity(pgd_handle ctx, pgd_handle mesh, const pgd_h
                                     double threshold, double *sample_stats, pgd_handle env_min, pgd_handle env_max,
                                     pgd_handle exceed, pgd_handle fields);
 
+/* ------------------------------------------------------- point sets (sensors) --- */
+/* The field at a few points of the large dimension - what a calibration compares with measurements (reference
+ * pgdrome/model.py: evaluate_sensor_response, evaluate_derivative_sensor_response, which load fenicstools.Probes for it).  A
+ * point set holds, on the device, the cell of every point and its barycentric coordinates there; sampling a nodal field at the
+ * set gathers through the cell records, so a mode never leaves the device.
+ *
+ * pgd_points_locate: pts: host, npts x gdim row-major;  mesh: any layout with cell records - intervals, triangles, tetrahedra,
+ * P1 or P2, scalar or blocked; only the vertex part of the records and the vertex coordinates are used.
+ *   The cell of a point is the one with the LARGEST SMALLEST barycentric coordinate; among cells whose minima are equal as
+ *   doubles the lowest cell index wins.  A maximum below -tol gives cell -1 (lam is then zeros), so does a point with a NaN
+ *   coordinate.  A cell whose determinant is zero or not finite is never chosen.  The barycentric coordinates come from the cell's
+ *   own vertices - edge matrix, cofactors, determinant, as pgd_cell_gradient forms its inverse Jacobian - and lam_0 = 1 - sum of
+ *   the others.  Cells and lam do not depend on the launch shape, bit for bit: (minimum, cell) pairs are compared, never added
+ *   (no atomics: persistent workgroups, one row of pairs each, a fixed-order final pass); the points go in tiles of 32, one pair
+ *   of launches per tile.  On regularly numbered 3-D box lattices (cell 6 q + t, see PGD_TUNE_ASM_LATTICE) and tol <= 1/8 a thread
+ *   per point tests the tetrahedra of the up to 27 cubes around the point instead (PGD_TUNE_LOCATE_LATTICE): the same cells and
+ *   lam, bit for bit.  PGD_ERR_INVALID for tol < 0 or not finite and for a null pts with npts > 0.
+ *   npts == 0 gives an empty set.  The call synchronises with the host once.
+ * pgd_points_from: the set of known (cell, lam) pairs - cells: host int32, lam: host, npts x (gdim + 1).  Cells are checked on the
+ *   host against [-1, nc) (PGD_ERR_INVALID, like null cells or lam with npts > 0); -1 is kept.  lam is taken as it is, and so is the cell: the caller answers for a degenerate one (zero
+ *   determinant), where sampled gradients are not numbers.
+ * pgd_points_download: cells_out (npts) and lam_out (npts x (gdim + 1)), host arrays; either may be NULL.
+ * pgd_points_info: the number of points, gdim and the first point whose cell is -1 (-1: none); null outputs are skipped.
+ * pgd_points_last_path: what the last pgd_points_locate of the context ran: 0 nothing, 1 the general kernel, 2 the lattice path.
+ *
+ * pgd_points_sample: layout: any P1 or P2 layout, scalar or blocked, over a mesh with the point set's number of cells and gdim
+ * (the caller guarantees it is the same mesh);  u: nv*ncomp entries, node*ncomp + c.
+ *   what = 0: out[p*ncomp + c] = sum_a N_a(lam_p) u[node_a*ncomp + c], the fma chain from 0 over the record's nodes in
+ *   ascending local order; P2: N = l (2 l - 1) at the vertices, 4 l_a l_b on the edges in the order pgd_mesh_upload states
+ *   (interval: the one edge).  A point at a node returns the nodal value bit for bit.
+ *   what = 1: out[(p*ncomp + c)*gdim + d] = d u_c / d x_d at the point: the cell's constant gradient for P1, the affine one at lam
+ *   with the formulas of pgd_cell_gradient_p2 for P2 (the 1-D P2 layout included: its records hold all that is needed).  The
+ *   gradient of a point on a face, an edge or a vertex is that of the cell the rule above chose - one-sided.
+ *   PGD_ERR_INVALID with a message, before anything is launched, for: a set that holds a cell -1 (the first such point is named:
+ *   no gather can go out of range), a layout of another cell count or gdim, u or out of the wrong size (out: npts*ncomp, times
+ *   gdim for gradients), out aliasing u, what out of range.  npts == 0 is PGD_OK.  A thread per point; no atomics, no host
+ *   synchronisation.                                                                                                          */
+int pgd_points_locate(pgd_handle ctx, pgd_handle mesh, const double *pts, int64_t npts, double tol, pgd_handle *points);
+int pgd_points_from(pgd_handle ctx, pgd_handle mesh, const int32_t *cells, const double *lam, int64_t npts, pgd_handle *points);
+int pgd_points_download(pgd_handle ctx, pgd_handle points, int32_t *cells_out, double *lam_out);
+int pgd_points_info(pgd_handle ctx, pgd_handle points, int64_t *npts, int *gdim, int64_t *first_outside);
+int pgd_points_last_path(pgd_handle ctx, int *path);
+int pgd_points_sample(pgd_handle ctx, pgd_handle points, pgd_handle layout, pgd_handle u, int what, pgd_handle out);
+int pgd_points_free(pgd_handle ctx, pgd_handle points);
+
 /* ------------------------------------------------------------------ tuning --- */
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_LOCATE_GRID_MAX = 61, /* pgd_points_locate, general kernel: > 0: at most this many (persistent) workgroups; 0 (default): as many as
+                                are resident at once.  Same cells and lam either way (tests reach the loop over the cells and the final
+                                pass over several rows with it). */
+    PGD_TUNE_LOCATE_LATTICE = 60, /* 1 (default): pgd_points_locate on a regularly numbered 3-D box lattice with tol <= 1/8 runs a thread per
+                                point over the tetrahedra of the cubes around it; 0: the general kernel over all cells.  Same cells and
+                                lam, bit for bit. */
     PGD_TUNE_SPMV_P2_LATTICE = 59, /* 1: an OPERATOR (pgd_op_combine) on a P2 layout that pgd_mesh_p2_bind has bound to the 3-D box lattice of its
                                 vertices - scalar, or pgd_mesh_blocked of one with 2 or 3 components; at least 3 vertices per axis, the
                                 edge list ascending - multiplies over its whole row range from a row-class form in k_spmv_p2lat: every

@@ -163,6 +163,13 @@ SIGNATURES = {
     "pgd_p2lat_counts": (C.c_int, [H, PI64, PI64, PI64]),
     "pgd_p2lat_times": (C.c_int, [H, C.POINTER(C.c_double)]),
     "pgd_calib_stream": (C.c_int, [H, H, C.c_int, C.c_int]),
+    "pgd_points_locate": (C.c_int, [H, H, PD, I64, F64, PH]),
+    "pgd_points_from": (C.c_int, [H, H, PI32, PD, I64, PH]),
+    "pgd_points_download": (C.c_int, [H, H, PI32, PD]),
+    "pgd_points_info": (C.c_int, [H, H, PI64, C.POINTER(C.c_int), PI64]),
+    "pgd_points_last_path": (C.c_int, [H, C.POINTER(C.c_int)]),
+    "pgd_points_sample": (C.c_int, [H, H, H, H, C.c_int, H]),
+    "pgd_points_free": (C.c_int, [H, H]),
     "pgd_timer_start": (C.c_int, [H]),
     "pgd_timer_stop": (C.c_int, [H, PD]),
 }
@@ -175,6 +182,9 @@ TUNE_BLOCK_STORAGE = 54
 TUNE_PCG_FOLD_MARCH, TUNE_PCG_SCALAR_S, TUNE_PCG_FUSED_MARCH = 55, 56, 57
 TUNE_SPMV_BLOCK_DIA = 58
 TUNE_SPMV_P2_LATTICE = 59
+TUNE_LOCATE_LATTICE, TUNE_LOCATE_GRID_MAX = 60, 61
+LOCATE_TILE = 32                                    # points per launch of the general location kernel (LOC_PT, csrc/pgd_locate.hip)
+LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE = 1, 2     # pgd_points_last_path
 BLOCK_F32, BLOCK_F64, BLOCK_MAXK = 0, 1, 64                                           # PGD_BLOCK_* (include/pgd_amd.h)
 
 
@@ -539,6 +549,53 @@ class Context:
         return self._eval_batch("eval_batch_grad_p2", self.lib.pgd_eval_batch_grad_p2,
                                 (dptr(lam) if lam.size else None, lam.shape[0], dptr(L) if L.size else None, L.shape[0], int(scale or 0)),
                                 modes, coefs, stats, env_min, env_max, exceed, threshold, fields, lead=(int(mesh),))
+
+    # ---- point sets
+    def points_locate(self, mesh, pts, tol=1e-10):
+        """pgd_points_locate: the point set handle of ``pts`` (P, gdim) on the layout ``mesh``; a point outside gets cell -1."""
+        pts = np.ascontiguousarray(pts, dtype=np.float64)
+        if pts.ndim != 2:
+            raise ValueError("points_locate: pts is a (points, gdim) array")
+        out = H(0)
+        self._ck(self.lib.pgd_points_locate(self.h, mesh, dptr(pts) if pts.size else None, pts.shape[0], float(tol), C.byref(out)))
+        return out.value
+
+    def points_from(self, mesh, cells, lam):
+        """pgd_points_from: the point set of known cells (P,) and barycentric coordinates (P, gdim + 1); a cell may be -1."""
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        if cells.ndim != 1 or lam.ndim != 2 or lam.shape[0] != cells.shape[0]:
+            raise ValueError("points_from: cells (P,) and lam (P, gdim + 1)")
+        out = H(0)
+        self._ck(self.lib.pgd_points_from(self.h, mesh, iptr(cells) if cells.size else None, dptr(lam) if lam.size else None,
+                                          cells.shape[0], C.byref(out)))
+        return out.value
+
+    def points_info(self, points):
+        """(number of points, gdim, first point outside the mesh or -1) of a point set."""
+        n, g, first = I64(0), C.c_int(0), I64(0)
+        self._ck(self.lib.pgd_points_info(self.h, points, C.byref(n), C.byref(g), C.byref(first)))
+        return n.value, g.value, first.value
+
+    def points_download(self, points):
+        """(cells (P,) int32, lam (P, gdim + 1)) of a point set."""
+        n, g, _ = self.points_info(points)
+        cells, lam = np.empty(n, dtype=np.int32), np.empty((n, g + 1), dtype=np.float64)
+        self._ck(self.lib.pgd_points_download(self.h, points, iptr(cells), dptr(lam)))
+        return cells, lam
+
+    def points_last_path(self):
+        """What the last points_locate ran: 0 nothing, LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE."""
+        path = C.c_int(0)
+        self._ck(self.lib.pgd_points_last_path(self.h, C.byref(path)))
+        return path.value
+
+    def points_sample(self, points, layout, u, out, gradient=False):
+        """pgd_points_sample: the values (``gradient``: the gradients) of the nodal field ``u`` of ``layout`` at the points, into ``out``."""
+        self._ck(self.lib.pgd_points_sample(self.h, points, layout, u, 1 if gradient else 0, out))
+
+    def points_free(self, points):
+        self._ck(self.lib.pgd_points_free(self.h, points))
 
     def vec_set(self, v, idx, val):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

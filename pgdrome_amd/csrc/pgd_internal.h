@@ -36,7 +36,7 @@ struct Ctx;
 void dev_release(Ctx *c, void *p, size_t bytes);   // back to the context's buffer pool
 
 struct Obj {
-    enum Kind { FREE = 0, VEC, MESH, CSR, BLOCK } kind = FREE;
+    enum Kind { FREE = 0, VEC, MESH, CSR, BLOCK, POINTS } kind = FREE;
     Ctx *ctx = nullptr;
     uint64_t serial = 0;        // unique per object of a context (handles are recycled, serials are not): put_obj
     virtual ~Obj() {}
@@ -405,6 +405,9 @@ struct Ctx {
     uint16_t *p2lat_tab = nullptr; // class slot tables on the device (pgd_p2lat.hip), built once per context: (offset, class) of a slot ...
     int16_t *p2lat_slot = nullptr; // ... and the slot of (class, offset, class)
     int block_storage = 1;        // storage of the spectral start space (PGD_TUNE_BLOCK_STORAGE): 0 = f64 vectors, 1 = fp32 block, 2 = f64 block
+    // pgd_points_locate (pgd_locate.hip): the one-thread-per-point path on regularly numbered box lattices (PGD_TUNE_LOCATE_LATTICE), the
+    // grid cap of the general kernel (PGD_TUNE_LOCATE_GRID_MAX; 0: what is resident at once) and what the last call ran (pgd_points_last_path)
+    int locate_lattice = 1, locate_grid_max = 0, locate_last_path = 0;
 
     // SpMV launch timing (HIP events on `stream`)
     bool prof = false;

@@ -31,6 +31,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import functools
+import hashlib
 import itertools
 import logging
 import math
@@ -1955,6 +1956,139 @@ def point_gradient(f, x):
         raise NotImplementedError("gradient of a vector-valued function")
     nodes, N, dN = point_basis(V._lay, x, grad=True)
     return dN.T @ f._vec.host()[nodes]
+
+
+# ---- point sets: many points located at once (the sensor side of the online phase, model.PGD.evaluate_sensor_response_many)
+def affine_inverse(X, cells):
+    """(Tinv, P0) of the given cell records: the inverse of the edge matrix T (columns: vertex a + 1 minus vertex 0) and vertex 0 -
+    the arithmetic ``point_basis`` caches for the whole mesh, here for any subset of the cells."""
+    P = X[cells]
+    T = np.transpose(P[:, 1:, :] - P[:, :1, :], (0, 2, 1))
+    return np.linalg.inv(T), P[:, 0, :].copy()
+
+
+def barycentric(Tinv, P0, x):
+    """L[p, c, :]: the barycentric coordinates of the points x (P, D) in the cells behind (Tinv, P0), ``point_basis``'s formula."""
+    lam = np.einsum("cij,pcj->pci", Tinv, x[:, None, :] - P0[None, :, :])
+    return np.concatenate([(1.0 - lam.sum(axis=2))[:, :, None], lam], axis=2)
+
+
+def shape_functions(lay, lam, g=None):
+    """N (P, nodes per cell) of the scalar layout at barycentric coordinates lam (P, D + 1), in the order of the layout's cell
+    records; with g (P, D + 1, D), the gradients of the barycentric coordinates, also dN (P, nodes, D).  ``point_basis``'s formulas."""
+    D = lam.shape[1] - 1
+    if lay.degree == 1:
+        return (lam, g) if g is not None else lam
+    edges = ((0, 1),) if D == 1 else lay.P2_EDGES[D]
+    N = np.stack([lam[:, i] * (2.0 * lam[:, i] - 1.0) for i in range(D + 1)] + [4.0 * lam[:, a] * lam[:, b] for a, b in edges], axis=1)
+    if g is None:
+        return N
+    dN = np.stack([(4.0 * lam[:, i] - 1.0)[:, None] * g[:, i] for i in range(D + 1)] +
+                  [4.0 * (lam[:, b, None] * g[:, a] + lam[:, a, None] * g[:, b]) for a, b in edges], axis=1)
+    return N, dN
+
+
+class LocatedPoints:
+    """Cells (int32, (P,)) and barycentric coordinates ((P, D + 1)) of a set of points of a mesh; ``handle``: the library's point set
+    on ``backend`` where the device located them (None on the host path).  ``key``: the digest the mesh caches it under."""
+
+    def __init__(self, mesh, points, cells, lam, key, backend=None, handle=None):
+        self.mesh, self.points, self.cells, self.lam, self.key = mesh, points, cells, lam, key
+        self.backend, self.handle = backend, handle
+
+    def grad_lambda(self):
+        """g (P, D + 1, D): the gradients of the barycentric coordinates in the points' cells (rows of Tinv, and minus their sum)."""
+        Tinv, _ = affine_inverse(self.mesh.coordinates(), self.mesh.cells()[self.cells])
+        return np.concatenate([-Tinv.sum(axis=1)[:, None, :], Tinv], axis=1)
+
+    def device_handle(self, be):
+        """The library's point set on ``be``: the one the location made, or one built from the cells and lam (pgd_points_from)."""
+        if self.handle is None or self.backend is not be:
+            self.free()
+            self.backend, self.handle = be, be.points_from(self.mesh.layout(1).handle(), self.cells, self.lam)
+        return self.handle
+
+    def free(self):
+        if self.handle is not None:
+            try:
+                self.backend.points_free(self.handle)
+            except Exception:
+                pass
+        self.backend = self.handle = None
+
+    def __del__(self):
+        self.free()
+
+
+_LOCATED_MESHES = weakref.WeakSet()      # meshes that hold located point sets (clear_caches frees their device handles)
+SENSOR_CACHES = weakref.WeakSet()        # model.PGD objects that hold sampled modes (PGD.sensor_modes): clear_caches empties their dictionaries
+LOCATE_CHUNK_ENTRIES = 1 << 21           # host location: points x cells per chunk (the 96 bytes per cell are per chunk, not per mesh)
+
+
+def _locate_host(mesh, pts):
+    X, cells = mesh.coordinates(), mesh.cells()
+    P, nc = pts.shape[0], cells.shape[0]
+    whole = getattr(mesh, "_affine_inv", None)       # point_basis's cache, where somebody has paid for it already
+    best = np.full(P, -np.inf)
+    where = np.full(P, -1, dtype=np.int64)
+    lam = np.zeros((P, X.shape[1] + 1))
+    step = max(1, LOCATE_CHUNK_ENTRIES // max(P, 1))
+    for c0 in range(0, nc, step):
+        c1 = min(nc, c0 + step)
+        Tinv, P0 = (whole[0][c0:c1], whole[1][c0:c1]) if whole is not None else affine_inverse(X, cells[c0:c1])
+        L = barycentric(Tinv, P0, pts)
+        mins = L.min(axis=2)
+        k = np.argmax(mins, axis=1)                  # the first of equal minima: the lowest cell, as point_basis's argmax
+        m = mins[np.arange(P), k]
+        take = m > best                              # strictly: an earlier chunk keeps an equal minimum
+        best[take], where[take] = m[take], c0 + k[take]
+        lam[take] = L[np.arange(P), k][take]
+    return where, lam, best
+
+
+def locate_points(mesh, points, tol=1e-10, device=None):
+    """The cells and barycentric coordinates of many points of a mesh at once: a ``LocatedPoints``.  The cell of a point is the one
+    with the largest smallest barycentric coordinate, the lowest cell among equal ones (``point_basis``'s choice).
+
+    device=None: on the device where the backend locates points (pgd_points_locate on the P1 layout; the set stays there for
+    ``points_sample``), else on the host; device=False: on the host - ``point_basis``'s own arithmetic over all points and chunks of
+    cells, giving its cells and its lam bit for bit.  A point whose best cell has a barycentric coordinate below -tol (or a NaN
+    coordinate) raises ValueError naming the first such point.  Cached on the mesh per (point bytes, tol, path)."""
+    if getattr(mesh, "part", None) is not None:
+        raise NotImplementedError("locate_points on a row-sharded mesh (every rank holds a slab of the cells)")
+    D = mesh.geometry().dim()
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, D))
+    tol = float(tol)
+    if not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError("locate_points: tol = %r, a finite tolerance >= 0 is needed" % (tol,))
+    be = get_backend()
+    on_device = hasattr(be, "points_locate") if device is None else bool(device)
+    if on_device and not hasattr(be, "points_locate"):
+        raise NotImplementedError("locate_points(device=True): the backend %r locates no points" % (getattr(be, "name", be),))
+    key = (hashlib.blake2b(pts.tobytes(), digest_size=16).hexdigest(), pts.shape[0], tol, on_device)
+    cache = mesh.__dict__.setdefault("_located", {})
+    hit = cache.get(key)
+    if hit is not None:
+        if not on_device or hit.backend is be:
+            return hit
+        cache.pop(key).free()                    # located on a backend that is no longer the current one: again, on this one
+    handle = None
+    if on_device:
+        handle = be.points_locate(mesh.layout(1).handle(), pts, tol)
+        cells, lam = be.points_download(handle)
+        bad = cells < 0
+    else:
+        cells, lam, best = _locate_host(mesh, pts)
+        bad = ~(best >= -tol)
+    if bad.any():
+        if handle is not None:
+            be.points_free(handle)
+        i = int(np.argmax(bad))
+        raise ValueError("point %d (%r) outside the mesh" % (i, pts[i]))
+    out = LocatedPoints(mesh, pts, cells.astype(np.int32), lam, key, be if on_device else None, handle)
+    cache[key] = out
+    _LOCATED_MESHES.add(mesh)
+    return out
 
 
 def gradient_quantity(name, gdim, ncomp):
@@ -4040,6 +4174,13 @@ def clear_caches():
     _SCALAR_MEMO.clear()
     _MV_CACHE.clear()
     _DS_CACHE.clear()
+    for mesh in list(_LOCATED_MESHES):          # located point sets: the cache entries go, and the library's point sets with them
+        for located in mesh.__dict__.pop("_located", {}).values():
+            located.free()
+    _LOCATED_MESHES.clear()
+    for sol in list(SENSOR_CACHES):
+        sol.__dict__.pop("_sensor_modes", None)
+    SENSOR_CACHES.clear()
 
 
 from . import spectral                       # noqa: E402  (the spectral start space of the large SPD solves)

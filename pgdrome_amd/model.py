@@ -104,6 +104,50 @@ class EvalManyResult:
     _fields_owner = None
 
 
+class SensorManyResult:
+    """What ``PGD.evaluate_sensor_response_many`` returns; outputs that were not asked for are None."""
+    values = jacobian = coefficients = None
+    min = max = max_abs = None
+
+
+class SensorModes:
+    """All modes of a fixed dimension sampled at a point set (``PGD.sensor_modes``): per mode ``m`` entries in the order
+    (point, component[, axis]) of ``shape`` - K library vectors on the backend ``be`` (``handles``), or a (K, m) array on the host."""
+
+    def __init__(self, shape, m, be=None, handles=None, host=None):
+        self.shape, self.m, self.be, self.handles, self._host = shape, m, be, handles, host
+
+    def host(self):
+        """The (K, m) array of the sampled modes (downloads K small vectors the first time on the device path)."""
+        if self._host is None:
+            self._host = np.stack([self.be.vec_to_host(h) for h in self.handles])
+        return self._host
+
+    def contract(self, C, K):
+        """(S, m): the first K sampled modes combined with the coefficients C (K, S) - numpy below DEVICE_EVAL_MIN_DOFS entries,
+        ``eval_batch`` on the sampled vectors above (device path)."""
+        C = np.ascontiguousarray(C, dtype=np.float64)
+        S = C.shape[1]
+        if self.handles is not None and self.m >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(self.be, "eval_batch"):
+            out = self.be.vec_zeros(self.m * S)
+            try:
+                self.be.eval_batch(self.handles[:K], C, stats=False, fields=out)
+                U = self.be.vec_to_host(out)
+            finally:
+                self.be.vec_free(out)
+            fem.STATS["sensor_eval_batch_calls"] = fem.STATS.get("sensor_eval_batch_calls", 0) + 1
+            return U.reshape(S, self.m)
+        return C.T @ self.host()[:K]
+
+    def __del__(self):
+        if self.handles is not None:
+            for h in self.handles:
+                try:
+                    self.be.vec_free(h)
+                except Exception:
+                    pass
+
+
 class _FieldStore:
     """The one library vector (n * S doubles, sample-major) behind the ``fields`` of a device ``evaluate_many``; freed with
     the last reference (the result and every field view hold one)."""
@@ -1195,6 +1239,168 @@ class PGD:
     def evaluate_derivative_sensor_response(self, fixed_dim, free_dim, coord, attri, d_dim, sensor_points):
         c = self._derivative_factors(free_dim, coord, attri, d_dim, fixed_dim)
         return self._contract_modes(self.eval_fixed_modes(sensor_points, fixed_dim, attri), c)
+
+    # ------------------------------------------------------ sensor responses for many samples
+    def sensor_modes(self, sensor_points, fixed_dim, attri, gradient=False, device=None):
+        """ALL ``numModes`` modes of the fixed dimension (``gradient``: their spatial gradients) at the sensor points: a
+        ``SensorModes`` of entries (point, component[, axis]) per mode.  The points are located once (``fem.locate_points``).  Where
+        the backend samples point sets (``device=None``: then) every mode is sampled on the device into a vector of P * nc (* gdim)
+        entries (pgd_points_sample) and no mode is downloaded; otherwise - the numpy backend, ``device=False`` - one gather and one
+        contraction over all modes on the host.  The gradient at a point on a face is that of the cell the location chose.
+        Cached per (point set, fixed_dim, attri, gradient, path)."""
+        modes = self.mesh[fixed_dim].attributes[attri].interpolationfct
+        if len(modes) < self.numModes or not all(isinstance(m, fem.Function) for m in modes[:self.numModes]):
+            raise ValueError("sensor_modes: the modes of dimension %d are no Functions (interp1d modes have no mesh to locate points on)"
+                             % (fixed_dim,))
+        V = modes[0].function_space()
+        fem._refuse_dg0(modes[0], "sensor values")
+        mesh, nc = V.mesh(), V._ncomp
+        base = V._lay.base if nc > 1 else V._lay
+        if mesh.part is not None or getattr(base, "part", None) is not None:
+            raise NotImplementedError("sensor_modes on a row-sharded fixed dimension (every rank holds a slab of the modes)")
+        be = fem.get_backend()
+        on_device = hasattr(be, "points_sample") if device is None else bool(device)
+        if on_device and not hasattr(be, "points_sample"):
+            raise NotImplementedError("sensor_modes(device=True): the backend %r samples no point sets" % (getattr(be, "name", be),))
+        located = fem.locate_points(mesh, sensor_points, device=True if on_device else False)
+        key = (located.key, fixed_dim, attri, bool(gradient), on_device)
+        cache = self.__dict__.setdefault("_sensor_modes", {})
+        fem.SENSOR_CACHES.add(self)              # fem.clear_caches empties the dictionary (the sampled vectors are freed with it)
+        # an entry is the samples of THESE mode vectors in their current versions on THIS backend: anything else is sampled again
+        vectors = [m.vector() for m in modes[:self.numModes]]
+        stamp = [v.version for v in vectors]
+        hit = cache.get(key)
+        if hit is not None:
+            res, be_then, vectors_then, stamp_then = hit
+            if be_then is (be if on_device else None) and len(vectors_then) == len(vectors) and stamp_then == stamp and \
+                    all(a is b for a, b in zip(vectors_then, vectors)):
+                return res
+            del cache[key]
+        P, D, K = located.cells.shape[0], mesh.geometry().dim(), self.numModes
+        if P == 0:
+            raise ValueError("sensor_modes: no sensor points")
+        shape = (P,) + ((nc,) if nc > 1 else ()) + ((D,) if gradient else ())
+        m = P * nc * (D if gradient else 1)
+        if on_device:
+            pts = located.device_handle(be)
+            handles = []
+            for k in range(K):
+                handles.append(be.vec_zeros(m))
+                be.points_sample(pts, V._lay.handle(), modes[k].vector().dev(), handles[-1], gradient=bool(gradient))
+            res = SensorModes(shape, m, be=be, handles=handles)
+        else:
+            nodes = base.cells[located.cells]                                   # (P, nodes per cell)
+            G = np.stack([modes[k].vector().host() for k in range(K)])          # (K, dofs)
+            Gn = G[:, (nodes[:, :, None] * nc + np.arange(nc)[None, None, :])]  # (K, P, nodes, nc)
+            if gradient:
+                _, dN = fem.shape_functions(base, located.lam, located.grad_lambda())
+                E = np.einsum("pad,kpac->kpcd", dN, Gn)
+            else:
+                E = np.einsum("pa,kpac->kpc", fem.shape_functions(base, located.lam), Gn)
+            res = SensorModes(shape, m, host=np.ascontiguousarray(E.reshape(K, m)))
+        cache[key] = (res, be if on_device else None, vectors, stamp)
+        return res
+
+    def mode_factor_derivatives_many(self, free_dim, coords, attri, d_dim):
+        """C_d[k, s]: ``mode_factors_many`` with the factor of dimension ``d_dim`` replaced by its derivative with respect to that
+        coordinate - the coefficients of d u / d coordinate(d_dim), shape (used_numModes, S).  Vectorised for 1-D scalar P1 / P2
+        Function modes; at a mesh node the derivative is the one-sided one of the cell ``fem.point_basis`` picks there (the cell
+        with the largest smallest barycentric coordinate, the lowest cell among equal ones), as ``fem.DerivativeFunction`` gives."""
+        coords = self._check_many(None, free_dim, coords, attri)
+        if d_dim not in list(free_dim):
+            raise ValueError("derivation against fixed dim not possible in the moment")
+        if self.mesh[free_dim[0]].attributes[attri].interpolationInfo["name"] == 0:
+            raise ValueError("derivation for interp1 functions not implemented (only fencis functions)")
+        C = np.ones((self.used_numModes, coords.shape[0]))
+        for i, d in enumerate(free_dim):
+            x = coords[:, i] if coords.ndim == 2 else coords[:, i, ...]
+            C *= self._free_mode_derivatives_at(d, x, attri) if d == d_dim else self._free_modes_at(d, x, attri)
+        return C
+
+    def _free_mode_derivatives_at(self, d, x, attri):
+        """d F^k / d x of all used modes of the free dimension d at the coordinates x: shape (used_numModes, S)."""
+        att = self.mesh[d].attributes[attri]
+        if att.interpolationInfo.get("name") == 0:
+            raise ValueError("derivation for interp1 functions not implemented (only fencis functions)")
+        fcts = att.interpolationfct[:self.used_numModes]
+        f0 = fcts[0]
+        V = f0.function_space() if isinstance(f0, fem.Function) else None
+        if V is not None and V._ncomp > 1:
+            raise NotImplementedError("derivative of vector-valued modes (tensor DG space)")
+        x = np.asarray(x, dtype=np.float64)
+        if (V is not None and not V._dg0 and V.mesh().topology().dim() == 1 and x.ndim == 1 and V._lay.degree in (1, 2)
+                and all(isinstance(f, fem.Function) and f.function_space() is V for f in fcts)):
+            lay, mesh = V._lay, V.mesh()
+            X, cells = mesh.coordinates()[:, 0], mesh.cells()
+            a, b = X[cells[:, 0]], X[cells[:, 1]]
+            lo = np.minimum(a, b)
+            order = np.argsort(lo, kind="stable")
+            slo = lo[order]
+            # the two cells that can hold x: the last one starting at or below it and the one before (x on their common node);
+            # point_basis's arithmetic decides between them - the larger smallest barycentric coordinate, then the lower cell
+            pos = np.clip(np.searchsorted(slo, x, side="right") - 1, 0, len(order) - 1)
+            cand = np.stack([order[pos], order[np.maximum(pos - 1, 0)]], axis=1)                     # (S, 2)
+            tinv = 1.0 / (b - a)
+            l1 = tinv[cand] * (x[:, None] - a[cand])
+            l0 = 1.0 - l1
+            mins = np.minimum(l0, l1)
+            first = (mins[:, 0] > mins[:, 1]) | ((mins[:, 0] == mins[:, 1]) & (cand[:, 0] <= cand[:, 1]))
+            pick = np.where(first, 0, 1)
+            rows = np.arange(x.shape[0])
+            c = cand[rows, pick]
+            bad = ~(mins[rows, pick] >= -1e-10)
+            if bad.any():
+                raise ValueError("point %r outside the mesh of dimension %d" % (float(x[np.argmax(bad)]), d))
+            lam = np.stack([l0[rows, pick], l1[rows, pick]], axis=1)
+            g = np.stack([-tinv[c], tinv[c]], axis=1)[:, :, None]                                     # (S, 2, 1)
+            _, dN = fem.shape_functions(lay, lam, g)
+            G = np.stack([f.vector().host() for f in fcts])
+            # dN^T u per point and mode as a stack of (1 x nodes) @ (nodes x 1) products: the operation, term order included, of
+            # fem.point_gradient behind DerivativeFunction - the terms are of size |u| / h and cancel, so another order of the sum
+            # would differ from the per-sample method by rounding errors of the terms, not of the derivative
+            return np.matmul(dN[None, :, :, 0][:, :, None, :], G[:, lay.cells[c]][:, :, :, None])[:, :, 0, 0]
+        # anything else: the derivative callables, point by point
+        out = np.empty((len(fcts), x.shape[0]))
+        for j in range(x.shape[0]):
+            for k, f in enumerate(fcts):
+                try:
+                    out[k, j] = float(fem.DerivativeFunction(f, 0)(x[j]))
+                except RuntimeError as e:
+                    raise ValueError(str(e)) from e
+        return out
+
+    def evaluate_sensor_response_many(self, fixed_dim, free_dim, coords, attri, sensor_points, d_dim=None, gradient=False,
+                                      stats=False, device=None):
+        """``evaluate_sensor_response`` for S coordinate sets of the free dimensions at once, with the parameter Jacobian: the
+        modes are sampled at the points once (``sensor_modes``), the samples are one product with ``mode_factors_many``.
+
+        Returns a ``SensorManyResult``: ``values`` of shape (S, P) for a scalar field, (S, P, nc) for a vector field, with a
+        trailing gdim axis when ``gradient`` (the spatial gradient at the points); ``jacobian``: when ``d_dim`` (a free dimension
+        or a list of them) is given, the derivatives of ``values`` with respect to those coordinates on a trailing len(d_dim)
+        axis; ``coefficients`` = C (used_numModes, S); with ``stats`` ``min`` / ``max`` / ``max_abs`` of ``values`` per sample.
+        The product is numpy below DEVICE_EVAL_MIN_DOFS entries per sample, ``pgd_eval_batch`` on the sampled vectors above."""
+        coords = self._check_many(fixed_dim, free_dim, coords, attri)
+        S, K = coords.shape[0], self.used_numModes
+        if self.mesh[free_dim[0]].attributes[attri].interpolationInfo["name"] == 0:
+            raise ValueError("evaluate_sensor_response_many: interp1d modes have no mesh to locate points on")
+        dims = None if d_dim is None else ([int(d_dim)] if np.isscalar(d_dim) else [int(d) for d in d_dim])
+        if dims is not None:
+            for d in dims:
+                if d == fixed_dim or d not in list(free_dim):
+                    raise ValueError("derivation against fixed dim not possible in the moment")
+        sm = self.sensor_modes(sensor_points, fixed_dim, attri, gradient=gradient, device=device)
+        C = self.mode_factors_many(free_dim, coords, attri)
+        res = SensorManyResult()
+        res.coefficients = C
+        res.values = sm.contract(C, K).reshape((S,) + sm.shape)
+        if dims is not None:
+            res.jacobian = np.stack([sm.contract(self.mode_factor_derivatives_many(free_dim, coords, attri, d), K).reshape((S,) + sm.shape)
+                                     for d in dims], axis=-1)
+        if stats:
+            flat = res.values.reshape(S, -1)
+            if flat.shape[1]:
+                res.min, res.max, res.max_abs = flat.min(axis=1), flat.max(axis=1), np.abs(flat).max(axis=1)
+        return res
 
 
 class PGDErrorComputation(object):

@@ -122,6 +122,10 @@ int pgd_vec_download(pgd_handle ctx, pgd_handle vec, double *host, int64_t offse
 int pgd_vec_ptr(pgd_handle ctx, pgd_handle vec, void **device_ptr);
 int pgd_vec_fill(pgd_handle ctx, pgd_handle vec, double value);
 int pgd_vec_copy(pgd_handle ctx, pgd_handle dst, pgd_handle src);
+/* dst[dst_off .. dst_off + count) = src[src_off .. src_off + count), on the stream (no synchronisation): cuts the sample-major
+ * fields vector of pgd_eval_batch into vectors that own their storage.  PGD_ERR_INVALID for a range outside either vector or
+ * overlapping ranges of one vector. */
+int pgd_vec_copy_range(pgd_handle ctx, pgd_handle dst, int64_t dst_off, pgd_handle src, int64_t src_off, int64_t count);
 int pgd_vec_scale(pgd_handle ctx, pgd_handle vec, double a);                 /* v *= a      */
 int pgd_vec_mul(pgd_handle ctx, pgd_handle y, pgd_handle a, pgd_handle x);   /* y = a .* x entry by entry (y may be x or a): the Jacobi
                                                                                * scaling of the sharded BiCGStab, pgdrome_amd/dist.py */
@@ -450,6 +454,20 @@ int pgd_vec_multidot(pgd_handle ctx, pgd_handle x, const pgd_handle *ys, int k, 
 int pgd_vec_multidot_pair(pgd_handle ctx, pgd_handle x0, pgd_handle x1, const pgd_handle *ys, int k, int64_t lo,
                           int64_t hi, double *out);
 
+/* Gram block of two families of vectors: out[i * ky + j] = sum_{lo <= r < hi} x_i[r] y_j[r] (hi < 0: the whole vector), every
+ * vector read ONCE (v_mfma_f64_16x16x4_f64 on row blocks staged in LDS; PGD_TUNE_GRAM_VARIANT = 0: plain fma chains) and ONE
+ * host synchronisation.  ys == NULL (then ky must equal kx) is the symmetric case X^T X: only the tiles on and above the
+ * diagonal are computed and mirrored, out is symmetric bit for bit.  1 <= kx, ky <= 128 per call (the binding blocks larger
+ * families).  No atomics: the rows are cut into at most 1024 segments that depend on (lo, hi) alone, their partials are added
+ * in ascending order - every output is bit-identical for any grid (PGD_TUNE_GRAM_GRID_MAX).  It replaces the kx calls of
+ * pgd_vec_multidot behind a Gram matrix ((ceil(k / 17) + k) k vector reads where k are needed), spectral.py's _gram over
+ * separate vectors, and it is the l2 statistic of a batch of fields that pgd_eval_batch leaves outside: |u_s|^2 = c_s^T G c_s
+ * with the modes' Gram G.  PGD_ERR_INVALID with a message, before anything is launched: null xs or out, kx or ky out of range,
+ * ky != kx without ys, an invalid handle, vectors of different lengths, a range outside the vectors.  An empty range gives
+ * zeros and PGD_OK.                                                                                                        */
+int pgd_vec_gram(pgd_handle ctx, const pgd_handle *xs, int kx, const pgd_handle *ys_or_null, int ky, int64_t lo, int64_t hi,
+                 double *out);
+
 /* ------------------------------------------------------------ column blocks --- */
 /* k <= 64 columns of n rows in ONE library-owned allocation, stored as fp32 or f64: the start space of the spatial solves
  * (pgdrome_amd/spectral.py; this library's addition in front of the solve that replaces solver.py:636,716), whose cost per
@@ -659,6 +677,10 @@ int pgd_points_free(pgd_handle ctx, pgd_handle points);
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_GRAM_GRID_MAX = 63, /* pgd_vec_gram: > 0: at most this many (persistent) workgroups; 0 (default): as many as are resident at once.
+                                The same bits either way: the segments and the order of their partials do not depend on the grid. */
+    PGD_TUNE_GRAM_VARIANT = 62, /* pgd_vec_gram: 1 (default) the product on the f64 matrix unit (k_gram_mfma), 0 one fma chain per entry
+                                (k_gram_plain): the cross-check and the baseline. */
     PGD_TUNE_LOCATE_GRID_MAX = 61, /* pgd_points_locate, general kernel: > 0: at most this many (persistent) workgroups; 0 (default): as many as
                                 are resident at once.  Same cells and lam either way (tests reach the loop over the cells and the final
                                 pass over several rows with it). */

@@ -53,6 +53,7 @@ SIGNATURES = {
     "pgd_vec_ptr": (C.c_int, [H, H, C.POINTER(VP)]),
     "pgd_vec_fill": (C.c_int, [H, H, F64]),
     "pgd_vec_copy": (C.c_int, [H, H, H]),
+    "pgd_vec_copy_range": (C.c_int, [H, H, I64, H, I64, I64]),
     "pgd_vec_scale": (C.c_int, [H, H, F64]),
     "pgd_vec_mul": (C.c_int, [H, H, H, H]),
     "pgd_vec_axpy": (C.c_int, [H, H, F64, H]),
@@ -103,6 +104,7 @@ SIGNATURES = {
     "pgd_product_plan": (C.c_int, [H, H, I64, I64, C.c_int, PI64, C.c_int]),
     "pgd_vec_multidot": (C.c_int, [H, H, PH, C.c_int, I64, I64, PD]),
     "pgd_vec_multidot_pair": (C.c_int, [H, H, H, PH, C.c_int, I64, I64, PD]),
+    "pgd_vec_gram": (C.c_int, [H, PH, C.c_int, PH, C.c_int, I64, I64, PD]),
     "pgd_pcg_solve": (C.c_int, [H, H, H, H, F64, F64, C.c_int, C.POINTER(C.c_int), PD]),
     "pgd_pcg_last_form": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pgd_band_solve": (C.c_int, [H, H, H, H]),
@@ -183,6 +185,8 @@ TUNE_PCG_FOLD_MARCH, TUNE_PCG_SCALAR_S, TUNE_PCG_FUSED_MARCH = 55, 56, 57
 TUNE_SPMV_BLOCK_DIA = 58
 TUNE_SPMV_P2_LATTICE = 59
 TUNE_LOCATE_LATTICE, TUNE_LOCATE_GRID_MAX = 60, 61
+TUNE_GRAM_VARIANT, TUNE_GRAM_GRID_MAX = 62, 63
+GRAM_KMAX = 128            # vectors per side and call of pgd_vec_gram
 LOCATE_TILE = 32                                    # points per launch of the general location kernel (LOC_PT, csrc/pgd_locate.hip)
 LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE = 1, 2     # pgd_points_last_path
 BLOCK_F32, BLOCK_F64, BLOCK_MAXK = 0, 1, 64                                           # PGD_BLOCK_* (include/pgd_amd.h)
@@ -386,6 +390,10 @@ class Context:
 
     def vec_copy(self, dst, src):
         self._ck(self.lib.pgd_vec_copy(self.h, dst, src))
+
+    def vec_copy_range(self, dst, dst_off, src, src_off, count):
+        """dst[dst_off : dst_off + count] = src[src_off : src_off + count] on the stream."""
+        self._ck(self.lib.pgd_vec_copy_range(self.h, dst, int(dst_off), src, int(src_off), int(count)))
 
     def vec_scale(self, v, a):
         self._ck(self.lib.pgd_vec_scale(self.h, v, float(a)))
@@ -622,6 +630,33 @@ class Context:
         out = np.zeros(2 * k, dtype=np.float64)
         self._ck(self.lib.pgd_vec_multidot_pair(self.h, x0, x1, arr, k, int(lo), int(hi), dptr(out)))
         return out[:k], out[k:]
+
+    def vec_gram(self, xs, ys=None, lo=0, hi=-1):
+        """pgd_vec_gram: the (kx, ky) array of x_i . y_j over [lo, hi), every vector read once per call.  ``ys`` None: the
+        symmetric block of ``xs`` with itself, symmetric bit for bit.  Families above 128 vectors go in blocks of at most 128 per
+        side; a symmetric request computes the blocks on and above the diagonal and mirrors the others."""
+        xs = [int(v) for v in xs]
+        sym = ys is None
+        ys = xs if sym else [int(v) for v in ys]
+        kx, ky = len(xs), len(ys)
+        out = np.zeros((kx, ky), dtype=np.float64)
+        for i0 in range(0, kx, GRAM_KMAX):
+            xb = xs[i0:i0 + GRAM_KMAX]
+            xa = (H * len(xb))(*xb)
+            for j0 in range(0, ky, GRAM_KMAX):
+                if sym and j0 < i0:
+                    continue
+                yb = ys[j0:j0 + GRAM_KMAX]
+                blk = np.zeros((len(xb), len(yb)), dtype=np.float64)
+                if sym and j0 == i0:
+                    self._ck(self.lib.pgd_vec_gram(self.h, xa, len(xb), None, len(xb), int(lo), int(hi), dptr(blk)))
+                else:
+                    ya = (H * len(yb))(*yb)
+                    self._ck(self.lib.pgd_vec_gram(self.h, xa, len(xb), ya, len(yb), int(lo), int(hi), dptr(blk)))
+                out[i0:i0 + len(xb), j0:j0 + len(yb)] = blk
+                if sym and j0 > i0:
+                    out[j0:j0 + len(yb), i0:i0 + len(xb)] = blk.T
+        return out
 
     # ---- atoms / operators
     def atom_product_form(self, atom):

@@ -408,6 +408,8 @@ struct Ctx {
     // pgd_points_locate (pgd_locate.hip): the one-thread-per-point path on regularly numbered box lattices (PGD_TUNE_LOCATE_LATTICE), the
     // grid cap of the general kernel (PGD_TUNE_LOCATE_GRID_MAX; 0: what is resident at once) and what the last call ran (pgd_points_last_path)
     int locate_lattice = 1, locate_grid_max = 0, locate_last_path = 0;
+    // pgd_vec_gram (pgd_gram.hip): kernel variant (1 MFMA, 0 plain fma chains; PGD_TUNE_GRAM_VARIANT) and grid cap (PGD_TUNE_GRAM_GRID_MAX; 0: what is resident at once)
+    int gram_variant = 1, gram_grid_max = 0;
 
     // SpMV launch timing (HIP events on `stream`)
     bool prof = false;

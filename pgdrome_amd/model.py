@@ -33,6 +33,7 @@ after the hot path:
 from __future__ import annotations
 
 import logging
+import math
 import os
 import xml.etree.ElementTree as et
 
@@ -389,6 +390,109 @@ def _host_function(V, a):
     f.vector()._host = np.array(a, dtype=np.float64)
     f.vector().touched_host()
     return f
+
+
+# ------------------------------------------------------------------ mode compression on Gram matrices
+COMPRESS_TOL_FLOOR = 1e-7        # the Gram route carries half the digits: sqrt(2^-53) |u| = 1.05e-8 |u| is its resolution
+_GRAM_EIG_DROP = 1e-14           # eigenvalues of a Gram matrix at most this fraction of the largest are rounding
+
+
+def _gram_coordinates(G):
+    """(L, P) of a Gram matrix G = F^T F: row k of L (K x r) holds the coordinates of mode k in an orthonormal basis of span F,
+    and F P (P = Q Lambda^-1/2, K x r) IS that basis, so coordinates B (r x R) map back to the modes F (P B)."""
+    lam, Q = np.linalg.eigh(0.5 * (G + G.T))
+    keep = lam > _GRAM_EIG_DROP * lam[-1] if lam[-1] > 0.0 else np.zeros(len(lam), dtype=bool)
+    lam, Q = lam[keep][::-1], Q[:, keep][:, ::-1]
+    root = np.sqrt(lam)
+    return Q * root, Q / root
+
+
+def _hadamard_sum(blocks):
+    """1^T (o_d blocks[d]) 1: the inner product of two separated functions from the Gram blocks of their dimensions."""
+    H = np.ones_like(blocks[0])
+    for b in blocks:
+        H = H * b
+    return float(H.sum())
+
+
+def _cp_rel_error(Ls, Bs, t2):
+    """|T - That| / |T| in the orthonormal coordinates: T = sum_k (x)_d Ls[d][k], That = sum_i (x)_d Bs[d][:, i], t2 = |T|^2.
+    The three sums are taken over small matrices of O(1) entries (no 1 / h^d weights of the big norms in them)."""
+    cross = _hadamard_sum([L @ B for L, B in zip(Ls, Bs)])
+    own = _hadamard_sum([B.T @ B for B in Bs])
+    return math.sqrt(max(t2 - 2.0 * cross + own, 0.0) / t2)
+
+
+def _cp_als(Ls, tol, cap, max_sweeps):
+    """CP-ALS on T = sum_k (x)_d Ls[d][k] (D >= 3), deterministic: R grows from 1, the factors that have converged are kept and
+    the largest remaining input term joins them; every normal equation is a Hadamard product of cross-Grams.  Returns
+    (Bs, rel_error, sweeps) of the first R that meets tol, or of the best R <= cap."""
+    D, K = len(Ls), Ls[0].shape[0]
+    t2 = _hadamard_sum([L @ L.T for L in Ls])
+    order = np.argsort(-np.prod([np.linalg.norm(L, axis=1) for L in Ls], axis=0), kind="stable")
+    Bs, best, sweeps = None, None, 0
+    for R in range(1, cap + 1):
+        new = [L[order[R - 1]].reshape(-1, 1) for L in Ls]
+        Bs = new if Bs is None else [np.hstack([B, b]) for B, b in zip(Bs, new)]
+        err = _cp_rel_error(Ls, Bs, t2)
+        for _ in range(max_sweeps):
+            if err <= tol:
+                break
+            for d in range(D):
+                H, M = np.ones((R, R)), np.ones((K, R))
+                for e in range(D):
+                    if e != d:
+                        H, M = H * (Bs[e].T @ Bs[e]), M * (Ls[e] @ Bs[e])
+                Bs[d] = np.linalg.lstsq(H, (Ls[d].T @ M).T, rcond=None)[0].T
+            sweeps += 1
+            last, err = err, _cp_rel_error(Ls, Bs, t2)
+            if last - err <= 1e-6 * err:          # stagnation at this R: one more term
+                break
+        if best is None or err < best[1]:
+            best = ([B.copy() for B in Bs], err)
+        if err <= tol:
+            break
+    return best[0], best[1], sweeps
+
+
+def compress_grams(Gs, tol, max_modes=None, max_sweeps=200):
+    """The host half of ``PGD.compress``: from the Gram matrices G_d (K x K) of the modes of every dimension to the matrices
+    W_d (K x R) whose products F_d W_d are the new modes.  dict: R, W (None: nothing shorter meets tol - keep the model),
+    rel_error, converged, ranks, sweeps."""
+    D, K = len(Gs), Gs[0].shape[0]
+    LP = [_gram_coordinates(G) for G in Gs]
+    Ls, Ps = [lp[0] for lp in LP], [lp[1] for lp in LP]
+    ranks = [int(L.shape[1]) for L in Ls]
+    out = {"R": K, "W": None, "rel_error": 0.0, "converged": True, "ranks": ranks, "sweeps": 0}
+    if min(ranks) == 0:                       # the zero function: one zero term says it all
+        return out if K == 1 else dict(out, R=1, W=[np.zeros((K, 1)) for _ in Gs])
+    cap = K - 1 if max_modes is None else min(K, int(max_modes))
+    if cap < 1:
+        return out
+    if D == 1:
+        Bs, err, sweeps = [Ls[0].sum(axis=0).reshape(-1, 1)], 0.0, 0
+    elif D == 2:
+        U, sv, Vt = np.linalg.svd(Ls[0].T @ Ls[1], full_matrices=False)      # Eckart-Young: the tail is the best error of its rank
+        tails = np.sqrt(np.concatenate([np.cumsum((sv ** 2)[::-1])[::-1], [0.0]])) / np.linalg.norm(sv)
+        R = max(1, min(int(np.argmax(tails <= tol)), cap))
+        Bs, err, sweeps = [U[:, :R] * sv[:R], Vt[:R].T.copy()], float(tails[R]), 0
+    else:
+        Bs, err, sweeps = _cp_als(Ls, tol, cap, max_sweeps)
+    if max_modes is None and err > tol:
+        return out
+    # balance: every dimension carries lambda^(1 / D) of a term's weight lambda = prod_d |b_d|; terms by descending weight
+    norms = np.array([np.linalg.norm(B, axis=0) for B in Bs])                # (D, R)
+    weight = np.prod(norms, axis=0)
+    live = weight > 0.0
+    if not live.any():
+        live[0] = True
+    order = np.argsort(-weight[live], kind="stable")
+    Ws = []
+    for d in range(D):
+        B, nd, w = Bs[d][:, live][:, order], norms[d][live][order], weight[live][order]
+        Ws.append(Ps[d] @ (B * np.where(nd > 0.0, w ** (1.0 / D) / np.where(nd > 0.0, nd, 1.0), 0.0)))
+    return {"R": int(Ws[0].shape[1]), "W": Ws, "rel_error": float(err), "converged": bool(err <= tol), "ranks": ranks,
+            "sweeps": int(sweeps)}
 
 
 class PGD:
@@ -909,6 +1013,204 @@ class PGD:
             res = _eval_many_host(lambda j0, step: F @ C[:, j0:j0 + step], n, S, sample_chunk, stats, envelope, thr, fields, wrap)
         res.coefficients = C
         return res
+
+    # ----------------------------------------------- Gram matrices of the modes: norms, distances, compression
+    def _gram_family(self, dim, attri):
+        """(modes, V) of a dimension for the Gram calls: Functions on one space, not row-sharded."""
+        if dim < 0 or dim >= self.num_pgd_var or attri < 0 or attri >= len(self.mesh[dim].attributes):
+            raise ValueError("dimension or attribute number not possible")
+        att = self.mesh[dim].attributes[attri]
+        if att.interpolationInfo.get("name") == 0:
+            raise NotImplementedError("Gram matrices of interp1d modes (the modes must be Functions: interpolation name 1)")
+        if len(att.interpolationfct) == 0:
+            self.create_interpolation_fcts([dim], attri)
+        modes = list(att.interpolationfct[:self.used_numModes])
+        if not modes or not all(isinstance(m, fem.Function) for m in modes):
+            raise NotImplementedError("Gram matrices need the modes as Functions")
+        V = modes[0].function_space()
+        lay = V._lay.base if V._ncomp > 1 else V._lay
+        if V.mesh().part is not None or getattr(lay, "part", None) is not None:
+            raise NotImplementedError("Gram matrices on a row-sharded dimension (every rank holds a slab of the modes; the "
+                                      "blocks would need a reduction across ranks)")
+        if not all(m.function_space() is V for m in modes):
+            raise ValueError("the modes of dimension %d live on different spaces" % dim)
+        return modes, V
+
+    @staticmethod
+    def _same_space(V, W):
+        if V is W:
+            return True
+        if V.dim() != W.dim() or V._ncomp != W._ncomp or V._lay.degree != W._lay.degree or V._dg0 != W._dg0:
+            return False
+        a, b = V.mesh(), W.mesh()
+        return a is b or (np.array_equal(a.coordinates(), b.coordinates()) and np.array_equal(a.cells(), b.cells()))
+
+    @staticmethod
+    def _gram_block(V, xs, ys=None):
+        """X^T Y of two lists of Functions on V (ys None: X^T X, symmetric bit for bit): ``pgd_vec_gram`` when the backend has
+        it and the space has at least DEVICE_EVAL_MIN_DOFS dofs - the rule of ``evaluate_many`` - otherwise numpy."""
+        be = fem.get_backend()
+        if V.dim() >= DEVICE_EVAL_MIN_DOFS and hasattr(be, "vec_gram"):
+            G = be.vec_gram([f.vector().dev() for f in xs], None if ys is None else [f.vector().dev() for f in ys])
+            fem.STATS["gram_calls"] = fem.STATS.get("gram_calls", 0) + 1
+            return G
+        X = np.stack([f.vector().host() for f in xs], axis=1)
+        if ys is None:
+            G = X.T @ X
+            return 0.5 * (G + G.T)
+        return X.T @ np.stack([f.vector().host() for f in ys], axis=1)
+
+    def _mass_products(self, dim, attri, modes, V):
+        """[M f for f in modes] with M the mass atom of V (u v dx; dot(u, v) dx on vector spaces), assembled once per attribute."""
+        att = self.mesh[dim].attributes[attri]
+        be = fem.get_backend()
+        hit = getattr(att, "_gram_mass", None)
+        if hit is None or hit[0] is not be or hit[1] is not V:
+            u, v = fem.TrialFunction(V), fem.TestFunction(V)
+            hit = (be, V, fem.assemble((fem.dot(u, v) if V._ncomp > 1 else u * v) * fem.dx).op())
+            att._gram_mass = hit
+        lo, hi = V._lay.owned_range()
+        out = []
+        for f in modes:
+            w = fem.Function(V)
+            be.spmv(hit[2], f.vector().dev(), w.vector().dev_for_write(), lo, hi)
+            w.vector().touched_dev()
+            out.append(w)
+        return out
+
+    def mode_gram(self, dim, attri=0, metric="l2", other=None):
+        """The Gram matrix G (K x K) of the used modes of dimension ``dim``; with another ``PGD`` on the same space the cross
+        block (K x K').  ``metric`` "l2": the Euclidean product of the dof vectors; "mass": F^T M F' with the mass matrix of the
+        dimension's space (the L2 product of the functions), symmetrised as (G + G^T) / 2 without ``other``.  One pass over the
+        modes on the device (``pgd_vec_gram``) under the rule of ``evaluate_many``, numpy otherwise."""
+        if metric not in ("l2", "mass"):
+            raise ValueError("mode_gram: metric must be 'l2' or 'mass', got %r" % (metric,))
+        if other is not None and not isinstance(other, PGD):
+            raise ValueError("mode_gram: other must be a PGD")
+        xs, V = self._gram_family(dim, attri)
+        ys = None
+        if other is not None and other is not self:
+            if dim >= other.num_pgd_var:
+                raise ValueError("mode_gram: the other model has no dimension %d" % dim)
+            ys, W = other._gram_family(dim, attri)
+            if not self._same_space(V, W):
+                raise ValueError("mode_gram: the two models live on different spaces in dimension %d" % dim)
+        if metric == "l2":
+            return self._gram_block(V, xs, ys)
+        if ys is None:
+            G = self._gram_block(V, xs, self._mass_products(dim, attri, xs, V))
+            return 0.5 * (G + G.T)
+        return self._gram_block(V, xs, other._mass_products(dim, attri, ys, ys[0].function_space()))
+
+    def _inner(self, other, attri, metric):
+        return _hadamard_sum([self.mode_gram(d, attri, metric, other) for d in range(self.num_pgd_var)])
+
+    def separated_norm(self, attri=0, metric="l2"):
+        """|u| = sqrt(1^T (o_d G_d) 1) of the separated function over all dimensions, from the Gram matrices of its modes."""
+        return math.sqrt(max(self._inner(None, attri, metric), 0.0))
+
+    def distance(self, other, attri=0, metric="l2", relative=True):
+        """|u - v| of two separated solutions on the same spaces from the three Hadamard products (u, u), (u, v), (v, v) of
+        their Gram blocks - no field is reconstructed - divided by |u| when ``relative``.
+
+        The difference of squares cancels: the result is NOT RESOLVED below about 1e-8 |u| (sqrt(2^-53) of the norms that
+        cancel).  Values below that floor are returned as they come, clipped at 0 before the root."""
+        if not isinstance(other, PGD) or other.num_pgd_var != self.num_pgd_var:
+            raise ValueError("distance: another PGD with the same number of dimensions is needed")
+        uu = self._inner(None, attri, metric)
+        if other is self:
+            uv = vv = uu
+        else:
+            uv, vv = self._inner(other, attri, metric), other._inner(None, attri, metric)
+        d = math.sqrt(max(uu - 2.0 * uv + vv, 0.0))
+        return d / math.sqrt(uu) if relative and uu > 0.0 else d
+
+    def evaluate_norm_many(self, fixed_dim, free_dim, coords, attri, metric="l2"):
+        """(S,) norms sqrt(c_s^T G c_s) of the fixed-dimension field at S coordinate sets of the other dimensions, with
+        C = ``mode_factors_many`` and ONE Gram matrix of the fixed dimension's modes: no field is formed."""
+        if metric not in ("l2", "mass"):
+            raise ValueError("evaluate_norm_many: metric must be 'l2' or 'mass', got %r" % (metric,))
+        coords = self._check_many(fixed_dim, free_dim, coords, attri)
+        G = self.mode_gram(fixed_dim, attri, metric)
+        Cm = self.mode_factors_many(free_dim, coords, attri)
+        return np.sqrt(np.maximum(np.einsum("ks,kl,ls->s", Cm, G, Cm), 0.0))
+
+    @staticmethod
+    def _combine_modes(V, modes, W):
+        """The R Functions F W (W: K x R) that own their vectors: one ``pgd_eval_batch`` with the fields output and R ranged
+        copies on the device under the rule of ``evaluate_many``, a numpy product otherwise."""
+        be = fem.get_backend()
+        n, (K, R) = V.dim(), W.shape
+        out = [fem.Function(V) for _ in range(R)]
+        if n >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "eval_batch") and hasattr(be, "vec_copy_range"):
+            store = _FieldStore(be, n, R)
+            be.eval_batch([m.vector().dev() for m in modes], np.ascontiguousarray(W), stats=False, fields=store.handle)
+            for i, f in enumerate(out):
+                be.vec_copy_range(f.vector().dev_for_write(), 0, store.handle, i * n, n)
+                f.vector().touched_dev()
+            fem.STATS["compress_eval_batch_calls"] = fem.STATS.get("compress_eval_batch_calls", 0) + 1
+        else:
+            F = np.stack([m.vector().host() for m in modes], axis=1) @ W
+            for i, f in enumerate(out):
+                f.vector()._host = np.ascontiguousarray(F[:, i])
+                f.vector().touched_host()
+        return out
+
+    def _like(self, modes, attri):
+        """A PGD with the meshes, names and modes_info of this one and the given modes (per dimension) as attribute 0."""
+        out = PGD(name=self.name, n_modes=len(modes[0]), fmeshes=self.fenics_meshes, pgd_modes=modes,
+                  name_coord=list(self.name_coord), modes_info=list(self.modes_info))
+        for pm, src in zip(out.mesh, self.mesh):
+            pm.name, pm.info = src.name, list(src.info)
+            pm.attributes[0].name = src.attributes[attri].name
+        out.problem, out.pos = self.problem, self.pos
+        return out
+
+    def compress(self, attri=0, tol=1e-6, max_modes=None, metric="l2", max_sweeps=200):
+        """A new ``PGD`` with R <= K modes and |u - u_R| <= tol |u| in ``metric``; this model is untouched.
+
+        The Gram matrices G_d of the modes (one pass per dimension, ``mode_gram``) turn the modes into coordinates in
+        orthonormal bases of their spans; there two dimensions are a truncated SVD (the optimal rank for ``tol``), three or more
+        a deterministic CP-ALS that grows R until ``tol`` is met (at most ``max_sweeps`` sweeps per R).  The new modes are the
+        combinations F_d W_d of the old ones (one ``pgd_eval_batch`` per dimension on the device), ordinary Functions that own
+        their vectors; every dimension carries the D-th root of a term's weight, terms come by descending weight, and the sign
+        makes the entry of largest magnitude of every mode of dimensions 1 .. D - 1 positive.
+
+        Without ``max_modes``: if no R < K meets ``tol`` a copy of the model comes back (modes_out = K, rel_error = 0).  With
+        it: the best R <= max_modes found, ``converged`` False if that misses ``tol``.  ``result.compression`` holds modes_in,
+        modes_out, rel_error, tol, metric, sweeps, converged, ranks (of the G_d).  Only attribute ``attri`` is carried over (as
+        attribute 0 of the result)."""
+        tol = float(tol)
+        if not tol >= COMPRESS_TOL_FLOOR:
+            raise ValueError("compress: tol = %g is below %g: the Gram route carries half the digits, components below "
+                             "sqrt(2^-53) |u| = 1.05e-8 |u| are not resolved" % (tol, COMPRESS_TOL_FLOOR))
+        if max_modes is not None and int(max_modes) < 1:
+            raise ValueError("compress: max_modes must be at least 1")
+        if metric not in ("l2", "mass"):
+            raise ValueError("compress: metric must be 'l2' or 'mass', got %r" % (metric,))
+        D, K = self.num_pgd_var, self.used_numModes
+        fam = [self._gram_family(d, attri) for d in range(D)]
+        Gs = [self.mode_gram(d, attri, metric) for d in range(D)]
+        plan = compress_grams(Gs, tol, max_modes, max_sweeps)
+        info = {"modes_in": K, "modes_out": plan["R"], "rel_error": plan["rel_error"], "tol": tol, "metric": metric,
+                "sweeps": plan["sweeps"], "converged": plan["converged"], "ranks": plan["ranks"]}
+        if plan["W"] is None:
+            out = self._like([[m.copy(deepcopy=True) for m in modes] for modes, _ in fam], attri)
+            out.compression = info
+            return out
+        Ws = [W.copy() for W in plan["W"]]
+        new = [None] * D
+        for d in range(D - 1, -1, -1):                # dimension 0 last: it takes the signs of the others
+            new[d] = self._combine_modes(fam[d][1], fam[d][0], Ws[d])
+            if d > 0:
+                for i, f in enumerate(new[d]):
+                    a = f.vector().host()
+                    if a.size and a[int(np.argmax(np.abs(a)))] < 0.0:
+                        f.vector().scale(-1.0)
+                        Ws[0][:, i] *= -1.0
+        out = self._like(new, attri)
+        out.compression = info
+        return out
 
     # ------------------------------------------------- batched evaluation of gradient quantities
     def evaluate_gradient_many(self, fixed_dim, free_dim, coords, attri, quantity="gradient_norm", scale=None, stats=True,

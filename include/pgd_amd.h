@@ -468,6 +468,25 @@ int pgd_vec_multidot_pair(pgd_handle ctx, pgd_handle x0, pgd_handle x1, const pg
 int pgd_vec_gram(pgd_handle ctx, const pgd_handle *xs, int kx, const pgd_handle *ys_or_null, int ky, int64_t lo, int64_t hi,
                  double *out);
 
+/* Quadratic forms of the modes at every entry: outs[q][i] = f_i^T Q_q f_i for nq matrices (q: nq row-major k x k doubles on the
+ * host, any matrix, symmetric or not), f_i = (modes[0][i] .. modes[k-1][i]); every mode read once per call.  outs[q] == 0: that
+ * field is not stored (outs may be NULL: none is).  flags & PGD_QUAD_CLAMP: values below 0 are stored (and reduced) as 0.
+ * extrema (may be NULL): min over the rows of form q in extrema[2 q], max in extrema[2 q + 1], of the values as stored.
+ * 1 <= k <= 256, 1 <= nq <= 64 (the binding blocks more forms).  The partial variances of a separated solution with independent
+ * parameters are such forms (model.py: variance_decomposition).  v_mfma_f64_16x16x4_f64 with the dofs on the fragment's column
+ * index as in pgd_eval_batch: a wave owns its rows, F Q is consumed in registers, each value is one fixed chain and the extrema
+ * do not depend on order - every output is bit-identical for any grid (PGD_TUNE_QUAD_GRID_MAX), and a form's field is the same
+ * bits alone or among others.  PGD_TUNE_QUAD_VARIANT = 0: plain fma chains.  ONE host synchronisation.  PGD_ERR_INVALID with a
+ * message, before anything is launched and with the outputs untouched: null modes or q, k or nq out of range, unknown flags, an
+ * invalid handle, vectors of different lengths, an output that is also a mode or another output, neither a field nor extrema.
+ * Vectors of length 0: PGD_OK, extrema (+inf, -inf).  NaNs give unspecified extrema.                                          */
+enum { PGD_QUAD_CLAMP = 1 };
+int pgd_quad_forms(pgd_handle ctx, const pgd_handle *modes, int k, const double *q, int nq, int flags, const pgd_handle *outs,
+                   double *extrema);
+/* out[i] = den[i] > floor ? num[i] / den[i] : 0 (out may be num or den).  The ratio fields of the forms above: a Sobol index
+ * where the variance is above a floor.  PGD_ERR_INVALID: invalid handles, different lengths, a NaN floor.  No synchronisation. */
+int pgd_vec_ratio(pgd_handle ctx, pgd_handle out, pgd_handle num, pgd_handle den, double floor);
+
 /* ------------------------------------------------------------ column blocks --- */
 /* k <= 64 columns of n rows in ONE library-owned allocation, stored as fp32 or f64: the start space of the spatial solves
  * (pgdrome_amd/spectral.py; this library's addition in front of the solve that replaces solver.py:636,716), whose cost per
@@ -677,6 +696,10 @@ int pgd_points_free(pgd_handle ctx, pgd_handle points);
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_QUAD_GRID_MAX = 65, /* pgd_quad_forms: > 0: at most this many (persistent) workgroups; 0 (default): as many as are resident at once.
+                                The same bits either way. */
+    PGD_TUNE_QUAD_VARIANT = 64, /* pgd_quad_forms: 1 (default) the product on the f64 matrix unit (k_quad_mfma), 0 ordinary fma chains
+                                (k_quad_plain): the cross-check and the baseline. */
     PGD_TUNE_GRAM_GRID_MAX = 63, /* pgd_vec_gram: > 0: at most this many (persistent) workgroups; 0 (default): as many as are resident at once.
                                 The same bits either way: the segments and the order of their partials do not depend on the grid. */
     PGD_TUNE_GRAM_VARIANT = 62, /* pgd_vec_gram: 1 (default) the product on the f64 matrix unit (k_gram_mfma), 0 one fma chain per entry

@@ -105,6 +105,8 @@ SIGNATURES = {
     "pgd_vec_multidot": (C.c_int, [H, H, PH, C.c_int, I64, I64, PD]),
     "pgd_vec_multidot_pair": (C.c_int, [H, H, H, PH, C.c_int, I64, I64, PD]),
     "pgd_vec_gram": (C.c_int, [H, PH, C.c_int, PH, C.c_int, I64, I64, PD]),
+    "pgd_quad_forms": (C.c_int, [H, PH, C.c_int, PD, C.c_int, C.c_int, PH, PD]),
+    "pgd_vec_ratio": (C.c_int, [H, H, H, H, C.c_double]),
     "pgd_pcg_solve": (C.c_int, [H, H, H, H, F64, F64, C.c_int, C.POINTER(C.c_int), PD]),
     "pgd_pcg_last_form": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pgd_band_solve": (C.c_int, [H, H, H, H]),
@@ -187,6 +189,9 @@ TUNE_SPMV_P2_LATTICE = 59
 TUNE_LOCATE_LATTICE, TUNE_LOCATE_GRID_MAX = 60, 61
 TUNE_GRAM_VARIANT, TUNE_GRAM_GRID_MAX = 62, 63
 GRAM_KMAX = 128            # vectors per side and call of pgd_vec_gram
+TUNE_QUAD_VARIANT, TUNE_QUAD_GRID_MAX = 64, 65
+QUAD_KMAX, QUAD_NQMAX = 256, 64   # modes and forms per call of pgd_quad_forms
+QUAD_CLAMP = 1
 LOCATE_TILE = 32                                    # points per launch of the general location kernel (LOC_PT, csrc/pgd_locate.hip)
 LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE = 1, 2     # pgd_points_last_path
 BLOCK_F32, BLOCK_F64, BLOCK_MAXK = 0, 1, 64                                           # PGD_BLOCK_* (include/pgd_amd.h)
@@ -657,6 +662,37 @@ class Context:
                 if sym and j0 > i0:
                     out[j0:j0 + len(yb), i0:i0 + len(xb)] = blk.T
         return out
+
+    def quad_forms(self, modes, Q, outs=None, clamp=False):
+        """pgd_quad_forms: f_i^T Q_q f_i at every entry i for the nq matrices ``Q`` (nq, k, k) or (k, k), every mode read once per
+        call of at most 64 forms.  ``outs``: one vector handle or None per form (None: no field is stored).  Returns the arrays
+        (min, max) over the entries of every form, of the values as stored (``clamp``: below 0 as 0)."""
+        modes = [int(v) for v in modes]
+        k = len(modes)
+        Q = np.asarray(Q, dtype=np.float64)
+        if Q.ndim == 2:
+            Q = Q[None]
+        if Q.ndim != 3 or Q.shape[1:] != (k, k) or Q.shape[0] < 1:
+            raise ValueError(f"quad_forms: Q has shape {Q.shape}, (nq, {k}, {k}) is needed")
+        nq = Q.shape[0]
+        outs = [None] * nq if outs is None else list(outs)
+        if len(outs) != nq:
+            raise ValueError(f"quad_forms: {len(outs)} outputs for {nq} forms")
+        ma = (H * k)(*modes)
+        mn, mx = np.empty(nq), np.empty(nq)
+        for q0 in range(0, nq, QUAD_NQMAX):
+            qb = np.ascontiguousarray(Q[q0:q0 + QUAD_NQMAX])
+            ob = [0 if o is None else int(o) for o in outs[q0:q0 + QUAD_NQMAX]]
+            oa = (H * len(ob))(*ob)
+            ext = np.zeros(2 * len(ob), dtype=np.float64)
+            self._ck(self.lib.pgd_quad_forms(self.h, ma, k, dptr(qb), len(ob), QUAD_CLAMP if clamp else 0, oa, dptr(ext)))
+            mn[q0:q0 + len(ob)] = ext[0::2]
+            mx[q0:q0 + len(ob)] = ext[1::2]
+        return mn, mx
+
+    def vec_ratio(self, out, num, den, floor=0.0):
+        """pgd_vec_ratio: out = num / den where den > floor, 0 elsewhere (``out`` may be ``num``)."""
+        self._ck(self.lib.pgd_vec_ratio(self.h, out, num, den, float(floor)))
 
     # ---- atoms / operators
     def atom_product_form(self, atom):

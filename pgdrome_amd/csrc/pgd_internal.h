@@ -410,6 +410,8 @@ struct Ctx {
     int locate_lattice = 1, locate_grid_max = 0, locate_last_path = 0;
     // pgd_vec_gram (pgd_gram.hip): kernel variant (1 MFMA, 0 plain fma chains; PGD_TUNE_GRAM_VARIANT) and grid cap (PGD_TUNE_GRAM_GRID_MAX; 0: what is resident at once)
     int gram_variant = 1, gram_grid_max = 0;
+    // pgd_quad_forms (pgd_quad.hip): kernel variant (1 MFMA, 0 plain fma chains; PGD_TUNE_QUAD_VARIANT) and grid cap (PGD_TUNE_QUAD_GRID_MAX; 0: what is resident at once)
+    int quad_variant = 1, quad_grid_max = 0;
 
     // SpMV launch timing (HIP events on `stream`)
     bool prof = false;

@@ -495,6 +495,63 @@ def compress_grams(Gs, tol, max_modes=None, max_sweeps=200):
             "sweeps": int(sweeps)}
 
 
+def _hadamard(mats):
+    out = np.array(mats[0], dtype=np.float64)
+    for M in mats[1:]:
+        out = out * M
+    return out
+
+
+def variance_forms(moments, random, order=1):
+    """The K x K matrices Q with V(x_i) = f_i^T Q f_i for the ANOVA / Sobol decomposition of u = sum_k F_k(x) prod_d G_dk(mu_d)
+    with independent parameters.  ``moments`` {d: (m_d, C_d)} over ALL parameter dimensions (``PGD.parameter_moments``; a
+    dimension that is given a value has C_d = 0), ``random`` the dimensions that vary.  With M_d = m_d m_d^T and o the
+    entrywise product, the keys of the result are
+
+        "total"   sum_j (o_{d<j} (C_d + M_d)) o C_j o (o_{d>j} M_d): the variance, P terms and no subtraction
+        (i,)      C_i o (o_{d != i} M_d): the first-order term Var E[u | mu_i]
+        (i, j)    C_i o C_j o (o_{d != i, j} M_d), i < j, with ``order`` 2: the second-order interaction
+        ("T", i)  C_i o (o_{d != i} (C_d + M_d)): the total effect E Var[u | mu_~i]
+
+    Every matrix is positive semidefinite (Schur products of such)."""
+    dims = sorted(moments)
+    random = sorted(random)
+    C = {d: np.asarray(moments[d][1], dtype=np.float64) for d in dims}
+    M = {d: np.outer(moments[d][0], moments[d][0]) for d in dims}
+    S = {d: C[d] + M[d] for d in dims}
+    forms = {"total": sum(_hadamard([S[d] if d < j else C[d] if d == j else M[d] for d in dims]) for j in random)}
+    for i in random:
+        forms[(i,)] = _hadamard([C[d] if d == i else M[d] for d in dims])
+    if order >= 2:
+        for a, i in enumerate(random):
+            for j in random[a + 1:]:
+                forms[(i, j)] = _hadamard([C[d] if d in (i, j) else M[d] for d in dims])
+    for i in random:
+        forms[("T", i)] = _hadamard([C[d] if d == i else S[d] for d in dims])
+    return forms
+
+
+class VarianceDecomposition:
+    """What ``PGD.variance_decomposition`` returns.  Fields (Functions on the fixed space; None / empty with ``fields=False``):
+    ``mean``, ``variance`` (clamped at 0), ``std`` (the root, taken on the host when asked for), ``sobol[(i,)]`` / ``sobol[(i, j)]``
+    and ``total[i]`` (ratio fields, 0 where the variance is at or below ``floor``), ``partial[key]`` / ``partial_total[i]`` (the
+    partial variances they are ratios of).  Numbers: ``variance_min`` / ``variance_max``, ``extrema[key]`` = (min, max) of every
+    form, ``floor``, ``global_variance`` = int V dx and ``global_sobol[key]`` / ``global_total[i]`` = int V_B dx / int V dx (exact,
+    from the mass Gram matrix of the fixed modes).  ``forms`` (the Q matrices by key, see ``variance_forms``), ``moments``
+    {dim: (m, C)}, ``mean_coefficients``, ``random``, ``given``."""
+
+    def __init__(self):
+        self.mean = self.variance = None
+        self.sobol, self.total, self.partial, self.partial_total = {}, {}, {}, {}
+        self._std = None
+
+    @property
+    def std(self):
+        if self._std is None and self.variance is not None:
+            self._std = _host_function(self.variance.function_space(), np.sqrt(np.maximum(self.variance.vector().host(), 0.0)))
+        return self._std
+
+
 class PGD:
     def __init__(self, name=None, n_modes=0, fmeshes=[], pgd_modes=[], name_coord=[], modes_info=[],
                  verbose=False, *args, **kwargs):
@@ -1211,6 +1268,198 @@ class PGD:
         out = self._like(new, attri)
         out.compression = info
         return out
+
+    # ------------------------------------------- moments over the parameter domain: mean, variance, Sobol index fields
+    @staticmethod
+    def _apply_atom(V, op, fs):
+        """[A f for f in fs] with the operator handle ``op`` on V."""
+        be = fem.get_backend()
+        lo, hi = V._lay.owned_range()
+        out = []
+        for f in fs:
+            w = fem.Function(V)
+            be.spmv(op, f.vector().dev(), w.vector().dev_for_write(), lo, hi)
+            w.vector().touched_dev()
+            out.append(w)
+        return out
+
+    def _density_function(self, dim, V, density):
+        """The density of a parameter dimension as a Function on the modes' space (None: uniform), its dof values checked."""
+        if density is None:
+            return None
+        if isinstance(density, fem.Function):
+            if not self._same_space(V, density.function_space()):
+                raise ValueError("parameter_moments: the density of dimension %d lives on another space than the modes" % dim)
+            rho = density
+        elif isinstance(density, fem.Expression):
+            rho = fem.interpolate(density, V)
+        elif callable(density):
+            X = V._lay.coords
+            rho = _host_function(V, np.array([float(density(float(x[0])) if X.shape[1] == 1 else density(x)) for x in X]))
+        else:
+            raise ValueError("parameter_moments: density must be None, a Function, an Expression or a callable, got %r"
+                             % (type(density),))
+        a = rho.vector().host()
+        if not np.all(np.isfinite(a)) or a.min() < 0.0:
+            raise ValueError("parameter_moments: the density of dimension %d is negative or not finite at a dof" % dim)
+        return rho
+
+    def parameter_moments(self, dim, attri=0, density=None, given=None):
+        """(m, C) of the used modes G_k of a parameter dimension under the probability density ``density`` (None: uniform; a
+        Function on the modes' space, an Expression or a callable interpolated to it; normalised by its own integral):
+        m[k] = int rho G_k and C[k, l] = int rho (G_k - m[k]) (G_l - m[l]).  Both come from the (weighted) mass atom of the
+        dimension, ``rho*u*v*dx``: m from one product with the constant, C from the CENTRED modes - the constant lies in the
+        space, so G - m 1 is a mode vector again; the difference S - m m^T would lose the variance of nearly constant modes.
+        ``given=c`` conditions on the value c of the parameter: (G(c), zeros)."""
+        modes, V = self._gram_family(dim, attri)
+        if V._ncomp > 1:
+            raise NotImplementedError("parameter_moments on a vector-valued parameter space")
+        if V._dg0:
+            raise NotImplementedError("parameter_moments of cell-wise constant modes")
+        K = len(modes)
+        if given is not None:
+            if density is not None:
+                raise ValueError("parameter_moments: dimension %d is given a value and a density" % dim)
+            x = np.atleast_1d(np.asarray(given, dtype=np.float64))
+            x = x if V.mesh().geometry().dim() == 1 and x.size == 1 else x.reshape(1, -1)
+            return np.array(self._free_modes_at(dim, x, attri)[:, 0], dtype=np.float64), np.zeros((K, K))
+        rho = self._density_function(dim, V, density)
+        be = fem.get_backend()
+        u, v = fem.TrialFunction(V), fem.TestFunction(V)
+        op = fem.assemble((u * v if rho is None else rho * u * v) * fem.dx).op()
+        try:
+            one = _host_function(V, np.ones(V.dim()))
+            w1 = self._apply_atom(V, op, [one])
+            Z = float(self._gram_block(V, [one], w1)[0, 0])
+            if not Z > 0.0:
+                raise ValueError("parameter_moments: the density of dimension %d has no positive integral" % dim)
+            m = self._gram_block(V, modes, w1)[:, 0] / Z
+            centred = [_host_function(V, f.vector().host() - m[k]) for k, f in enumerate(modes)]
+            C = self._gram_block(V, centred, self._apply_atom(V, op, centred)) / Z
+        finally:
+            be.atom_free(op)
+        return m, 0.5 * (C + C.T)
+
+    def quadratic_forms(self, dim, Q, attri=0, clamp=False, fields=True, row_chunk=8192):
+        """The quadratic forms f_i^T Q_q f_i of the used modes of dimension ``dim`` at every dof i, f_i = (F_1(x_i) .. F_K(x_i)),
+        for ``Q`` of shape (nq, K, K) or (K, K) - any matrices.  Returns (functions, min, max): a list of nq Functions on the
+        dimension's space (None with ``fields=False``) and the arrays of the extrema over the dofs; ``clamp`` stores and reduces
+        values below 0 as 0.  One pass over the modes on the device (``pgd_quad_forms``, at most 64 forms per call) under the
+        rule of ``evaluate_many``, numpy over ``row_chunk`` rows at a time otherwise."""
+        modes, V = self._gram_family(dim, attri)
+        K, n = len(modes), V.dim()
+        Q = np.asarray(Q, dtype=np.float64)
+        if Q.ndim == 2:
+            Q = Q[None]
+        if Q.ndim != 3 or Q.shape[0] < 1 or Q.shape[1:] != (K, K):
+            raise ValueError("quadratic_forms: Q has shape %s, (nq, %d, %d) or (%d, %d) is needed" % (Q.shape, K, K, K, K))
+        if not np.all(np.isfinite(Q)):
+            raise ValueError("quadratic_forms: Q holds a value that is not finite")
+        nq = Q.shape[0]
+        be = fem.get_backend()
+        out = [fem.Function(V) for _ in range(nq)] if fields else None
+        if n >= DEVICE_EVAL_MIN_DOFS and K <= 256 and hasattr(be, "quad_forms"):
+            outs = None if out is None else [f.vector().dev_for_write() for f in out]
+            mn, mx = be.quad_forms([f.vector().dev() for f in modes], Q, outs, clamp)
+            for f in out or ():
+                f.vector().touched_dev()
+            fem.STATS["quad_forms_calls"] = fem.STATS.get("quad_forms_calls", 0) + 1
+            return out, mn, mx
+        F = np.stack([f.vector().host() for f in modes], axis=1)
+        vals = np.empty((nq, n)) if fields else None
+        mn, mx = np.full(nq, np.inf), np.full(nq, -np.inf)
+        for r0 in range(0, n, int(row_chunk)):
+            Fc = F[r0:r0 + int(row_chunk)]
+            for q in range(nq):
+                v = np.einsum("ik,ik->i", Fc @ Q[q].T, Fc)
+                if clamp:
+                    v = np.where(v < 0.0, 0.0, v)
+                if v.size:
+                    mn[q], mx[q] = min(mn[q], v.min()), max(mx[q], v.max())
+                if fields:
+                    vals[q, r0:r0 + Fc.shape[0]] = v
+        for q, f in enumerate(out or ()):
+            f.vector()._host = np.ascontiguousarray(vals[q])
+            f.vector().touched_host()
+        return out, mn, mx
+
+    @staticmethod
+    def _ratio_field(V, num, den, floor):
+        """num / den where den > floor, 0 elsewhere: ``pgd_vec_ratio`` under the rule of ``evaluate_many``, numpy otherwise."""
+        be = fem.get_backend()
+        out = fem.Function(V)
+        if V.dim() >= DEVICE_EVAL_MIN_DOFS and hasattr(be, "vec_ratio"):
+            be.vec_ratio(out.vector().dev_for_write(), num.vector().dev(), den.vector().dev(), floor)
+            out.vector().touched_dev()
+        else:
+            a, b = num.vector().host(), den.vector().host()
+            ok = b > floor
+            out.vector()._host = np.where(ok, a / np.where(ok, b, 1.0), 0.0)
+            out.vector().touched_host()
+        return out
+
+    def variance_decomposition(self, fixed_dim, attri=0, densities=None, given=None, order=1, fields=True, variance_floor=1e-12):
+        """Mean, variance and Sobol index fields of the solution on ``fixed_dim`` over the domain of the other dimensions, taken
+        as independent random parameters - exact integrals of the separated form, no sampling.  ``densities`` {dim: density}
+        (see ``parameter_moments``; missing: uniform), ``given`` {dim: value} conditions on fixed values; every other dimension
+        is either random or given.  ``order`` 1 or 2: first-order indices, or second-order interactions as well.
+
+        Every partial variance is a quadratic form of the fixed dimension's modes (``variance_forms``, ``quadratic_forms``: one
+        pass over the modes for all of them).  Ratio fields are V_B / V where V > variance_floor * max V and 0 elsewhere
+        (Dirichlet nodes are such places).  ``fields=False`` forms extrema and global numbers only.  Returns a
+        ``VarianceDecomposition``."""
+        D = self.num_pgd_var
+        if fixed_dim < 0 or fixed_dim >= D:
+            raise ValueError("variance_decomposition: fixed dimension %r not possible" % (fixed_dim,))
+        if order not in (1, 2):
+            raise ValueError("variance_decomposition: order must be 1 or 2, got %r" % (order,))
+        if not (float(variance_floor) >= 0.0):
+            raise ValueError("variance_decomposition: variance_floor must be >= 0")
+        densities, given = dict(densities or {}), dict(given or {})
+        dims = [d for d in range(D) if d != fixed_dim]
+        for name, table in (("densities", densities), ("given", given)):
+            for d in table:
+                if d not in dims:
+                    raise ValueError("variance_decomposition: %s names dimension %r, the parameter dimensions are %s" % (name, d, dims))
+        both = sorted(set(densities) & set(given))
+        if both:
+            raise ValueError("variance_decomposition: dimensions %s are given a value and a density" % both)
+        random = [d for d in dims if d not in given]
+        if not random:
+            raise ValueError("variance_decomposition: no random dimension is left (every parameter dimension is given)")
+        modes, V = self._gram_family(fixed_dim, attri)
+        moments = {d: self.parameter_moments(d, attri, densities.get(d), given.get(d)) for d in dims}
+        forms = variance_forms(moments, random, order)
+        keys = list(forms)
+        funcs, mn, mx = self.quadratic_forms(fixed_dim, np.stack([forms[k] for k in keys]), attri, clamp=True, fields=fields)
+        res = VarianceDecomposition()
+        res.forms, res.moments, res.random, res.given = forms, moments, list(random), given
+        it = keys.index("total")
+        res.variance_min, res.variance_max = float(mn[it]), float(mx[it])
+        res.extrema = {k: (float(mn[i]), float(mx[i])) for i, k in enumerate(keys)}
+        res.floor = float(variance_floor) * res.variance_max
+        Gm = self.mode_gram(fixed_dim, attri, "mass")
+        glob = {k: float(np.sum(Gm * forms[k].T)) for k in keys}
+        res.global_variance = glob["total"]
+        ratio = (lambda x: x / glob["total"]) if glob["total"] > 0.0 else (lambda x: 0.0)
+        res.global_sobol = {k: ratio(glob[k]) for k in keys if isinstance(k, tuple) and k[0] != "T"}
+        res.global_total = {k[1]: ratio(glob[k]) for k in keys if isinstance(k, tuple) and k[0] == "T"}
+        m = np.ones(len(modes))
+        for d in dims:
+            m = m * moments[d][0]
+        res.mean_coefficients = m
+        if fields:
+            res.mean = self._combine_modes(V, modes, m.reshape(-1, 1))[0]
+            res.variance = funcs[it]
+            for i, k in enumerate(keys):
+                if k == "total":
+                    continue
+                r = self._ratio_field(V, funcs[i], res.variance, res.floor)
+                if k[0] == "T":
+                    res.partial_total[k[1]], res.total[k[1]] = funcs[i], r
+                else:
+                    res.partial[k], res.sobol[k] = funcs[i], r
+        return res
 
     # ------------------------------------------------- batched evaluation of gradient quantities
     def evaluate_gradient_many(self, fixed_dim, free_dim, coords, attri, quantity="gradient_norm", scale=None, stats=True,

@@ -670,7 +670,22 @@ int pgd_eval_batch_grad_p2_quantity(pgd_handle ctx, pgd_handle mesh, const pgd_h
  *   determinant), where sampled gradients are not numbers.
  * pgd_points_download: cells_out (npts) and lam_out (npts x (gdim + 1)), host arrays; either may be NULL.
  * pgd_points_info: the number of points, gdim and the first point whose cell is -1 (-1: none); null outputs are skipped.
- * pgd_points_last_path: what the last pgd_points_locate of the context ran: 0 nothing, 1 the general kernel, 2 the lattice path.
+ * pgd_points_last_path: what the last pgd_points_locate of the context ran: 0 nothing, 1 the general kernel, 2 the lattice path,
+ *   3 the bin index.
+ *
+ * The bin index (PGD_TUNE_LOCATE_INDEX = 1; 2-D and 3-D meshes, tol <= 2^-10; the lattice path keeps precedence where it applies):
+ *   a uniform grid of bins over the bounding box of the mesh, every cell registered in the bins that its bounding box, inflated
+ *   by (gdim + 1) (2^-10 + 2^-20) of its extent per axis, touches; a thread per point tests the cells of the point's bin only.
+ *   The same cells and lam as the general kernel, bit for bit, on meshes whose edge matrices have a condition below about 2^30.
+ *   The index belongs to the scalar layout behind `mesh`: the first indexed call builds it on the device (about 48 cells per bin in
+ *   3-D, 8 in 2-D, or PGD_TUNE_LOCATE_INDEX_TARGET; coarsened while it holds more than 16 entries per cell), later calls use it,
+ *   a call under another target rebuilds it; pgd_mesh_free or pgd_points_index_drop free it.  A build waits for the host three
+ *   times and once more per coarsening (the box, the number of entries, the end); a build that fails leaves no index and no memory.
+ * pgd_points_index_info: out[8] = built (0/1), builds so far, bins along x, y, z (1 for a missing axis), entries, the longest
+ *   list, device bytes held; all 0 before a build and after a drop.
+ * pgd_points_index_download: bin_ptr (bins + 1), bin_cells (entries), geom[9] = origin, inv = bins / extent, bins per axis (as
+ *   doubles), 3 each; any may be NULL.  PGD_ERR_INVALID without an index.
+ * pgd_points_index_drop: frees the index of the mesh; PGD_OK without one.
  *
  * pgd_points_sample: layout: any P1 or P2 layout, scalar or blocked, over a mesh with the point set's number of cells and gdim
  * (the caller guarantees it is the same mesh);  u: nv*ncomp entries, node*ncomp + c.
@@ -689,6 +704,9 @@ int pgd_points_from(pgd_handle ctx, pgd_handle mesh, const int32_t *cells, const
 int pgd_points_download(pgd_handle ctx, pgd_handle points, int32_t *cells_out, double *lam_out);
 int pgd_points_info(pgd_handle ctx, pgd_handle points, int64_t *npts, int *gdim, int64_t *first_outside);
 int pgd_points_last_path(pgd_handle ctx, int *path);
+int pgd_points_index_info(pgd_handle ctx, pgd_handle mesh, int64_t *out);
+int pgd_points_index_download(pgd_handle ctx, pgd_handle mesh, int32_t *bin_ptr, int32_t *bin_cells, double *geom);
+int pgd_points_index_drop(pgd_handle ctx, pgd_handle mesh);
 int pgd_points_sample(pgd_handle ctx, pgd_handle points, pgd_handle layout, pgd_handle u, int what, pgd_handle out);
 int pgd_points_free(pgd_handle ctx, pgd_handle points);
 
@@ -696,6 +714,11 @@ int pgd_points_free(pgd_handle ctx, pgd_handle points);
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_LOCATE_INDEX_TARGET = 67, /* the bin index of pgd_points_locate: > 0: this many cells per bin; 0 (default): 48 in 3-D, 8 in 2-D.  A
+                                call under another value than the index of the mesh was built with rebuilds it.  Same cells and lam. */
+    PGD_TUNE_LOCATE_INDEX = 66, /* 1: pgd_points_locate on a 2-D or 3-D mesh with tol <= 2^-10, where the lattice path does not apply, tests a
+                                point against the cells of its bin of a uniform grid over the mesh (built on first use, kept with the
+                                mesh); 0 (default): never.  Same cells and lam as the general kernel, bit for bit. */
     PGD_TUNE_QUAD_GRID_MAX = 65, /* pgd_quad_forms: > 0: at most this many (persistent) workgroups; 0 (default): as many as are resident at once.
                                 The same bits either way. */
     PGD_TUNE_QUAD_VARIANT = 64, /* pgd_quad_forms: 1 (default) the product on the f64 matrix unit (k_quad_mfma), 0 ordinary fma chains

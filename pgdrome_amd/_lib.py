@@ -172,6 +172,9 @@ SIGNATURES = {
     "pgd_points_download": (C.c_int, [H, H, PI32, PD]),
     "pgd_points_info": (C.c_int, [H, H, PI64, C.POINTER(C.c_int), PI64]),
     "pgd_points_last_path": (C.c_int, [H, C.POINTER(C.c_int)]),
+    "pgd_points_index_info": (C.c_int, [H, H, PI64]),
+    "pgd_points_index_download": (C.c_int, [H, H, PI32, PI32, PD]),
+    "pgd_points_index_drop": (C.c_int, [H, H]),
     "pgd_points_sample": (C.c_int, [H, H, H, H, C.c_int, H]),
     "pgd_points_free": (C.c_int, [H, H]),
     "pgd_timer_start": (C.c_int, [H]),
@@ -187,6 +190,7 @@ TUNE_PCG_FOLD_MARCH, TUNE_PCG_SCALAR_S, TUNE_PCG_FUSED_MARCH = 55, 56, 57
 TUNE_SPMV_BLOCK_DIA = 58
 TUNE_SPMV_P2_LATTICE = 59
 TUNE_LOCATE_LATTICE, TUNE_LOCATE_GRID_MAX = 60, 61
+TUNE_LOCATE_INDEX, TUNE_LOCATE_INDEX_TARGET = 66, 67
 TUNE_GRAM_VARIANT, TUNE_GRAM_GRID_MAX = 62, 63
 GRAM_KMAX = 128            # vectors per side and call of pgd_vec_gram
 TUNE_QUAD_VARIANT, TUNE_QUAD_GRID_MAX = 64, 65
@@ -194,6 +198,8 @@ QUAD_KMAX, QUAD_NQMAX = 256, 64   # modes and forms per call of pgd_quad_forms
 QUAD_CLAMP = 1
 LOCATE_TILE = 32                                    # points per launch of the general location kernel (LOC_PT, csrc/pgd_locate.hip)
 LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE = 1, 2     # pgd_points_last_path
+LOCATE_PATH_INDEX = 3                               # ... the bin index (TUNE_LOCATE_INDEX)
+LOCATE_INDEX_TOL = 2.0 ** -10                       # the bin index serves tolerances up to here (LOC_INDEX_TOL, csrc/pgd_locate.hip)
 BLOCK_F32, BLOCK_F64, BLOCK_MAXK = 0, 1, 64                                           # PGD_BLOCK_* (include/pgd_amd.h)
 
 
@@ -274,6 +280,7 @@ class Context:
         self.h = h.value
         self.device = device
         self._block_k = {}            # column blocks of this context: handle -> k
+        self._locate_index = 0        # the value of TUNE_LOCATE_INDEX (tune keeps it: points_locate restores it)
 
     def close(self):
         if getattr(self, "h", 0):
@@ -564,13 +571,23 @@ class Context:
                                 modes, coefs, stats, env_min, env_max, exceed, threshold, fields, lead=(int(mesh),))
 
     # ---- point sets
-    def points_locate(self, mesh, pts, tol=1e-10):
-        """pgd_points_locate: the point set handle of ``pts`` (P, gdim) on the layout ``mesh``; a point outside gets cell -1."""
+    def points_locate(self, mesh, pts, tol=1e-10, index=False):
+        """pgd_points_locate: the point set handle of ``pts`` (P, gdim) on the layout ``mesh``; a point outside gets cell -1.
+        ``index``: True / False set TUNE_LOCATE_INDEX to 1 / 0 around the call and restore it (the bin index of the mesh is used, and
+        built where there is none, wherever it applies: 2-D and 3-D, tol <= LOCATE_INDEX_TOL, no lattice path); None leaves the knob
+        as ``tune`` set it."""
         pts = np.ascontiguousarray(pts, dtype=np.float64)
         if pts.ndim != 2:
             raise ValueError("points_locate: pts is a (points, gdim) array")
         out = H(0)
-        self._ck(self.lib.pgd_points_locate(self.h, mesh, dptr(pts) if pts.size else None, pts.shape[0], float(tol), C.byref(out)))
+        before = self._locate_index
+        if index is not None:
+            self.tune(TUNE_LOCATE_INDEX, 1 if index else 0)
+        try:
+            self._ck(self.lib.pgd_points_locate(self.h, mesh, dptr(pts) if pts.size else None, pts.shape[0], float(tol), C.byref(out)))
+        finally:
+            if index is not None:
+                self.tune(TUNE_LOCATE_INDEX, before)
         return out.value
 
     def points_from(self, mesh, cells, lam):
@@ -598,10 +615,31 @@ class Context:
         return cells, lam
 
     def points_last_path(self):
-        """What the last points_locate ran: 0 nothing, LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE."""
+        """What the last points_locate ran: 0 nothing, LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE, LOCATE_PATH_INDEX."""
         path = C.c_int(0)
         self._ck(self.lib.pgd_points_last_path(self.h, C.byref(path)))
         return path.value
+
+    def points_index_info(self, mesh):
+        """pgd_points_index_info: the bin index of the mesh as a dict - built, builds, n (bins per axis), entries, longest, bytes; all
+        zero before a build and after a drop."""
+        out = (I64 * 8)()
+        self._ck(self.lib.pgd_points_index_info(self.h, mesh, out))
+        v = [int(x) for x in out]
+        return dict(built=v[0], builds=v[1], n=(v[2], v[3], v[4]), entries=v[5], longest=v[6], bytes=v[7])
+
+    def points_index_download(self, mesh):
+        """pgd_points_index_download: (bin_ptr (bins + 1,), bin_cells (entries,), origin (3,), inv (3,), n (3,) int64)."""
+        info = self.points_index_info(mesh)
+        bins = info["n"][0] * info["n"][1] * info["n"][2]
+        bin_ptr, bin_cells = np.zeros(bins + 1, dtype=np.int32), np.zeros(max(info["entries"], 1), dtype=np.int32)
+        geom = np.zeros(9)
+        self._ck(self.lib.pgd_points_index_download(self.h, mesh, iptr(bin_ptr), iptr(bin_cells), dptr(geom)))
+        return bin_ptr, bin_cells[:info["entries"]], geom[:3].copy(), geom[3:6].copy(), geom[6:].astype(np.int64)
+
+    def points_index_drop(self, mesh):
+        """pgd_points_index_drop: frees the bin index of the mesh (nothing happens without one)."""
+        self._ck(self.lib.pgd_points_index_drop(self.h, mesh))
 
     def points_sample(self, points, layout, u, out, gradient=False):
         """pgd_points_sample: the values (``gradient``: the gradients) of the nodal field ``u`` of ``layout`` at the points, into ``out``."""
@@ -1041,6 +1079,8 @@ class Context:
 
     def tune(self, knob, value):
         self._ck(self.lib.pgd_tune(self.h, int(knob), int(value)))
+        if int(knob) == TUNE_LOCATE_INDEX:
+            self._locate_index = int(value)
 
     # ---- measuring
     def prof_enable(self, on=True):

@@ -134,7 +134,31 @@ struct Mesh : Obj {
     // (node ids ascend with the anchor vertex first, the class second), at least 3 vertices per axis.  0: no; otherwise the largest
     // component count (1..3) with ncomp * nv < 2^31
     int p2_lat = 0;
+    // The bin index of pgd_points_locate (pgd_locate.hip, PGD_TUNE_LOCATE_INDEX) on a scalar 2-D or 3-D layout: a uniform grid of
+    // n[0] n[1] n[2] bins over the bounding box, bin b holding the cells bin_cells[bin_ptr[b] .. bin_ptr[b + 1]).  Built by the first
+    // indexed call, kept until the mesh goes, pgd_points_index_drop or a call under another PGD_TUNE_LOCATE_INDEX_TARGET
+    struct LocIndex {
+        bool built = false;
+        int64_t builds = 0;          // since the mesh was uploaded or the index dropped
+        int64_t target = 0;          // the knob's value it was built under
+        double o[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
+        int n[3] = {1, 1, 1};
+        int *bin_ptr = nullptr;      // bins + 1
+        int *bin_cells = nullptr;    // entries
+        int64_t bins = 0, entries = 0, longest = 0;
+        size_t bytes = 0;
+        void release() {             // (the caller has synchronised the stream)
+            if (bin_ptr) (void)hipFree(bin_ptr);
+            if (bin_cells) (void)hipFree(bin_cells);
+            bin_ptr = bin_cells = nullptr;
+            built = false;
+            bins = entries = longest = 0;
+            bytes = 0;
+        }
+    };
+    mutable LocIndex loc_index;
     ~Mesh() override {
+        loc_index.release();
         for (void *p : {(void *)coords, (void *)cells, (void *)cellsN, (void *)v2c_ptr, (void *)v2c,
                         (void *)row_ptr, (void *)cols, (void *)pids, (void *)dict_off, (void *)sym_tab, (void *)p2_par, (void *)p2_v2e})
             if (p) (void)hipFree(p);
@@ -408,6 +432,8 @@ struct Ctx {
     // pgd_points_locate (pgd_locate.hip): the one-thread-per-point path on regularly numbered box lattices (PGD_TUNE_LOCATE_LATTICE), the
     // grid cap of the general kernel (PGD_TUNE_LOCATE_GRID_MAX; 0: what is resident at once) and what the last call ran (pgd_points_last_path)
     int locate_lattice = 1, locate_grid_max = 0, locate_last_path = 0;
+    int locate_index = 0;               // PGD_TUNE_LOCATE_INDEX
+    int64_t locate_index_target = 0;    // PGD_TUNE_LOCATE_INDEX_TARGET
     // pgd_vec_gram (pgd_gram.hip): kernel variant (1 MFMA, 0 plain fma chains; PGD_TUNE_GRAM_VARIANT) and grid cap (PGD_TUNE_GRAM_GRID_MAX; 0: what is resident at once)
     int gram_variant = 1, gram_grid_max = 0;
     // pgd_quad_forms (pgd_quad.hip): kernel variant (1 MFMA, 0 plain fma chains; PGD_TUNE_QUAD_VARIANT) and grid cap (PGD_TUNE_QUAD_GRID_MAX; 0: what is resident at once)

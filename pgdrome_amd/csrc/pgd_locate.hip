@@ -16,6 +16,9 @@
 //     ascending order (no atomics), applies tol and writes cell and lam of the winner - recomputed by cell_bary, the same bits.
 //   - k_locate_lattice (Mesh::lattice_regular): a thread per point, the 6 tetrahedra of the up to 27 cubes around the point's cube
 //     in ascending cell order under the same rule.
+//   - k_locate_index (any 2-D or 3-D mesh, PGD_TUNE_LOCATE_INDEX): a thread per point over the cells registered in the point's bin
+//     of a uniform grid over the mesh's bounding box (Mesh::loc_index, built on the device once per mesh: k_index_bounds,
+//     k_index_count, scan, k_index_fill), under the same rule.
 #include "pgd_internal.h"
 
 #include <cmath>
@@ -26,6 +29,10 @@ namespace pgd {
 
 constexpr int LOC_PT = 32;                 // points per launch of k_locate_cells: 3 registers each for the running best (96 of ~150 VGPRs: 3 waves per SIMD)
 constexpr double LOC_LATTICE_TOL = 0.125;  // the lattice path serves tolerances up to here (why: k_locate_lattice)
+constexpr double LOC_INDEX_TOL = 0x1p-10;  // the bin index serves tolerances up to here (why: k_locate_index)
+constexpr double LOC_INDEX_SLACK = 0x1p-20;      // ... and edge matrices of condition up to about 2^30 (part (b) of the argument there)
+constexpr int LOC_INDEX_TARGET_3D = 48, LOC_INDEX_TARGET_2D = 8;      // cells per bin the grid aims at: a bin edge of two lattice steps
+constexpr int64_t LOC_INDEX_CAP = 16;      // entries per cell beyond which the grid is coarsened
 
 struct Points : Obj {
     int gdim = 0;
@@ -290,6 +297,207 @@ __global__ __launch_bounds__(TPB) void k_locate_lattice(const int4 *__restrict__
     locate_store<3>(cells4, nullptr, 0, coords, nv, x, bm, be, tol, cell_out + p, lam_out + p * 4);
 }
 
+// ---- the bin index: a uniform grid of n[0] x n[1] x n[2] bins over the bounding box of the mesh (origin o, inv = n / extent per
+// axis; n = 1 and inv = 0 on an axis the mesh does not have or does not extend along), CSR-like: the cells registered in bin b are
+// bin_cells[bin_ptr[b] .. bin_ptr[b + 1]).  A cell is registered in every bin that its INFLATED bounding box touches.
+struct LocGrid {
+    double o[3], inv[3];
+    int n[3];
+};
+
+// the bin of a coordinate along one axis - the ONE function that the count, the fill and the query share.  Clamped: a coordinate
+// outside the box lands in the first or last bin, a NaN (also inf * 0 on a flat axis) in bin 0
+__device__ __forceinline__ int bin_of(double x, double o, double inv, int n) {
+#pragma clang fp contract(off)
+    double f = floor((x - o) * inv);
+    f = f >= 0.0 ? f : 0.0;                                    // (a NaN becomes 0)
+    f = f <= (double)(n - 1) ? f : (double)(n - 1);
+    return (int)f;
+}
+
+// the bounding box of cell e over its vertices (the first G + 1 record entries); comparisons only
+template <int G>
+__device__ __forceinline__ void cell_box(const int4 *__restrict__ cells4, const int *__restrict__ cellsN, int nn, const double *__restrict__ coords,
+                                         int64_t nv, int64_t e, double (&lo)[G], double (&hi)[G]) {
+    int v[G + 1];
+    cell_vertices<G>(cells4, cellsN, nn, e, v);
+#pragma unroll
+    for (int d = 0; d < G; ++d) {
+        const double *x = coords + (int64_t)d * nv;
+        lo[d] = hi[d] = x[v[0]];
+#pragma unroll
+        for (int a = 1; a <= G; ++a) {
+            const double t = x[v[a]];
+            lo[d] = t < lo[d] ? t : lo[d];
+            hi[d] = t > hi[d] ? t : hi[d];
+        }
+    }
+}
+
+// the bins [r0[a], r1[a]] per axis of cell e: those of its box inflated by m_a = (G + 1) (LOC_INDEX_TOL + LOC_INDEX_SLACK) (hi_a - lo_a)
+// on either side.  Contraction off, every rounding spelt out: hi - lo, K times that, lo - m, hi + m
+template <int G>
+__device__ __forceinline__ void index_range(const int4 *__restrict__ cells4, const int *__restrict__ cellsN, int nn, const double *__restrict__ coords,
+                                            int64_t nv, int64_t e, const LocGrid &g, int (&r0)[3], int (&r1)[3]) {
+#pragma clang fp contract(off)
+    constexpr double K = (G + 1) * (LOC_INDEX_TOL + LOC_INDEX_SLACK);      // exact
+    double lo[G], hi[G];
+    cell_box<G>(cells4, cellsN, nn, coords, nv, e, lo, hi);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { r0[a] = 0; r1[a] = 0; }
+#pragma unroll
+    for (int a = 0; a < G; ++a) {
+        const double d = hi[a] - lo[a];
+        const double m = K * d;
+        r0[a] = bin_of(lo[a] - m, g.o[a], g.inv[a], g.n[a]);
+        r1[a] = bin_of(hi[a] + m, g.o[a], g.inv[a], g.n[a]);
+    }
+}
+
+// the global box: minima and maxima of the cell boxes, per workgroup one row lo[0..G), hi[0..G) of `part` (exact and order-free:
+// comparisons, no sums; the host takes the rows together)
+template <int G>
+__global__ __launch_bounds__(TPB) void k_index_bounds(const int4 *__restrict__ cells4, const int *__restrict__ cellsN, int nn,
+                                                      const double *__restrict__ coords, int64_t nv, int64_t nc, double *__restrict__ part) {
+    __shared__ double s_box[TPB / WAVE][2 * G];
+    const double inf = std::numeric_limits<double>::infinity();
+    double lo[G], hi[G];
+#pragma unroll
+    for (int d = 0; d < G; ++d) { lo[d] = inf; hi[d] = -inf; }
+    for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < nc; e += (int64_t)gridDim.x * TPB) {
+        double l[G], h[G];
+        cell_box<G>(cells4, cellsN, nn, coords, nv, e, l, h);
+#pragma unroll
+        for (int d = 0; d < G; ++d) {
+            lo[d] = l[d] < lo[d] ? l[d] : lo[d];
+            hi[d] = h[d] > hi[d] ? h[d] : hi[d];
+        }
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 0; d < G; ++d) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double l2 = __shfl_down(lo[d], off, 64), h2 = __shfl_down(hi[d], off, 64);
+            lo[d] = l2 < lo[d] ? l2 : lo[d];
+            hi[d] = h2 > hi[d] ? h2 : hi[d];
+        }
+        if (lane == 0) { s_box[wv][d] = lo[d]; s_box[wv][G + d] = hi[d]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < G) {
+        const int d = threadIdx.x;
+        double l = s_box[0][d], h = s_box[0][G + d];
+#pragma unroll
+        for (int w = 1; w < TPB / WAVE; ++w) {
+            l = s_box[w][d] < l ? s_box[w][d] : l;
+            h = s_box[w][G + d] > h ? s_box[w][G + d] : h;
+        }
+        part[(int64_t)blockIdx.x * 2 * G + d] = l;
+        part[(int64_t)blockIdx.x * 2 * G + G + d] = h;
+    }
+}
+
+// cnt[b] += 1 for every bin b in the ranges of a cell; total: all registrations, in 64 bits (it decides whether the grid stands
+// before anything is sized by it)
+template <int G>
+__global__ __launch_bounds__(TPB) void k_index_count(const int4 *__restrict__ cells4, const int *__restrict__ cellsN, int nn,
+                                                     const double *__restrict__ coords, int64_t nv, int64_t nc, LocGrid g, int *__restrict__ cnt,
+                                                     unsigned long long *__restrict__ total) {
+    unsigned long long mine = 0;
+    for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < nc; e += (int64_t)gridDim.x * TPB) {
+        int r0[3], r1[3];
+        index_range<G>(cells4, cellsN, nn, coords, nv, e, g, r0, r1);
+        for (int bz = r0[2]; bz <= r1[2]; ++bz)
+            for (int by = r0[1]; by <= r1[1]; ++by)
+                for (int bx = r0[0]; bx <= r1[0]; ++bx) {
+                    atomicAdd(&cnt[bx + g.n[0] * (by + g.n[1] * bz)], 1);
+                    ++mine;
+                }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(total, mine);
+}
+
+// the same ranges from the same function; the order inside a bin is the order of arrival.  A registration past the end of its
+// bin's list cannot happen while count and fill agree - it is dropped, not stored, all the same
+template <int G>
+__global__ __launch_bounds__(TPB) void k_index_fill(const int4 *__restrict__ cells4, const int *__restrict__ cellsN, int nn,
+                                                    const double *__restrict__ coords, int64_t nv, int64_t nc, LocGrid g,
+                                                    const int *__restrict__ bin_ptr, int *__restrict__ cursor, int *__restrict__ bin_cells) {
+    for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < nc; e += (int64_t)gridDim.x * TPB) {
+        int r0[3], r1[3];
+        index_range<G>(cells4, cellsN, nn, coords, nv, e, g, r0, r1);
+        for (int bz = r0[2]; bz <= r1[2]; ++bz)
+            for (int by = r0[1]; by <= r1[1]; ++by)
+                for (int bx = r0[0]; bx <= r1[0]; ++bx) {
+                    const int b = bx + g.n[0] * (by + g.n[1] * bz);
+                    const int first = bin_ptr[b], len = bin_ptr[b + 1] - first;
+                    const int pos = atomicAdd(&cursor[b], 1);
+                    if (pos < len) bin_cells[first + pos] = (int)e;
+                }
+    }
+}
+
+__global__ __launch_bounds__(TPB) void k_index_longest(const int *__restrict__ cnt, int64_t nbins, int *__restrict__ longest) {
+    int m = 0;
+    for (int64_t b = (int64_t)blockIdx.x * TPB + threadIdx.x; b < nbins; b += (int64_t)gridDim.x * TPB) m = cnt[b] > m ? cnt[b] : m;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int m2 = __shfl_down(m, off, 64);
+        m = m2 > m ? m2 : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(longest, m);
+}
+
+// ---- the indexed path: a thread per point, the cells of the point's bin under the rule.  No LDS, no barrier, no atomics.
+// Why the bin's list suffices for tol <= LOC_INDEX_TOL (t below), on any mesh:
+// (a) The inflated box holds the point.  A cell with all exact lam_i >= -t and sum lam = 1: write lam_i = -t + mu_i, mu >= 0,
+//     sum mu = 1 + (G + 1) t.  Then x_a = sum lam_i v_ia = sum mu_i v_ia - t sum v_ia <= hi_a sum mu_i - t sum v_ia
+//     = hi_a + t sum_i (hi_a - v_ia) <= hi_a + (G + 1) t (hi_a - lo_a), and likewise x_a >= lo_a - (G + 1) t (hi_a - lo_a).
+// (b) The slack covers the rounding of cell_bary.  A COMPUTED minimum >= -tol means an exact minimum >= -tol - c u kappa(E), c a few
+//     tens (the error of the cofactor solve, relative to lam of order one): the margin is formed with LOC_INDEX_TOL + 2^-20 in
+//     place of t, which covers edge matrices of condition up to about 2^30 - THE LIMIT of this path; a mesh with worse cells keeps
+//     the general kernel.  (The margin itself and lo - m, hi + m round by a relative 2^-52, far inside the 2^-20.)
+// (c) Bins are monotone.  Subtracting a constant, multiplying by a non-negative constant, floor and the clamp are monotone in
+//     floating point, so lo' <= x <= hi' gives bin_of(lo') <= bin_of(x) <= bin_of(hi') on every axis - no epsilon, and also for a
+//     point that is clamped into the grid from outside the box: the bin of x is among those the cell was registered in.
+// (d) The winner is the general kernel's.  Every cell whose computed minimum is >= -tol is therefore in the list of the point's
+//     bin.  If the general kernel's winner has a minimum >= -tol, it is in the list, and so is every cell tied with it (the same
+//     minimum); the best pair over a subset that holds the overall best pair is that pair - loc_better is a total order, and the
+//     list is walked with it because the list is not ascending.  Otherwise no listed cell reaches -tol either (the list is a
+//     subset), and both paths store -1 and zeros.  A NaN or infinite coordinate fails every test in any bin, as in any cell.
+template <int G>
+__global__ __launch_bounds__(TPB) void k_locate_index(const int4 *__restrict__ cells4, const int *__restrict__ cellsN, int nn,
+                                                      const double *__restrict__ coords, int64_t nv, LocGrid g, const int *__restrict__ bin_ptr,
+                                                      const int *__restrict__ bin_cells, const double *__restrict__ pts, int64_t npts, double tol,
+                                                      int *__restrict__ cell_out, double *__restrict__ lam_out) {
+    const int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (p >= npts) return;
+    double x[G];
+    int q[3] = {0, 0, 0};
+#pragma unroll
+    for (int d = 0; d < G; ++d) {
+        x[d] = pts[p * G + d];
+        q[d] = bin_of(x[d], g.o[d], g.inv[d], g.n[d]);
+    }
+    const int b = q[0] + g.n[0] * (q[1] + g.n[1] * q[2]);
+    const int k1 = bin_ptr[b + 1];
+    double bm = LOC_NONE;
+    int be = -1;
+    for (int k = bin_ptr[b]; k < k1; ++k) {
+        const int e = bin_cells[k];
+        int v[G + 1];
+        double J[G][G], x0[G], lam[G + 1];
+        cell_vertices<G>(cells4, cellsN, nn, e, v);
+        if (!cell_map<G>(v, coords, nv, J, x0)) continue;
+        const double m = cell_bary<G>(J, x0, x, lam);
+        if (loc_better(m, e, bm, be)) { bm = m; be = e; }
+    }
+    locate_store<G>(cells4, cellsN, nn, coords, nv, x, bm, be, tol, cell_out + p, lam_out + p * (G + 1));
+}
+
 // ---- sampling: a thread per point, the components in a loop.  P2 shape functions l (2 l - 1) and 4 l_a l_b; the edge order of the
 // records (pgd_cell_gradient_p2; interval: the one edge (0, 1))
 __host__ __device__ constexpr int loc_nodes(int G, int deg) { return deg == 1 ? G + 1 : (G + 1) * (G + 2) / 2; }
@@ -432,6 +640,157 @@ static int locate_general(Ctx *c, const Mesh *b, const double *pts_dev, int64_t 
     return PGD_OK;
 }
 
+// ---- the bin index, host side
+// bins per axis from the number of cells and the extents of the box: about `target` cells per bin, bins as cubic as the box allows.
+// An axis without extent has one bin and inv = 0.  Plain double arithmetic, restated by the tests: pow, nearbyint
+static void index_grid(int G, int64_t nc, int64_t target, const double *lo, const double *top, LocGrid &g, double (&L)[3]) {
+    int live = 0;
+    double prod = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        L[a] = a < G ? top[a] - lo[a] : 0.0;
+        if (!(L[a] > 0.0) || !std::isfinite(L[a])) L[a] = 0.0;
+        g.o[a] = a < G ? lo[a] : 0.0;
+        g.n[a] = 1;
+        g.inv[a] = 0.0;
+        if (L[a] > 0.0) { ++live; prod *= L[a]; }
+    }
+    if (!live) return;
+    const double B = (double)nc / (double)target;
+    const double s = std::pow(B / prod, 1.0 / live);
+    for (int a = 0; a < 3; ++a) {
+        if (!(L[a] > 0.0)) continue;
+        double f = std::nearbyint(L[a] * s);
+        if (!(f >= 1.0)) f = 1.0;
+        if (f > 1073741824.0) f = 1073741824.0;
+        g.n[a] = (int)f;
+    }
+    while ((double)g.n[0] * g.n[1] * g.n[2] >= 2147483647.0)
+        for (int a = 0; a < 3; ++a) g.n[a] = g.n[a] > 1 ? g.n[a] / 2 : 1;
+    for (int a = 0; a < 3; ++a) g.inv[a] = L[a] > 0.0 ? (double)g.n[a] / L[a] : 0.0;
+}
+
+// builds Mesh::loc_index of the scalar layout b under the current target.  Everything is queued on c->stream; the host waits for
+// the box and for the number of registrations (once per coarsening).  On an error the mesh holds no index and no allocation of the build is left
+template <int G>
+static int index_build(Ctx *c, const Mesh *b) {
+    Mesh::LocIndex &ix = b->loc_index;
+    hipStream_t st = c->stream;
+    const int nn = b->cellsN ? b->nvpc : 0;
+    const int64_t nc = b->nc;
+    const int grid = grid_for(nc);
+    double *part = nullptr;
+    int *cnt = nullptr, *bin_ptr = nullptr, *bin_cells = nullptr;
+    unsigned long long *stats = nullptr;      // [0] registrations, [1] (as int) the longest list
+    size_t part_bytes = (size_t)grid * 2 * G * sizeof(double), cnt_bytes = 0;
+    auto cleanup = [&](int rc) {
+        (void)hipStreamSynchronize(st);
+        if (part) dev_release(c, part, part_bytes);
+        if (cnt) dev_release(c, cnt, cnt_bytes);
+        if (stats) (void)hipFree(stats);
+        if (rc != PGD_OK) {
+            if (bin_ptr) (void)hipFree(bin_ptr);
+            if (bin_cells) (void)hipFree(bin_cells);
+        }
+        return rc;
+    };
+#define PGD_IX(call)                                                                                                  \
+    do {                                                                                                              \
+        hipError_t e_ = (call);                                                                                       \
+        if (e_ != hipSuccess) return cleanup(fail(c, PGD_ERR_HIP, "points index: %s", hipGetErrorString(e_)));        \
+    } while (0)
+#define PGD_IX_TRY(call)                                \
+    do {                                                \
+        const int rc_ = (call);                         \
+        if (rc_ != PGD_OK) return cleanup(rc_);         \
+    } while (0)
+    void *q;
+    PGD_IX_TRY(dev_alloc(c, &q, part_bytes)); part = (double *)q;
+    PGD_IX_TRY(dev_alloc(c, &q, 2 * sizeof(unsigned long long))); stats = (unsigned long long *)q;
+    k_index_bounds<G><<<grid, TPB, 0, st>>>(b->cells, b->cellsN, nn, b->coords, b->nv, nc, part);
+    PGD_IX(hipGetLastError());
+    std::vector<double> rows((size_t)grid * 2 * G);
+    PGD_IX(hipMemcpyAsync(rows.data(), part, part_bytes, hipMemcpyDeviceToHost, st));
+    PGD_IX(hipStreamSynchronize(st));
+    double lo[3] = {0, 0, 0}, top[3] = {0, 0, 0};
+    for (int d = 0; d < G; ++d) {
+        lo[d] = rows[d]; top[d] = rows[G + d];
+        for (int r = 1; r < grid; ++r) {
+            const double l = rows[(size_t)r * 2 * G + d], h = rows[(size_t)r * 2 * G + G + d];
+            lo[d] = l < lo[d] ? l : lo[d];
+            top[d] = h > top[d] ? h : top[d];
+        }
+    }
+    const int64_t knob = c->locate_index_target;
+    const int64_t target = knob > 0 ? knob : (G == 3 ? LOC_INDEX_TARGET_3D : LOC_INDEX_TARGET_2D);
+    LocGrid g;
+    double L[3];
+    index_grid(G, nc, target, lo, top, g, L);
+    int64_t bins = (int64_t)g.n[0] * g.n[1] * g.n[2];
+    cnt_bytes = (size_t)(bins + 1) * sizeof(int);      // (coarsening only shrinks the grid: sized once)
+    PGD_IX_TRY(dev_alloc(c, &q, cnt_bytes)); cnt = (int *)q;
+    unsigned long long total = 0;
+    for (;;) {
+        bins = (int64_t)g.n[0] * g.n[1] * g.n[2];
+        PGD_IX(hipMemsetAsync(cnt, 0, (size_t)(bins + 1) * sizeof(int), st));
+        PGD_IX(hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), st));
+        k_index_count<G><<<grid, TPB, 0, st>>>(b->cells, b->cellsN, nn, b->coords, b->nv, nc, g, cnt, stats);
+        PGD_IX(hipGetLastError());
+        PGD_IX(hipMemcpyAsync(&total, stats, sizeof total, hipMemcpyDeviceToHost, st));
+        PGD_IX(hipStreamSynchronize(st));
+        if (total <= (unsigned long long)(LOC_INDEX_CAP * nc) && total <= 2147483647ull) break;
+        if (bins == 1) return cleanup(fail(c, PGD_ERR_LIMIT, "points index: %llu registrations in one bin", total));      // (nc < 2^31: not reached)
+        for (int a = 0; a < 3; ++a) {
+            g.n[a] = g.n[a] > 1 ? g.n[a] / 2 : 1;
+            g.inv[a] = L[a] > 0.0 ? (double)g.n[a] / L[a] : 0.0;
+        }
+    }
+    const size_t ptr_bytes = (size_t)(bins + 1) * sizeof(int), list_bytes = (size_t)(total > 0 ? total : 1) * sizeof(int);
+    PGD_IX_TRY(dev_alloc(c, &q, ptr_bytes)); bin_ptr = (int *)q;
+    PGD_IX_TRY(dev_alloc(c, &q, list_bytes)); bin_cells = (int *)q;
+    PGD_IX_TRY(scan_exclusive_i32(c, cnt, bin_ptr, bins));
+    k_index_longest<<<grid_for(bins), TPB, 0, st>>>(cnt, bins, (int *)(stats + 1));
+    PGD_IX(hipMemsetAsync(cnt, 0, (size_t)(bins + 1) * sizeof(int), st));
+    PGD_IX(hipMemsetAsync(bin_cells, 0, list_bytes, st));
+    k_index_fill<G><<<grid, TPB, 0, st>>>(b->cells, b->cellsN, nn, b->coords, b->nv, nc, g, bin_ptr, cnt, bin_cells);
+    PGD_IX(hipGetLastError());
+    int longest = 0;
+    PGD_IX(hipMemcpyAsync(&longest, stats + 1, sizeof longest, hipMemcpyDeviceToHost, st));
+    PGD_IX(hipStreamSynchronize(st));
+#undef PGD_IX
+#undef PGD_IX_TRY
+    for (int a = 0; a < 3; ++a) { ix.o[a] = g.o[a]; ix.inv[a] = g.inv[a]; ix.n[a] = g.n[a]; }
+    ix.bin_ptr = bin_ptr; ix.bin_cells = bin_cells;
+    ix.bins = bins; ix.entries = (int64_t)total; ix.longest = longest;
+    ix.bytes = ptr_bytes + list_bytes;
+    ix.target = knob;
+    ix.built = true;
+    ++ix.builds;
+    return cleanup(PGD_OK);
+}
+
+// the index of b under the current target: the one it holds, or a new one
+static int index_ensure(Ctx *c, const Mesh *b) {
+    Mesh::LocIndex &ix = b->loc_index;
+    if (ix.built && ix.target == c->locate_index_target) return PGD_OK;
+    if (ix.built) {
+        (void)hipStreamSynchronize(c->stream);
+        ix.release();
+    }
+    return b->gdim == 2 ? index_build<2>(c, b) : index_build<3>(c, b);
+}
+
+template <int G>
+static int locate_index(Ctx *c, const Mesh *b, const double *pts_dev, int64_t npts, double tol, Points *P) {
+    const Mesh::LocIndex &ix = b->loc_index;
+    LocGrid g;
+    for (int a = 0; a < 3; ++a) { g.o[a] = ix.o[a]; g.inv[a] = ix.inv[a]; g.n[a] = ix.n[a]; }
+    k_locate_index<G><<<(int)((npts + TPB - 1) / TPB), TPB, 0, c->stream>>>(b->cells, b->cellsN, b->cellsN ? b->nvpc : 0, b->coords, b->nv, g, ix.bin_ptr,
+                                                                           ix.bin_cells, pts_dev, npts, tol, P->cells, P->lam);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, PGD_ERR_HIP, "points_locate: launch failed: %s", hipGetErrorString(e));
+    return PGD_OK;
+}
+
 // the host's copy of the cells decides what pgd_points_sample may do with the set
 static int points_scan(Ctx *c, Points *P) {
     P->first_outside = -1;
@@ -478,6 +837,10 @@ int pgd_points_locate(pgd_handle h, pgd_handle mh, const double *pts, int64_t np
                 e = hipGetLastError();
                 if (e != hipSuccess) rc = fail(c, PGD_ERR_HIP, "points_locate: launch failed: %s", hipGetErrorString(e));
                 c->locate_last_path = 2;
+            } else if (c->locate_index && (G == 2 || G == 3) && tol <= LOC_INDEX_TOL) {
+                rc = index_ensure(c, b);
+                if (rc == PGD_OK) rc = G == 2 ? locate_index<2>(c, b, pts_dev, npts, tol, P.get()) : locate_index<3>(c, b, pts_dev, npts, tol, P.get());
+                c->locate_last_path = 3;
             } else {
                 rc = G == 1 ? locate_general<1>(c, b, pts_dev, npts, tol, P.get()) : G == 2 ? locate_general<2>(c, b, pts_dev, npts, tol, P.get())
                                                                                             : locate_general<3>(c, b, pts_dev, npts, tol, P.get());
@@ -541,6 +904,48 @@ int pgd_points_last_path(pgd_handle h, int *path) {
     PGD_CTX(c, h);
     if (!path) return fail(c, PGD_ERR_INVALID, "points_last_path: null output");
     *path = c->locate_last_path;
+    return PGD_OK;
+}
+
+int pgd_points_index_info(pgd_handle h, pgd_handle mh, int64_t *out) {
+    PGD_CTX(c, h);
+    const Mesh *b = points_base(c, "points_index_info", mh, nullptr);
+    if (!b) return PGD_ERR_INVALID;
+    if (!out) return fail(c, PGD_ERR_INVALID, "points_index_info: null output");
+    const Mesh::LocIndex &ix = b->loc_index;
+    out[0] = ix.built ? 1 : 0;
+    out[1] = ix.builds;
+    for (int a = 0; a < 3; ++a) out[2 + a] = ix.built ? ix.n[a] : 0;
+    out[5] = ix.entries;
+    out[6] = ix.longest;
+    out[7] = (int64_t)ix.bytes;
+    return PGD_OK;
+}
+
+int pgd_points_index_download(pgd_handle h, pgd_handle mh, int32_t *bin_ptr, int32_t *bin_cells, double *geom) {
+    PGD_CTX(c, h);
+    const Mesh *b = points_base(c, "points_index_download", mh, nullptr);
+    if (!b) return PGD_ERR_INVALID;
+    const Mesh::LocIndex &ix = b->loc_index;
+    if (!ix.built) return fail(c, PGD_ERR_INVALID, "points_index_download: the mesh holds no index");
+    if (bin_ptr) PGD_HIP(c, hipMemcpyAsync(bin_ptr, ix.bin_ptr, (size_t)(ix.bins + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (bin_cells && ix.entries > 0)
+        PGD_HIP(c, hipMemcpyAsync(bin_cells, ix.bin_cells, (size_t)ix.entries * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    PGD_HIP(c, hipStreamSynchronize(c->stream));
+    if (geom)
+        for (int a = 0; a < 3; ++a) { geom[a] = ix.o[a]; geom[3 + a] = ix.inv[a]; geom[6 + a] = (double)ix.n[a]; }
+    return PGD_OK;
+}
+
+int pgd_points_index_drop(pgd_handle h, pgd_handle mh) {
+    PGD_CTX(c, h);
+    const Mesh *b = points_base(c, "points_index_drop", mh, nullptr);
+    if (!b) return PGD_ERR_INVALID;
+    if (b->loc_index.built) {
+        (void)hipStreamSynchronize(c->stream);      // (the arrays go straight back to HIP)
+        b->loc_index.release();
+    }
+    b->loc_index.builds = 0;
     return PGD_OK;
 }
 

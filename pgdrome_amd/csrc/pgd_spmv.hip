@@ -2708,6 +2708,8 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_SPMV_P2_LATTICE && value >= 0 && value <= 1) { c->spmv_p2_lattice = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_LOCATE_LATTICE && value >= 0 && value <= 1) { c->locate_lattice = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_LOCATE_GRID_MAX && value >= 0 && value <= 1 << 20) { c->locate_grid_max = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_LOCATE_INDEX && value >= 0 && value <= 1) { c->locate_index = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_LOCATE_INDEX_TARGET && value >= 0 && value <= 0x7fffffff) { c->locate_index_target = value; return PGD_OK; }
     if (knob == PGD_TUNE_GRAM_VARIANT && value >= 0 && value <= 1) { c->gram_variant = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_GRAM_GRID_MAX && value >= 0 && value <= 1 << 20) { c->gram_grid_max = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_QUAD_VARIANT && value >= 0 && value <= 1) { c->quad_variant = (int)value; return PGD_OK; }

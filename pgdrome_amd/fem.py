@@ -1992,9 +1992,10 @@ class LocatedPoints:
     """Cells (int32, (P,)) and barycentric coordinates ((P, D + 1)) of a set of points of a mesh; ``handle``: the library's point set
     on ``backend`` where the device located them (None on the host path).  ``key``: the digest the mesh caches it under."""
 
-    def __init__(self, mesh, points, cells, lam, key, backend=None, handle=None):
+    def __init__(self, mesh, points, cells, lam, key, backend=None, handle=None, path="host"):
         self.mesh, self.points, self.cells, self.lam, self.key = mesh, points, cells, lam, key
         self.backend, self.handle = backend, handle
+        self.path = path      # what located them: "host", or the library's "general", "lattice" or "index" (the same cells and lam)
 
     def grad_lambda(self):
         """g (P, D + 1, D): the gradients of the barycentric coordinates in the points' cells (rows of Tinv, and minus their sum)."""
@@ -2023,6 +2024,12 @@ class LocatedPoints:
 _LOCATED_MESHES = weakref.WeakSet()      # meshes that hold located point sets (clear_caches frees their device handles)
 SENSOR_CACHES = weakref.WeakSet()        # model.PGD objects that hold sampled modes (PGD.sensor_modes): clear_caches empties their dictionaries
 LOCATE_CHUNK_ENTRIES = 1 << 21           # host location: points x cells per chunk (the 96 bytes per cell are per chunk, not per mesh)
+# locate_points(index=None) builds the bin index of a mesh from this many points x cells on: the smallest measured size at which
+# the FIRST indexed call, build included, beats the general kernel by more than the spread of the rounds, rounded up to a power of
+# ten (profiles/locate_index_bench_n1.jsonl: 1.6e10 - 10^4 points on 1.6 M cells, 1.9 ms against 106 ms - is the smallest such size
+# measured; the three sizes up to 1.0e10, all with 100 points, lose to the general kernel by the time of the build)
+LOCATE_INDEX_MIN_WORK = 1e11
+_LOCATE_PATHS = {1: "general", 2: "lattice", 3: "index"}      # pgd_points_last_path
 
 
 def _locate_host(mesh, pts):
@@ -2046,14 +2053,23 @@ def _locate_host(mesh, pts):
     return where, lam, best
 
 
-def locate_points(mesh, points, tol=1e-10, device=None):
+def locate_points(mesh, points, tol=1e-10, device=None, index=None):
     """The cells and barycentric coordinates of many points of a mesh at once: a ``LocatedPoints``.  The cell of a point is the one
     with the largest smallest barycentric coordinate, the lowest cell among equal ones (``point_basis``'s choice).
 
     device=None: on the device where the backend locates points (pgd_points_locate on the P1 layout; the set stays there for
     ``points_sample``), else on the host; device=False: on the host - ``point_basis``'s own arithmetic over all points and chunks of
     cells, giving its cells and its lam bit for bit.  A point whose best cell has a barycentric coordinate below -tol (or a NaN
-    coordinate) raises ValueError naming the first such point.  Cached on the mesh per (point bytes, tol, path)."""
+    coordinate) raises ValueError naming the first such point.  Cached on the mesh per (point bytes, tol, path).
+
+    index: whether the device tests a point against the cells of its bin of a uniform grid over the mesh (pgd_points_locate under
+    PGD_TUNE_LOCATE_INDEX; built by the first such call and kept with the mesh) instead of against every cell: True / False decide,
+    None indexes where the mesh holds an index already or points x cells >= LOCATE_INDEX_MIN_WORK.  The same cells and lam, bit for
+    bit, so the cache does not tell the two apart; ``path`` of the result says what ran.  The library uses the index in 2-D and 3-D for
+    tol <= 2^-10 where no lattice path applies, and the general kernel elsewhere.  index=True on the host path or on a backend without
+    the index is a NotImplementedError."""
+    if index is not None and index is not True and index is not False:
+        raise ValueError("locate_points: index = %r (True, False or None)" % (index,))
     if getattr(mesh, "part", None) is not None:
         raise NotImplementedError("locate_points on a row-sharded mesh (every rank holds a slab of the cells)")
     D = mesh.geometry().dim()
@@ -2065,6 +2081,10 @@ def locate_points(mesh, points, tol=1e-10, device=None):
     on_device = hasattr(be, "points_locate") if device is None else bool(device)
     if on_device and not hasattr(be, "points_locate"):
         raise NotImplementedError("locate_points(device=True): the backend %r locates no points" % (getattr(be, "name", be),))
+    can_index = on_device and hasattr(be, "points_index_info")
+    if index is True and not can_index:
+        raise NotImplementedError("locate_points(index=True): %s" % ("the host path has no index" if not on_device else
+                                                                     "the backend %r has no point index" % (getattr(be, "name", be),)))
     key = (hashlib.blake2b(pts.tobytes(), digest_size=16).hexdigest(), pts.shape[0], tol, on_device)
     cache = mesh.__dict__.setdefault("_located", {})
     hit = cache.get(key)
@@ -2072,9 +2092,20 @@ def locate_points(mesh, points, tol=1e-10, device=None):
         if not on_device or hit.backend is be:
             return hit
         cache.pop(key).free()                    # located on a backend that is no longer the current one: again, on this one
-    handle = None
+    handle, path = None, "host"
     if on_device:
-        handle = be.points_locate(mesh.layout(1).handle(), pts, tol)
+        mh = mesh.layout(1).handle()
+        if can_index:
+            use = index if index is not None else bool(be.points_index_info(mh)["built"]) or pts.shape[0] * mesh.num_cells() >= LOCATE_INDEX_MIN_WORK
+            if use:
+                held = mesh.__dict__.setdefault("_index_on", [])      # clear_caches drops the index there
+                if not any(b is be for b in held):
+                    held.append(be)
+                _LOCATED_MESHES.add(mesh)
+            handle = be.points_locate(mh, pts, tol, index=bool(use))
+        else:
+            handle = be.points_locate(mh, pts, tol)
+        path = _LOCATE_PATHS.get(be.points_last_path(), "general") if hasattr(be, "points_last_path") else "general"
         cells, lam = be.points_download(handle)
         bad = cells < 0
     else:
@@ -2085,7 +2116,7 @@ def locate_points(mesh, points, tol=1e-10, device=None):
             be.points_free(handle)
         i = int(np.argmax(bad))
         raise ValueError("point %d (%r) outside the mesh" % (i, pts[i]))
-    out = LocatedPoints(mesh, pts, cells.astype(np.int32), lam, key, be if on_device else None, handle)
+    out = LocatedPoints(mesh, pts, cells.astype(np.int32), lam, key, be if on_device else None, handle, path)
     cache[key] = out
     _LOCATED_MESHES.add(mesh)
     return out
@@ -4177,6 +4208,13 @@ def clear_caches():
     for mesh in list(_LOCATED_MESHES):          # located point sets: the cache entries go, and the library's point sets with them
         for located in mesh.__dict__.pop("_located", {}).values():
             located.free()
+        for be in mesh.__dict__.pop("_index_on", []):      # ... and the bin indexes that locate_points(index=...) had built
+            h = mesh.layout(1)._handles.get(id(be))
+            if h is not None:
+                try:
+                    be.points_index_drop(h)
+                except Exception:
+                    pass
     _LOCATED_MESHES.clear()
     for sol in list(SENSOR_CACHES):
         sol.__dict__.pop("_sensor_modes", None)

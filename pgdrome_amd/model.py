@@ -1792,13 +1792,14 @@ class PGD:
         return self._contract_modes(self.eval_fixed_modes(sensor_points, fixed_dim, attri), c)
 
     # ------------------------------------------------------ sensor responses for many samples
-    def sensor_modes(self, sensor_points, fixed_dim, attri, gradient=False, device=None):
+    def sensor_modes(self, sensor_points, fixed_dim, attri, gradient=False, device=None, index=None):
         """ALL ``numModes`` modes of the fixed dimension (``gradient``: their spatial gradients) at the sensor points: a
         ``SensorModes`` of entries (point, component[, axis]) per mode.  The points are located once (``fem.locate_points``).  Where
         the backend samples point sets (``device=None``: then) every mode is sampled on the device into a vector of P * nc (* gdim)
         entries (pgd_points_sample) and no mode is downloaded; otherwise - the numpy backend, ``device=False`` - one gather and one
         contraction over all modes on the host.  The gradient at a point on a face is that of the cell the location chose.
-        Cached per (point set, fixed_dim, attri, gradient, path)."""
+        Cached per (point set, fixed_dim, attri, gradient, path).  ``index``: handed to ``fem.locate_points`` (the bin index of the mesh:
+        the same cells and coordinates, located faster for many points on a mesh that is no lattice)."""
         modes = self.mesh[fixed_dim].attributes[attri].interpolationfct
         if len(modes) < self.numModes or not all(isinstance(m, fem.Function) for m in modes[:self.numModes]):
             raise ValueError("sensor_modes: the modes of dimension %d are no Functions (interp1d modes have no mesh to locate points on)"
@@ -1813,7 +1814,7 @@ class PGD:
         on_device = hasattr(be, "points_sample") if device is None else bool(device)
         if on_device and not hasattr(be, "points_sample"):
             raise NotImplementedError("sensor_modes(device=True): the backend %r samples no point sets" % (getattr(be, "name", be),))
-        located = fem.locate_points(mesh, sensor_points, device=True if on_device else False)
+        located = fem.locate_points(mesh, sensor_points, device=True if on_device else False, index=index)
         key = (located.key, fixed_dim, attri, bool(gradient), on_device)
         cache = self.__dict__.setdefault("_sensor_modes", {})
         fem.SENSOR_CACHES.add(self)              # fem.clear_caches empties the dictionary (the sampled vectors are freed with it)
@@ -1921,7 +1922,7 @@ class PGD:
         return out
 
     def evaluate_sensor_response_many(self, fixed_dim, free_dim, coords, attri, sensor_points, d_dim=None, gradient=False,
-                                      stats=False, device=None):
+                                      stats=False, device=None, index=None):
         """``evaluate_sensor_response`` for S coordinate sets of the free dimensions at once, with the parameter Jacobian: the
         modes are sampled at the points once (``sensor_modes``), the samples are one product with ``mode_factors_many``.
 
@@ -1929,7 +1930,8 @@ class PGD:
         trailing gdim axis when ``gradient`` (the spatial gradient at the points); ``jacobian``: when ``d_dim`` (a free dimension
         or a list of them) is given, the derivatives of ``values`` with respect to those coordinates on a trailing len(d_dim)
         axis; ``coefficients`` = C (used_numModes, S); with ``stats`` ``min`` / ``max`` / ``max_abs`` of ``values`` per sample.
-        The product is numpy below DEVICE_EVAL_MIN_DOFS entries per sample, ``pgd_eval_batch`` on the sampled vectors above."""
+        The product is numpy below DEVICE_EVAL_MIN_DOFS entries per sample, ``pgd_eval_batch`` on the sampled vectors above.
+        ``index``: handed to ``sensor_modes``."""
         coords = self._check_many(fixed_dim, free_dim, coords, attri)
         S, K = coords.shape[0], self.used_numModes
         if self.mesh[free_dim[0]].attributes[attri].interpolationInfo["name"] == 0:
@@ -1939,7 +1941,7 @@ class PGD:
             for d in dims:
                 if d == fixed_dim or d not in list(free_dim):
                     raise ValueError("derivation against fixed dim not possible in the moment")
-        sm = self.sensor_modes(sensor_points, fixed_dim, attri, gradient=gradient, device=device)
+        sm = self.sensor_modes(sensor_points, fixed_dim, attri, gradient=gradient, device=device, index=index)
         C = self.mode_factors_many(free_dim, coords, attri)
         res = SensorManyResult()
         res.coefficients = C

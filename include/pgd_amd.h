@@ -487,6 +487,42 @@ int pgd_quad_forms(pgd_handle ctx, const pgd_handle *modes, int k, const double 
  * where the variance is above a floor.  PGD_ERR_INVALID: invalid handles, different lengths, a NaN floor.  No synchronisation. */
 int pgd_vec_ratio(pgd_handle ctx, pgd_handle out, pgd_handle num, pgd_handle den, double floor);
 
+/* Misfits of sensor data on a tensor grid of the free coordinates: chi2[s] = sum_p (y_p - sum_t a[p * k + t] c_t(s))^2 for every
+ * sample s = (i_0 .. i_{ndim-1}), last index fastest, S = prod n[d] of them, with c_t(s) = 1 * T_0[t, i_0] * T_1[t, i_1] * .. formed
+ * in ascending d where it is used (the bits of model.py's mode_factors_many on the same tables): the K x S coefficient matrix is
+ * never stored.  a: m x k row-major on the host (the whitened sensor modes), y: m values (the whitened data), tables: the ndim
+ * tables one after the other, table d being k x n[d] row-major, n: ndim point counts; chi2: a vector of S entries.  min_out /
+ * argmin_out (either may be NULL): the smallest chi2 and the lowest sample that holds it (-1 if no value compares: all NaN).
+ * 1 <= k <= 256, 1 <= m <= 256, 1 <= ndim <= 6, S < 2^31.  v_mfma_f64_16x16x4_f64 with 16 samples on the fragment's column index as
+ * in pgd_eval_batch and pgd_quad_forms, a laid out in fragment order by the library: a wave owns its samples, each chi2 value is
+ * one fixed chain and the minimum does not depend on order - every output is bit-identical for any grid
+ * (PGD_TUNE_MISFIT_GRID_MAX).  PGD_TUNE_MISFIT_VARIANT = 0: plain fma chains.  ONE host synchronisation.  PGD_ERR_INVALID with a
+ * message, before anything is launched and with the outputs untouched: a null a, y, tables or n, k, m or ndim out of range, a
+ * dimension without points, S >= 2^31, chi2 not a vector or not of S entries.  Scattered samples are one dimension whose table
+ * is the k x S coefficient matrix itself.                                                                                     */
+int pgd_grid_misfit(pgd_handle ctx, const double *a, const double *y, int m, int k, const double *tables, const int *n, int ndim,
+                    pgd_handle chi2, double *min_out, int64_t *argmin_out);
+/* Reductions of the posterior over those misfits: with e_s = w_s exp(-(chi2[s] - shift) / 2), w_s = 1 * weights_0[i_0] * weights_1[i_1] * ..
+ * (weights, abscissae: the ndim arrays of n[d] entries one after the other; tables, n, ndim, k as in pgd_grid_misfit),
+ *   sums[0] = Z = sum e_s, sums[1] = sum e_s^2                                                         (always)
+ *   PGD_POST_MARGINALS: marginals[off_d + i] = the sum of e_s over the samples with i_d = i, off_d = n[0] + .. + n[d-1]
+ *   PGD_POST_THETA:     theta1[d] = sum e_s th_d, theta2[d * ndim + f] = sum e_s th_d th_f, th_d = abscissae_d[i_d]
+ *   PGD_POST_COEF:      coef1[t] = sum e_s c_t(s), coef2[t * k + u] = sum e_s c_t(s) c_u(s) - a product over the samples on the
+ *                       matrix unit, 1 <= k <= 64 (PGD_ERR_INVALID above); symmetric bit for bit (the upper triangle, mirrored).
+ * Outputs that are not asked for, and tables / abscissae they alone need, may be NULL (k is ignored without PGD_POST_COEF).  No
+ * floating-point atomics: the samples are cut into at most 1024 segments that depend on S alone, a segment's partial sums are
+ * formed in an order that depends on the segment alone and the segments are added in ascending order; an entry of the
+ * marginals is summed by one workgroup in a fixed order - every output is bit-identical from run to run and for any grid
+ * (PGD_TUNE_POST_GRID_MAX).  PGD_TUNE_POST_VARIANT = 0: the coefficient moments from plain fma chains.  ONE host synchronisation.
+ * PGD_ERR_INVALID with a message, before anything is launched and with the outputs untouched: unknown bits in want, a shift that
+ * is not finite, ndim out of range, a null n, weights or sums, a requested output (or what it needs) that is missing, k out of
+ * range with PGD_POST_COEF, a dimension without points, S >= 2^31, chi2 not a vector or not of S entries.  A shift equal to the
+ * smallest chi2 keeps Z >= the weight of that sample however far off the others are (their e underflows to 0).             */
+enum { PGD_POST_MARGINALS = 1, PGD_POST_THETA = 2, PGD_POST_COEF = 4 };
+int pgd_grid_posterior(pgd_handle ctx, pgd_handle chi2, double shift, const double *tables, const int *n, int ndim, int k,
+                       const double *weights, const double *abscissae, int want, double *sums, double *marginals, double *theta1,
+                       double *theta2, double *coef1, double *coef2);
+
 /* ------------------------------------------------------------ column blocks --- */
 /* k <= 64 columns of n rows in ONE library-owned allocation, stored as fp32 or f64: the start space of the spatial solves
  * (pgdrome_amd/spectral.py; this library's addition in front of the solve that replaces solver.py:636,716), whose cost per
@@ -714,6 +750,14 @@ int pgd_points_free(pgd_handle ctx, pgd_handle points);
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_POST_GRID_MAX = 71, /* pgd_grid_posterior: > 0: at most this many (persistent) workgroups per kernel; 0 (default): four per CU.  The
+                                same bits either way: the segments and the order of their partials do not depend on the grid. */
+    PGD_TUNE_POST_VARIANT = 70, /* pgd_grid_posterior, PGD_POST_COEF: 1 (default) the product over the samples on the f64 matrix unit
+                                (k_post_coef_mfma), 0 ordinary fma chains (k_post_coef_plain): the cross-check and the baseline. */
+    PGD_TUNE_MISFIT_GRID_MAX = 69, /* pgd_grid_misfit: > 0: at most this many (persistent) workgroups; 0 (default): as many as are resident at
+                                once.  The same bits either way. */
+    PGD_TUNE_MISFIT_VARIANT = 68, /* pgd_grid_misfit: 1 (default) the product on the f64 matrix unit (k_misfit_mfma), 0 ordinary fma chains
+                                (k_misfit_plain): the cross-check and the baseline. */
     PGD_TUNE_LOCATE_INDEX_TARGET = 67, /* the bin index of pgd_points_locate: > 0: this many cells per bin; 0 (default): 48 in 3-D, 8 in 2-D.  A
                                 call under another value than the index of the mesh was built with rebuilds it.  Same cells and lam. */
     PGD_TUNE_LOCATE_INDEX = 66, /* 1: pgd_points_locate on a 2-D or 3-D mesh with tol <= 2^-10, where the lattice path does not apply, tests a

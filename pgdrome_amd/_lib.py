@@ -106,6 +106,8 @@ SIGNATURES = {
     "pgd_vec_multidot_pair": (C.c_int, [H, H, H, PH, C.c_int, I64, I64, PD]),
     "pgd_vec_gram": (C.c_int, [H, PH, C.c_int, PH, C.c_int, I64, I64, PD]),
     "pgd_quad_forms": (C.c_int, [H, PH, C.c_int, PD, C.c_int, C.c_int, PH, PD]),
+    "pgd_grid_misfit": (C.c_int, [H, PD, PD, C.c_int, C.c_int, PD, PI32, C.c_int, H, PD, PI64]),
+    "pgd_grid_posterior": (C.c_int, [H, H, F64, PD, PI32, C.c_int, C.c_int, PD, PD, C.c_int, PD, PD, PD, PD, PD, PD]),
     "pgd_vec_ratio": (C.c_int, [H, H, H, H, C.c_double]),
     "pgd_pcg_solve": (C.c_int, [H, H, H, H, F64, F64, C.c_int, C.POINTER(C.c_int), PD]),
     "pgd_pcg_last_form": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -196,6 +198,9 @@ GRAM_KMAX = 128            # vectors per side and call of pgd_vec_gram
 TUNE_QUAD_VARIANT, TUNE_QUAD_GRID_MAX = 64, 65
 QUAD_KMAX, QUAD_NQMAX = 256, 64   # modes and forms per call of pgd_quad_forms
 QUAD_CLAMP = 1
+TUNE_MISFIT_VARIANT, TUNE_MISFIT_GRID_MAX, TUNE_POST_VARIANT, TUNE_POST_GRID_MAX = 68, 69, 70, 71
+POST_KMAX, POST_MMAX, POST_DMAX, POST_COEF_KMAX = 256, 256, 6, 64   # modes, rows and dimensions of pgd_grid_misfit; modes of PGD_POST_COEF
+POST_MARGINALS, POST_THETA, POST_COEF = 1, 2, 4                     # PGD_POST_* (include/pgd_amd.h)
 LOCATE_TILE = 32                                    # points per launch of the general location kernel (LOC_PT, csrc/pgd_locate.hip)
 LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE = 1, 2     # pgd_points_last_path
 LOCATE_PATH_INDEX = 3                               # ... the bin index (TUNE_LOCATE_INDEX)
@@ -727,6 +732,71 @@ class Context:
             mn[q0:q0 + len(ob)] = ext[0::2]
             mx[q0:q0 + len(ob)] = ext[1::2]
         return mn, mx
+
+    @staticmethod
+    def _grid_tables(tables, k):
+        """(concatenated tables, n): the k x n[d] tables of a grid one after the other, as the two grid calls take them."""
+        tables = [np.ascontiguousarray(t, dtype=np.float64) for t in tables]
+        for d, t in enumerate(tables):
+            if t.ndim != 2 or t.shape[0] != k:
+                raise ValueError(f"grid tables: table {d} has shape {t.shape}, ({k}, n) is needed")
+        n = np.array([t.shape[1] for t in tables], dtype=np.int32)
+        flat = tables[0].reshape(-1) if len(tables) == 1 else np.concatenate([t.reshape(-1) for t in tables])    # (one table: no copy)
+        return np.ascontiguousarray(flat), n
+
+    def grid_misfit(self, a, y, tables, chi2):
+        """pgd_grid_misfit: chi2[s] = |y - a c(s)|^2 on the tensor grid of the ``tables`` (one (k, n[d]) array per dimension, last
+        dimension fastest) into the vector ``chi2`` of prod n[d] entries.  Returns (min, lowest index of the min)."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if a.ndim != 2 or a.shape[0] != y.size:
+            raise ValueError(f"grid_misfit: a has shape {a.shape} for {y.size} data")
+        m, k = a.shape
+        flat, n = self._grid_tables(tables, k)
+        mn, arg = F64(0.0), I64(0)
+        self._ck(self.lib.pgd_grid_misfit(self.h, dptr(a), dptr(y), m, k, dptr(flat), iptr(n), len(n), chi2, C.byref(mn), C.byref(arg)))
+        return mn.value, arg.value
+
+    def grid_posterior(self, chi2, shift, n, weights, tables=None, abscissae=None, want=0):
+        """pgd_grid_posterior: the sums of e_s = w_s exp(-(chi2[s] - shift) / 2) over the grid of ``n`` points per dimension;
+        ``weights`` / ``abscissae``: one array per dimension, ``tables`` as in ``grid_misfit`` (only for POST_COEF).  Returns a dict:
+        "Z", "sum_e2", and per bit of ``want`` "marginals" (a list of arrays), "theta1", "theta2", "coef1", "coef2"."""
+        n = np.ascontiguousarray(n, dtype=np.int32).reshape(-1)
+        nd = len(n)
+        cat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1) for x in xs]))
+        w = cat(weights)
+        if len(weights) != nd or w.size != int(n.sum()):
+            raise ValueError("grid_posterior: the weights do not match n")
+        none = C.cast(None, PD)
+        x = none
+        if want & POST_THETA:
+            xa = cat(abscissae)
+            if len(abscissae) != nd or xa.size != w.size:
+                raise ValueError("grid_posterior: the abscissae do not match n")
+            x = dptr(xa)
+        k, t = 0, none
+        if want & POST_COEF:
+            k = int(np.asarray(tables[0]).shape[0])
+            flat, nt = self._grid_tables(tables, k)
+            if not np.array_equal(nt, n):
+                raise ValueError("grid_posterior: the tables do not match n")
+            t = dptr(flat)
+        sums = np.zeros(2)
+        marg = np.zeros(w.size if want & POST_MARGINALS else 0)
+        th1, th2 = np.zeros(nd), np.zeros((nd, nd))
+        c1, c2 = np.zeros(k), np.zeros((k, k))
+        opt = lambda arr, bit: dptr(arr) if want & bit else none
+        self._ck(self.lib.pgd_grid_posterior(self.h, chi2, float(shift), t, iptr(n), nd, k, dptr(w), x, int(want), dptr(sums),
+                                             opt(marg, POST_MARGINALS), opt(th1, POST_THETA), opt(th2, POST_THETA),
+                                             opt(c1, POST_COEF), opt(c2, POST_COEF)))
+        out = {"Z": float(sums[0]), "sum_e2": float(sums[1])}
+        if want & POST_MARGINALS:
+            out["marginals"] = np.split(marg, np.cumsum(n)[:-1])
+        if want & POST_THETA:
+            out["theta1"], out["theta2"] = th1, th2
+        if want & POST_COEF:
+            out["coef1"], out["coef2"] = c1, c2
+        return out
 
     def vec_ratio(self, out, num, den, floor=0.0):
         """pgd_vec_ratio: out = num / den where den > floor, 0 elsewhere (``out`` may be ``num``)."""

@@ -438,6 +438,9 @@ struct Ctx {
     int gram_variant = 1, gram_grid_max = 0;
     // pgd_quad_forms (pgd_quad.hip): kernel variant (1 MFMA, 0 plain fma chains; PGD_TUNE_QUAD_VARIANT) and grid cap (PGD_TUNE_QUAD_GRID_MAX; 0: what is resident at once)
     int quad_variant = 1, quad_grid_max = 0;
+    // pgd_grid_misfit / pgd_grid_posterior (pgd_post.hip): kernel variants (1 MFMA, 0 plain fma chains; PGD_TUNE_MISFIT_VARIANT, PGD_TUNE_POST_VARIANT)
+    // and grid caps (PGD_TUNE_MISFIT_GRID_MAX, PGD_TUNE_POST_GRID_MAX; 0: the launcher's choice)
+    int misfit_variant = 1, misfit_grid_max = 0, post_variant = 1, post_grid_max = 0;
 
     // SpMV launch timing (HIP events on `stream`)
     bool prof = false;

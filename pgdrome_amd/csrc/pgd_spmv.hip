@@ -2714,6 +2714,10 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_GRAM_GRID_MAX && value >= 0 && value <= 1 << 20) { c->gram_grid_max = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_QUAD_VARIANT && value >= 0 && value <= 1) { c->quad_variant = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_QUAD_GRID_MAX && value >= 0 && value <= 1 << 20) { c->quad_grid_max = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_MISFIT_VARIANT && value >= 0 && value <= 1) { c->misfit_variant = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_MISFIT_GRID_MAX && value >= 0 && value <= 1 << 20) { c->misfit_grid_max = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_POST_VARIANT && value >= 0 && value <= 1) { c->post_variant = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_POST_GRID_MAX && value >= 0 && value <= 1 << 20) { c->post_grid_max = (int)value; return PGD_OK; }
     return fail(c, PGD_ERR_INVALID, "tune: unknown knob %d or value out of range", knob);
 }
 

@@ -552,6 +552,124 @@ class VarianceDecomposition:
         return self._std
 
 
+# ----------------------------------------------------------------- Bayesian calibration from sensor data
+DEVICE_POSTERIOR_MIN_SAMPLES = 1 << 12   # grids with at least this many samples form their misfits and reductions on the GPU
+POST_MARGINALS, POST_THETA, POST_COEF = 1, 2, 4      # what ``grid_posterior`` is asked for (PGD_POST_* of include/pgd_amd.h)
+POSTERIOR_MAX_ROWS, POSTERIOR_MAX_MODES, POSTERIOR_MAX_DIMS, POSTERIOR_COEF_MAX_MODES = 256, 256, 6, 64
+
+
+class DeviceArray:
+    """A library vector kept with a result (``PosteriorResult.chi2``): ``handle`` on the backend ``be``; ``host()`` downloads it
+    and adds ``offset`` (the part of the misfit that the thin QR took out of the kernel's rows).  Freed with the object."""
+
+    def __init__(self, be, handle, n, offset=0.0):
+        self.be, self.handle, self.n, self.offset = be, handle, int(n), float(offset)
+
+    def host(self):
+        return self.be.vec_to_host(self.handle) + self.offset
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.host()
+        return a if dtype is None else a.astype(dtype)
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        try:
+            self.be.vec_free(self.handle)
+        except Exception:
+            pass
+
+
+class PosteriorResult:
+    """What ``PGD.sensor_posterior`` returns; outputs that were not asked for are None.
+
+    ``chi2_min`` / ``map_index`` / ``map_coords``: the smallest misfit, its grid indices (a tuple; the sample number for scattered
+    samples) and coordinates.  ``log_evidence``: log of sum_s w_s N(data | prediction(s), covariance), the prior in w.
+    ``marginals[d]`` (masses, sum 1) and ``densities[d]`` (masses over the quadrature weights) per free dimension;
+    ``mean`` / ``cov`` of the parameters; ``coef_mean`` = E[c], ``coef_second`` = E[c c^T] of the mode coefficients
+    (``PGD.posterior_predictive``); ``ess`` = Z^2 / sum e^2; ``chi2`` with ``keep_chi2`` (numpy array or ``DeviceArray``, the
+    grid's shape in C order); ``path``: "device" or "numpy"; ``grids``, ``weights``, ``free_dim``: what the sums ran over."""
+    chi2_min = map_index = map_coords = log_evidence = None
+    marginals = densities = mean = cov = coef_mean = coef_second = None
+    ess = chi2 = path = None
+    grids = weights = free_dim = None
+    Z = shift = None
+
+
+def trapezoid_weights(x):
+    """Weights of the trapezoid rule on the non-decreasing abscissae x (one point: weight 1)."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.size == 1:
+        return np.ones(1)
+    w = np.zeros(x.size)
+    h = np.diff(x)
+    w[:-1] += 0.5 * h
+    w[1:] += 0.5 * h
+    return w
+
+
+def _grid_coefficients(tables, n, s):
+    """(C, idx): the coefficients c_k(s) = 1 * T_0[k, i_0] * T_1[k, i_1] * .. of the samples s (last index fastest) and their indices."""
+    idx = np.unravel_index(s, n)
+    C = np.ones((tables[0].shape[0], len(s)))
+    for d, t in enumerate(tables):
+        C *= t[:, idx[d]]
+    return C, idx
+
+
+def grid_misfit_numpy(a, y, tables, sample_chunk=1 << 14):
+    """The arithmetic of ``pgd_grid_misfit`` in numpy, ``sample_chunk`` samples at a time: (chi2, min, lowest index of the min)."""
+    n = [t.shape[1] for t in tables]
+    S = int(np.prod(n, dtype=np.int64))
+    chi2 = np.empty(S)
+    for s0 in range(0, S, int(sample_chunk)):
+        s = np.arange(s0, min(S, s0 + int(sample_chunk)))
+        C, _ = _grid_coefficients(tables, n, s)
+        r = y[:, None] - a @ C
+        chi2[s0:s0 + len(s)] = np.einsum("ps,ps->s", r, r)
+    arg = int(np.argmin(chi2))
+    return chi2, float(chi2[arg]), arg
+
+
+def grid_posterior_numpy(chi2, shift, n, weights, tables=None, abscissae=None, want=0, sample_chunk=1 << 14):
+    """The arithmetic of ``pgd_grid_posterior`` in numpy, ``sample_chunk`` samples at a time: the dict of ``Context.grid_posterior``."""
+    n = [int(v) for v in n]
+    S, nd = int(np.prod(n, dtype=np.int64)), len(n)
+    out = {"Z": 0.0, "sum_e2": 0.0}
+    if want & POST_MARGINALS:
+        out["marginals"] = [np.zeros(v) for v in n]
+    if want & POST_THETA:
+        out["theta1"], out["theta2"] = np.zeros(nd), np.zeros((nd, nd))
+    if want & POST_COEF:
+        k = tables[0].shape[0]
+        out["coef1"], out["coef2"] = np.zeros(k), np.zeros((k, k))
+    for s0 in range(0, S, int(sample_chunk)):
+        s = np.arange(s0, min(S, s0 + int(sample_chunk)))
+        idx = np.unravel_index(s, n)
+        w = np.ones(len(s))
+        for d in range(nd):
+            w *= weights[d][idx[d]]
+        e = w * np.exp(-0.5 * (chi2[s] - shift))
+        out["Z"] += float(e.sum())
+        out["sum_e2"] += float(e @ e)
+        if want & POST_MARGINALS:
+            for d in range(nd):
+                out["marginals"][d] += np.bincount(idx[d], weights=e, minlength=n[d])
+        if want & POST_THETA:
+            th = np.stack([np.asarray(abscissae[d], dtype=np.float64)[idx[d]] for d in range(nd)])
+            out["theta1"] += th @ e
+            out["theta2"] += (th * e) @ th.T
+        if want & POST_COEF:
+            C, _ = _grid_coefficients(tables, n, s)
+            out["coef1"] += C @ e
+            out["coef2"] += (C * e) @ C.T
+    if want & POST_COEF:
+        out["coef2"] = np.triu(out["coef2"]) + np.triu(out["coef2"], 1).T        # the upper triangle, mirrored (as the device call)
+    return out
+
+
 class PGD:
     def __init__(self, name=None, n_modes=0, fmeshes=[], pgd_modes=[], name_coord=[], modes_info=[],
                  verbose=False, *args, **kwargs):
@@ -1954,6 +2072,204 @@ class PGD:
             if flat.shape[1]:
                 res.min, res.max, res.max_abs = flat.min(axis=1), flat.max(axis=1), np.abs(flat).max(axis=1)
         return res
+
+
+    # ------------------------------------------------------ Bayesian calibration from sensor data
+    def sensor_posterior(self, fixed_dim, free_dim, attri, sensor_points, data, grids=None, coords=None, sigma=1.0, cov=None, prior=None,
+                         quadrature="trapezoid", gradient=False, outputs=("marginals", "theta", "coef"), keep_chi2=False, device=None,
+                         index=None, reduce=True):
+        """The posterior of the free coordinates given ``data`` measured at the sensor points (shaped like one sample of
+        ``evaluate_sensor_response_many``, or flat; ``gradient``: the spatial gradients there), under Gaussian noise - a scalar
+        ``sigma``, an array of it shaped like ``data``, or a full covariance ``cov`` (m x m) - as a ``PosteriorResult``.
+
+        Exactly one of ``grids`` (one 1-D array of abscissae per free dimension: the tensor grid, last dimension fastest) and
+        ``coords`` ((S, len(free_dim)) scattered samples drawn from the prior, weights 1 / S: self-normalised importance sampling,
+        no marginals) is given.  ``prior``: None (uniform) or {dimension: callable | array on the grid}, separable, multiplied into
+        the quadrature weights of that dimension, which are then normalised to sum 1 (``quadrature``: "trapezoid" on non-decreasing
+        abscissae, or "none": unit weights).  On the grid the coefficient of mode k is the product of D' small tables of the 1-D
+        modes at the abscissae, the prediction is Phi c(s) with Phi the whitened ``sensor_modes``: the misfits are one product whose
+        right-hand factor is never stored (``pgd_grid_misfit``), everything else a reduction over them (``pgd_grid_posterior``).
+        More data than modes are first reduced exactly by a thin QR, chi2 = |R c - Q^T y|^2 + |y - Q Q^T y|^2 (``reduce``).  On the
+        device when the backend has ``grid_misfit`` and S >= DEVICE_POSTERIOR_MIN_SAMPLES (``device``: force either route),
+        otherwise the same arithmetic in numpy.  ``outputs``: any of "marginals", "theta" (mean, cov), "coef" (coef_mean,
+        coef_second; at most 64 modes on the device).  ``index``: handed to ``sensor_modes``."""
+        free_dim = [int(d) for d in free_dim]
+        if (grids is None) == (coords is None):
+            raise ValueError("sensor_posterior: exactly one of grids and coords must be given")
+        unknown = set(outputs) - {"marginals", "theta", "coef"}
+        if unknown:
+            raise ValueError("sensor_posterior: unknown outputs %s" % sorted(unknown))
+        if quadrature not in ("trapezoid", "none"):
+            raise ValueError("sensor_posterior: quadrature must be 'trapezoid' or 'none', got %r" % (quadrature,))
+        if fixed_dim in free_dim or len(set(free_dim)) != len(free_dim) or not free_dim:
+            raise ValueError("sensor_posterior: free_dim %s must name distinct dimensions other than the fixed one" % (free_dim,))
+        for d in free_dim:
+            if d < 0 or d >= self.num_pgd_var or attri < 0 or attri >= len(self.mesh[d].attributes):
+                raise ValueError("dimension or attribute number not possible")
+            if self.mesh[d].attributes[attri].interpolationInfo.get("name") == 0:
+                raise ValueError("sensor_posterior: interp1d modes have no mesh to locate points on")
+            if len(self.mesh[d].attributes[attri].interpolationfct) == 0:
+                self.create_interpolation_fcts(free_dim, attri)
+        K = self.used_numModes
+        # ---- the samples: tables of the 1-D modes, weights, abscissae
+        prior = dict(prior or {})
+        for d in prior:
+            if d not in free_dim:
+                raise ValueError("sensor_posterior: the prior names dimension %r, the free dimensions are %s" % (d, free_dim))
+        if grids is not None:
+            if len(grids) != len(free_dim):
+                raise ValueError("sensor_posterior: %d grids for %d free dimensions" % (len(grids), len(free_dim)))
+            if len(free_dim) > POSTERIOR_MAX_DIMS:
+                raise ValueError("sensor_posterior: %d free dimensions, at most %d are possible" % (len(free_dim), POSTERIOR_MAX_DIMS))
+            absc, tables, weights, quad = [], [], [], []
+            for d, g in zip(free_dim, grids):
+                f0 = self.mesh[d].attributes[attri].interpolationfct[0]
+                V = f0.function_space() if isinstance(f0, fem.Function) else None
+                if V is None or V._ncomp > 1 or V.mesh().topology().dim() != 1:
+                    raise NotImplementedError("sensor_posterior: grids need scalar modes on 1-D free dimensions (dimension %d is not)" % d)
+                x = np.asarray(g, dtype=np.float64)
+                if x.ndim != 1 or x.size < 1 or not np.all(np.isfinite(x)):
+                    raise ValueError("sensor_posterior: the grid of dimension %d must be a finite 1-D array with at least one point" % d)
+                if quadrature == "trapezoid" and np.any(np.diff(x) < 0.0):
+                    raise ValueError("sensor_posterior: the trapezoid rule needs non-decreasing abscissae (dimension %d)" % d)
+                q = trapezoid_weights(x) if quadrature == "trapezoid" else np.ones(x.size)
+                w = q.copy()
+                if d in prior:
+                    p = prior[d]
+                    p = np.asarray([float(p(v)) for v in x]) if callable(p) else np.asarray(p, dtype=np.float64)
+                    if p.shape != x.shape or not np.all(np.isfinite(p)) or p.min() < 0.0:
+                        raise ValueError("sensor_posterior: the prior of dimension %d must be finite and >= 0 at the %d abscissae" % (d, x.size))
+                    w = w * p
+                if not w.sum() > 0.0:
+                    raise ValueError("sensor_posterior: the weights of dimension %d have no positive sum" % d)
+                w = w / w.sum()
+                absc.append(x)
+                quad.append(q)
+                weights.append(w)
+                tables.append(np.ascontiguousarray(self._free_modes_at(d, x, attri)))
+            shape = tuple(x.size for x in absc)
+        else:
+            if prior:
+                raise ValueError("sensor_posterior: scattered samples are draws from the prior; no prior is taken with coords")
+            coords = self._check_many(None, free_dim, coords, attri)
+            S = coords.shape[0]
+            tables = [np.ascontiguousarray(self.mode_factors_many(free_dim, coords, attri))]
+            weights, absc, quad, shape = [np.full(S, 1.0 / S)], None, None, (S,)
+        S = int(np.prod(shape, dtype=np.int64))
+        if S >= 1 << 31:
+            raise ValueError("sensor_posterior: %d samples, fewer than 2^31 are possible" % S)
+        # ---- the whitened sensor modes and data
+        sm = self.sensor_modes(sensor_points, fixed_dim, attri, gradient=gradient, device=None, index=index)
+        m = sm.m
+        y = np.asarray(data, dtype=np.float64)
+        if y.size != m or (y.ndim > 1 and y.shape != sm.shape):
+            raise ValueError("sensor_posterior: data has shape %s, the sensors give %s (%d entries)" % (y.shape, sm.shape, m))
+        y = y.reshape(-1)
+        if not np.all(np.isfinite(y)):
+            raise ValueError("sensor_posterior: data holds a value that is not finite")
+        A = sm.host()[:K].T                                                  # (m, K)
+        if cov is not None:
+            cv = np.asarray(cov, dtype=np.float64)
+            if cv.shape != (m, m):
+                raise ValueError("sensor_posterior: cov has shape %s, (%d, %d) is needed" % (cv.shape, m, m))
+            try:
+                L = np.linalg.cholesky(cv)
+            except np.linalg.LinAlgError as e:
+                raise ValueError("sensor_posterior: cov is not positive definite") from e
+            from scipy.linalg import solve_triangular
+            A, y = solve_triangular(L, A, lower=True), solve_triangular(L, y, lower=True)
+            logdet = float(np.sum(np.log(np.diag(L))))
+        else:
+            sg = np.asarray(sigma, dtype=np.float64)
+            if sg.ndim > 0 and sg.size != m:
+                raise ValueError("sensor_posterior: sigma has %d entries, a scalar or %d are needed" % (sg.size, m))
+            sg = np.broadcast_to(sg.reshape(-1) if sg.ndim else sg, (m,))
+            if not np.all(np.isfinite(sg)) or sg.min() <= 0.0:
+                raise ValueError("sensor_posterior: sigma must be finite and > 0")
+            A, y = A / sg[:, None], y / sg
+            logdet = float(np.sum(np.log(sg)))
+        rest = 0.0
+        if reduce and m > K:
+            Q, R = np.linalg.qr(A)                                           # thin: Q (m, K), R (K, K)
+            z = Q.T @ y
+            r = y - Q @ z
+            A, y, rest = R, z, float(r @ r)
+        if A.shape[0] > POSTERIOR_MAX_ROWS or K > POSTERIOR_MAX_MODES:
+            raise ValueError("sensor_posterior: %d rows and %d modes, at most %d and %d are possible: compress the solution first "
+                             "(PGD.compress)" % (A.shape[0], K, POSTERIOR_MAX_ROWS, POSTERIOR_MAX_MODES))
+        A, y = np.ascontiguousarray(A), np.ascontiguousarray(y)
+        want = (POST_MARGINALS if "marginals" in outputs and grids is not None else 0) | \
+               (POST_THETA if "theta" in outputs and grids is not None else 0) | (POST_COEF if "coef" in outputs else 0)
+        # ---- the route
+        be = fem.get_backend()
+        has = hasattr(be, "grid_misfit")
+        on_device = (has and S >= DEVICE_POSTERIOR_MIN_SAMPLES) if device is None else bool(device)
+        if on_device and not has:
+            raise NotImplementedError("sensor_posterior(device=True): the backend %r has no grid_misfit" % (getattr(be, "name", be),))
+        if on_device and (want & POST_COEF) and K > POSTERIOR_COEF_MAX_MODES:
+            raise ValueError("sensor_posterior: the coefficient moments on the device take at most %d modes, the solution uses %d: "
+                             "compress it first (PGD.compress) or leave \"coef\" out of the outputs" % (POSTERIOR_COEF_MAX_MODES, K))
+        res = PosteriorResult()
+        n = [int(v) for v in shape]
+        chi2_host = None
+        if on_device:
+            h = be.vec_zeros(S)
+            keep = DeviceArray(be, h, S, rest)
+            cmin, arg = be.grid_misfit(A, y, tables, h)
+            sums = be.grid_posterior(h, cmin, n, weights, tables=tables, abscissae=absc, want=want)
+            fem.STATS["posterior_calls"] = fem.STATS.get("posterior_calls", 0) + 1
+            res.path = "device"
+            if keep_chi2:
+                res.chi2 = keep
+            if grids is None and "theta" in outputs:
+                chi2_host = be.vec_to_host(h)
+        else:
+            chi2_host, cmin, arg = grid_misfit_numpy(A, y, tables)
+            sums = grid_posterior_numpy(chi2_host, cmin, n, weights, tables=tables, abscissae=absc, want=want)
+            res.path = "numpy"
+            if keep_chi2:
+                res.chi2 = (chi2_host + rest).reshape(shape)
+        Z = sums["Z"]
+        if not (Z > 0.0 and np.isfinite(Z)):
+            raise ValueError("sensor_posterior: the posterior has no mass on the samples (Z = %r)" % (Z,))
+        res.Z, res.shift = Z, cmin
+        res.chi2_min = cmin + rest
+        res.free_dim, res.grids, res.weights = list(free_dim), absc, weights
+        if grids is not None:
+            res.map_index = tuple(int(i) for i in np.unravel_index(arg, shape))
+            res.map_coords = np.array([absc[j][i] for j, i in enumerate(res.map_index)])
+        else:
+            res.map_index, res.map_coords = int(arg), coords[arg].copy()
+        res.log_evidence = math.log(Z) - 0.5 * (cmin + rest) - 0.5 * m * math.log(2.0 * math.pi) - logdet
+        res.ess = Z * Z / sums["sum_e2"]
+        if want & POST_MARGINALS:
+            res.marginals = [mg / Z for mg in sums["marginals"]]
+            res.densities = [np.where(q > 0.0, mg / np.where(q > 0.0, q, 1.0), 0.0) for mg, q in zip(res.marginals, quad)]
+        if want & POST_THETA:
+            res.mean = sums["theta1"] / Z
+            res.cov = sums["theta2"] / Z - np.outer(res.mean, res.mean)
+        elif grids is None and "theta" in outputs:
+            e = np.exp(-0.5 * (chi2_host - cmin)) / S
+            th = coords.reshape(S, -1)
+            res.mean = (e @ th) / Z
+            res.cov = (th.T * e) @ th / Z - np.outer(res.mean, res.mean)
+        if want & POST_COEF:
+            res.coef_mean, res.coef_second = sums["coef1"] / Z, sums["coef2"] / Z
+        return res
+
+    def posterior_predictive(self, res, fixed_dim, attri):
+        """(mean, variance): the posterior predictive mean and variance Functions on the fixed space from a ``PosteriorResult`` with
+        the "coef" output: F E[c] through ``eval_batch`` and f_i^T (E[c c^T] - E[c] E[c]^T) f_i through ``quadratic_forms``
+        (clamped at 0), both under the rule of ``evaluate_many``."""
+        if res.coef_mean is None or res.coef_second is None:
+            raise ValueError("posterior_predictive: the result holds no coefficient moments (outputs must name \"coef\")")
+        modes, V = self._gram_family(fixed_dim, attri)
+        mbar = np.asarray(res.coef_mean, dtype=np.float64)
+        if mbar.shape != (len(modes),):
+            raise ValueError("posterior_predictive: %d coefficient moments for %d modes" % (mbar.size, len(modes)))
+        mean = self._combine_modes(V, modes, mbar.reshape(-1, 1))[0]
+        funcs, _, _ = self.quadratic_forms(fixed_dim, res.coef_second - np.outer(mbar, mbar), attri, clamp=True)
+        return mean, funcs[0]
 
 
 class PGDErrorComputation(object):

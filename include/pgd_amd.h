@@ -522,6 +522,28 @@ enum { PGD_POST_MARGINALS = 1, PGD_POST_THETA = 2, PGD_POST_COEF = 4 };
 int pgd_grid_posterior(pgd_handle ctx, pgd_handle chi2, double shift, const double *tables, const int *n, int ndim, int k,
                        const double *weights, const double *abscissae, int want, double *sums, double *marginals, double *theta1,
                        double *theta2, double *coef1, double *coef2);
+/* Posteriors of nd data sets on the same grid in one pass (samples, tables, weights, abscissae and sample order as above; c_t(s) by
+ * the same chain).  Data set j is a row u_j (u: nd x m row-major on the host) and the scalars alpha[j], beta[j]:
+ *   p_s = a c(s) (m entries),  chi2[j, s] = beta_j - 2 u_j . p_s + alpha_j |p_s|^2
+ *   chi2_min[j] = shift_j = min_s chi2[j, s],  argmin[j] = the lowest sample that holds it (-1: no value compares)
+ *   e_js = w_s exp(-(chi2[j, s] - shift_j) / 2),  sums[2 j] = sum_s e_js,  sums[2 j + 1] = sum_s e_js^2
+ *   PGD_POST_THETA: theta1[j * ndim + d] = sum e_js th_d, theta2[(j * ndim + d) * ndim + f] = sum e_js th_d th_f (symmetric bit for
+ *                   bit: the upper triangle, mirrored); without the bit abscissae, theta1 and theta2 may be NULL.
+ * Independent data sets y_j are the rows (y_j, 1, |y_j|^2); "all data up to step j" is (sum_{i<=j} y_i, j + 1, sum_{i<=j} |y_i|^2).
+ * The nd x S misfits are never stored: three chained products on v_mfma_f64_16x16x4_f64 (a c, then u against it, then e against
+ * the features 1, th_d, th_d th_f) in two passes, the minima first.  No floating-point atomics; the segments of the samples depend
+ * on S alone: every output of a data set is bit-identical from run to run, for any grid (PGD_TUNE_POSTMANY_GRID_MAX), with or
+ * without the skip of underflowed tiles (PGD_TUNE_POSTMANY_SKIP), alone or among others, in any position.  The data sets are
+ * taken in chunks whose device scratch stays below 256 MB: ONE host synchronisation per chunk.  PGD_TUNE_POSTMANY_VARIANT = 0:
+ * plain fma chains (the cross-check; it agrees within rounding, not bit for bit).  1 <= k <= 64, 1 <= m <= 64 (compress the
+ * solution first otherwise), 1 <= ndim <= 6, S < 2^31, 1 <= nd < 2^31.  PGD_ERR_INVALID with a message, before anything is
+ * launched and with the outputs untouched: a bit of want other than PGD_POST_THETA, k, m, ndim or nd out of range, a null input
+ * or output that is needed, a dimension without points, S >= 2^31, a weight or (with PGD_POST_THETA) an abscissa that is not
+ * finite.  pgd_postmany_data_block: the data sets a wave of the matrix-unit kernel holds for ndim dimensions.                 */
+int pgd_grid_posterior_many(pgd_handle ctx, const double *a, int m, int k, const double *u, const double *alpha, const double *beta,
+                            int64_t nd, const double *tables, const int *n, int ndim, const double *weights, const double *abscissae,
+                            int want, double *chi2_min, int64_t *argmin, double *sums, double *theta1, double *theta2);
+int pgd_postmany_data_block(int ndim);
 
 /* ------------------------------------------------------------ column blocks --- */
 /* k <= 64 columns of n rows in ONE library-owned allocation, stored as fp32 or f64: the start space of the spatial solves
@@ -750,6 +772,12 @@ int pgd_points_free(pgd_handle ctx, pgd_handle points);
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_POSTMANY_SKIP = 74, /* pgd_grid_posterior_many: 1 (default) the exponentials and the third product of a (sample tile, data tile) whose
+                                e all underflow to 0 are left out, 0: never.  The same bits either way. */
+    PGD_TUNE_POSTMANY_GRID_MAX = 73, /* pgd_grid_posterior_many: > 0: at most this many (persistent) workgroups per kernel; 0 (default): as many
+                                as are resident at once.  The same bits either way. */
+    PGD_TUNE_POSTMANY_VARIANT = 72, /* pgd_grid_posterior_many: 1 (default) the chained products on the f64 matrix unit (k_postmany_mfma),
+                                0 ordinary fma chains (k_postmany_plain): the cross-check and the baseline. */
     PGD_TUNE_POST_GRID_MAX = 71, /* pgd_grid_posterior: > 0: at most this many (persistent) workgroups per kernel; 0 (default): four per CU.  The
                                 same bits either way: the segments and the order of their partials do not depend on the grid. */
     PGD_TUNE_POST_VARIANT = 70, /* pgd_grid_posterior, PGD_POST_COEF: 1 (default) the product over the samples on the f64 matrix unit

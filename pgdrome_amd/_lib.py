@@ -108,6 +108,8 @@ SIGNATURES = {
     "pgd_quad_forms": (C.c_int, [H, PH, C.c_int, PD, C.c_int, C.c_int, PH, PD]),
     "pgd_grid_misfit": (C.c_int, [H, PD, PD, C.c_int, C.c_int, PD, PI32, C.c_int, H, PD, PI64]),
     "pgd_grid_posterior": (C.c_int, [H, H, F64, PD, PI32, C.c_int, C.c_int, PD, PD, C.c_int, PD, PD, PD, PD, PD, PD]),
+    "pgd_grid_posterior_many": (C.c_int, [H, PD, C.c_int, C.c_int, PD, PD, PD, I64, PD, PI32, C.c_int, PD, PD, C.c_int, PD, PI64, PD, PD, PD]),
+    "pgd_postmany_data_block": (C.c_int, [C.c_int]),
     "pgd_vec_ratio": (C.c_int, [H, H, H, H, C.c_double]),
     "pgd_pcg_solve": (C.c_int, [H, H, H, H, F64, F64, C.c_int, C.POINTER(C.c_int), PD]),
     "pgd_pcg_last_form": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -201,6 +203,8 @@ QUAD_CLAMP = 1
 TUNE_MISFIT_VARIANT, TUNE_MISFIT_GRID_MAX, TUNE_POST_VARIANT, TUNE_POST_GRID_MAX = 68, 69, 70, 71
 POST_KMAX, POST_MMAX, POST_DMAX, POST_COEF_KMAX = 256, 256, 6, 64   # modes, rows and dimensions of pgd_grid_misfit; modes of PGD_POST_COEF
 POST_MARGINALS, POST_THETA, POST_COEF = 1, 2, 4                     # PGD_POST_* (include/pgd_amd.h)
+TUNE_POSTMANY_VARIANT, TUNE_POSTMANY_GRID_MAX, TUNE_POSTMANY_SKIP = 72, 73, 74
+POSTMANY_KMAX, POSTMANY_MMAX = 64, 64                               # modes and rows of pgd_grid_posterior_many
 LOCATE_TILE = 32                                    # points per launch of the general location kernel (LOC_PT, csrc/pgd_locate.hip)
 LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE = 1, 2     # pgd_points_last_path
 LOCATE_PATH_INDEX = 3                               # ... the bin index (TUNE_LOCATE_INDEX)
@@ -796,6 +800,47 @@ class Context:
             out["theta1"], out["theta2"] = th1, th2
         if want & POST_COEF:
             out["coef1"], out["coef2"] = c1, c2
+        return out
+
+    def postmany_data_block(self, ndim):
+        """The data sets a wave of the matrix-unit kernel of ``grid_posterior_many`` holds for ``ndim`` dimensions."""
+        return int(self.lib.pgd_postmany_data_block(int(ndim)))
+
+    def grid_posterior_many(self, a, u, alpha, beta, tables, weights, abscissae=None, want=0):
+        """pgd_grid_posterior_many: for every row j of ``u`` (nd, m) with the scalars ``alpha[j]``, ``beta[j]`` the misfits
+        chi2[j, s] = beta_j - 2 u_j . (a c(s)) + alpha_j |a c(s)|^2 over the grid of the ``tables`` (as in ``grid_misfit``), reduced
+        where they are formed.  Returns a dict of arrays of leading size nd: "chi2_min", "argmin", "Z", "sum_e2" and, with
+        POST_THETA, "theta1" (nd, D), "theta2" (nd, D, D)."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if a.ndim != 2 or u.ndim != 2 or u.shape[1] != a.shape[0] or u.shape[0] < 1:
+            raise ValueError(f"grid_posterior_many: a has shape {a.shape}, u has shape {u.shape}: (m, k) and (nd, m) are needed")
+        m, k = a.shape
+        nd = u.shape[0]
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+        beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+        if alpha.size != nd or beta.size != nd:
+            raise ValueError(f"grid_posterior_many: {alpha.size} alpha and {beta.size} beta for {nd} data sets")
+        flat, n = self._grid_tables(tables, k)
+        D = len(n)
+        cat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1) for x in xs]))
+        w = cat(weights)
+        if len(weights) != D or w.size != int(n.sum()):
+            raise ValueError("grid_posterior_many: the weights do not match the tables")
+        x = C.cast(None, PD)
+        if want & POST_THETA:
+            xa = cat(abscissae)
+            if len(abscissae) != D or xa.size != w.size:
+                raise ValueError("grid_posterior_many: the abscissae do not match the tables")
+            x = dptr(xa)
+        cmin, arg, sums = np.zeros(nd), np.zeros(nd, dtype=np.int64), np.zeros((nd, 2))
+        th1, th2 = np.zeros((nd, D)), np.zeros((nd, D, D))
+        self._ck(self.lib.pgd_grid_posterior_many(self.h, dptr(a), m, k, dptr(u), dptr(alpha), dptr(beta), nd, dptr(flat), iptr(n), D,
+                                                  dptr(w), x, int(want), dptr(cmin), arg.ctypes.data_as(PI64), dptr(sums), dptr(th1),
+                                                  dptr(th2)))
+        out = {"chi2_min": cmin, "argmin": arg, "Z": sums[:, 0].copy(), "sum_e2": sums[:, 1].copy()}
+        if want & POST_THETA:
+            out["theta1"], out["theta2"] = th1, th2
         return out
 
     def vec_ratio(self, out, num, den, floor=0.0):

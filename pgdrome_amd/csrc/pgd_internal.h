@@ -441,6 +441,8 @@ struct Ctx {
     // pgd_grid_misfit / pgd_grid_posterior (pgd_post.hip): kernel variants (1 MFMA, 0 plain fma chains; PGD_TUNE_MISFIT_VARIANT, PGD_TUNE_POST_VARIANT)
     // and grid caps (PGD_TUNE_MISFIT_GRID_MAX, PGD_TUNE_POST_GRID_MAX; 0: the launcher's choice)
     int misfit_variant = 1, misfit_grid_max = 0, post_variant = 1, post_grid_max = 0;
+    // pgd_grid_posterior_many (pgd_postmany.hip): PGD_TUNE_POSTMANY_VARIANT, PGD_TUNE_POSTMANY_GRID_MAX, PGD_TUNE_POSTMANY_SKIP
+    int postmany_variant = 1, postmany_grid_max = 0, postmany_skip = 1;
 
     // SpMV launch timing (HIP events on `stream`)
     bool prof = false;

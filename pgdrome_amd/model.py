@@ -556,6 +556,12 @@ class VarianceDecomposition:
 DEVICE_POSTERIOR_MIN_SAMPLES = 1 << 12   # grids with at least this many samples form their misfits and reductions on the GPU
 POST_MARGINALS, POST_THETA, POST_COEF = 1, 2, 4      # what ``grid_posterior`` is asked for (PGD_POST_* of include/pgd_amd.h)
 POSTERIOR_MAX_ROWS, POSTERIOR_MAX_MODES, POSTERIOR_MAX_DIMS, POSTERIOR_COEF_MAX_MODES = 256, 256, 6, 64
+# sensor_posterior_many takes the device when (data sets) x (samples) reaches this: DEVICE_POSTERIOR_MIN_SAMPLES, one data set on the
+# smallest grid sensor_posterior sends to the device.  tools/bench_posterior_many.py (64 data sets on 64^3 samples and up: the device
+# call is 20 to 70 times faster than the per-data-set calls) measured nothing near this threshold, so it has not been moved.
+DEVICE_POSTERIOR_MANY_MIN_WORK = DEVICE_POSTERIOR_MIN_SAMPLES
+POSTERIOR_MANY_MAX_ROWS, POSTERIOR_MANY_MAX_MODES = 64, 64
+POSTERIOR_MANY_PARTIALS = 1 << 25                    # doubles of device scratch a chunk of data sets may take (256 MB)
 
 
 class DeviceArray:
@@ -596,6 +602,19 @@ class PosteriorResult:
     ess = chi2 = path = None
     grids = weights = free_dim = None
     Z = shift = None
+
+
+class PosteriorManyResult:
+    """What ``PGD.sensor_posterior_many`` returns for N data sets (with ``accumulate``: N steps, step n holding all data up to n);
+    every array has the leading size N.
+
+    ``chi2_min`` (the smallest misfit, recomputed on the host in the difference form at the MAP sample), ``map_index`` (N, D) and
+    ``map_coords`` (N, D), ``log_evidence``, ``ess`` = Z^2 / sum e^2, ``mean`` (N, D) and ``cov`` (N, D, D) with the "theta" output;
+    ``Z`` and ``shift`` (the kernel's own minimum of the expanded misfit, what Z is relative to); ``path``: "device" or "numpy";
+    ``grids``, ``weights``, ``free_dim``: what the sums ran over."""
+    chi2_min = map_index = map_coords = log_evidence = ess = mean = cov = None
+    Z = shift = path = None
+    grids = weights = free_dim = None
 
 
 def trapezoid_weights(x):
@@ -667,6 +686,63 @@ def grid_posterior_numpy(chi2, shift, n, weights, tables=None, abscissae=None, w
             out["coef2"] += (C * e) @ C.T
     if want & POST_COEF:
         out["coef2"] = np.triu(out["coef2"]) + np.triu(out["coef2"], 1).T        # the upper triangle, mirrored (as the device call)
+    return out
+
+
+def posterior_many_segments(S):
+    """(number, length) of the sample segments of ``pgd_grid_posterior_many``: a function of S alone (postmany_segments of the library)."""
+    ns = min(max((S + 1023) // 1024, 1), 1024)
+    length = ((S + ns - 1) // ns + 255) // 256 * 256
+    return max((S + length - 1) // length, 1), length
+
+
+def grid_posterior_many_numpy(a, u, alpha, beta, tables, weights, abscissae=None, want=0, sample_chunk=1 << 12):
+    """The arithmetic of ``pgd_grid_posterior_many`` in numpy, ``sample_chunk`` samples at a time, in two passes over the same
+    expanded misfits chi2[j, s] = beta_j - 2 u_j . p_s + alpha_j |p_s|^2: the dict of ``Context.grid_posterior_many``.  Every number
+    of a data set is formed by element-wise operations and sums along its own row: it does not depend on the other rows."""
+    a, u = np.asarray(a, dtype=np.float64), np.asarray(u, dtype=np.float64)
+    alpha, beta = np.asarray(alpha, dtype=np.float64).reshape(-1, 1), np.asarray(beta, dtype=np.float64).reshape(-1, 1)
+    n = [t.shape[1] for t in tables]
+    S, D, nd, m = int(np.prod(n, dtype=np.int64)), len(n), u.shape[0], a.shape[0]
+
+    def chunk(s0):
+        s = np.arange(s0, min(S, s0 + int(sample_chunk)))
+        C, idx = _grid_coefficients(tables, n, s)
+        Pm = a @ C
+        dot = np.zeros((nd, len(s)))
+        for p in range(m):
+            dot += u[:, p:p + 1] * Pm[p]
+        return (beta - 2.0 * dot) + alpha * np.einsum("ps,ps->s", Pm, Pm), idx
+
+    cmin, arg = np.full(nd, np.inf), np.full(nd, -1, dtype=np.int64)
+    for s0 in range(0, S, int(sample_chunk)):
+        chi2, _ = chunk(s0)
+        loc = np.argmin(chi2, axis=1)
+        val = chi2[np.arange(nd), loc]
+        better = val < cmin                                   # (strict: the lowest sample keeps a tie)
+        cmin[better], arg[better] = val[better], s0 + loc[better]
+    out = {"chi2_min": cmin, "argmin": arg, "Z": np.zeros(nd), "sum_e2": np.zeros(nd)}
+    if want & POST_THETA:
+        out["theta1"], out["theta2"] = np.zeros((nd, D)), np.zeros((nd, D, D))
+    for s0 in range(0, S, int(sample_chunk)):
+        chi2, idx = chunk(s0)
+        w = np.ones(chi2.shape[1])
+        for d in range(D):
+            w *= weights[d][idx[d]]
+        e = w * np.exp(-0.5 * (chi2 - cmin[:, None]))
+        out["Z"] += e.sum(axis=1)
+        out["sum_e2"] += (e * e).sum(axis=1)
+        if want & POST_THETA:
+            th = [np.asarray(abscissae[d], dtype=np.float64)[idx[d]] for d in range(D)]
+            for d in range(D):
+                et = e * th[d]
+                out["theta1"][:, d] += et.sum(axis=1)
+                for f in range(d, D):
+                    out["theta2"][:, d, f] += (et * th[f]).sum(axis=1)
+    if want & POST_THETA:
+        for d in range(D):
+            for f in range(d):
+                out["theta2"][:, d, f] = out["theta2"][:, f, d]                   # the upper triangle, mirrored (as the device call)
     return out
 
 
@@ -2075,6 +2151,100 @@ class PGD:
 
 
     # ------------------------------------------------------ Bayesian calibration from sensor data
+    def _posterior_samples(self, name, fixed_dim, free_dim, attri, grids, coords, prior, quadrature):
+        """The samples of ``sensor_posterior`` / ``sensor_posterior_many`` (``name``: who asks, for the messages): the checked free
+        dimensions, K, and per dimension the abscissae, mode tables, normalised weights and quadrature weights; the grid's shape,
+        S and the checked scattered coordinates (None on a grid)."""
+        free_dim = [int(d) for d in free_dim]
+        if (grids is None) == (coords is None):
+            raise ValueError("%s: exactly one of grids and coords must be given" % name)
+        if quadrature not in ("trapezoid", "none"):
+            raise ValueError("%s: quadrature must be 'trapezoid' or 'none', got %r" % (name, quadrature,))
+        if fixed_dim in free_dim or len(set(free_dim)) != len(free_dim) or not free_dim:
+            raise ValueError("%s: free_dim %s must name distinct dimensions other than the fixed one" % (name, free_dim,))
+        for d in free_dim:
+            if d < 0 or d >= self.num_pgd_var or attri < 0 or attri >= len(self.mesh[d].attributes):
+                raise ValueError("dimension or attribute number not possible")
+            if self.mesh[d].attributes[attri].interpolationInfo.get("name") == 0:
+                raise ValueError("%s: interp1d modes have no mesh to locate points on" % name)
+            if len(self.mesh[d].attributes[attri].interpolationfct) == 0:
+                self.create_interpolation_fcts(free_dim, attri)
+        K = self.used_numModes
+        # ---- the samples: tables of the 1-D modes, weights, abscissae
+        prior = dict(prior or {})
+        for d in prior:
+            if d not in free_dim:
+                raise ValueError("%s: the prior names dimension %r, the free dimensions are %s" % (name, d, free_dim))
+        if grids is not None:
+            if len(grids) != len(free_dim):
+                raise ValueError("%s: %d grids for %d free dimensions" % (name, len(grids), len(free_dim)))
+            if len(free_dim) > POSTERIOR_MAX_DIMS:
+                raise ValueError("%s: %d free dimensions, at most %d are possible" % (name, len(free_dim), POSTERIOR_MAX_DIMS))
+            absc, tables, weights, quad = [], [], [], []
+            for d, g in zip(free_dim, grids):
+                f0 = self.mesh[d].attributes[attri].interpolationfct[0]
+                V = f0.function_space() if isinstance(f0, fem.Function) else None
+                if V is None or V._ncomp > 1 or V.mesh().topology().dim() != 1:
+                    raise NotImplementedError("%s: grids need scalar modes on 1-D free dimensions (dimension %d is not)" % (name, d))
+                x = np.asarray(g, dtype=np.float64)
+                if x.ndim != 1 or x.size < 1 or not np.all(np.isfinite(x)):
+                    raise ValueError("%s: the grid of dimension %d must be a finite 1-D array with at least one point" % (name, d))
+                if quadrature == "trapezoid" and np.any(np.diff(x) < 0.0):
+                    raise ValueError("%s: the trapezoid rule needs non-decreasing abscissae (dimension %d)" % (name, d))
+                q = trapezoid_weights(x) if quadrature == "trapezoid" else np.ones(x.size)
+                w = q.copy()
+                if d in prior:
+                    p = prior[d]
+                    p = np.asarray([float(p(v)) for v in x]) if callable(p) else np.asarray(p, dtype=np.float64)
+                    if p.shape != x.shape or not np.all(np.isfinite(p)) or p.min() < 0.0:
+                        raise ValueError("%s: the prior of dimension %d must be finite and >= 0 at the %d abscissae" % (name, d, x.size))
+                    w = w * p
+                if not w.sum() > 0.0:
+                    raise ValueError("%s: the weights of dimension %d have no positive sum" % (name, d))
+                w = w / w.sum()
+                absc.append(x)
+                quad.append(q)
+                weights.append(w)
+                tables.append(np.ascontiguousarray(self._free_modes_at(d, x, attri)))
+            shape = tuple(x.size for x in absc)
+        else:
+            if prior:
+                raise ValueError("%s: scattered samples are draws from the prior; no prior is taken with coords" % name)
+            coords = self._check_many(None, free_dim, coords, attri)
+            S = coords.shape[0]
+            tables = [np.ascontiguousarray(self.mode_factors_many(free_dim, coords, attri))]
+            weights, absc, quad, shape = [np.full(S, 1.0 / S)], None, None, (S,)
+        S = int(np.prod(shape, dtype=np.int64))
+        if S >= 1 << 31:
+            raise ValueError("%s: %d samples, fewer than 2^31 are possible" % (name, S))
+        return free_dim, K, absc, tables, weights, quad, shape, S, coords
+
+    @staticmethod
+    def _posterior_whitening(name, A, m, sigma, cov):
+        """(A whitened, whiten, logdet) for the (m, K) sensor modes ``A`` under the noise ``sigma`` or ``cov``: ``whiten(y)`` does to data
+        (m,) or (m, N) what was done to A's rows; logdet = log sqrt det of the covariance."""
+        if cov is not None:
+            cv = np.asarray(cov, dtype=np.float64)
+            if cv.shape != (m, m):
+                raise ValueError("%s: cov has shape %s, (%d, %d) is needed" % (name, cv.shape, m, m))
+            try:
+                L = np.linalg.cholesky(cv)
+            except np.linalg.LinAlgError as e:
+                raise ValueError("%s: cov is not positive definite" % name) from e
+            from scipy.linalg import solve_triangular
+            A, whiten = solve_triangular(L, A, lower=True), lambda y: solve_triangular(L, y, lower=True)
+            logdet = float(np.sum(np.log(np.diag(L))))
+        else:
+            sg = np.asarray(sigma, dtype=np.float64)
+            if sg.ndim > 0 and sg.size != m:
+                raise ValueError("%s: sigma has %d entries, a scalar or %d are needed" % (name, sg.size, m))
+            sg = np.broadcast_to(sg.reshape(-1) if sg.ndim else sg, (m,))
+            if not np.all(np.isfinite(sg)) or sg.min() <= 0.0:
+                raise ValueError("%s: sigma must be finite and > 0" % name)
+            A, whiten = A / sg[:, None], lambda y: y / (sg if y.ndim == 1 else sg[:, None])
+            logdet = float(np.sum(np.log(sg)))
+        return A, whiten, logdet
+
     def sensor_posterior(self, fixed_dim, free_dim, attri, sensor_points, data, grids=None, coords=None, sigma=1.0, cov=None, prior=None,
                          quadrature="trapezoid", gradient=False, outputs=("marginals", "theta", "coef"), keep_chi2=False, device=None,
                          index=None, reduce=True):
@@ -2093,71 +2263,11 @@ class PGD:
         device when the backend has ``grid_misfit`` and S >= DEVICE_POSTERIOR_MIN_SAMPLES (``device``: force either route),
         otherwise the same arithmetic in numpy.  ``outputs``: any of "marginals", "theta" (mean, cov), "coef" (coef_mean,
         coef_second; at most 64 modes on the device).  ``index``: handed to ``sensor_modes``."""
-        free_dim = [int(d) for d in free_dim]
-        if (grids is None) == (coords is None):
-            raise ValueError("sensor_posterior: exactly one of grids and coords must be given")
         unknown = set(outputs) - {"marginals", "theta", "coef"}
         if unknown:
             raise ValueError("sensor_posterior: unknown outputs %s" % sorted(unknown))
-        if quadrature not in ("trapezoid", "none"):
-            raise ValueError("sensor_posterior: quadrature must be 'trapezoid' or 'none', got %r" % (quadrature,))
-        if fixed_dim in free_dim or len(set(free_dim)) != len(free_dim) or not free_dim:
-            raise ValueError("sensor_posterior: free_dim %s must name distinct dimensions other than the fixed one" % (free_dim,))
-        for d in free_dim:
-            if d < 0 or d >= self.num_pgd_var or attri < 0 or attri >= len(self.mesh[d].attributes):
-                raise ValueError("dimension or attribute number not possible")
-            if self.mesh[d].attributes[attri].interpolationInfo.get("name") == 0:
-                raise ValueError("sensor_posterior: interp1d modes have no mesh to locate points on")
-            if len(self.mesh[d].attributes[attri].interpolationfct) == 0:
-                self.create_interpolation_fcts(free_dim, attri)
-        K = self.used_numModes
-        # ---- the samples: tables of the 1-D modes, weights, abscissae
-        prior = dict(prior or {})
-        for d in prior:
-            if d not in free_dim:
-                raise ValueError("sensor_posterior: the prior names dimension %r, the free dimensions are %s" % (d, free_dim))
-        if grids is not None:
-            if len(grids) != len(free_dim):
-                raise ValueError("sensor_posterior: %d grids for %d free dimensions" % (len(grids), len(free_dim)))
-            if len(free_dim) > POSTERIOR_MAX_DIMS:
-                raise ValueError("sensor_posterior: %d free dimensions, at most %d are possible" % (len(free_dim), POSTERIOR_MAX_DIMS))
-            absc, tables, weights, quad = [], [], [], []
-            for d, g in zip(free_dim, grids):
-                f0 = self.mesh[d].attributes[attri].interpolationfct[0]
-                V = f0.function_space() if isinstance(f0, fem.Function) else None
-                if V is None or V._ncomp > 1 or V.mesh().topology().dim() != 1:
-                    raise NotImplementedError("sensor_posterior: grids need scalar modes on 1-D free dimensions (dimension %d is not)" % d)
-                x = np.asarray(g, dtype=np.float64)
-                if x.ndim != 1 or x.size < 1 or not np.all(np.isfinite(x)):
-                    raise ValueError("sensor_posterior: the grid of dimension %d must be a finite 1-D array with at least one point" % d)
-                if quadrature == "trapezoid" and np.any(np.diff(x) < 0.0):
-                    raise ValueError("sensor_posterior: the trapezoid rule needs non-decreasing abscissae (dimension %d)" % d)
-                q = trapezoid_weights(x) if quadrature == "trapezoid" else np.ones(x.size)
-                w = q.copy()
-                if d in prior:
-                    p = prior[d]
-                    p = np.asarray([float(p(v)) for v in x]) if callable(p) else np.asarray(p, dtype=np.float64)
-                    if p.shape != x.shape or not np.all(np.isfinite(p)) or p.min() < 0.0:
-                        raise ValueError("sensor_posterior: the prior of dimension %d must be finite and >= 0 at the %d abscissae" % (d, x.size))
-                    w = w * p
-                if not w.sum() > 0.0:
-                    raise ValueError("sensor_posterior: the weights of dimension %d have no positive sum" % d)
-                w = w / w.sum()
-                absc.append(x)
-                quad.append(q)
-                weights.append(w)
-                tables.append(np.ascontiguousarray(self._free_modes_at(d, x, attri)))
-            shape = tuple(x.size for x in absc)
-        else:
-            if prior:
-                raise ValueError("sensor_posterior: scattered samples are draws from the prior; no prior is taken with coords")
-            coords = self._check_many(None, free_dim, coords, attri)
-            S = coords.shape[0]
-            tables = [np.ascontiguousarray(self.mode_factors_many(free_dim, coords, attri))]
-            weights, absc, quad, shape = [np.full(S, 1.0 / S)], None, None, (S,)
-        S = int(np.prod(shape, dtype=np.int64))
-        if S >= 1 << 31:
-            raise ValueError("sensor_posterior: %d samples, fewer than 2^31 are possible" % S)
+        free_dim, K, absc, tables, weights, quad, shape, S, coords = self._posterior_samples("sensor_posterior", fixed_dim, free_dim, attri, grids,
+                                                                                              coords, prior, quadrature)
         # ---- the whitened sensor modes and data
         sm = self.sensor_modes(sensor_points, fixed_dim, attri, gradient=gradient, device=None, index=index)
         m = sm.m
@@ -2168,26 +2278,8 @@ class PGD:
         if not np.all(np.isfinite(y)):
             raise ValueError("sensor_posterior: data holds a value that is not finite")
         A = sm.host()[:K].T                                                  # (m, K)
-        if cov is not None:
-            cv = np.asarray(cov, dtype=np.float64)
-            if cv.shape != (m, m):
-                raise ValueError("sensor_posterior: cov has shape %s, (%d, %d) is needed" % (cv.shape, m, m))
-            try:
-                L = np.linalg.cholesky(cv)
-            except np.linalg.LinAlgError as e:
-                raise ValueError("sensor_posterior: cov is not positive definite") from e
-            from scipy.linalg import solve_triangular
-            A, y = solve_triangular(L, A, lower=True), solve_triangular(L, y, lower=True)
-            logdet = float(np.sum(np.log(np.diag(L))))
-        else:
-            sg = np.asarray(sigma, dtype=np.float64)
-            if sg.ndim > 0 and sg.size != m:
-                raise ValueError("sensor_posterior: sigma has %d entries, a scalar or %d are needed" % (sg.size, m))
-            sg = np.broadcast_to(sg.reshape(-1) if sg.ndim else sg, (m,))
-            if not np.all(np.isfinite(sg)) or sg.min() <= 0.0:
-                raise ValueError("sensor_posterior: sigma must be finite and > 0")
-            A, y = A / sg[:, None], y / sg
-            logdet = float(np.sum(np.log(sg)))
+        A, whiten, logdet = self._posterior_whitening("sensor_posterior", A, m, sigma, cov)
+        y = whiten(y)
         rest = 0.0
         if reduce and m > K:
             Q, R = np.linalg.qr(A)                                           # thin: Q (m, K), R (K, K)
@@ -2255,6 +2347,116 @@ class PGD:
             res.cov = (th.T * e) @ th / Z - np.outer(res.mean, res.mean)
         if want & POST_COEF:
             res.coef_mean, res.coef_second = sums["coef1"] / Z, sums["coef2"] / Z
+        return res
+
+    def sensor_posterior_many(self, fixed_dim, free_dim, attri, sensor_points, data, grids=None, coords=None, sigma=1.0, cov=None,
+                              prior=None, quadrature="trapezoid", gradient=False, outputs=("theta",), accumulate=False, device=None,
+                              index=None, reduce=True, data_chunk=None):
+        """The posteriors of ``sensor_posterior`` for a stream of N data sets from the same sensors under the same noise, in one
+        pass over the grid - a ``PosteriorManyResult``.  ``data``: (N, *shape of one sample) or (N, m); samples, noise, ``prior``,
+        ``quadrature`` and the thin QR (``reduce``; it reduces all N data vectors at once) are ``sensor_posterior``'s.
+        ``accumulate``: the posterior of step n is that of ALL data up to n (independent measurements of the same state).
+        ``outputs``: () or ("theta",) (mean, cov); marginals and coefficient moments of a step of interest: ``sensor_posterior``.
+
+        The predictions p_s = A c(s) do not depend on the data: the misfits of all data sets are chi2[n, s] = beta_n - 2 u_n . p_s +
+        alpha_n |p_s|^2 with (u, alpha, beta) = (y_n, 1, |y_n|^2), or their prefix sums with ``accumulate`` - one more dense product
+        behind the one that forms p, reduced where it is formed (``pgd_grid_posterior_many``).  On the device when the backend has
+        ``grid_posterior_many`` and N S >= DEVICE_POSTERIOR_MANY_MIN_WORK (``device``: force either route), otherwise the same
+        arithmetic in numpy; ``data_chunk`` data sets per call (default: what keeps the scratch of a call under 256 MB).  The
+        expanded form cancels where the misfit is small against |y|^2: ``chi2_min`` is therefore recomputed in the difference form at
+        the MAP sample, ``shift`` is the kernel's own minimum.  At most 64 modes and 64 rows (after the QR)."""
+        name = "sensor_posterior_many"
+        if coords is not None:
+            raise NotImplementedError("sensor_posterior_many: scattered samples (coords) are not taken; sensor_posterior takes them, one data "
+                                      "set at a time")
+        unknown = set(outputs) - {"theta"}
+        if unknown:
+            raise ValueError("sensor_posterior_many: unknown outputs %s (\"theta\" is the only one; sensor_posterior gives marginals and "
+                             "coefficient moments)" % sorted(unknown))
+        free_dim, K, absc, tables, weights, quad, shape, S, _ = self._posterior_samples(name, fixed_dim, free_dim, attri, grids, None, prior,
+                                                                                         quadrature)
+        D = len(free_dim)
+        # ---- the whitened sensor modes and data
+        sm = self.sensor_modes(sensor_points, fixed_dim, attri, gradient=gradient, device=None, index=index)
+        m = sm.m
+        Y = np.asarray(data, dtype=np.float64)
+        if Y.ndim < 2 or Y.shape[0] < 1 or (Y.shape[1:] != (m,) and Y.shape[1:] != tuple(sm.shape)):
+            raise ValueError("sensor_posterior_many: data has shape %s, (N, %d) or (N,) + %s is needed" % (Y.shape, m, tuple(sm.shape)))
+        N = Y.shape[0]
+        Y = Y.reshape(N, m)
+        if not np.all(np.isfinite(Y)):
+            raise ValueError("sensor_posterior_many: data holds a value that is not finite")
+        A = sm.host()[:K].T                                                  # (m, K)
+        A, whiten, logdet = self._posterior_whitening(name, A, m, sigma, cov)
+        Y = np.ascontiguousarray(whiten(Y.T).T)                              # (N, m), whitened
+        rest = np.zeros(N)
+        if reduce and m > K:
+            Q, R = np.linalg.qr(A)                                           # thin: Q (m, K), R (K, K)
+            Z = Y @ Q
+            r = Y - Z @ Q.T
+            A, Y, rest = R, Z, np.einsum("np,np->n", r, r)
+        rows = A.shape[0]
+        if rows > POSTERIOR_MANY_MAX_ROWS or K > POSTERIOR_MANY_MAX_MODES:
+            raise ValueError("sensor_posterior_many: %d rows and %d modes, at most %d and %d are possible: compress the solution first "
+                             "(PGD.compress)" % (rows, K, POSTERIOR_MANY_MAX_ROWS, POSTERIOR_MANY_MAX_MODES))
+        A, Y = np.ascontiguousarray(A), np.ascontiguousarray(Y)
+        y2 = np.einsum("np,np->n", Y, Y)
+        steps = np.arange(1, N + 1, dtype=np.float64)
+        if accumulate:
+            u, alpha, beta, rest = np.cumsum(Y, axis=0), steps, np.cumsum(y2), np.cumsum(rest)
+        else:
+            u, alpha, beta = Y, np.ones(N), y2
+        want = POST_THETA if "theta" in outputs else 0
+        # ---- the route
+        be = fem.get_backend()
+        has = hasattr(be, "grid_posterior_many")
+        on_device = (has and N * S >= DEVICE_POSTERIOR_MANY_MIN_WORK) if device is None else bool(device)
+        if on_device and not has:
+            raise NotImplementedError("sensor_posterior_many(device=True): the backend %r has no grid_posterior_many" % (getattr(be, "name", be),))
+        if data_chunk is None:
+            nseg, _ = posterior_many_segments(S)
+            nvs = (D + 1) * (D + 2) // 2 + 1
+            data_chunk = max(POSTERIOR_MANY_PARTIALS // (nseg * nvs), 1) if on_device else max((1 << 22) // min(S, 1 << 12), 1)
+        data_chunk = int(data_chunk)
+        if data_chunk < 1:
+            raise ValueError("sensor_posterior_many: data_chunk = %d, at least 1 is needed" % data_chunk)
+        parts = []
+        for n0 in range(0, N, data_chunk):
+            sl = slice(n0, min(N, n0 + data_chunk))
+            if on_device:
+                parts.append(be.grid_posterior_many(A, u[sl], alpha[sl], beta[sl], tables, weights, abscissae=absc, want=want))
+                fem.STATS["posterior_many_calls"] = fem.STATS.get("posterior_many_calls", 0) + 1
+            else:
+                parts.append(grid_posterior_many_numpy(A, u[sl], alpha[sl], beta[sl], tables, weights, abscissae=absc, want=want))
+        sums = {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
+        Zs = sums["Z"]
+        if not np.all((Zs > 0.0) & np.isfinite(Zs)):
+            bad = int(np.flatnonzero(~((Zs > 0.0) & np.isfinite(Zs)))[0])
+            raise ValueError("sensor_posterior_many: the posterior of data set %d has no mass on the samples (Z = %r)" % (bad, Zs[bad]))
+        res = PosteriorManyResult()
+        res.path = "device" if on_device else "numpy"
+        res.Z, res.shift = Zs, sums["chi2_min"]
+        res.free_dim, res.grids, res.weights = list(free_dim), absc, weights
+        arg = sums["argmin"]
+        res.map_index = np.stack(np.unravel_index(arg, shape), axis=1)
+        res.map_coords = np.stack([absc[d][res.map_index[:, d]] for d in range(D)], axis=1)
+        # ---- the misfit at the MAP sample in the difference form: alpha |p - u / alpha|^2 + the scatter of the data about their mean
+        Cm = np.ones((K, N))
+        for d, t in enumerate(tables):
+            Cm *= t[:, res.map_index[:, d]]
+        Pm = (A @ Cm).T                                                      # (N, rows): the predictions at the N MAP samples
+        ubar = u / alpha[:, None]
+        scatter = np.zeros(N)
+        if accumulate and N > 1:                                             # Welford: sum_{i <= n} |y_i - mean_n|^2
+            scatter[1:] = np.cumsum(np.einsum("np,np->n", Y[1:] - ubar[:-1], Y[1:] - ubar[1:]))
+        dlt = Pm - ubar
+        res.chi2_min = alpha * np.einsum("np,np->n", dlt, dlt) + scatter + rest
+        m_eff = m * alpha
+        res.log_evidence = np.log(Zs) - 0.5 * (res.shift + rest) - 0.5 * m_eff * math.log(2.0 * math.pi) - alpha * logdet
+        res.ess = Zs * Zs / sums["sum_e2"]
+        if want & POST_THETA:
+            res.mean = sums["theta1"] / Zs[:, None]
+            res.cov = sums["theta2"] / Zs[:, None, None] - res.mean[:, :, None] * res.mean[:, None, :]
         return res
 
     def posterior_predictive(self, res, fixed_dim, attri):

@@ -544,6 +544,34 @@ int pgd_grid_posterior_many(pgd_handle ctx, const double *a, int m, int k, const
                             int64_t nd, const double *tables, const int *n, int ndim, const double *weights, const double *abscissae,
                             int want, double *chi2_min, int64_t *argmin, double *sums, double *theta1, double *theta2);
 int pgd_postmany_data_block(int ndim);
+/* Sensor placement by greedy expected information gain (Bayesian D-optimality in the linearised form) on the same grid (samples,
+ * tables, weights and sample order as above).  dtables: the derivatives of the tables, laid out like them; the derivative
+ * coefficient of mode t against coordinate d is the chain cd_t(s) = 1 * U_0[t, i_0] * U_1[t, i_1] * .. in ascending f with
+ * U_f = dtables_f for f == d and tables_f otherwise, and the Jacobian of a row p (k entries) is g_p,d(s) = sum_t p[t] cd_t(s), an fma
+ * chain in ascending t.  state: a vector of 2 nh S doubles, nh = ndim (ndim + 1) / 2, plane-major: state[c S + s] is entry c of
+ * H_s, the UPPER triangle in row order (c = 0: (0, 0), 1: (0, 1) .. ndim: (1, 1) ..), state[(nh + c) S + s] entry c of W_s, the
+ * inverse of the lower Cholesky factor of H_s, the LOWER triangle in row order (c = i (i + 1) / 2 + j, j <= i).
+ *   pgd_design_update: with h0 (ndim x ndim row-major, symmetric positive definite; may be NULL) every H_s is first set to it;
+ *     then H_s += sum_r g_r(s) g_r(s)^T for the 0 <= R <= 256 rows (added, never downdated); W_s is recomputed;
+ *     sums[0] = sum_s w_s log det H_s, formed as -2 sum log diag W_s; sums[1 .. nh] = sum_s w_s (W_s^T W_s), the expected posterior
+ *     covariance, packed like H.  R = 0 with h0 is the reset.  A thread per sample; ONE host synchronisation.
+ *   pgd_design_gains: gains[j] = 1/2 sum_s w_s log det(I_R + V^T V), V = W_s [g_jR(s) .. g_jR+R-1(s)], for the M candidates whose
+ *     rows are a[(j R + r) k + t] (a: M R x k row-major on the host), from the LDL^T pivots of I + V^T V as log1p(pivot - 1).  The
+ *     M x S x R x ndim Jacobian is never stored: v_mfma_f64_16x16x4_f64 with 16 samples on the fragment's column index as in
+ *     pgd_grid_misfit and 16 candidates on its row index, a laid out in fragment order per plane r by the library; the epilogue is
+ *     lane-local.  1 <= k <= 64 (compress first otherwise), 1 <= R <= 3, 1 <= ndim <= 6, S < 2^31, 1 <= M < 2^31.  The candidates
+ *     are taken in chunks whose device scratch stays below 256 MB: ONE host synchronisation per chunk.
+ * No floating-point atomics; the samples are cut by the segments of pgd_grid_posterior (a function of S alone), a partial sum of a
+ * segment is formed in an order that depends on the segment alone and the segments are added in ascending order: every gain and
+ * every entry of sums is bit-identical from run to run, for any grid (PGD_TUNE_DESIGN_GRID_MAX), and a candidate's gain alone or
+ * among others at any position.  PGD_TUNE_DESIGN_VARIANT = 0: the gains from plain fma chains (the cross-check; it agrees within
+ * rounding, not bit for bit).  PGD_ERR_INVALID with a message, before anything is launched and with the outputs untouched: a null
+ * input or output, k, R, ndim or M out of range, a dimension without points, S >= 2^31, a state that is not a vector of 2 nh S
+ * entries, a weight that is not finite, an h0 that is not symmetric positive definite.                                          */
+int pgd_design_update(pgd_handle ctx, const double *h0_or_null, const double *rows, int R, int k, const double *tables,
+                      const double *dtables, const int *n, int ndim, const double *weights, pgd_handle state, double *sums);
+int pgd_design_gains(pgd_handle ctx, const double *a, int64_t M, int R, int k, const double *tables, const double *dtables,
+                     const int *n, int ndim, const double *weights, pgd_handle state, double *gains);
 
 /* ------------------------------------------------------------ column blocks --- */
 /* k <= 64 columns of n rows in ONE library-owned allocation, stored as fp32 or f64: the start space of the spatial solves
@@ -772,6 +800,10 @@ int pgd_points_free(pgd_handle ctx, pgd_handle points);
 /* Launch-shape knobs; they change speed (and the order of the dot's partial
  * sums), never which result is computed (PGD_TUNE_FAULT_ITERATION excepted: a test hook).  */
 enum {
+    PGD_TUNE_DESIGN_GRID_MAX = 76, /* pgd_design_gains, pgd_design_update: > 0: at most this many (persistent) workgroups per kernel; 0 (default):
+                                as many as are resident at once (update: four per CU).  The same bits either way. */
+    PGD_TUNE_DESIGN_VARIANT = 75, /* pgd_design_gains: 1 (default) the Jacobians on the f64 matrix unit (k_design_gains_mfma), 0 ordinary fma
+                                chains (k_design_gains_plain): the cross-check and the baseline. */
     PGD_TUNE_POSTMANY_SKIP = 74, /* pgd_grid_posterior_many: 1 (default) the exponentials and the third product of a (sample tile, data tile) whose
                                 e all underflow to 0 are left out, 0: never.  The same bits either way. */
     PGD_TUNE_POSTMANY_GRID_MAX = 73, /* pgd_grid_posterior_many: > 0: at most this many (persistent) workgroups per kernel; 0 (default): as many

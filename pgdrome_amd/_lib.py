@@ -110,6 +110,8 @@ SIGNATURES = {
     "pgd_grid_posterior": (C.c_int, [H, H, F64, PD, PI32, C.c_int, C.c_int, PD, PD, C.c_int, PD, PD, PD, PD, PD, PD]),
     "pgd_grid_posterior_many": (C.c_int, [H, PD, C.c_int, C.c_int, PD, PD, PD, I64, PD, PI32, C.c_int, PD, PD, C.c_int, PD, PI64, PD, PD, PD]),
     "pgd_postmany_data_block": (C.c_int, [C.c_int]),
+    "pgd_design_update": (C.c_int, [H, PD, PD, C.c_int, C.c_int, PD, PD, PI32, C.c_int, PD, H, PD]),
+    "pgd_design_gains": (C.c_int, [H, PD, I64, C.c_int, C.c_int, PD, PD, PI32, C.c_int, PD, H, PD]),
     "pgd_vec_ratio": (C.c_int, [H, H, H, H, C.c_double]),
     "pgd_pcg_solve": (C.c_int, [H, H, H, H, F64, F64, C.c_int, C.POINTER(C.c_int), PD]),
     "pgd_pcg_last_form": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -205,6 +207,8 @@ POST_KMAX, POST_MMAX, POST_DMAX, POST_COEF_KMAX = 256, 256, 6, 64   # modes, row
 POST_MARGINALS, POST_THETA, POST_COEF = 1, 2, 4                     # PGD_POST_* (include/pgd_amd.h)
 TUNE_POSTMANY_VARIANT, TUNE_POSTMANY_GRID_MAX, TUNE_POSTMANY_SKIP = 72, 73, 74
 POSTMANY_KMAX, POSTMANY_MMAX = 64, 64                               # modes and rows of pgd_grid_posterior_many
+TUNE_DESIGN_VARIANT, TUNE_DESIGN_GRID_MAX = 75, 76
+DESIGN_KMAX, DESIGN_RMAX = 64, 3                                    # modes and rows per candidate of pgd_design_gains
 LOCATE_TILE = 32                                    # points per launch of the general location kernel (LOC_PT, csrc/pgd_locate.hip)
 LOCATE_PATH_GENERAL, LOCATE_PATH_LATTICE = 1, 2     # pgd_points_last_path
 LOCATE_PATH_INDEX = 3                               # ... the bin index (TUNE_LOCATE_INDEX)
@@ -842,6 +846,55 @@ class Context:
         if want & POST_THETA:
             out["theta1"], out["theta2"] = th1, th2
         return out
+
+    def _design_grid(self, who, tables, dtables, weights, k):
+        flat, n = self._grid_tables(tables, k)
+        dflat, dn = self._grid_tables(dtables, k)
+        if not np.array_equal(n, dn):
+            raise ValueError(f"{who}: the dtables do not match the tables")
+        w = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1) for x in weights]))
+        if len(weights) != len(n) or w.size != int(n.sum()):
+            raise ValueError(f"{who}: the weights do not match the tables")
+        return flat, dflat, n, w
+
+    def design_state(self, n):
+        """A vector for the state of ``design_update`` / ``design_gains`` on the grid of ``n`` points per dimension: 2 nh S doubles."""
+        D = len(n)
+        return self.vec_alloc(D * (D + 1) * int(np.prod(n, dtype=np.int64)))
+
+    def design_update(self, state, tables, dtables, weights, rows=None, h0=None):
+        """pgd_design_update: H_s (= ``h0`` first, if given) += g g^T for the ``rows`` (R, k), W_s recomputed.  Returns
+        (sum_s w_s log det H_s, the expected posterior covariance sum_s w_s H_s^-1 as a (D, D) matrix)."""
+        k = int(np.asarray(tables[0]).shape[0])
+        rows = np.zeros((0, k)) if rows is None else np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, k)
+        flat, dflat, n, w = self._design_grid("design_update", tables, dtables, weights, k)
+        D = len(n)
+        none = C.cast(None, PD)
+        hp = none
+        if h0 is not None:
+            h0 = np.ascontiguousarray(h0, dtype=np.float64)
+            if h0.shape != (D, D):
+                raise ValueError(f"design_update: h0 has shape {h0.shape}, ({D}, {D}) is needed")
+            hp = dptr(h0)
+        sums = np.zeros(1 + D * (D + 1) // 2)
+        self._ck(self.lib.pgd_design_update(self.h, hp, dptr(rows) if rows.shape[0] else none, rows.shape[0], k, dptr(flat), dptr(dflat),
+                                            iptr(n), D, dptr(w), state, dptr(sums)))
+        cov = np.zeros((D, D))
+        cov[np.triu_indices(D)] = sums[1:]
+        return float(sums[0]), cov + np.triu(cov, 1).T
+
+    def design_gains(self, a, R, state, tables, dtables, weights):
+        """pgd_design_gains: the gains (in nats) of the M candidates whose R rows each are the rows of ``a`` (M R, k), at the state."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        R = int(R)
+        if a.ndim != 2 or R < 1 or a.shape[0] % R or a.shape[0] < R:
+            raise ValueError(f"design_gains: a has shape {a.shape}, (M R, k) with R = {R} is needed")
+        k = a.shape[1]
+        flat, dflat, n, w = self._design_grid("design_gains", tables, dtables, weights, k)
+        gains = np.zeros(a.shape[0] // R)
+        self._ck(self.lib.pgd_design_gains(self.h, dptr(a), gains.size, R, k, dptr(flat), dptr(dflat), iptr(n), len(n), dptr(w), state,
+                                           dptr(gains)))
+        return gains
 
     def vec_ratio(self, out, num, den, floor=0.0):
         """pgd_vec_ratio: out = num / den where den > floor, 0 elsewhere (``out`` may be ``num``)."""

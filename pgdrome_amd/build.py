@@ -17,7 +17,7 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIBDIR = HERE / "lib"
 LIB = LIBDIR / "libpgd_amd.so"
-SOURCES = ["pgd_ctx.hip", "pgd_vec.hip", "pgd_mesh.hip", "pgd_spmv.hip", "pgd_classify.hip", "pgd_pcg.hip", "pgd_comm.hip", "pgd_mg.hip", "pgd_vmg.hip", "pgd_pmg.hip", "pgd_krylov.hip", "pgd_eval.hip", "pgd_block.hip", "pgd_bdia.hip", "pgd_p2lat.hip", "pgd_locate.hip", "pgd_gram.hip", "pgd_quad.hip", "pgd_post.hip", "pgd_postmany.hip"]
+SOURCES = ["pgd_ctx.hip", "pgd_vec.hip", "pgd_mesh.hip", "pgd_spmv.hip", "pgd_classify.hip", "pgd_pcg.hip", "pgd_comm.hip", "pgd_mg.hip", "pgd_vmg.hip", "pgd_pmg.hip", "pgd_krylov.hip", "pgd_eval.hip", "pgd_block.hip", "pgd_bdia.hip", "pgd_p2lat.hip", "pgd_locate.hip", "pgd_gram.hip", "pgd_quad.hip", "pgd_post.hip", "pgd_postmany.hip", "pgd_design.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-result",
          "-fno-gpu-rdc"]
 

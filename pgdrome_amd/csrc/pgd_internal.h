@@ -443,6 +443,8 @@ struct Ctx {
     int misfit_variant = 1, misfit_grid_max = 0, post_variant = 1, post_grid_max = 0;
     // pgd_grid_posterior_many (pgd_postmany.hip): PGD_TUNE_POSTMANY_VARIANT, PGD_TUNE_POSTMANY_GRID_MAX, PGD_TUNE_POSTMANY_SKIP
     int postmany_variant = 1, postmany_grid_max = 0, postmany_skip = 1;
+    // pgd_design_update / pgd_design_gains (pgd_design.hip): PGD_TUNE_DESIGN_VARIANT, PGD_TUNE_DESIGN_GRID_MAX
+    int design_variant = 1, design_grid_max = 0;
 
     // SpMV launch timing (HIP events on `stream`)
     bool prof = false;

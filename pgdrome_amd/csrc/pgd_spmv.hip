@@ -2721,6 +2721,8 @@ int pgd_tune(pgd_handle h, int knob, int64_t value) {
     if (knob == PGD_TUNE_POSTMANY_VARIANT && value >= 0 && value <= 1) { c->postmany_variant = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_POSTMANY_GRID_MAX && value >= 0 && value <= 1 << 20) { c->postmany_grid_max = (int)value; return PGD_OK; }
     if (knob == PGD_TUNE_POSTMANY_SKIP && value >= 0 && value <= 1) { c->postmany_skip = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_DESIGN_VARIANT && value >= 0 && value <= 1) { c->design_variant = (int)value; return PGD_OK; }
+    if (knob == PGD_TUNE_DESIGN_GRID_MAX && value >= 0 && value <= 1 << 20) { c->design_grid_max = (int)value; return PGD_OK; }
     return fail(c, PGD_ERR_INVALID, "tune: unknown knob %d or value out of range", knob);
 }
 

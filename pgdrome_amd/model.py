@@ -746,6 +746,118 @@ def grid_posterior_many_numpy(a, u, alpha, beta, tables, weights, abscissae=None
     return out
 
 
+# ----------------------------------------------------------------- sensor placement by expected information gain
+# sensor_placement takes the device when (candidates) x (samples) reaches this.  Measured (tools/bench_placement.py --crossover,
+# profiles/placement_crossover_n1.jsonl: whole 8-step calls, 48 modes, three dimensions): at M S = 2^10, the smallest problem timed, the
+# two routes take the same time (1.37 against 1.42 ms); from 2^13 on the device call is 1.3 to 2 times faster, from 2^19 on 5 to 60 times.
+DEVICE_PLACEMENT_MIN_WORK = 1 << 10
+PLACEMENT_MAX_MODES, PLACEMENT_MAX_ROWS = 64, 3      # modes and rows per candidate of pgd_design_gains
+
+
+class PlacementResult:
+    """What ``PGD.sensor_placement`` returns.  ``selected`` (n_select candidate indices in the order they were chosen) and
+    ``selected_points``; ``gains`` (n_select marginal gains, in nats); ``installed_gains`` (those of the ``installed`` candidates, in
+    order); ``utility``: the expected information gain after 0, 1, .. sensors (installed ones first), from the log-determinants the
+    updates report - len(installed) + n_select + 1 values starting at 0; ``first_gains`` (M): every candidate's gain at the first free
+    step; ``gain_history`` (n_select, M) with ``keep_gains``; ``expected_cov``: n_select + 1 matrices, the expected posterior
+    covariance before the first free step and after each one; ``prior_precision``; ``path``: "device" or "numpy"."""
+    selected = selected_points = gains = installed_gains = utility = first_gains = gain_history = expected_cov = None
+    prior_precision = path = None
+
+
+def _grid_derivative_coefficients(tables, dtables, n, s):
+    """(CD, idx): CD[d] (K, len(s)) holds cd_t(s) = 1 * U_0[t, i_0] * U_1[t, i_1] * .. with U_f = dtables[f] for f == d, tables[f]
+    otherwise - one chain in ascending f per coordinate d (pgd_design_update / pgd_design_gains)."""
+    idx = np.unravel_index(s, n)
+    D = len(tables)
+    CD = np.ones((D, tables[0].shape[0], len(s)))
+    for d in range(D):
+        for f in range(D):
+            CD[d] *= (dtables[f] if f == d else tables[f])[:, idx[f]]
+    return CD, idx
+
+
+def _cholesky_inverse_batch(H):
+    """W (.., D, D), the inverse of the lower Cholesky factor of every H (.., D, D): the factor row by row, W by forward substitution
+    of the columns of the identity (the arithmetic of k_design_update, vectorised over the leading axes)."""
+    D = H.shape[-1]
+    L, W = np.zeros_like(H), np.zeros_like(H)
+    for i in range(D):
+        for j in range(i + 1):
+            t = H[..., j, i] - np.einsum("...m,...m->...", L[..., i, :j], L[..., j, :j])
+            L[..., i, j] = np.sqrt(t) if i == j else t / L[..., j, j]
+    for j in range(D):
+        W[..., j, j] = 1.0 / L[..., j, j]
+        for i in range(j + 1, D):
+            W[..., i, j] = -np.einsum("...m,...m->...", L[..., i, j:i], W[..., j:i, j]) / L[..., i, i]
+    return W
+
+
+def design_state_numpy(n):
+    """The state of the numpy route on the grid of ``n`` points per dimension: H_s and W_s as full (S, D, D) arrays."""
+    S, D = int(np.prod(n, dtype=np.int64)), len(n)
+    return {"H": np.zeros((S, D, D)), "W": np.zeros((S, D, D))}
+
+
+def design_update_numpy(state, tables, dtables, weights, rows=None, h0=None, sample_chunk=1 << 14):
+    """The arithmetic of ``pgd_design_update`` in numpy, ``sample_chunk`` samples at a time: (sum w log det H, sum w H^-1)."""
+    n = [t.shape[1] for t in tables]
+    S, D = int(np.prod(n, dtype=np.int64)), len(n)
+    rows = np.zeros((0, tables[0].shape[0])) if rows is None else np.asarray(rows, dtype=np.float64).reshape(-1, tables[0].shape[0])
+    logdet, cov = 0.0, np.zeros((D, D))
+    for s0 in range(0, S, int(sample_chunk)):
+        s = np.arange(s0, min(S, s0 + int(sample_chunk)))
+        sl = slice(s0, s0 + len(s))
+        CD, idx = _grid_derivative_coefficients(tables, dtables, n, s)
+        H = state["H"][sl]
+        if h0 is not None:
+            H[:] = np.asarray(h0, dtype=np.float64)
+        if rows.shape[0]:
+            G = np.einsum("rt,dts->rds", rows, CD)                           # (R, D, s)
+            for r in range(rows.shape[0]):
+                H += G[r].T[:, :, None] * G[r].T[:, None, :]
+        W = _cholesky_inverse_batch(H)
+        state["W"][sl] = W
+        w = np.ones(len(s))
+        for d in range(D):
+            w *= weights[d][idx[d]]
+        logdet += float(np.sum(w * (-2.0 * np.sum(np.log(np.einsum("sii->si", W)), axis=1))))
+        cov += np.einsum("s,smi,smj->ij", w, W, W)
+    return logdet, np.triu(cov) + np.triu(cov, 1).T
+
+
+def design_gains_numpy(a, R, state, tables, dtables, weights, work=1 << 22):
+    """The arithmetic of ``pgd_design_gains`` in numpy, in chunks of samples that keep the Jacobians below ``work`` doubles: the gains
+    of the M candidates whose R rows each are the rows of ``a`` (M R, k), from the LDL^T pivots of I + V^T V as log1p(pivot - 1)."""
+    a = np.asarray(a, dtype=np.float64)
+    n = [t.shape[1] for t in tables]
+    S, D, M = int(np.prod(n, dtype=np.int64)), len(n), a.shape[0] // R
+    chunk = max(int(work) // max(a.shape[0] * D, 1), 1)
+    gains = np.zeros(M)
+    for s0 in range(0, S, chunk):
+        s = np.arange(s0, min(S, s0 + chunk))
+        CD, idx = _grid_derivative_coefficients(tables, dtables, n, s)
+        G = np.stack([a @ CD[d] for d in range(D)])                           # (D, M R, s)
+        W = state["W"][s0:s0 + len(s)]
+        V = np.stack([np.einsum("sj,jps->ps", W[:, i, :i + 1], G[:i + 1]) for i in range(D)]).reshape(D, M, R, len(s))
+        # LDL^T of I + V^T V without the 1 on the diagonal: mm[p][q] is row p of the Schur complement, mm[p][p] = pivot p less 1
+        mm, lf, val = {}, {}, 0.0
+        for p in range(R):
+            for q in range(p, R):
+                t = np.einsum("ims,ims->ms", V[:, :, p], V[:, :, q])
+                for r in range(p):
+                    t = t - lf[p, r] * mm[r, q]
+                mm[p, q] = t
+            val = val + np.log1p(mm[p, p])
+            for q in range(p + 1, R):
+                lf[q, p] = mm[p, q] / (1.0 + mm[p, p])
+        w = np.ones(len(s))
+        for d in range(D):
+            w *= weights[d][idx[d]]
+        gains += (val * w).sum(axis=1)
+    return 0.5 * gains
+
+
 class PGD:
     def __init__(self, name=None, n_modes=0, fmeshes=[], pgd_modes=[], name_coord=[], modes_info=[],
                  verbose=False, *args, **kwargs):
@@ -2457,6 +2569,135 @@ class PGD:
         if want & POST_THETA:
             res.mean = sums["theta1"] / Zs[:, None]
             res.cov = sums["theta2"] / Zs[:, None, None] - res.mean[:, :, None] * res.mean[:, None, :]
+        return res
+
+    def sensor_placement(self, fixed_dim, free_dim, attri, candidate_points, n_select, grids=None, coords=None, sigma=1.0, prior=None,
+                         prior_precision=None, quadrature="trapezoid", gradient=False, group="point", installed=None, exclude=None,
+                         keep_gains=False, device=None, index=None):
+        """Of the M places where a sensor could be mounted, the ``n_select`` that make the posterior of the free coordinates narrowest,
+        chosen greedily by the expected information gain in the linearised (Laplace) form - Bayesian D-optimality - before any data
+        exists: a ``PlacementResult``.
+
+        Samples, ``prior`` and ``quadrature`` are ``sensor_posterior``'s on ``grids`` (scattered ``coords`` are refused); the noise is
+        independent, ``sigma`` a scalar or an array shaped like one sample's data (no ``cov``: rank-one gains need independent noise).
+        ``group``: "point" - a sensor is everything measured at a point, R = prod(shape[1:]) rows - or "entry": every scalar entry is
+        its own candidate, R = 1.  With the parameter Jacobian g_p(s) of row p at sample s (the whitened ``sensor_modes`` against the
+        derivative coefficients of ``mode_factor_derivatives_many``) and H_s = prior_precision + sum of g g^T over the rows chosen so
+        far, the utility is 1/2 sum_s w_s [log det H_s - log det prior_precision], and a candidate's marginal gain
+        1/2 sum_s w_s log det(I + V^T V), V = W_s [g ..], W_s the inverse Cholesky factor of H_s.  ``prior_precision``: a symmetric
+        positive definite D x D matrix, or None: diag(1 / var_d) of each dimension's normalised weights over its abscissae.
+        ``installed``: candidates applied first, in order (their gains in ``installed_gains``); ``exclude``: never chosen; a chosen
+        candidate is not offered again; ties go to the lowest index.
+
+        On the device (``pgd_design_update`` / ``pgd_design_gains``: the M x S x R x D Jacobian is never stored) when the backend has
+        ``design_gains``, at most 64 modes, R <= 3 and M S >= DEVICE_PLACEMENT_MIN_WORK (``device``: force either route), otherwise the
+        same arithmetic in numpy, in chunks of samples.  ``index``: handed to ``sensor_modes``."""
+        name = "sensor_placement"
+        if coords is not None:
+            raise ValueError("sensor_placement: scattered samples (coords) are not taken, only grids")
+        if group not in ("point", "entry"):
+            raise ValueError("sensor_placement: group must be 'point' or 'entry', got %r" % (group,))
+        free_dim, K, absc, tables, weights, quad, shape, S, _ = self._posterior_samples(name, fixed_dim, free_dim, attri, grids, None, prior,
+                                                                                         quadrature)
+        D = len(free_dim)
+        dtables = [np.ascontiguousarray(self._free_mode_derivatives_at(d, x, attri)) for d, x in zip(free_dim, absc)]
+        # ---- the whitened sensor modes of the candidates
+        points = np.asarray(candidate_points, dtype=np.float64)
+        sm = self.sensor_modes(candidate_points, fixed_dim, attri, gradient=gradient, device=None, index=index)
+        m = sm.m
+        A = sm.host()[:K].T                                                  # (m, K), rows in the order (point, component[, axis])
+        A, _, _ = self._posterior_whitening(name, A, m, sigma, None)
+        A = np.ascontiguousarray(A)
+        per_point = int(np.prod(sm.shape[1:], dtype=np.int64))
+        R = per_point if group == "point" else 1
+        M = m // R
+        # ---- the prior precision
+        if prior_precision is None:
+            var = np.array([float(w @ (x * x) - (w @ x) ** 2) for w, x in zip(weights, absc)])
+            if not np.all(var > 0.0):
+                raise ValueError("sensor_placement: dimension %d has zero variance under its weights; give prior_precision"
+                                 % free_dim[int(np.argmin(var > 0.0))])
+            H0 = np.diag(1.0 / var)
+        else:
+            H0 = np.array(prior_precision, dtype=np.float64)
+            ok = H0.shape == (D, D) and np.all(np.isfinite(H0)) and np.array_equal(H0, H0.T)
+            if ok:
+                try:
+                    np.linalg.cholesky(H0)
+                except np.linalg.LinAlgError:
+                    ok = False
+            if not ok:
+                raise ValueError("sensor_placement: prior_precision must be a symmetric positive definite %d x %d matrix" % (D, D))
+        H0 = np.ascontiguousarray(H0)
+        # ---- what is on offer
+        def indices(what, v):
+            v = np.asarray([] if v is None else v, dtype=np.int64).reshape(-1)
+            if v.size and (v.min() < 0 or v.max() >= M):
+                raise ValueError("sensor_placement: %s names candidate %d, there are %d" % (what, int(v[(v < 0) | (v >= M)][0]), M))
+            return [int(j) for j in v]
+        installed, exclude = indices("installed", installed), indices("exclude", exclude)
+        n_select = int(n_select)
+        taken = np.zeros(M, dtype=bool)
+        taken[installed] = True
+        taken[exclude] = True
+        if n_select < 0 or n_select > M - int(taken.sum()):
+            raise ValueError("sensor_placement: n_select = %d, %d candidates are on offer" % (n_select, M - int(taken.sum())))
+        # ---- the route
+        be = fem.get_backend()
+        has = hasattr(be, "design_gains")
+        fits = K <= PLACEMENT_MAX_MODES and R <= PLACEMENT_MAX_ROWS
+        on_device = (has and fits and M * S >= DEVICE_PLACEMENT_MIN_WORK) if device is None else bool(device)
+        if on_device and not fits:
+            raise ValueError("sensor_placement(device=True): %d modes and %d rows per candidate, the device takes at most %d and %d: "
+                             "compress the solution first (PGD.compress), or make every entry a candidate (group=\"entry\")"
+                             % (K, R, PLACEMENT_MAX_MODES, PLACEMENT_MAX_ROWS))
+        if on_device and not has:
+            raise NotImplementedError("sensor_placement(device=True): the backend %r has no design_gains" % (getattr(be, "name", be),))
+        n = [int(v) for v in shape]
+        if on_device:
+            state = be.design_state(n)
+            update = lambda **kw: be.design_update(state, tables, dtables, weights, **kw)
+            gains_of = lambda a: be.design_gains(a, R, state, tables, dtables, weights)
+            fem.STATS["placement_calls"] = fem.STATS.get("placement_calls", 0) + 1
+        else:
+            state = design_state_numpy(n)
+            update = lambda **kw: design_update_numpy(state, tables, dtables, weights, **kw)
+            gains_of = lambda a: design_gains_numpy(a, R, state, tables, dtables, weights)
+        rows_of = lambda j: A[j * R:(j + 1) * R]
+        res = PlacementResult()
+        res.path, res.prior_precision = "device" if on_device else "numpy", H0
+        try:
+            logdet0, cov = update(h0=H0)
+            logdets, covs = [logdet0], []
+            res.installed_gains = np.zeros(len(installed))
+            for i, j in enumerate(installed):
+                res.installed_gains[i] = gains_of(rows_of(j))[0]
+                ld, cov = update(rows=rows_of(j))
+                logdets.append(ld)
+            covs.append(cov)
+            res.selected, res.gains = np.zeros(n_select, dtype=np.int64), np.zeros(n_select)
+            res.gain_history = np.zeros((n_select, M)) if keep_gains else None
+            for step in range(n_select):
+                g = gains_of(A)
+                if step == 0:
+                    res.first_gains = g.copy()
+                if keep_gains:
+                    res.gain_history[step] = g
+                j = int(np.argmax(np.where(taken, -np.inf, g)))              # (argmax: the lowest index among equal gains)
+                taken[j] = True
+                res.selected[step], res.gains[step] = j, g[j]
+                ld, cov = update(rows=rows_of(j))
+                logdets.append(ld)
+                covs.append(cov)
+        finally:
+            if on_device:
+                be.vec_free(state)
+        if res.first_gains is None:
+            res.first_gains = np.zeros(0)
+        res.utility = 0.5 * (np.array(logdets) - logdets[0])
+        res.expected_cov = np.stack(covs)
+        pts = points.reshape(sm.shape[0], -1) if points.size else points
+        res.selected_points = pts[res.selected if group == "point" else res.selected // per_point]
         return res
 
     def posterior_predictive(self, res, fixed_dim, attri):

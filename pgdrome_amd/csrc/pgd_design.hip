@@ -12,12 +12,12 @@
 // k_design_update<ND>: a thread per sample.  H_s (= h0 first, if given) += g_r g_r^T for the R rows, g from fma chains in ascending t,
 // the products into H in ascending r; the Cholesky factor L (row by row, fma chains in ascending column), W by forward substitution
 // of the columns of the identity; sums[0] += w_s (-2 sum_i log W_ii), sums[1 + c] += w_s (W^T W)_c (upper triangle, row order).
-// H is only ever added to.  The partial sums of a segment (post_segments: a function of S alone) are formed in an order that depends
-// on the segment alone; k_design_sum adds the segments in ascending order.
+// H is only ever added to.  The partial sums of a segment (grid_segments: a function of S alone) are formed in an order that depends
+// on the segment alone; k_seg_sum adds the segments in ascending order.
 //
 // k_design_gains_mfma<R, ND>: the Jacobians of ALL candidates at ALL samples as one dense product on v_mfma_f64_16x16x4_f64 that is
 // never stored.  Lane (lq, lr) = (lane >> 4, lane & 15).  A: 16 candidates on the row index, lane holds a[row r of candidate 16 ct + lr]
-// [t = 4 q + lq] (the host lays a out in fragment order per plane r: post_af_index, zero padded).  B: 16 samples on the column index, lane
+// [t = 4 q + lq] (the host lays a out in fragment order per plane r: pack_a_fragments, zero padded).  B: 16 samples on the column index, lane
 // holds cd_{4 q + lq}(sample lr).  acc[r][d][rr] = g_{r, d} of candidate 16 ct + 4 rr + lq at sample lr: a lane holds the same
 // (candidate, sample) entry of all R ND tiles, the epilogue is lane-local (design_gain below), then w_s times it.
 //   * A workgroup takes one (chunk of at most 2048 candidates, segment of the samples) at a time.  It stages the derivative coefficients
@@ -26,7 +26,7 @@
 //     the chunk's candidate tiles (wave w: tiles w, w + 4, ..): A from global memory (L2) four k-steps at a time, B from LDS.
 //   * The 16 sample lanes are added by a fixed xor tree (1, 2, 4, 8), the lanes lr == 0 add into the candidate's accumulator in LDS:
 //     one writer wave per accumulator, blocks and tiles in ascending order.  part[seg * Mp + j] = the segment's sum of candidate j.
-//   * k_design_sum: gains[j] = 1/2 of the sum over the segments in ascending order.
+//   * k_seg_sum: gains[j] = 1/2 of the sum over the segments in ascending order.
 // No floating-point atomics.  A row of an MFMA result does not depend on the other rows, the order of a candidate's sum depends on the
 // segment alone: every gain is the same bits from run to run, for any grid (PGD_TUNE_DESIGN_GRID_MAX), for any chunking, alone or among
 // others, at any position.
@@ -198,16 +198,6 @@ __global__ __launch_bounds__(TPB) void k_design_update(PostDims P, const double 
     }
 }
 
-// out[i] = scale times the sum over the segments, ascending, of part[seg * stride + i]
-__global__ __launch_bounds__(TPB) void k_design_sum(const double *__restrict__ part, int nseg, int64_t stride, int64_t n, double scale,
-                                                    double *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= n) return;
-    double t = 0.0;
-    for (int seg = 0; seg < nseg; ++seg) t += part[(size_t)seg * stride + i];
-    out[i] = scale * t;
-}
-
 // af: R planes of (Mp / 16) tiles of kt k-steps of 64 doubles; ncc chunks of cc candidates (cc a multiple of 64, Mp of 16)
 template <int R, int ND>
 __global__ __launch_bounds__(TPB) void k_design_gains_mfma(PostDims P, const double *__restrict__ tab, const double *__restrict__ dtab, int k, int kt,
@@ -250,11 +240,11 @@ __global__ __launch_bounds__(TPB) void k_design_gains_mfma(PostDims P, const dou
                 const double wj = s_w[16 * j + lr];
 #pragma unroll 1
                 for (int ct = wv; ct < ntile; ct += 4) {
-                    po_d4 acc[R][ND];
+                    d4_t acc[R][ND];
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
 #pragma unroll
-                        for (int d = 0; d < ND; ++d) acc[r][d] = po_d4{0.0, 0.0, 0.0, 0.0};
+                        for (int d = 0; d < ND; ++d) acc[r][d] = d4_t{0.0, 0.0, 0.0, 0.0};
                     }
                     const double *ap = af + ((size_t)(c0 / 16 + ct) * kt) * 64 + lane;
                     const double *bp = s_b + (size_t)lq * SB + 16 * j + lr;
@@ -368,36 +358,16 @@ template <int R, int ND>
 static int design_launch_mfma(Ctx *c, const DsArgs &A) {
     constexpr int SB = ds_sb(ND);
     const size_t lds = ((size_t)ND * 4 * A.kt * SB + SB + A.cc) * sizeof(double);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)k_design_gains_mfma<R, ND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, PGD_ERR_HIP, "design_gains: %zu bytes of LDS refused", lds);
-    }
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_design_gains_mfma<R, ND>, TPB, lds) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
-    const int64_t nitem = (int64_t)A.ncc * A.nseg;
-    int64_t g = (int64_t)c->num_cu * occ;
-    if (c->design_grid_max > 0 && g > c->design_grid_max) g = c->design_grid_max;
-    if (g > nitem) g = nitem;
-    k_design_gains_mfma<R, ND><<<(int)g, TPB, lds, c->stream>>>(A.P, A.tab, A.dtab, A.k, A.kt, A.a, A.plane, A.wts, A.state, A.S, A.nseg, A.seglen,
-                                                              A.ncc, A.cc, A.Mp, A.part);
-    PGD_LAUNCH_CHECK(c);
-    return PGD_OK;
+    PGD_TRY(raise_lds(c, (const void *)k_design_gains_mfma<R, ND>, lds, "design_gains"));
+    return launch_persistent(c, k_design_gains_mfma<R, ND>, TPB, lds, (int64_t)A.ncc * A.nseg, c->design_grid_max, 0, nullptr, A.P, A.tab, A.dtab, A.k, A.kt,
+                             A.a, A.plane, A.wts, A.state, A.S, A.nseg, A.seglen, A.ncc, A.cc, A.Mp, A.part);
 }
 
 template <int R, int ND>
 static int design_launch_plain(Ctx *c, const DsArgs &A) {
     const int ncb = (int)((A.M + TPB - 1) / TPB);
-    const int64_t nitem = (int64_t)ncb * A.nseg;
-    int64_t g = (int64_t)c->num_cu * 4;
-    if (c->design_grid_max > 0 && g > c->design_grid_max) g = c->design_grid_max;
-    if (g > nitem) g = nitem;
-    k_design_gains_plain<R, ND><<<(int)g, TPB, 0, c->stream>>>(A.P, A.tab, A.dtab, A.k, A.a, A.wts, A.state, A.S, A.nseg, A.seglen, ncb, A.M, A.Mp,
-                                                             A.part);
-    PGD_LAUNCH_CHECK(c);
-    return PGD_OK;
+    return launch_persistent(c, k_design_gains_plain<R, ND>, TPB, 0, (int64_t)ncb * A.nseg, c->design_grid_max, 4, nullptr, A.P, A.tab, A.dtab, A.k, A.a,
+                             A.wts, A.state, A.S, A.nseg, A.seglen, ncb, A.M, A.Mp, A.part);
 }
 
 template <int R>
@@ -478,7 +448,7 @@ int pgd_design_update(pgd_handle h, const double *h0, const double *rows, int R,
     const int nh = ds_nh(ndim), nv = 1 + nh;
     int nseg = 1;
     int64_t seglen = 0;
-    post_segments(S, &nseg, &seglen);
+    grid_segments(S, PO_SEGMIN, &nseg, &seglen);
     std::vector<double> hbuf((size_t)R * k + nh, 0.0);          // the rows, then the upper triangle of h0
     if (R > 0) std::copy(rows, rows + (size_t)R * k, hbuf.begin());
     if (h0) {
@@ -486,11 +456,8 @@ int pgd_design_update(pgd_handle h, const double *h0, const double *rows, int R,
         for (int i = 0; i < ndim; ++i)
             for (int j = i; j < ndim; ++j, ++cc) hbuf[(size_t)R * k + cc] = h0[i * ndim + j];
     }
-    const size_t bytes = pool_bytes(2 * (size_t)ntab + (size_t)nw + hbuf.size());
-    void *p_in = nullptr;
-    PGD_TRY(dev_alloc(c, &p_in, bytes));
     double out[1 + PO_DMAX * (PO_DMAX + 1) / 2];
-    auto run = [&]() -> int {
+    const int rc = with_pool_input(c, pool_bytes(2 * (size_t)ntab + (size_t)nw + hbuf.size()), [&](void *p_in) -> int {
         PGD_TRY(ensure_work(c, 6, nv));
         PGD_TRY(ensure_partials(c, (int64_t)nseg * nv));
         double *tab = (double *)p_in, *dtab = tab + ntab, *wd = dtab + ntab, *rd = wd + nw, *hd = rd + (size_t)R * k;
@@ -511,15 +478,11 @@ int pgd_design_update(pgd_handle h, const double *h0, const double *rows, int R,
             default: design_update_go<6>(c, g, P, tab, dtab, k, R, rd, h0d, wd, S, nseg, seglen, sv->d, c->partials); break;
         }
         PGD_LAUNCH_CHECK(c);
-        k_design_sum<<<1, TPB, 0, c->stream>>>(c->partials, nseg, nv, nv, 1.0, c->work[6]);
-        PGD_LAUNCH_CHECK(c);
+        PGD_TRY(seg_sum(c, c->partials, nseg, nv, nv, 1.0, c->work[6]));
         PGD_HIP(c, hipMemcpyAsync(out, c->work[6], (size_t)nv * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         PGD_HIP(c, hipStreamSynchronize(c->stream));   // the one synchronisation of the call
         return PGD_OK;
-    };
-    const int rc = run();
-    if (rc != PGD_OK) (void)hipStreamSynchronize(c->stream);   // nothing reads the inputs once they go back to the pool
-    dev_release(c, p_in, bytes);
+    });
     if (rc != PGD_OK) return rc;
     std::copy(out, out + nv, sums);
     return PGD_OK;
@@ -540,9 +503,9 @@ int pgd_design_gains(pgd_handle h, const double *a, int64_t M, int R, int k, con
 
     int nseg = 1;
     int64_t seglen = 0;
-    post_segments(S, &nseg, &seglen);
+    grid_segments(S, PO_SEGMIN, &nseg, &seglen);
     const bool mfma = c->design_variant != 0;
-    const int kt = post_kt(k);
+    const int kt = dense_kt(k);
     // ---- the candidates of a work item (enough items for the device, a tile per wave at least), those of a chunk of device scratch
     int64_t cc = (M * nseg / (2 * (int64_t)c->num_cu) + 63) / 64 * 64;
     cc = std::min<int64_t>(std::max<int64_t>(cc, DS_CHUNK_MIN), DS_CHUNK);
@@ -551,10 +514,7 @@ int pgd_design_gains(pgd_handle h, const double *a, int64_t M, int R, int k, con
     const int64_t mp_max = std::min(chunk, (M + 15) / 16 * 16);
     const size_t na_max = mfma ? (size_t)R * (mp_max / 16) * kt * 64 : (size_t)std::min(chunk, M) * R * k;
     std::vector<double> ha(mfma ? na_max : 0, 0.0), res((size_t)M);
-    const size_t bytes = pool_bytes(2 * (size_t)ntab + (size_t)nw + na_max);
-    void *p_in = nullptr;
-    PGD_TRY(dev_alloc(c, &p_in, bytes));
-    auto run = [&]() -> int {
+    const int rc = with_pool_input(c, pool_bytes(2 * (size_t)ntab + (size_t)nw + na_max), [&](void *p_in) -> int {
         PGD_TRY(ensure_work(c, 6, mp_max));
         PGD_TRY(ensure_partials(c, (int64_t)nseg * mp_max));
         double *tab = (double *)p_in, *dtab = tab + ntab, *wd = dtab + ntab, *ad = wd + nw;
@@ -566,12 +526,7 @@ int pgd_design_gains(pgd_handle h, const double *a, int64_t M, int R, int k, con
             const int64_t plane = (Mp / 16) * kt * 64;
             if (mfma) {
                 std::fill(ha.begin(), ha.begin() + (size_t)R * plane, 0.0);
-                for (int64_t j = 0; j < cn; ++j)
-                    for (int r = 0; r < R; ++r) {
-                        const double *row = a + ((size_t)(j0 + j) * R + r) * k;
-                        double *f = ha.data() + (size_t)r * plane + ((size_t)(j >> 4) * kt) * 64 + (j & 15);
-                        for (int t = 0; t < k; ++t) f[(size_t)(t >> 2) * 64 + ((t & 3) << 4)] = row[t];      // post_af_index
-                    }
+                for (int r = 0; r < R; ++r) pack_a_fragments(ha.data() + (size_t)r * plane, kt, a + ((size_t)j0 * R + r) * k, cn, k, (size_t)R * k);
                 PGD_HIP(c, hipMemcpyAsync(ad, ha.data(), (size_t)R * plane * sizeof(double), hipMemcpyHostToDevice, c->stream));
             } else {
                 PGD_HIP(c, hipMemcpyAsync(ad, a + (size_t)j0 * R * k, (size_t)cn * R * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -585,16 +540,12 @@ int pgd_design_gains(pgd_handle h, const double *a, int64_t M, int R, int k, con
                 case 2: PGD_TRY(design_launch_nd<2>(c, mfma, ndim, A)); break;
                 default: PGD_TRY(design_launch_nd<3>(c, mfma, ndim, A)); break;
             }
-            k_design_sum<<<(int)((cn + TPB - 1) / TPB), TPB, 0, c->stream>>>(c->partials, nseg, Mp, cn, 0.5, c->work[6]);
-            PGD_LAUNCH_CHECK(c);
+            PGD_TRY(seg_sum(c, c->partials, nseg, Mp, cn, 0.5, c->work[6]));
             PGD_HIP(c, hipMemcpyAsync(res.data() + j0, c->work[6], (size_t)cn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
             PGD_HIP(c, hipStreamSynchronize(c->stream));   // the one synchronisation of the chunk
         }
         return PGD_OK;
-    };
-    const int rc = run();
-    if (rc != PGD_OK) (void)hipStreamSynchronize(c->stream);   // nothing reads the inputs once they go back to the pool
-    dev_release(c, p_in, bytes);
+    });
     if (rc != PGD_OK) return rc;
     std::copy(res.begin(), res.end(), gains);    // ---- the caller's array is written only now
     return PGD_OK;

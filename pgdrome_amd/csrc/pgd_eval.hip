@@ -43,7 +43,6 @@ constexpr int64_t EVAL_SMAX = (int64_t)1 << 24;
 constexpr int EVAL_PLAIN_TPB = 64;         // k_eval_plain: one wave per workgroup, one row per lane
 constexpr int EVAL_PLAIN_NS = 8;           // ... and this many samples per pass over the block's mode values
 
-typedef double d4_t __attribute__((ext_vector_type(4)));
 
 struct EvalModes { const double *p[EVAL_KMAX]; };
 
@@ -616,36 +615,15 @@ __global__ __launch_bounds__(TPB) void k_eval_finish(const double *__restrict__ 
     stats[2 * s_total + j0 + j] = fmax(fabs(mn), fabs(mx));
 }
 
-// Launch of a persistent matrix-unit kernel on the nblk row blocks of a call: as many workgroups as are resident at once (the
-// occupancy the runtime reports for this kernel and LDS size), at most grid_cap and at most one per row block
-template <class... P, class... A>
-static int eval_launch_persistent(Ctx *c, void (*kern)(P...), size_t lds, int64_t nblk, int grid_cap, int *grid_out, const A &...args) {
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, TPB, lds) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
-    int64_t g = (int64_t)c->num_cu * occ;
-    if (g > grid_cap) g = grid_cap;
-    if (g > nblk) g = nblk;
-    kern<<<(int)g, TPB, lds, c->stream>>>(args...);
-    PGD_LAUNCH_CHECK(c);
-    *grid_out = (int)g;
-    return PGD_OK;
-}
-
+// (the matrix-unit kernels are persistent over the row blocks of a call: launch_persistent with the occupancy the runtime reports)
 template <int KT, int T>
 static int eval_launch_mfma(Ctx *c, const EvalModes &M, int k, int64_t n, const double *cf, int cs, int64_t j0, int want,
                             int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const int cs16 = (cs + 15) & ~15;
     const size_t lds = ((size_t)4 * KT * 16 * T + 2 * (size_t)cs16 + 12 * 16 * T) * sizeof(double);
-    return eval_launch_persistent(c, k_eval_mfma<KT, T>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, n, cf, cs, j0, want,
+    return launch_persistent(c, k_eval_mfma<KT, T>, TPB, lds, (n + 16 * T - 1) / (16 * T), grid_cap, 0, grid_out, M, k, n, cf, cs, j0, want,
                                   first, thr, O);
 }
-
-// k-steps of 4 the kernel is compiled for: k <= 16, 32, 48, 64 with 64 rows per workgroup, <= 128 with 32, <= 256 with 16
-// (the B fragments of a wave are at most 64 doubles per lane)
-static int eval_kt(int k) { return k <= 16 ? 4 : k <= 32 ? 8 : k <= 48 ? 12 : k <= 64 ? 16 : k <= 128 ? 32 : 64; }
 
 // ---- k_eval_norm_mfma: the row block and where the B fragments come from, chosen once per call
 constexpr size_t EVAL_LDS_PLAIN = 64 * 1024;      // dynamic LDS a kernel may ask for as it is; up to EVAL_LDS_MAX with the function attribute
@@ -690,7 +668,7 @@ template <int T, bool LDSB, int QK>
 static int eval_launch_norm(Ctx *c, const EvalModes &M, int k, int kt, int q, int64_t n, const double *cf, int cs, int64_t j0, int want,
                             int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const size_t lds = eval_norm_lds(T, LDSB, q, kt, (cs + 15) & ~15);
-    return eval_launch_persistent(c, k_eval_norm_mfma<T, LDSB, QK>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q, n, cf,
+    return launch_persistent(c, k_eval_norm_mfma<T, LDSB, QK>, TPB, lds, (n + 16 * T - 1) / (16 * T), grid_cap, 0, grid_out, M, k, kt, q, n, cf,
                                   cs, j0, want, first, thr, O);
 }
 
@@ -1103,7 +1081,7 @@ template <int T, int G, int NC, int QK>
 static int eval_launch_grad(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf, int cs,
                             int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const size_t lds = eval_norm_lds(T, true, q, kt, (cs + 15) & ~15);
-    return eval_launch_persistent(c, k_eval_grad_mfma<T, G, NC, QK>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q, S, n, cf,
+    return launch_persistent(c, k_eval_grad_mfma<T, G, NC, QK>, TPB, lds, (n + 16 * T - 1) / (16 * T), grid_cap, 0, grid_out, M, k, kt, q, S, n, cf,
                                   cs, j0, want, first, thr, O);
 }
 
@@ -1286,7 +1264,7 @@ template <int T, int G, int NC, int QK>
 static int eval_launch_grad_p2(Ctx *c, const EvalModes &M, int k, int kt, int q, const EvalGradSrc &S, int64_t n, const double *cf, int cs,
                                int64_t j0, int want, int first, double thr, const EvalOut &O, int grid_cap, int *grid_out) {
     const size_t lds = eval_norm_lds(T, true, q, kt, (cs + 15) & ~15);
-    return eval_launch_persistent(c, k_eval_grad_p2_mfma<T, G, NC, QK>, lds, (n + 16 * T - 1) / (16 * T), grid_cap, grid_out, M, k, kt, q,
+    return launch_persistent(c, k_eval_grad_p2_mfma<T, G, NC, QK>, TPB, lds, (n + 16 * T - 1) / (16 * T), grid_cap, 0, grid_out, M, k, kt, q,
                                   static_cast<const EvalGradP2Src &>(S), n, cf, cs, j0, want, first, thr, O);
 }
 
@@ -1441,7 +1419,7 @@ static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_
     if (n == 0) return PGD_OK;
 
     const bool mfma = c->eval_variant != 0;
-    const int kt = (mfma && q == 0) ? eval_kt(k) : (k + 3) / 4;
+    const int kt = (mfma && q == 0) ? dense_kt(k) : (k + 3) / 4;
     int64_t chunk = c->eval_chunk > 0 ? c->eval_chunk : EVAL_CHUNK_DEFAULT;
     if (chunk > s) chunk = s;
     const int cs16_max = (int)((chunk + 15) & ~(int64_t)15);
@@ -1528,14 +1506,10 @@ static int eval_batch_run(Ctx *c, const char *fn, const EvalGrad *gs, const pgd_
             } else if (q > 0) {
                 PGD_TRY(nfn.launch(c, mfma, ncfg, M, k, kt, q, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g));
             } else if (mfma) {
-                switch (kt) {
-                    case 4: PGD_TRY((eval_launch_mfma<4, 4>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g))); break;
-                    case 8: PGD_TRY((eval_launch_mfma<8, 4>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g))); break;
-                    case 12: PGD_TRY((eval_launch_mfma<12, 4>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g))); break;
-                    case 16: PGD_TRY((eval_launch_mfma<16, 4>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g))); break;
-                    case 32: PGD_TRY((eval_launch_mfma<32, 2>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g))); break;
-                    default: PGD_TRY((eval_launch_mfma<64, 1>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g))); break;
-                }
+                // (KT k-steps with 16 T rows per workgroup: 64 up to 64 modes, 32 up to 128, 16 up to 256)
+                PGD_TRY(dense_dispatch(kt, [&](auto KT, auto T) {
+                    return eval_launch_mfma<decltype(KT)::value, decltype(T)::value>(c, M, k, n, cf, cs, j0, want, first, threshold, O, (int)gmax, &g);
+                }));
             } else {
                 const int64_t nblk = (n + EVAL_PLAIN_TPB - 1) / EVAL_PLAIN_TPB;
                 g = (int)(nblk < gmax ? nblk : gmax);

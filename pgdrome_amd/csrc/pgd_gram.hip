@@ -36,7 +36,6 @@ constexpr int GM_SEG_MAX = 1024;        // segments per call
 constexpr int GM_TPW_MAX = 13;          // tiles per wave the MFMA kernel is compiled for: 256 vector registers, two waves per SIMD
 constexpr int GM_SEG_MIN_BLOCKS = 8;    // row blocks per segment at least (a partial is written per segment)
 
-typedef double gm_d4 __attribute__((ext_vector_type(4)));
 
 struct GramVecs { const double *p[2 * GM_KMAX]; };   // x_0 .. at 0, y_0 .. at GM_KMAX
 
@@ -129,9 +128,9 @@ __global__ __launch_bounds__(TPB, NIT > 0 ? (TPW <= 3 ? 4 : 2) : TPW <= 6 ? 4 : 
     const int64_t pstride = (int64_t)kxp * kyp;
     for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
         const int64_t r0 = lo + (int64_t)seg * seg_rows, r1 = r0 + seg_rows < hi ? r0 + seg_rows : hi;
-        gm_d4 acc[TPW];
+        d4_t acc[TPW];
 #pragma unroll
-        for (int s = 0; s < TPW; ++s) acc[s] = gm_d4{0.0, 0.0, 0.0, 0.0};
+        for (int s = 0; s < TPW; ++s) acc[s] = d4_t{0.0, 0.0, 0.0, 0.0};
         double val[NIT > 0 ? NIT : 1];
         if constexpr (NIT > 0) gram_fetch<NIT>(V, kx, ky, kxp, nv, r0, r1, val);
         for (int64_t rb = r0; rb < r1; rb += GM_RB) {
@@ -243,21 +242,8 @@ static void gram_segments(int64_t lo, int64_t hi, int64_t *seg_rows, int *nseg) 
 template <class K>
 static int gram_launch(Ctx *c, K kern, size_t lds, int nseg, const GramVecs &V, int kx, int ky, int sym, int64_t lo, int64_t hi,
                        int64_t seg_rows, double *part) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, PGD_ERR_HIP, "vec_gram: %zu bytes of LDS refused", lds);
-    }
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, TPB, lds) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
-    int64_t g = (int64_t)c->num_cu * occ;
-    if (c->gram_grid_max > 0 && g > c->gram_grid_max) g = c->gram_grid_max;
-    if (g > nseg) g = nseg;
-    kern<<<(int)g, TPB, lds, c->stream>>>(V, kx, ky, sym, lo, hi, seg_rows, nseg, part);
-    PGD_LAUNCH_CHECK(c);
-    return PGD_OK;
+    PGD_TRY(raise_lds(c, (const void *)kern, lds, "vec_gram"));
+    return launch_persistent(c, kern, TPB, lds, nseg, c->gram_grid_max, 0, nullptr, V, kx, ky, sym, lo, hi, seg_rows, nseg, part);
 }
 
 // One launch of the variant's kernel on the block and its finish into columns [j0, j0 + ky) of res (rows of ldo entries)

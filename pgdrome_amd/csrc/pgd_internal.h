@@ -10,6 +10,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pgd_amd.h"
@@ -648,6 +649,92 @@ inline int grid_for(int64_t n, int per_block = TPB, int cap = MAX_VEC_BLOCKS) {
     if (g < 1) g = 1;
     if (g > cap) g = cap;
     return (int)g;
+}
+
+// ---- what the dense products on v_mfma_f64_16x16x4_f64 share (pgd_eval, pgd_gram, pgd_quad, pgd_post, pgd_postmany, pgd_design)
+typedef double d4_t __attribute__((ext_vector_type(4)));       // the accumulator of one instruction
+
+// Dynamic LDS beyond 64 KiB has to be asked for, kernel by kernel (the attribute belongs to one instantiation); who: the call's name
+inline int raise_lds(Ctx *c, const void *kern, size_t lds, const char *who) {
+    if (lds <= 64 * 1024 || hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) return PGD_OK;
+    (void)hipGetLastError();
+    return fail(c, PGD_ERR_HIP, "%s: %zu bytes of LDS refused", who, lds);
+}
+
+// Workgroups of a persistent kernel over nitems work items: what is resident at once - `resident` workgroups per CU, or with
+// resident = 0 the occupancy the runtime reports for this kernel, block and LDS size (1 where it reports none) - at most grid_cap
+// (<= 0: no cap) and at most one per item
+template <class... P>
+int64_t persistent_grid(Ctx *c, void (*kern)(P...), int tpb, size_t lds, int64_t nitems, int64_t grid_cap, int resident = 0) {
+    if (resident < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, tpb, lds) != hipSuccess || resident < 1)) {
+        (void)hipGetLastError();
+        resident = 1;
+    }
+    int64_t g = (int64_t)c->num_cu * resident;
+    if (grid_cap > 0 && g > grid_cap) g = grid_cap;
+    return g < nitems ? g : nitems;
+}
+
+template <class... P, class... A>
+int launch_grid(Ctx *c, void (*kern)(P...), int64_t g, int tpb, size_t lds, const A &...args) {
+    kern<<<(int)g, tpb, lds, c->stream>>>(args...);
+    PGD_LAUNCH_CHECK(c);
+    return PGD_OK;
+}
+
+// ... both at once, for the callers whose buffers do not depend on the grid (it comes back in *grid_out, if asked for)
+template <class... P, class... A>
+int launch_persistent(Ctx *c, void (*kern)(P...), int tpb, size_t lds, int64_t nitems, int64_t grid_cap, int resident, int *grid_out,
+                      const A &...args) {
+    const int64_t g = persistent_grid(c, kern, tpb, lds, nitems, grid_cap, resident);
+    if (grid_out) *grid_out = (int)g;
+    return launch_grid(c, kern, g, tpb, lds, args...);
+}
+
+// k-steps of 4 of the instance for k modes: k <= 16, 32, 48, 64, 128, 256.  An instance holds T = 4, 4, 4, 4, 2, 1 tiles of 16 per
+// wave: the B fragments are at most 64 doubles per lane
+inline int dense_kt(int k) { return k <= 16 ? 4 : k <= 32 ? 8 : k <= 48 ? 12 : k <= 64 ? 16 : k <= 128 ? 32 : 64; }
+
+// f(KT, T) for the instance of kt k-steps, both as std::integral_constant; KTMAX = 16: the callers that stop at 64 modes instantiate
+// nothing beyond it
+template <int KTMAX = 64, class F>
+int dense_dispatch(int kt, F &&f) {
+    static_assert(KTMAX == 16 || KTMAX == 64, "the instances end at 64 or at 256 modes");
+    using std::integral_constant;
+    switch (kt) {
+        case 4: return f(integral_constant<int, 4>(), integral_constant<int, 4>());
+        case 8: return f(integral_constant<int, 8>(), integral_constant<int, 4>());
+        case 12: return f(integral_constant<int, 12>(), integral_constant<int, 4>());
+    }
+    if constexpr (KTMAX > 16) {
+        if (kt == 32) return f(integral_constant<int, 32>(), integral_constant<int, 2>());
+        if (kt != 16) return f(integral_constant<int, 64>(), integral_constant<int, 1>());
+    }
+    return f(integral_constant<int, 16>(), integral_constant<int, 4>());
+}
+
+// The A operand of a row-major block, nrows rows of k entries ld apart, in fragment order: kt k-steps of 4 per tile of 16 rows, lane
+// (lq, lr) of k-step q of tile i reads entry (16 i + lr, 4 q + lq) at ((i kt + q) 64 + 16 lq + lr).  dst is zeroed by the caller
+inline void pack_a_fragments(double *dst, int kt, const double *rows, int64_t nrows, int k, size_t ld) {
+    for (int64_t p = 0; p < nrows; ++p) {
+        double *f = dst + ((size_t)(p >> 4) * kt) * 64 + (p & 15);
+        for (int t = 0; t < k; ++t) f[(size_t)(t >> 2) * 64 + ((t & 3) << 4)] = rows[(size_t)p * ld + t];
+    }
+}
+
+inline size_t pool_bytes(size_t n_doubles) { return (n_doubles * sizeof(double) + 65535) & ~(size_t)65535; }   // (whole 64 KiB: the pool takes them back)
+
+// The skeleton of a call whose inputs go up in one pooled buffer: run(p) queues the call's work and returns after its one
+// synchronisation; after a failure the stream is drained first - nothing reads the inputs once they go back to the pool.  The caller
+// writes its output arrays after this has returned PGD_OK
+template <class F>
+int with_pool_input(Ctx *c, size_t bytes, F &&run) {
+    void *p = nullptr;
+    PGD_TRY(dev_alloc(c, &p, bytes));
+    const int rc = run(p);
+    if (rc != PGD_OK) (void)hipStreamSynchronize(c->stream);
+    dev_release(c, p, bytes);
+    return rc;
 }
 
 // ---- launchers implemented across translation units

@@ -16,8 +16,8 @@
 // k_misfit_plain: the same from ordinary ascending fma chains, a lane per sample (PGD_TUNE_MISFIT_VARIANT = 0).
 //
 // pgd_grid_posterior: e_s = w_s exp(-(chi2[s] - shift) / 2), w_s = 1 * weights_0[i_0] * weights_1[i_1] * ..  No floating-point atomics:
-//   * S is cut into nseg <= 1024 segments of seglen samples (post_segments: a function of S alone); a workgroup forms the partial sums
-//     of a segment in an order that depends on the segment alone, k_post_finish adds the segments in ascending order.
+//   * S is cut into nseg <= 1024 segments of seglen samples (grid_segments: a function of S alone); a workgroup forms the partial sums
+//     of a segment in an order that depends on the segment alone, k_seg_sum adds the segments in ascending order.
 //   * Z, sum e^2 and the parameter moments: k_post_sums, one accumulator set per thread.
 //   * sum e c and sum e c c^T (k <= 64): k_post_coef_mfma.  The contraction runs over the SAMPLES, four per instruction: A = e c_i(s),
 //     B = c_j(s), lane (lq, lr) holds mode 16 it + lr at sample s0 + lq.  A lane forms e for one sample of a batch of 64 and the lanes
@@ -38,15 +38,6 @@ constexpr int PO_COEF_KMAX = 64;        // modes of PGD_POST_COEF: 10 tiles of 1
 constexpr int PO_NV = 32;               // Z, sum e^2, 6 first and 21 second parameter moments, padded
 constexpr int PO_PLAIN_TPB = 64;        // k_misfit_plain: one wave per workgroup, one sample per lane
 constexpr int PO_PLAIN_ACC = 17;        // k_post_coef_plain: (64 * 64 + 64) / 256 entries per thread, rounded up
-
-// the wave's (min, lowest index of it) from the lanes'; idx as a double (S < 2^31 is exact)
-__device__ __forceinline__ void misfit_wave_min(double &mn, double &ix) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const double omn = __shfl_xor(mn, m, 64), oix = __shfl_xor(ix, m, 64);
-        if (omn < mn || (omn == mn && oix < ix)) { mn = omn; ix = oix; }
-    }
-}
 
 // KT: k-steps of 4 the kernel is compiled for (4 KT >= k); T: sample tiles a wave holds at a time; mtn: tiles of 16 rows of a
 template <int KT, int T>
@@ -85,9 +76,9 @@ __global__ __launch_bounds__(TPB) void k_misfit_mfma(PostDims P, const double *_
 #pragma unroll
         for (int j = 0; j < T; ++j) v[j] = 0.0;
         for (int mt = 0; mt < mtn; ++mt) {
-            po_d4 acc[T];
+            d4_t acc[T];
 #pragma unroll
-            for (int j = 0; j < T; ++j) acc[j] = po_d4{0.0, 0.0, 0.0, 0.0};
+            for (int j = 0; j < T; ++j) acc[j] = d4_t{0.0, 0.0, 0.0, 0.0};
             const double *ap = af + (size_t)mt * KT * 64 + lane;
 #pragma unroll
             for (int q = 0; q < KT; ++q) {
@@ -112,11 +103,11 @@ __global__ __launch_bounds__(TPB) void k_misfit_mfma(PostDims P, const double *_
             if (sv[j]) {
                 if (lq == 0) chi2[smp[j]] = v[j];
                 const double ix = (double)smp[j];
-                if (v[j] < bmn || (v[j] == bmn && ix < bix)) { bmn = v[j]; bix = ix; }
+                if (post_less(v[j], ix, bmn, bix)) { bmn = v[j]; bix = ix; }
             }
         }
     }
-    misfit_wave_min(bmn, bix);
+    wave_min_index(bmn, bix);
     if (lane == 0) {
         const int64_t w = (int64_t)blockIdx.x * 4 + wv;
         part[2 * w] = bmn;
@@ -151,10 +142,10 @@ __global__ __launch_bounds__(PO_PLAIN_TPB) void k_misfit_plain(PostDims P, const
         if (sv) {
             chi2[s] = v;
             const double ix = (double)s;
-            if (v < bmn || (v == bmn && ix < bix)) { bmn = v; bix = ix; }
+            if (post_less(v, ix, bmn, bix)) { bmn = v; bix = ix; }
         }
     }
-    misfit_wave_min(bmn, bix);
+    wave_min_index(bmn, bix);
     if (lane == 0) {
         part[2 * (int64_t)blockIdx.x] = bmn;
         part[2 * (int64_t)blockIdx.x + 1] = bix;
@@ -168,7 +159,7 @@ __global__ __launch_bounds__(TPB) void k_misfit_finish(const double *__restrict_
     double mn = __builtin_huge_val(), ix = __builtin_huge_val();
     for (int64_t w = tid; w < nrows; w += TPB) {
         const double omn = part[2 * w], oix = part[2 * w + 1];
-        if (omn < mn || (omn == mn && oix < ix)) { mn = omn; ix = oix; }
+        if (post_less(omn, oix, mn, ix)) { mn = omn; ix = oix; }
     }
     s_mn[tid] = mn;
     s_ix[tid] = ix;
@@ -176,7 +167,7 @@ __global__ __launch_bounds__(TPB) void k_misfit_finish(const double *__restrict_
     for (int h = TPB / 2; h > 0; h >>= 1) {
         if (tid < h) {
             const double omn = s_mn[tid + h], oix = s_ix[tid + h];
-            if (omn < s_mn[tid] || (omn == s_mn[tid] && oix < s_ix[tid])) { s_mn[tid] = omn; s_ix[tid] = oix; }
+            if (post_less(omn, oix, s_mn[tid], s_ix[tid])) { s_mn[tid] = omn; s_ix[tid] = oix; }
         }
         __syncthreads();
     }
@@ -229,15 +220,6 @@ __global__ __launch_bounds__(TPB) void k_post_sums(PostDims P, const double *__r
     }
 }
 
-// out[v] = the sum over the segments, ascending, of part[seg * stride + v]
-__global__ __launch_bounds__(TPB) void k_post_finish(const double *__restrict__ part, int nseg, int64_t stride, int nv, double *__restrict__ out) {
-    const int v = blockIdx.x * TPB + threadIdx.x;
-    if (v >= nv) return;
-    double t = 0.0;
-    for (int seg = 0; seg < nseg; ++seg) t += part[(size_t)seg * stride + v];
-    out[v] = t;
-}
-
 // a workgroup per entry of the marginals: the sum of e over the samples with i_d = i, thread t takes the samples t, t + 256, .. of them
 __global__ __launch_bounds__(TPB) void k_post_marginals(PostDims P, const double *__restrict__ chi2, double shift, const double *__restrict__ wts,
                                                         int64_t S, int64_t nent, double *__restrict__ out) {
@@ -278,10 +260,10 @@ __global__ __launch_bounds__(TPB) void k_post_coef_mfma(PostDims P, const double
     for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
         const int64_t lo = seg * seglen, hi = lo + seglen < S ? lo + seglen : S;
         const int64_t nbatch = (hi - lo + 63) / 64;
-        po_d4 acc[NT];
+        d4_t acc[NT];
         double m1[KB];
 #pragma unroll
-        for (int u = 0; u < NT; ++u) acc[u] = po_d4{0.0, 0.0, 0.0, 0.0};
+        for (int u = 0; u < NT; ++u) acc[u] = d4_t{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int it = 0; it < KB; ++it) m1[it] = 0.0;
         for (int64_t bt = wv; bt < nbatch; bt += 4) {
@@ -414,49 +396,25 @@ __global__ __launch_bounds__(TPB) void k_post_coef_plain(PostDims P, const doubl
 }
 
 
+// (a wave of the persistent grid leaves one row of partials: they are sized once the grid is known)
 template <int KT, int T>
 static int misfit_launch_mfma(Ctx *c, const PostDims &P, const double *tab, int k, int mtn, const double *af, const double *yp, int64_t S,
                               double *chi2, int64_t *nrows) {
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_misfit_mfma<KT, T>, TPB, 0) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
     const int64_t ntile = (S + 16 * T - 1) / (16 * T);
-    int64_t g = (int64_t)c->num_cu * occ;
-    if (c->misfit_grid_max > 0 && g > c->misfit_grid_max) g = c->misfit_grid_max;
-    if (g > (ntile + 3) / 4) g = (ntile + 3) / 4;
+    const int64_t g = persistent_grid(c, k_misfit_mfma<KT, T>, TPB, 0, (ntile + 3) / 4, c->misfit_grid_max);
     PGD_TRY(ensure_partials(c, g * 4 * 2));
-    k_misfit_mfma<KT, T><<<(int)g, TPB, 0, c->stream>>>(P, tab, k, mtn, af, yp, S, chi2, c->partials);
-    PGD_LAUNCH_CHECK(c);
     *nrows = g * 4;
-    return PGD_OK;
+    return launch_grid(c, k_misfit_mfma<KT, T>, g, TPB, 0, P, tab, k, mtn, af, yp, S, chi2, c->partials);
 }
 
 static int misfit_launch_plain(Ctx *c, const PostDims &P, const double *tab, int k, int m, const double *a, const double *y, int64_t S,
                                double *chi2, int64_t *nrows) {
     const size_t lds = (size_t)k * PO_PLAIN_TPB * sizeof(double);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)k_misfit_plain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, PGD_ERR_HIP, "grid_misfit: %zu bytes of LDS refused", lds);
-    }
-    const int64_t nblk = (S + PO_PLAIN_TPB - 1) / PO_PLAIN_TPB;
-    int64_t g = (int64_t)c->num_cu * 8;
-    if (c->misfit_grid_max > 0 && g > c->misfit_grid_max) g = c->misfit_grid_max;
-    if (g > nblk) g = nblk;
+    PGD_TRY(raise_lds(c, (const void *)k_misfit_plain, lds, "grid_misfit"));
+    const int64_t g = persistent_grid(c, k_misfit_plain, PO_PLAIN_TPB, lds, (S + PO_PLAIN_TPB - 1) / PO_PLAIN_TPB, c->misfit_grid_max, 8);
     PGD_TRY(ensure_partials(c, g * 2));
-    k_misfit_plain<<<(int)g, PO_PLAIN_TPB, lds, c->stream>>>(P, tab, k, m, a, y, S, chi2, c->partials);
-    PGD_LAUNCH_CHECK(c);
     *nrows = g;
-    return PGD_OK;
-}
-
-template <int KB>
-static int coef_launch_mfma(Ctx *c, int g, const PostDims &P, const double *tab, int k, const double *chi2, double shift, const double *wts,
-                            int64_t S, int nseg, int64_t seglen, int64_t stride, double *part) {
-    k_post_coef_mfma<KB><<<g, TPB, 0, c->stream>>>(P, tab, k, chi2, shift, wts, S, nseg, seglen, stride, part);
-    PGD_LAUNCH_CHECK(c);
-    return PGD_OK;
+    return launch_grid(c, k_misfit_plain, g, PO_PLAIN_TPB, lds, P, tab, k, m, a, y, S, chi2, c->partials);
 }
 
 }  // namespace pgd
@@ -483,36 +441,24 @@ int pgd_grid_misfit(pgd_handle h, const double *a, const double *y, int m, int k
 
     // ---- a and y in the order the variant reads them, behind the tables in one upload
     const bool mfma = c->misfit_variant != 0;
-    const int kt = post_kt(k), mtn = (m + 15) / 16;
+    const int kt = dense_kt(k), mtn = (m + 15) / 16;
     const size_t na = mfma ? (size_t)mtn * kt * 64 : (size_t)m * k, ny = mfma ? (size_t)16 * mtn : (size_t)m;
     std::vector<double> hbuf(na + ny, 0.0);                 // (the tables go up from the caller's array: no host copy of them)
     double *ha = hbuf.data(), *hy = ha + na;
-    if (mfma) {
-        for (int p = 0; p < m; ++p)
-            for (int t = 0; t < k; ++t) ha[post_af_index(kt, p, t)] = a[(size_t)p * k + t];
-    } else {
-        std::copy(a, a + (size_t)m * k, ha);
-    }
+    if (mfma) pack_a_fragments(ha, kt, a, m, k, k);
+    else std::copy(a, a + (size_t)m * k, ha);
     std::copy(y, y + m, hy);
-    const size_t bytes = pool_bytes((size_t)ntab + hbuf.size());
-    void *p_in = nullptr;
-    PGD_TRY(dev_alloc(c, &p_in, bytes));
     double res[2] = {0.0, 0.0};
-    auto run = [&]() -> int {
+    const int rc = with_pool_input(c, pool_bytes((size_t)ntab + hbuf.size()), [&](void *p_in) -> int {
         PGD_TRY(ensure_work(c, 6, 2));
         PGD_HIP(c, hipMemcpyAsync(p_in, tables, (size_t)ntab * sizeof(double), hipMemcpyHostToDevice, c->stream));
         PGD_HIP(c, hipMemcpyAsync((double *)p_in + ntab, hbuf.data(), hbuf.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         const double *tab = (const double *)p_in, *ad = tab + ntab, *yd = ad + na;
         int64_t nrows = 0;
         if (mfma) {
-            switch (kt) {
-                case 4: PGD_TRY((misfit_launch_mfma<4, 4>(c, P, tab, k, mtn, ad, yd, S, cv->d, &nrows))); break;
-                case 8: PGD_TRY((misfit_launch_mfma<8, 4>(c, P, tab, k, mtn, ad, yd, S, cv->d, &nrows))); break;
-                case 12: PGD_TRY((misfit_launch_mfma<12, 4>(c, P, tab, k, mtn, ad, yd, S, cv->d, &nrows))); break;
-                case 16: PGD_TRY((misfit_launch_mfma<16, 4>(c, P, tab, k, mtn, ad, yd, S, cv->d, &nrows))); break;
-                case 32: PGD_TRY((misfit_launch_mfma<32, 2>(c, P, tab, k, mtn, ad, yd, S, cv->d, &nrows))); break;
-                default: PGD_TRY((misfit_launch_mfma<64, 1>(c, P, tab, k, mtn, ad, yd, S, cv->d, &nrows))); break;
-            }
+            PGD_TRY(dense_dispatch(kt, [&](auto KT, auto T) {
+                return misfit_launch_mfma<decltype(KT)::value, decltype(T)::value>(c, P, tab, k, mtn, ad, yd, S, cv->d, &nrows);
+            }));
         } else {
             PGD_TRY(misfit_launch_plain(c, P, tab, k, m, ad, yd, S, cv->d, &nrows));
         }
@@ -521,10 +467,7 @@ int pgd_grid_misfit(pgd_handle h, const double *a, const double *y, int m, int k
         PGD_HIP(c, hipMemcpyAsync(res, c->work[6], 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         PGD_HIP(c, hipStreamSynchronize(c->stream));   // the one synchronisation of the call
         return PGD_OK;
-    };
-    const int rc = run();
-    if (rc != PGD_OK) (void)hipStreamSynchronize(c->stream);   // nothing reads the inputs once they go back to the pool
-    dev_release(c, p_in, bytes);
+    });
     if (rc != PGD_OK) return rc;
     if (min_out) *min_out = res[0];
     if (argmin_out) *argmin_out = res[1] < 2147483648.0 ? (int64_t)res[1] : -1;   // (-1: no value compares, every chi2 is NaN)
@@ -558,17 +501,14 @@ int pgd_grid_posterior(pgd_handle h, pgd_handle chi2h, double shift, const doubl
 
     int nseg = 1;
     int64_t seglen = 0;
-    post_segments(S, &nseg, &seglen);
+    grid_segments(S, PO_SEGMIN, &nseg, &seglen);
     const int kb = (kk + 15) / 16, kp = 16 * kb, ncoef = kp * kp + kp;
-    // uploads from the caller's arrays: tables (PGD_POST_COEF), weights, abscissae (PGD_POST_THETA)
-    const size_t bytes = pool_bytes((size_t)ntab + 2 * (size_t)nw);
     // the outputs on the device: sums and moments (PO_NV), coefficient moments (ncoef), marginals (nw)
     const int64_t nout = PO_NV + ncoef + (marg ? nw : 0);
     const int64_t npart = (int64_t)nseg * (PO_NV + ncoef);
     std::vector<double> out((size_t)nout, 0.0);
-    void *p_in = nullptr;
-    PGD_TRY(dev_alloc(c, &p_in, bytes));
-    auto run = [&]() -> int {
+    // uploads from the caller's arrays: tables (PGD_POST_COEF), weights, abscissae (PGD_POST_THETA)
+    const int rc = with_pool_input(c, pool_bytes((size_t)ntab + 2 * (size_t)nw), [&](void *p_in) -> int {
         PGD_TRY(ensure_work(c, 6, nout));
         PGD_TRY(ensure_partials(c, npart));
         double *tab = (double *)p_in, *wd = tab + ntab, *xd = wd + nw;
@@ -581,15 +521,14 @@ int pgd_grid_posterior(pgd_handle h, pgd_handle chi2h, double shift, const doubl
         const int g = (int)(nseg < cap ? nseg : cap);
         k_post_sums<<<g, TPB, 0, c->stream>>>(P, cv->d, shift, wd, xd, S, nseg, seglen, theta ? 1 : 0, part_s);
         PGD_LAUNCH_CHECK(c);
-        k_post_finish<<<1, TPB, 0, c->stream>>>(part_s, nseg, PO_NV, theta ? 29 : 2, od);
-        PGD_LAUNCH_CHECK(c);
+        PGD_TRY(seg_sum(c, part_s, nseg, PO_NV, theta ? 29 : 2, 1.0, od));
         if (coef) {
             if (c->post_variant != 0) {
                 switch (kb) {
-                    case 1: PGD_TRY(coef_launch_mfma<1>(c, g, P, tab, k, cv->d, shift, wd, S, nseg, seglen, ncoef, part_c)); break;
-                    case 2: PGD_TRY(coef_launch_mfma<2>(c, g, P, tab, k, cv->d, shift, wd, S, nseg, seglen, ncoef, part_c)); break;
-                    case 3: PGD_TRY(coef_launch_mfma<3>(c, g, P, tab, k, cv->d, shift, wd, S, nseg, seglen, ncoef, part_c)); break;
-                    default: PGD_TRY(coef_launch_mfma<4>(c, g, P, tab, k, cv->d, shift, wd, S, nseg, seglen, ncoef, part_c)); break;
+                    case 1: PGD_TRY(launch_grid(c, k_post_coef_mfma<1>, g, TPB, 0, P, tab, k, cv->d, shift, wd, S, nseg, seglen, ncoef, part_c)); break;
+                    case 2: PGD_TRY(launch_grid(c, k_post_coef_mfma<2>, g, TPB, 0, P, tab, k, cv->d, shift, wd, S, nseg, seglen, ncoef, part_c)); break;
+                    case 3: PGD_TRY(launch_grid(c, k_post_coef_mfma<3>, g, TPB, 0, P, tab, k, cv->d, shift, wd, S, nseg, seglen, ncoef, part_c)); break;
+                    default: PGD_TRY(launch_grid(c, k_post_coef_mfma<4>, g, TPB, 0, P, tab, k, cv->d, shift, wd, S, nseg, seglen, ncoef, part_c)); break;
                 }
             } else {
                 PGD_HIP(c, hipMemsetAsync(part_c, 0, (size_t)nseg * ncoef * sizeof(double), c->stream));
@@ -597,8 +536,7 @@ int pgd_grid_posterior(pgd_handle h, pgd_handle chi2h, double shift, const doubl
                 k_post_coef_plain<<<g, TPB, lds, c->stream>>>(P, tab, k, kp, cv->d, shift, wd, S, nseg, seglen, ncoef, part_c);
                 PGD_LAUNCH_CHECK(c);
             }
-            k_post_finish<<<(ncoef + TPB - 1) / TPB, TPB, 0, c->stream>>>(part_c, nseg, ncoef, ncoef, od + PO_NV);
-            PGD_LAUNCH_CHECK(c);
+            PGD_TRY(seg_sum(c, part_c, nseg, ncoef, ncoef, 1.0, od + PO_NV));
         }
         if (marg) {
             const int gm = (int)(nw < cap ? nw : cap);
@@ -608,10 +546,7 @@ int pgd_grid_posterior(pgd_handle h, pgd_handle chi2h, double shift, const doubl
         PGD_HIP(c, hipMemcpyAsync(out.data(), od, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         PGD_HIP(c, hipStreamSynchronize(c->stream));   // the one synchronisation of the call
         return PGD_OK;
-    };
-    const int rc = run();
-    if (rc != PGD_OK) (void)hipStreamSynchronize(c->stream);
-    dev_release(c, p_in, bytes);
+    });
     if (rc != PGD_OK) return rc;
     // ---- the caller's arrays are written only now
     sums[0] = out[0];

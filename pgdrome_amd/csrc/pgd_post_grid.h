@@ -1,5 +1,7 @@
-// What pgd_post.hip and pgd_postmany.hip share: the tensor grid of the free coordinates (its offsets, the decoding of a sample, the
-// coefficient and weight chains), the segments of the reductions and the fragment order of a.
+// What pgd_post.hip, pgd_postmany.hip and pgd_design.hip share: the tensor grid of the free coordinates (its offsets, the decoding of a
+// sample, the coefficient and weight chains), the ordered minimum, the segments of the reductions and their ascending sum.  (The
+// launcher, the instance table, the fragment order of a and the call skeleton are pgd_internal.h's: the products that know no grid
+// use them too.)
 #pragma once
 #include "pgd_internal.h"
 
@@ -8,8 +10,7 @@ namespace pgd {
 constexpr int PO_DMAX = 6;              // dimensions of the grid
 constexpr int PO_NSEG = 1024;           // most segments of the reductions
 constexpr int PO_SEGMIN = 4096;         // fewest samples of a segment (the last one excepted)
-
-typedef double po_d4 __attribute__((ext_vector_type(4)));
+constexpr int PM_SEGMIN = 1024;         // .. of pgd_grid_posterior_many, whose work items are (segment) x (data block): a few data sets already fill the device
 
 // the grid: n[d] points per dimension, table d at tab[toff[d] + t n[d] + i], weights and abscissae of dimension d from woff[d] on
 struct PostDims {
@@ -52,15 +53,35 @@ __device__ __forceinline__ double post_weight(const PostDims &P, const double *_
 
 __device__ __forceinline__ double post_e(double chi2, double shift, double w) { return w * exp(-0.5 * (chi2 - shift)); }
 
-// k-steps of 4 of the misfit instance for k modes; it holds T = 4, 4, 4, 4, 2, 1 sample tiles per wave (quad_kt)
-inline int post_kt(int k) { return k <= 16 ? 4 : k <= 32 ? 8 : k <= 48 ? 12 : k <= 64 ? 16 : k <= 128 ? 32 : 64; }
+// the order of the minima: the smaller value, among equal ones the lower index (as a double: S < 2^31 is exact)
+__device__ __forceinline__ bool post_less(double omn, double oix, double mn, double ix) { return omn < mn || (omn == mn && oix < ix); }
 
-// entry (p, t) of a in fragment order: kt k-steps of 4 per tile of 16 rows
-inline size_t post_af_index(int kt, int p, int t) { return ((size_t)(p >> 4) * kt + (t >> 2)) * 64 + ((t & 3) << 4) + (p & 15); }
+// the wave's (min, lowest index of it) from the lanes'
+__device__ __forceinline__ void wave_min_index(double &mn, double &ix) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const double omn = __shfl_xor(mn, m, 64), oix = __shfl_xor(ix, m, 64);
+        if (post_less(omn, oix, mn, ix)) { mn = omn; ix = oix; }
+    }
+}
 
-// the segments of the reductions: a function of S alone
-inline void post_segments(int64_t S, int *nseg, int64_t *seglen) {
-    int64_t ns = (S + PO_SEGMIN - 1) / PO_SEGMIN;
+// out[i] = scale times the sum over the segments, ascending, of part[seg * stride + i], i < n
+static __global__ __launch_bounds__(TPB) void k_seg_sum(const double *__restrict__ part, int nseg, int64_t stride, int64_t n, double scale,
+                                                        double *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    double t = 0.0;
+    for (int seg = 0; seg < nseg; ++seg) t += part[(size_t)seg * stride + i];
+    out[i] = scale * t;
+}
+
+inline int seg_sum(Ctx *c, const double *part, int nseg, int64_t stride, int64_t n, double scale, double *out) {
+    return launch_grid(c, k_seg_sum, (n + TPB - 1) / TPB, TPB, 0, part, nseg, stride, n, scale, out);
+}
+
+// the segments of the reductions, of segmin samples or more (the last one excepted): a function of S alone
+inline void grid_segments(int64_t S, int segmin, int *nseg, int64_t *seglen) {
+    int64_t ns = (S + segmin - 1) / segmin;
     if (ns > PO_NSEG) ns = PO_NSEG;
     if (ns < 1) ns = 1;
     int64_t len = (S + ns - 1) / ns;
@@ -91,7 +112,5 @@ inline bool post_dims(const int *n, int ndim, int k, PostDims *P, int64_t *S, in
     *nw = wo;
     return true;
 }
-
-inline size_t pool_bytes(size_t n_doubles) { return (n_doubles * sizeof(double) + 65535) & ~(size_t)65535; }   // (whole 64 KiB: the pool takes them back)
 
 }  // namespace pgd

@@ -11,8 +11,10 @@
 //
 // k_postmany_mfma: three chained products on v_mfma_f64_16x16x4_f64.  Lane (lq, lr) = (lane >> 4, lane & 15); the instruction's
 // A operand is A[row lr][k lq], its B operand B[k lq][col lr], and D[4 r + lq][lr] comes back in acc[r].
-//   * stage 1 (k_misfit_mfma's): acc1[r] = P[p = 16 mt + 4 r + lq][sample lr] from a in fragment order (A) and the coefficients of the
-//     tile's 16 samples (B), formed from the tables.  pp = |p|^2 of sample lr: one fma chain in ascending (mt, r), two __shfl_xor.
+//   * stage 1 (the product of k_misfit_mfma with one sample tile per wave; the two kernels keep their own copy of these few lines - as a
+//     shared inline function they came out of the register allocator differently): acc1[r] = P[p = 16 mt + 4 r + lq][sample lr] from a
+//     in fragment order (A, pack_a_fragments) and the coefficients of the tile's 16 samples (B), formed from the tables.  pp = |p|^2
+//     of sample lr: one fma chain in ascending (mt, r), two __shfl_xor.
 //   * stage 2: acc1[r] IS the A operand of the k-step (mt, r) of chi2^T = P^T U~^T (row = sample lr, k = p): nothing moves.  The B
 //     operand is -2 u[data set lr][p = 16 mt + 4 r + lq], laid out by the host.  One more k-step carries (pp, 1, 0, 0) against
 //     (alpha_j, beta_j, 0, 0).  acc2[dt][r] = chi2[sample 4 r + lq][data set 16 dt + lr] for the DB data tiles a wave holds.
@@ -23,7 +25,7 @@
 //     sum e^2 is a plain fma chain per lane, two __shfl_xor at the end.
 // A workgroup takes one (block of 16 DB data sets, segment of samples) at a time; its four waves deal the segment's tiles of 16
 // samples (wave w: tiles w, w + 4, ..) and are added in ascending order through LDS; the block's fragments of u are staged in LDS
-// once per such item, those of a once per workgroup.  The segments are postmany_segments': a function of S alone.  k_postmany_sum
+// once per such item, those of a once per workgroup.  The segments are grid_segments' with PM_SEGMIN: a function of S alone.  k_seg_sum
 // adds them in ascending order.  No floating-point atomics; a column of an MFMA result does not depend on the other columns -
 // every output of a data set is the same bits from run to run, for any grid (PGD_TUNE_POSTMANY_GRID_MAX), alone or among others,
 // in any position of any chunk.
@@ -46,22 +48,6 @@ constexpr int PM_DB2 = 4;               // .. with two feature tiles
 constexpr double PM_SKIP = 1500.0;      // exp(-750) rounds to 0: the smallest subnormal is exp(-744.44..)
 constexpr int64_t PM_PART_MAX = (int64_t)1 << 25;   // doubles of the partials of a chunk of data sets (256 MB)
 constexpr int PM_PLAIN_SB = 16;         // k_postmany_plain: samples per batch
-constexpr int PM_NSEG = 1024;           // most segments of the samples
-constexpr int PM_SEGMIN = 1024;         // fewest samples of a segment (the last one excepted): a few data sets already fill the device
-
-// the segments of the samples: a function of S alone (finer than post_segments: a workgroup's work is (segment) x (data block))
-static void postmany_segments(int64_t S, int *nseg, int64_t *seglen) {
-    int64_t ns = (S + PM_SEGMIN - 1) / PM_SEGMIN;
-    if (ns > PM_NSEG) ns = PM_NSEG;
-    if (ns < 1) ns = 1;
-    int64_t len = (S + ns - 1) / ns;
-    len = (len + 255) / 256 * 256;
-    *nseg = (int)((S + len - 1) / len);
-    if (*nseg < 1) *nseg = 1;
-    *seglen = len;
-}
-
-__device__ __forceinline__ bool pm_less(double omn, double oix, double mn, double ix) { return omn < mn || (omn == mn && oix < ix); }
 
 // th_{a-1} of the sample with the indices idx; a = 0: the constant 1
 __device__ __forceinline__ double pm_theta(const PostDims &P, const double *__restrict__ absc, const int (&idx)[PO_DMAX], int a) {
@@ -92,7 +78,7 @@ __device__ __forceinline__ void pm_feature(int D, int v, int &a, int &b) {
 // af, uf: a's and the block's fragments (both in LDS), nstep = 4 mtn + 1 k-steps of 64 doubles per data tile.
 template <int KT, int DB>
 __device__ __forceinline__ void pm_chi2_tile(const PostDims &P, const double *__restrict__ tab, int k, int mtn, const double *__restrict__ af,
-                                             const double *__restrict__ uf, unsigned s_lr, int lane, po_d4 (&acc2)[DB]) {
+                                             const double *__restrict__ uf, unsigned s_lr, int lane, d4_t (&acc2)[DB]) {
     const int lq = lane >> 4;
     const int nstep = 4 * mtn + 1;
     int idx[PO_DMAX];
@@ -109,10 +95,10 @@ __device__ __forceinline__ void pm_chi2_tile(const PostDims &P, const double *__
         }
     }
 #pragma unroll
-    for (int dt = 0; dt < DB; ++dt) acc2[dt] = po_d4{0.0, 0.0, 0.0, 0.0};
+    for (int dt = 0; dt < DB; ++dt) acc2[dt] = d4_t{0.0, 0.0, 0.0, 0.0};
     double pp = 0.0;
     for (int mt = 0; mt < mtn; ++mt) {
-        po_d4 acc1 = po_d4{0.0, 0.0, 0.0, 0.0};
+        d4_t acc1 = d4_t{0.0, 0.0, 0.0, 0.0};
         const double *ap = af + (size_t)mt * KT * 64 + lane;
 #pragma unroll
         for (int q = 0; q < KT; ++q) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[q * 64], b[q], acc1, 0, 0, 0);
@@ -158,12 +144,12 @@ __global__ __launch_bounds__(TPB) void k_postmany_mfma(PostDims P, const double 
         const int64_t j0 = (int64_t)dblk * DB * 16;
         for (int i = threadIdx.x; i < DB * nstep * 64; i += TPB) s_uf[i] = ufb[i];
         __syncthreads();
-        po_d4 M[FT][DB];
+        d4_t M[FT][DB];
         double s2[DB], sh[DB], bmn[DB], bix[DB];
 #pragma unroll
         for (int dt = 0; dt < DB; ++dt) {
 #pragma unroll
-            for (int ft = 0; ft < FT; ++ft) M[ft][dt] = po_d4{0.0, 0.0, 0.0, 0.0};
+            for (int ft = 0; ft < FT; ++ft) M[ft][dt] = d4_t{0.0, 0.0, 0.0, 0.0};
             s2[dt] = 0.0;
             sh[dt] = SUMS ? shift[j0 + 16 * dt + lr] : 0.0;
             bmn[dt] = bix[dt] = INF;
@@ -171,7 +157,7 @@ __global__ __launch_bounds__(TPB) void k_postmany_mfma(PostDims P, const double 
         for (int64_t t = wv; t < ntile; t += 4) {
             const int64_t base = lo + 16 * t;
             const int64_t s1 = base + lr < hi ? base + lr : hi - 1;        // (a sample beyond the segment repeats its last one: its e is 0)
-            po_d4 acc2[DB];
+            d4_t acc2[DB];
             pm_chi2_tile<KT, DB>(P, tab, k, mtn, s_af, s_uf, (unsigned)s1, lane, acc2);
             if (!SUMS) {
 #pragma unroll
@@ -181,7 +167,7 @@ __global__ __launch_bounds__(TPB) void k_postmany_mfma(PostDims P, const double 
                         const double ix = (double)s;
 #pragma unroll
                         for (int dt = 0; dt < DB; ++dt)
-                            if (pm_less(acc2[dt][r], ix, bmn[dt], bix[dt])) { bmn[dt] = acc2[dt][r]; bix[dt] = ix; }
+                            if (post_less(acc2[dt][r], ix, bmn[dt], bix[dt])) { bmn[dt] = acc2[dt][r]; bix[dt] = ix; }
                     }
                 }
             } else {
@@ -226,7 +212,7 @@ __global__ __launch_bounds__(TPB) void k_postmany_mfma(PostDims P, const double 
 #pragma unroll
                 for (int x = 16; x < 64; x <<= 1) {
                     const double omn = __shfl_xor(bmn[dt], x, 64), oix = __shfl_xor(bix[dt], x, 64);
-                    if (pm_less(omn, oix, bmn[dt], bix[dt])) { bmn[dt] = omn; bix[dt] = oix; }
+                    if (post_less(omn, oix, bmn[dt], bix[dt])) { bmn[dt] = omn; bix[dt] = oix; }
                 }
             }
         } else {
@@ -263,7 +249,7 @@ __global__ __launch_bounds__(TPB) void k_postmany_mfma(PostDims P, const double 
 #pragma unroll
                     for (int dt = 0; dt < DB; ++dt) {
                         const double omn = s_acc[(2 * dt) * 64 + lane], oix = s_acc[(2 * dt + 1) * 64 + lane];
-                        if (pm_less(omn, oix, bmn[dt], bix[dt])) { bmn[dt] = omn; bix[dt] = oix; }
+                        if (post_less(omn, oix, bmn[dt], bix[dt])) { bmn[dt] = omn; bix[dt] = oix; }
                     }
                 } else {
 #pragma unroll
@@ -378,7 +364,7 @@ __global__ __launch_bounds__(TPB) void k_postmany_plain(PostDims P, const double
                         const double chi2 = fma(alpha, s_pp[x], c2[x]) + beta;
                         if (!SUMS) {
                             const double ix = (double)(b0 + x);
-                            if (pm_less(chi2, ix, bmn, bix)) { bmn = chi2; bix = ix; }
+                            if (post_less(chi2, ix, bmn, bix)) { bmn = chi2; bix = ix; }
                         } else {
                             const double e = s_w[x] * exp(-0.5 * (chi2 - sh));
                             z += e;
@@ -427,19 +413,10 @@ __global__ __launch_bounds__(TPB) void k_postmany_min(const double *__restrict__
     double mn = __builtin_huge_val(), ix = __builtin_huge_val();
     for (int seg = 0; seg < nseg; ++seg) {
         const double omn = part[((size_t)seg * 2) * ndp + j], oix = part[((size_t)seg * 2 + 1) * ndp + j];
-        if (pm_less(omn, oix, mn, ix)) { mn = omn; ix = oix; }
+        if (post_less(omn, oix, mn, ix)) { mn = omn; ix = oix; }
     }
     out[j] = mn;
     out[ndp + j] = ix;
-}
-
-// out[i] = the sum over the segments, ascending, of part[seg * n + i]
-__global__ __launch_bounds__(TPB) void k_postmany_sum(const double *__restrict__ part, int nseg, int64_t n, double *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= n) return;
-    double t = 0.0;
-    for (int seg = 0; seg < nseg; ++seg) t += part[(size_t)seg * n + i];
-    out[i] = t;
 }
 
 struct PmArgs {
@@ -453,45 +430,21 @@ struct PmArgs {
 template <int KT, int DB, int FT, bool SUMS>
 static int postmany_launch(Ctx *c, const PmArgs &A) {
     const size_t lds = ((size_t)A.mtn * KT + (size_t)DB * (4 * A.mtn + 1) + (SUMS ? FT * DB * 4 + DB : 2 * DB)) * 64 * sizeof(double);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)k_postmany_mfma<KT, DB, FT, SUMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, PGD_ERR_HIP, "grid_posterior_many: %zu bytes of LDS refused", lds);
-    }
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_postmany_mfma<KT, DB, FT, SUMS>, TPB, lds) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
-    const int64_t nitem = (int64_t)A.ndblk * A.nseg;
-    int64_t g = (int64_t)c->num_cu * occ;
-    if (c->postmany_grid_max > 0 && g > c->postmany_grid_max) g = c->postmany_grid_max;
-    if (g > nitem) g = nitem;
-    k_postmany_mfma<KT, DB, FT, SUMS><<<(int)g, TPB, lds, c->stream>>>(A.P, A.tab, A.k, A.mtn, A.af, A.uf, A.wts, A.absc, A.shift, A.S, A.nseg, A.seglen,
-                                                                    A.ndblk, A.ndp, A.nfeat, A.skip, A.part);
-    PGD_LAUNCH_CHECK(c);
-    return PGD_OK;
+    PGD_TRY(raise_lds(c, (const void *)k_postmany_mfma<KT, DB, FT, SUMS>, lds, "grid_posterior_many"));
+    return launch_persistent(c, k_postmany_mfma<KT, DB, FT, SUMS>, TPB, lds, (int64_t)A.ndblk * A.nseg, c->postmany_grid_max, 0, nullptr, A.P, A.tab, A.k,
+                             A.mtn, A.af, A.uf, A.wts, A.absc, A.shift, A.S, A.nseg, A.seglen, A.ndblk, A.ndp, A.nfeat, A.skip, A.part);
 }
 
+// (k <= PM_KMAX = 64: the instances end at KT = 16)
 template <int DB, int FT, bool SUMS>
 static int postmany_launch_kt(Ctx *c, int kt, const PmArgs &A) {
-    switch (kt) {
-        case 4: return postmany_launch<4, DB, FT, SUMS>(c, A);
-        case 8: return postmany_launch<8, DB, FT, SUMS>(c, A);
-        case 12: return postmany_launch<12, DB, FT, SUMS>(c, A);
-        default: return postmany_launch<16, DB, FT, SUMS>(c, A);
-    }
+    return dense_dispatch<16>(kt, [&](auto KT, auto) { return postmany_launch<decltype(KT)::value, DB, FT, SUMS>(c, A); });
 }
 
 template <bool SUMS>
 static int postmany_launch_plain(Ctx *c, const PmArgs &A) {
-    const int64_t nitem = (int64_t)A.ndblk * A.nseg;
-    int64_t g = (int64_t)c->num_cu * 4;
-    if (c->postmany_grid_max > 0 && g > c->postmany_grid_max) g = c->postmany_grid_max;
-    if (g > nitem) g = nitem;
-    k_postmany_plain<SUMS><<<(int)g, TPB, 0, c->stream>>>(A.P, A.tab, A.k, A.m, A.af, A.uf, A.wts, A.absc, A.shift, A.S, A.nseg, A.seglen, A.ndblk,
-                                                         A.ndp, A.nfeat, A.part);
-    PGD_LAUNCH_CHECK(c);
-    return PGD_OK;
+    return launch_persistent(c, k_postmany_plain<SUMS>, TPB, 0, (int64_t)A.ndblk * A.nseg, c->postmany_grid_max, 4, nullptr, A.P, A.tab, A.k, A.m, A.af,
+                             A.uf, A.wts, A.absc, A.shift, A.S, A.nseg, A.seglen, A.ndblk, A.ndp, A.nfeat, A.part);
 }
 
 }  // namespace pgd
@@ -527,9 +480,9 @@ int pgd_grid_posterior_many(pgd_handle h, const double *a, int m, int k, const d
 
     int nseg = 1;
     int64_t seglen = 0;
-    postmany_segments(S, &nseg, &seglen);
+    grid_segments(S, PM_SEGMIN, &nseg, &seglen);
     const bool mfma = c->postmany_variant != 0;
-    const int kt = post_kt(k), mtn = (m + 15) / 16, nstep = 4 * mtn + 1;
+    const int kt = dense_kt(k), mtn = (m + 15) / 16, nstep = 4 * mtn + 1;
     const int db = ndim <= 3 ? PM_DB1 : PM_DB2, blk = 16 * db;
     const int nfeat = theta ? (ndim + 1) * (ndim + 2) / 2 : 1, nvs = nfeat + 1;
     // ---- the chunk of data sets whose partials stay below PM_PART_MAX doubles: whole blocks, at least one
@@ -540,20 +493,13 @@ int pgd_grid_posterior_many(pgd_handle h, const double *a, int m, int k, const d
     const size_t na = mfma ? (size_t)mtn * kt * 64 : (size_t)m * k;
     const size_t nu_max = mfma ? (size_t)(ndp_max / 16) * nstep * 64 : (size_t)(m + 2) * ndp_max;
     std::vector<double> ha(na, 0.0), hu(nu_max, 0.0);
-    if (mfma) {
-        for (int p = 0; p < m; ++p)
-            for (int t = 0; t < k; ++t) ha[post_af_index(kt, p, t)] = a[(size_t)p * k + t];
-    } else {
-        std::copy(a, a + (size_t)m * k, ha.begin());
-    }
+    if (mfma) pack_a_fragments(ha.data(), kt, a, m, k, k);
+    else std::copy(a, a + (size_t)m * k, ha.begin());
     const int64_t nout_max = (int64_t)(2 + nvs) * ndp_max;
     std::vector<double> out((size_t)nout_max, 0.0);
     std::vector<double> r_min((size_t)nd), r_arg((size_t)nd), r_sum((size_t)nd * nvs);
-    const size_t bytes = pool_bytes((size_t)ntab + 2 * (size_t)nw + na + nu_max);
-    void *p_in = nullptr;
-    PGD_TRY(dev_alloc(c, &p_in, bytes));
-    double *tab = (double *)p_in, *wd = tab + ntab, *xd = wd + nw, *ad = xd + nw, *ud = ad + na;
-    auto run = [&]() -> int {
+    const int rc = with_pool_input(c, pool_bytes((size_t)ntab + 2 * (size_t)nw + na + nu_max), [&](void *p_in) -> int {
+        double *tab = (double *)p_in, *wd = tab + ntab, *xd = wd + nw, *ad = xd + nw, *ud = ad + na;
         PGD_TRY(ensure_work(c, 6, nout_max));
         PGD_TRY(ensure_partials(c, (int64_t)nseg * nvs * ndp_max > 2 * (int64_t)nseg * ndp_max ? (int64_t)nseg * nvs * ndp_max : 2 * (int64_t)nseg * ndp_max));
         PGD_HIP(c, hipMemcpyAsync(tab, tables, (size_t)ntab * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -594,8 +540,7 @@ int pgd_grid_posterior_many(pgd_handle h, const double *a, int m, int k, const d
             else if (db == PM_DB1) PGD_TRY((postmany_launch_kt<PM_DB1, 1, true>(c, kt, A)));
             else PGD_TRY((postmany_launch_kt<PM_DB2, 2, true>(c, kt, A)));
             const int64_t nsum = (int64_t)nvs * ndp;
-            k_postmany_sum<<<(int)((nsum + TPB - 1) / TPB), TPB, 0, c->stream>>>(c->partials, nseg, nsum, od + 2 * ndp);
-            PGD_LAUNCH_CHECK(c);
+            PGD_TRY(seg_sum(c, c->partials, nseg, nsum, nsum, 1.0, od + 2 * ndp));
             PGD_HIP(c, hipMemcpyAsync(out.data(), od, (size_t)(2 + nvs) * ndp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
             PGD_HIP(c, hipStreamSynchronize(c->stream));   // the one synchronisation of the chunk
             for (int64_t j = 0; j < cn; ++j) {
@@ -605,10 +550,7 @@ int pgd_grid_posterior_many(pgd_handle h, const double *a, int m, int k, const d
             }
         }
         return PGD_OK;
-    };
-    const int rc = run();
-    if (rc != PGD_OK) (void)hipStreamSynchronize(c->stream);   // nothing reads the inputs once they go back to the pool
-    dev_release(c, p_in, bytes);
+    });
     if (rc != PGD_OK) return rc;
     // ---- the caller's arrays are written only now
     for (int64_t j = 0; j < nd; ++j) {

@@ -9,7 +9,7 @@
 //     from the mode vectors (per load instruction four runs of 16 consecutive doubles, whole 128-byte lines), not through LDS.
 //     The kernel uses no LDS and has no barrier.
 //   * A holds 16 rows l of Q: lane (lq, lr) holds Q[16 lt + lr][4 q' + lq].  The host lays the matrices out in that fragment
-//     order (quad_qf_index) and uploads them once per call; a fragment is one coalesced 512-byte load, served by L2, and is
+//     order (pack_a_fragments, kt / 4 tiles of 16 rows per form) and uploads them once per call; a fragment is one coalesced 512-byte load, served by L2, and is
 //     used for the T row tiles the wave holds.
 //   * D[l][dof] = (Q f)_l: the lane holds D[16 lt + 4 r + lq][lr] in acc[r], and the multiplier of that entry, F[dof lr][16 lt +
 //     4 r + lq], is b[j][4 lt + r] - already in the lane's registers.  The value is sum_{lt, r} b[j][4 lt + r] acc[r] as one fma
@@ -33,15 +33,8 @@ constexpr int QD_KMAX = 256;            // modes per call (EVAL_KMAX)
 constexpr int QD_NQMAX = 64;            // forms per call: one lane of a wave per form
 constexpr int QD_PLAIN_TPB = 64;        // k_quad_plain: one wave per workgroup, one row per lane
 
-typedef double qd_d4 __attribute__((ext_vector_type(4)));
-
 struct QuadModes { const double *p[QD_KMAX]; };
 struct QuadOuts { double *p[QD_NQMAX]; };   // nullptr: the field of that form is not stored
-
-// entry (l, t) of form f in fragment order: kt k-steps of 4, kt / 4 tiles of 16 rows of Q
-static inline size_t quad_qf_index(int kt, int f, int l, int t) {
-    return (((size_t)f * (kt >> 2) + (l >> 4)) * kt + (t >> 2)) * 64 + ((t & 3) << 4) + (l & 15);
-}
 
 // what becomes of the values v of form f at the wave's rows: clamp, store, the wave's running extrema (lane f holds form f's)
 template <int NV>
@@ -98,9 +91,9 @@ __global__ __launch_bounds__(TPB) void k_quad_mfma(QuadModes M, int k, int64_t n
             for (int j = 0; j < T; ++j) v[j] = 0.0;
 #pragma unroll
             for (int lt = 0; lt < LT; ++lt) {
-                qd_d4 acc[T];
+                d4_t acc[T];
 #pragma unroll
-                for (int j = 0; j < T; ++j) acc[j] = qd_d4{0.0, 0.0, 0.0, 0.0};
+                for (int j = 0; j < T; ++j) acc[j] = d4_t{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                 for (int q = 0; q < KT; ++q) {
                     const double a = qp[(lt * KT + q) * 64];
@@ -188,43 +181,23 @@ __global__ __launch_bounds__(TPB) void k_vec_ratio(double *out, const double *nu
     }
 }
 
-// k-steps of 4 of the instance for k modes; it holds T = 4, 4, 4, 4, 2, 1 row tiles per wave: the B fragments are at most 64 doubles per lane
-static int quad_kt(int k) { return k <= 16 ? 4 : k <= 32 ? 8 : k <= 48 ? 12 : k <= 64 ? 16 : k <= 128 ? 32 : 64; }
-
-// persistent grid of the matrix-unit kernel: what is resident at once, at most the cap, at most one wave per tile
+// persistent grid of the matrix-unit kernel: at most one wave per tile; a wave leaves one row of partials, sized once the grid is known
 template <int KT, int T>
 static int quad_launch_mfma(Ctx *c, const QuadModes &M, int k, int64_t n, const double *qf, int nq, int clamp, const QuadOuts &O, int64_t *nrows) {
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_quad_mfma<KT, T>, TPB, 0) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
     const int64_t ntile = (n + 16 * T - 1) / (16 * T);
-    int64_t g = (int64_t)c->num_cu * occ;
-    if (c->quad_grid_max > 0 && g > c->quad_grid_max) g = c->quad_grid_max;
-    if (g > (ntile + 3) / 4) g = (ntile + 3) / 4;
+    const int64_t g = persistent_grid(c, k_quad_mfma<KT, T>, TPB, 0, (ntile + 3) / 4, c->quad_grid_max);
     PGD_TRY(ensure_partials(c, g * 4 * 2 * QD_NQMAX));
-    k_quad_mfma<KT, T><<<(int)g, TPB, 0, c->stream>>>(M, k, n, qf, nq, clamp, O, c->partials);
-    PGD_LAUNCH_CHECK(c);
     *nrows = g * 4;
-    return PGD_OK;
+    return launch_grid(c, k_quad_mfma<KT, T>, g, TPB, 0, M, k, n, qf, nq, clamp, O, c->partials);
 }
 
 static int quad_launch_plain(Ctx *c, const QuadModes &M, int k, int64_t n, const double *qd, int nq, int clamp, const QuadOuts &O, int64_t *nrows) {
     const size_t lds = (size_t)k * QD_PLAIN_TPB * sizeof(double);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)k_quad_plain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, PGD_ERR_HIP, "quad_forms: %zu bytes of LDS refused", lds);
-    }
-    const int64_t nblk = (n + QD_PLAIN_TPB - 1) / QD_PLAIN_TPB;
-    int64_t g = (int64_t)c->num_cu * 8;
-    if (c->quad_grid_max > 0 && g > c->quad_grid_max) g = c->quad_grid_max;
-    if (g > nblk) g = nblk;
+    PGD_TRY(raise_lds(c, (const void *)k_quad_plain, lds, "quad_forms"));
+    const int64_t g = persistent_grid(c, k_quad_plain, QD_PLAIN_TPB, lds, (n + QD_PLAIN_TPB - 1) / QD_PLAIN_TPB, c->quad_grid_max, 8);
     PGD_TRY(ensure_partials(c, g * 2 * QD_NQMAX));
-    k_quad_plain<<<(int)g, QD_PLAIN_TPB, lds, c->stream>>>(M, k, n, qd, nq, clamp, O, c->partials);
-    PGD_LAUNCH_CHECK(c);
     *nrows = g;
-    return PGD_OK;
+    return launch_grid(c, k_quad_plain, g, QD_PLAIN_TPB, lds, M, k, n, qd, nq, clamp, O, c->partials);
 }
 
 }  // namespace pgd
@@ -280,37 +253,25 @@ int pgd_quad_forms(pgd_handle h, const pgd_handle *modes, int k, const double *q
 
     // ---- the matrices in the order the variant reads them, uploaded once
     const bool mfma = c->quad_variant != 0;
-    const int kt = quad_kt(k);
+    const int kt = dense_kt(k);
     const size_t qn = mfma ? (size_t)nq * (kt >> 2) * kt * 64 : (size_t)nq * k * k;
     std::vector<double> qh;
     const double *qsrc = q;
     if (mfma) {
         qh.assign(qn, 0.0);
-        for (int f = 0; f < nq; ++f)
-            for (int l = 0; l < k; ++l) {
-                const double *src = q + ((size_t)f * k + l) * k;
-                for (int t = 0; t < k; ++t) qh[quad_qf_index(kt, f, l, t)] = src[t];
-            }
+        for (int f = 0; f < nq; ++f) pack_a_fragments(qh.data() + (size_t)f * (kt >> 2) * kt * 64, kt, q + (size_t)f * k * k, k, k, k);
         qsrc = qh.data();
     }
-    const size_t q_bytes = (qn * sizeof(double) + 65535) & ~(size_t)65535;   // (whole 64 KiB: the pool takes them back)
-    void *p_q = nullptr;
-    PGD_TRY(dev_alloc(c, &p_q, q_bytes));
     const int clamp = (flags & PGD_QUAD_CLAMP) ? 1 : 0;
-    auto run = [&]() -> int {
+    return with_pool_input(c, pool_bytes(qn), [&](void *p_q) -> int {
         PGD_TRY(ensure_work(c, 6, 2 * QD_NQMAX));
         PGD_HIP(c, hipMemcpyAsync(p_q, qsrc, qn * sizeof(double), hipMemcpyHostToDevice, c->stream));
         const double *qdev = (const double *)p_q;
         int64_t nrows = 0;
         if (mfma) {
-            switch (kt) {
-                case 4: PGD_TRY((quad_launch_mfma<4, 4>(c, M, k, n, qdev, nq, clamp, O, &nrows))); break;
-                case 8: PGD_TRY((quad_launch_mfma<8, 4>(c, M, k, n, qdev, nq, clamp, O, &nrows))); break;
-                case 12: PGD_TRY((quad_launch_mfma<12, 4>(c, M, k, n, qdev, nq, clamp, O, &nrows))); break;
-                case 16: PGD_TRY((quad_launch_mfma<16, 4>(c, M, k, n, qdev, nq, clamp, O, &nrows))); break;
-                case 32: PGD_TRY((quad_launch_mfma<32, 2>(c, M, k, n, qdev, nq, clamp, O, &nrows))); break;
-                default: PGD_TRY((quad_launch_mfma<64, 1>(c, M, k, n, qdev, nq, clamp, O, &nrows))); break;
-            }
+            PGD_TRY(dense_dispatch(kt, [&](auto KT, auto T) {
+                return quad_launch_mfma<decltype(KT)::value, decltype(T)::value>(c, M, k, n, qdev, nq, clamp, O, &nrows);
+            }));
         } else {
             PGD_TRY(quad_launch_plain(c, M, k, n, qdev, nq, clamp, O, &nrows));
         }
@@ -321,11 +282,7 @@ int pgd_quad_forms(pgd_handle h, const pgd_handle *modes, int k, const double *q
         }
         PGD_HIP(c, hipStreamSynchronize(c->stream));   // the one synchronisation of the call (the host buffers are the caller's)
         return PGD_OK;
-    };
-    const int rc = run();
-    if (rc != PGD_OK) (void)hipStreamSynchronize(c->stream);   // nothing reads the matrices once they go back to the pool
-    dev_release(c, p_q, q_bytes);
-    return rc;
+    });
 }
 
 int pgd_vec_ratio(pgd_handle h, pgd_handle outh, pgd_handle numh, pgd_handle denh, double floor) {

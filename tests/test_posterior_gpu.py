@@ -39,11 +39,12 @@ class Knobs:
 # k in {1, 5, 16, 17, 64} x m in {1, 15, 16, 17, 33} rotated over the grids: zero padding of both fragment directions, 16-sample tiles
 # that straddle changes of the slow indices, a dimension of length 1, S a multiple of 16 and not, ndim 1, 2, 3 and 6, scattered
 # samples (one dimension: the table is the coefficient matrix) of S = 1 and 1000; then the two large instances of the misfit kernel
-# (k = 129, 256: no coefficient moments) and a grid of two segments (5863 samples) for the reductions
+# (k = 129, 256: no coefficient moments) and a grid of two segments (5863 samples) for the reductions; last the instance between them
+# (65 .. 128 modes, two sample tiles per wave) at its smallest k, on two segments whose last sample tile is ragged (4160 samples)
 GRIDS = [(3, 5, 7), (1, 33), (16, 16), (2, 2, 2, 3, 2, 2), (1,), (1000,)]
 KS, MS = [1, 5, 16, 17, 64], [1, 15, 16, 17, 33]
 CASES = [(g, k, MS[(i + j) % 5]) for i, g in enumerate(GRIDS) for j, k in enumerate(KS)]
-CASES += [((3, 5, 7), 129, 17), ((16, 16), 256, 33), ((41, 11, 13), 17, 16), ((41, 11, 13), 48, 33)]
+CASES += [((3, 5, 7), 129, 17), ((16, 16), 256, 33), ((41, 11, 13), 17, 16), ((41, 11, 13), 48, 33), ((65, 64), 65, 17)]
 IDS = ["n%s-k%d-m%d" % ("x".join(map(str, g)), k, m) for g, k, m in CASES]
 
 _cache = {}
@@ -147,8 +148,8 @@ def test_misfit_and_posterior_against_the_restatement(ctx, grid, k, m):
         assert np.array_equal(outs["mfma"][key], outs["plain"][key])
 
 
-@pytest.mark.parametrize("grid,k,m", [CASES[0], CASES[18], CASES[29], CASES[31], CASES[32], CASES[33]],
-                         ids=[IDS[0], IDS[18], IDS[29], IDS[31], IDS[32], IDS[33]])
+@pytest.mark.parametrize("grid,k,m", [CASES[0], CASES[18], CASES[29], CASES[31], CASES[32], CASES[33], CASES[34]],
+                         ids=[IDS[0], IDS[18], IDS[29], IDS[31], IDS[32], IDS[33], IDS[34]])
 @pytest.mark.parametrize("variant", [1, 0], ids=["mfma", "plain"])
 def test_bit_identical_for_any_grid_and_from_run_to_run(ctx, grid, k, m, variant):
     cs = case(grid, k, m)

@@ -8,6 +8,7 @@ whole = the operator's products run in the stencil march over the whole grid.  F
   knob 12 && n <= 2^20 -> FOLDED | knob 18 && grid -> SINGLE_SYNC (_RECOMPUTE with knob 53 && whole) | knob 16 -> DEFERRED_X | PLAIN.
 Preconditioner (knob 40): 1 -> MG and 2 -> VMG (grid only) on the scaled branch, 3 -> CMG on the unscaled branch of a blocked
 layout, each only where its hierarchy can be built; everything else is Jacobi and counted as a fallback of the cycle asked for.
+The fetch depth of the stencil march (knob 38) is no input of either table: the rows at depth 6 must report what their depth-3 twins do.
 
 The expected names are literals from those tables, not read back from the library.  (The second way into TWO_LAUNCH - a grid of
 more than 2^20 rows - has no case: a system of that size does not solve in a test's few seconds.)
@@ -22,7 +23,7 @@ import numpy as np
 
 from oracle import fem_numpy as F
 
-KNOB_DEFAULTS = {10: 1, 12: 1, 16: 1, 18: 1, 25: 1, 53: 1, 7: 0, 36: 0, 40: 0}
+KNOB_DEFAULTS = {10: 1, 12: 1, 16: 1, 18: 1, 25: 1, 53: 1, 7: 0, 36: 0, 38: 0, 40: 0}
 LARGE = {25: 0, 12: 0}                         # the recurrences of large systems on a small one
 MARCH = {25: 0, 12: 0, 7: 4, 36: 7}            # ... with the stencil march (7 planes per march) forced onto the small grid
 CUT = 37                                        # inside a chunk and odd: a lagged or deferred x term is outstanding
@@ -34,6 +35,9 @@ CASES = [
     ("single_sync_recompute", "lattice", "hull+column", MARCH, "SINGLE_SYNC_RECOMPUTE", "JACOBI", None),
     ("single_sync_not_one_stencil", "lattice", "face", MARCH, "SINGLE_SYNC", "JACOBI", None),
     ("single_sync_knob_off", "lattice", "hull+column", {**MARCH, 53: 0}, "SINGLE_SYNC", "JACOBI", None),
+    # the product with six plane fetches in flight (knob 38): the update that forms A p again stays at three, the choice is the same
+    ("single_sync_recompute_depth6", "lattice", "hull+column", {**MARCH, 38: 6}, "SINGLE_SYNC_RECOMPUTE", "JACOBI", None),
+    ("single_sync_knob_off_depth6", "lattice", "hull+column", {**MARCH, 38: 6, 53: 0}, "SINGLE_SYNC", "JACOBI", None),
     ("deferred_x_lattice", "lattice", "hull+column", {**LARGE, 18: 0}, "DEFERRED_X", "JACOBI", None),
     ("plain_lattice", "lattice", "hull+column", {**LARGE, 18: 0, 16: 0}, "PLAIN", "JACOBI", None),
     ("textbook_knob", "lattice", "hull+column", {10: 0}, "TEXTBOOK", "JACOBI", None),
@@ -110,6 +114,29 @@ def build_system(ctx, name):
         return {"n": n, "b": rng.uniform(-1, 1, n), "x0": 0.01 * rng.uniform(-1, 1, n), "bc": {"clamped": np.asarray(bc, dtype=np.int32)},
                 "op": lambda bc: A.op(), "free": lambda: None, "keep": A}
     raise KeyError(name)
+
+
+# The fused march of PGD_PCG_FORM_SINGLE_SYNC_RECOMPUTE exists only where the product's launch and the update's have one shape
+# (stencil_fused_ok, pgdrome_amd/csrc/pgd_spmv.hip): these fields of the two plans
+PLAN_SHAPE = ("wgs", "zchunk", "rows_per_thread", "tiles_y")
+
+
+def product_and_update_plans(ctx, op, depth):
+    """(plan of the whole-grid product of `op` under the knobs as set and PGD_TUNE_STENCIL_DEPTH = depth, plan of the update that forms
+    A p again), both through pgd_product_plan.  The update's plan is the product's at fetch depth 3 whatever knob 38 says
+    (plan_stencil_update), read here with the knob at 3; apart from the depth the two calls can differ only in the rows-per-thread rule
+    of marches whose length the launcher chooses, so march lengths must be forced (PGD_TUNE_SPMV_ZCHUNK_STENCIL > 0) around this call.
+    Knob 38 is left at `depth`."""
+    ctx.tune(38, depth)
+    product = ctx.product_plan(op)
+    ctx.tune(38, 3)
+    update = ctx.product_plan(op)
+    ctx.tune(38, depth)
+    return product, update
+
+
+def plans_agree(product, update):
+    return all(product[k] == update[k] for k in PLAN_SHAPE)
 
 
 def set_knobs(ctx, knobs):

@@ -130,6 +130,7 @@ def test_halo_exchange_with_itself_overlapped_or_not_is_the_same_solve():
     torch.cuda.set_device(0)
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
     old = fem._backend
+    ctx = None
     try:
         tstream = torch.cuda.Stream(device=0)
         torch.cuda.set_stream(tstream)
@@ -160,7 +161,10 @@ def test_halo_exchange_with_itself_overlapped_or_not_is_the_same_solve():
 
         uid = ctx.comm_unique_id()
         out = {}
-        for variant in ("callbacks", "rccl", "rccl+overlap"):
+        # the "rccl" binding twice more, each with one knob of the sharded loop off: PGD_TUNE_PCG_FOLD_FINISH (29) = 0 - the stop test,
+        # alpha and beta in a launch of their own (k_pcg1_finish) - and PGD_TUNE_SHARD_ONE_MARCH (46) = 0 - the exchange in stream order,
+        # but the interior march + the boundary planes in row order, as under overlap
+        for variant in ("callbacks", "rccl", "rccl+overlap", "rccl, finish unfolded", "rccl, boundary planes apart"):
             ctx.comm_unbind()
             if variant == "callbacks":
                 ctx.comm_bind_callbacks(cb_halo, cb_allreduce, 0, 1)
@@ -169,6 +173,8 @@ def test_halo_exchange_with_itself_overlapped_or_not_is_the_same_solve():
                 assert ctx.comm_overlap(1 if variant == "rccl+overlap" else 0) == (variant == "rccl+overlap")
             ctx.tune(44, 1)                              # (a binding starts from the defaults)
             ctx.tune(45, 0)                              # the second stream whatever the slab's size
+            ctx.tune(29, 0 if variant == "rccl, finish unfolded" else 1)
+            ctx.tune(46, 0 if variant == "rccl, boundary planes apart" else 1)
             xv = ctx.vec_alloc(n)
             k0 = ctx.kernel_counts()
             it, rel = ctx.pcg_solve_sharded(op, bv, xv, own0, own1, plane, plane, 1e-10, 0.0, 10000)
@@ -176,7 +182,7 @@ def test_halo_exchange_with_itself_overlapped_or_not_is_the_same_solve():
             # overlapped: the interior rows march while the planes travel, the two boundary planes follow in row order; in stream
             # order ALL owned planes march in one launch, the ghost planes staged as data (k_stencil_ghost)
             assert k1["stencil_march"] > k0["stencil_march"]
-            assert (k1["dia_rows"] > k0["dia_rows"]) == (variant == "rccl+overlap"), (variant, k0, k1)
+            assert (k1["dia_rows"] > k0["dia_rows"]) == (variant in ("rccl+overlap", "rccl, boundary planes apart")), (variant, k0, k1)
             assert ctx.comm_overlap(-2) == (variant == "rccl+overlap")
             x = ctx.vec_download(xv)
             out[variant] = (it, rel, x)
@@ -196,8 +202,17 @@ def test_halo_exchange_with_itself_overlapped_or_not_is_the_same_solve():
         assert a[0] == c[0] and a[1] == c[1] and np.array_equal(a[2], c[2]), (a[0], c[0], a[1], c[1])      # the same launches
         # (three launches instead of one: y is bit-identical, the fused dots are grouped differently - iterates equal to rounding)
         assert abs(o[0] - a[0]) <= 1 and np.linalg.norm(o[2] - a[2]) <= 1e-9 * np.linalg.norm(a[2])
+        # knob 29 = 0: bit-identical iterates (include/pgd_amd.h) - the "rccl" run's count, residual and x
+        u = out["rccl, finish unfolded"]
+        assert u[0] == c[0] and u[1] == c[1] and np.array_equal(u[2], c[2]), (u[0], c[0], u[1], c[1])
+        # knob 46 = 0: the same y, the fused dots grouped as under overlap - held to the comparison of the overlapped run
+        t = out["rccl, boundary planes apart"]
+        assert abs(t[0] - a[0]) <= 1 and np.linalg.norm(t[2] - a[2]) <= 1e-9 * np.linalg.norm(a[2])
         ctx.comm_unbind()
     finally:
+        if ctx is not None:
+            ctx.tune(29, 1)
+            ctx.tune(46, 1)
         torch.cuda.set_stream(torch.cuda.default_stream(0))
         fem.set_backend(old)
         fem.clear_caches()

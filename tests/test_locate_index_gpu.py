@@ -157,6 +157,23 @@ def test_the_knob_is_off_by_default(ctx, uploaded):
     assert ctx.points_last_path() == _lib.LOCATE_PATH_GENERAL
 
 
+def test_the_knob_itself_selects_the_index(ctx, uploaded):
+    """PGD_TUNE_LOCATE_INDEX set through tune() - what a call with ``index=None`` runs under: 1 takes the bin index, with the cells and lam
+    of the general kernel bit for bit, and 0 afterwards takes the general kernel again."""
+    X, C, _, mh, pts, (cells0, lam0) = uploaded["rectangle_jittered"]
+    try:
+        with Knobs(ctx, lattice=0):
+            ctx.tune(_lib.TUNE_LOCATE_INDEX, 1)
+            cells, lam, path = locate(ctx, mh, pts, index=None)
+            ctx.tune(_lib.TUNE_LOCATE_INDEX, 0)
+            cells2, lam2, path2 = locate(ctx, mh, pts, index=None)
+    finally:
+        ctx.tune(_lib.TUNE_LOCATE_INDEX, 0)
+    assert (path, path2) == (_lib.LOCATE_PATH_INDEX, _lib.LOCATE_PATH_GENERAL)
+    for c, l in ((cells, lam), (cells2, lam2)):
+        assert np.array_equal(c, cells0) and np.array_equal(l, lam0)
+
+
 @pytest.mark.parametrize("target", TARGETS)
 @pytest.mark.parametrize("name", MESHES)
 def test_index_equals_the_general_kernel(ctx, uploaded, name, target):

@@ -14,12 +14,13 @@ import numpy as np
 import pytest
 
 from oracle import fem_numpy as F
+from tests import pcg_form_cases as PC
 
 pytestmark = pytest.mark.gpu
 
 GRIDS = {"130x37x41": (130, 37, 41), "65x4x9": (65, 4, 9)}
-KNOBS = (25, 12, 7, 36, 48, 22, 23, 53, 3, 55, 56)
-DEFAULTS = {25: 1, 12: 1, 7: 0, 36: 0, 48: 0, 22: 1, 23: 1, 53: 1, 3: 1, 55: 0, 56: 1}
+KNOBS = (25, 12, 7, 36, 48, 22, 23, 53, 3, 55, 56, 38, 57)
+DEFAULTS = {25: 1, 12: 1, 7: 0, 36: 0, 48: 0, 22: 1, 23: 1, 53: 1, 3: 1, 55: 0, 56: 1, 38: 0, 57: 1}
 # below a chunk of 16 iterations, exactly one, just past one (graph replay + a pipelined chunk behind it), odd and even cut-offs
 # (with and without a lagged x term outstanding), more than two chunks, convergence
 MAXITS = (1, 2, 15, 16, 17, 23, 24, 37, 10000)
@@ -53,7 +54,9 @@ def grid(request, ctx):
     ctx.mesh_free(h)
 
 
-def forced(ctx, L, rows=0, lag=1, hints=1):
+def forced(ctx, L, rows=0, lag=1, hints=1, depth=0, fused=1):
+    ctx.tune(38, depth)
+    ctx.tune(57, fused)
     ctx.tune(25, 0)
     ctx.tune(12, 0)
     ctx.tune(7, 4)
@@ -165,6 +168,50 @@ def test_exact_phase_without_the_s_stream_keeps_every_bit(ctx, grid, bc, L, on_b
         assert new[k55][10000][3] > 0 and new[k55][10000][1] <= 1e-10
         print("true residual %.4g" % new[k55]["residual"])
         assert new[k55]["residual"] <= 1.05e-10
+
+
+DEPTH6_CASES = [(bc, L, 0) for bc in ("hull", "hull+column") for L in (3, 7, 1000)]
+DEPTH6_CASES += [("hull+column", 7, 2)]           # two rows per thread asked for: the product of depth 6 has four, the update two
+
+
+@pytest.mark.parametrize("bc,L,rows", DEPTH6_CASES)
+def test_both_knobs_keep_every_bit_under_a_product_at_depth_6(ctx, grid, bc, L, rows):
+    """PGD_TUNE_STENCIL_DEPTH = 6: the product marches with six plane fetches in flight, the update march - which with knob 55 sums the
+    product's pairs itself - is planned at three, so with marches of 3 planes (6 in the product) the two launches leave different
+    numbers of partial sums, and with two rows per thread asked for they run different instances.  The fused march is switched off
+    (knob 57 = 0; it would take precedence over knob 55 wherever the two plans agree), so the three-launch loop and the folded scalar
+    step are what runs.  Knob 55 on / off and knob 56 on / off, each BITWISE against both off, as their comments promise; every
+    cut-off of MAXITS, convergence, a second solve from the converged x; launches counted."""
+    keys = MAXITS + ("again",)
+    try:
+        forced(ctx, L, rows, depth=6, fused=0)
+        op = ctx.op_combine(grid["h"], [grid["ak"], grid["am"]], [1.0, 3.0], grid["bc"][bc])
+        assert 1 <= ctx.op_classify(op) <= 255
+        product, update = PC.product_and_update_plans(ctx, op, 6)
+        ctx.atom_free(op)
+        print(grid["name"], bc, L, rows, "product", product, "update", update)
+        assert product["family"] == update["family"] == "stencil_march" and product["depth"] == 6 and update["depth"] == 3
+        assert product["rows_per_thread"] == 4 and update["rows_per_thread"] == (2 if rows == 2 else 4)
+        f0 = ctx.pcg_fused_marches()
+        ref = solves(ctx, grid, grid["bc"][bc], 0, 0, keys)
+        new55 = solves(ctx, grid, grid["bc"][bc], 1, 0, keys)
+        new56 = solves(ctx, grid, grid["bc"][bc], 0, 1, (23, 10000))
+        both = solves(ctx, grid, grid["bc"][bc], 1, 1, (23, 10000))
+        assert ctx.pcg_fused_marches() == f0
+        assert ctx.pcg_last_form()[0] == "SINGLE_SYNC_RECOMPUTE"
+    finally:
+        restore(ctx)
+    same_bits(new55, ref, keys, "depth 6, 55 on / off")
+    same_bits(new56, ref, (23, 10000), "depth 6, 56 on / off")
+    same_bits(both, ref, (23, 10000), "depth 6, 55 + 56 on / off")
+    for k in COUNTED:
+        for run in (ref, new55):
+            assert run[k][3] == k and run[k][4] == k + 1, (k, run[k][0], run[k][3], run[k][4])
+    for k in (1, 2, 15):
+        assert new55[k][0] == k
+    assert new55[10000][3] > 0 and new55[10000][1] <= 1e-10 and new55["residual"] <= 1.05e-10
+    assert new56["residual"] <= 1.05e-10 and both["residual"] <= 1.05e-10
+    assert new55["again"][0] == ref["again"][0] <= 1
 
 
 def test_operators_that_are_not_one_stencil_are_left_alone(ctx, grid):

@@ -60,3 +60,45 @@ def test_the_form_is_the_tables_and_it_solves(systems, name, system, bc, knobs, 
     assert full[0] < 10000 and full[1] <= 1e-10 and full[3] <= 1.05e-10
     assert cut2[0] == cut[0] and cut2[1] == cut[1] and np.array_equal(cut2[2], cut[2])
     assert full2[0] == full[0] and full2[1] == full[1] and np.array_equal(full2[2], full[2])
+
+
+# knobs that change how the host follows the loop, never a launch's arguments: (case of PC.CASES, {knob: (value, default)})
+HOST_SIDE = [
+    ("two_launch_lattice", {31: (0, 1)}),        # PGD_TUNE_PCG_PIPELINE = 0: look at the flags, then queue the next chunk
+    ("single_sync_recompute", {31: (0, 1)}),
+    ("mg", {31: (0, 1)}),
+    ("mg", {41: (4, 2)}),                        # PGD_TUNE_MG_CHUNK: 4 and 16 iterations between two looks instead of 2
+    ("mg", {41: (16, 2)}),
+]
+
+
+@pytest.mark.parametrize("name,setting", HOST_SIDE, ids=["%s-%s" % (c[0], "".join("%d=%d" % (k, v[0]) for k, v in c[1].items())) for c in HOST_SIDE])
+def test_how_the_host_follows_the_loop_changes_no_bit(systems, name, setting):
+    """PGD_TUNE_PCG_PIPELINE ("same iterates, same iteration count") and PGD_TUNE_MG_CHUNK (how many iterations are queued between two
+    looks at the flags; even, so that a replayed chunk keeps its slot parity) decide when the host reads the flags and how many no-op
+    launches follow the iteration that converged.  No launch gets other arguments: form, iteration count, reported residual and x are
+    those of the default, bit for bit, cut at 37 iterations and at convergence."""
+    ctx, built = systems
+    _, system, bc, knobs, form, precond, _ = [c for c in PC.CASES if c[0] == name][0]
+    if system not in built:
+        built[system] = PC.build_system(ctx, system)
+    s = built[system]
+    (knob, (value, default)), = setting.items()
+    runs = {}
+    try:
+        for v in (default, value):
+            PC.set_knobs(ctx, knobs)
+            ctx.tune(knob, v)
+            cut = PC.solve(ctx, s, bc, PC.CUT, 0.0)
+            full = PC.solve(ctx, s, bc, 10000, 1e-10, residual=True)
+            runs[v] = (cut, full, ctx.pcg_last_form())
+    finally:
+        ctx.tune(knob, default)
+        PC.set_knobs(ctx, {})
+    for v in (default, value):
+        cut, full, chosen = runs[v]
+        print("%s, knob %d = %d: %s, cut %d, converged in %d, reported %.3g, true residual %.3g" % (name, knob, v, chosen, cut[0], full[0], full[1], full[3]))
+        assert chosen == (form, precond)
+        assert cut[0] == PC.CUT and full[0] < 10000 and full[1] <= 1e-10 and full[3] <= 1.05e-10
+    for a, b in zip(runs[value][:2], runs[default][:2]):
+        assert a[0] == b[0] and a[1] == b[1] and np.array_equal(a[2], b[2])

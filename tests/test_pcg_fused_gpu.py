@@ -14,12 +14,13 @@ import numpy as np
 import pytest
 
 from oracle import fem_numpy as F
+from tests import pcg_form_cases as PC
 
 pytestmark = pytest.mark.gpu
 
 GRIDS = {"130x37x41": (130, 37, 41), "65x4x9": (65, 4, 9)}
-KNOBS = (25, 12, 7, 36, 48, 22, 23, 53, 3, 55, 56, 57)
-DEFAULTS = {25: 1, 12: 1, 7: 0, 36: 0, 48: 0, 22: 1, 23: 1, 53: 1, 3: 1, 55: 0, 56: 1, 57: 1}
+KNOBS = (25, 12, 7, 36, 48, 22, 23, 53, 3, 55, 56, 57, 38)
+DEFAULTS = {25: 1, 12: 1, 7: 0, 36: 0, 48: 0, 22: 1, 23: 1, 53: 1, 3: 1, 55: 0, 56: 1, 57: 1, 38: 0}
 # below a chunk of 16 iterations, exactly one, just past one (graph replay + a pipelined chunk behind it), odd and even cut-offs
 # (with and without a lagged x term outstanding; the live r and p in either buffer), more than two chunks, convergence
 MAXITS = (1, 2, 15, 16, 17, 23, 24, 37, 10000)
@@ -53,7 +54,8 @@ def grid(request, ctx):
     ctx.mesh_free(h)
 
 
-def forced(ctx, L, rows=0, lag=1, hints=1):
+def forced(ctx, L, rows=0, lag=1, hints=1, depth=0):
+    ctx.tune(38, depth)
     ctx.tune(25, 0)
     ctx.tune(12, 0)
     ctx.tune(7, 4)
@@ -145,6 +147,47 @@ def test_one_march_per_iteration_keeps_every_bit(ctx, grid, bc, L, rows, lag, hi
     for k in COUNTED:
         assert new[k][3] == k and new[k][4] == k + 1 and new[k][5] == k, (k, new[k][0], new[k][3], new[k][4], new[k][5])
         assert ref[k][3] == k and ref[k][4] == k + 1 and ref[k][5] == 0, (k, ref[k][0], ref[k][3], ref[k][4], ref[k][5])
+    for k in (1, 2, 15):
+        assert new[k][0] == k
+    assert new[10000][3] > 0 and new[10000][1] <= 1e-10 and new["residual"] <= 1.05e-10
+    assert new["again"][0] == ref["again"][0] <= 1
+
+
+DEPTH6_CASES = [(bc, L, 0) for bc in ("hull", "hull+column") for L in (3, 7, 1000)]
+DEPTH6_CASES += [("hull+column", 7, 2)]           # two rows per thread asked for: the product of depth 6 has four, the update two
+
+
+@pytest.mark.parametrize("bc,L,rows", DEPTH6_CASES)
+def test_one_march_per_iteration_under_a_product_at_depth_6(ctx, grid, bc, L, rows):
+    """PGD_TUNE_STENCIL_DEPTH = 6: the stand-alone product of p0 marches with six plane fetches in flight, the fused march is planned
+    like the update, at three.  Its workgroups leave the product's pairs where a product launch would, so it may run only where the two
+    plans have one shape (stencil_fused_ok): read from pgd_product_plan here, never assumed.  Where they agree knob 57 on must run one
+    fused march per iteration; where they differ - marches of 3 planes are 6 in the product, two rows per thread exist at depth 3 only -
+    none at all, in the same recurrence.  Either way knob 57 on against off is BITWISE, as its comment promises, at every cut-off of
+    MAXITS, at convergence and from the converged x."""
+    keys = MAXITS + ("again",)
+    try:
+        forced(ctx, L, rows, depth=6)
+        op = ctx.op_combine(grid["h"], [grid["ak"], grid["am"]], [1.0, 3.0], grid["bc"][bc])
+        assert 1 <= ctx.op_classify(op) <= 255
+        product, update = PC.product_and_update_plans(ctx, op, 6)
+        ctx.atom_free(op)
+        agree = PC.plans_agree(product, update)
+        print(grid["name"], bc, L, rows, "plans agree" if agree else "plans differ", "product", product, "update", update)
+        assert product["family"] == update["family"] == "stencil_march" and product["depth"] == 6 and update["depth"] == 3
+        assert product["rows_per_thread"] == 4 and update["rows_per_thread"] == (2 if rows == 2 else 4)
+        ref = solves(ctx, grid, grid["bc"][bc], 0, keys)
+        new = solves(ctx, grid, grid["bc"][bc], 1, keys)
+        assert ctx.pcg_last_form()[0] == "SINGLE_SYNC_RECOMPUTE"
+        rep = solves(ctx, grid, grid["bc"][bc], 1, (23, 10000))
+    finally:
+        restore(ctx)
+    same_bits(new, ref, keys, "depth 6, 57 on / off")
+    same_bits(rep, new, (23, 10000), "depth 6, 57 on, twice")
+    for k in COUNTED:
+        assert new[k][3] == k and new[k][4] == k + 1 and new[k][5] == (k if agree else 0), (agree, k, new[k][3], new[k][4], new[k][5])
+        assert ref[k][3] == k and ref[k][4] == k + 1 and ref[k][5] == 0, (k, ref[k][3], ref[k][4], ref[k][5])
+    assert (new[10000][5] > 0) == agree
     for k in (1, 2, 15):
         assert new[k][0] == k
     assert new[10000][3] > 0 and new[10000][1] <= 1e-10 and new["residual"] <= 1.05e-10

@@ -18,12 +18,13 @@ import numpy as np
 import pytest
 
 from oracle import fem_numpy as F
+from tests import pcg_form_cases as PC
 
 pytestmark = pytest.mark.gpu
 
 GRIDS = {"130x37x41": (130, 37, 41), "65x4x9": (65, 4, 9)}     # several x-tiles with a partial last one, partial y-tiles, odd plane counts
-KNOBS = (25, 12, 7, 36, 48, 22, 23, 53, 3)
-DEFAULTS = {25: 1, 12: 1, 7: 0, 36: 0, 48: 0, 22: 1, 23: 1, 53: 1, 3: 1}
+KNOBS = (25, 12, 7, 36, 48, 22, 23, 53, 3, 38)
+DEFAULTS = {25: 1, 12: 1, 7: 0, 36: 0, 48: 0, 22: 1, 23: 1, 53: 1, 3: 1, 38: 0}
 
 
 def boundary_dofs(coords):
@@ -52,7 +53,8 @@ def grid(request, ctx):
     ctx.mesh_free(h)
 
 
-def forced(ctx, L, rows=0, lag=1, hints=1):
+def forced(ctx, L, rows=0, lag=1, hints=1, depth=0):
+    ctx.tune(38, depth)
     ctx.tune(25, 0)
     ctx.tune(12, 0)
     ctx.tune(7, 4)
@@ -153,6 +155,41 @@ def test_update_that_forms_q_walks_the_iterates_of_the_stored_q(ctx, grid, bc, L
         rep = solves(ctx, grid, grid["bc"][bc], 1, (23, 10000))
     finally:
         restore(ctx)
+    compare(new, ref, True)
+    for key in (23, 10000):
+        assert new[key][0] == rep[key][0] and new[key][1] == rep[key][1] and np.array_equal(new[key][2], rep[key][2]), key
+
+
+DEPTH6_CASES = [(bc, L, 0) for bc in ("hull", "hull+column") for L in (3, 7, 1000)]
+DEPTH6_CASES += [("hull+column", 7, 2)]           # two rows per thread asked for: the product of depth 6 has four, the update two
+
+
+@pytest.mark.parametrize("bc,L,rows", DEPTH6_CASES)
+def test_update_at_depth_3_under_a_product_at_depth_6(ctx, grid, bc, L, rows):
+    """PGD_TUNE_STENCIL_DEPTH = 6: the product marches with six plane fetches in flight, the update that forms q again is planned at
+    three.  Knob 53 on against off at that depth, held to what the knob's comment promises - the same q and per-row operations, another
+    grouping of the residual's partial sums - i.e. to the bounds of compare().  Marches of 3 planes become marches of 6 in the product
+    only (other workgroup counts in the two launches, no fused march); 7 planes and one march over the grid keep one shape.  Whether
+    the fused march runs is read from the two plans, never assumed."""
+    keys = (1, 2, 23, 24, 10000, "again")
+    try:
+        forced(ctx, L, rows, depth=6)
+        op = ctx.op_combine(grid["h"], [grid["ak"], grid["am"]], [1.0, 3.0], grid["bc"][bc])
+        assert 1 <= ctx.op_classify(op) <= 255
+        product, update = PC.product_and_update_plans(ctx, op, 6)
+        ctx.atom_free(op)
+        print(grid["name"], bc, L, rows, "product", product, "update", update)
+        assert product["family"] == update["family"] == "stencil_march"
+        assert product["depth"] == 6 and product["rows_per_thread"] == 4 and product["zchunk"] >= 6
+        assert update["depth"] == 3 and update["rows_per_thread"] == (2 if rows == 2 else 4) and update["zchunk"] == max(3, L)
+        ref = solves(ctx, grid, grid["bc"][bc], 0, keys)
+        f0 = ctx.pcg_fused_marches()
+        new = solves(ctx, grid, grid["bc"][bc], 1, keys)
+        fused = ctx.pcg_fused_marches() - f0
+        rep = solves(ctx, grid, grid["bc"][bc], 1, (23, 10000))
+    finally:
+        restore(ctx)
+    assert (fused > 0) == PC.plans_agree(product, update), (fused, product, update)
     compare(new, ref, True)
     for key in (23, 10000):
         assert new[key][0] == rep[key][0] and new[key][1] == rep[key][1] and np.array_equal(new[key][2], rep[key][2]), key

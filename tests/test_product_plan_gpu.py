@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import fem_numpy as F
+from tests import pcg_form_cases as PC
 
 pytestmark = pytest.mark.gpu
 
@@ -175,4 +176,51 @@ def test_fused_solve_where_the_plans_say_so(ctx, lattice, bc):
         restore(ctx)
         ctx.atom_free(op)
         for v in (bv, sv):
+            ctx.vec_free(v)
+
+
+@pytest.mark.parametrize("rows", [0, 2])
+@pytest.mark.parametrize("L", [3, 5, 6, 7, 13])
+@pytest.mark.parametrize("bc", ["hull", "hull + column"])
+def test_fused_solve_at_depth_6_only_where_the_two_plans_agree(ctx, lattice, bc, L, rows):
+    """(d) with the product at fetch depth 6 (PGD_TUNE_STENCIL_DEPTH): the update that forms A p again and the fused march are planned at
+    depth 3 (plan_stencil_update), so the product's launch can have another shape - marches of at least 6 planes, four rows per thread
+    whatever PGD_TUNE_STENCIL_ROWS asks.  Both plans are read through pgd_product_plan.  Where they differ in wgs, zchunk,
+    rows_per_thread or tiles_y the fused march must not run (its workgroups would leave the product's pairs in another count or
+    order than the scalar step sums), the recurrence stays SINGLE_SYNC_RECOMPUTE and the solve meets the residual bar of the PCG
+    tests; where they agree the fused march runs."""
+    g = lattice
+    knobs = {25: (0, 1), 12: (0, 1), FORCE: (4, 0), ZSTENCIL: (L, 0), ROWS: (rows, 0), DEPTH: (6, 0)}
+    b = np.random.default_rng(31).uniform(-1, 1, g["n"])
+    b[g["bcs"][bc]] = 0.0
+    bv, sv, yv = ctx.vec_from(b), ctx.vec_alloc(g["n"]), ctx.vec_alloc(g["n"])
+    op = ctx.op_combine(g["h"], [g["ak"], g["am"]], [1.0, 3.0], g["bcs"][bc])
+    try:
+        for k, (v, _) in knobs.items():
+            ctx.tune(k, v)
+        assert 1 <= ctx.op_classify(op) <= 255
+        product, update = PC.product_and_update_plans(ctx, op, 6)
+        agree = PC.plans_agree(product, update)
+        print(g["shape"], bc, L, rows, "plans agree" if agree else "plans differ", "product", product, "update", update)
+        assert product["family"] == update["family"] == "stencil_march"
+        assert product["depth"] == 6 and product["rows_per_thread"] == 4 and product["zchunk"] >= 6
+        assert update["depth"] == 3 and update["rows_per_thread"] == (2 if rows == 2 else 4) and update["zchunk"] == max(3, L)
+        ctx.vec_fill(sv, 0.0)
+        f0, u0 = ctx.pcg_fused_marches(), ctx.pcg_recompute_updates()
+        its, rel = ctx.pcg_solve(op, bv, sv, 1e-10, 0.0, 10000)
+        assert ctx.pcg_last_form()[0] == "SINGLE_SYNC_RECOMPUTE"
+        fused, updates = ctx.pcg_fused_marches() - f0, ctx.pcg_recompute_updates() - u0
+        assert updates > 0 and (fused > 0 if agree else fused == 0), (its, rel, fused, updates, product, update)
+        ctx.tune(SYM, 0)
+        ctx.spmv(op, sv, yv)
+        ctx.tune(SYM, 1)
+        res = np.linalg.norm(b - ctx.vec_download(yv)) / np.linalg.norm(b)
+        print("iterations %d, reported %.3g, true residual %.3g, fused marches %d of %d updates" % (its, rel, res, fused, updates))
+        assert its < 10000 and rel <= 1e-10 and res <= 1.05e-10
+    finally:
+        for k, (_, d) in knobs.items():
+            ctx.tune(k, d)
+        restore(ctx)
+        ctx.atom_free(op)
+        for v in (bv, sv, yv):
             ctx.vec_free(v)
